@@ -2,16 +2,17 @@
 """bench.py — signatures clustered per second on MI355X (BASELINE.json's metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg3|cfg2|cfg4|cfg5|rebuild|extract] [--scale S] [--mode replica|shard]
+                    [--full [--full-line]] [--dump-outputs DIR]
 
 A "step" is one pass of the whole hot path (chain -> refine -> order [-> reads order -> genotype]) over one synthetic
 signature batch that is already resident in HBM when the timed region starts, AND the delivery of its result - the calls'
 structure-of-arrays and the support lists - into the caller's host memory: the region of SURVEY.md 8(d) ("flat arrays ->
-rows SoA in host RAM") with the inputs resident as the bench contract asks.  `value` = signatures / that step.  The same
-line carries the two neighbouring regions: `kernel_only` (the launch sequence alone, results left in HBM: what r01-r03
+rows SoA in host RAM") with the inputs resident as the bench contract asks.  `value` = signatures / that step.  With --full
+the same line carries the two neighbouring regions: `kernel_only` (the launch sequence alone, results left in HBM: what r01-r03
 reported as value) and `boundary.one_shot_call_ms` (page-locked host columns -> host SoA, PCIe both ways).
 At N = 1 the workload is BASELINE config 3 (synthetic HG002-shaped ONT 30x, ~2.8 M INS+DEL signatures, ONT preset): the
-metric is quoted "on 30x WGS", and this is the 30x whole-genome configuration that names one MI355X; the other configs
-(cfg2, cfg4, cfg5) are measured in the same run in compact form (`other_workloads`).  The reads table of the genotyping
+metric is quoted "on 30x WGS", and this is the 30x whole-genome configuration that names one MI355X; with --full the other
+configs (cfg2, cfg4, cfg5) are measured in the same run in compact form (`other_workloads`).  The reads table of the genotyping
 workloads (cfg4 / cfg5) is fed in the order cuteSV's extraction leaves it (synth.extraction_order), so the device-side
 reads ordering is inside every step.
 
@@ -19,14 +20,16 @@ N > 1: one process per GPU.  Launched by torch.distributed.run the ranks come fr
 `python bench.py --gpus N` spawns the N ranks itself (127.0.0.1 rendezvous).  The path shards with no data-path
 collective; the only communication is the timing barrier / max-reduce (gloo, CPU tensors).
   --mode replica (default for cfg3)  every rank clusters its own genome of the workload's shape (seed + rank): "weak"
-                            scaling; the line ALSO carries a `sharded` object: BASELINE config 4 (one HiFi genome with
+                            scaling; with --full the line ALSO carries a `sharded` object: BASELINE config 4 (one HiFi genome with
                             --genotype) split over the N ranks, measured right after the replica loop.
   --mode shard              ONE genome (BASELINE configs 4 and 5: "chromosomes sharded over 8 MI355X"): the ranks split
                             its chromosomes with shard.plan; a step is the rank's whole csv_cluster_batch call
                             (H2D + kernels + D2H); rank 0 then merges the ranks' rows and checks them against the
                             unsharded run: "strong" scaling.
 
-Prints ONE JSON line on rank 0.  Extra objects:
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the K steps and prints the headline keys alone
+(metric, value, unit, ms_per_step, dtype, config, ...).  --dump-outputs DIR then also writes what the last timed step
+delivered (rank 0's) as DIR/<name>.npy.  --full runs every other measurement and check as well; its extra objects:
   roofline      dominant kernel (largest average HIP-event duration over the K steps of a second, event-instrumented
                 pass on the library's own stream): algorithmic bytes (32 B per signature the launch
                 processes + 64 B per call; genotype 21 B per read + 32 B per call) / duration vs the 8 TB/s HBM peak.
@@ -526,10 +529,12 @@ def stage_leg(name, store, params):
 SLIM = dict(no_support=True, coord32=True, fields=("call_aux", "cipos", "cilen", "seq_pick", "dr", "gl_idx"))
 
 
-def resident_loops(ctx, phb, steps, warmup, dist=None):
+def resident_loops(ctx, phb, steps, warmup, dist=None, full=True):
     """The resident timed loops of an uploaded batch.  Returns (seconds of `steps` steps WITH the full result - calls + support
-    lists - delivered to page-locked host arrays each step, seconds of the launch sequences alone, the last delivered result,
-    seconds of `steps` steps with the SLIM result delivered: what a run without --report_readid consumes, ABI v7)."""
+    lists - delivered to page-locked host arrays each step, seconds of the launch sequences alone, the result arrays the last
+    pipelined step delivered into, seconds of `steps` steps with the SLIM result delivered: what a run without --report_readid
+    consumes, ABI v7, seconds of the pipelined loops with the full and the slim result).  full=False: the pipelined loop with the
+    full result alone (the headline); the other figures are None."""
     ctx.upload(phb, per_sig=False)
     # every step does the whole stage, the ordering / packing of the reads table included (the library would keep the
     # ordered table of an upload across runs: CSV_OPT_REUSE_READS_ORDER, measured separately)
@@ -540,35 +545,36 @@ def resident_loops(ctx, phb, steps, warmup, dist=None):
     # numbers in 60 instead of 76 bytes per call)
     c32 = phb.a.dtype == np.int32
     res = ctx.result_buffers(cap_calls=probe.n_calls + 64, cap_support=probe.n_support + 64, coord32=c32)
-    for _ in range(warmup):
-        ctx.run(); ctx.download(into=res)
-    if dist is not None:
-        dist.barrier()
-    t0 = time.perf_counter()
-    for _ in range(steps):
-        ctx.run()
-        ctx.download(into=res)                               # k_publish into the page-locked arrays + ONE stream synchronisation
-    if dist is not None:
-        dist.barrier()
-    dt = time.perf_counter() - t0
-    for _ in range(warmup):
-        ctx.run()
-    ctx.sync()
-    t0 = time.perf_counter()
-    for _ in range(steps):
-        ctx.run()
-    ctx.sync()
-    dt_k = time.perf_counter() - t0
-    dt_slim = None
-    if phb.a.dtype == np.int32:
-        slim = ctx.result_buffers(cap_calls=probe.n_calls + 64, cap_support=64, **SLIM)
+    dt = dt_k = dt_slim = None
+    if full:
         for _ in range(warmup):
-            ctx.run(); ctx.download(into=slim)
+            ctx.run(); ctx.download(into=res)
+        if dist is not None:
+            dist.barrier()
         t0 = time.perf_counter()
         for _ in range(steps):
             ctx.run()
-            ctx.download(into=slim)
-        dt_slim = time.perf_counter() - t0
+            ctx.download(into=res)                               # k_publish into the page-locked arrays + ONE stream synchronisation
+        if dist is not None:
+            dist.barrier()
+        dt = time.perf_counter() - t0
+        for _ in range(warmup):
+            ctx.run()
+        ctx.sync()
+        t0 = time.perf_counter()
+        for _ in range(steps):
+            ctx.run()
+        ctx.sync()
+        dt_k = time.perf_counter() - t0
+        if phb.a.dtype == np.int32:
+            slim = ctx.result_buffers(cap_calls=probe.n_calls + 64, cap_support=64, **SLIM)
+            for _ in range(warmup):
+                ctx.run(); ctx.download(into=slim)
+            t0 = time.perf_counter()
+            for _ in range(steps):
+                ctx.run()
+                ctx.download(into=slim)
+            dt_slim = time.perf_counter() - t0
     # pipelined delivery (csv_batch_publish_async): run k's result crosses PCIe while run k + 1 computes, two result arenas on
     # the device, two sets of page-locked arrays on the host; every step's full result is in host memory when the clock stops
     def pipelined(bufs):
@@ -586,11 +592,12 @@ def resident_loops(ctx, phb, steps, warmup, dist=None):
         return time.perf_counter() - t0
     res_b = ctx.result_buffers(cap_calls=probe.n_calls + 64, cap_support=probe.n_support + 64, coord32=c32)
     dt_pipe = pipelined([res, res_b])
+    last = (res, res_b)[(steps - 1) & 1]                      # (step k delivers into bufs[k & 1])
     dt_pipe_slim = None
     if dt_slim is not None:
         slim_b = ctx.result_buffers(cap_calls=probe.n_calls + 64, cap_support=64, **SLIM)
         dt_pipe_slim = pipelined([slim, slim_b])
-    return dt, dt_k, res, dt_slim, dt_pipe, dt_pipe_slim
+    return dt, dt_k, last, dt_slim, dt_pipe, dt_pipe_slim
 
 
 def instrumented(ctx, phb, steps):
@@ -707,10 +714,11 @@ def compact_workload(ctx, name, a, cpu):
     return out
 
 
-def measure_sharded(ctx, dist, rank, world, workload, scale, steps, warmup):
+def measure_sharded(ctx, dist, rank, world, workload, scale, steps, warmup, keep_last=False):
     """ONE genome over `world` ranks (BASELINE configs 4 / 5): every rank computes the same plan without communicating, a step
     is the rank's whole boundary call (H2D + kernels + D2H); rank 0 merges the ranks' rows exactly as main_ctrl concatenates
-    task results and compares them with the unsharded run.  Returns (dict on rank 0 / None, seconds, signatures of the genome)."""
+    task results and compares them with the unsharded run.  Returns (dict on rank 0 / None, seconds, signatures of the genome,
+    ..., keep_last: a private copy of the rank's last timed result, else None)."""
     from cutesv_amd.columns import SigStore
     shared = "/dev/shm/cutesv_amd_bench_%s_%s" % (os.environ.get("MASTER_PORT", "0"), workload)
     if world > 1:
@@ -739,8 +747,9 @@ def measure_sharded(ctx, dist, rank, world, workload, scale, steps, warmup):
         dist.barrier()
     t0 = time.perf_counter()
     for _ in range(steps):
-        ctx.cluster_batch(phb, reuse=True)
+        last = ctx.cluster_batch(phb, reuse=True)
     t_rank = time.perf_counter() - t0
+    last = last.snapshot() if keep_last else None            # (the recycled arrays are overwritten by the calls below)
     if dist is not None:
         dist.barrier()
     dt = time.perf_counter() - t0
@@ -777,7 +786,7 @@ def measure_sharded(ctx, dist, rank, world, workload, scale, steps, warmup):
                "signature_load_max_over_mean": (max(x[0] for x in loads) / (total_sig / world)) if dist is not None else 1.0}
     tasks = list(dict.fromkeys((t, c) for (t, c, _) in unit_keys))
     hb_plain, _ = shard.host_batch(store, params, units)          # (the same pieces from the pageable store: the one-shot-pageable leg, kernel_units)
-    return out, dt, total_sig, store, params, wl_name, pstore, phb, tasks, hb_plain
+    return out, dt, total_sig, store, params, wl_name, pstore, phb, tasks, hb_plain, last
 
 
 _OUT_FD = None
@@ -794,7 +803,7 @@ def quiet_stdout():
 
 
 LINE_LIMIT = 7600        # bytes: the driver keeps an 8 000-byte tail of stdout (BENCH_r04.json): the whole line must fit it
-FULL_LINE = False         # --full: print every object (the scripts under scripts/ read kernel_us_cold, traffic_per_kernel, ...)
+FULL_LINE = False         # --full-line: print every object (the scripts under scripts/ read kernel_us_cold, traffic_per_kernel, ...)
 
 
 def _num(x, nd=4):
@@ -911,6 +920,24 @@ def emit(out):
         os.write(_OUT_FD, line)
 
 
+DUMP_LIMIT = 60_000_000   # bytes of array data --dump-outputs writes at most (the .npy headers stay well inside 64 MB)
+
+
+def dump_outputs(d, res):
+    """--dump-outputs: what the caller of the timed path received from its last step - every array of res.trimmed() (the call
+    fields, the support lists, the segments' status) and n_clusters - as d/<name>.npy in float64, which holds each of these
+    integers exactly.  Above DUMP_LIMIT bytes in all, every array is cut to the same share of its rows, picked by a fixed seed."""
+    arrays = {k: np.atleast_1d(np.asarray(v, np.float64)) for k, v in res.trimmed().items() if v is not None}
+    total = sum(v.nbytes for v in arrays.values())
+    if total > DUMP_LIMIT:
+        for k, v in arrays.items():
+            keep = np.random.default_rng(20260103).choice(len(v), int(np.ceil(len(v) * DUMP_LIMIT / total)), replace=False)
+            arrays[k] = v[np.sort(keep)]
+    os.makedirs(d, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(d, k + ".npy"), v)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -919,17 +946,26 @@ def main():
     ap.add_argument("--workload", default="cfg3")
     ap.add_argument("--scale", type=float, default=1.0)
     ap.add_argument("--mode", default="auto", choices=["auto", "replica", "shard"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-others", action="store_true", help="skip the compact cfg2 / cfg4 / cfg5 objects of the default N = 1 line")
+    ap.add_argument("--full", action="store_true", help="also run every other measurement and check of the line: CPU baselines, the "
+                    "cfg2 / cfg4 / cfg5 objects, the mode1 stage, the other timed regions, per-kernel and roofline figures, parity with "
+                    "the oracle, the sharded object of N > 1 (default: set up, warm up, time the steps, print the headline line)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baselines")
+    ap.add_argument("--no-others", action="store_true", help="(--full) skip the compact cfg2 / cfg4 / cfg5 objects of the N = 1 line")
     ap.add_argument("--cpu-procs", type=int, default=0)
-    ap.add_argument("--no-mode1", action="store_true", help="skip the mode1_stage legs (the drop-in under the reference's forked Pool, bench_stage.py)")
-    ap.add_argument("--full", action="store_true", help="print every object on the one line (default: the compact line, full objects on stderr and in gpurun_out/)")
+    ap.add_argument("--no-mode1", action="store_true", help="(--full) skip the mode1_stage legs (the drop-in under the reference's forked Pool, bench_stage.py)")
+    ap.add_argument("--full-line", action="store_true", help="(--full) print every object on the one line (default: the compact line, "
+                    "the full objects on stderr and in a detail file)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step delivered to its caller as DIR/<name>.npy (float64)")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
     global FULL_LINE
-    FULL_LINE = a.full
+    FULL_LINE = a.full_line
     if "WORLD_SIZE" in os.environ or a.gpus == 1:
         quiet_stdout()
 
+    if a.dump_outputs and a.workload in ("rebuild", "extract"):
+        raise SystemExit("--dump-outputs: the clustering workloads (cfg2 - cfg5) only")
     if a.workload == "rebuild":
         return bench_rebuild(a)
     if a.workload == "extract":
@@ -966,7 +1002,8 @@ def main():
     if shard_mode:
         if ctx is None:
             ctx = engine.Context(local_rank % max(1, engine.device_count()))
-        sharded_obj, dt, total_sig, store, params, wl_name, pstore, phb, tasks, hb = measure_sharded(ctx, dist, rank, world, a.workload, a.scale, a.steps, a.warmup)
+        sharded_obj, dt, total_sig, store, params, wl_name, pstore, phb, tasks, hb, last = measure_sharded(
+            ctx, dist, rank, world, a.workload, a.scale, a.steps, a.warmup, keep_last=bool(a.dump_outputs))
         n_sig = int((phb.segments["sig_end"] - phb.segments["sig_begin"]).sum())
         dt_k = dt_slim = dt_serial = dt_pipe_slim = None
         t_upload = t_pin = None
@@ -979,7 +1016,7 @@ def main():
     # ---------------- CPU baselines first (fork pools before any HIP state exists in this process)
     cpu = cpu_c = cpu_c_mt = ores = mode1 = None
     others = {}
-    if rank == 0 and world == 1 and not a.no_cpu_baseline and not shard_mode:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline and not shard_mode:
         procs = a.cpu_procs or os.cpu_count() or 1
         cpu, cpu_c, cpu_c_mt, ores = cpu_legs(a.workload, store, params, tasks, hb, n_sig, procs, py_pool=True, full_pool=False)
         cal = os.path.join(ROOT, "profiles", "calibration_py_restatement.json")
@@ -1012,20 +1049,24 @@ def main():
         pstore = store.pinned()
         t_pin = time.perf_counter() - t0
         phb = pstore.host_batch(tasks, params)
-        t0 = time.perf_counter()
-        ctx.upload(phb, per_sig=False)
-        t_upload = time.perf_counter() - t0
-        dt_serial, dt_k, _, dt_slim, dt, dt_pipe_slim = resident_loops(ctx, phb, a.steps, a.warmup, dist)
+        t_upload = None
+        if a.full:
+            t0 = time.perf_counter()
+            ctx.upload(phb, per_sig=False)
+            t_upload = time.perf_counter() - t0
+        dt_serial, dt_k, last, dt_slim, dt, dt_pipe_slim = resident_loops(ctx, phb, a.steps, a.warmup, dist, full=a.full)
         total_sig = n_sig
         dt_own = dt
         if dist is not None:
             import torch
-            tt = torch.tensor([dt, dt_k], dtype=torch.float64)
+            tt = torch.tensor([dt, dt_k or 0.0], dtype=torch.float64)
             dist.all_reduce(tt, op=dist.ReduceOp.MAX)
-            dt, dt_k = float(tt[0]), float(tt[1])
+            dt, dt_k = float(tt[0]), (None if dt_k is None else float(tt[1]))
             ts = torch.tensor([n_sig], dtype=torch.float64)
             dist.all_reduce(ts, op=dist.ReduceOp.SUM)
             total_sig = int(ts[0])
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, last)
     # which device every rank sat on (a SCALE record can then show N distinct GPUs) and what it measured by itself
     try:
         bus, ncu = engine.device_info(ctx.device)
@@ -1039,7 +1080,7 @@ def main():
         dist.all_gather_object(gl, per_rank[0])
         per_rank = gl
     ms_reads_kept = None
-    if not shard_mode and phb.r_start is not None:
+    if a.full and not shard_mode and phb.r_start is not None:
         ctx.option(1, 1)
         for _ in range(3):
             ctx.run()
@@ -1054,8 +1095,8 @@ def main():
     value = total_sig * a.steps / dt
     ms_kernel_only = None if dt_k is None else dt_k / a.steps * 1e3
 
-    # world > 1, replica mode: the un-parameterised command also measures ONE genome sharded over the ranks (BASELINE config 4)
-    if world > 1 and not shard_mode and a.workload == "cfg3":
+    # world > 1, replica mode: --full also measures ONE genome sharded over the ranks (BASELINE config 4)
+    if a.full and world > 1 and not shard_mode and a.workload == "cfg3":
         try:
             sharded_obj = measure_sharded(ctx, dist, rank, world, "cfg4", a.scale, max(5, min(a.steps, 20)), 2)[0]
         except Exception as e:          # noqa: BLE001
@@ -1063,8 +1104,24 @@ def main():
             if dist is not None:
                 raise
 
-    out = None
     if rank == 0:
+        head = {
+            "metric": "SV signatures clustered/sec (whole node)", "value": value, "unit": "signatures/s",
+            "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": ms_per_step,
+            "timed_region": ("the rank's whole boundary call: page-locked host columns -> kernels -> host SoA" if shard_mode else
+                             "inputs resident in HBM -> all kernels -> every call field + the int32 support lists delivered into page-locked host arrays (int32 coordinates with int32 columns), every step's full "
+                             "result; the delivery of step k (one copy-engine transfer of the result block, written as a device image behind the run) runs under the kernels of step k + 1 (csv_batch_publish_async)"),
+            "higher_is_better": True, "scaling": "strong" if shard_mode else "weak", "vs_baseline": None, "dtype": "int32 columns, int64+f64 arithmetic" if phb.a.dtype == np.int32 else "int64+f64", "data": "synthetic",
+            "config": {"workload": wl_name, "signatures_per_gpu": n_sig, "signatures_total": total_sig, "segments": len(tasks),
+                       "preset": "ONT" if a.workload in ("cfg2", "cfg3", "cfg5") else "HiFi",
+                       "genotype": bool(params.genotype), "mode": a.mode, "columns": "int32 positions / lengths (SigStore.pinned())",
+                       "sharding": (sharded_obj["mode"] if (shard_mode and sharded_obj) else "one genome per GPU, no collective")},
+            "value_region": "sharded_boundary_call" if shard_mode else "resident_delivered_pipelined",
+            "per_rank": per_rank,
+        }
+    if rank == 0 and not a.full:
+        emit(head)
+    elif rank == 0:
         names = engine.stage_names()
         per_kernel, per_kernel_nps, st, res, kernel_time_us = instrumented(ctx, phb, a.steps)
         # cold: caches evicted before every step (the flush is outside the event-timed region of csv_batch_run)
@@ -1185,19 +1242,10 @@ def main():
                 other_out[name] = {"error": repr(e)}
             cpu_o.clear()
         out = {
-            "metric": "SV signatures clustered/sec (whole node)", "value": value, "unit": "signatures/s",
-            "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": ms_per_step,
-            "timed_region": ("the rank's whole boundary call: page-locked host columns -> kernels -> host SoA" if shard_mode else
-                             "inputs resident in HBM -> all kernels -> every call field + the int32 support lists delivered into page-locked host arrays (int32 coordinates with int32 columns), every step's full "
-                             "result; the delivery of step k (one copy-engine transfer of the result block, written as a device image behind the run) runs under the kernels of step k + 1 (csv_batch_publish_async)"),
+            **head,
             "kernel_only": None if ko_ms is None else {"ms_per_step": ko_ms, "value": total_sig / (ko_ms * 1e-3),
                                                        "note": "the launch sequence alone, results left in HBM (the region r01-r03 reported as value)"},
             "ms_per_step_reads_order_kept": ms_reads_kept,
-            "higher_is_better": True, "scaling": "strong" if shard_mode else "weak", "vs_baseline": None, "dtype": "int32 columns, int64+f64 arithmetic" if phb.a.dtype == np.int32 else "int64+f64", "data": "synthetic",
-            "config": {"workload": wl_name, "signatures_per_gpu": n_sig, "signatures_total": total_sig, "segments": len(tasks),
-                       "preset": "ONT" if a.workload in ("cfg2", "cfg3", "cfg5") else "HiFi",
-                       "genotype": bool(params.genotype), "mode": a.mode, "columns": "int32 positions / lengths (SigStore.pinned())",
-                       "sharding": (sharded_obj["mode"] if (shard_mode and sharded_obj) else "one genome per GPU, no collective")},
             "roofline": {"bound": "hbm", "kernel": dom, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
                          "traffic_note": "L2 <-> fabric bytes per launch (2 x FETCH_SIZE + WRITE_SIZE, rocprofv3 PMC passes of this command, calibrated on "
@@ -1221,7 +1269,6 @@ def main():
             "cpu_baseline": cpu, "cpu_baseline_c": cpu_c, "cpu_baseline_c_mt": cpu_c_mt,
             # speed-ups, each over ONE named pair of regions (r03's speedup_vs_cpu_baseline divided the kernel-only loop by a Python pool)
             "mode1_stage": mode1,
-            "value_region": "sharded_boundary_call" if shard_mode else "resident_delivered_pipelined",
             "speedups": {
                 "stage_wall_vs_reference_model": (cpu["wall_s"] * 1e3 / stage_ms) if (cpu and cpu.get("full_workload")) else None,
                 "stage_wall_vs_reference_model_pool_fit": (cpu["wall_s_pool_fit"] * 1e3 / stage_ms) if (cpu and cpu.get("full_workload") and cpu.get("wall_s_pool_fit")) else None,
@@ -1247,7 +1294,6 @@ def main():
                          "vcf_emit_native": t_vcf, "per_task_drop_in": t_task,
                          "stage_signatures_per_s": n_sig / (stage_ms * 1e-3)},
             "other_workloads": other_out or None,
-            "per_rank": per_rank,
             "sharded": sharded_obj if not shard_mode else None,
             "parity_vs_oracle": parity, "shard_merge_equals_unsharded": (sharded_obj or {}).get("shard_merge_equals_unsharded") if shard_mode else None,
         }

@@ -1,9 +1,9 @@
 #!/bin/bash
-# what the driver runs at round end, in its order: smoke(), the default bench line, the bench line with explicit flags
+# a rehearsal of the end-to-end checks, in order and timed: smoke(), the bench line with --full, the plain bench line with explicit flags
 R=${GRAFT_REPO_ROOT:-/root/repo}; cd $R
 O=$R/gpurun_out/dress; mkdir -p $O
 T0=$(date +%s.%N); python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" 2>&1 | tail -2
-T1=$(date +%s.%N); python bench.py > $O/bench_default.json 2> $O/bench_default.err; tail -1 $O/bench_default.err
+T1=$(date +%s.%N); python bench.py --full > $O/bench_default.json 2> $O/bench_default.err; tail -1 $O/bench_default.err
 python - <<'P'
 import json
 l=open('gpurun_out/dress/bench_default.json').read().strip().split('\n')

@@ -9,7 +9,7 @@ OUT=$R/gpurun_out/prof; F=$R/gpurun_out/final
 mkdir -p $OUT $F
 cd $R
 export CSV_BENCH_EXIT_ALARM=15
-ARGS="bench.py --workload $WL --steps 30 --warmup 5 --no-cpu-baseline --no-others"
+ARGS="bench.py --full --workload $WL --steps 30 --warmup 5 --no-cpu-baseline --no-others"
 timeout -k 5 150 rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAVES -d $OUT/${TAG}_${WL}_i1 -o pmc -- python $ARGS > $OUT/${TAG}_${WL}_i1.log 2>&1
 echo "pass 1 rc=$?"
 timeout -k 5 150 rocprofv3 --kernel-trace --pmc SQ_BUSY_CYCLES SQ_ACTIVE_INST_VALU SQ_WAIT_INST_ANY SQ_WAVE_CYCLES -d $OUT/${TAG}_${WL}_i2 -o pmc -- python $ARGS > $OUT/${TAG}_${WL}_i2.log 2>&1

@@ -15,9 +15,9 @@ for wl in cfg3 cfg4; do timeout 300 python scripts/stage_timeline.py --workload 
 ( echo "# the first 32-worker stage of a broker (after one 8-worker stage): descriptor table grown on demand, then grown once at start"; for v in 0 1; do echo "## CUTESV_AMD_BROKER_FD_TABLE=$v"; CUTESV_AMD_BROKER_FD_TABLE=$v timeout 300 python scripts/stage_timeline.py --workload cfg3 --workers 8,32 --all 2>/dev/null | grep -v "^\[" | awk '/== T=32/{f=1} f' | cut -c1-400 | head -42; done ) > $F/${TAG}_stage_timeline_cfg3_first_t32.txt
 timeout 300 python bench.py --workload rebuild > $F/${TAG}_bench_rebuild.json 2>/dev/null
 timeout 300 python bench.py --workload extract > $F/${TAG}_bench_extract.json 2>/dev/null
-timeout 600 python bench.py --full --gpus 8 --steps 10 --warmup 2 > $F/${TAG}_bench_cfg3_replica_plus_cfg4_sharded_8ranks_one_device.json 2>/dev/null; echo "8 ranks rc=$?"
-timeout 600 python bench.py --full --workload cfg5 --mode shard --gpus 8 --steps 5 --warmup 2 > $F/${TAG}_bench_cfg5_sharded_8ranks_one_device.json 2>/dev/null; echo "cfg5 8 ranks rc=$?"
-timeout 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 bench.py --full --gpus 2 --steps 5 --warmup 2 2>/dev/null | tail -1 > $F/${TAG}_bench_torchrun_2ranks_one_device.json; echo "torchrun rc=$?"
+timeout 600 python bench.py --full --full-line --gpus 8 --steps 10 --warmup 2 > $F/${TAG}_bench_cfg3_replica_plus_cfg4_sharded_8ranks_one_device.json 2>/dev/null; echo "8 ranks rc=$?"
+timeout 600 python bench.py --full --full-line --workload cfg5 --mode shard --gpus 8 --steps 5 --warmup 2 > $F/${TAG}_bench_cfg5_sharded_8ranks_one_device.json 2>/dev/null; echo "cfg5 8 ranks rc=$?"
+timeout 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 bench.py --full --full-line --gpus 2 --steps 5 --warmup 2 2>/dev/null | tail -1 > $F/${TAG}_bench_torchrun_2ranks_one_device.json; echo "torchrun rc=$?"
 timeout 700 python scripts/stress_gpu.py ${STRESS_N:-30000} 1200000 > $F/${TAG}_stress.log 2>&1; tail -2 $F/${TAG}_stress.log
 timeout 300 python scripts/stress_gpu.py ${STRESS_BIG:-3000} 1300000 big > $F/${TAG}_stress_big.log 2>&1; tail -2 $F/${TAG}_stress_big.log
 timeout 600 python scripts/stress_pool.py ${STRESS_POOL:-400} 70000 > $F/${TAG}_stress_pool.log 2>&1; tail -2 $F/${TAG}_stress_pool.log
