@@ -244,6 +244,111 @@ def _reads_near(pos1, pos2, r_start, r_end, margin, shift=10):
     return None if m is None else np.frombuffer(bytearray(m), np.bool_)
 
 
+def default_threads():
+    """host threads of a walk: the CPUs this process may run on, at most 16"""
+    try:
+        n = len(os.sched_getaffinity(0))
+    except (AttributeError, OSError):
+        n = os.cpu_count() or 1
+    return max(1, min(16, n))
+
+
+def _map_file(path):
+    """the file mapped read-only (None: empty or missing); what holds a span of it keeps the mapping alive"""
+    import mmap
+    try:
+        if os.path.getsize(path) == 0:
+            return None
+        with open(path, "rb") as f:
+            return mmap.mmap(f.fileno(), 0, access=mmap.ACCESS_READ)
+    except (OSError, ValueError):
+        return None
+
+
+# What SigStore.from_reference_workdir_native walks of each kind of block: (tuple width, int fields, str fields, the str slot
+# of the chromosome - checked against the block's key -, the key whose order the walk reports as (0: int slot | 1: str slot,
+# slot)).  The signature blocks are taken in the order the file holds them, as the reference's workers take them; the reads
+# block is start-sorted where it is not (from_tuple_lists).
+_WALK = {
+    "DEL": (5, (0, 1), (2, 4), 1, ()),
+    "DUP": (5, (0, 1), (2, 4), 1, ()),
+    "INS": (6, (0, 1), (2, 3, 5), 2, ()),
+    "INV": (6, (1, 2), (0, 3, 5), 2, ()),
+    "TRA": (7, (1, 3), (0, 2, 4, 6), 3, ()),
+    "reads": (5, (0, 1, 2), (3, 4), 1, ((0, 0),)),
+}
+_NAME_SLOT = {"DEL": 0, "DUP": 0, "INS": 0, "INV": 1, "TRA": 2, "reads": 0}
+
+
+def _nonempty_reads_blocks(sigs_index, work_dir):
+    """the chromosomes of sigs_index["reads"] whose block holds a row, without reading the blocks: a pickled list with a row in
+    it takes more than 64 bytes, or the block is short enough to unpickle (an empty list names no chromosome: from_tuple_lists)"""
+    offs = sigs_index.get("reads", {})
+    path = work_dir + "reads.pickle"
+    try:
+        size = os.path.getsize(path)
+    except OSError:
+        size = 0
+    starts = sorted({int(o) for o in offs.values()})
+    out = []
+    for ch, off in offs.items():
+        off = int(off)
+        k = np.searchsorted(starts, off, side="right")
+        end = starts[k] if k < len(starts) else size
+        if end - off > 64:
+            out.append(ch)
+            continue
+        try:
+            with open(path, "rb") as f:
+                f.seek(off)
+                if len(pickle.load(f)):
+                    out.append(ch)
+        except Exception:                              # noqa: BLE001  (a block nobody reads here: it names its chromosome)
+            out.append(ch)
+    return out
+
+
+class _Block:
+    """One walked block: n rows, int64 columns, (offset, length) spans of the str fields inside `buf`, and whether every string
+    of it is ASCII"""
+
+    def __init__(self, n, buf, ints, spans, ascii_):
+        self.n, self.buf, self.ints, self.spans, self.ascii = n, buf, ints, spans, ascii_
+
+    def span(self, k):
+        return (self.buf,) + tuple(self.spans[k])
+
+    @classmethod
+    def walked(cls, buf, t, n_int):
+        ints = [np.frombuffer(x, np.int64) for x in t[2]]
+        spans = [(np.frombuffer(o, np.int64), np.frombuffer(l, np.int32)) for o, l in t[3]]
+        return cls(int(t[0]), buf, ints, spans, bool(t[4]))
+
+    def take(self, sel):
+        return _Block(self.n, self.buf, [x[sel] for x in self.ints], [(o[sel], l[sel]) for o, l in self.spans], self.ascii)
+
+    @classmethod
+    def from_list(cls, kind, lst):
+        """a block pickle.load read (reads: start-sorted, stable), its strings encoded into a buffer of its own"""
+        if kind == "reads":
+            lst = sorted(lst, key=lambda r: r[0])
+        _, fi, fs, _, _ = _WALK[kind]
+        n = len(lst)
+        ints = [np.array([int(x[f]) for x in lst], np.int64) for f in fi]
+        parts, spans, at = [], [], 0
+        for f in fs:
+            enc = [x[f].encode("utf-8", "surrogatepass") for x in lst]
+            ln = np.array([len(e) for e in enc], np.int32)
+            off = np.zeros(n, np.int64)
+            if n:
+                off[1:] = np.cumsum(ln[:-1], dtype=np.int64)
+            spans.append((off + at, ln))
+            at += int(ln.sum())
+            parts.extend(enc)
+        buf = b"".join(parts)
+        return cls(n, buf, ints, spans, buf.isascii())
+
+
 @dataclass
 class SigStore:
     chroms: list                                  # chromosome names; index = chrom id (also the chr2 rank for TRA)
@@ -293,12 +398,20 @@ class SigStore:
         """A store whose columns live in page-locked host memory (csv_host_alloc): csv_cluster_batch then moves them to
         the GPU by DMA straight from these pages (PCIe rate) instead of through the runtime's staging copies.  The
         natural home of the columns in a worker process: load the flat `.cols` files into it once."""
-        import dataclasses
         from . import engine
+        return self._with_narrow(engine.pinned_copy, engine.pinned_empty)
+
+    def with_narrow(self):
+        """The `narrow` forms pinned() makes (int32 twins, 16-bit gaps and lengths, interleaved rows), in ordinary memory and
+        without copying the other columns: what a one-shot call on a freshly built store uploads."""
+        return self._with_narrow(lambda v: v, np.empty)
+
+    def _with_narrow(self, copy, empty):
+        import dataclasses
         cols = {}
         for k in ("read_id", "aux", "reads_off", "r_primary", "r_id", "contig_len"):
             v = getattr(self, k)
-            cols[k] = None if v is None else engine.pinned_copy(v)
+            cols[k] = None if v is None else copy(v)
         # positions and lengths: int32 twins when they fit (a genome's coordinates do) - a third less data on the link
         # (CSV_IN_SIG_I32 / CSV_IN_READS_I32); the int64 columns stay what every host-side consumer reads
         narrow = {}
@@ -309,33 +422,33 @@ class SigStore:
             fits = all(len(v) == 0 or (int(v.min()) >= -(1 << 31) and int(v.max()) < (1 << 31)) for v in vs)
             for k, v in zip(pair, vs):
                 if fits:
-                    narrow[k] = engine.pinned_copy(v.astype(np.int32))
+                    narrow[k] = copy(v.astype(np.int32))
                 else:
-                    cols[k] = engine.pinned_copy(v)
+                    cols[k] = copy(v)
         if "b" in narrow and self.n_sig:
             # ... the lengths and read ids once more, interleaved {b, read_id}: what a gate-first call's device-side fetch reads
-            r8 = engine.pinned_empty((self.n_sig, 2), np.int32)
+            r8 = empty((self.n_sig, 2), np.int32)
             r8[:, 0] = narrow["b"]
             r8[:, 1] = self.read_id
             narrow["rows8"] = r8
         if self.r_id is not None and self.n_reads and int(self.r_id.min()) >= 0:
             # ... the read id and the primary flag in one word (the form the device keeps them in): 5 -> 4 bytes per read on the link
-            idp = engine.pinned_empty(self.n_reads, np.uint32)
+            idp = empty(self.n_reads, np.uint32)
             np.copyto(idp, self.r_id.astype(np.uint32) | (self.r_primary.astype(np.uint32) << np.uint32(31)), casting="unsafe")
             narrow["r_idp"] = idp
         if "r_start" in narrow and self.n_reads:
             # ... the reads table's starts as 16-bit gaps and its ends as 16-bit lengths (CSV_IN_READS_DELTA16), each where the
             # column is not mostly escapes (a shuffled block; ultra-long reads)
             keep_all = bool(os.environ.get("CSV_DELTA16_ESC"))
-            rd = _abi.delta16_of(narrow["r_start"], alloc=engine.pinned_empty)
+            rd = _abi.delta16_of(narrow["r_start"], alloc=empty)
             if keep_all or len(rd[1]) * 64 <= len(rd[0]):
                 narrow["r_delta"] = rd
-            rl = _abi.len16_of(narrow["r_start"], narrow["r_end"], alloc=engine.pinned_empty)
+            rl = _abi.len16_of(narrow["r_start"], narrow["r_end"], alloc=empty)
             if keep_all or len(rl[1]) * 64 <= len(rl[0]):
                 narrow["r_len16"] = rl
         if "a" in narrow:
             # ... and the position column once more as 16-bit gaps (CSV_IN_SIG_DELTA16): half of the largest transfer of a call
-            ad = _abi.delta16_of(narrow["a"], alloc=engine.pinned_empty)
+            ad = _abi.delta16_of(narrow["a"], alloc=empty)
             if len(ad[1]) * 64 <= len(ad[0]) or os.environ.get("CSV_DELTA16_ESC"):      # (a sparse column is mostly escapes: the column itself travels)
                 narrow["a_delta"] = ad
         return dataclasses.replace(self, narrow=narrow or None, **cols)
@@ -784,6 +897,166 @@ class SigStore:
                 f.seek(off)
                 reads.extend(pickle.load(f))
         return cls.from_tuple_lists(per_type, reads, contig_len=contig_len)
+
+    @classmethod
+    def from_reference_workdir_native(cls, work_dir, sigs_index=None, contig_len=None, threads=None, reads=True):
+        """from_reference_workdir without a Python object per signature or per read: every block of `<TYPE>.pickle` /
+        `reads.pickle` (each its own pickle stream, main script :817-857) is walked in C straight out of the mapped files, on
+        `threads` threads with the interpreter lock released (`_cols_native.walk_workdir`), and the read names are interned per
+        chromosome - over its signature blocks of every type and its reads block - into one genome-wide id space
+        (`_cols_native.intern_groups`).  The store is the one from_reference_workdir builds - chromosome ranks, segments, INV
+        strands, TRA mates, read names and inserted sequences as strings, the reads block of every chromosome - with these
+        differences of form only: read ids number the names by first appearance within a chromosome (the kernels compare ids
+        within a chromosome, and the rows are already in the rebuild's order: from_task_pickles does the same per task), the
+        inserted sequences are spans of the mapped INS.pickle (kept alive by the store), and `narrow` is filled as pinned() fills
+        it.  The signatures stay in the order of the files, as the reference's phase 3 takes them (its rebuild step sorted and
+        de-duplicated them before writing, main script :764-802, :958-969; from_tuple_lists does that once more, for input of
+        any order - on the reference's files the two agree).  A block the walker does not know (another pickle protocol,
+        another opcode) is read by pickle.load, that block alone.  A row whose chromosome is not the one its block is filed
+        under sends the whole directory through from_reference_workdir.
+        reads=False: the reads blocks are not read at all (a stage that does not genotype never uploads them).
+        threads: default min(16, CPUs this process may run on)."""
+        from . import _cols_native as cn
+        if not work_dir.endswith("/"):
+            work_dir += "/"
+        if sigs_index is None:
+            with open(work_dir + "sigindex.pickle", "rb") as f:
+                sigs_index = pickle.load(f)
+        threads = default_threads() if threads is None else max(1, int(threads))
+        kinds = list(TYPES) + (["reads"] if reads else [])
+        blocks = {}                                   # (kind, chr) -> _Block
+        jobs, job_keys, fallback = [], [], []
+        for kind in kinds:
+            offs = sigs_index.get(kind, {})
+            if not offs:
+                continue
+            path = "%s%s.pickle" % (work_dir, kind)
+            mm = _map_file(path)
+            size = 0 if mm is None else len(mm)
+            starts = sorted({int(o) for o in offs.values()})
+            width, fi, fs, chk, key = _WALK[kind]
+            for ch, off in offs.items():
+                off = int(off)
+                if mm is None or not 0 <= off < size:
+                    fallback.append((kind, ch, path, off))             # (pickle says what is wrong with it)
+                    continue
+                k = np.searchsorted(starts, off, side="right")
+                end = starts[k] if k < len(starts) else size
+                jobs.append((mm, off, end, width, fi, fs, chk, ch.encode("utf-8", "surrogatepass"), key))
+                job_keys.append((kind, ch, path, off))
+        walked = cn.walk_workdir(tuple(jobs), threads) if jobs else []
+        for (kind, ch, path, off), job, t in zip(job_keys, jobs, walked):
+            if t is False:
+                return cls._from_reference_workdir_narrow(work_dir, sigs_index, contig_len)
+            if t is None:
+                fallback.append((kind, ch, path, off))
+                continue
+            blk = _Block.walked(job[0], t, len(_WALK[kind][1]))
+            if not t[5]:
+                blk = blk.take(np.argsort(blk.ints[0], kind="stable"))   # reads: a start-sorted block (stable), as from_tuple_lists
+            blocks[(kind, ch)] = blk
+        for kind, ch, path, off in fallback:
+            with open(path, "rb") as f:
+                f.seek(off)
+                lst = pickle.load(f)
+            if any(x[-1] != ch for x in lst):
+                return cls._from_reference_workdir_narrow(work_dir, sigs_index, contig_len)
+            blocks[(kind, ch)] = _Block.from_list(kind, lst)
+        return cls._from_blocks(blocks, sigs_index, contig_len, threads, reads, work_dir)
+
+    @classmethod
+    def _from_reference_workdir_narrow(cls, work_dir, sigs_index, contig_len):
+        return cls.from_reference_workdir(work_dir, sigs_index, contig_len=contig_len).with_narrow()
+
+    @classmethod
+    def _from_blocks(cls, blocks, sigs_index, contig_len, threads, reads, work_dir):
+        from . import _cols_native as cn
+        blocks = {k: v for k, v in blocks.items() if v.n}           # (an empty list names no chromosome: from_tuple_lists)
+
+        def distinct(specs):                                         # a small string field over many blocks -> (values, ids per spec)
+            ids = [np.empty(len(o), np.int32) for _, o, _ in specs]
+            blob, uo, ul = cn.span_intern(tuple((b, o, l, i) for (b, o, l), i in zip(specs, ids)))
+            return list(SpanList(blob, np.frombuffer(uo, np.int64), np.frombuffer(ul, np.int32))), ids
+
+        cs = {ch for (_, ch) in blocks}
+        if not reads:
+            cs.update(_nonempty_reads_blocks(sigs_index, work_dir))     # (the ranks do not depend on whether the reads are read)
+        tra = [ch for (t, ch) in blocks if t == "TRA"]
+        if tra:
+            mates, mate_ids = distinct([blocks[("TRA", ch)].span(1) for ch in tra])
+            cs.update(mates)
+        chroms = sorted(cs)
+        crank = {c: i for i, c in enumerate(chroms)}
+        order = [(t, ch) for t in TYPES for ch in chroms if (t, ch) in blocks]
+        seg_index, n = {}, 0
+        for t, ch in order:
+            seg_index[(t, ch)] = (n, n + blocks[(t, ch)].n)
+            n += blocks[(t, ch)].n
+        cat = lambda parts, dt: np.concatenate(parts).astype(dt, copy=False) if parts else np.zeros(0, dt)      # noqa: E731
+        a = cat([blocks[k].ints[0] for k in order], np.int64)
+        b = cat([blocks[k].ints[1] for k in order], np.int64)
+        aux = np.zeros(n, np.int32)
+        strands = ("++", "--")
+        inv = [k for k in order if k[0] == "INV"]
+        if inv:
+            sd, sid = distinct([blocks[k].span(0) for k in inv])
+            strands = tuple(sorted(sd))
+            lut = np.array([strands.index(x) for x in sd], np.int32)
+            for k, ids in zip(inv, sid):
+                aux[slice(*seg_index[k])] = lut[ids]
+        if tra:
+            td, tid = distinct([blocks[("TRA", ch)].span(0) for ch in tra])
+            tlut = np.array([BND_CODE.get(x, 4) for x in td], np.int32)
+            clut = np.array([crank[c] for c in mates], np.int32)
+            for ch, ti, ci in zip(tra, tid, mate_ids):
+                aux[slice(*seg_index[("TRA", ch)])] = clut[ci] * 8 + tlut[ti]
+        ins = [k for k in order if k[0] == "INS"]
+        ins_seq = {}
+        for k in ins:
+            blk, sl = blocks[k], slice(*seg_index[k])
+            if blk.ascii:
+                aux[sl] = blk.spans[1][1]
+            else:
+                cn.span_cplen(blk.buf, blk.spans[1][0], blk.spans[1][1], aux[sl])
+        if ins and len({id(blocks[k].buf) for k in ins}) == 1:          # every INS block walked out of the one mapped file
+            so, sl_ = np.zeros(n, np.int64), np.zeros(n, np.int32)
+            for k in ins:
+                so[slice(*seg_index[k])], sl_[slice(*seg_index[k])] = blocks[k].spans[1]
+            ins_seq = SpanList(blocks[ins[0]].buf, so, sl_)
+        elif ins:
+            for k in ins:
+                sp = SpanList(blocks[k].buf, *blocks[k].spans[1])
+                beg = seg_index[k][0]
+                ins_seq.update((beg + i, sp[i]) for i in range(len(sp)))
+        # read names: one group per chromosome (its signature blocks in the submission order of the types, then its reads block),
+        # ids written straight into the store's columns
+        read_id = np.empty(n, np.int32)
+        rblocks = [ch for ch in chroms if ("reads", ch) in blocks]
+        reads_off = np.zeros(len(chroms) + 1, np.int64)
+        for ch in chroms:
+            reads_off[crank[ch] + 1] = reads_off[crank[ch]] + (blocks[("reads", ch)].n if ("reads", ch) in blocks else 0)
+        nr = int(reads_off[-1])
+        r_id = np.empty(nr, np.int32)
+        groups = []
+        for ch in chroms:
+            g = [blocks[(t, ch)].span(_NAME_SLOT[t]) + (read_id[slice(*seg_index[(t, ch)])],) for t in TYPES if (t, ch) in blocks]
+            if ("reads", ch) in blocks:
+                c = crank[ch]
+                g.append(blocks[("reads", ch)].span(0) + (r_id[reads_off[c]:reads_off[c + 1]],))
+            if g:
+                groups.append(tuple(g))
+        blob, uo, ul = cn.intern_groups(tuple(groups), threads)
+        names = NameTable(SpanList(blob, np.frombuffer(uo, np.int64), np.frombuffer(ul, np.int32)))
+        kw = {}
+        if nr:
+            kw = dict(reads_off=reads_off, r_start=cat([blocks[("reads", ch)].ints[0] for ch in rblocks], np.int64),
+                      r_end=cat([blocks[("reads", ch)].ints[1] for ch in rblocks], np.int64),
+                      r_primary=cat([blocks[("reads", ch)].ints[2] for ch in rblocks], np.uint8), r_id=r_id)
+        if contig_len is not None:
+            kw["contig_len"] = np.array([int(contig_len[c]) for c in chroms], np.int64)
+        st = cls(chroms=chroms, a=a, b=b, read_id=read_id, aux=aux, seg_index=seg_index, names=names, ins_seq=ins_seq,
+                 strands=strands, **kw)
+        return st.with_narrow()
 
     @classmethod
     def from_sigs_dir(cls, work_dir, contig_len=None):

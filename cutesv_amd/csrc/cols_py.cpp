@@ -19,6 +19,10 @@
 #include <Python.h>
 #include <stdint.h>
 #include <string.h>
+#include <algorithm>
+#include <atomic>
+#include <string>
+#include <thread>
 #include <vector>
 
 namespace {
@@ -412,35 +416,56 @@ struct Columns {
     }
     PyObject* take(size_t k) { PyObject* x = o[k]; o[k] = nullptr; return x; }
 };
-}   // namespace pk
 
-PyObject* pickle_table(PyObject*, PyObject* args)
+// The same columns in plain memory, for a walk on a thread that does not hold the interpreter lock (walk_workdir): realloc'ed
+// together, cut to the row count, handed to an Owned object at the end.
+struct MallocColumns {
+    std::vector<char*> base; std::vector<int> item;
+    size_t cap = 0;
+    ~MallocColumns() { for (char* x : base) free(x); }
+    void add(int itemsize) { base.push_back(nullptr); item.push_back(itemsize); }
+    bool reserve(size_t rows)
+    {
+        for (size_t k = 0; k < base.size(); k++) {
+            void* q = realloc(base[k], rows * (size_t)item[k] + 1);
+            if (!q) return false;
+            base[k] = (char*)q;
+        }
+        cap = rows;
+        return true;
+    }
+    char* take(size_t k) { char* x = base[k]; base[k] = nullptr; return x; }
+};
+
+// the int / str field numbers of a call (non-negative)
+inline bool fields_of(PyObject* oints, PyObject* ostrs, std::vector<Py_ssize_t>& fi, std::vector<Py_ssize_t>& fs)
 {
-    PyObject *obuf, *oints, *ostrs; Py_ssize_t offset, width, end_hint = -1;
-    if (!PyArg_ParseTuple(args, "OnnO!O!|n", &obuf, &offset, &width, &PyTuple_Type, &oints, &PyTuple_Type, &ostrs, &end_hint)) return nullptr;
-    Py_buffer view{};
-    if (PyObject_GetBuffer(obuf, &view, PyBUF_SIMPLE) != 0) return nullptr;
-    struct Rel { Py_buffer* v; ~Rel() { PyBuffer_Release(v); } } rel{&view};
-    if (offset < 0 || offset > view.len) { PyErr_SetString(PyExc_ValueError, "pickle_table: offset outside the buffer"); return nullptr; }
-    std::vector<Py_ssize_t> fi, fs;
+    if (!PyTuple_Check(oints) || !PyTuple_Check(ostrs)) { PyErr_SetString(PyExc_TypeError, "fields must be tuples"); return false; }
     for (Py_ssize_t k = 0; k < PyTuple_GET_SIZE(oints); k++) { fi.push_back(PyLong_AsSsize_t(PyTuple_GET_ITEM(oints, k))); }
     for (Py_ssize_t k = 0; k < PyTuple_GET_SIZE(ostrs); k++) { fs.push_back(PyLong_AsSsize_t(PyTuple_GET_ITEM(ostrs, k))); }
-    if (PyErr_Occurred()) return nullptr;
-    for (Py_ssize_t f : fi) if (f < 0) { PyErr_SetString(PyExc_ValueError, "pickle_table: negative field"); return nullptr; }
-    for (Py_ssize_t f : fs) if (f < 0) { PyErr_SetString(PyExc_ValueError, "pickle_table: negative field"); return nullptr; }
+    if (PyErr_Occurred()) return false;
+    for (Py_ssize_t f : fi) if (f < 0) { PyErr_SetString(PyExc_ValueError, "pickle_table: negative field"); return false; }
+    for (Py_ssize_t f : fs) if (f < 0) { PyErr_SetString(PyExc_ValueError, "pickle_table: negative field"); return false; }
+    return true;
+}
 
-    using namespace pk;
-    Reader R{(const unsigned char*)view.buf, (int64_t)view.len, (int64_t)offset};
+// The opcode walker itself, over any column store with add / reserve / base / cap: Columns (bytes objects, under the interpreter
+// lock: pickle_table) or MallocColumns (plain memory, on a thread of walk_workdir without the lock).  W.unsupported: the stream
+// holds something the walker does not know; W.corrupt: pickle would raise too; W.oom: the columns could not grow.
+struct WalkOut { int64_t n_rows = 0, end = 0; bool unsupported = false, oom = false, any_non_ascii = false; const char* corrupt = nullptr; };
+
+template <class Cols>
+void walk_stream(const unsigned char* buf, int64_t len, int64_t offset, Py_ssize_t width, const std::vector<Py_ssize_t>& fi,
+                 const std::vector<Py_ssize_t>& fs, Py_ssize_t end_hint, Cols& C, WalkOut& W)
+{
+    Reader R{buf, len, offset};
     std::vector<Cell> st;
     Pod<Cell> memo;
-    Columns C;                                                           // int fields (int64), then (offset int64, length int32) per string field
     const size_t NI = fi.size(), NS = fs.size();
-    for (size_t k = 0; k < NI; k++) C.add(8);
-    for (size_t k = 0; k < NS; k++) { C.add(8); C.add(4); }
-    if (!C.reserve(1024)) return nullptr;
-    int64_t n_rows = 0;
-    bool done = false, unsupported = false, oom = false, any_non_ascii = false;       // (all-ASCII text: len() of a string is its byte count)
-    const char* corrupt = nullptr;
+    int64_t& n_rows = W.n_rows;
+    bool done = false;
+    bool &unsupported = W.unsupported, &oom = W.oom, &any_non_ascii = W.any_non_ascii;      // (all-ASCII text: len() of a string is its byte count)
+    const char*& corrupt = W.corrupt;
     auto memo_put = [&](uint64_t k) {
         if (st.empty()) { corrupt = "memo of an empty stack"; return; }
         if (k > memo.n) { unsupported = true; return; }                              // (pickle numbers its memo densely; anything else: not ours)
@@ -676,9 +701,33 @@ PyObject* pickle_table(PyObject*, PyObject* args)
         default: unsupported = true; break;
         }
     }
-    if (oom) { if (!PyErr_Occurred()) PyErr_NoMemory(); return nullptr; }
-    if (corrupt) { PyErr_Format(PyExc_ValueError, "pickle_table: %s at byte %lld", corrupt, (long long)R.i); return nullptr; }
-    if (unsupported) Py_RETURN_NONE;
+    W.end = R.i;
+}
+}   // namespace pk
+
+PyObject* pickle_table(PyObject*, PyObject* args)
+{
+    PyObject *obuf, *oints, *ostrs; Py_ssize_t offset, width, end_hint = -1;
+    if (!PyArg_ParseTuple(args, "OnnO!O!|n", &obuf, &offset, &width, &PyTuple_Type, &oints, &PyTuple_Type, &ostrs, &end_hint)) return nullptr;
+    Py_buffer view{};
+    if (PyObject_GetBuffer(obuf, &view, PyBUF_SIMPLE) != 0) return nullptr;
+    struct Rel { Py_buffer* v; ~Rel() { PyBuffer_Release(v); } } rel{&view};
+    if (offset < 0 || offset > view.len) { PyErr_SetString(PyExc_ValueError, "pickle_table: offset outside the buffer"); return nullptr; }
+    std::vector<Py_ssize_t> fi, fs;
+    if (!pk::fields_of(oints, ostrs, fi, fs)) return nullptr;
+
+    using namespace pk;
+    Columns C;                                                           // int fields (int64), then (offset int64, length int32) per string field
+    const size_t NI = fi.size(), NS = fs.size();
+    for (size_t k = 0; k < NI; k++) C.add(8);
+    for (size_t k = 0; k < NS; k++) { C.add(8); C.add(4); }
+    if (!C.reserve(1024)) return nullptr;
+    WalkOut W;
+    walk_stream((const unsigned char*)view.buf, (int64_t)view.len, (int64_t)offset, width, fi, fs, end_hint, C, W);
+    const int64_t n_rows = W.n_rows;
+    if (W.oom) { if (!PyErr_Occurred()) PyErr_NoMemory(); return nullptr; }
+    if (W.corrupt) { PyErr_Format(PyExc_ValueError, "pickle_table: %s at byte %lld", W.corrupt, (long long)W.end); return nullptr; }
+    if (W.unsupported) Py_RETURN_NONE;
     if (!C.reserve((size_t)n_rows)) return nullptr;                       // cut to the rows there are
     PyObject* ints = PyList_New((Py_ssize_t)NI);
     PyObject* strs = PyList_New((Py_ssize_t)NS);
@@ -692,7 +741,7 @@ PyObject* pickle_table(PyObject*, PyObject* args)
         if (!t) { Py_DECREF(ints); Py_DECREF(strs); return nullptr; }
         PyList_SET_ITEM(strs, (Py_ssize_t)k, t);
     }
-    return Py_BuildValue("(LLNNO)", (long long)n_rows, (long long)R.i, ints, strs, any_non_ascii ? Py_False : Py_True);
+    return Py_BuildValue("(LLNNO)", (long long)n_rows, (long long)W.end, ints, strs, W.any_non_ascii ? Py_False : Py_True);
 }
 
 // read-only views of (buffer, int64 offsets, int32 lengths)
@@ -731,64 +780,63 @@ inline uint64_t hash_bytes(const char* p, int32_t n)
     return h ^ (h >> 29);
 }
 
-PyObject* span_intern(PyObject*, PyObject* args)
+// span_intern's table, for any number of callers at a time (each with its own Scratch): ids by first appearance, ONE id space over
+// the specs in the order given; the distinct strings are left in S.uniq.  -> 0, or 1 (a span outside its buffer: *bad = its
+// index), or 2 (more than 2^31 distinct values).
+struct SpanSrc { const char* buf; int64_t buflen; const int64_t* off; const int32_t* len; int64_t n; int32_t* ids; };
+struct InternScratch {
+    struct Slot { uint32_t tag; int32_t id; };
+    struct U { const char* p; int32_t n; };
+    std::vector<Slot> slot;
+    std::vector<U> uniq;
+    std::vector<uint64_t> hs;
+    int64_t blob_bytes = 0;
+};
+
+inline bool span_at(const SpanSrc& S, int64_t i, const char*& p, int32_t& n)
 {
-    PyObject* specs;
-    if (!PyArg_ParseTuple(args, "O!", &PyTuple_Type, &specs)) return nullptr;
-    const Py_ssize_t ns = PyTuple_GET_SIZE(specs);
-    std::vector<SpanArgs> sp((size_t)ns);
-    std::vector<Buf> ids((size_t)ns);
-    Py_ssize_t total = 0;
-    for (Py_ssize_t k = 0; k < ns; k++) {
-        PyObject *b, *o, *l, *out;
-        if (!PyArg_ParseTuple(PyTuple_GET_ITEM(specs, k), "OOOO", &b, &o, &l, &out) || !sp[(size_t)k].get(b, o, l)) return nullptr;
-        if (!ids[(size_t)k].get(out, sp[(size_t)k].n(), "span_intern ids") || ids[(size_t)k].v.itemsize != 4) { if (!PyErr_Occurred()) PyErr_SetString(PyExc_ValueError, "span_intern: ids must be int32"); return nullptr; }
-        total += sp[(size_t)k].n();
-    }
+    const int64_t o = S.off[i]; n = S.len[i];
+    if (o < 0 || n < 0 || o + n > S.buflen) return false;
+    p = S.buf + o;
+    return true;
+}
+
+int intern_spans(const SpanSrc* specs, size_t ns, InternScratch& X, int64_t* bad)
+{
+    int64_t total = 0;
+    for (size_t k = 0; k < ns; k++) total += specs[k].n;
     size_t cap = 64;
     while (cap < (size_t)total * 2 + 8) cap <<= 1;
     // a slot keeps 32 bits of the hash beside the id: a probe that passes somebody else's entry never leaves the table
-    struct Slot { uint32_t tag; int32_t id; };
-    struct U { const char* p; int32_t n; };
-    // the scratch outlives the call (one call at a time, under the interpreter lock): a worker interns task after task of about
-    // the same size, and fresh pages cost more than the probes (1.4 us a page on the pool's virtual machines; ~5 MB a task).
-    // What has grown beyond 64 MB is given back at the end.
-    static std::vector<Slot> slot;
-    static std::vector<U> uniq;
-    static std::vector<uint64_t> hs;
-    struct Trim {
-        ~Trim()
-        {
-            if (slot.capacity() * sizeof(Slot) > (64u << 20)) std::vector<Slot>().swap(slot);
-            if (uniq.capacity() * sizeof(U) > (64u << 20)) std::vector<U>().swap(uniq);
-            if (hs.capacity() * 8 > (64u << 20)) std::vector<uint64_t>().swap(hs);
-        }
-    } trim;
+    using Slot = InternScratch::Slot;
+    std::vector<Slot>& slot = X.slot;
+    std::vector<InternScratch::U>& uniq = X.uniq;
+    std::vector<uint64_t>& hs = X.hs;
     slot.assign(cap, Slot{0, -1});
     uniq.clear();
-    int64_t blob_bytes = 0;
-    for (Py_ssize_t k = 0; k < ns; k++) {
-        const SpanArgs& S = sp[(size_t)k];
-        int32_t* out = (int32_t*)ids[(size_t)k].v.buf;
-        const Py_ssize_t m = S.n();
+    X.blob_bytes = 0;
+    for (size_t k = 0; k < ns; k++) {
+        const SpanSrc& S = specs[k];
+        int32_t* out = S.ids;
+        const int64_t m = S.n;
         // Two passes, each with its misses asked for ahead of time: the hashes (the payloads - the kept reads of a task lie
         // scattered over a 0.2 GB file - fetched 12 names ahead), then the table (a name's first slot fetched 8 names ahead).
         // One name at a time, miss after miss, this was 60-75 ns a name; a task of a 30x genome has 10^5 of them.
         hs.resize((size_t)m);
-        for (Py_ssize_t i = 0; i < m; i++) {
+        for (int64_t i = 0; i < m; i++) {
             if (i + 12 < m) {
-                const int64_t o = ((const int64_t*)S.off.buf)[i + 12];
-                if (o >= 0 && o < S.buf.len) __builtin_prefetch((const char*)S.buf.buf + o);
+                const int64_t o = S.off[i + 12];
+                if (o >= 0 && o < S.buflen) __builtin_prefetch(S.buf + o);
             }
             const char* p; int32_t n;
-            if (!S.span(i, p, n)) return nullptr;
+            if (!span_at(S, i, p, n)) { *bad = i; return 1; }
             hs[(size_t)i] = hash_bytes(p, n);
         }
         const char* prev_p = nullptr; int32_t prev_n = -1, prev_id = -1;
-        for (Py_ssize_t i = 0; i < m; i++) {
+        for (int64_t i = 0; i < m; i++) {
             if (i + 8 < m) __builtin_prefetch(&slot[(size_t)(hs[(size_t)i + 8] >> 7) & (cap - 1)]);
             const char* p; int32_t n;
-            if (!S.span(i, p, n)) return nullptr;
+            if (!span_at(S, i, p, n)) { *bad = i; return 1; }
             // the SAME bytes as the row before - a memo reference of the pickle: the chromosome of every row of a reads block, the
             // "DEL" of every signature - need no probe
             if (p == prev_p && n == prev_n) { out[i] = prev_id; continue; }
@@ -800,21 +848,56 @@ PyObject* span_intern(PyObject*, PyObject* args)
                 const Slot e = slot[q];
                 if (e.id < 0) break;
                 if (e.tag != tag) continue;
-                const U& x = uniq[(size_t)e.id];
+                const InternScratch::U& x = uniq[(size_t)e.id];
                 if (x.n == n && memcmp(x.p, p, (size_t)n) == 0) { id = e.id; break; }
             }
             if (id < 0) {
-                if (uniq.size() >= (size_t)INT32_MAX) { PyErr_SetString(PyExc_OverflowError, "span_intern: more than 2^31 distinct values"); return nullptr; }
+                if (uniq.size() >= (size_t)INT32_MAX) return 2;
                 id = (int32_t)uniq.size();
                 slot[q] = Slot{tag, id};
-                uniq.push_back(U{p, n});
-                blob_bytes += n;
+                uniq.push_back(InternScratch::U{p, n});
+                X.blob_bytes += n;
             }
             out[i] = id;
             prev_p = p; prev_n = n; prev_id = id;
         }
     }
-    PyObject* blob = PyBytes_FromStringAndSize(nullptr, (Py_ssize_t)blob_bytes);
+    return 0;
+}
+
+PyObject* span_intern(PyObject*, PyObject* args)
+{
+    PyObject* specs;
+    if (!PyArg_ParseTuple(args, "O!", &PyTuple_Type, &specs)) return nullptr;
+    const Py_ssize_t ns = PyTuple_GET_SIZE(specs);
+    std::vector<SpanArgs> sp((size_t)ns);
+    std::vector<Buf> ids((size_t)ns);
+    std::vector<SpanSrc> src((size_t)ns);
+    for (Py_ssize_t k = 0; k < ns; k++) {
+        PyObject *b, *o, *l, *out;
+        if (!PyArg_ParseTuple(PyTuple_GET_ITEM(specs, k), "OOOO", &b, &o, &l, &out) || !sp[(size_t)k].get(b, o, l)) return nullptr;
+        if (!ids[(size_t)k].get(out, sp[(size_t)k].n(), "span_intern ids") || ids[(size_t)k].v.itemsize != 4) { if (!PyErr_Occurred()) PyErr_SetString(PyExc_ValueError, "span_intern: ids must be int32"); return nullptr; }
+        const SpanArgs& S = sp[(size_t)k];
+        src[(size_t)k] = SpanSrc{(const char*)S.buf.buf, (int64_t)S.buf.len, (const int64_t*)S.off.buf, (const int32_t*)S.len.buf, (int64_t)S.n(), (int32_t*)ids[(size_t)k].v.buf};
+    }
+    // the scratch outlives the call (one call at a time, under the interpreter lock): a worker interns task after task of about
+    // the same size, and fresh pages cost more than the probes (1.4 us a page on the pool's virtual machines; ~5 MB a task).
+    // What has grown beyond 64 MB is given back at the end.
+    static InternScratch X;
+    struct Trim {
+        ~Trim()
+        {
+            if (X.slot.capacity() * sizeof(InternScratch::Slot) > (64u << 20)) std::vector<InternScratch::Slot>().swap(X.slot);
+            if (X.uniq.capacity() * sizeof(InternScratch::U) > (64u << 20)) std::vector<InternScratch::U>().swap(X.uniq);
+            if (X.hs.capacity() * 8 > (64u << 20)) std::vector<uint64_t>().swap(X.hs);
+        }
+    } trim;
+    int64_t bad = 0;
+    const int rc = intern_spans(src.data(), src.size(), X, &bad);
+    if (rc == 1) { PyErr_Format(PyExc_ValueError, "span %zd lies outside the buffer", (Py_ssize_t)bad); return nullptr; }
+    if (rc == 2) { PyErr_SetString(PyExc_OverflowError, "span_intern: more than 2^31 distinct values"); return nullptr; }
+    const std::vector<InternScratch::U>& uniq = X.uniq;
+    PyObject* blob = PyBytes_FromStringAndSize(nullptr, (Py_ssize_t)X.blob_bytes);
     PyObject* off = PyBytes_FromStringAndSize(nullptr, (Py_ssize_t)(uniq.size() * 8));
     PyObject* len = PyBytes_FromStringAndSize(nullptr, (Py_ssize_t)(uniq.size() * 4));
     if (!blob || !off || !len) { Py_XDECREF(blob); Py_XDECREF(off); Py_XDECREF(len); return nullptr; }
@@ -976,6 +1059,272 @@ PyObject* span_cplen(PyObject*, PyObject* args)
     Py_RETURN_NONE;
 }
 
+// ------------------------------------------------------------------------------------------ a whole work directory, off the lock
+// The reference's phase 3 reads one pickled list per (type, chromosome) - and, to genotype, the chromosome's reads block - out of
+// <TYPE>.pickle / reads.pickle (main script :817-857).  Every block is its own pickle stream, so the blocks of a genome are
+// independent units of work: walk_workdir() runs walk_stream over all of them on threads of its own, with the interpreter lock
+// released for the whole walk, into plain memory; intern_groups() then numbers the read names of each chromosome (span_intern's
+// table, one per group) on the same kind of threads and lays all groups out as ONE id space and ONE blob.
+//
+//   walk_workdir(jobs, n_threads) -> [None | False | (n_rows, end, [int64 Owned per int field], [(offsets int64 Owned, lengths
+//                                                     int32 Owned) per str field], all_ascii, ordered) per job]
+//     job = (buf, offset, end_hint, width, int_fields, str_fields, chk, chk_bytes, key)
+//       chk        index into str_fields of a field every row must hold as exactly chk_bytes (the chromosome), or -1
+//       key        ((kind, index), ...): kind 0 an int field, 1 a str field (by position in int_fields / str_fields); `ordered`
+//                  says whether the rows are in non-decreasing order of that key, compared as Python compares the tuples'
+//                  fields (ints; str by code point = UTF-8 bytes); always True for an empty key
+//     None: the stream holds something the walker does not know (or is damaged: pickle will say how); False: a row's chk field
+//     differs from chk_bytes.
+//   intern_groups(((buf, offsets, lengths, ids int32 out), ...) per group, n_threads) -> (blob, offsets int64, lengths int32) as
+//     Owned: the distinct strings of every group by first appearance, group after group; the ids written are global (a group's
+//     own ids plus the number of distinct strings of the groups before it).
+// Owned: a read-write buffer over malloc'ed memory, freed with the object (np.frombuffer(Owned) keeps it alive).
+struct OwnedObj { PyObject_HEAD char* p; Py_ssize_t n; };
+PyTypeObject OwnedType = {PyVarObject_HEAD_INIT(nullptr, 0)};
+
+int owned_getbuffer(PyObject* self, Py_buffer* view, int flags)
+{
+    static char empty[8];
+    OwnedObj* o = (OwnedObj*)self;
+    return PyBuffer_FillInfo(view, self, o->p ? o->p : empty, o->n, 0, flags);
+}
+void owned_dealloc(PyObject* self) { free(((OwnedObj*)self)->p); PyObject_Del(self); }
+PyBufferProcs owned_as_buffer = {owned_getbuffer, nullptr};
+
+PyObject* owned(char* p, Py_ssize_t n)                           // takes p (freed here if the object cannot be made)
+{
+    OwnedObj* o = PyObject_New(OwnedObj, &OwnedType);
+    if (!o) { free(p); return nullptr; }
+    o->p = p; o->n = n;
+    return (PyObject*)o;
+}
+
+// run fn(i) for i in [0, n) in the order `order` gives, on up to n_threads threads (this one included); called without the lock
+template <class Fn>
+void run_parallel(const std::vector<size_t>& order, int n_threads, Fn fn)
+{
+    std::atomic<size_t> next{0};
+    auto work = [&]() { for (size_t k; (k = next.fetch_add(1)) < order.size();) fn(order[k]); };
+    std::vector<std::thread> th;
+    const size_t extra = (size_t)(n_threads > 1 ? n_threads - 1 : 0);
+    for (size_t t = 0; t < extra && t + 1 < order.size(); t++) {
+        try { th.emplace_back(work); } catch (...) { break; }     // (fewer threads, same work)
+    }
+    work();
+    for (auto& x : th) x.join();
+}
+
+struct WorkJob {
+    Py_buffer view{}; bool held = false;
+    int64_t offset = 0; Py_ssize_t end_hint = -1, width = -1;
+    std::vector<Py_ssize_t> fi, fs;
+    Py_ssize_t chk = -1; std::string chk_bytes;
+    std::vector<std::pair<int, Py_ssize_t>> key;
+    // results
+    pk::MallocColumns C; pk::WalkOut W;
+    bool ok = false, foreign = false, ordered = true;
+    ~WorkJob() { if (held) PyBuffer_Release(&view); }
+};
+
+inline int cmp_span(const char* b, int64_t o1, int32_t l1, int64_t o2, int32_t l2)
+{
+    const int c = memcmp(b + o1, b + o2, (size_t)(l1 < l2 ? l1 : l2));
+    return c ? c : (l1 < l2 ? -1 : (l1 > l2 ? 1 : 0));
+}
+
+void run_job(WorkJob& J)
+{
+    const size_t NI = J.fi.size(), NS = J.fs.size();
+    for (size_t k = 0; k < NI; k++) J.C.add(8);
+    for (size_t k = 0; k < NS; k++) { J.C.add(8); J.C.add(4); }
+    if (!J.C.reserve(1024)) return;
+    const unsigned char* buf = (const unsigned char*)J.view.buf;
+    pk::walk_stream(buf, (int64_t)J.view.len, J.offset, J.width, J.fi, J.fs, J.end_hint, J.C, J.W);
+    if (J.W.oom || J.W.corrupt || J.W.unsupported || !J.C.reserve((size_t)J.W.n_rows)) return;
+    const int64_t n = J.W.n_rows;
+    if (J.chk >= 0 && (size_t)J.chk < NS) {                     // every row's chromosome field is the block's chromosome
+        const int64_t* o = (const int64_t*)J.C.base[NI + 2 * (size_t)J.chk];
+        const int32_t* l = (const int32_t*)J.C.base[NI + 2 * (size_t)J.chk + 1];
+        const int32_t want = (int32_t)J.chk_bytes.size();
+        int64_t good_o = -1;
+        for (int64_t i = 0; i < n; i++) {
+            if (o[i] == good_o && l[i] == want) continue;          // (a memo reference: the same bytes as the row before)
+            if (l[i] != want || memcmp(buf + o[i], J.chk_bytes.data(), (size_t)want) != 0) { J.foreign = true; return; }
+            good_o = o[i];
+        }
+    }
+    for (int64_t i = 1; i < n && J.ordered && !J.key.empty(); i++) {
+        int c = 0;
+        for (const auto& kf : J.key) {
+            const size_t k = (size_t)kf.second;
+            if (kf.first == 0) {
+                const int64_t* v = (const int64_t*)J.C.base[k];
+                c = v[i - 1] < v[i] ? -1 : (v[i - 1] > v[i] ? 1 : 0);
+            } else {
+                const int64_t* o = (const int64_t*)J.C.base[NI + 2 * k];
+                const int32_t* l = (const int32_t*)J.C.base[NI + 2 * k + 1];
+                c = (o[i - 1] == o[i] && l[i - 1] == l[i]) ? 0 : cmp_span((const char*)buf, o[i - 1], l[i - 1], o[i], l[i]);
+            }
+            if (c) break;
+        }
+        if (c > 0) J.ordered = false;
+    }
+    J.ok = true;
+}
+
+PyObject* walk_workdir(PyObject*, PyObject* args)
+{
+    PyObject* ojobs; int n_threads = 1;
+    if (!PyArg_ParseTuple(args, "O!i", &PyTuple_Type, &ojobs, &n_threads)) return nullptr;
+    const Py_ssize_t nj = PyTuple_GET_SIZE(ojobs);
+    std::vector<WorkJob> jobs((size_t)nj);
+    std::vector<size_t> order((size_t)nj);
+    std::vector<int64_t> size((size_t)nj);
+    for (Py_ssize_t j = 0; j < nj; j++) {
+        WorkJob& J = jobs[(size_t)j];
+        PyObject *b, *oints, *ostrs, *ochk, *okey; Py_ssize_t offset;
+        if (!PyArg_ParseTuple(PyTuple_GET_ITEM(ojobs, j), "OnnnO!O!nOO!", &b, &offset, &J.end_hint, &J.width, &PyTuple_Type, &oints,
+                              &PyTuple_Type, &ostrs, &J.chk, &ochk, &PyTuple_Type, &okey)) return nullptr;
+        if (PyObject_GetBuffer(b, &J.view, PyBUF_SIMPLE) != 0) return nullptr;
+        J.held = true;
+        if (offset < 0 || offset > J.view.len) { PyErr_SetString(PyExc_ValueError, "walk_workdir: offset outside the buffer"); return nullptr; }
+        J.offset = (int64_t)offset;
+        if (!pk::fields_of(oints, ostrs, J.fi, J.fs)) return nullptr;
+        if (J.chk >= 0) {
+            char* cb; Py_ssize_t cl;
+            if (PyBytes_AsStringAndSize(ochk, &cb, &cl) != 0) return nullptr;
+            J.chk_bytes.assign(cb, (size_t)cl);
+        }
+        for (Py_ssize_t k = 0; k < PyTuple_GET_SIZE(okey); k++) {
+            int kind; Py_ssize_t idx;
+            if (!PyArg_ParseTuple(PyTuple_GET_ITEM(okey, k), "in", &kind, &idx)) return nullptr;
+            if (idx < 0 || (kind == 0 && (size_t)idx >= J.fi.size()) || (kind != 0 && (size_t)idx >= J.fs.size())) { PyErr_SetString(PyExc_ValueError, "walk_workdir: key field out of range"); return nullptr; }
+            J.key.emplace_back(kind == 0 ? 0 : 1, idx);
+        }
+        order[(size_t)j] = (size_t)j;
+        size[(size_t)j] = (J.end_hint > offset && J.end_hint <= J.view.len ? J.end_hint : J.view.len) - offset;
+    }
+    std::sort(order.begin(), order.end(), [&](size_t x, size_t y) { return size[x] > size[y]; });      // the largest blocks first
+    Py_BEGIN_ALLOW_THREADS
+    run_parallel(order, n_threads, [&](size_t j) {
+        try { run_job(jobs[j]); } catch (...) { jobs[j].W.oom = true; jobs[j].ok = false; }     // (std::bad_alloc of the stack or the memo: the job is not ours)
+    });
+    Py_END_ALLOW_THREADS
+    PyObject* out = PyList_New(nj);
+    if (!out) return nullptr;
+    for (Py_ssize_t j = 0; j < nj; j++) {
+        WorkJob& J = jobs[(size_t)j];
+        PyObject* r;
+        if (J.foreign) { r = Py_False; Py_INCREF(r); }
+        else if (!J.ok) { r = Py_None; Py_INCREF(r); }
+        else {
+            const size_t NI = J.fi.size(), NS = J.fs.size();
+            const Py_ssize_t n = (Py_ssize_t)J.W.n_rows;
+            PyObject* ints = PyList_New((Py_ssize_t)NI);
+            PyObject* strs = PyList_New((Py_ssize_t)NS);
+            if (!ints || !strs) { Py_XDECREF(ints); Py_XDECREF(strs); Py_DECREF(out); return nullptr; }
+            bool bad = false;
+            for (size_t k = 0; k < NI && !bad; k++) {
+                PyObject* x = owned(J.C.take(k), n * 8);
+                if (!x) bad = true; else PyList_SET_ITEM(ints, (Py_ssize_t)k, x);
+            }
+            for (size_t k = 0; k < NS && !bad; k++) {
+                PyObject* o = owned(J.C.take(NI + 2 * k), n * 8);
+                PyObject* l = owned(J.C.take(NI + 2 * k + 1), n * 4);
+                PyObject* t = (o && l) ? PyTuple_Pack(2, o, l) : nullptr;
+                Py_XDECREF(o); Py_XDECREF(l);
+                if (!t) bad = true; else PyList_SET_ITEM(strs, (Py_ssize_t)k, t);
+            }
+            if (bad) { Py_DECREF(ints); Py_DECREF(strs); Py_DECREF(out); return nullptr; }
+            r = Py_BuildValue("(LLNNOO)", (long long)n, (long long)J.W.end, ints, strs, J.W.any_non_ascii ? Py_False : Py_True,
+                              J.ordered ? Py_True : Py_False);
+            if (!r) { Py_DECREF(out); return nullptr; }
+        }
+        PyList_SET_ITEM(out, j, r);
+    }
+    return out;
+}
+
+PyObject* intern_groups(PyObject*, PyObject* args)
+{
+    PyObject* ogroups; int n_threads = 1;
+    if (!PyArg_ParseTuple(args, "O!i", &PyTuple_Type, &ogroups, &n_threads)) return nullptr;
+    const Py_ssize_t ng = PyTuple_GET_SIZE(ogroups);
+    std::vector<std::vector<SpanArgs>> sp((size_t)ng);
+    std::vector<std::vector<Buf>> ids((size_t)ng);
+    std::vector<std::vector<SpanSrc>> src((size_t)ng);
+    std::vector<size_t> order((size_t)ng);
+    std::vector<int64_t> rows((size_t)ng, 0);
+    for (Py_ssize_t g = 0; g < ng; g++) {
+        PyObject* grp = PyTuple_GET_ITEM(ogroups, g);
+        if (!PyTuple_Check(grp)) { PyErr_SetString(PyExc_TypeError, "intern_groups: a group is a tuple of specs"); return nullptr; }
+        const Py_ssize_t ns = PyTuple_GET_SIZE(grp);
+        sp[(size_t)g].resize((size_t)ns); ids[(size_t)g].resize((size_t)ns); src[(size_t)g].resize((size_t)ns);
+        for (Py_ssize_t k = 0; k < ns; k++) {
+            PyObject *b, *o, *l, *out;
+            SpanArgs& S = sp[(size_t)g][(size_t)k];
+            Buf& I = ids[(size_t)g][(size_t)k];
+            if (!PyArg_ParseTuple(PyTuple_GET_ITEM(grp, k), "OOOO", &b, &o, &l, &out) || !S.get(b, o, l)) return nullptr;
+            if (!I.get(out, S.n(), "intern_groups ids") || I.v.itemsize != 4) { if (!PyErr_Occurred()) PyErr_SetString(PyExc_ValueError, "intern_groups: ids must be int32"); return nullptr; }
+            src[(size_t)g][(size_t)k] = SpanSrc{(const char*)S.buf.buf, (int64_t)S.buf.len, (const int64_t*)S.off.buf, (const int32_t*)S.len.buf, (int64_t)S.n(), (int32_t*)I.v.buf};
+            rows[(size_t)g] += S.n();
+        }
+        order[(size_t)g] = (size_t)g;
+    }
+    std::sort(order.begin(), order.end(), [&](size_t x, size_t y) { return rows[x] > rows[y]; });
+    std::vector<std::vector<InternScratch::U>> uniq((size_t)ng);
+    std::vector<int64_t> bytes((size_t)ng, 0), bad((size_t)ng, 0);
+    std::vector<int> rc((size_t)ng, 0);
+    char *blob = nullptr, *poff = nullptr, *plen = nullptr;
+    int64_t n_uniq = 0, n_bytes = 0;
+    bool oom = false;
+    Py_BEGIN_ALLOW_THREADS
+    run_parallel(order, n_threads, [&](size_t g) {
+        try {
+            InternScratch X;
+            rc[g] = intern_spans(src[g].data(), src[g].size(), X, &bad[g]);
+            bytes[g] = X.blob_bytes;
+            uniq[g].swap(X.uniq);
+        } catch (...) { rc[g] = 3; }                     // (std::bad_alloc of the table: reported, not thrown across the thread)
+    });
+    std::vector<int64_t> id0((size_t)ng + 1, 0), at0((size_t)ng + 1, 0);
+    for (size_t g = 0; g < (size_t)ng; g++) { id0[g + 1] = id0[g] + (int64_t)uniq[g].size(); at0[g + 1] = at0[g] + bytes[g]; }
+    n_uniq = id0[(size_t)ng]; n_bytes = at0[(size_t)ng];
+    bool fine = n_uniq <= (int64_t)INT32_MAX;
+    for (int r : rc) fine = fine && r == 0;
+    if (fine) {
+        blob = (char*)malloc((size_t)n_bytes + 1); poff = (char*)malloc((size_t)n_uniq * 8 + 1); plen = (char*)malloc((size_t)n_uniq * 4 + 1);
+        oom = !blob || !poff || !plen;
+        if (!oom)
+            run_parallel(order, n_threads, [&](size_t g) {            // the groups' strings and ids into the one space
+                int64_t at = at0[g];
+                int64_t* po = (int64_t*)poff + id0[g];
+                int32_t* pl = (int32_t*)plen + id0[g];
+                for (size_t u = 0; u < uniq[g].size(); u++) {
+                    memcpy(blob + at, uniq[g][u].p, (size_t)uniq[g][u].n);
+                    po[u] = at; pl[u] = uniq[g][u].n; at += uniq[g][u].n;
+                }
+                const int32_t add = (int32_t)id0[g];
+                if (add)
+                    for (const SpanSrc& S : src[g]) for (int64_t i = 0; i < S.n; i++) S.ids[i] += add;
+            });
+    }
+    Py_END_ALLOW_THREADS
+    for (size_t g = 0; g < (size_t)ng; g++) {
+        if (rc[g] == 1) { PyErr_Format(PyExc_ValueError, "span %zd lies outside the buffer", (Py_ssize_t)bad[g]); break; }
+        if (rc[g] == 2) { PyErr_SetString(PyExc_OverflowError, "intern_groups: more than 2^31 distinct values"); break; }
+        if (rc[g] == 3) { PyErr_NoMemory(); break; }
+    }
+    if (!PyErr_Occurred() && n_uniq > (int64_t)INT32_MAX) PyErr_SetString(PyExc_OverflowError, "intern_groups: more than 2^31 distinct values");
+    if (!PyErr_Occurred() && oom) PyErr_NoMemory();
+    if (PyErr_Occurred()) { free(blob); free(poff); free(plen); return nullptr; }
+    PyObject* ob = owned(blob, (Py_ssize_t)n_bytes);
+    PyObject* oo = owned(poff, (Py_ssize_t)(n_uniq * 8));
+    PyObject* ol = owned(plen, (Py_ssize_t)(n_uniq * 4));
+    if (!ob || !oo || !ol) { Py_XDECREF(ob); Py_XDECREF(oo); Py_XDECREF(ol); return nullptr; }
+    return Py_BuildValue("(NNN)", ob, oo, ol);
+}
+
 PyMethodDef kMethods[] = {
     {"walk", walk, METH_VARARGS, "walk(seq, ints, interns, lens): fill column buffers from a list of tuples"},
     {"intern", intern, METH_VARARGS, "intern(((seq, field, int32 buffer), ...)) -> distinct values by first appearance; ids into the buffers"},
@@ -986,9 +1335,21 @@ PyMethodDef kMethods[] = {
     {"span_join", span_join, METH_VARARGS, "span_join(buf, off, len, picks, clips | None, out_len) -> bytes"},
     {"span_cplen", span_cplen, METH_VARARGS, "span_cplen(buf, off, len, out int32): len() of every string"},
     {"clip_join", clip_join, METH_VARARGS, "clip_join(table, picks, lens, out_len) -> bytes of table[picks[i]][:lens[i]] joined"},
+    {"walk_workdir", walk_workdir, METH_VARARGS, "walk_workdir(jobs, n_threads) -> [None | False | (n, end, [ints], [(off, len)], all_ascii, ordered)] per job, walked on threads without the GIL"},
+    {"intern_groups", intern_groups, METH_VARARGS, "intern_groups(groups, n_threads) -> (blob, off, len): the strings of each group by first appearance, one id space"},
     {nullptr, nullptr, 0, nullptr}};
 PyModuleDef kModule = {PyModuleDef_HEAD_INIT, "_cols_native", "task lists -> flat columns (cutesv_amd/columns.py)", -1, kMethods, nullptr, nullptr, nullptr, nullptr};
 
 }   // namespace
 
-PyMODINIT_FUNC PyInit__cols_native(void) { return PyModule_Create(&kModule); }
+PyMODINIT_FUNC PyInit__cols_native(void)
+{
+    OwnedType.tp_name = "_cols_native.Owned";
+    OwnedType.tp_basicsize = sizeof(OwnedObj);
+    OwnedType.tp_flags = Py_TPFLAGS_DEFAULT;
+    OwnedType.tp_dealloc = owned_dealloc;
+    OwnedType.tp_as_buffer = &owned_as_buffer;
+    OwnedType.tp_doc = "a read-write buffer over memory the walk allocated (freed with the object)";
+    if (PyType_Ready(&OwnedType) < 0) return nullptr;
+    return PyModule_Create(&kModule);
+}

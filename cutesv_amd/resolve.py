@@ -24,6 +24,8 @@ import logging
 import os
 import time
 
+import numpy as np
+
 from . import _abi, engine, rows as rows_mod
 from .columns import SigStore, Params, TYPES
 
@@ -434,6 +436,190 @@ def _one_tra_reads_table(work_dir, chrom, sigs_index, seg_of_store):
     rows = run_batch(store, [seg_of_store(store)], [("TRA", chrom)])[("TRA", chrom)]
     logging.info("Finished %s:TRA." % chrom)
     return (chrom, rows)
+
+
+# ------------------------------------------------------------------------------------------------ the whole phase in one call
+def phase3(work_dir, sigs_index, params, bam=None, devices=None, threads=None, lazy=True, ctx=None, contig_len=None):
+    """The reference's phase 3 (main script :1113-1199: the `with Pool(...)` block) in ONE call, without a pool, a broker or a
+    Python object per signature or per read -> {chr: rows}, the dict main_ctrl builds at :1191-1197: every chromosome of
+    sigs_index, in the order main_ctrl meets them, its rows extended in DEL, INS, INV, DUP, TRA order.
+    The work directory is read by SigStore.from_reference_workdir_native (the pickles walked in C on `threads` host threads,
+    the interpreter lock released) - the reads blocks only when params.genotype - and clustered by csv_cluster_batch, once per
+    device for the whole genome.
+      devices   GPUs to use (default: CUTESV_AMD_DEVICES, else this process's device_index()); with several, the chromosomes
+                are dealt out longest first (by signatures, and reads when genotyping), one host thread and one context each.
+      ctx       None: the call makes its own engine.Context per device and closes it; an object with cluster_batch: that
+                engine, for every task (devices then ignored); a callable device -> engine: one per device.
+      lazy      rows.LazyRows (list-like, backed by the result arrays; vcf.emit_stage reads them) or plain lists.
+    With several devices the results are joined into one, so every row - and vcf.emit_stage - reads one result.
+    TRA genotyping follows run_tra's CUTESV_AMD_TRA_GT: bam (default) - the calls are genotyped on the host from `bam` after
+    the batch (tra_bam.py) and the answer is written into the result's TRA calls; reads_table - on the GPU from the reads table (Params.genotype_tra; the reference lengths from
+    contig_len or the BAM header); off - '.' fields.
+    Call it in a process that has not forked a pool of GPU workers: the contexts are this process's own."""
+    import dataclasses
+    import threading
+    global _warned_tra
+    mode = os.environ.get("CUTESV_AMD_TRA_GT", "bam") if params.genotype else "off"
+    if mode not in ("bam", "reads_table", "off"):
+        raise ValueError("CUTESV_AMD_TRA_GT must be bam, reads_table or off")
+    has_tra = bool(sigs_index.get("TRA"))
+    if mode == "bam" and has_tra and bam is None:
+        raise ValueError("genotyping TRA calls from the BAM (CUTESV_AMD_TRA_GT=bam) needs bam=; or set CUTESV_AMD_TRA_GT to reads_table or off")
+    if mode == "reads_table" and has_tra and not _warned_tra:
+        logging.warning("TRA calls are genotyped from the reads table (CUTESV_AMD_TRA_GT=reads_table): DR / GT / PL can differ "
+                        "from cuteSV's BAM-based call_gt where secondary or low-mapq alignments overlap a breakpoint window")
+        _warned_tra = True
+    p = dataclasses.replace(params, genotype_tra=(mode == "reads_table"))
+    if not work_dir.endswith("/"):
+        work_dir += "/"
+    store = SigStore.from_reference_workdir_native(work_dir, sigs_index, contig_len=contig_len, threads=threads, reads=bool(p.genotype))
+    tasks = [(t, ch) for t in TYPES for ch in sigs_index.get(t, {}) if (t, ch) in store.seg_index]
+    if p.genotype_tra and store.contig_len is None and any(t == "TRA" for t, _ in tasks):
+        from .bam_header import reference_lengths
+        lens = reference_lengths(bam)
+        store.contig_len = np.array([lens[c] for c in store.chroms], np.int64)
+
+    if ctx is not None and hasattr(ctx, "cluster_batch"):
+        shards, make = [tasks], None
+    else:
+        devs = list(devices) if devices is not None else (device_list() or [device_index()])
+        shards = _deal_chromosomes(store, tasks, len(devs), p.genotype)
+        make = ctx if ctx is not None else engine.Context
+    parts, errors = [None] * len(shards), []
+
+    def run(k, shard):
+        own = None
+        try:
+            if make is None:
+                eng = ctx
+            else:
+                eng = own = make(devs[k])
+            hb = _batch_of(store, [store.segment(t, ch, p) for t, ch in shard])
+            res = eng.cluster_batch(hb, reuse=True)
+            parts[k] = (np.array(hb.segments, copy=True), res.snapshot())    # (ordinary memory: outlives the context and its next call)
+        except BaseException as e:                    # noqa: BLE001  (raised below, in the caller's thread)
+            errors.append(e)
+        finally:
+            if own is not None and hasattr(own, "close"):
+                own.close()
+
+    live = [(k, sh) for k, sh in enumerate(shards) if sh]
+    if len(live) == 1:
+        run(*live[0])
+    else:
+        ths = [threading.Thread(target=run, args=ks) for ks in live]
+        for th in ths:
+            th.start()
+        for th in ths:
+            th.join()
+    if errors:
+        raise errors[0]
+    # ONE result for the whole stage, whatever the number of devices: the devices' segments and calls back to back (a chromosome
+    # lies on one device, so its calls keep main_ctrl's order) - every row is then backed by it, and vcf.emit_stage writes it
+    done = [(k, sh) for k, sh in live]
+    order = [tc for _, sh in done for tc in sh]
+    segs, res = _merge_results([parts[k] for k, _ in done]) if done else (None, None)
+    if mode == "bam" and res is not None:
+        _genotype_tra_from_bam(store, segs, res, bam, p)
+    by_task = {}
+    if res is not None:
+        if lazy:
+            backing, ranges = rows_mod.lazy_rows_by_segment(store, segs, res)
+            by_task = {tc: rows_mod.LazyRows(backing, np.arange(lo, hi, dtype=np.int64)) for tc, (lo, hi) in zip(order, ranges)}
+        else:
+            by_task = dict(zip(order, rows_mod.rows_by_segment(store, segs, res)))
+    any_rows = next(iter(by_task.values()), None)
+    results = {}
+    for t in TYPES:                                   # main script :1116-1197: submission order, then results[chr].extend(rows)
+        for ch in sigs_index.get(t, {}):
+            if ch not in results:
+                results[ch] = rows_mod.LazyRows() if lazy else []
+                if lazy and any_rows is not None:
+                    results[ch].extend(rows_mod.LazyRows(any_rows.backing(), []))       # (every value backed: vcf.emit_stage)
+            rows = by_task.get((t, ch))
+            if rows is not None:                      # (a task without signatures returns before its log line: _one)
+                results[ch].extend(rows)
+                logging.info("Finished %s:%s." % (ch, t))
+    return results
+
+
+def _merge_results(parts):
+    """[(segments, HostResult)] of batches over ONE store -> (segments, HostResult) of all of them: segments back to back, calls
+    back to back with their segment, cluster and support-list offsets moved (support_sig holds store indices: unchanged)"""
+    if len(parts) == 1:
+        return parts[0]
+    r0 = parts[0][1]
+    segs = np.concatenate([s for s, _ in parts])
+    nc = sum(r.n_calls for _, r in parts)
+    ns = sum(r.n_support for _, r in parts)
+    out = _abi.HostResult(r0.n_sig, max(1, nc), max(1, ns), n_seg=max(1, len(segs)), narrow_support=r0.narrow_support,
+                          no_support=r0.no_support, coord32=r0.coord32, fields=r0.fields)
+    c0 = s0 = g0 = k0 = 0
+    for sg, r in parts:
+        t = r.trimmed()
+        n = r.n_calls
+        for name, _, cap in _abi._OUT_ARRAYS:
+            dst, src = out.arrays.get(name), t.get(name)
+            if dst is None or src is None or cap == "sig":
+                continue
+            if cap == "calls":
+                dst[c0:c0 + n] = src
+            elif cap == "calls+1":
+                dst[c0:c0 + n + 1] = src + s0
+            elif cap == "support":
+                dst[s0:s0 + r.n_support] = src
+            elif cap == "seg":
+                dst[g0:g0 + len(sg)] = src[:len(sg)]
+        out.arrays["call_seg"][c0:c0 + n] += g0
+        if out.arrays.get("call_cluster") is not None:
+            out.arrays["call_cluster"][c0:c0 + n] += k0
+        c0, s0, g0, k0 = c0 + n, s0 + r.n_support, g0 + len(sg), k0 + r.n_clusters
+    out.c.n_calls, out.c.n_support, out.c.n_clusters = nc, ns, k0
+    out.n_seg_used = len(segs)
+    return segs, out
+
+
+def _genotype_tra_from_bam(store, segs, res, bam, p):
+    """CUTESV_AMD_TRA_GT=bam: the TRA calls genotyped on the host from the BAM (tra_bam.genotype_rows: cuteSV_resolveTRA.py:258-309)
+    and the answer written into the result - DR, and the GL table index of (DR, DV), -1 where count_coverage gave up - with
+    the TRA segments marked as genotyped: the rows and the VCF records are then built from it like those of any genotyped call"""
+    from .tra_bam import genotype_rows
+    from .genotype import gl_index
+    n = res.n_calls
+    tra_seg = np.flatnonzero(segs["svtype"] == _abi.TRA)
+    idx = np.flatnonzero(np.isin(res.arrays["call_seg"][:n], tra_seg))
+    if not len(idx):
+        return
+    rows = rows_mod.RowsBacking(store, segs, res).build(idx)           # (the '.' fields: the segments are not genotyped yet)
+    got = genotype_rows(rows, bam, p.max_cluster_bias_TRA, p.gt_round)
+    for c, g in zip(idx.tolist(), got):
+        if g[6] == ".":
+            res.arrays["gl_idx"][c] = -1
+        else:
+            res.arrays["dr"][c] = int(g[6])
+            res.arrays["gl_idx"][c] = gl_index(int(g[6]), int(g[5]))
+    segs["genotype"][tra_seg] = 1
+
+
+def _deal_chromosomes(store, tasks, n, genotype):
+    """tasks -> n lists: whole chromosomes, heaviest first onto the least loaded device (longest processing time first); each
+    list keeps the order of `tasks`"""
+    if n <= 1:
+        return [list(tasks)]
+    cost = {}
+    for t, ch in tasks:
+        beg, end = store.seg_index[(t, ch)]
+        cost[ch] = cost.get(ch, 0) + (end - beg)
+    if genotype and store.reads_off is not None:
+        for ch in cost:
+            c = store.chroms.index(ch)
+            cost[ch] += int(store.reads_off[c + 1] - store.reads_off[c])
+    load, where = [0] * n, {}
+    for ch in sorted(cost, key=lambda c: (-cost[c], c)):
+        k = min(range(n), key=lambda i: (load[i], i))
+        where[ch] = k
+        load[k] += cost[ch]
+    return [[tc for tc in tasks if where[tc[1]] == k] for k in range(n)]
 
 
 # ------------------------------------------------------------------------------------------------ the caller, restated
