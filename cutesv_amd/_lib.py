@@ -46,6 +46,13 @@ SYMBOLS = [
     ("csv_pool_rows", C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
     ("csv_pool_append", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("csv_vcf_emit", C.c_int, None),           # prototype set in cutesv_amd/vcf.py (needs its struct)
+    ("csv_bam_open", C.c_int, [C.c_char_p, C.c_int, C.POINTER(C.c_void_p), C.c_char_p, C.c_int]),
+    ("csv_bam_close", None, [C.c_void_p]),
+    ("csv_bam_error", C.c_char_p, [C.c_void_p]),
+    ("csv_bam_header", C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]),
+    ("csv_bam_read", C.c_int, None),           # prototype set in cutesv_amd/bam.py (needs its struct)
+    ("csv_bam_struct_size", C.c_int, [C.c_int]),
+    ("csv_bam_decode", C.c_int, None),         # prototype set in cutesv_amd/bam.py
     ("csv_fasta_index", C.c_int64, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
 ]
 

@@ -1,0 +1,364 @@
+"""Native BAM reader: a coordinate-sorted .bam -> the columns the extraction kernels take, without
+pysam and without a Python object per record.
+
+`BamFile` is the host side (cutesv_amd/csrc/bam_host.cpp: BGZF inflate on host threads with the interpreter lock released,
+header, record framing, region scan without an index).  It hands out `Chunk`s: the slim image that goes to the device (per
+record the 32 fixed bytes, the CIGAR words and the aux bytes) and the host image that stays behind (read names and 4-bit
+sequences, sliced only for the records somebody asks for).  `decode(ctx, chunk)` is the face of `csv_bam_decode`
+(bam.hip.h); `decode_host(chunk)` is the same function in numpy / Python - the CPU path, and what the tests compare the
+kernels with.
+
+    python -m cutesv_amd.bam FILE [--chrom C] [--dump-columns DIR]
+"""
+import ctypes as C
+import os
+
+import numpy as np
+
+from . import _abi
+from ._lib import lib
+
+ALL = 1 << 62                              # "no bound" of a region
+
+
+class BamError(ValueError):
+    pass
+
+
+class ChunkC(C.Structure):
+    _fields_ = [("n_records", C.c_int64), ("more", C.c_int32), ("reserved", C.c_int32), ("slim", C.c_void_p), ("slim_bytes", C.c_int64),
+                ("rec_off", C.c_void_p), ("rec_len", C.c_void_p), ("host", C.c_void_p), ("host_bytes", C.c_int64), ("host_off", C.c_void_p),
+                ("record_bytes", C.c_int64), ("inflated_bytes", C.c_int64), ("compressed_bytes", C.c_int64), ("ms_inflate", C.c_double),
+                ("ms_frame", C.c_double)]
+
+
+class BamIn(C.Structure):
+    _fields_ = [("n_records", C.c_int64), ("slim", C.c_void_p), ("slim_bytes", C.c_int64), ("rec_off", C.c_void_p), ("rec_len", C.c_void_p),
+                ("flags", C.c_int32), ("reserved", C.c_int32)]
+
+
+# per-record columns of csv_bam_out, in its order: (name, dtype, length class: n = records, n1 = records + 1, o = operations, s = SA tags)
+_OUT = [("ref_start", np.int64, "n"), ("ref_end", np.int64, "n"), ("flag", np.int32, "n"), ("mapq", np.int32, "n"), ("query_len", np.int32, "n"),
+        ("clip_left", np.int32, "n"), ("clip_right", np.int32, "n"), ("cls", np.uint8, "n"), ("status", np.uint8, "n"),
+        ("cig_off", np.int64, "n1"), ("cigar", np.uint32, "o"), ("sa_off", np.int64, "n1"), ("sa_beg", np.int64, "s"), ("sa_end", np.int64, "s"),
+        ("cg_beg", np.int64, "n"), ("cg_end", np.int64, "n")]
+_DEV = ["dev_ref_start", "dev_ref_end", "dev_flag", "dev_mapq", "dev_query_len", "dev_clip_left", "dev_clip_right", "dev_cls", "dev_cig_off", "dev_cigar"]
+
+
+class BamOut(C.Structure):
+    _fields_ = ([("cap_ops", C.c_int64), ("cap_sa", C.c_int64), ("n_ops", C.c_int64), ("n_sa", C.c_int64)] + [(n, C.c_void_p) for n, _, _ in _OUT]
+                + [(n, C.c_void_p) for n in _DEV] + [("bytes_uploaded", C.c_int64), ("n_bad", C.c_int64), ("ms_device", C.c_float), ("ms_upload", C.c_float)])
+
+
+def default_threads():
+    """host threads of the inflate: min(16, CPUs), the rule phase3 uses - never the whole machine's count"""
+    return max(1, min(16, os.cpu_count() or 1))
+
+
+def _from_ptr(ptr, count, dtype):
+    """a copy of `count` items of `dtype` at address `ptr` (the reader's arrays live only until its next call)"""
+    if not count:
+        return np.zeros(0, dtype)
+    buf = (C.c_char * (count * np.dtype(dtype).itemsize)).from_address(ptr)
+    return np.frombuffer(buf, dtype, count).copy()
+
+
+_NIBBLE = np.frombuffer(b"=ACMGRSVTWYHKDBN", np.uint8)
+
+
+class Chunk:
+    """the records one csv_bam_read handed out: `slim` / `rec_off` / `rec_len` go to the device, `host` / `host_off` stay"""
+
+    def __init__(self, chrom, refid, slim, rec_off, rec_len, host, host_off, more, stats):
+        self.chrom, self.refid, self.more, self.stats = chrom, refid, more, stats
+        self.slim, self.rec_off, self.rec_len, self.host, self.host_off = slim, rec_off, rec_len, host, host_off
+        self.n = len(rec_off)
+
+    def __len__(self):
+        return self.n
+
+    def _name_len(self, i):
+        return int(self.slim[int(self.rec_off[i]) + 8])                       # l_read_name, NUL included
+
+    def name(self, i):
+        h0 = int(self.host_off[i])
+        return self.host[h0 : h0 + self._name_len(i) - 1].tobytes().decode()
+
+    def sequence(self, i):
+        """the query sequence of record i, decoded from its 4 bits per base"""
+        off = int(self.rec_off[i])
+        l_seq = int(self.slim[off + 16 : off + 20].view(np.uint32)[0])
+        h0 = int(self.host_off[i]) + self._name_len(i)
+        packed = self.host[h0 : h0 + (l_seq + 1) // 2]
+        both = np.empty(2 * len(packed), np.uint8)
+        both[0::2] = packed >> 4
+        both[1::2] = packed & 15
+        return _NIBBLE[both[:l_seq]].tobytes().decode()
+
+    def text(self, beg, end):
+        """bytes [beg, end) of the slim image as text (an SA value)"""
+        return self.slim[int(beg) : int(end)].tobytes().decode()
+
+    def sa_values(self, cols, i):
+        """the values of record i's SA tags, in tag order"""
+        return [self.text(cols["sa_beg"][k], cols["sa_end"][k]) for k in range(int(cols["sa_off"][i]), int(cols["sa_off"][i + 1]))]
+
+
+class BamFile:
+    """A coordinate-sorted BAM file.  `.references`, `.lengths`, `.header_text`; `.chunks(chrom)` iterates a contig in file
+    order, `.records(chrom, start, end)` returns the records that overlap a region (what pysam's fetch yields), found by
+    a forward scan that stops at the first record starting at or after `end`: no index file is needed."""
+
+    def __init__(self, path, threads=None):
+        L = self._L = lib()
+        L.csv_bam_read.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.POINTER(ChunkC)]
+        self._h = C.c_void_p()
+        self.threads = default_threads() if threads is None else max(1, int(threads))
+        err = C.create_string_buffer(512)
+        rc = L.csv_bam_open(os.fsencode(path), self.threads, C.byref(self._h), err, len(err))
+        if rc:
+            self._h = C.c_void_p()
+            raise BamError("%s: %s" % (path, err.value.decode(errors="replace") or "cannot be read"))
+        n_ref, names, lengths, text, text_len = C.c_int32(), C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_int64()
+        L.csv_bam_header(self._h, C.byref(n_ref), C.byref(names), C.byref(lengths), C.byref(text), C.byref(text_len))
+        self.header_text = C.string_at(text.value, text_len.value).decode(errors="replace") if text_len.value else ""
+        self.lengths = _from_ptr(lengths.value, n_ref.value, np.int64).tolist()
+        self.references, p = [], names.value
+        for _ in range(n_ref.value):
+            s = C.string_at(p)
+            self.references.append(s.decode()); p += len(s) + 1
+        self._refid = {r: i for i, r in enumerate(self.references)}
+        self.path = path
+        hd = [ln for ln in self.header_text.split("\n") if ln.startswith("@HD")]
+        so = [f[3:] for ln in hd for f in ln.split("\t") if f.startswith("SO:")]
+        self.sort_order = so[0] if so else None
+        if self.sort_order != "coordinate":
+            self.close()
+            raise BamError("%s: the header says SO:%s; a coordinate-sorted file is needed (samtools sort)" % (path, self.sort_order or "<missing>"))
+
+    def close(self):
+        if self._h:
+            self._L.csv_bam_close(self._h)
+            self._h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def refid(self, chrom):
+        """chrom: a reference name, or None for the unmapped tail (refID -1)"""
+        if chrom is None:
+            return -1
+        if chrom not in self._refid:
+            raise KeyError("no reference %r in %s" % (chrom, self.path))
+        return self._refid[chrom]
+
+    def _read(self, chrom, beg, end, max_records, flags):
+        cc = ChunkC()
+        refid = self.refid(chrom)
+        rc = self._L.csv_bam_read(self._h, refid, int(beg), int(end), int(max_records), int(flags), C.byref(cc))
+        if rc:
+            raise BamError("%s: %s" % (self.path, (self._L.csv_bam_error(self._h) or b"").decode(errors="replace")))
+        n = int(cc.n_records)
+        stats = dict(n_records=n, record_bytes=int(cc.record_bytes), inflated_bytes=int(cc.inflated_bytes), compressed_bytes=int(cc.compressed_bytes),
+                     slim_bytes=int(cc.slim_bytes), ms_inflate=float(cc.ms_inflate), ms_frame=float(cc.ms_frame))
+        if flags & _abi.BAM_COUNT_ONLY:
+            return n, bool(cc.more)
+        # bytes that cross PCIe per record (image + offset + length) next to the inflated bytes of the record
+        stats["upload_bytes_per_record"] = (int(cc.slim_bytes) + 12 * n) / n if n else 0.0
+        stats["inflated_bytes_per_record"] = int(cc.record_bytes) / n if n else 0.0
+        return Chunk(chrom, refid, _from_ptr(cc.slim, int(cc.slim_bytes), np.uint8), _from_ptr(cc.rec_off, n, np.int64), _from_ptr(cc.rec_len, n, np.uint32),
+                     _from_ptr(cc.host, int(cc.host_bytes), np.uint8), _from_ptr(cc.host_off, n + 1, np.int64), bool(cc.more), stats)
+
+    def chunks(self, chrom, chunk_records=65536, start=-ALL, end=ALL):
+        """the records of `chrom` (None: the unmapped tail) in file order, at most chunk_records per Chunk"""
+        flags = _abi.BAM_RESTART
+        while True:
+            ch = self._read(chrom, start, end, chunk_records, flags)
+            if ch.n:
+                yield ch
+            if not ch.more:
+                return
+            flags = 0
+
+    def records(self, chrom, start, end):
+        """one Chunk with the records of `chrom` that overlap [start, end): what fetch(chrom, start, end) yields, in its order"""
+        return self._read(chrom, start, end, (1 << 31) - 8192, _abi.BAM_RESTART)
+
+    def count(self, chrom):
+        total, flags = 0, _abi.BAM_RESTART | _abi.BAM_COUNT_ONLY
+        while True:
+            n, more = self._read(chrom, -ALL, ALL, 1 << 30, flags)
+            total += n
+            if not more:
+                return total
+            flags = _abi.BAM_COUNT_ONLY
+
+
+# ------------------------------------------------------------------------------------ decode: device
+def decode(ctx, chunk, host_outputs=True):
+    """csv_bam_decode on a Chunk -> dict of the columns of csv_bam_out (+ n_ops, n_sa, ms_device, ms_upload, bytes_uploaded).
+    The columns also stay in the context's device memory until its next decode: extract.cigar_signatures(..., from_bam=True)
+    scans them there.  host_outputs=False: only the small per-record columns come back (no CIGAR array)."""
+    L = lib()
+    L.csv_bam_decode.restype = C.c_int
+    L.csv_bam_decode.argtypes = [C.c_void_p, C.POINTER(BamIn), C.POINTER(BamOut)]
+    n = chunk.n
+    slim, rec_off, rec_len = np.ascontiguousarray(chunk.slim, np.uint8), np.ascontiguousarray(chunk.rec_off, np.int64), np.ascontiguousarray(chunk.rec_len, np.uint32)
+    bin_ = BamIn(n_records=n, slim=slim.ctypes.data if len(slim) else None, slim_bytes=len(slim), rec_off=rec_off.ctypes.data if n else None,
+                 rec_len=rec_len.ctypes.data if n else None)
+    bound = len(slim) // 4 + 1                            # an operation or an SA tag takes at least 4 bytes of the image
+    size = dict(n=n, n1=n + 1, o=bound if host_outputs else 0, s=bound)
+    arrs = {name: np.zeros(size[k], dt) if k in ("n", "n1") else np.empty(size[k], dt) for name, dt, k in _OUT}
+    out = BamOut(cap_ops=size["o"], cap_sa=size["s"], **{k: (v.ctypes.data if len(v) else None) for k, v in arrs.items()})
+    rc = L.csv_bam_decode(ctx._h, C.byref(bin_), C.byref(out))
+    ctx._check(rc)
+    cut = dict(n=n, n1=n + 1, o=int(out.n_ops) if host_outputs else 0, s=int(out.n_sa))
+    cols = {name: (arrs[name][:cut[k]].copy() if k in ("o", "s") else arrs[name]) for name, _, k in _OUT}
+    cols.update(n_ops=int(out.n_ops), n_sa=int(out.n_sa), ms_device=float(out.ms_device), ms_upload=float(out.ms_upload),
+                bytes_uploaded=int(out.bytes_uploaded), on_device=True)
+    return cols
+
+
+# ------------------------------------------------------------------------------------ decode: host
+_AUX_SIZE = {ord("A"): 1, ord("c"): 1, ord("C"): 1, ord("s"): 2, ord("S"): 2, ord("i"): 4, ord("I"): 4, ord("f"): 4}
+_REF_OPS = (0, 2, 3, 7, 8)                                 # M D N = X
+
+
+def _aux_walk(s, p, end):
+    """the tags of the aux area [p, end) of the bytes `s`: [(key, type, subtype, value begin, value end)], well-formed"""
+    tags = []
+    while p < end:
+        if end - p < 3:
+            return tags, False
+        key, typ = s[p : p + 2], s[p + 2]
+        p += 3
+        sub = 0
+        if typ in _AUX_SIZE:
+            b, e = p, p + _AUX_SIZE[typ]
+            if e > end:
+                return tags, False
+            p = e
+        elif typ in (ord("Z"), ord("H")):
+            q = s.find(b"\0", p, end)
+            if q < 0:
+                return tags, False
+            b, e, p = p, q, q + 1
+        elif typ == ord("B"):
+            if end - p < 5:
+                return tags, False
+            sub = s[p]
+            cnt = int.from_bytes(s[p + 1 : p + 5], "little")
+            if sub not in _AUX_SIZE or sub == ord("A"):
+                return tags, False
+            p += 5
+            if cnt > (end - p) // _AUX_SIZE[sub]:
+                return tags, False
+            b, e = p, p + cnt * _AUX_SIZE[sub]
+            p = e
+        else:
+            return tags, False
+        tags.append((key, typ, sub, b, e))
+    return tags, True
+
+
+def decode_host(chunk, check=True):
+    """What csv_bam_decode computes, in numpy (fixed fields) and Python (aux walk, CIGAR): the same dict of columns.
+    check: raise BamError when a record is malformed (status != 0), as the device entry fails with E_INVALID."""
+    n = chunk.n
+    s = chunk.slim.tobytes()
+    w = chunk.slim[: len(chunk.slim) // 4 * 4].view(np.uint32)
+    base = (chunk.rec_off // 4).astype(np.int64)
+    fld = lambda k: w[base + k] if n else np.zeros(0, np.uint32)                   # noqa: E731
+    pos = fld(1).astype(np.int32).astype(np.int64)
+    flag = (fld(3) >> 16).astype(np.int32)
+    cols = dict(ref_start=pos, flag=flag, mapq=((fld(2) >> 8) & 255).astype(np.int32), query_len=fld(4).astype(np.int32),
+                cls=np.where((flag == 256) | (flag == 272), 0, np.where((flag == 0) | (flag == 16), 1, 2)).astype(np.uint8))
+    n_cig = (fld(3) & 0xFFFF).astype(np.int64)
+    l_seq = fld(4).astype(np.int64)
+    ref_end, cl, cr = np.zeros(n, np.int64), np.zeros(n, np.int32), np.zeros(n, np.int32)
+    status, cg_beg, cg_end = np.zeros(n, np.uint8), np.full(n, -1, np.int64), np.full(n, -1, np.int64)
+    cig_off, sa_off = np.zeros(n + 1, np.int64), np.zeros(n + 1, np.int64)
+    cig_parts, sa_beg, sa_end = [], [], []
+    for i in range(n):
+        off, ln, nc = int(chunk.rec_off[i]), int(chunk.rec_len[i]), int(n_cig[i])
+        if 32 + 4 * nc > ln:
+            status[i] |= 2
+            nc = 0
+        tags, ok = _aux_walk(s, off + 32 + 4 * nc, off + ln)
+        if not ok:
+            status[i] |= 1
+        src, n_ops = off + 32, nc
+        for key, typ, sub, b, e in tags:
+            if key == b"SA" and typ == ord("Z"):
+                sa_beg.append(b); sa_end.append(e)
+            elif key == b"CG" and typ == ord("B") and sub == ord("I") and cg_beg[i] < 0:
+                cg_beg[i], cg_end[i] = b, e
+        if nc == 2 and cg_beg[i] >= 0:
+            op0, op1 = int(w[off // 4 + 8]), int(w[off // 4 + 9])
+            if op0 & 15 == 4 and op0 >> 4 == int(l_seq[i]) and op1 & 15 == 3:
+                src, n_ops = int(cg_beg[i]), int(cg_end[i] - cg_beg[i]) // 4
+        ops = np.frombuffer(s, np.uint32, n_ops, src) if n_ops else np.zeros(0, np.uint32)
+        cig_parts.append(ops)
+        cig_off[i + 1] = cig_off[i] + n_ops
+        sa_off[i + 1] = len(sa_beg)
+        ref_end[i] = pos[i] + int((ops >> 4)[np.isin(ops & 15, _REF_OPS)].sum(dtype=np.int64))
+        if n_ops:
+            if int(ops[0]) & 15 in (4, 5):
+                cl[i] = int(ops[0]) >> 4
+            if int(ops[-1]) & 15 in (4, 5):
+                cr[i] = int(ops[-1]) >> 4
+    cols.update(ref_end=ref_end, clip_left=cl, clip_right=cr, status=status, cig_off=cig_off,
+                cigar=np.concatenate(cig_parts) if cig_parts else np.zeros(0, np.uint32), sa_off=sa_off,
+                sa_beg=np.asarray(sa_beg, np.int64), sa_end=np.asarray(sa_end, np.int64), cg_beg=cg_beg, cg_end=cg_end)
+    cols.update(n_ops=int(cig_off[-1]), n_sa=len(sa_beg), on_device=False)
+    if check and status.any():
+        raise BamError("%d record(s) of the chunk have a malformed aux area or CIGAR (first: record %d)" % (int((status != 0).sum()), int(np.flatnonzero(status)[0])))
+    return cols
+
+
+COLUMNS = tuple(name for name, _, _ in _OUT)
+
+
+# ------------------------------------------------------------------------------------ command line
+def main(argv=None):
+    import argparse
+    ap = argparse.ArgumentParser(prog="python -m cutesv_amd.bam", description="header and per-contig record counts of a coordinate-sorted BAM file")
+    ap.add_argument("bam")
+    ap.add_argument("--chrom", default=None, help="only this contig")
+    ap.add_argument("--threads", type=int, default=None, help="host threads of the inflate (default: min(16, CPUs))")
+    ap.add_argument("--dump-columns", metavar="DIR", default=None, help="write the decoded columns of --chrom (host decode) as DIR/<column>.npy")
+    a = ap.parse_args(argv)
+    with BamFile(a.bam, threads=a.threads) as bf:
+        print(bf.header_text.rstrip("\n"))
+        names = [a.chrom] if a.chrom is not None else list(bf.references) + [None]
+        for name in names:
+            print("%s\t%d" % ("*" if name is None else name, bf.count(name)))
+        if a.dump_columns:
+            if a.chrom is None:
+                ap.error("--dump-columns needs --chrom")
+            os.makedirs(a.dump_columns, exist_ok=True)
+            parts = [decode_host(ch, check=False) for ch in bf.chunks(a.chrom)]
+            for k in COLUMNS:
+                if k in ("cig_off", "sa_off"):              # offsets restart in every chunk: made global here
+                    tot, pieces = 0, [np.zeros(1, np.int64)]
+                    for c in parts:
+                        pieces.append(c[k][1:] + tot); tot += int(c[k][-1])
+                    arr = np.concatenate(pieces)
+                else:
+                    arr = np.concatenate([c[k] for c in parts]) if parts else np.zeros(0)
+                np.save(os.path.join(a.dump_columns, k + ".npy"), arr)
+            print("wrote %d columns to %s" % (len(COLUMNS), a.dump_columns))
+    return 0
+
+
+if __name__ == "__main__":
+    raise SystemExit(main())

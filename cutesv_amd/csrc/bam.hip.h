@@ -1,0 +1,229 @@
+// bam.hip.h — BAM alignment records -> the columns of the extraction step, on the GPU.
+//
+// Input: the slim image the host packs while it frames the records (bam_host.cpp): per record the 32 fixed bytes after
+// block_size, the CIGAR words and the aux bytes, 16-byte aligned.  Field offsets are the SAM/BAM specification's (4.2):
+//   +0 refID  +4 pos  +8 l_read_name  +9 mapq  +10 bin  +12 n_cigar_op  +14 flag  +16 l_seq  +20 next_refID  +24 next_pos  +28 tlen
+//
+//   k_bam_fixed   one thread per record: fixed fields, flag class, aux walk (SA tags counted, CG:B,I found), the number of
+//                 CIGAR operations (the tag's when the record holds the <l_seq>S<n>N placeholder) and where they are
+//   k_bam_scan    one workgroup: operation counts -> cig_off, SA counts -> sa_off
+//   k_bam_cigar   one wavefront per record (up to BAM_WAVE_MAX operations): copies the words into the packed array - the
+//                 packed form IS BAM's oplen << 4 | op - and sums the reference span; 16-byte loads where the source is
+//                 aligned (always, outside a CG tag)
+//   k_bam_cigar_long   one workgroup per longer record (a list k_bam_fixed appends to)
+//   k_bam_sa      one thread per record with SA tags: the walk again, now writing the value ranges
+// Every byte a kernel reads lies inside [rec_off, rec_off + rec_len) of its record: the host entry checks those ranges
+// against the image, k_bam_fixed checks the CIGAR and every aux value against the record.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+namespace csv {
+
+constexpr int BAM_WAVE_MAX = 4096;          // operations a wavefront copies (64 steps of 64); longer records get a workgroup
+constexpr int BAM_ST_AUX = 1, BAM_ST_CIGAR = 2;
+
+struct BamArgs {
+    i64 n;
+    const uint8_t* slim;
+    const i64* rec_off;
+    const unsigned* rec_len;
+    i64* ref_start; i64* ref_end; int* flag; int* mapq; int* qlen; int* clip_l; int* clip_r; uint8_t* cls; uint8_t* status;
+    i64* cig_off;                   // n + 1: counts (k_bam_fixed), then exclusive offsets (k_bam_scan)
+    i64* sa_off;                    // n + 1: likewise, SA tags
+    i64* cig_src;                   // byte offset in slim of the record's operation words (the record's own, or the CG tag's)
+    i64* cg_beg; i64* cg_end;
+    unsigned* cigar;
+    i64* sa_beg; i64* sa_end;
+    int* long_list;                 // records with more than BAM_WAVE_MAX operations
+    int* counters;                  // [0] entries of long_list, [1] records with status != 0
+    i64* totals;                    // [0] operations, [1] SA tags
+};
+
+struct AuxTag { int k0, k1, type, sub; i64 vbeg, vend; };
+
+// the next tag of the aux area [p, end) of `s`: 1 = read (p moves behind it), 0 = end of the area, -1 = malformed (an
+// unknown type byte or a value that does not end inside the area).  Never reads at or beyond `end`.
+__device__ __forceinline__ int aux_next(const uint8_t* s, i64& p, const i64 end, AuxTag& t)
+{
+    if (p >= end) return 0;
+    if (end - p < 3) return -1;
+    t.k0 = s[p]; t.k1 = s[p + 1]; t.type = s[p + 2]; t.sub = 0;
+    p += 3;
+    i64 sz = 0;
+    switch (t.type) {
+    case 'A': case 'c': case 'C': sz = 1; break;
+    case 's': case 'S': sz = 2; break;
+    case 'i': case 'I': case 'f': sz = 4; break;
+    case 'Z': case 'H': {
+        i64 q = p;
+        while (q < end && s[q]) q++;
+        if (q >= end) return -1;                             // no NUL inside the record
+        t.vbeg = p; t.vend = q; p = q + 1;
+        return 1;
+    }
+    case 'B': {
+        if (end - p < 5) return -1;
+        t.sub = s[p];
+        const i64 cnt = (i64)s[p + 1] | ((i64)s[p + 2] << 8) | ((i64)s[p + 3] << 16) | ((i64)s[p + 4] << 24);
+        i64 es;
+        switch (t.sub) {
+        case 'c': case 'C': es = 1; break;
+        case 's': case 'S': es = 2; break;
+        case 'i': case 'I': case 'f': es = 4; break;
+        default: return -1;
+        }
+        p += 5;
+        if (cnt > (end - p) / es) return -1;
+        t.vbeg = p; t.vend = p + cnt * es; p = t.vend;
+        return 1;
+    }
+    default: return -1;
+    }
+    if (end - p < sz) return -1;
+    t.vbeg = p; t.vend = p + sz; p += sz;
+    return 1;
+}
+
+__global__ __launch_bounds__(256) void k_bam_fixed(BamArgs A)
+{
+    const i64 i = (i64)blockIdx.x * 256 + threadIdx.x;
+    if (i >= A.n) return;
+    const i64 off = A.rec_off[i], len = A.rec_len[i];       // (host-checked: off % 16 == 0, len >= 32, off + len inside the image)
+    const unsigned* w = (const unsigned*)(A.slim + off);
+    const i64 pos = (int)w[1];
+    const int mapq = (int)((w[2] >> 8) & 255u);
+    int n_cig = (int)(w[3] & 0xffffu);
+    const int flag = (int)(w[3] >> 16);
+    const unsigned l_seq = w[4];
+    int st = 0;
+    if (32 + 4 * (i64)n_cig > len) { st = BAM_ST_CIGAR; n_cig = 0; }       // the CIGAR leaves the record: treated as empty, reported
+    i64 n_ops = n_cig, src = off + 32, cgb = -1, cge = -1;
+    int n_sa = 0;
+    i64 p = off + 32 + 4 * (i64)n_cig;
+    const i64 end = off + len;
+    AuxTag t;
+    int rc;
+    while ((rc = aux_next(A.slim, p, end, t)) == 1) {
+        if (t.k0 == 'S' && t.k1 == 'A' && t.type == 'Z') n_sa++;
+        else if (t.k0 == 'C' && t.k1 == 'G' && t.type == 'B' && t.sub == 'I' && cgb < 0) { cgb = t.vbeg; cge = t.vend; }
+    }
+    if (rc < 0) st |= BAM_ST_AUX;
+    // more than 65 535 operations: the record holds <l_seq>S<reference length>N and the real CIGAR is the CG array (SAM spec 4.2.2)
+    if (n_cig == 2 && cgb >= 0 && (w[8] & 15u) == 4u && (w[8] >> 4) == l_seq && (w[9] & 15u) == 3u) { n_ops = (cge - cgb) >> 2; src = cgb; }
+    A.ref_start[i] = pos; A.flag[i] = flag; A.mapq[i] = mapq; A.qlen[i] = (int)l_seq;
+    A.cls[i] = (flag == 256 || flag == 272) ? 0 : (flag == 0 || flag == 16) ? 1 : 2;
+    A.status[i] = (uint8_t)st;
+    A.cig_off[i] = n_ops; A.sa_off[i] = n_sa; A.cig_src[i] = src; A.cg_beg[i] = cgb; A.cg_end[i] = cge;
+    if (n_ops > BAM_WAVE_MAX) A.long_list[atomicAdd(&A.counters[0], 1)] = (int)i;
+    if (st) atomicAdd(&A.counters[1], 1);
+}
+
+// counts -> exclusive offsets, both columns, in place; one workgroup of 1024: thread t owns a contiguous span of records
+__global__ __launch_bounds__(1024) void k_bam_scan(BamArgs A)
+{
+    __shared__ i64 ws[2][16];
+    const int t = threadIdx.x;
+    const i64 per = (A.n + 1023) / 1024, b = (i64)t * per < A.n ? (i64)t * per : A.n, e = b + per < A.n ? b + per : A.n;
+    i64 s0 = 0, s1 = 0;
+    for (i64 i = b; i < e; i++) { s0 += A.cig_off[i]; s1 += A.sa_off[i]; }
+    const i64 i0 = wave_incl_scan_i64(s0), i1 = wave_incl_scan_i64(s1);
+    if ((t & 63) == 63) { ws[0][t >> 6] = i0; ws[1][t >> 6] = i1; }
+    __syncthreads();
+    i64 o0 = i0 - s0, o1 = i1 - s1, tot0 = 0, tot1 = 0;
+    for (int q = 0; q < 16; q++) {
+        if (q < (t >> 6)) { o0 += ws[0][q]; o1 += ws[1][q]; }
+        tot0 += ws[0][q]; tot1 += ws[1][q];
+    }
+    for (i64 i = b; i < e; i++) {
+        const i64 c0 = A.cig_off[i], c1 = A.sa_off[i];
+        A.cig_off[i] = o0; A.sa_off[i] = o1;
+        o0 += c0; o1 += c1;
+    }
+    if (t == 0) { A.cig_off[A.n] = tot0; A.sa_off[A.n] = tot1; A.totals[0] = tot0; A.totals[1] = tot1; }
+}
+
+__device__ __forceinline__ i64 ref_len_of(unsigned w)
+{
+    const unsigned op = w & 15u;
+    return (op == 0u || op == 2u || op == 3u || op == 7u || op == 8u) ? (i64)(w >> 4) : 0;     // M D N = X
+}
+
+__device__ __forceinline__ unsigned load_op(const uint8_t* s, i64 at)          // an operation word at any byte alignment
+{
+    if ((at & 3) == 0) return *(const unsigned*)(s + at);
+    return (unsigned)s[at] | ((unsigned)s[at + 1] << 8) | ((unsigned)s[at + 2] << 16) | ((unsigned)s[at + 3] << 24);
+}
+
+// threads t of nt copy the n operation words at byte `src` of the image to dst; returns this thread's share of the reference span
+__device__ __forceinline__ i64 copy_ops(const uint8_t* slim, i64 src, unsigned* dst, i64 n, int t, int nt)
+{
+    i64 span = 0;
+    if ((src & 15) == 0) {                                   // 16 bytes per lane: a wavefront moves 1 KiB per step
+        const uint4* s4 = (const uint4*)(slim + src);
+        const i64 n4 = n >> 2;
+        for (i64 k = t; k < n4; k += nt) {
+            const uint4 v = s4[k];
+            dst[4 * k] = v.x; dst[4 * k + 1] = v.y; dst[4 * k + 2] = v.z; dst[4 * k + 3] = v.w;
+            span += ref_len_of(v.x) + ref_len_of(v.y) + ref_len_of(v.z) + ref_len_of(v.w);
+        }
+        const unsigned* s1 = (const unsigned*)(slim + src);
+        for (i64 k = 4 * n4 + t; k < n; k += nt) { const unsigned v = s1[k]; dst[k] = v; span += ref_len_of(v); }
+    } else {                                                 // a CG array sits wherever the tags before it end
+        for (i64 k = t; k < n; k += nt) { const unsigned v = load_op(slim, src + 4 * k); dst[k] = v; span += ref_len_of(v); }
+    }
+    return span;
+}
+
+__device__ __forceinline__ void bam_finish(const BamArgs& A, i64 r, i64 n_ops, i64 src, i64 span)
+{
+    int cl = 0, cr = 0;
+    if (n_ops > 0) {
+        const unsigned f = load_op(A.slim, src), l = load_op(A.slim, src + 4 * (n_ops - 1));
+        if ((f & 15u) == 4u || (f & 15u) == 5u) cl = (int)(f >> 4);            // S, or the H that replaces it
+        if ((l & 15u) == 4u || (l & 15u) == 5u) cr = (int)(l >> 4);
+    }
+    A.ref_end[r] = A.ref_start[r] + span; A.clip_l[r] = cl; A.clip_r[r] = cr;
+}
+
+__global__ __launch_bounds__(256) void k_bam_cigar(BamArgs A)
+{
+    const i64 wave = ((i64)blockIdx.x * 256 + threadIdx.x) >> 6, nwaves = ((i64)gridDim.x * 256) >> 6;
+    const int lane = lane_id();
+    for (i64 r = wave; r < A.n; r += nwaves) {
+        const i64 c0 = A.cig_off[r], n_ops = A.cig_off[r + 1] - c0;
+        if (n_ops > BAM_WAVE_MAX) continue;                  // k_bam_cigar_long's
+        const i64 src = A.cig_src[r];
+        const i64 span = wave_sum_i64(copy_ops(A.slim, src, A.cigar + c0, n_ops, lane, 64));
+        if (lane == 0) bam_finish(A, r, n_ops, src, span);
+    }
+}
+
+__global__ __launch_bounds__(256) void k_bam_cigar_long(BamArgs A)
+{
+    __shared__ i64 sh[4];
+    const i64 r = A.long_list[blockIdx.x];
+    const i64 c0 = A.cig_off[r], n_ops = A.cig_off[r + 1] - c0, src = A.cig_src[r];
+    const i64 part = wave_sum_i64(copy_ops(A.slim, src, A.cigar + c0, n_ops, (int)threadIdx.x, 256));
+    if (lane_id() == 0) sh[threadIdx.x >> 6] = part;
+    __syncthreads();
+    if (threadIdx.x == 0) bam_finish(A, r, n_ops, src, sh[0] + sh[1] + sh[2] + sh[3]);
+}
+
+__global__ __launch_bounds__(256) void k_bam_sa(BamArgs A)
+{
+    const i64 i = (i64)blockIdx.x * 256 + threadIdx.x;
+    if (i >= A.n) return;
+    i64 o = A.sa_off[i];
+    const i64 o_end = A.sa_off[i + 1];
+    if (o_end <= o) return;
+    const i64 off = A.rec_off[i], end = off + A.rec_len[i];
+    const unsigned* w = (const unsigned*)(A.slim + off);
+    i64 p = off + 32 + 4 * (i64)(w[3] & 0xffffu);           // (the CIGAR fits: a record where it does not has no SA count)
+    if (A.status[i] & BAM_ST_CIGAR) p = off + 32;
+    AuxTag t;
+    while (o < o_end && aux_next(A.slim, p, end, t) == 1)
+        if (t.k0 == 'S' && t.k1 == 'A' && t.type == 'Z') { A.sa_beg[o] = t.vbeg; A.sa_end[o] = t.vend; o++; }
+}
+
+}  // namespace csv

@@ -1,0 +1,373 @@
+// bam_host.cpp — the host side of the native BAM reader: BGZF inflate on host threads, the BAM
+// header, record framing, region scan and the slim image the decode kernels (bam.hip.h) take.
+//
+// Written from the SAM/BAM specification (SAMv1, sections 4.1 "The BGZF compression format" and 4.2 "The BAM format"):
+//   BGZF block  = gzip member with one extra subfield 'B','C' (u16 BSIZE = block size - 1), raw deflate payload, CRC32, ISIZE
+//   BAM         = "BAM\1", l_text, text, n_ref, {l_name, name, l_ref} * n_ref, then records
+//   record      = block_size, then block_size bytes: refID pos l_read_name mapq bin n_cigar_op flag l_seq next_refID
+//                 next_pos tlen (32 bytes), read_name, cigar (u32 * n_cigar_op), seq ((l_seq + 1) / 2), qual (l_seq), aux
+// No index is used: a region is a forward scan over the sorted records with an early exit.  What goes to the device per
+// record is the slim image {32 fixed bytes, CIGAR words, aux bytes}; the read name and the 4-bit sequence stay in a host
+// buffer; the qualities are dropped.
+#include <stdint.h>
+#include <stdio.h>
+#include <string.h>
+#include <sys/mman.h>
+#include <sys/stat.h>
+#include <fcntl.h>
+#include <unistd.h>
+#include <zlib.h>
+
+#include <algorithm>
+#include <atomic>
+#include <chrono>
+#include <map>
+#include <string>
+#include <thread>
+#include <vector>
+
+#include "../../include/cutesv_hip.h"
+
+namespace {
+
+typedef int64_t i64;
+
+inline uint32_t rd_u32(const uint8_t* p) { uint32_t v; memcpy(&v, p, 4); return v; }     // (little-endian hosts only, as the rest of the library)
+inline int32_t  rd_i32(const uint8_t* p) { int32_t v; memcpy(&v, p, 4); return v; }
+inline uint16_t rd_u16(const uint8_t* p) { uint16_t v; memcpy(&v, p, 2); return v; }
+
+double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+
+struct Block { i64 coff; int32_t csize, hdr; uint32_t isize; i64 uoff; };      // coff: file offset, hdr: bytes before the deflate payload
+
+constexpr i64 SLIM_ALIGN = 16;               // a slim record starts 16-byte aligned: its CIGAR words (at + 32) are too
+constexpr int REFILL_BLOCKS = 256;           // BGZF blocks inflated per refill of the window (<= 16 MiB inflated)
+
+}  // namespace
+
+struct csv_bam {
+    int            fd = -1;
+    const uint8_t* map = nullptr;
+    i64            fsize = 0;
+    int            threads = 1;
+    std::string    err;
+    std::vector<Block> blocks;
+    i64            utotal = 0;
+    // header
+    std::string          text, names;       // names: NUL-terminated, back to back
+    std::vector<i64>     lengths;
+    int32_t              n_ref = 0;
+    i64                  first_rec = 0;      // uncompressed offset of the first record
+    // the inflated window [win_u0, win_u0 + win.size())
+    std::vector<uint8_t> win;
+    i64                  win_u0 = 0;
+    i64                  cur = 0;            // uncompressed offset of the next record
+    std::map<uint32_t, i64> contig_at;       // (uint32)refID -> offset of its first record, as found (-1 sorts last, as in a sorted file)
+    uint32_t             scanned_key = 0;    // every contig with a key <= this one that exists is in contig_at
+    bool                 scanned_any = false;
+    // the last region scan: its first record.  Records before it end at or before hint_beg, so a later region of the same
+    // contig that begins at or after hint_beg starts its scan there
+    uint32_t             hint_key = 0;
+    i64                  hint_beg = 0, hint_at = -1;
+    // the chunk handed out last
+    std::vector<uint8_t> slim, host;
+    std::vector<i64>     rec_off, host_off;
+    std::vector<uint32_t> rec_len;
+    double               ms_inflate = 0;
+    i64                  inflated = 0, compressed = 0;
+};
+
+namespace {
+
+int fail(csv_bam* b, int code, const char* fmt, const char* a = "", long long x = 0)
+{
+    char buf[512];
+    snprintf(buf, sizeof buf, fmt, a, x);
+    b->err = buf;
+    return code;
+}
+
+// the block table: one pass over the block headers of the mapped file
+int index_blocks(csv_bam* b)
+{
+    i64 o = 0, u = 0;
+    while (o < b->fsize) {
+        const uint8_t* p = b->map + o;
+        if (o + 18 > b->fsize) return fail(b, CSV_E_INVALID, "%struncated BGZF block header at byte %lld", "", (long long)o);
+        if (p[0] != 0x1f || p[1] != 0x8b || p[2] != 8 || !(p[3] & 4)) return fail(b, CSV_E_INVALID, "%snot a BGZF block at byte %lld", "", (long long)o);
+        const int xlen = rd_u16(p + 10);
+        if (o + 12 + xlen > b->fsize) return fail(b, CSV_E_INVALID, "%struncated BGZF block header at byte %lld", "", (long long)o);
+        int bsize = -1;
+        for (int x = 0; x + 4 <= xlen;) {                  // extra subfields: SI1 SI2 SLEN data
+            const uint8_t* s = p + 12 + x;
+            const int slen = rd_u16(s + 2);
+            if (s[0] == 'B' && s[1] == 'C' && slen == 2 && x + 6 <= xlen) bsize = rd_u16(s + 4);
+            x += 4 + slen;
+        }
+        if (bsize < 0) return fail(b, CSV_E_INVALID, "%sBGZF block without a BC subfield at byte %lld", "", (long long)o);
+        const i64 total = (i64)bsize + 1;
+        if (total < 12 + xlen + 8) return fail(b, CSV_E_INVALID, "%sBGZF block too short at byte %lld", "", (long long)o);
+        if (o + total > b->fsize) return fail(b, CSV_E_INVALID, "%struncated BGZF block at byte %lld", "", (long long)o);
+        Block k;
+        k.coff = o; k.csize = (int32_t)total; k.hdr = 12 + xlen; k.isize = rd_u32(p + total - 4); k.uoff = u;
+        if (k.isize > 65536) return fail(b, CSV_E_INVALID, "%sBGZF block inflates to more than 64 KiB at byte %lld", "", (long long)o);
+        b->blocks.push_back(k);
+        u += k.isize; o += total;
+    }
+    b->utotal = u;
+    if (b->blocks.empty() || b->blocks.back().isize != 0 || b->blocks.back().csize != 28)
+        return fail(b, CSV_E_INVALID, "%sthe BGZF end-of-file block is missing (truncated file?)", "");
+    return CSV_OK;
+}
+
+bool inflate_block(const csv_bam* b, const Block& k, uint8_t* dst)
+{
+    if (k.isize == 0) return true;
+    z_stream z;
+    memset(&z, 0, sizeof z);
+    if (inflateInit2(&z, -15) != Z_OK) return false;
+    z.next_in = const_cast<Bytef*>(b->map + k.coff + k.hdr);
+    z.avail_in = (uInt)(k.csize - k.hdr - 8);
+    z.next_out = dst; z.avail_out = k.isize;
+    const int rc = inflate(&z, Z_FINISH);
+    const bool ok = rc == Z_STREAM_END && z.avail_out == 0;
+    inflateEnd(&z);
+    if (!ok) return false;
+    return (uint32_t)crc32(crc32(0L, Z_NULL, 0), dst, k.isize) == rd_u32(b->map + k.coff + k.csize - 8);
+}
+
+// the window becomes the inflated blocks [b0, b1)
+int load_window(csv_bam* b, size_t b0, size_t b1)
+{
+    const double t0 = now_ms();
+    b->win_u0 = b->blocks[b0].uoff;
+    const i64 bytes = (b1 < b->blocks.size() ? b->blocks[b1].uoff : b->utotal) - b->win_u0;
+    b->win.resize((size_t)bytes);
+    std::atomic<size_t> next(b0);
+    std::atomic<i64> bad(-1);
+    auto work = [&] {
+        for (;;) {
+            const size_t k = next.fetch_add(8);            // 8 blocks at a time: neighbours stay on one thread
+            if (k >= b1) return;
+            for (size_t j = k; j < std::min(k + 8, b1); j++)
+                if (!inflate_block(b, b->blocks[j], b->win.data() + (b->blocks[j].uoff - b->win_u0))) bad.store((i64)j);
+        }
+    };
+    const int nt = (int)std::max<size_t>(1, std::min<size_t>((size_t)b->threads, (b1 - b0 + 7) / 8));
+    std::vector<std::thread> th;
+    for (int t = 1; t < nt; t++) th.emplace_back(work);
+    work();
+    for (auto& t : th) t.join();
+    for (size_t j = b0; j < b1; j++) b->compressed += b->blocks[j].csize;
+    b->inflated += bytes;
+    b->ms_inflate += now_ms() - t0;
+    if (bad.load() >= 0) return fail(b, CSV_E_INVALID, "%sBGZF block at byte %lld does not inflate (or fails its CRC)", "", (long long)b->blocks[(size_t)bad.load()].coff);
+    return CSV_OK;
+}
+
+size_t block_of(const csv_bam* b, i64 u)                  // the block that holds uncompressed offset u (u < utotal)
+{
+    size_t lo = 0, hi = b->blocks.size();
+    while (hi - lo > 1) { const size_t m = (lo + hi) / 2; if (b->blocks[m].uoff <= u) lo = m; else hi = m; }
+    while (lo + 1 < b->blocks.size() && b->blocks[lo].isize == 0) lo++;
+    return lo;
+}
+
+// a pointer to [u, u + need) of the inflated stream, refilling the window when it does not hold the range; nullptr with
+// *rc = CSV_OK: the stream ends before u + need
+const uint8_t* at(csv_bam* b, i64 u, i64 need, int* rc)
+{
+    *rc = CSV_OK;
+    if (u + need > b->utotal) return nullptr;
+    if (u < b->win_u0 || u + need > b->win_u0 + (i64)b->win.size()) {
+        const size_t b0 = block_of(b, u);
+        size_t b1 = std::min(b->blocks.size(), b0 + REFILL_BLOCKS);
+        while (b1 < b->blocks.size() && b->blocks[b1].uoff < u + need) b1++;
+        *rc = load_window(b, b0, b1);
+        if (*rc) return nullptr;
+    }
+    return b->win.data() + (u - b->win_u0);
+}
+
+int read_header(csv_bam* b)
+{
+    int rc;
+    const uint8_t* p = at(b, 0, 12, &rc);
+    if (rc) return rc;
+    if (!p || memcmp(p, "BAM\1", 4) != 0) return fail(b, CSV_E_INVALID, "%snot a BAM file (no BAM\\1 magic)", "");
+    const i64 l_text = rd_i32(p + 4);
+    if (l_text < 0) return fail(b, CSV_E_INVALID, "%sbad l_text", "");
+    p = at(b, 8, l_text + 4, &rc);
+    if (rc) return rc;
+    if (!p) return fail(b, CSV_E_INVALID, "%sthe file ends inside the BAM header", "");
+    b->text.assign((const char*)p, (size_t)l_text);
+    while (!b->text.empty() && b->text.back() == '\0') b->text.pop_back();
+    b->n_ref = rd_i32(p + l_text);
+    if (b->n_ref < 0) return fail(b, CSV_E_INVALID, "%sbad n_ref", "");
+    i64 u = 8 + l_text + 4;
+    for (int r = 0; r < b->n_ref; r++) {
+        p = at(b, u, 4, &rc);
+        if (rc) return rc;
+        const i64 l_name = p ? rd_i32(p) : -1;
+        if (l_name < 1 || l_name > 1 << 20) return fail(b, CSV_E_INVALID, "%sbad reference name length (reference %lld)", "", r);
+        p = at(b, u + 4, l_name + 4, &rc);
+        if (rc) return rc;
+        if (!p) return fail(b, CSV_E_INVALID, "%sthe file ends inside the BAM header", "");
+        b->names.append((const char*)p, strnlen((const char*)p, (size_t)l_name));
+        b->names.push_back('\0');
+        b->lengths.push_back(rd_u32(p + l_name));
+        u += 8 + l_name;
+    }
+    b->first_rec = b->cur = u;
+    return CSV_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int csv_bam_struct_size(int which)
+{
+    switch (which) {
+    case 0: return (int)sizeof(csv_bam_chunk);
+    case 1: return (int)sizeof(csv_bam_in);
+    case 2: return (int)sizeof(csv_bam_out);
+    default: return -1;
+    }
+}
+
+int csv_bam_open(const char* path, int threads, csv_bam** out, char* err, int err_cap)
+{
+    if (!path || !out) return CSV_E_INVALID;
+    *out = nullptr;
+    csv_bam* b = new csv_bam;
+    b->threads = std::max(1, std::min(threads, 64));
+    int rc = CSV_OK;
+    struct stat st;
+    b->fd = open(path, O_RDONLY);
+    if (b->fd < 0 || fstat(b->fd, &st) != 0) rc = fail(b, CSV_E_INVALID, "cannot open %s", path);
+    else if (st.st_size < 28) rc = fail(b, CSV_E_INVALID, "%s is too short to be a BAM file (truncated?)", path);
+    else {
+        b->fsize = st.st_size;
+        void* m = mmap(nullptr, (size_t)b->fsize, PROT_READ, MAP_PRIVATE, b->fd, 0);
+        if (m == MAP_FAILED) rc = fail(b, CSV_E_NOMEM, "cannot map %s", path);
+        else b->map = (const uint8_t*)m;
+    }
+    if (!rc) rc = index_blocks(b);
+    if (!rc) rc = read_header(b);
+    if (rc) {
+        if (err && err_cap > 0) snprintf(err, (size_t)err_cap, "%s", b->err.c_str());
+        csv_bam_close(b);
+        return rc;
+    }
+    *out = b;
+    return CSV_OK;
+}
+
+void csv_bam_close(csv_bam* b)
+{
+    if (!b) return;
+    if (b->map) munmap(const_cast<uint8_t*>(b->map), (size_t)b->fsize);
+    if (b->fd >= 0) close(b->fd);
+    delete b;
+}
+
+const char* csv_bam_error(const csv_bam* b) { return b ? b->err.c_str() : ""; }
+
+int csv_bam_header(const csv_bam* b, int32_t* n_ref, const char** names, const int64_t** lengths, const char** text, int64_t* text_len)
+{
+    if (!b) return CSV_E_INVALID;
+    if (n_ref) *n_ref = b->n_ref;
+    if (names) *names = b->names.data();
+    if (lengths) *lengths = b->lengths.data();
+    if (text) *text = b->text.data();
+    if (text_len) *text_len = (int64_t)b->text.size();
+    return CSV_OK;
+}
+
+int csv_bam_read(csv_bam* b, int32_t refid, int64_t beg, int64_t end, int64_t max_records, int32_t flags, csv_bam_chunk* out)
+{
+    if (!b || !out || max_records < 1) return CSV_E_INVALID;
+    const double t0 = now_ms();
+    memset(out, 0, sizeof *out);
+    b->ms_inflate = 0; b->inflated = b->compressed = 0;
+    b->slim.clear(); b->host.clear(); b->rec_off.clear(); b->host_off.clear(); b->rec_len.clear();
+    const bool count_only = (flags & CSV_BAM_COUNT_ONLY) != 0;
+    const uint32_t key = (uint32_t)refid;
+    if (flags & CSV_BAM_RESTART) {                           // start of the contig if it was seen, else the last contig start before it
+        b->cur = b->first_rec;
+        auto it = b->contig_at.upper_bound(key);
+        if (it != b->contig_at.begin()) { --it; b->cur = it->second; }
+        if (b->hint_at >= 0 && b->hint_key == key && beg >= b->hint_beg) b->cur = b->hint_at;
+        b->hint_at = -1;
+    }
+    const bool set_hint = (flags & CSV_BAM_RESTART) != 0;
+    i64 n = 0;
+    bool more = false;
+    int rc = CSV_OK;
+    for (;;) {
+        const uint8_t* p = at(b, b->cur, 4, &rc);
+        if (rc) return rc;
+        if (!p) {
+            if (b->cur != b->utotal) return fail(b, CSV_E_INVALID, "%sthe file ends inside a record (at inflated byte %lld)", "", (long long)b->cur);
+            b->scanned_key = 0xffffffffu; b->scanned_any = true;
+            break;
+        }
+        const i64 bs = rd_i32(p);
+        if (bs < 32) return fail(b, CSV_E_INVALID, "%srecord with block_size < 32 at inflated byte %lld", "", (long long)b->cur);
+        p = at(b, b->cur + 4, bs, &rc);
+        if (rc) return rc;
+        if (!p) return fail(b, CSV_E_INVALID, "%sthe file ends inside a record (at inflated byte %lld)", "", (long long)b->cur);
+        const uint32_t rkey = (uint32_t)rd_i32(p);
+        if (!b->contig_at.count(rkey)) b->contig_at[rkey] = b->cur;
+        if (!b->scanned_any || rkey > b->scanned_key) { b->scanned_key = rkey; b->scanned_any = true; }
+        if (rkey > key) break;                               // the next contig (the unmapped tail sorts last): not consumed
+        if (rkey < key) { b->cur += 4 + bs; continue; }
+        const i64 pos = rd_i32(p + 4), l_name = p[8], n_cig = rd_u16(p + 12), l_seq = rd_u32(p + 16);
+        const i64 fixed_to_aux = 32 + l_name + 4 * n_cig + (l_seq + 1) / 2 + l_seq;
+        if (fixed_to_aux > bs) return fail(b, CSV_E_INVALID, "%srecord fields exceed its block_size at inflated byte %lld", "", (long long)b->cur);
+        if (pos >= end) break;                               // sorted: nothing later can start before `end`
+        if (pos < beg) {                                     // overlaps the region only if it reaches past `beg`
+            i64 span = 0;
+            const uint8_t* cg = p + 32 + l_name;
+            for (i64 k = 0; k < n_cig; k++) {
+                const uint32_t w = rd_u32(cg + 4 * k);
+                const uint32_t op = w & 15u;
+                if (op == 0 || op == 2 || op == 3 || op == 7 || op == 8) span += w >> 4;
+            }
+            if (pos + (span ? span : 1) <= beg) { b->cur += 4 + bs; continue; }
+        }
+        if (n == max_records) { more = true; break; }
+        if (n == 0 && set_hint) { b->hint_key = key; b->hint_beg = beg; b->hint_at = b->cur; }
+        if (!count_only) {
+            const i64 aux_len = bs - fixed_to_aux, slim_len = 32 + 4 * n_cig + aux_len;
+            const size_t s0 = b->slim.size();
+            b->rec_off.push_back((i64)s0);
+            b->rec_len.push_back((uint32_t)slim_len);
+            b->slim.resize(s0 + (size_t)((slim_len + SLIM_ALIGN - 1) / SLIM_ALIGN * SLIM_ALIGN));
+            uint8_t* d = b->slim.data() + s0;
+            memcpy(d, p, 32);
+            memcpy(d + 32, p + 32 + l_name, (size_t)(4 * n_cig));
+            memcpy(d + 32 + 4 * n_cig, p + fixed_to_aux, (size_t)aux_len);
+            memset(d + slim_len, 0, b->slim.size() - s0 - (size_t)slim_len);
+            const size_t h0 = b->host.size();
+            b->host_off.push_back((i64)h0);
+            b->host.resize(h0 + (size_t)(l_name + (l_seq + 1) / 2));
+            memcpy(b->host.data() + h0, p + 32, (size_t)l_name);
+            memcpy(b->host.data() + h0 + l_name, p + 32 + l_name + 4 * n_cig, (size_t)((l_seq + 1) / 2));
+        }
+        n++;
+        out->record_bytes += 4 + bs;
+        b->cur += 4 + bs;
+    }
+    b->host_off.push_back((i64)b->host.size());
+    out->n_records = n; out->more = more ? 1 : 0;
+    out->slim = b->slim.data(); out->slim_bytes = (int64_t)b->slim.size();
+    out->rec_off = b->rec_off.data(); out->rec_len = b->rec_len.data();
+    out->host = b->host.data(); out->host_bytes = (int64_t)b->host.size(); out->host_off = b->host_off.data();
+    out->inflated_bytes = b->inflated; out->compressed_bytes = b->compressed;
+    out->ms_inflate = b->ms_inflate; out->ms_frame = now_ms() - t0 - b->ms_inflate;
+    return CSV_OK;
+}
+
+}  // extern "C"

@@ -19,6 +19,7 @@
 #include "sort.hip.h"
 #include "cigar.hip.h"
 #include "split.hip.h"
+#include "bam.hip.h"
 
 using namespace csv;
 
@@ -115,7 +116,7 @@ struct csv_ctx {
     hipEvent_t  ev_init = nullptr, ev_sel = nullptr, ev_aux[3] = {}, ev_copy[N_COPY_STREAMS] = {}, ev_reads = nullptr, ev_anc = nullptr, ev_rd[5] = {};
     std::string err;
     hipEvent_t  ev[CSV_N_STAGES + 2] = {};
-    Arena       arena, arena_rb;
+    Arena       arena, arena_rb, arena_bam;
     // batch buffers (slices of `arena`)
     Buf seg, woff, seg_drop, a, b, rid, aux, a32, b32;
     Buf tile_lead, tabs;
@@ -149,6 +150,11 @@ struct csv_ctx {
     Buf sp_off, sp_len, sp_c0, sp_c1, sp_f0, sp_f1, sp_chr, sp_mapq, sp_strand, sp_primary, sp_seg, sp_cnt, sp_tiles, sp_tot,
         sp_kind, sp_read, sp_ochr, sp_aux, sp_a, sp_b, sp_c, sp_d;
     Buf cg_qlen, cg_off, cg_ops, cg_start, cg_use, cg_cnt, cg_tiles, cg_tot, cg_iread, cg_ipos, cg_ilen, cg_ip0, cg_inp, cg_pq, cg_pl, cg_dread, cg_dpos, cg_dlen;
+    // BAM decode (slices of `arena_bam`, which lives until the next decode: csv_cigar_signatures with CSV_CG_FROM_BAM scans
+    // bm_cigoff / bm_cigar / bm_start in place; the SA ranges are sized after the scan, so they stand alone)
+    Buf bm_slim, bm_recoff, bm_reclen, bm_start, bm_end, bm_flag, bm_mapq, bm_qlen, bm_cl, bm_cr, bm_cls, bm_status, bm_cigoff, bm_saoff, bm_cigsrc,
+        bm_cgb, bm_cge, bm_cigar, bm_long, bm_cnt, bm_tot, bm_sabeg, bm_saend;
+    i64 bam_n = -1, bam_nops = 0;              // records / operations of the last successful decode (-1: none)
     // page-locked host staging: small tables on the way in, counters + call records + support lists on the way out
     char*  h_pin = nullptr;
     size_t h_pin_cap = 0;
@@ -449,10 +455,11 @@ void csv_ctx_destroy(csv_ctx* c)
     if (!c) return;
     (void)hipSetDevice(c->device);
     (void)hipDeviceSynchronize();
-    Buf* own[] = {&c->pool_seg, &c->pool_a, &c->pool_b, &c->pool_read, &c->pool_aux, &c->sp_qlen, &c->sqrt_tab, &c->rcp_tab, &c->cipk_tab, &c->cnt, &c->rstate, &c->gs_chrom, &c->gs_perm0, &c->gs_perm1, &c->gs_hist, &c->gs_tot, &c->flush};
+    Buf* own[] = {&c->pool_seg, &c->pool_a, &c->pool_b, &c->pool_read, &c->pool_aux, &c->sp_qlen, &c->sqrt_tab, &c->rcp_tab, &c->cipk_tab, &c->cnt, &c->rstate, &c->gs_chrom, &c->gs_perm0, &c->gs_perm1, &c->gs_hist, &c->gs_tot, &c->flush, &c->bm_sabeg, &c->bm_saend};
     for (Buf* b : own) if (b->p) (void)hipFree(b->p);
     if (c->arena.base) (void)hipFree(c->arena.base);
     if (c->arena_rb.base) (void)hipFree(c->arena_rb.base);
+    if (c->arena_bam.base) (void)hipFree(c->arena_bam.base);
     if (c->h_pin) (void)hipHostFree(c->h_pin);
     if (c->h_flag) (void)hipHostFree((void*)c->h_flag);
     if (c->h_pub) (void)hipHostFree(c->h_pub);
@@ -2049,12 +2056,16 @@ int csv_cigar_signatures(csv_ctx* c, const csv_cigar_in* in, csv_cigar_out* out)
     HIP_TRY(c, hipSetDevice(c->device));
     out->n_sig_ins = out->n_piece_ins = out->n_sig_del = 0; out->ms_device = 0;
     const i64 n = in->n_reads;
-    if (n < 0 || (n > 0 && (!in->cig_off || !in->ref_start))) return fail(c, CSV_E_INVALID, "bad CIGAR batch header");
+    // CSV_CG_FROM_BAM: the columns are the ones csv_bam_decode left on the device (offsets from its own scan: they start at 0,
+    // do not decrease and end at its operation count)
+    const bool from_bam = (in->flags & CSV_CG_FROM_BAM) != 0;
+    if (from_bam && (c->bam_n < 0 || n != c->bam_n)) return fail(c, CSV_E_INVALID, "CSV_CG_FROM_BAM: n_reads is not the record count of the context's last csv_bam_decode");
+    if (n < 0 || (n > 0 && !from_bam && (!in->cig_off || !in->ref_start))) return fail(c, CSV_E_INVALID, "bad CIGAR batch header");
     if (n == 0) return CSV_OK;
-    const i64 nops = in->cig_off[n] - in->cig_off[0];
-    if (in->cig_off[0] != 0 || nops < 0 || (nops > 0 && !in->cigar)) return fail(c, CSV_E_INVALID, "cig_off must start at 0 and not decrease");
+    const i64 nops = from_bam ? c->bam_nops : in->cig_off[n] - in->cig_off[0];
+    if (!from_bam && (in->cig_off[0] != 0 || nops < 0 || (nops > 0 && !in->cigar))) return fail(c, CSV_E_INVALID, "cig_off must start at 0 and not decrease");
     if (nops >= (1ll << 31) - 4096) return fail(c, CSV_E_INVALID, "CIGAR batch too large (%lld operations): split it", (long long)nops);
-    for (i64 r = 0; r < n; r++)                                 // the kernels index `cigar` with these: every offset is checked here
+    for (i64 r = 0; r < n && !from_bam; r++)                    // the kernels index `cigar` with these: every offset is checked here
         if (in->cig_off[r] < 0 || in->cig_off[r + 1] < in->cig_off[r] || in->cig_off[r + 1] > nops)
             return fail(c, CSV_E_INVALID, "cig_off decreases or leaves the CIGAR array at read %lld", (long long)r);
     const int ntile = div_up(n, CG_TILE);
@@ -2065,7 +2076,8 @@ int csv_cigar_signatures(csv_ctx* c, const csv_cigar_in* in, csv_cigar_out* out)
     Plan P;
 #define PL(buf, bytes) P.add(c->buf, (size_t)(bytes))
     const bool to_pool = (in->flags & CSV_CG_TO_POOL) != 0;
-    PL(cg_off, (n + 1) * 8); PL(cg_ops, (nops + 1) * 4); PL(cg_start, n * 8); PL(cg_use, n); PL(cg_cnt, n * 16);
+    if (!from_bam) { PL(cg_off, (n + 1) * 8); PL(cg_ops, (nops + 1) * 4); PL(cg_start, n * 8); }
+    PL(cg_use, n); PL(cg_cnt, n * 16);
     if (to_pool && in->query_len) PL(cg_qlen, n * 4);
     PL(cg_tiles, (size_t)ntile * 24); PL(cg_tot, 32);
     PL(cg_iread, (cap_i + 1) * 4); PL(cg_ipos, (cap_i + 1) * 8); PL(cg_ilen, (cap_i + 1) * 8); PL(cg_ip0, (cap_i + 1) * 8); PL(cg_inp, (cap_i + 1) * 4);
@@ -2078,12 +2090,15 @@ int csv_cigar_signatures(csv_ctx* c, const csv_cigar_in* in, csv_cigar_out* out)
         if (rc) return rc;
     }
     hipStream_t st = c->stream;
-    HIP_TRY(c, hipMemcpyAsync(c->cg_off.p, in->cig_off, (size_t)(n + 1) * 8, hipMemcpyHostToDevice, st));
-    if (nops) HIP_TRY(c, hipMemcpyAsync(c->cg_ops.p, in->cigar, (size_t)nops * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(c, hipMemcpyAsync(c->cg_start.p, in->ref_start, (size_t)n * 8, hipMemcpyHostToDevice, st));
+    if (!from_bam) {
+        HIP_TRY(c, hipMemcpyAsync(c->cg_off.p, in->cig_off, (size_t)(n + 1) * 8, hipMemcpyHostToDevice, st));
+        if (nops) HIP_TRY(c, hipMemcpyAsync(c->cg_ops.p, in->cigar, (size_t)nops * 4, hipMemcpyHostToDevice, st));
+        HIP_TRY(c, hipMemcpyAsync(c->cg_start.p, in->ref_start, (size_t)n * 8, hipMemcpyHostToDevice, st));
+    }
     if (in->use) HIP_TRY(c, hipMemcpyAsync(c->cg_use.p, in->use, (size_t)n, hipMemcpyHostToDevice, st));
     CigarArgs A{};
     A.n_reads = n; A.cig_off = dp<i64>(c->cg_off); A.cigar = dp<unsigned>(c->cg_ops); A.ref_start = dp<i64>(c->cg_start);
+    if (from_bam) { A.cig_off = dp<i64>(c->bm_cigoff); A.cigar = dp<unsigned>(c->bm_cigar); A.ref_start = dp<i64>(c->bm_start); }
     A.use = in->use ? dp<uint8_t>(c->cg_use) : nullptr;
     A.min_siglength = in->min_siglength; A.merge_ins = in->merge_ins_threshold; A.merge_del = in->merge_del_threshold;
     A.cnt = dp<int4>(c->cg_cnt); A.tile_sum = dp<i64>(c->cg_tiles); A.totals = dp<i64>(c->cg_tot);
@@ -2216,6 +2231,95 @@ int csv_split_signatures(csv_ctx* c, const csv_split_in* in, csv_split_out* out)
     HIP_TRY(c, hipEventElapsedTime(&ms1, c->ev[0], c->ev[1]));
     HIP_TRY(c, hipEventElapsedTime(&ms2, c->ev[2], c->ev[3]));
     out->ms_device = ms1 + ms2;
+    return CSV_OK;
+}
+
+int csv_bam_decode(csv_ctx* c, const csv_bam_in* in, csv_bam_out* out)
+{
+    if (!c || !in || !out) return CSV_E_INVALID;
+    HIP_TRY(c, hipSetDevice(c->device));
+    out->n_ops = out->n_sa = out->n_bad = out->bytes_uploaded = 0; out->ms_device = out->ms_upload = 0;
+    out->dev_ref_start = out->dev_ref_end = out->dev_flag = out->dev_mapq = out->dev_query_len = out->dev_clip_left = out->dev_clip_right =
+        out->dev_cls = out->dev_cig_off = out->dev_cigar = nullptr;
+    c->bam_n = -1;
+    const i64 n = in->n_records, nb = in->slim_bytes;
+    if (n < 0 || nb < 0 || in->flags != 0 || (n > 0 && (!in->slim || !in->rec_off || !in->rec_len))) return fail(c, CSV_E_INVALID, "bad BAM chunk header");
+    if (n >= (1ll << 31) - 4096) return fail(c, CSV_E_INVALID, "BAM chunk too large (%lld records): split it", (long long)n);
+    // the kernels read [rec_off, rec_off + rec_len) of every record and nothing else: each range is checked against the image
+    for (i64 r = 0; r < n; r++) {
+        const i64 o = in->rec_off[r], l = in->rec_len[r];
+        if (o < 0 || (o & 15) || l < 32 || o > nb || l > nb - o) return fail(c, CSV_E_INVALID, "record %lld of the BAM chunk leaves the slim image (or is misaligned / shorter than 32 bytes)", (long long)r);
+    }
+    if (n == 0) { c->bam_n = 0; c->bam_nops = 0; if (out->cig_off) out->cig_off[0] = 0; if (out->sa_off) out->sa_off[0] = 0; return CSV_OK; }
+    const i64 max_ops = nb / 4;                              // every operation is 4 bytes of the image
+    Plan P;
+#define PL(buf, bytes) P.add(c->buf, (size_t)(bytes))
+    PL(bm_slim, nb + 16); PL(bm_recoff, n * 8); PL(bm_reclen, n * 4);
+    PL(bm_start, n * 8); PL(bm_end, n * 8); PL(bm_flag, n * 4); PL(bm_mapq, n * 4); PL(bm_qlen, n * 4); PL(bm_cl, n * 4); PL(bm_cr, n * 4);
+    PL(bm_cls, n); PL(bm_status, n); PL(bm_cigoff, (n + 1) * 8); PL(bm_saoff, (n + 1) * 8); PL(bm_cigsrc, n * 8); PL(bm_cgb, n * 8); PL(bm_cge, n * 8);
+    PL(bm_cigar, (max_ops + 1) * 4); PL(bm_long, n * 4); PL(bm_cnt, 16); PL(bm_tot, 16);
+#undef PL
+    {
+        if (P.total > c->arena_bam.cap) HIP_TRY(c, hipDeviceSynchronize());
+        const int rc = commit(c, c->arena_bam, P);
+        if (rc) return rc;
+    }
+    hipStream_t st = c->stream;
+    HIP_TRY(c, hipEventRecord(c->ev[4], st));
+    HIP_TRY(c, hipMemcpyAsync(c->bm_slim.p, in->slim, (size_t)nb, hipMemcpyHostToDevice, st));
+    HIP_TRY(c, hipMemcpyAsync(c->bm_recoff.p, in->rec_off, (size_t)n * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(c, hipMemcpyAsync(c->bm_reclen.p, in->rec_len, (size_t)n * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(c, hipEventRecord(c->ev[5], st));
+    out->bytes_uploaded = nb + n * 12;
+    HIP_TRY(c, hipMemsetAsync(c->bm_cnt.p, 0, 16, st));
+    BamArgs A{};
+    A.n = n; A.slim = dp<uint8_t>(c->bm_slim); A.rec_off = dp<i64>(c->bm_recoff); A.rec_len = dp<unsigned>(c->bm_reclen);
+    A.ref_start = dp<i64>(c->bm_start); A.ref_end = dp<i64>(c->bm_end); A.flag = dp<int>(c->bm_flag); A.mapq = dp<int>(c->bm_mapq); A.qlen = dp<int>(c->bm_qlen);
+    A.clip_l = dp<int>(c->bm_cl); A.clip_r = dp<int>(c->bm_cr); A.cls = dp<uint8_t>(c->bm_cls); A.status = dp<uint8_t>(c->bm_status);
+    A.cig_off = dp<i64>(c->bm_cigoff); A.sa_off = dp<i64>(c->bm_saoff); A.cig_src = dp<i64>(c->bm_cigsrc); A.cg_beg = dp<i64>(c->bm_cgb); A.cg_end = dp<i64>(c->bm_cge);
+    A.cigar = dp<unsigned>(c->bm_cigar); A.long_list = dp<int>(c->bm_long); A.counters = dp<int>(c->bm_cnt); A.totals = dp<i64>(c->bm_tot);
+    HIP_TRY(c, hipEventRecord(c->ev[0], st));
+    hipLaunchKernelGGL(k_bam_fixed, dim3(div_up(n, 256)), dim3(256), 0, st, A);
+    hipLaunchKernelGGL(k_bam_scan, dim3(1), dim3(1024), 0, st, A);
+    HIP_TRY(c, hipEventRecord(c->ev[1], st));
+    HIP_TRY(c, hipGetLastError());
+    i64 tot[2] = {0, 0};
+    int cnt[4] = {0, 0, 0, 0};
+    HIP_TRY(c, hipMemcpyAsync(tot, c->bm_tot.p, 16, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipMemcpyAsync(cnt, c->bm_cnt.p, 16, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    // (what the kernels counted is bounded by the image they counted it in; anything else would be a bug here, not in the file)
+    if (tot[0] < 0 || tot[0] > max_ops || tot[1] < 0 || tot[1] > nb / 4 || cnt[0] < 0 || cnt[0] > n)
+        return fail(c, CSV_E_INVALID, "BAM decode: inconsistent counts (%lld operations, %lld SA tags)", (long long)tot[0], (long long)tot[1]);
+    out->n_ops = tot[0]; out->n_sa = tot[1]; out->n_bad = cnt[1];
+    if ((out->cigar && tot[0] > out->cap_ops) || ((out->sa_beg || out->sa_end) && tot[1] > out->cap_sa))
+        return fail(c, CSV_E_CAPACITY, "need %lld CIGAR operations / %lld SA ranges", (long long)tot[0], (long long)tot[1]);
+    { int rc = reserve(c, c->bm_sabeg, (size_t)(tot[1] + 1) * 8); if (!rc) rc = reserve(c, c->bm_saend, (size_t)(tot[1] + 1) * 8); if (rc) return rc; }
+    A.sa_beg = dp<i64>(c->bm_sabeg); A.sa_end = dp<i64>(c->bm_saend);
+    HIP_TRY(c, hipEventRecord(c->ev[2], st));
+    const int grid = div_up(n, 4) < 8192 ? div_up(n, 4) : 8192;
+    hipLaunchKernelGGL(k_bam_cigar, dim3(grid), dim3(256), 0, st, A);
+    if (cnt[0] > 0) hipLaunchKernelGGL(k_bam_cigar_long, dim3(cnt[0]), dim3(256), 0, st, A);
+    if (tot[1] > 0) hipLaunchKernelGGL(k_bam_sa, dim3(div_up(n, 256)), dim3(256), 0, st, A);
+    HIP_TRY(c, hipEventRecord(c->ev[3], st));
+    HIP_TRY(c, hipGetLastError());
+#define D2H(dst, buf, bytes) do { if ((dst) && (bytes) > 0) HIP_TRY(c, hipMemcpyAsync((dst), c->buf.p, (size_t)(bytes), hipMemcpyDeviceToHost, st)); } while (0)
+    D2H(out->ref_start, bm_start, n * 8); D2H(out->ref_end, bm_end, n * 8); D2H(out->flag, bm_flag, n * 4); D2H(out->mapq, bm_mapq, n * 4);
+    D2H(out->query_len, bm_qlen, n * 4); D2H(out->clip_left, bm_cl, n * 4); D2H(out->clip_right, bm_cr, n * 4); D2H(out->cls, bm_cls, n);
+    D2H(out->status, bm_status, n); D2H(out->cig_off, bm_cigoff, (n + 1) * 8); D2H(out->cigar, bm_cigar, tot[0] * 4);
+    D2H(out->sa_off, bm_saoff, (n + 1) * 8); D2H(out->sa_beg, bm_sabeg, tot[1] * 8); D2H(out->sa_end, bm_saend, tot[1] * 8);
+    D2H(out->cg_beg, bm_cgb, n * 8); D2H(out->cg_end, bm_cge, n * 8);
+#undef D2H
+    HIP_TRY(c, hipStreamSynchronize(st));
+    float ms1 = 0, ms2 = 0;
+    HIP_TRY(c, hipEventElapsedTime(&ms1, c->ev[0], c->ev[1]));
+    HIP_TRY(c, hipEventElapsedTime(&ms2, c->ev[2], c->ev[3]));
+    HIP_TRY(c, hipEventElapsedTime(&out->ms_upload, c->ev[4], c->ev[5]));
+    out->ms_device = ms1 + ms2;
+    if (cnt[1] > 0) return fail(c, CSV_E_INVALID, "%d record(s) of the BAM chunk have a malformed aux area or CIGAR (see status)", cnt[1]);
+    out->dev_ref_start = c->bm_start.p; out->dev_ref_end = c->bm_end.p; out->dev_flag = c->bm_flag.p; out->dev_mapq = c->bm_mapq.p; out->dev_query_len = c->bm_qlen.p;
+    out->dev_clip_left = c->bm_cl.p; out->dev_clip_right = c->bm_cr.p; out->dev_cls = c->bm_cls.p; out->dev_cig_off = c->bm_cigoff.p; out->dev_cigar = c->bm_cigar.p;
+    c->bam_n = n; c->bam_nops = tot[0];
     return CSV_OK;
 }
 

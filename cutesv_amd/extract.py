@@ -8,7 +8,8 @@ the reads' query sequences here: the bases never travel to the GPU).  `split_sig
 primary alignments and SA-tag entries.  BAM decode, the SA text and everything else of the extraction stay in the Python
 driver with pysam, as north_star has it: a driver would collect
 `read.cigartuples`, `read.reference_start`, `read.mapq >= min_mapq and read.query_length >= min_read_len` for a task's
-reads, make one call here, and extend candidate["INS"] / candidate["DEL"] with the result.
+reads, make one call here, and extend candidate["INS"] / candidate["DEL"] with the result.  `single_pipe_bam` is the same task
+body fed from a BAM file by the native reader (cutesv_amd/bam.py): no pysam and no object per record.
 """
 import ctypes as C
 
@@ -52,18 +53,24 @@ def encode_cigars(cigartuples_per_read):
     return off, flat
 
 
-def _run(fn, handle, cig_off, cigar, ref_start, use, min_siglength, merge_ins_threshold, merge_del_threshold, check, pool=None, host_outputs=True):
-    cig_off = np.ascontiguousarray(cig_off, np.int64); cigar = np.ascontiguousarray(cigar, np.uint32)
-    ref_start = np.ascontiguousarray(ref_start, np.int64)
+def _run(fn, handle, cig_off, cigar, ref_start, use, min_siglength, merge_ins_threshold, merge_del_threshold, check, pool=None, host_outputs=True,
+         from_bam=None):
     use = None if use is None else np.ascontiguousarray(use, np.uint8)
-    n = len(ref_start)
-    cin = CigarIn(n_reads=n, cig_off=cig_off.ctypes.data, cigar=cigar.ctypes.data if len(cigar) else None, ref_start=ref_start.ctypes.data,
-                  use=None if use is None else use.ctypes.data, min_siglength=int(min_siglength),
-                  merge_ins_threshold=int(merge_ins_threshold), merge_del_threshold=int(merge_del_threshold))
+    if from_bam is not None:                              # CSV_CG_FROM_BAM: the three columns are on the device already (bam.decode)
+        n, n_ops = int(from_bam["n"]), int(from_bam["n_ops"])
+        cin = CigarIn(n_reads=n, use=None if use is None else use.ctypes.data, min_siglength=int(min_siglength),
+                      merge_ins_threshold=int(merge_ins_threshold), merge_del_threshold=int(merge_del_threshold), flags=_abi.CG_FROM_BAM)
+    else:
+        cig_off = np.ascontiguousarray(cig_off, np.int64); cigar = np.ascontiguousarray(cigar, np.uint32)
+        ref_start = np.ascontiguousarray(ref_start, np.int64)
+        n, n_ops = len(ref_start), int(cig_off[-1])
+        cin = CigarIn(n_reads=n, cig_off=cig_off.ctypes.data, cigar=cigar.ctypes.data if len(cigar) else None, ref_start=ref_start.ctypes.data,
+                      use=None if use is None else use.ctypes.data, min_siglength=int(min_siglength),
+                      merge_ins_threshold=int(merge_ins_threshold), merge_del_threshold=int(merge_del_threshold))
     qlen = None
     if pool is not None:                                  # CSV_CG_TO_POOL: the signatures also become rows of the context's pool
         qlen = None if pool.get("query_len") is None else np.ascontiguousarray(pool["query_len"], np.int32)
-        cin.flags = _abi.CG_TO_POOL
+        cin.flags |= _abi.CG_TO_POOL
         cin.seg_ins = int(pool["seg_ins"]); cin.seg_del = int(pool["seg_del"]); cin.read_base = int(pool["read_base"])
         cin.query_len = None if qlen is None else qlen.ctypes.data
     caps = dict(i=max(16, n // 4), p=max(16, n // 4), d=max(16, n // 4))
@@ -73,7 +80,7 @@ def _run(fn, handle, cig_off, cigar, ref_start, use, min_siglength, merge_ins_th
             cout = CigarOut(cap_sig_ins=caps["i"], cap_piece_ins=caps["p"], cap_sig_del=caps["d"], **{k: v.ctypes.data for k, v in arrs.items()})
         else:                                             # pool only: nothing but the counts comes back
             arrs = {name: np.zeros(0, dt) for name, dt, k in _OUT}
-            big = int(cig_off[-1]) + 1
+            big = n_ops + 1
             cout = CigarOut(cap_sig_ins=big, cap_piece_ins=big, cap_sig_del=big)
         rc = fn(handle, C.byref(cin), C.byref(cout)) if handle is not None else fn(C.byref(cin), C.byref(cout))
         if rc == _abi.E_CAPACITY:
@@ -88,17 +95,20 @@ def _run(fn, handle, cig_off, cigar, ref_start, use, min_siglength, merge_ins_th
     raise RuntimeError("csv_cigar_signatures: capacity retry failed")
 
 
-def cigar_signatures(ctx, cig_off, cigar, ref_start, use=None, min_siglength=10, merge_ins_threshold=100, merge_del_threshold=0, pool=None, host_outputs=True):
+def cigar_signatures(ctx, cig_off, cigar, ref_start, use=None, min_siglength=10, merge_ins_threshold=100, merge_del_threshold=0, pool=None, host_outputs=True,
+                     from_bam=None):
     """flat CIGARs of a batch of reads -> dict of the signature arrays of csv_cigar_out (defaults: cuteSV_Description.py:123-152).
     pool = dict(seg_ins, seg_del, read_base, query_len=None): the signatures ALSO become rows of the context's device-resident
     pool (CSV_CG_TO_POOL; INS rows in segment seg_ins, DEL rows in seg_del, read index = read_base + index in this batch), in the
     order INS then DEL - what `rebuild.rebuild_pool` sorts without the rows ever crossing PCIe; host_outputs=False (with a pool):
-    the arrays of the result stay empty, only the counts come back."""
+    the arrays of the result stay empty, only the counts come back.
+    from_bam = the columns `bam.decode(ctx, chunk)` returned: cig_off / cigar / ref_start are not taken from the arguments (pass
+    None) but scanned where that decode left them on the device (CSV_CG_FROM_BAM); `use` is still the caller's."""
     L = lib()
     L.csv_cigar_signatures.restype = C.c_int
     L.csv_cigar_signatures.argtypes = [C.c_void_p, C.POINTER(CigarIn), C.POINTER(CigarOut)]
     return _run(L.csv_cigar_signatures, ctx._h, cig_off, cigar, ref_start, use, min_siglength, merge_ins_threshold, merge_del_threshold, ctx._check, pool=pool,
-                host_outputs=host_outputs)
+                host_outputs=host_outputs, from_bam=None if from_bam is None else dict(n=len(from_bam["ref_start"]), n_ops=from_bam["n_ops"]))
 
 
 def candidates(sig, read_names, query_sequences, chrom):
@@ -278,31 +288,60 @@ def parse_reads(reads, chrom, chrom_rank, sv_size, min_mapq, max_split_parts, mi
     sig = cigar_fn(cig_off, cigar, ref_start, use, min_siglength=min_siglength, merge_ins_threshold=merge_ins_threshold,
                    merge_del_threshold=merge_del_threshold)
     names = [r.query_name for r in keep]
-    c_ins, c_del = candidates(sig, names, [r.query_sequence for r in keep], chrom)
     # reads with an SA tag on a primary record (flag 0 / 16, :657): their segments go through the split-read analysis
-    sp_reads, sp_idx, sp_query = [], [], []
+    sp = []
     for i, r in enumerate(keep):
         if r.flag not in (0, 16):
             continue
         sa = [v for k, v in r.get_tags() if k == "SA"]
         if not sa:
             continue
-        primary = []
-        if r.mapq >= min_mapq:
-            ct = r.cigartuples or ((0, 0),)                                                         # (no CIGAR: no clips)
-            left = ct[0][1] if ct[0][0] in (4, 5) else 0                                            # soft clip, or the hard clip that replaces it (:619-652)
-            right = ct[-1][1] if ct[-1][0] in (4, 5) else 0
-            primary = ([left, r.query_length - right, r.reference_start, r.reference_end, chrom, "+"] if r.flag == 0 else
-                       [right, r.query_length - left, r.reference_start, r.reference_end, chrom, "-"])
-        q = r.query_sequence if r.flag == 0 else str(r.query_sequence).translate(_COMP)[::-1]       # (:673-675)
+        ct = r.cigartuples or ((0, 0),)                                                             # (no CIGAR: no clips)
+        left = ct[0][1] if ct[0][0] in (4, 5) else 0                                                # soft clip, or the hard clip that replaces it (:619-652)
+        right = ct[-1][1] if ct[-1][0] in (4, 5) else 0
+        primary = _primary_info(r.flag, r.mapq >= min_mapq, left, right, r.query_length, r.reference_start, r.reference_end, chrom)
+        sp.append((i, primary, sa, r.query_length, r.flag == 16))
+    return _assemble(sig, names, [r.query_sequence for r in keep], sp, chrom, chrom_rank, sv_size, min_mapq, max_split_parts, max_size, split_fn)
+
+
+def _primary_info(flag, mapq_ok, left, right, query_length, reference_start, reference_end, chrom):
+    """primary_info of parse_read (:660-668) for a primary record (flag 0 / 16): [] when its mapq does not pass"""
+    if not mapq_ok:
+        return []
+    return ([left, query_length - right, reference_start, reference_end, chrom, "+"] if flag == 0 else
+            [right, query_length - left, reference_start, reference_end, chrom, "-"])
+
+
+class _SplitQueries:
+    """queries[k] of split_candidates: the query parse_read passes for split-read call k - the read's sequence, reverse-
+    complemented for a reverse-strand read (:673-675) - made when a candidate asks for it (only INS candidates do)"""
+
+    def __init__(self, seqs, idx, reverse):
+        self.seqs, self.idx, self.reverse, self.cache = seqs, idx, reverse, {}
+
+    def __getitem__(self, k):
+        if k not in self.cache:
+            q = self.seqs[self.idx[k]]
+            self.cache[k] = str(q).translate(_COMP)[::-1] if self.reverse[k] else q
+        return self.cache[k]
+
+
+def _assemble(sig, names, seqs, sp, chrom, chrom_rank, sv_size, min_mapq, max_split_parts, max_size, split_fn):
+    """The second half of parse_reads, shared by the object path and the BAM path: the CIGAR signatures `sig` and the
+    split-read inputs `sp` = [(read index, primary_info, [SA values], query_length, reverse strand)] in read order -> the
+    five candidate lists.  names / seqs: indexable by read index (lists, or lazy views that slice a BAM chunk's host image)."""
+    cand = {t: [] for t in ("DEL", "INS", "DUP", "INV", "TRA")}
+    c_ins, c_del = candidates(sig, names, seqs, chrom)
+    sp_reads, sp_idx, sp_query = [], [], []
+    for i, primary, sa, qlen, reverse in sp:
         for tag in sa:                                                                              # (one call per SA tag, :671)
-            sp_reads.append((primary, tag, r.query_length)); sp_idx.append(i); sp_query.append(q)
+            sp_reads.append((primary, tag, qlen)); sp_idx.append(i); sp_query.append(reverse)
     s_cand = {t: [] for t in cand}
     s_read = {t: [] for t in cand}
     if sp_reads:
         enc = encode_split_reads(sp_reads, chrom_rank)
         ssig = split_fn(enc, sv_size=sv_size, min_mapq=min_mapq, max_split_parts=max_split_parts, max_size=max_size)
-        s_cand = split_candidates(ssig, [names[i] for i in sp_idx], sp_query, sorted(chrom_rank, key=chrom_rank.get))
+        s_cand = split_candidates(ssig, [names[i] for i in sp_idx], _SplitQueries(seqs, sp_idx, sp_query), sorted(chrom_rank, key=chrom_rank.get))
         kind_name = ("DEL", "INS", "DUP", "INV", "TRA")
         for k, rd in zip(ssig["kind"].tolist(), ssig["read"].tolist()):
             s_read[kind_name[k]].append(sp_idx[rd])
@@ -346,4 +385,62 @@ def single_pipe(alignments, chrom, task_start, chrom_rank, sv_size, min_mapq, ma
     cand = parse_reads(recs, chrom, chrom_rank, sv_size, min_mapq, max_split_parts, min_read_len, min_siglength, merge_del_threshold,
                        merge_ins_threshold, max_size, cigar_fn, split_fn)
     reads_info = [(r.reference_start, r.reference_end, 1 if r.flag in (0, 16) else 0, r.query_name, chrom) for r in recs if r.mapq >= min_mapq]
+    return cand, reads_info
+
+
+# ------------------------------------------------------------------------------------ single_pipe from a BAM file
+class _Lazy:
+    """names / sequences of a BAM chunk by record index, sliced out of its host image on first use"""
+
+    def __init__(self, get):
+        self.get, self.cache = get, {}
+
+    def __getitem__(self, i):
+        if i not in self.cache:
+            self.cache[i] = self.get(i)
+        return self.cache[i]
+
+
+def single_pipe_bam(ctx_or_fns, bamfile, chrom, task_start, task_end, chrom_rank, sv_size, min_mapq, max_split_parts, min_read_len, min_siglength,
+                    merge_del_threshold, merge_ins_threshold, max_size, bed_regions=None):
+    """`single_pipe` for the records `fetch(chrom, task_start, task_end)` would yield, read from `bamfile` (a bam.BamFile)
+    without an object per record: -> (cand, reads_info) exactly as `single_pipe` returns them.
+
+    ctx_or_fns: an engine.Context - the records are decoded by csv_bam_decode and the CIGAR scan runs on the device columns
+    it leaves (the CIGARs cross PCIe once, inside the slim image, and never come back) - or a pair (cigar_fn, split_fn) as
+    `single_pipe` takes them: then `bam.decode_host` decodes, the CPU path of the tests.
+
+    The gates are single_pipe's, applied to the columns: secondary records are skipped (:711), a read belongs to the task
+    it starts in (:725), the bed overlap (:715-723), reads-table rows for mapq >= min_mapq (:729-733); parse_read's own
+    gates (query_length >= min_read_len, :607; mapq, :614) become the `use` column of the CIGAR scan.  Read indices are
+    chunk indices throughout: a record that fails a gate has use = 0 and no split-read input, so it contributes nothing."""
+    from . import bam as bam_mod
+    chunk = bamfile.records(chrom, task_start, task_end)
+    on_device = not isinstance(ctx_or_fns, (tuple, list))
+    cols = bam_mod.decode(ctx_or_fns, chunk, host_outputs=False) if on_device else bam_mod.decode_host(chunk)
+    start, end, flag, mapq, qlen = cols["ref_start"], cols["ref_end"], cols["flag"], cols["mapq"], cols["query_len"]
+    gate = (cols["cls"] != 0) & (start >= task_start)
+    if bed_regions is not None:
+        in_bed = np.zeros(chunk.n, bool)
+        for b0, b1 in bed_regions:                           # not (pos_end <= b0 or pos_start >= b1)
+            in_bed |= (end > b0) & (start < b1)
+        gate &= in_bed
+    parsed = gate & (qlen >= min_read_len)                    # the reads parse_read does not return from at once (:607)
+    use = (parsed & (mapq >= min_mapq)).astype(np.uint8)
+    kw = dict(min_siglength=min_siglength, merge_ins_threshold=merge_ins_threshold, merge_del_threshold=merge_del_threshold)
+    if on_device:
+        sig = cigar_signatures(ctx_or_fns, None, None, None, use, from_bam=cols, **kw)
+        split_fn = lambda enc, **k: split_signatures(ctx_or_fns, enc, **k)             # noqa: E731
+    else:
+        cigar_fn, split_fn = ctx_or_fns
+        sig = cigar_fn(cols["cig_off"], cols["cigar"], start, use, **kw)
+    names, seqs = _Lazy(chunk.name), _Lazy(chunk.sequence)
+    sp = []
+    has_sa = cols["sa_off"][1:] > cols["sa_off"][:-1]
+    for i in np.flatnonzero(parsed & (cols["cls"] == 1) & has_sa).tolist():     # primary records with an SA tag: few
+        primary = _primary_info(int(flag[i]), mapq[i] >= min_mapq, int(cols["clip_left"][i]), int(cols["clip_right"][i]), int(qlen[i]),
+                                int(start[i]), int(end[i]), chrom)
+        sp.append((i, primary, chunk.sa_values(cols, i), int(qlen[i]), int(flag[i]) == 16))
+    cand = _assemble(sig, names, seqs, sp, chrom, chrom_rank, sv_size, min_mapq, max_split_parts, max_size, split_fn)
+    reads_info = [(int(start[i]), int(end[i]), 1 if cols["cls"][i] == 1 else 0, names[i], chrom) for i in np.flatnonzero(gate & (mapq >= min_mapq)).tolist()]
     return cand, reads_info

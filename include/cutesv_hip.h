@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define CSV_ABI_VERSION 8
+#define CSV_ABI_VERSION 9
 
 /* SV types: one (chromosome, type) pair is one segment == one reference pool task
  * (MAIN:1116-1189).  Order of the enum is irrelevant to results. */
@@ -461,7 +461,10 @@ typedef struct csv_cigar_in {
     int64_t         read_base;
     const int32_t*  query_len;      /* n_reads or NULL */
 } csv_cigar_in;
-enum { CSV_CG_TO_POOL = 1 };
+enum { CSV_CG_TO_POOL = 1,
+       /* cig_off, cigar and ref_start are NOT read from `in`: they are the device columns the context's last csv_bam_decode
+        * made (n_reads must be its record count).  `use` is still the caller's host array.  The CIGARs never cross PCIe. */
+       CSV_CG_FROM_BAM = 2 };
 
 typedef struct csv_cigar_out {
     int64_t  cap_sig_ins, cap_piece_ins, cap_sig_del;
@@ -620,6 +623,89 @@ typedef struct csv_rows_in {
 
 /* Writes the rows into `out` (capacity `cap`) and returns CSV_OK, or CSV_E_CAPACITY with *n_written = the need. */
 int csv_rows_emit(const csv_rows_in* in, char* out, int64_t cap, int64_t* n_written);
+
+/* ---------------------------------------------------------------------------------------------
+ * Native BAM reader: a coordinate-sorted .bam -> the columns the extraction entries take.
+ *
+ * Host side (no GPU, no context): csv_bam_open maps the file, indexes its BGZF blocks, reads the BAM header and refuses a
+ * file whose blocks are truncated or whose end-of-file block is missing.  csv_bam_read inflates blocks on `threads` host
+ * threads, walks the block_size chain and hands out one chunk: the records of reference `refid` (-1: the unmapped tail)
+ * that overlap [beg, end) - pos < end and pos + max(reference span, 1) > beg - at most max_records of them.  No index
+ * file is used: the scan starts at the contig (or where the previous region of the same contig started) and stops at the
+ * first record with pos >= end.  CSV_BAM_RESTART begins a new scan; without it the call continues behind the previous
+ * chunk (more = 1 said there is one).  CSV_BAM_COUNT_ONLY counts records and packs nothing.
+ *
+ * A chunk is two byte images.  `slim` goes to the device: per record the 32 fixed bytes that follow block_size, the CIGAR
+ * words and the aux bytes, rec_len[i] bytes at rec_off[i] (16-byte aligned, zero padded).  `host` stays behind: per
+ * record the read name (l_read_name bytes, NUL included) and the 4-bit sequence, at host_off[i] .. host_off[i + 1].
+ * Qualities are dropped.  The arrays belong to the reader and live until its next csv_bam_read / csv_bam_close.
+ */
+typedef struct csv_bam csv_bam;
+
+typedef struct csv_bam_chunk {
+    int64_t         n_records;
+    int32_t         more;            /* 1: max_records was reached, the next call (without CSV_BAM_RESTART) continues */
+    int32_t         reserved;
+    const uint8_t*  slim;   int64_t slim_bytes;
+    const int64_t*  rec_off;         /* n_records */
+    const uint32_t* rec_len;         /* n_records */
+    const uint8_t*  host;   int64_t host_bytes;
+    const int64_t*  host_off;        /* n_records + 1 */
+    int64_t         record_bytes;    /* inflated bytes of the chunk's records (block_size words included) */
+    int64_t         inflated_bytes, compressed_bytes;    /* BGZF blocks inflated during the call */
+    double          ms_inflate, ms_frame;                /* host wall time: inflate; framing + packing */
+} csv_bam_chunk;
+enum { CSV_BAM_RESTART = 1, CSV_BAM_COUNT_ONLY = 2 };
+
+int         csv_bam_open(const char* path, int threads, csv_bam** out, char* err, int err_cap);
+void        csv_bam_close(csv_bam* bam);
+const char* csv_bam_error(const csv_bam* bam);
+/* names: n_ref NUL-terminated strings back to back; text: the SAM header text (text_len bytes) */
+int         csv_bam_header(const csv_bam* bam, int32_t* n_ref, const char** names, const int64_t** lengths, const char** text, int64_t* text_len);
+int         csv_bam_read(csv_bam* bam, int32_t refid, int64_t beg, int64_t end, int64_t max_records, int32_t flags, csv_bam_chunk* out);
+/* sizeof of 0 csv_bam_chunk, 1 csv_bam_in, 2 csv_bam_out; -1 otherwise */
+int         csv_bam_struct_size(int which);
+
+/* Device side (bam.hip.h): the slim image of a chunk -> per-record columns, the packed CIGARs and the byte ranges of the
+ * SA / CG tags, in device memory of the context (valid until its next csv_bam_decode; csv_cigar_signatures with
+ * CSV_CG_FROM_BAM scans them in place) and, for every host array that is not NULL, in the caller's memory.
+ *   ref_start = pos, query_len = l_seq, ref_end = pos + lengths of M D N = X, clip_left / clip_right = length of the
+ *   first / last CIGAR operation when it is S or H (else 0), cls = 0 secondary (flag 256 / 272), 1 primary (flag 0 / 16),
+ *   2 other.  A record whose CIGAR is the placeholder <l_seq>S<n>N and that carries a CG:B,I tag (more than 65 535
+ *   operations) is decoded from the tag.  sa_beg / sa_end: byte ranges, in `slim`, of the values of the record's SA:Z
+ *   tags (sa_off[i] .. sa_off[i + 1], in tag order, NUL excluded); cg_beg / cg_end: of the CG array's words, -1 if none.
+ * The aux walk knows the types A c C s S i I f Z H and B (subtypes c C s S i I f).  Any other type byte, or a value that
+ * runs past the record, sets status[i] != 0, and the call fails with CSV_E_INVALID after the host arrays are filled.
+ * CSV_E_CAPACITY: cap_ops / cap_sa are too small, n_ops / n_sa hold the need.
+ */
+typedef struct csv_bam_in {
+    int64_t         n_records;
+    const uint8_t*  slim;   int64_t slim_bytes;
+    const int64_t*  rec_off;
+    const uint32_t* rec_len;
+    int32_t         flags;           /* 0 */
+    int32_t         reserved;
+} csv_bam_in;
+
+typedef struct csv_bam_out {
+    int64_t  cap_ops, cap_sa;        /* capacities of the host arrays cigar / sa_beg, sa_end */
+    int64_t  n_ops, n_sa;            /* out */
+    /* host arrays, each may be NULL: n_records entries (cig_off, sa_off: n_records + 1) */
+    int64_t* ref_start;  int64_t* ref_end;  int32_t* flag;  int32_t* mapq;  int32_t* query_len;
+    int32_t* clip_left;  int32_t* clip_right;  uint8_t* cls;  uint8_t* status;
+    int64_t* cig_off;  uint32_t* cigar;
+    int64_t* sa_off;  int64_t* sa_beg;  int64_t* sa_end;
+    int64_t* cg_beg;  int64_t* cg_end;
+    /* out: the same columns in device memory */
+    void* dev_ref_start;  void* dev_ref_end;  void* dev_flag;  void* dev_mapq;  void* dev_query_len;
+    void* dev_clip_left;  void* dev_clip_right;  void* dev_cls;  void* dev_cig_off;  void* dev_cigar;
+    int64_t  bytes_uploaded;         /* out: slim image + offsets */
+    int64_t  n_bad;                  /* out: records with status != 0 */
+    float    ms_device;              /* out: kernels only (HIP events) */
+    float    ms_upload;              /* out: host -> device copies (HIP events) */
+} csv_bam_out;
+
+int csv_bam_decode(csv_ctx* ctx, const csv_bam_in* in, csv_bam_out* out);
 
 #ifdef __cplusplus
 }
