@@ -53,6 +53,8 @@ SYMBOLS = [
     ("csv_bam_read", C.c_int, None),           # prototype set in cutesv_amd/bam.py (needs its struct)
     ("csv_bam_struct_size", C.c_int, [C.c_int]),
     ("csv_bam_decode", C.c_int, None),         # prototype set in cutesv_amd/bam.py
+    ("csv_bam_split_inputs", C.c_int, None),   # prototype set in cutesv_amd/extract.py
+    ("csv_sa_struct_size", C.c_int, [C.c_int]),
     ("csv_fasta_index", C.c_int64, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
 ]
 

@@ -20,6 +20,7 @@
 #include "cigar.hip.h"
 #include "split.hip.h"
 #include "bam.hip.h"
+#include "sa.hip.h"
 
 using namespace csv;
 
@@ -116,7 +117,7 @@ struct csv_ctx {
     hipEvent_t  ev_init = nullptr, ev_sel = nullptr, ev_aux[3] = {}, ev_copy[N_COPY_STREAMS] = {}, ev_reads = nullptr, ev_anc = nullptr, ev_rd[5] = {};
     std::string err;
     hipEvent_t  ev[CSV_N_STAGES + 2] = {};
-    Arena       arena, arena_rb, arena_bam;
+    Arena       arena, arena_rb, arena_bam, arena_sa;
     // batch buffers (slices of `arena`)
     Buf seg, woff, seg_drop, a, b, rid, aux, a32, b32;
     Buf tile_lead, tabs;
@@ -154,7 +155,13 @@ struct csv_ctx {
     // bm_cigoff / bm_cigar / bm_start in place; the SA ranges are sized after the scan, so they stand alone)
     Buf bm_slim, bm_recoff, bm_reclen, bm_start, bm_end, bm_flag, bm_mapq, bm_qlen, bm_cl, bm_cr, bm_cls, bm_status, bm_cigoff, bm_saoff, bm_cigsrc,
         bm_cgb, bm_cge, bm_cigar, bm_long, bm_cnt, bm_tot, bm_sabeg, bm_saend;
-    i64 bam_n = -1, bam_nops = 0;              // records / operations of the last successful decode (-1: none)
+    i64 bam_n = -1, bam_nops = 0, bam_nsa = 0; // records / operations / SA tags of the last successful decode (-1: none)
+    // split inputs of the last decode (csv_bam_split_inputs; sa.hip.h): the tables sized before the kernels run are slices of
+    // `arena_sa`, the entry columns are sized by the count pass and stand alone.  They live until the next decode or the next
+    // csv_bam_split_inputs: csv_split_signatures with CSV_SP_FROM_BAM reads them in place.
+    Buf sa_sel, sa_names, sa_nameoff, sa_namerank, sa_calloff, sa_callrec, sa_callsa, sa_entoff, sa_readlen, sa_status, sa_tot;
+    Buf sa_c0, sa_c1, sa_f0, sa_f1, sa_chr, sa_mapq, sa_strand, sa_primary;
+    i64 sa_calls = -1, sa_entries = 0;         // calls / entries the context holds (-1: no split inputs)
     // page-locked host staging: small tables on the way in, counters + call records + support lists on the way out
     char*  h_pin = nullptr;
     size_t h_pin_cap = 0;
@@ -455,11 +462,13 @@ void csv_ctx_destroy(csv_ctx* c)
     if (!c) return;
     (void)hipSetDevice(c->device);
     (void)hipDeviceSynchronize();
-    Buf* own[] = {&c->pool_seg, &c->pool_a, &c->pool_b, &c->pool_read, &c->pool_aux, &c->sp_qlen, &c->sqrt_tab, &c->rcp_tab, &c->cipk_tab, &c->cnt, &c->rstate, &c->gs_chrom, &c->gs_perm0, &c->gs_perm1, &c->gs_hist, &c->gs_tot, &c->flush, &c->bm_sabeg, &c->bm_saend};
+    Buf* own[] = {&c->pool_seg, &c->pool_a, &c->pool_b, &c->pool_read, &c->pool_aux, &c->sp_qlen, &c->sqrt_tab, &c->rcp_tab, &c->cipk_tab, &c->cnt, &c->rstate, &c->gs_chrom, &c->gs_perm0, &c->gs_perm1, &c->gs_hist, &c->gs_tot, &c->flush, &c->bm_sabeg, &c->bm_saend,
+                  &c->sa_c0, &c->sa_c1, &c->sa_f0, &c->sa_f1, &c->sa_chr, &c->sa_mapq, &c->sa_strand, &c->sa_primary};
     for (Buf* b : own) if (b->p) (void)hipFree(b->p);
     if (c->arena.base) (void)hipFree(c->arena.base);
     if (c->arena_rb.base) (void)hipFree(c->arena_rb.base);
     if (c->arena_bam.base) (void)hipFree(c->arena_bam.base);
+    if (c->arena_sa.base) (void)hipFree(c->arena_sa.base);
     if (c->h_pin) (void)hipHostFree(c->h_pin);
     if (c->h_flag) (void)hipHostFree((void*)c->h_flag);
     if (c->h_pub) (void)hipHostFree(c->h_pub);
@@ -2152,22 +2161,34 @@ int csv_split_signatures(csv_ctx* c, const csv_split_in* in, csv_split_out* out)
     if (!c || !in || !out) return CSV_E_INVALID;
     HIP_TRY(c, hipSetDevice(c->device));
     out->n = 0; out->ms_device = 0;
-    const i64 n = in->n_reads;
-    if (n < 0 || (n > 0 && (!in->ent_off || !in->read_len))) return fail(c, CSV_E_INVALID, "bad split-read batch header");
+    // CSV_SP_FROM_BAM: the reads are the calls csv_bam_split_inputs left on the device, with its entry columns (offsets from
+    // its own scan: they start at 0, do not decrease and end at its entry count)
+    const bool from_bam = (in->flags & CSV_SP_FROM_BAM) != 0;
+    if (from_bam && (c->sa_calls < 0 || c->bam_n < 0)) return fail(c, CSV_E_INVALID, "CSV_SP_FROM_BAM: the context holds no split inputs (csv_bam_split_inputs after the last csv_bam_decode)");
+    const i64 n = from_bam ? c->sa_calls : in->n_reads;
+    if (n < 0 || (n > 0 && !from_bam && (!in->ent_off || !in->read_len))) return fail(c, CSV_E_INVALID, "bad split-read batch header");
     if (n == 0) return CSV_OK;
-    const i64 ne = in->ent_off[n] - in->ent_off[0];
-    if (in->ent_off[0] != 0 || ne < 0) return fail(c, CSV_E_INVALID, "ent_off must start at 0 and not decrease");
-    if (ne > 0 && (!in->c0 || !in->c1 || !in->f0 || !in->f1 || !in->chr || !in->mapq || !in->strand || !in->primary))
-        return fail(c, CSV_E_INVALID, "split-read entry columns missing");
+    const i64 ne = from_bam ? c->sa_entries : in->ent_off[n] - in->ent_off[0];
+    if (!from_bam) {
+        if (in->ent_off[0] != 0 || ne < 0) return fail(c, CSV_E_INVALID, "ent_off must start at 0 and not decrease");
+        if (ne > 0 && (!in->c0 || !in->c1 || !in->f0 || !in->f1 || !in->chr || !in->mapq || !in->strand || !in->primary))
+            return fail(c, CSV_E_INVALID, "split-read entry columns missing");
+    }
     if (ne >= (1ll << 31) - 4096 || n >= (1ll << 31) - 4096) return fail(c, CSV_E_INVALID, "split-read batch too large: split it");
-    for (i64 r = 0; r < n; r++)
+    for (i64 r = 0; r < n && !from_bam; r++)
         if (in->ent_off[r + 1] < in->ent_off[r]) return fail(c, CSV_E_INVALID, "ent_off decreases at read %lld", (long long)r);
     const int ntile = div_up(n, CG_TILE);
-    const i64 cap = out->cap < 0 ? 0 : out->cap;
+    // the candidate columns are sized for what the caller allows, but never for more than the entries can yield: a read of s
+    // segments emits nothing for s < 2, at most 3 candidates for s = 2 and at most 12 per window of three plus 2 for s >= 3
+    // (split_read: the rules of one window that can fire together put 2 + 2 + 6 + 2) - at most 12 per entry either way
+    const i64 cap_max = 12 * ne, cap = out->cap < 0 ? 0 : out->cap < cap_max ? out->cap : cap_max;
     Plan P;
 #define PL(buf, bytes) P.add(c->buf, (size_t)(bytes))
-    PL(sp_off, (n + 1) * 8); PL(sp_len, n * 8); PL(sp_c0, (ne + 1) * 8); PL(sp_c1, (ne + 1) * 8); PL(sp_f0, (ne + 1) * 8); PL(sp_f1, (ne + 1) * 8);
-    PL(sp_chr, (ne + 1) * 4); PL(sp_mapq, (ne + 1) * 4); PL(sp_strand, ne + 1); PL(sp_primary, ne + 1); PL(sp_seg, (ne + 1) * sizeof(SpSeg));
+    if (!from_bam) {
+        PL(sp_off, (n + 1) * 8); PL(sp_len, n * 8); PL(sp_c0, (ne + 1) * 8); PL(sp_c1, (ne + 1) * 8); PL(sp_f0, (ne + 1) * 8); PL(sp_f1, (ne + 1) * 8);
+        PL(sp_chr, (ne + 1) * 4); PL(sp_mapq, (ne + 1) * 4); PL(sp_strand, ne + 1); PL(sp_primary, ne + 1);
+    }
+    PL(sp_seg, (ne + 1) * sizeof(SpSeg));
     PL(sp_cnt, n * 16); PL(sp_tiles, (size_t)ntile * 24); PL(sp_tot, 32);
     PL(sp_kind, cap + 1); PL(sp_read, (cap + 1) * 4); PL(sp_ochr, (cap + 1) * 4); PL(sp_aux, (cap + 1) * 4);
     PL(sp_a, (cap + 1) * 8); PL(sp_b, (cap + 1) * 8); PL(sp_c, (cap + 1) * 8); PL(sp_d, (cap + 1) * 8);
@@ -2178,7 +2199,7 @@ int csv_split_signatures(csv_ctx* c, const csv_split_in* in, csv_split_out* out)
         if (rc) return rc;
     }
     hipStream_t st = c->stream;
-#define H2D(buf, src, bytes) do { if ((bytes) > 0) HIP_TRY(c, hipMemcpyAsync(c->buf.p, (src), (size_t)(bytes), hipMemcpyHostToDevice, st)); } while (0)
+#define H2D(buf, src, bytes) do { if ((bytes) > 0 && !from_bam) HIP_TRY(c, hipMemcpyAsync(c->buf.p, (src), (size_t)(bytes), hipMemcpyHostToDevice, st)); } while (0)
     H2D(sp_off, in->ent_off, (n + 1) * 8); H2D(sp_len, in->read_len, n * 8);
     H2D(sp_c0, in->c0, ne * 8); H2D(sp_c1, in->c1, ne * 8); H2D(sp_f0, in->f0, ne * 8); H2D(sp_f1, in->f1, ne * 8);
     H2D(sp_chr, in->chr, ne * 4); H2D(sp_mapq, in->mapq, ne * 4); H2D(sp_strand, in->strand, ne); H2D(sp_primary, in->primary, ne);
@@ -2187,6 +2208,11 @@ int csv_split_signatures(csv_ctx* c, const csv_split_in* in, csv_split_out* out)
     A.n_reads = n; A.ent_off = dp<i64>(c->sp_off); A.read_len = dp<i64>(c->sp_len);
     A.c0 = dp<i64>(c->sp_c0); A.c1 = dp<i64>(c->sp_c1); A.f0 = dp<i64>(c->sp_f0); A.f1 = dp<i64>(c->sp_f1);
     A.chr = dp<int>(c->sp_chr); A.mapq = dp<int>(c->sp_mapq); A.strand = dp<uint8_t>(c->sp_strand); A.primary = dp<uint8_t>(c->sp_primary);
+    if (from_bam) {
+        A.ent_off = dp<i64>(c->sa_entoff); A.read_len = dp<i64>(c->sa_readlen);
+        A.c0 = dp<i64>(c->sa_c0); A.c1 = dp<i64>(c->sa_c1); A.f0 = dp<i64>(c->sa_f0); A.f1 = dp<i64>(c->sa_f1);
+        A.chr = dp<int>(c->sa_chr); A.mapq = dp<int>(c->sa_mapq); A.strand = dp<uint8_t>(c->sa_strand); A.primary = dp<uint8_t>(c->sa_primary);
+    }
     A.sv = in->sv_size; A.max_size = in->max_size; A.min_mapq = in->min_mapq; A.parts = in->max_split_parts;
     A.seg = dp<SpSeg>(c->sp_seg); A.cnt = dp<int4>(c->sp_cnt); A.cap = cap;
     A.kind = dp<uint8_t>(c->sp_kind); A.read = dp<int>(c->sp_read); A.o_chr = dp<int>(c->sp_ochr); A.aux = dp<int>(c->sp_aux);
@@ -2205,20 +2231,24 @@ int csv_split_signatures(csv_ctx* c, const csv_split_in* in, csv_split_out* out)
     HIP_TRY(c, hipStreamSynchronize(st));
     out->n = tot[0];
     if (tot[0] > out->cap) return fail(c, CSV_E_CAPACITY, "need %lld candidates", (long long)tot[0]);
+    if (tot[0] < 0 || tot[0] > cap_max) return fail(c, CSV_E_INVALID, "split-read analysis: inconsistent count (%lld candidates of %lld entries)", (long long)tot[0], (long long)ne);
     HIP_TRY(c, hipEventRecord(c->ev[2], st));
     hipLaunchKernelGGL(k_split_emit, dim3(grid), dim3(256), 0, st, A);
     HIP_TRY(c, hipEventRecord(c->ev[3], st));
     HIP_TRY(c, hipGetLastError());
     const bool to_pool = (in->flags & CSV_CG_TO_POOL) != 0;
     if (to_pool && tot[0] > 0) {
-        if (in->read_base < 0 || in->read_base + n >= (1ll << 31)) return fail(c, CSV_E_INVALID, "read_base out of range");
+        // (CSV_SP_FROM_BAM: a row's read is the call's RECORD - the index space of the CIGAR scan's rows of the chunk - and the
+        // query length is the decode's, which is what read_len holds per call)
+        if (in->read_base < 0 || in->read_base + (from_bam ? c->bam_n : n) >= (1ll << 31)) return fail(c, CSV_E_INVALID, "read_base out of range");
         { const int rc = pool_reserve(c, tot[0]); if (rc) return rc; }
-        if (in->query_len) { const int rc = reserve(c, c->sp_qlen, (size_t)n * 4); if (rc) return rc; HIP_TRY(c, hipMemcpyAsync(c->sp_qlen.p, in->query_len, (size_t)n * 4, hipMemcpyHostToDevice, st)); }
+        const bool own_qlen = in->query_len && !from_bam;
+        if (own_qlen) { const int rc = reserve(c, c->sp_qlen, (size_t)n * 4); if (rc) return rc; HIP_TRY(c, hipMemcpyAsync(c->sp_qlen.p, in->query_len, (size_t)n * 4, hipMemcpyHostToDevice, st)); }
         PoolCols PC{dp<int>(c->pool_seg), dp<i64>(c->pool_a), dp<i64>(c->pool_b), dp<int>(c->pool_read), dp<int>(c->pool_aux)};
         PoolSegBase SB{};
         for (int k = 0; k < 5; k++) SB.b[k] = in->pool_seg_base[k];
         hipLaunchKernelGGL(k_pool_from_split, dim3(div_up(tot[0], 256)), dim3(256), 0, st, PC, c->pool_n, A, tot[0], SB, in->read_base,
-                           in->query_len ? dp<int>(c->sp_qlen) : nullptr);
+                           own_qlen ? dp<int>(c->sp_qlen) : nullptr, from_bam ? dp<int>(c->sa_callrec) : nullptr);
         HIP_TRY(c, hipGetLastError());
         c->pool_n += tot[0];
     }
@@ -2241,7 +2271,7 @@ int csv_bam_decode(csv_ctx* c, const csv_bam_in* in, csv_bam_out* out)
     out->n_ops = out->n_sa = out->n_bad = out->bytes_uploaded = 0; out->ms_device = out->ms_upload = 0;
     out->dev_ref_start = out->dev_ref_end = out->dev_flag = out->dev_mapq = out->dev_query_len = out->dev_clip_left = out->dev_clip_right =
         out->dev_cls = out->dev_cig_off = out->dev_cigar = nullptr;
-    c->bam_n = -1;
+    c->bam_n = -1; c->sa_calls = -1;
     const i64 n = in->n_records, nb = in->slim_bytes;
     if (n < 0 || nb < 0 || in->flags != 0 || (n > 0 && (!in->slim || !in->rec_off || !in->rec_len))) return fail(c, CSV_E_INVALID, "bad BAM chunk header");
     if (n >= (1ll << 31) - 4096) return fail(c, CSV_E_INVALID, "BAM chunk too large (%lld records): split it", (long long)n);
@@ -2250,7 +2280,7 @@ int csv_bam_decode(csv_ctx* c, const csv_bam_in* in, csv_bam_out* out)
         const i64 o = in->rec_off[r], l = in->rec_len[r];
         if (o < 0 || (o & 15) || l < 32 || o > nb || l > nb - o) return fail(c, CSV_E_INVALID, "record %lld of the BAM chunk leaves the slim image (or is misaligned / shorter than 32 bytes)", (long long)r);
     }
-    if (n == 0) { c->bam_n = 0; c->bam_nops = 0; if (out->cig_off) out->cig_off[0] = 0; if (out->sa_off) out->sa_off[0] = 0; return CSV_OK; }
+    if (n == 0) { c->bam_n = 0; c->bam_nops = 0; c->bam_nsa = 0; if (out->cig_off) out->cig_off[0] = 0; if (out->sa_off) out->sa_off[0] = 0; return CSV_OK; }
     const i64 max_ops = nb / 4;                              // every operation is 4 bytes of the image
     Plan P;
 #define PL(buf, bytes) P.add(c->buf, (size_t)(bytes))
@@ -2319,7 +2349,126 @@ int csv_bam_decode(csv_ctx* c, const csv_bam_in* in, csv_bam_out* out)
     if (cnt[1] > 0) return fail(c, CSV_E_INVALID, "%d record(s) of the BAM chunk have a malformed aux area or CIGAR (see status)", cnt[1]);
     out->dev_ref_start = c->bm_start.p; out->dev_ref_end = c->bm_end.p; out->dev_flag = c->bm_flag.p; out->dev_mapq = c->bm_mapq.p; out->dev_query_len = c->bm_qlen.p;
     out->dev_clip_left = c->bm_cl.p; out->dev_clip_right = c->bm_cr.p; out->dev_cls = c->bm_cls.p; out->dev_cig_off = c->bm_cigoff.p; out->dev_cigar = c->bm_cigar.p;
-    c->bam_n = n; c->bam_nops = tot[0];
+    c->bam_n = n; c->bam_nops = tot[0]; c->bam_nsa = tot[1];
+    return CSV_OK;
+}
+
+int csv_sa_struct_size(int which)
+{
+    switch (which) {
+    case 0: return (int)sizeof(csv_sa_in);
+    case 1: return (int)sizeof(csv_sa_out);
+    default: return -1;
+    }
+}
+
+int csv_bam_split_inputs(csv_ctx* c, const csv_sa_in* in, csv_sa_out* out)
+{
+    if (!c || !in || !out) return CSV_E_INVALID;
+    HIP_TRY(c, hipSetDevice(c->device));
+    out->n_calls = out->n_entries = out->n_flagged = 0; out->ms_device = 0;
+    c->sa_calls = -1;
+    const i64 n = in->n_records, nn = in->n_names, nbytes = in->name_bytes;
+    if (c->bam_n < 0) return fail(c, CSV_E_INVALID, "csv_bam_split_inputs: the context holds no decoded BAM chunk");
+    if (n != c->bam_n) return fail(c, CSV_E_INVALID, "csv_bam_split_inputs: n_records is not the record count of the context's last csv_bam_decode");
+    if (in->flags != 0 || nn < 0 || nbytes < 0 || (n > 0 && !in->sel) || (nn > 0 && (!in->name_off || !in->name_rank)) || (nbytes > 0 && !in->names))
+        return fail(c, CSV_E_INVALID, "bad split-input header");
+    // the kernels index `names` with these offsets and search the table by halving: both are checked here
+    for (i64 k = 0; k < nn; k++) {
+        const i64 b = in->name_off[k], e = in->name_off[k + 1];
+        if (b < 0 || e < b || e > nbytes) return fail(c, CSV_E_INVALID, "name_off decreases or leaves the name bytes at name %lld", (long long)k);
+        if (k > 0) {
+            const i64 pb = in->name_off[k - 1], pl = b - pb, l = e - b;
+            int cmp = memcmp(in->names + pb, in->names + b, (size_t)(pl < l ? pl : l));
+            if (cmp == 0) cmp = pl < l ? -1 : pl > l ? 1 : 0;
+            if (cmp >= 0) return fail(c, CSV_E_INVALID, "the contig names are not strictly ascending in byte order at name %lld", (long long)k);
+        }
+    }
+    const i64 max_calls = c->bam_nsa;                        // every call is an SA tag of the chunk
+    if (n == 0 || max_calls == 0) {
+        if (out->ent_off) out->ent_off[0] = 0;
+        c->sa_calls = 0; c->sa_entries = 0;
+        return CSV_OK;
+    }
+    Plan P;
+#define PL(buf, bytes) P.add(c->buf, (size_t)(bytes))
+    PL(sa_sel, n); PL(sa_names, nbytes + 1); PL(sa_nameoff, (nn + 1) * 8); PL(sa_namerank, (nn + 1) * 4);
+    PL(sa_calloff, (n + 1) * 8); PL(sa_callrec, (max_calls + 1) * 4); PL(sa_callsa, (max_calls + 1) * 8); PL(sa_entoff, (max_calls + 1) * 8);
+    PL(sa_readlen, (max_calls + 1) * 8); PL(sa_status, max_calls + 1); PL(sa_tot, 32);
+#undef PL
+    {
+        if (P.total > c->arena_sa.cap) HIP_TRY(c, hipDeviceSynchronize());
+        const int rc = commit(c, c->arena_sa, P);
+        if (rc) return rc;
+    }
+    hipStream_t st = c->stream;
+    HIP_TRY(c, hipMemcpyAsync(c->sa_sel.p, in->sel, (size_t)n, hipMemcpyHostToDevice, st));
+    if (nbytes) HIP_TRY(c, hipMemcpyAsync(c->sa_names.p, in->names, (size_t)nbytes, hipMemcpyHostToDevice, st));
+    if (nn) {
+        HIP_TRY(c, hipMemcpyAsync(c->sa_nameoff.p, in->name_off, (size_t)(nn + 1) * 8, hipMemcpyHostToDevice, st));
+        HIP_TRY(c, hipMemcpyAsync(c->sa_namerank.p, in->name_rank, (size_t)nn * 4, hipMemcpyHostToDevice, st));
+    }
+    HIP_TRY(c, hipMemsetAsync(c->sa_tot.p, 0, 32, st));
+    SaArgs A{};
+    A.n = n; A.cap_calls = max_calls; A.cap_entries = 0;
+    A.slim = dp<uint8_t>(c->bm_slim); A.sa_off = dp<i64>(c->bm_saoff); A.sa_beg = dp<i64>(c->bm_sabeg); A.sa_end = dp<i64>(c->bm_saend);
+    A.flag = dp<int>(c->bm_flag); A.mapq = dp<int>(c->bm_mapq); A.qlen = dp<int>(c->bm_qlen); A.clip_l = dp<int>(c->bm_cl); A.clip_r = dp<int>(c->bm_cr);
+    A.ref_start = dp<i64>(c->bm_start); A.ref_end = dp<i64>(c->bm_end);
+    A.sel = dp<uint8_t>(c->sa_sel); A.min_mapq = in->min_mapq; A.task_rank = in->task_rank;
+    A.names = dp<uint8_t>(c->sa_names); A.name_off = dp<i64>(c->sa_nameoff); A.name_rank = dp<int>(c->sa_namerank); A.n_names = (int)nn;
+    A.call_off = dp<i64>(c->sa_calloff); A.call_rec = dp<int>(c->sa_callrec); A.call_sa = dp<i64>(c->sa_callsa); A.ent_off = dp<i64>(c->sa_entoff);
+    A.read_len = dp<i64>(c->sa_readlen); A.status = dp<uint8_t>(c->sa_status); A.tot = dp<i64>(c->sa_tot);
+    HIP_TRY(c, hipEventRecord(c->ev[0], st));
+    hipLaunchKernelGGL(k_sa_mark, dim3(div_up(n, 256)), dim3(256), 0, st, A);
+    hipLaunchKernelGGL(k_sa_scan, dim3(1), dim3(1024), 0, st, A.call_off, n, (const i64*)nullptr, n, A.tot);
+    hipLaunchKernelGGL(k_sa_calls, dim3(div_up(n, 256)), dim3(256), 0, st, A);
+    hipLaunchKernelGGL(k_sa_parse<false>, dim3(max_calls < 8192 ? (int)max_calls : 8192), dim3(64), 0, st, A);
+    hipLaunchKernelGGL(k_sa_scan, dim3(1), dim3(1024), 0, st, A.ent_off, (i64)0, (const i64*)A.tot, max_calls, A.tot + 1);
+    HIP_TRY(c, hipEventRecord(c->ev[1], st));
+    HIP_TRY(c, hipGetLastError());
+    i64 tot[3] = {0, 0, 0};
+    HIP_TRY(c, hipMemcpyAsync(tot, c->sa_tot.p, 24, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    // (what the kernels counted is bounded by the text they counted it in; anything else would be a bug here, not in the file)
+    if (tot[0] < 0 || tot[0] > max_calls || tot[1] < 0 || tot[1] > c->bm_slim.cap + max_calls || tot[2] < 0 || tot[2] > tot[0])
+        return fail(c, CSV_E_INVALID, "split inputs: inconsistent counts (%lld calls, %lld entries)", (long long)tot[0], (long long)tot[1]);
+    const i64 nc = tot[0], ne = tot[1];
+    out->n_calls = nc; out->n_entries = ne; out->n_flagged = tot[2];
+    float ms1 = 0, ms2 = 0;
+    HIP_TRY(c, hipEventElapsedTime(&ms1, c->ev[0], c->ev[1]));
+    out->ms_device = ms1;
+    const bool want_calls = out->ent_off || out->read_len || out->call_rec || out->status;
+    const bool want_entries = out->c0 || out->c1 || out->f0 || out->f1 || out->chr || out->mapq || out->strand || out->primary;
+    if ((want_calls && nc > out->cap_calls) || (want_entries && ne > out->cap_entries))
+        return fail(c, CSV_E_CAPACITY, "need %lld calls / %lld entries", (long long)nc, (long long)ne);
+    {
+        int rc = reserve(c, c->sa_c0, (size_t)(ne + 1) * 8);
+        if (!rc) rc = reserve(c, c->sa_c1, (size_t)(ne + 1) * 8);
+        if (!rc) rc = reserve(c, c->sa_f0, (size_t)(ne + 1) * 8);
+        if (!rc) rc = reserve(c, c->sa_f1, (size_t)(ne + 1) * 8);
+        if (!rc) rc = reserve(c, c->sa_chr, (size_t)(ne + 1) * 4);
+        if (!rc) rc = reserve(c, c->sa_mapq, (size_t)(ne + 1) * 4);
+        if (!rc) rc = reserve(c, c->sa_strand, (size_t)ne + 1);
+        if (!rc) rc = reserve(c, c->sa_primary, (size_t)ne + 1);
+        if (rc) return rc;
+    }
+    A.cap_entries = ne;
+    A.c0 = dp<i64>(c->sa_c0); A.c1 = dp<i64>(c->sa_c1); A.f0 = dp<i64>(c->sa_f0); A.f1 = dp<i64>(c->sa_f1);
+    A.chr = dp<int>(c->sa_chr); A.emapq = dp<int>(c->sa_mapq); A.strand = dp<uint8_t>(c->sa_strand); A.primary = dp<uint8_t>(c->sa_primary);
+    if (nc > 0 && ne > 0) {
+        HIP_TRY(c, hipEventRecord(c->ev[2], st));
+        hipLaunchKernelGGL(k_sa_parse<true>, dim3(nc < 8192 ? (int)nc : 8192), dim3(64), 0, st, A);
+        HIP_TRY(c, hipEventRecord(c->ev[3], st));
+        HIP_TRY(c, hipGetLastError());
+    }
+#define D2H(dst, buf, bytes) do { if ((dst) && (bytes) > 0) HIP_TRY(c, hipMemcpyAsync((dst), c->buf.p, (size_t)(bytes), hipMemcpyDeviceToHost, st)); } while (0)
+    D2H(out->ent_off, sa_entoff, (nc + 1) * 8); D2H(out->read_len, sa_readlen, nc * 8); D2H(out->call_rec, sa_callrec, nc * 4); D2H(out->status, sa_status, nc);
+    D2H(out->c0, sa_c0, ne * 8); D2H(out->c1, sa_c1, ne * 8); D2H(out->f0, sa_f0, ne * 8); D2H(out->f1, sa_f1, ne * 8);
+    D2H(out->chr, sa_chr, ne * 4); D2H(out->mapq, sa_mapq, ne * 4); D2H(out->strand, sa_strand, ne); D2H(out->primary, sa_primary, ne);
+#undef D2H
+    HIP_TRY(c, hipStreamSynchronize(st));
+    if (nc > 0 && ne > 0) { HIP_TRY(c, hipEventElapsedTime(&ms2, c->ev[2], c->ev[3])); out->ms_device = ms1 + ms2; }
+    c->sa_calls = nc; c->sa_entries = ne;
     return CSV_OK;
 }
 

@@ -4,8 +4,8 @@
 // (:50-464).  A read contributes its primary alignment and the entries of its SA tag; each becomes a segment
 // [read_start, read_end, ref_start, ref_end, chr, strand]; the segments are sorted by read_start (stable) and walked with
 // the reference's two-segment and sliding three-segment rules, which emit INV / TRA / DUP / INS / DEL candidates.  The
-// text of the SA tag (and acquire_clip_pos on its CIGAR strings, :466-481) stays with pysam in the Python driver
-// (north_star): the input is flat per-entry numbers.
+// input is flat per-entry numbers: the text of the SA tag (and acquire_clip_pos on its CIGAR strings, :466-481) is parsed by
+// the caller (extract.encode_split_reads) or, for a chunk of the native BAM reader, by the kernels of sa.hip.h.
 //
 // One THREAD per read: a read has a handful of segments (--max_split_parts 7 by default) and the rules are scalar
 // branches on a few integers, so the parallelism is across the reads of a batch (a task region holds 10^4 - 10^5).  Two
@@ -193,7 +193,8 @@ __global__ __launch_bounds__(256) void k_split_emit(SplitArgs A)
 // CSV_CG_TO_POOL: the candidates as rows of the device-resident signature pool (cigar.hip.h PoolCols), in the columns the rebuild
 // sorts on (cutesv_amd/columns.py from_tuple_lists has the same encoding: INV aux = strand code, TRA aux = chr2 * 8 + type)
 struct PoolSegBase { int b[5]; };
-__global__ __launch_bounds__(256) void k_pool_from_split(PoolCols P, i64 base, SplitArgs A, i64 n, PoolSegBase sb, i64 read_base, const int* query_len)
+__global__ __launch_bounds__(256) void k_pool_from_split(PoolCols P, i64 base, SplitArgs A, i64 n, PoolSegBase sb, i64 read_base, const int* query_len,
+                                                         const int* read_map)       // CSV_SP_FROM_BAM: call -> record of the chunk (else NULL)
 {
     const i64 i = (i64)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
@@ -208,7 +209,7 @@ __global__ __launch_bounds__(256) void k_pool_from_split(PoolCols P, i64 base, S
     } else if (kind == 3) ax = aux;
     else if (kind == 4) ax = (int)(A.c[i] * 8 + aux);
     const i64 o = base + i;
-    P.seg[o] = sb.b[kind] + A.o_chr[i]; P.a[o] = a; P.b[o] = b; P.read[o] = (int)(read_base + r); P.aux[o] = ax;
+    P.seg[o] = sb.b[kind] + A.o_chr[i]; P.a[o] = a; P.b[o] = b; P.read[o] = (int)(read_base + (read_map ? read_map[r] : r)); P.aux[o] = ax;
 }
 
 }  // namespace csv

@@ -5,11 +5,13 @@ of a batch of reads -> the INS / DEL signatures parse_read + generate_combine_si
 of them.  `candidates` turns the flat result into the reference's candidate tuples (the inserted sequence is cut out of
 the reads' query sequences here: the bases never travel to the GPU).  `split_signatures` is the face of
 `csv_split_signatures` (split.hip.h): organize_split_signal + analysis_split_read (:50-513) on the numbers of a batch of
-primary alignments and SA-tag entries.  BAM decode, the SA text and everything else of the extraction stay in the Python
-driver with pysam, as north_star has it: a driver would collect
+primary alignments and SA-tag entries.  For a driver with pysam, BAM decode, the SA text (`encode_split_reads`) and
+everything else of the extraction stay in Python, as north_star has it: a driver would collect
 `read.cigartuples`, `read.reference_start`, `read.mapq >= min_mapq and read.query_length >= min_read_len` for a task's
 reads, make one call here, and extend candidate["INS"] / candidate["DEL"] with the result.  `single_pipe_bam` is the same task
-body fed from a BAM file by the native reader (cutesv_amd/bam.py): no pysam and no object per record.
+body fed from a BAM file by the native reader (cutesv_amd/bam.py): no pysam and no object per record.  With sa="device" the
+SA text is parsed where the decode left it (`split_inputs_bam`, the face of `csv_bam_split_inputs`, sa.hip.h) and
+`task_to_pool` takes a task's region of the file to rows of the context's device-resident pool with no Python per record.
 """
 import ctypes as C
 
@@ -184,24 +186,159 @@ def encode_split_reads(reads, chrom_rank):
     return out
 
 
-def _run_split(fn, handle, enc, sv_size, min_mapq, max_split_parts, max_size, check, pool=None):
-    a = {k: np.ascontiguousarray(v) for k, v in enc.items()}
-    n = len(a["read_len"])
-    ptr = lambda x: x.ctypes.data if len(x) else None                      # noqa: E731
-    sin = SplitIn(n_reads=n, ent_off=a["ent_off"].ctypes.data, read_len=ptr(a["read_len"]), c0=ptr(a["c0"]), c1=ptr(a["c1"]), f0=ptr(a["f0"]),
-                  f1=ptr(a["f1"]), chr=ptr(a["chr"]), mapq=ptr(a["mapq"]), strand=ptr(a["strand"]), primary=ptr(a["primary"]),
-                  sv_size=int(sv_size), max_size=int(max_size), min_mapq=int(min_mapq), max_split_parts=int(max_split_parts))
+# ------------------------------------------------------------------------------------ SA text parsed on the device
+class SaIn(C.Structure):
+    _fields_ = [("n_records", C.c_int64), ("sel", C.c_void_p), ("min_mapq", C.c_int32), ("task_rank", C.c_int32), ("n_names", C.c_int32), ("flags", C.c_int32),
+                ("names", C.c_void_p), ("name_bytes", C.c_int64), ("name_off", C.c_void_p), ("name_rank", C.c_void_p)]
+
+
+_SA_CALL = [("ent_off", np.int64), ("read_len", np.int64), ("call_rec", np.int32), ("status", np.uint8)]
+_SA_ENT = [("c0", np.int64), ("c1", np.int64), ("f0", np.int64), ("f1", np.int64), ("chr", np.int32), ("mapq", np.int32), ("strand", np.uint8), ("primary", np.uint8)]
+
+
+class SaOut(C.Structure):
+    _fields_ = ([("cap_calls", C.c_int64), ("cap_entries", C.c_int64), ("n_calls", C.c_int64), ("n_entries", C.c_int64), ("n_flagged", C.c_int64)]
+                + [(n, C.c_void_p) for n, _ in _SA_CALL + _SA_ENT] + [("ms_device", C.c_float), ("reserved", C.c_int32)])
+
+
+SA_ST_NUMBER, SA_ST_STRAND, SA_ST_CIGAR, SA_ST_FIELDS, SA_ST_NAME = 1, 2, 4, 8, 16
+_SA_STRICT_CIGAR = None
+
+
+def _sa_number(f, max_digits):
+    return 0 < len(f) <= max_digits and f.isdigit()          # (bytes.isdigit: ASCII digits only)
+
+
+def sa_names(names):
+    """the contig names of a name table as sa_status takes them: a frozenset of bytes, made once for many values"""
+    return frozenset(n.encode() if isinstance(n, str) else n for n in names)
+
+
+def sa_status(value, names):
+    """The strict grammar of the device parser (sa.hip.h) on the host: the status byte csv_bam_split_inputs gives a call with
+    this SA value (bytes, or str) when `names` are the contigs of its name table (`sa_names(...)`; any other iterable of
+    names is converted on every call).  0: the device parses the value itself, exactly as encode_split_reads would;
+    anything else: the call is flagged and goes through encode_split_reads."""
+    global _SA_STRICT_CIGAR
+    if _SA_STRICT_CIGAR is None:
+        import re
+        _SA_STRICT_CIGAR = re.compile(rb"(?:([0-9]{1,18})([MIDNSHP=XB]))+")
+    if isinstance(value, str):
+        value = value.encode()
+    known = names if isinstance(names, frozenset) else sa_names(names)
+    st = 0
+    for entry in value.split(b";")[:-1]:
+        f = entry.split(b",")
+        if f[0] not in known:
+            st |= SA_ST_NAME
+        if len(f) > 1 and not _sa_number(f[1], 18):
+            st |= SA_ST_NUMBER
+        if len(f) > 2 and len(f[2]) != 1:
+            st |= SA_ST_STRAND
+        if len(f) > 3 and f[3] != b"*":
+            if not _SA_STRICT_CIGAR.fullmatch(f[3]):
+                st |= SA_ST_CIGAR
+            elif clip_and_span(f[3].decode())[2] > 1 << 62:      # (the device sums in 64 bits)
+                st |= SA_ST_CIGAR
+        if len(f) > 4 and not _sa_number(f[4], 9):
+            st |= SA_ST_NUMBER
+        if len(f) < 5:
+            st |= SA_ST_FIELDS
+    return st
+
+
+def _name_table(chrom_rank):
+    """chrom_rank -> (names back to back in byte order, offsets, the caller's ranks in that order)"""
+    items = sorted((k.encode(), int(r)) for k, r in chrom_rank.items())
+    off = np.zeros(len(items) + 1, np.int64)
+    if items:
+        np.cumsum([len(k) for k, _ in items], out=off[1:])
+    blob = np.frombuffer(b"".join(k for k, _ in items), np.uint8)
+    return blob, off, np.asarray([r for _, r in items], np.int32)
+
+
+def split_inputs_bam(ctx, chunk, cols, sel, chrom_rank, chrom, min_mapq, host_outputs=True):
+    """csv_bam_split_inputs on the context's last `bam.decode(ctx, chunk)` (= cols): the SA tags of the records with sel != 0,
+    parsed where the decode left them -> the dict `encode_split_reads` returns for those reads built the old way
+    (_primary_info + Chunk.sa_values; same keys, same dtypes), one call per (selected record, SA tag), plus call_rec (the
+    call's record in the chunk), status (per call, see sa_status: a flagged call has NO entries here and is the caller's to
+    send through encode_split_reads), n_calls, n_entries, n_flagged, ms_device.  The columns also stay on the device until
+    the context's next decode / split inputs: split_signatures(ctx, None, from_bam=<this dict>) analyses them there.
+    host_outputs=False: only call_rec and status come back (the entry columns and ent_off / read_len stay empty)."""
+    L = lib()
+    L.csv_bam_split_inputs.restype = C.c_int
+    L.csv_bam_split_inputs.argtypes = [C.c_void_p, C.POINTER(SaIn), C.POINTER(SaOut)]
+    n = chunk.n
+    sel = np.ascontiguousarray(sel, np.uint8)
+    assert len(sel) == n
+    if chrom not in chrom_rank and bool(np.any((sel != 0) & (np.asarray(cols["mapq"]) >= min_mapq))):
+        raise KeyError(chrom)                              # (encode_split_reads looks the primary's contig up, too)
+    blob, name_off, name_rank = _name_table(chrom_rank)
+    sin = SaIn(n_records=n, sel=sel.ctypes.data if n else None, min_mapq=int(min_mapq), task_rank=int(chrom_rank.get(chrom, -1)), n_names=len(name_rank),
+               names=blob.ctypes.data if len(blob) else None, name_bytes=len(blob), name_off=name_off.ctypes.data, name_rank=name_rank.ctypes.data if len(name_rank) else None)
+    cap_calls = int(cols["n_sa"])
+    # an entry the device accepts has at least ten bytes ("a,1,+,*,0;"), a flagged call has none: plus one primary entry per call
+    cap_ent = int((cols["sa_end"] - cols["sa_beg"]).sum()) // 10 + cap_calls if cap_calls else 0
+    for _ in range(2):
+        arrs = {k: np.zeros((cap_calls + 1) if k == "ent_off" else cap_calls, dt) for k, dt in _SA_CALL}
+        arrs.update({k: np.zeros(cap_ent if host_outputs else 0, dt) for k, dt in _SA_ENT})
+        give = [k for k, _ in _SA_CALL + _SA_ENT] if host_outputs else ["call_rec", "status"]
+        sout = SaOut(cap_calls=cap_calls, cap_entries=cap_ent, **{k: arrs[k].ctypes.data for k in give if len(arrs[k])})
+        rc = L.csv_bam_split_inputs(ctx._h, C.byref(sin), C.byref(sout))
+        if rc == _abi.E_CAPACITY:
+            cap_calls, cap_ent = int(sout.n_calls), int(sout.n_entries)
+            continue
+        ctx._check(rc)
+        nc, ne = int(sout.n_calls), int(sout.n_entries)
+        out = {k: arrs[k][:ne].copy() for k, _ in _SA_ENT} if host_outputs else {k: arrs[k] for k, _ in _SA_ENT}
+        out.update(ent_off=arrs["ent_off"][:nc + 1] if host_outputs else np.zeros(0, np.int64), read_len=arrs["read_len"][:nc if host_outputs else 0],
+                   call_rec=arrs["call_rec"][:nc], status=arrs["status"][:nc], n_calls=nc, n_entries=ne, n_flagged=int(sout.n_flagged),
+                   ms_device=float(sout.ms_device))
+        return out
+    raise RuntimeError("csv_bam_split_inputs: capacity retry failed")
+
+
+def _flagged_reads(chunk, cols, si, sel, chrom, min_mapq):
+    """the calls `split_inputs_bam` flagged, as encode_split_reads takes them: (call indices, [(primary_info, SA value, query_length)])"""
+    calls = np.flatnonzero(si["status"])
+    per_rec = np.where(np.asarray(sel) != 0, np.diff(cols["sa_off"]), 0)
+    first = np.concatenate([[0], np.cumsum(per_rec)])          # first call of every record
+    reads = []
+    for k in calls.tolist():
+        i = int(si["call_rec"][k])
+        t = int(cols["sa_off"][i]) + (k - int(first[i]))
+        primary = _primary_info(int(cols["flag"][i]), cols["mapq"][i] >= min_mapq, int(cols["clip_left"][i]), int(cols["clip_right"][i]),
+                                int(cols["query_len"][i]), int(cols["ref_start"][i]), int(cols["ref_end"][i]), chrom)
+        reads.append((primary, chunk.text(cols["sa_beg"][t], cols["sa_end"][t]), int(cols["query_len"][i])))
+    return calls, reads
+
+
+def _run_split(fn, handle, enc, sv_size, min_mapq, max_split_parts, max_size, check, pool=None, from_bam=None, host_outputs=True):
+    if from_bam is not None:                              # CSV_SP_FROM_BAM: calls and entry columns are on the device already (split_inputs_bam)
+        n, n_ent = int(from_bam["n_calls"]), int(from_bam.get("n_entries", 0))
+        sin = SplitIn(sv_size=int(sv_size), max_size=int(max_size), min_mapq=int(min_mapq), max_split_parts=int(max_split_parts), flags=_abi.SP_FROM_BAM)
+    else:
+        a = {k: np.ascontiguousarray(v) for k, v in enc.items()}
+        n, n_ent = len(a["read_len"]), int(a["ent_off"][-1])
+        ptr = lambda x: x.ctypes.data if len(x) else None                      # noqa: E731
+        sin = SplitIn(n_reads=n, ent_off=a["ent_off"].ctypes.data, read_len=ptr(a["read_len"]), c0=ptr(a["c0"]), c1=ptr(a["c1"]), f0=ptr(a["f0"]),
+                      f1=ptr(a["f1"]), chr=ptr(a["chr"]), mapq=ptr(a["mapq"]), strand=ptr(a["strand"]), primary=ptr(a["primary"]),
+                      sv_size=int(sv_size), max_size=int(max_size), min_mapq=int(min_mapq), max_split_parts=int(max_split_parts))
     qlen = None
     if pool is not None:                                  # CSV_CG_TO_POOL: the candidates also become rows of the context's pool
         qlen = None if pool.get("query_len") is None else np.ascontiguousarray(pool["query_len"], np.int32)
-        sin.flags = _abi.CG_TO_POOL
+        sin.flags |= _abi.CG_TO_POOL
         sin.pool_seg_base = (C.c_int32 * 5)(*[int(x) for x in pool["seg_base"]])
         sin.read_base = int(pool["read_base"])
         sin.query_len = None if qlen is None else qlen.ctypes.data
     cap = max(16, 2 * n)
     for _ in range(2):
-        arrs = {name: np.zeros(cap, dt) for name, dt in _SPLIT_OUT}
-        sout = SplitOut(cap=cap, **{k: v.ctypes.data for k, v in arrs.items()})
+        if host_outputs or pool is None:
+            arrs = {name: np.zeros(cap, dt) for name, dt in _SPLIT_OUT}
+            sout = SplitOut(cap=cap, **{k: v.ctypes.data for k, v in arrs.items()})
+        else:                                             # pool only: nothing but the count comes back; no entry yields more than 12 candidates
+            arrs = {name: np.zeros(0, dt) for name, dt in _SPLIT_OUT}
+            sout = SplitOut(cap=12 * n_ent)
         rc = fn(handle, C.byref(sin), C.byref(sout)) if handle is not None else fn(C.byref(sin), C.byref(sout))
         if rc == _abi.E_CAPACITY:
             cap = int(sout.n) + 1
@@ -209,19 +346,26 @@ def _run_split(fn, handle, enc, sv_size, min_mapq, max_split_parts, max_size, ch
         check(rc)
         out = {name: arrs[name][:int(sout.n)] for name, _ in _SPLIT_OUT}
         out["ms_device"] = float(sout.ms_device)
+        if not (host_outputs or pool is None):
+            out["n"] = int(sout.n)
         return out
     raise RuntimeError("csv_split_signatures: capacity retry failed")
 
 
-def split_signatures(ctx, enc, sv_size=30, min_mapq=20, max_split_parts=7, max_size=100000, pool=None):
+def split_signatures(ctx, enc, sv_size=30, min_mapq=20, max_split_parts=7, max_size=100000, pool=None, from_bam=None, host_outputs=True):
     """flat split-read entries of a batch of reads (encode_split_reads) -> dict of the candidate arrays of csv_split_out
     (defaults: cuteSV_Description.py: --min_size 30, --min_mapq 20, --max_split_parts 7, --max_size 100000).
     pool = dict(seg_base=[segment of chromosome rank 0 for kind DEL, INS, DUP, INV, TRA], read_base, query_len=None): the
-    candidates ALSO become rows of the context's device-resident pool (`pool_rows_of_split` is the same mapping on the host)."""
+    candidates ALSO become rows of the context's device-resident pool (`pool_rows_of_split` is the same mapping on the host);
+    host_outputs=False (with a pool): the arrays of the result stay empty and the result gains the key `n`, the number of candidates.
+    from_bam = the dict `split_inputs_bam` returned (pass enc=None): the reads are its calls and the entry columns are read where
+    it left them on the device (CSV_SP_FROM_BAM); the result's `read` is the call index, a pool row's read index is
+    read_base + call_rec[call] and the pool's query_len is the decode's."""
     L = lib()
     L.csv_split_signatures.restype = C.c_int
     L.csv_split_signatures.argtypes = [C.c_void_p, C.POINTER(SplitIn), C.POINTER(SplitOut)]
-    return _run_split(L.csv_split_signatures, ctx._h, enc, sv_size, min_mapq, max_split_parts, max_size, ctx._check, pool=pool)
+    return _run_split(L.csv_split_signatures, ctx._h, enc, sv_size, min_mapq, max_split_parts, max_size, ctx._check, pool=pool, from_bam=from_bam,
+                      host_outputs=host_outputs)
 
 
 def pool_rows_of_split(sig, seg_base, read_base, query_len):
@@ -330,17 +474,25 @@ def _assemble(sig, names, seqs, sp, chrom, chrom_rank, sv_size, min_mapq, max_sp
     """The second half of parse_reads, shared by the object path and the BAM path: the CIGAR signatures `sig` and the
     split-read inputs `sp` = [(read index, primary_info, [SA values], query_length, reverse strand)] in read order -> the
     five candidate lists.  names / seqs: indexable by read index (lists, or lazy views that slice a BAM chunk's host image)."""
-    cand = {t: [] for t in ("DEL", "INS", "DUP", "INV", "TRA")}
     c_ins, c_del = candidates(sig, names, seqs, chrom)
     sp_reads, sp_idx, sp_query = [], [], []
     for i, primary, sa, qlen, reverse in sp:
         for tag in sa:                                                                              # (one call per SA tag, :671)
             sp_reads.append((primary, tag, qlen)); sp_idx.append(i); sp_query.append(reverse)
-    s_cand = {t: [] for t in cand}
-    s_read = {t: [] for t in cand}
+    ssig = None
     if sp_reads:
         enc = encode_split_reads(sp_reads, chrom_rank)
         ssig = split_fn(enc, sv_size=sv_size, min_mapq=min_mapq, max_split_parts=max_split_parts, max_size=max_size)
+    return _merge(sig, names, seqs, c_ins, c_del, ssig, sp_idx, sp_query, chrom_rank)
+
+
+def _merge(sig, names, seqs, c_ins, c_del, ssig, sp_idx, sp_query, chrom_rank):
+    """the tail of _assemble: the CIGAR candidates c_ins / c_del and the split-read candidates `ssig` (None: no split-read
+    call; its `read` numbers the calls, sp_idx[call] = read index, sp_query[call] = reverse strand) -> the five lists"""
+    cand = {t: [] for t in ("DEL", "INS", "DUP", "INV", "TRA")}
+    s_cand = {t: [] for t in cand}
+    s_read = {t: [] for t in cand}
+    if ssig is not None:
         s_cand = split_candidates(ssig, [names[i] for i in sp_idx], _SplitQueries(seqs, sp_idx, sp_query), sorted(chrom_rank, key=chrom_rank.get))
         kind_name = ("DEL", "INS", "DUP", "INV", "TRA")
         for k, rd in zip(ssig["kind"].tolist(), ssig["read"].tolist()):
@@ -402,7 +554,7 @@ class _Lazy:
 
 
 def single_pipe_bam(ctx_or_fns, bamfile, chrom, task_start, task_end, chrom_rank, sv_size, min_mapq, max_split_parts, min_read_len, min_siglength,
-                    merge_del_threshold, merge_ins_threshold, max_size, bed_regions=None):
+                    merge_del_threshold, merge_ins_threshold, max_size, bed_regions=None, sa="host"):
     """`single_pipe` for the records `fetch(chrom, task_start, task_end)` would yield, read from `bamfile` (a bam.BamFile)
     without an object per record: -> (cand, reads_info) exactly as `single_pipe` returns them.
 
@@ -413,10 +565,19 @@ def single_pipe_bam(ctx_or_fns, bamfile, chrom, task_start, task_end, chrom_rank
     The gates are single_pipe's, applied to the columns: secondary records are skipped (:711), a read belongs to the task
     it starts in (:725), the bed overlap (:715-723), reads-table rows for mapq >= min_mapq (:729-733); parse_read's own
     gates (query_length >= min_read_len, :607; mapq, :614) become the `use` column of the CIGAR scan.  Read indices are
-    chunk indices throughout: a record that fails a gate has use = 0 and no split-read input, so it contributes nothing."""
+    chunk indices throughout: a record that fails a gate has use = 0 and no split-read input, so it contributes nothing.
+
+    sa: "host" - the SA values are sliced out of the chunk and parsed by encode_split_reads - or "device" (needs a Context): they
+    are parsed where the decode left them (split_inputs_bam) and analysed in place; only the calls the device flags (text
+    outside its strict grammar) go through encode_split_reads, and their candidates are merged at their place in read order.
+    Same result either way."""
     from . import bam as bam_mod
-    chunk = bamfile.records(chrom, task_start, task_end)
     on_device = not isinstance(ctx_or_fns, (tuple, list))
+    if sa not in ("host", "device"):
+        raise ValueError("sa must be 'host' or 'device', not %r" % (sa,))
+    if sa == "device" and not on_device:
+        raise ValueError("sa='device' needs an engine.Context: a (cigar_fn, split_fn) pair has no device to parse on")
+    chunk = bamfile.records(chrom, task_start, task_end)
     cols = bam_mod.decode(ctx_or_fns, chunk, host_outputs=False) if on_device else bam_mod.decode_host(chunk)
     start, end, flag, mapq, qlen = cols["ref_start"], cols["ref_end"], cols["flag"], cols["mapq"], cols["query_len"]
     gate = (cols["cls"] != 0) & (start >= task_start)
@@ -435,12 +596,76 @@ def single_pipe_bam(ctx_or_fns, bamfile, chrom, task_start, task_end, chrom_rank
         cigar_fn, split_fn = ctx_or_fns
         sig = cigar_fn(cols["cig_off"], cols["cigar"], start, use, **kw)
     names, seqs = _Lazy(chunk.name), _Lazy(chunk.sequence)
-    sp = []
-    has_sa = cols["sa_off"][1:] > cols["sa_off"][:-1]
-    for i in np.flatnonzero(parsed & (cols["cls"] == 1) & has_sa).tolist():     # primary records with an SA tag: few
-        primary = _primary_info(int(flag[i]), mapq[i] >= min_mapq, int(cols["clip_left"][i]), int(cols["clip_right"][i]), int(qlen[i]),
-                                int(start[i]), int(end[i]), chrom)
-        sp.append((i, primary, chunk.sa_values(cols, i), int(qlen[i]), int(flag[i]) == 16))
-    cand = _assemble(sig, names, seqs, sp, chrom, chrom_rank, sv_size, min_mapq, max_split_parts, max_size, split_fn)
+    sel = parsed & (cols["cls"] == 1) & (cols["sa_off"][1:] > cols["sa_off"][:-1])     # primary records with an SA tag: few
+    if sa == "device":
+        cand = _assemble_device(ctx_or_fns, chunk, cols, sig, names, seqs, sel, chrom, chrom_rank, sv_size, min_mapq, max_split_parts, max_size)
+    else:
+        sp = []
+        for i in np.flatnonzero(sel).tolist():
+            primary = _primary_info(int(flag[i]), mapq[i] >= min_mapq, int(cols["clip_left"][i]), int(cols["clip_right"][i]), int(qlen[i]),
+                                    int(start[i]), int(end[i]), chrom)
+            sp.append((i, primary, chunk.sa_values(cols, i), int(qlen[i]), int(flag[i]) == 16))
+        cand = _assemble(sig, names, seqs, sp, chrom, chrom_rank, sv_size, min_mapq, max_split_parts, max_size, split_fn)
     reads_info = [(int(start[i]), int(end[i]), 1 if cols["cls"][i] == 1 else 0, names[i], chrom) for i in np.flatnonzero(gate & (mapq >= min_mapq)).tolist()]
     return cand, reads_info
+
+
+def _assemble_device(ctx, chunk, cols, sig, names, seqs, sel, chrom, chrom_rank, sv_size, min_mapq, max_split_parts, max_size):
+    """_assemble for sa="device": the split-read inputs of the records `sel` are parsed and analysed on the device; the calls
+    it flags go through encode_split_reads and their candidates are merged at their place in call (= read) order"""
+    skw = dict(sv_size=sv_size, min_mapq=min_mapq, max_split_parts=max_split_parts, max_size=max_size)
+    si = split_inputs_bam(ctx, chunk, cols, sel, chrom_rank, chrom, min_mapq, host_outputs=False)
+    ssig = split_signatures(ctx, None, from_bam=si, **skw) if si["n_calls"] else None
+    if si["n_flagged"]:
+        calls, reads = _flagged_reads(chunk, cols, si, sel, chrom, min_mapq)
+        fsig = split_signatures(ctx, encode_split_reads(reads, chrom_rank), **skw)
+        both = {k: np.concatenate([ssig[k], calls[fsig[k]].astype(np.int32) if k == "read" else fsig[k]]) for k, _ in _SPLIT_OUT}
+        order = np.argsort(both["read"], kind="stable")      # (a call's candidates all come from one side, in their order)
+        ssig = {k: v[order] for k, v in both.items()}
+    c_ins, c_del = candidates(sig, names, seqs, chrom)
+    return _merge(sig, names, seqs, c_ins, c_del, ssig, si["call_rec"].tolist(), (cols["flag"][si["call_rec"]] == 16).tolist(), chrom_rank)
+
+
+# ------------------------------------------------------------------------------------ a task's region -> rows of the pool
+def task_to_pool(ctx, bamfile, chrom, task_start, task_end, chrom_rank, sv_size, min_mapq, max_split_parts, min_read_len, min_siglength,
+                 merge_del_threshold, merge_ins_threshold, max_size, seg_ins, seg_del, seg_base, read_base, bed_regions=None):
+    """The body of an extraction task without a candidate tuple, a name string or a sequence: the records of the region
+    (`bamfile.records`) are decoded on the device, the CIGAR scan appends its signatures to the context's pool from the decoded
+    columns (CSV_CG_FROM_BAM | CSV_CG_TO_POOL), the SA tags are parsed there (split_inputs_bam) and the split-read analysis appends
+    its candidates (CSV_SP_FROM_BAM | CSV_CG_TO_POOL).  Gates and parameters are single_pipe_bam's.  seg_ins / seg_del: the pool
+    segments of the task's INS / DEL signatures; seg_base: per candidate kind (DEL, INS, DUP, INV, TRA) the segment of chromosome
+    rank 0; a row's read index is read_base + the record's index in the region's chunk.  Calls the device flags go through
+    encode_split_reads and are appended with pool_append before the function returns: the pool is complete then.
+
+    -> dict: n_records, n_sig_ins, n_sig_del, n_calls, n_entries, n_split (candidates of the device path), n_split_host (of the
+    flagged calls), n_flagged, flagged_calls / flagged_records (indices of the flagged calls and of their records), and the
+    columns of the reads table rows (:729-733) reads_start, reads_end, reads_primary, reads_index (index in the chunk)."""
+    from . import bam as bam_mod, rebuild
+    chunk = bamfile.records(chrom, task_start, task_end)
+    cols = bam_mod.decode(ctx, chunk, host_outputs=False)
+    start, end, mapq, qlen = cols["ref_start"], cols["ref_end"], cols["mapq"], cols["query_len"]
+    gate = (cols["cls"] != 0) & (start >= task_start)
+    if bed_regions is not None:
+        in_bed = np.zeros(chunk.n, bool)
+        for b0, b1 in bed_regions:                           # not (pos_end <= b0 or pos_start >= b1)
+            in_bed |= (end > b0) & (start < b1)
+        gate &= in_bed
+    parsed = gate & (qlen >= min_read_len)
+    use = (parsed & (mapq >= min_mapq)).astype(np.uint8)
+    sig = cigar_signatures(ctx, None, None, None, use, min_siglength=min_siglength, merge_ins_threshold=merge_ins_threshold, merge_del_threshold=merge_del_threshold,
+                           pool=dict(seg_ins=seg_ins, seg_del=seg_del, read_base=read_base, query_len=qlen), host_outputs=False, from_bam=cols)
+    sel = parsed & (cols["cls"] == 1) & (cols["sa_off"][1:] > cols["sa_off"][:-1])
+    skw = dict(sv_size=sv_size, min_mapq=min_mapq, max_split_parts=max_split_parts, max_size=max_size)
+    si = split_inputs_bam(ctx, chunk, cols, sel, chrom_rank, chrom, min_mapq, host_outputs=False)
+    n_split = split_signatures(ctx, None, from_bam=si, pool=dict(seg_base=seg_base, read_base=read_base), host_outputs=False, **skw)["n"] if si["n_calls"] else 0
+    calls, n_host = np.zeros(0, np.int64), 0
+    if si["n_flagged"]:
+        calls, reads = _flagged_reads(chunk, cols, si, sel, chrom, min_mapq)
+        fsig = split_signatures(ctx, encode_split_reads(reads, chrom_rank), **skw)
+        rows = pool_rows_of_split(fsig, seg_base, 0, [r[2] for r in reads])
+        rebuild.pool_append(ctx, rows["seg"], rows["a"], rows["b"], read_base + si["call_rec"][calls][fsig["read"]], rows["aux"])
+        n_host = len(fsig["kind"])
+    keep = np.flatnonzero(gate & (mapq >= min_mapq))
+    return dict(n_records=chunk.n, n_sig_ins=sig["n_sig_ins"], n_sig_del=sig["n_sig_del"], n_calls=si["n_calls"], n_entries=si["n_entries"], n_split=n_split,
+                n_split_host=n_host, n_flagged=si["n_flagged"], flagged_calls=calls, flagged_records=si["call_rec"][calls],
+                reads_start=start[keep], reads_end=end[keep], reads_primary=(cols["cls"][keep] == 1).astype(np.uint8), reads_index=keep)

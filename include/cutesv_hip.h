@@ -483,9 +483,10 @@ int csv_cigar_signatures(csv_ctx* ctx, const csv_cigar_in* in, csv_cigar_out* ou
  * organize_split_signal (cuteSV main script :483-513: the primary alignment plus the SA-tag entries that pass min_mapq
  * become [read_start, read_end, ref_start, ref_end, chr, strand] segments; reads with more than max_split_parts segments
  * are skipped) and analysis_split_read with analysis_inv / analysis_bnd (:50-464: segments sorted by read_start, then
- * the two-segment and sliding three-segment rules that emit INV / TRA / DUP / INS / DEL candidates).  BAM decode and
- * the text of the SA tag stay in the Python driver with pysam (north_star): per entry the caller passes what
- * acquire_clip_pos (:466-481) takes out of the SA entry's CIGAR and the numbers of the entry itself.
+ * the two-segment and sliding three-segment rules that emit INV / TRA / DUP / INS / DEL candidates).  The input is
+ * numbers, not text: per entry what acquire_clip_pos (:466-481) takes out of the SA entry's CIGAR and the numbers of the
+ * entry itself.  A caller with pysam records makes them from the tag's text (extract.encode_split_reads); for a chunk of
+ * the native BAM reader csv_bam_split_inputs makes them on the device and CSV_SP_FROM_BAM uses them where they are.
  *
  * Entries of read r: [ent_off[r], ent_off[r + 1]), the primary alignment first when the read has one (parse_read
  * :660-668, primary = 1: c0/c1 = read_start/read_end, f0/f1 = ref_start/ref_end as parse_read computes them), then the
@@ -517,11 +518,18 @@ typedef struct csv_split_in {
      * query_len[read] - NULL: read_len - like a Python slice), (pos1, pos2) for DUP, aux = strand code for INV, aux = chr2 * 8 +
      * type for TRA; read index = read_base + the read's index in this batch.  Output arrays of csv_split_out that are NULL are
      * then not written. */
-    int32_t         flags;
+    int32_t         flags;          /* CSV_CG_TO_POOL, CSV_SP_FROM_BAM */
     int32_t         pool_seg_base[5];
     int64_t         read_base;
     const int32_t*  query_len;      /* n_reads or NULL */
 } csv_split_in;
+/* csv_split_in.flags, next to CSV_CG_TO_POOL = 1: n_reads, ent_off, read_len and the eight entry columns are NOT read from
+ * `in`: the reads are the calls of the context's last csv_bam_split_inputs and the columns are the ones it left on the
+ * device (CSV_E_INVALID when the context holds none).  A call it flagged has no entries and yields nothing.  out->read is
+ * the call index.  With CSV_CG_TO_POOL a row's read index is read_base + call_rec[call] - the record's index in the
+ * chunk, the index space of the CIGAR scan's rows of that chunk - and the query length is the decode's column: the
+ * query_len pointer of `in` is ignored. */
+enum { CSV_SP_FROM_BAM = 4 };
 
 typedef struct csv_split_out {
     int64_t  cap;
@@ -668,7 +676,7 @@ int         csv_bam_struct_size(int which);
 
 /* Device side (bam.hip.h): the slim image of a chunk -> per-record columns, the packed CIGARs and the byte ranges of the
  * SA / CG tags, in device memory of the context (valid until its next csv_bam_decode; csv_cigar_signatures with
- * CSV_CG_FROM_BAM scans them in place) and, for every host array that is not NULL, in the caller's memory.
+ * CSV_CG_FROM_BAM scans them in place, csv_bam_split_inputs parses the SA values there) and, for every host array that is not NULL, in the caller's memory.
  *   ref_start = pos, query_len = l_seq, ref_end = pos + lengths of M D N = X, clip_left / clip_right = length of the
  *   first / last CIGAR operation when it is S or H (else 0), cls = 0 secondary (flag 256 / 272), 1 primary (flag 0 / 16),
  *   2 other.  A record whose CIGAR is the placeholder <l_seq>S<n>N and that carries a CG:B,I tag (more than 65 535
@@ -706,6 +714,54 @@ typedef struct csv_bam_out {
 } csv_bam_out;
 
 int csv_bam_decode(csv_ctx* ctx, const csv_bam_in* in, csv_bam_out* out);
+
+/* The SA tags of the context's last csv_bam_decode -> the entry columns of csv_split_in, parsed on the device (sa.hip.h,
+ * DESIGN.md section 14).  A CALL is one (record i with sel[i] != 0, SA tag of that record) pair, in record order and then
+ * tag order.  Its entries are the primary alignment when mapq[i] >= min_mapq (parse_read :660-668, from the decode's
+ * columns: flag 0 -> c0 = clip_left, c1 = query_len - clip_right, strand 0; else the clips swapped, strand 1; f0 / f1 =
+ * ref_start / ref_end, chr = task_rank, mapq 0, primary 1) and then one per "name,pos,strand,CIGAR,mapq[,...];" of the
+ * value, in order (text behind the last ';' is dropped, as value.split(";")[:-1] drops it): chr = the rank of `name`,
+ * f0 = pos - 1, strand 0 for '+' else 1, c0 / c1 / f1 = leading S length / trailing S length / span over M D = X of the
+ * CIGAR text, mapq.  read_len = the record's query_len, call_rec = the record's index in the chunk.
+ *
+ * Contig names: n_names names back to back in `names` in ascending byte order, name k = bytes [name_off[k],
+ * name_off[k + 1]), name_rank[k] = the caller's rank for it (any integers).
+ *
+ * The device accepts a strict grammar only: a name of the table; pos an unsigned decimal number of 1 - 18 digits, mapq
+ * of 1 - 9; a strand of one character; a CIGAR that is "*" or a run of <1 - 18 digits><one of MIDNSHP=XB>; at least
+ * five fields.  A call with any other entry gets status != 0 (bits: 1 number, 2 strand, 4 CIGAR, 8 fewer than five
+ * fields, 16 unknown name), is counted in n_flagged and has NO entries: it is the caller's to parse (the Python layer
+ * sends exactly those through encode_split_reads, so the reference's behaviour on such text, exceptions included, stays).
+ *
+ * The columns stay in device memory of the context until its next csv_bam_decode / csv_bam_split_inputs
+ * (csv_split_signatures with CSV_SP_FROM_BAM reads them there); every host array that is not NULL is filled as well.
+ * CSV_E_CAPACITY: a per-call array is given and cap_calls < n_calls, or a per-entry array and cap_entries < n_entries;
+ * the counts hold the need.  CSV_E_INVALID, before anything is launched: no decode in the context, n_records is not the
+ * decode's, or the name table is inconsistent (offsets that decrease or leave `names`, names not strictly ascending). */
+typedef struct csv_sa_in {
+    int64_t         n_records;
+    const uint8_t*  sel;             /* n_records */
+    int32_t         min_mapq;
+    int32_t         task_rank;       /* rank of the contig the chunk lies on */
+    int32_t         n_names;
+    int32_t         flags;           /* 0 */
+    const uint8_t*  names;   int64_t name_bytes;
+    const int64_t*  name_off;        /* n_names + 1 */
+    const int32_t*  name_rank;       /* n_names */
+} csv_sa_in;
+
+typedef struct csv_sa_out {
+    int64_t  cap_calls, cap_entries;
+    int64_t  n_calls, n_entries, n_flagged;                 /* out */
+    int64_t* ent_off;  int64_t* read_len;  int32_t* call_rec;  uint8_t* status;      /* cap_calls (ent_off: + 1) */
+    int64_t* c0;  int64_t* c1;  int64_t* f0;  int64_t* f1;  int32_t* chr;  int32_t* mapq;  uint8_t* strand;  uint8_t* primary;   /* cap_entries */
+    float    ms_device;              /* out: kernels only (HIP events) */
+    int32_t  reserved;
+} csv_sa_out;
+
+int csv_bam_split_inputs(csv_ctx* ctx, const csv_sa_in* in, csv_sa_out* out);
+/* sizeof of 0 csv_sa_in, 1 csv_sa_out; -1 otherwise */
+int csv_sa_struct_size(int which);
 
 #ifdef __cplusplus
 }
