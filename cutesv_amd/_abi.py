@@ -85,6 +85,134 @@ class RunStats(C.Structure):
                 ("n_calls", C.c_int64), ("n_support", C.c_int64)]
 
 
+class RebuildIn(C.Structure):
+    _fields_ = [("n", C.c_int64), ("n_seg", C.c_int32), ("flags", C.c_int32), ("seg_aux_major", C.c_void_p),
+                ("seg_id", C.c_void_p), ("a", C.c_void_p), ("b", C.c_void_p), ("read_id", C.c_void_p), ("aux", C.c_void_p),
+                ("seg_nodedup", C.c_void_p), ("read_rank", C.c_void_p), ("n_rank", C.c_int64), ("tie_order", C.c_void_p), ("tie_user", C.c_void_p)]
+
+
+# csv_tie_order_fn (include/cutesv_hip.h): int (*)(void* user, int64 n_groups, const int64* group_off, const int32* src_row, int32* order, uint8* drop)
+TIE_ORDER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_uint8))
+
+
+class RebuildOut(C.Structure):
+    _fields_ = [("n_out", C.c_int64), ("seg_id", C.c_void_p), ("a", C.c_void_p), ("b", C.c_void_p), ("read_id", C.c_void_p),
+                ("aux", C.c_void_p), ("src_row", C.c_void_p), ("ms_device", C.c_float), ("n_passes", C.c_int32),
+                ("seg_count", C.c_void_p), ("n_ins_ties", C.c_int64), ("dev_seg_id", C.c_void_p), ("dev_a", C.c_void_p), ("dev_b", C.c_void_p),
+                ("dev_read_id", C.c_void_p), ("dev_aux", C.c_void_p), ("dev_src_row", C.c_void_p), ("n_tie_rows", C.c_int64), ("n_tie_dropped", C.c_int64)]
+
+
+class VcfIn(C.Structure):
+    _fields_ = [
+        ("res", C.POINTER(BatchOut)), ("seg", C.c_void_p), ("n_seg", C.c_int32), ("n_chrom", C.c_int32),
+        ("chrom_name", C.POINTER(C.c_char_p)), ("chrom_seq", C.POINTER(C.c_char_p)), ("chrom_len", C.c_void_p),
+        ("chrom_rank", C.c_void_p),
+        ("ins_alt", C.c_char_p), ("ins_alt_off", C.c_void_p), ("rnames", C.c_char_p), ("rnames_off", C.c_void_p),
+        ("strand_name", C.POINTER(C.c_char_p)),
+        ("gl_key", C.c_void_p), ("gl_str", C.POINTER(C.c_char_p)), ("n_gl", C.c_int32),
+        ("min_size", C.c_int64), ("max_size", C.c_int64),
+        ("genotype", C.c_int32), ("report_readid", C.c_int32), ("ignore_sequence", C.c_int32), ("reserved", C.c_int32),
+        ("chrom_line_bases", C.c_void_p), ("chrom_line_width", C.c_void_p),
+    ]
+
+
+class RowsIn(C.Structure):
+    _fields_ = [
+        ("res", C.POINTER(BatchOut)), ("seg", C.c_void_p), ("n_seg", C.c_int32), ("n_chrom", C.c_int32),
+        ("chrom_name", C.POINTER(C.c_char_p)),
+        ("read_id", C.c_void_p), ("aux", C.c_void_p),
+        ("name_blob", C.c_char_p), ("name_off", C.c_void_p), ("n_names", C.c_int64),
+        ("name_prefix", C.c_char_p), ("name_width", C.c_int32), ("n_strand", C.c_int32),
+        ("ins_blob", C.c_char_p), ("ins_off", C.c_void_p),
+        ("strand_name", C.POINTER(C.c_char_p)),
+        ("gl_blob", C.c_char_p), ("gl_off", C.c_void_p),
+    ]
+
+
+# ------------------------------------------------------------------------------------ extraction (cutesv_amd/extract.py)
+# Result columns are (name, dtype, capacity class): the class names the capacity / count pair of the out-struct a column is sized by.
+class CigarIn(C.Structure):
+    _fields_ = [("n_reads", C.c_int64), ("cig_off", C.c_void_p), ("cigar", C.c_void_p), ("ref_start", C.c_void_p), ("use", C.c_void_p),
+                ("min_siglength", C.c_int32), ("flags", C.c_int32), ("merge_ins_threshold", C.c_int64), ("merge_del_threshold", C.c_int64),
+                ("seg_ins", C.c_int32), ("seg_del", C.c_int32), ("read_base", C.c_int64), ("query_len", C.c_void_p)]
+
+
+CIGAR_OUT = [("ins_read", np.int32, "i"), ("ins_pos", np.int64, "i"), ("ins_len", np.int64, "i"), ("ins_piece0", np.int64, "i"), ("ins_npiece", np.int32, "i"),
+             ("piece_qoff", np.int32, "p"), ("piece_len", np.int32, "p"), ("del_read", np.int32, "d"), ("del_pos", np.int64, "d"), ("del_len", np.int64, "d")]
+
+
+class CigarOut(C.Structure):
+    _fields_ = ([("cap_sig_ins", C.c_int64), ("cap_piece_ins", C.c_int64), ("cap_sig_del", C.c_int64),
+                 ("n_sig_ins", C.c_int64), ("n_piece_ins", C.c_int64), ("n_sig_del", C.c_int64)]
+                + [(n, C.c_void_p) for n, _, _ in CIGAR_OUT] + [("ms_device", C.c_float), ("reserved", C.c_int32)])
+
+
+class SplitIn(C.Structure):
+    _fields_ = [("n_reads", C.c_int64), ("ent_off", C.c_void_p), ("read_len", C.c_void_p), ("c0", C.c_void_p), ("c1", C.c_void_p),
+                ("f0", C.c_void_p), ("f1", C.c_void_p), ("chr", C.c_void_p), ("mapq", C.c_void_p), ("strand", C.c_void_p), ("primary", C.c_void_p),
+                ("sv_size", C.c_int64), ("max_size", C.c_int64), ("min_mapq", C.c_int32), ("max_split_parts", C.c_int32),
+                ("flags", C.c_int32), ("pool_seg_base", C.c_int32 * 5), ("read_base", C.c_int64), ("query_len", C.c_void_p)]
+
+
+SPLIT_OUT = [("kind", np.uint8, "n"), ("read", np.int32, "n"), ("chr", np.int32, "n"), ("aux", np.int32, "n"),
+             ("a", np.int64, "n"), ("b", np.int64, "n"), ("c", np.int64, "n"), ("d", np.int64, "n")]
+
+
+class SplitOut(C.Structure):
+    _fields_ = [("cap", C.c_int64), ("n", C.c_int64)] + [(n, C.c_void_p) for n, _, _ in SPLIT_OUT] + [("ms_device", C.c_float), ("reserved", C.c_int32)]
+
+
+class SaIn(C.Structure):
+    _fields_ = [("n_records", C.c_int64), ("sel", C.c_void_p), ("min_mapq", C.c_int32), ("task_rank", C.c_int32), ("n_names", C.c_int32), ("flags", C.c_int32),
+                ("names", C.c_void_p), ("name_bytes", C.c_int64), ("name_off", C.c_void_p), ("name_rank", C.c_void_p)]
+
+
+SA_CALL = [("ent_off", np.int64, "c"), ("read_len", np.int64, "c"), ("call_rec", np.int32, "c"), ("status", np.uint8, "c")]
+SA_ENT = [("c0", np.int64, "e"), ("c1", np.int64, "e"), ("f0", np.int64, "e"), ("f1", np.int64, "e"), ("chr", np.int32, "e"), ("mapq", np.int32, "e"),
+          ("strand", np.uint8, "e"), ("primary", np.uint8, "e")]
+
+
+class SaOut(C.Structure):
+    _fields_ = ([("cap_calls", C.c_int64), ("cap_entries", C.c_int64), ("n_calls", C.c_int64), ("n_entries", C.c_int64), ("n_flagged", C.c_int64)]
+                + [(n, C.c_void_p) for n, _, _ in SA_CALL + SA_ENT] + [("ms_device", C.c_float), ("reserved", C.c_int32)])
+
+
+# ------------------------------------------------------------------------------------ native BAM reader (cutesv_amd/bam.py)
+class ChunkC(C.Structure):
+    _fields_ = [("n_records", C.c_int64), ("more", C.c_int32), ("reserved", C.c_int32), ("slim", C.c_void_p), ("slim_bytes", C.c_int64),
+                ("rec_off", C.c_void_p), ("rec_len", C.c_void_p), ("host", C.c_void_p), ("host_bytes", C.c_int64), ("host_off", C.c_void_p),
+                ("record_bytes", C.c_int64), ("inflated_bytes", C.c_int64), ("compressed_bytes", C.c_int64), ("ms_inflate", C.c_double),
+                ("ms_frame", C.c_double)]
+
+
+class BamIn(C.Structure):
+    _fields_ = [("n_records", C.c_int64), ("slim", C.c_void_p), ("slim_bytes", C.c_int64), ("rec_off", C.c_void_p), ("rec_len", C.c_void_p),
+                ("flags", C.c_int32), ("reserved", C.c_int32)]
+
+
+# per-record columns of csv_bam_out, in its order: (name, dtype, length class: n = records, n1 = records + 1, o = operations, s = SA tags)
+BAM_OUT = [("ref_start", np.int64, "n"), ("ref_end", np.int64, "n"), ("flag", np.int32, "n"), ("mapq", np.int32, "n"), ("query_len", np.int32, "n"),
+           ("clip_left", np.int32, "n"), ("clip_right", np.int32, "n"), ("cls", np.uint8, "n"), ("status", np.uint8, "n"),
+           ("cig_off", np.int64, "n1"), ("cigar", np.uint32, "o"), ("sa_off", np.int64, "n1"), ("sa_beg", np.int64, "s"), ("sa_end", np.int64, "s"),
+           ("cg_beg", np.int64, "n"), ("cg_end", np.int64, "n")]
+BAM_DEV = ["dev_ref_start", "dev_ref_end", "dev_flag", "dev_mapq", "dev_query_len", "dev_clip_left", "dev_clip_right", "dev_cls", "dev_cig_off", "dev_cigar"]
+
+
+class BamOut(C.Structure):
+    _fields_ = ([("cap_ops", C.c_int64), ("cap_sa", C.c_int64), ("n_ops", C.c_int64), ("n_sa", C.c_int64)] + [(n, C.c_void_p) for n, _, _ in BAM_OUT]
+                + [(n, C.c_void_p) for n in BAM_DEV] + [("bytes_uploaded", C.c_int64), ("n_bad", C.c_int64), ("ms_device", C.c_float), ("ms_upload", C.c_float)])
+
+
+# What csv_struct_size / csv_bam_struct_size / csv_sa_struct_size report for index 0, 1, ...: (C name, size of the mirror).
+# _lib.lib() compares them with the library it loads.
+STRUCT_SIZES = [("csv_segment", SEGMENT_DTYPE.itemsize), ("csv_batch_in", C.sizeof(BatchIn)), ("csv_batch_out", C.sizeof(BatchOut)),
+                ("csv_run_stats", C.sizeof(RunStats)), ("csv_rebuild_in", C.sizeof(RebuildIn)), ("csv_rebuild_out", C.sizeof(RebuildOut)),
+                ("csv_vcf_in", C.sizeof(VcfIn)), ("csv_rows_in", C.sizeof(RowsIn)), ("csv_cigar_in", C.sizeof(CigarIn)),
+                ("csv_cigar_out", C.sizeof(CigarOut)), ("csv_split_in", C.sizeof(SplitIn)), ("csv_split_out", C.sizeof(SplitOut))]
+BAM_STRUCT_SIZES = [("csv_bam_chunk", C.sizeof(ChunkC)), ("csv_bam_in", C.sizeof(BamIn)), ("csv_bam_out", C.sizeof(BamOut))]
+SA_STRUCT_SIZES = [("csv_sa_in", C.sizeof(SaIn)), ("csv_sa_out", C.sizeof(SaOut))]
+
+
 def _ptr(arr):
     return None if arr is None else arr.ctypes.data
 

@@ -38,22 +38,22 @@ SYMBOLS = [
     ("csv_host_free", None, [C.c_void_p]),
     ("csv_host_register", C.c_int, [C.c_void_p, C.c_int64]),
     ("csv_host_unregister", C.c_int, [C.c_void_p]),
-    ("csv_rows_emit", C.c_int, None),          # prototype set in cutesv_amd/rows.py (needs its struct)
-    ("csv_cigar_signatures", C.c_int, None),   # prototype set in cutesv_amd/extract.py
-    ("csv_split_signatures", C.c_int, None),   # prototype set in cutesv_amd/extract.py
-    ("csv_rebuild_signatures", C.c_int, None),  # prototype set in cutesv_amd/rebuild.py
+    ("csv_rows_emit", C.c_int, [C.POINTER(_abi.RowsIn), C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]),
+    ("csv_cigar_signatures", C.c_int, [C.c_void_p, C.POINTER(_abi.CigarIn), C.POINTER(_abi.CigarOut)]),
+    ("csv_split_signatures", C.c_int, [C.c_void_p, C.POINTER(_abi.SplitIn), C.POINTER(_abi.SplitOut)]),
+    ("csv_rebuild_signatures", C.c_int, [C.c_void_p, C.POINTER(_abi.RebuildIn), C.POINTER(_abi.RebuildOut)]),
     ("csv_pool_reset", C.c_int, [C.c_void_p]),
     ("csv_pool_rows", C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
     ("csv_pool_append", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    ("csv_vcf_emit", C.c_int, None),           # prototype set in cutesv_amd/vcf.py (needs its struct)
+    ("csv_vcf_emit", C.c_int, [C.POINTER(_abi.VcfIn), C.c_char_p, C.c_int64, C.POINTER(C.c_int64), C.c_void_p]),
     ("csv_bam_open", C.c_int, [C.c_char_p, C.c_int, C.POINTER(C.c_void_p), C.c_char_p, C.c_int]),
     ("csv_bam_close", None, [C.c_void_p]),
     ("csv_bam_error", C.c_char_p, [C.c_void_p]),
     ("csv_bam_header", C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]),
-    ("csv_bam_read", C.c_int, None),           # prototype set in cutesv_amd/bam.py (needs its struct)
+    ("csv_bam_read", C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.POINTER(_abi.ChunkC)]),
     ("csv_bam_struct_size", C.c_int, [C.c_int]),
-    ("csv_bam_decode", C.c_int, None),         # prototype set in cutesv_amd/bam.py
-    ("csv_bam_split_inputs", C.c_int, None),   # prototype set in cutesv_amd/extract.py
+    ("csv_bam_decode", C.c_int, [C.c_void_p, C.POINTER(_abi.BamIn), C.POINTER(_abi.BamOut)]),
+    ("csv_bam_split_inputs", C.c_int, [C.c_void_p, C.POINTER(_abi.SaIn), C.POINTER(_abi.SaOut)]),
     ("csv_sa_struct_size", C.c_int, [C.c_int]),
     ("csv_fasta_index", C.c_int64, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
 ]
@@ -73,10 +73,13 @@ def lib():
         L = C.CDLL(LIB_PATH)
         for name, res, args in SYMBOLS:
             fn = getattr(L, name)          # AttributeError here == ABI mismatch, fail loudly
-            fn.restype = res
-            if args is not None:
-                fn.argtypes = args
+            fn.restype, fn.argtypes = res, args
         if L.csv_abi_version() != _abi.ABI_VERSION:
             raise ExtensionMissing("libcutesv_hip.so ABI %d != python side %d" % (L.csv_abi_version(), _abi.ABI_VERSION))
+        # a stale build with the same ABI number: every struct must have the size of its mirror
+        for size_of, table in ((L.csv_struct_size, _abi.STRUCT_SIZES), (L.csv_bam_struct_size, _abi.BAM_STRUCT_SIZES), (L.csv_sa_struct_size, _abi.SA_STRUCT_SIZES)):
+            for i, (name, size) in enumerate(table):
+                if size_of(i) != size:
+                    raise ExtensionMissing("%s: sizeof(%s) is %d, its python mirror has %d bytes: rebuild the library" % (LIB_PATH, name, size_of(i), size))
         _LIB = L
     return _LIB

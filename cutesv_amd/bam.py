@@ -16,6 +16,7 @@ import os
 import numpy as np
 
 from . import _abi
+from ._abi import ChunkC, BamIn, BamOut, BAM_OUT as _OUT, BAM_DEV as _DEV      # noqa: F401  (the mirrors live in _abi)
 from ._lib import lib
 
 ALL = 1 << 62                              # "no bound" of a region
@@ -23,31 +24,6 @@ ALL = 1 << 62                              # "no bound" of a region
 
 class BamError(ValueError):
     pass
-
-
-class ChunkC(C.Structure):
-    _fields_ = [("n_records", C.c_int64), ("more", C.c_int32), ("reserved", C.c_int32), ("slim", C.c_void_p), ("slim_bytes", C.c_int64),
-                ("rec_off", C.c_void_p), ("rec_len", C.c_void_p), ("host", C.c_void_p), ("host_bytes", C.c_int64), ("host_off", C.c_void_p),
-                ("record_bytes", C.c_int64), ("inflated_bytes", C.c_int64), ("compressed_bytes", C.c_int64), ("ms_inflate", C.c_double),
-                ("ms_frame", C.c_double)]
-
-
-class BamIn(C.Structure):
-    _fields_ = [("n_records", C.c_int64), ("slim", C.c_void_p), ("slim_bytes", C.c_int64), ("rec_off", C.c_void_p), ("rec_len", C.c_void_p),
-                ("flags", C.c_int32), ("reserved", C.c_int32)]
-
-
-# per-record columns of csv_bam_out, in its order: (name, dtype, length class: n = records, n1 = records + 1, o = operations, s = SA tags)
-_OUT = [("ref_start", np.int64, "n"), ("ref_end", np.int64, "n"), ("flag", np.int32, "n"), ("mapq", np.int32, "n"), ("query_len", np.int32, "n"),
-        ("clip_left", np.int32, "n"), ("clip_right", np.int32, "n"), ("cls", np.uint8, "n"), ("status", np.uint8, "n"),
-        ("cig_off", np.int64, "n1"), ("cigar", np.uint32, "o"), ("sa_off", np.int64, "n1"), ("sa_beg", np.int64, "s"), ("sa_end", np.int64, "s"),
-        ("cg_beg", np.int64, "n"), ("cg_end", np.int64, "n")]
-_DEV = ["dev_ref_start", "dev_ref_end", "dev_flag", "dev_mapq", "dev_query_len", "dev_clip_left", "dev_clip_right", "dev_cls", "dev_cig_off", "dev_cigar"]
-
-
-class BamOut(C.Structure):
-    _fields_ = ([("cap_ops", C.c_int64), ("cap_sa", C.c_int64), ("n_ops", C.c_int64), ("n_sa", C.c_int64)] + [(n, C.c_void_p) for n, _, _ in _OUT]
-                + [(n, C.c_void_p) for n in _DEV] + [("bytes_uploaded", C.c_int64), ("n_bad", C.c_int64), ("ms_device", C.c_float), ("ms_upload", C.c_float)])
 
 
 def default_threads():
@@ -111,7 +87,6 @@ class BamFile:
 
     def __init__(self, path, threads=None):
         L = self._L = lib()
-        L.csv_bam_read.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.POINTER(ChunkC)]
         self._h = C.c_void_p()
         self.threads = default_threads() if threads is None else max(1, int(threads))
         err = C.create_string_buffer(512)
@@ -209,8 +184,6 @@ def decode(ctx, chunk, host_outputs=True):
     The columns also stay in the context's device memory until its next decode: extract.cigar_signatures(..., from_bam=True)
     scans them there.  host_outputs=False: only the small per-record columns come back (no CIGAR array)."""
     L = lib()
-    L.csv_bam_decode.restype = C.c_int
-    L.csv_bam_decode.argtypes = [C.c_void_p, C.POINTER(BamIn), C.POINTER(BamOut)]
     n = chunk.n
     slim, rec_off, rec_len = np.ascontiguousarray(chunk.slim, np.uint8), np.ascontiguousarray(chunk.rec_off, np.int64), np.ascontiguousarray(chunk.rec_len, np.uint32)
     bin_ = BamIn(n_records=n, slim=slim.ctypes.data if len(slim) else None, slim_bytes=len(slim), rec_off=rec_off.ctypes.data if n else None,

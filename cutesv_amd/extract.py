@@ -18,23 +18,9 @@ import ctypes as C
 import numpy as np
 
 from . import _abi
+from ._abi import (CigarIn, CigarOut, SplitIn, SplitOut, SaIn, SaOut,      # noqa: F401  (the mirrors live in _abi)
+                   CIGAR_OUT as _OUT, SPLIT_OUT as _SPLIT_OUT, SA_CALL as _SA_CALL, SA_ENT as _SA_ENT)
 from ._lib import lib
-
-
-class CigarIn(C.Structure):
-    _fields_ = [("n_reads", C.c_int64), ("cig_off", C.c_void_p), ("cigar", C.c_void_p), ("ref_start", C.c_void_p), ("use", C.c_void_p),
-                ("min_siglength", C.c_int32), ("flags", C.c_int32), ("merge_ins_threshold", C.c_int64), ("merge_del_threshold", C.c_int64),
-                ("seg_ins", C.c_int32), ("seg_del", C.c_int32), ("read_base", C.c_int64), ("query_len", C.c_void_p)]
-
-
-_OUT = [("ins_read", np.int32, "i"), ("ins_pos", np.int64, "i"), ("ins_len", np.int64, "i"), ("ins_piece0", np.int64, "i"), ("ins_npiece", np.int32, "i"),
-        ("piece_qoff", np.int32, "p"), ("piece_len", np.int32, "p"), ("del_read", np.int32, "d"), ("del_pos", np.int64, "d"), ("del_len", np.int64, "d")]
-
-
-class CigarOut(C.Structure):
-    _fields_ = ([("cap_sig_ins", C.c_int64), ("cap_piece_ins", C.c_int64), ("cap_sig_del", C.c_int64),
-                 ("n_sig_ins", C.c_int64), ("n_piece_ins", C.c_int64), ("n_sig_del", C.c_int64)]
-                + [(n, C.c_void_p) for n, _, _ in _OUT] + [("ms_device", C.c_float), ("reserved", C.c_int32)])
 
 
 def encode_cigars(cigartuples_per_read):
@@ -55,46 +41,60 @@ def encode_cigars(cigartuples_per_read):
     return off, flat
 
 
+def _negotiate(fn, handle, cin, out_type, table, classes, give, check, what, longer=()):
+    """The one capacity-negotiating call of this module: fn([handle,] &cin, &out) with caller-allocated result columns.
+    table: the out-struct's columns (name, dtype, capacity class); classes: {class: (capacity field, count field, first capacity,
+    what a retry adds to the count)}; give: the columns handed over - the others stay NULL and empty, their capacities are still
+    passed; longer: columns with one entry more than their class.  On CSV_E_CAPACITY the capacities are re-made from the counts
+    of the failed call and it is repeated once.  -> ({column: array cut to its count}, out-struct)"""
+    caps = {k: c[2] for k, c in classes.items()}
+    for _ in range(2):
+        arrs = {name: np.zeros(caps[k] + (name in longer) if name in give else 0, dt) for name, dt, k in table}
+        cout = out_type(**{c[0]: caps[k] for k, c in classes.items()}, **{name: a.ctypes.data for name, a in arrs.items() if len(a)})
+        rc = fn(handle, C.byref(cin), C.byref(cout)) if handle is not None else fn(C.byref(cin), C.byref(cout))
+        if rc == _abi.E_CAPACITY:
+            caps = {k: int(getattr(cout, c[1])) + c[3] for k, c in classes.items()}
+            continue
+        check(rc)
+        n = {k: int(getattr(cout, c[1])) for k, c in classes.items()}
+        return {name: arrs[name][:n[k] + (name in longer)] if name in give else arrs[name] for name, _, k in table}, cout
+    raise RuntimeError("%s: capacity retry failed" % what)
+
+
+def _to_pool(cin, pool):
+    """CSV_CG_TO_POOL on a csv_cigar_in / csv_split_in: the results also become rows of the context's pool.
+    -> the converted query_len column (or None): the caller holds it until the call has returned"""
+    qlen = None if pool.get("query_len") is None else np.ascontiguousarray(pool["query_len"], np.int32)
+    cin.flags |= _abi.CG_TO_POOL
+    cin.read_base = int(pool["read_base"])
+    cin.query_len = None if qlen is None else qlen.ctypes.data
+    return qlen
+
+
 def _run(fn, handle, cig_off, cigar, ref_start, use, min_siglength, merge_ins_threshold, merge_del_threshold, check, pool=None, host_outputs=True,
          from_bam=None):
     use = None if use is None else np.ascontiguousarray(use, np.uint8)
     if from_bam is not None:                              # CSV_CG_FROM_BAM: the three columns are on the device already (bam.decode)
         n, n_ops = int(from_bam["n"]), int(from_bam["n_ops"])
-        cin = CigarIn(n_reads=n, use=None if use is None else use.ctypes.data, min_siglength=int(min_siglength),
-                      merge_ins_threshold=int(merge_ins_threshold), merge_del_threshold=int(merge_del_threshold), flags=_abi.CG_FROM_BAM)
+        cin = CigarIn(n_reads=n, flags=_abi.CG_FROM_BAM)
     else:
         cig_off = np.ascontiguousarray(cig_off, np.int64); cigar = np.ascontiguousarray(cigar, np.uint32)
         ref_start = np.ascontiguousarray(ref_start, np.int64)
         n, n_ops = len(ref_start), int(cig_off[-1])
-        cin = CigarIn(n_reads=n, cig_off=cig_off.ctypes.data, cigar=cigar.ctypes.data if len(cigar) else None, ref_start=ref_start.ctypes.data,
-                      use=None if use is None else use.ctypes.data, min_siglength=int(min_siglength),
-                      merge_ins_threshold=int(merge_ins_threshold), merge_del_threshold=int(merge_del_threshold))
+        cin = CigarIn(n_reads=n, cig_off=cig_off.ctypes.data, cigar=cigar.ctypes.data if len(cigar) else None, ref_start=ref_start.ctypes.data)
+    cin.use = None if use is None else use.ctypes.data
+    cin.min_siglength, cin.merge_ins_threshold, cin.merge_del_threshold = int(min_siglength), int(merge_ins_threshold), int(merge_del_threshold)
     qlen = None
-    if pool is not None:                                  # CSV_CG_TO_POOL: the signatures also become rows of the context's pool
-        qlen = None if pool.get("query_len") is None else np.ascontiguousarray(pool["query_len"], np.int32)
-        cin.flags |= _abi.CG_TO_POOL
-        cin.seg_ins = int(pool["seg_ins"]); cin.seg_del = int(pool["seg_del"]); cin.read_base = int(pool["read_base"])
-        cin.query_len = None if qlen is None else qlen.ctypes.data
-    caps = dict(i=max(16, n // 4), p=max(16, n // 4), d=max(16, n // 4))
-    for _ in range(2):
-        if host_outputs or pool is None:
-            arrs = {name: np.zeros(caps[k], dt) for name, dt, k in _OUT}
-            cout = CigarOut(cap_sig_ins=caps["i"], cap_piece_ins=caps["p"], cap_sig_del=caps["d"], **{k: v.ctypes.data for k, v in arrs.items()})
-        else:                                             # pool only: nothing but the counts comes back
-            arrs = {name: np.zeros(0, dt) for name, dt, k in _OUT}
-            big = n_ops + 1
-            cout = CigarOut(cap_sig_ins=big, cap_piece_ins=big, cap_sig_del=big)
-        rc = fn(handle, C.byref(cin), C.byref(cout)) if handle is not None else fn(C.byref(cin), C.byref(cout))
-        if rc == _abi.E_CAPACITY:
-            caps = dict(i=int(cout.n_sig_ins) + 1, p=int(cout.n_piece_ins) + 1, d=int(cout.n_sig_del) + 1)
-            continue
-        check(rc)
-        cut = dict(i=int(cout.n_sig_ins), p=int(cout.n_piece_ins), d=int(cout.n_sig_del))
-        out = {name: arrs[name][:cut[k]] for name, _, k in _OUT}
-        out["n_sig_ins"], out["n_sig_del"] = cut["i"], cut["d"]
-        out["ms_device"] = float(cout.ms_device)
-        return out
-    raise RuntimeError("csv_cigar_signatures: capacity retry failed")
+    if pool is not None:                                  # the signatures also become rows of the context's pool
+        qlen = _to_pool(cin, pool)
+        cin.seg_ins, cin.seg_del = int(pool["seg_ins"]), int(pool["seg_del"])
+    to_host = host_outputs or pool is None                # (pool only: nothing but the counts comes back)
+    cap = max(16, n // 4) if to_host else n_ops + 1
+    classes = dict(i=("cap_sig_ins", "n_sig_ins", cap, 1), p=("cap_piece_ins", "n_piece_ins", cap, 1), d=("cap_sig_del", "n_sig_del", cap, 1))
+    out, cout = _negotiate(fn, handle, cin, CigarOut, _OUT, classes, [name for name, _, _ in _OUT] if to_host else (), check, "csv_cigar_signatures")
+    out["n_sig_ins"], out["n_sig_del"] = int(cout.n_sig_ins), int(cout.n_sig_del)
+    out["ms_device"] = float(cout.ms_device)
+    return out
 
 
 def cigar_signatures(ctx, cig_off, cigar, ref_start, use=None, min_siglength=10, merge_ins_threshold=100, merge_del_threshold=0, pool=None, host_outputs=True,
@@ -106,10 +106,7 @@ def cigar_signatures(ctx, cig_off, cigar, ref_start, use=None, min_siglength=10,
     the arrays of the result stay empty, only the counts come back.
     from_bam = the columns `bam.decode(ctx, chunk)` returned: cig_off / cigar / ref_start are not taken from the arguments (pass
     None) but scanned where that decode left them on the device (CSV_CG_FROM_BAM); `use` is still the caller's."""
-    L = lib()
-    L.csv_cigar_signatures.restype = C.c_int
-    L.csv_cigar_signatures.argtypes = [C.c_void_p, C.POINTER(CigarIn), C.POINTER(CigarOut)]
-    return _run(L.csv_cigar_signatures, ctx._h, cig_off, cigar, ref_start, use, min_siglength, merge_ins_threshold, merge_del_threshold, ctx._check, pool=pool,
+    return _run(lib().csv_cigar_signatures, ctx._h, cig_off, cigar, ref_start, use, min_siglength, merge_ins_threshold, merge_del_threshold, ctx._check, pool=pool,
                 host_outputs=host_outputs, from_bam=None if from_bam is None else dict(n=len(from_bam["ref_start"]), n_ops=from_bam["n_ops"]))
 
 
@@ -129,20 +126,6 @@ def candidates(sig, read_names, query_sequences, chrom):
 
 
 # ------------------------------------------------------------------------------------ split reads (SA tag)
-class SplitIn(C.Structure):
-    _fields_ = [("n_reads", C.c_int64), ("ent_off", C.c_void_p), ("read_len", C.c_void_p), ("c0", C.c_void_p), ("c1", C.c_void_p),
-                ("f0", C.c_void_p), ("f1", C.c_void_p), ("chr", C.c_void_p), ("mapq", C.c_void_p), ("strand", C.c_void_p), ("primary", C.c_void_p),
-                ("sv_size", C.c_int64), ("max_size", C.c_int64), ("min_mapq", C.c_int32), ("max_split_parts", C.c_int32),
-                ("flags", C.c_int32), ("pool_seg_base", C.c_int32 * 5), ("read_base", C.c_int64), ("query_len", C.c_void_p)]
-
-
-_SPLIT_OUT = [("kind", np.uint8), ("read", np.int32), ("chr", np.int32), ("aux", np.int32), ("a", np.int64), ("b", np.int64), ("c", np.int64), ("d", np.int64)]
-
-
-class SplitOut(C.Structure):
-    _fields_ = [("cap", C.c_int64), ("n", C.c_int64)] + [(n, C.c_void_p) for n, _ in _SPLIT_OUT] + [("ms_device", C.c_float), ("reserved", C.c_int32)]
-
-
 _CIGAR_RE = None
 
 
@@ -187,20 +170,6 @@ def encode_split_reads(reads, chrom_rank):
 
 
 # ------------------------------------------------------------------------------------ SA text parsed on the device
-class SaIn(C.Structure):
-    _fields_ = [("n_records", C.c_int64), ("sel", C.c_void_p), ("min_mapq", C.c_int32), ("task_rank", C.c_int32), ("n_names", C.c_int32), ("flags", C.c_int32),
-                ("names", C.c_void_p), ("name_bytes", C.c_int64), ("name_off", C.c_void_p), ("name_rank", C.c_void_p)]
-
-
-_SA_CALL = [("ent_off", np.int64), ("read_len", np.int64), ("call_rec", np.int32), ("status", np.uint8)]
-_SA_ENT = [("c0", np.int64), ("c1", np.int64), ("f0", np.int64), ("f1", np.int64), ("chr", np.int32), ("mapq", np.int32), ("strand", np.uint8), ("primary", np.uint8)]
-
-
-class SaOut(C.Structure):
-    _fields_ = ([("cap_calls", C.c_int64), ("cap_entries", C.c_int64), ("n_calls", C.c_int64), ("n_entries", C.c_int64), ("n_flagged", C.c_int64)]
-                + [(n, C.c_void_p) for n, _ in _SA_CALL + _SA_ENT] + [("ms_device", C.c_float), ("reserved", C.c_int32)])
-
-
 SA_ST_NUMBER, SA_ST_STRAND, SA_ST_CIGAR, SA_ST_FIELDS, SA_ST_NAME = 1, 2, 4, 8, 16
 _SA_STRICT_CIGAR = None
 
@@ -265,9 +234,6 @@ def split_inputs_bam(ctx, chunk, cols, sel, chrom_rank, chrom, min_mapq, host_ou
     send through encode_split_reads), n_calls, n_entries, n_flagged, ms_device.  The columns also stay on the device until
     the context's next decode / split inputs: split_signatures(ctx, None, from_bam=<this dict>) analyses them there.
     host_outputs=False: only call_rec and status come back (the entry columns and ent_off / read_len stay empty)."""
-    L = lib()
-    L.csv_bam_split_inputs.restype = C.c_int
-    L.csv_bam_split_inputs.argtypes = [C.c_void_p, C.POINTER(SaIn), C.POINTER(SaOut)]
     n = chunk.n
     sel = np.ascontiguousarray(sel, np.uint8)
     assert len(sel) == n
@@ -279,23 +245,13 @@ def split_inputs_bam(ctx, chunk, cols, sel, chrom_rank, chrom, min_mapq, host_ou
     cap_calls = int(cols["n_sa"])
     # an entry the device accepts has at least ten bytes ("a,1,+,*,0;"), a flagged call has none: plus one primary entry per call
     cap_ent = int((cols["sa_end"] - cols["sa_beg"]).sum()) // 10 + cap_calls if cap_calls else 0
-    for _ in range(2):
-        arrs = {k: np.zeros((cap_calls + 1) if k == "ent_off" else cap_calls, dt) for k, dt in _SA_CALL}
-        arrs.update({k: np.zeros(cap_ent if host_outputs else 0, dt) for k, dt in _SA_ENT})
-        give = [k for k, _ in _SA_CALL + _SA_ENT] if host_outputs else ["call_rec", "status"]
-        sout = SaOut(cap_calls=cap_calls, cap_entries=cap_ent, **{k: arrs[k].ctypes.data for k in give if len(arrs[k])})
-        rc = L.csv_bam_split_inputs(ctx._h, C.byref(sin), C.byref(sout))
-        if rc == _abi.E_CAPACITY:
-            cap_calls, cap_ent = int(sout.n_calls), int(sout.n_entries)
-            continue
-        ctx._check(rc)
-        nc, ne = int(sout.n_calls), int(sout.n_entries)
-        out = {k: arrs[k][:ne].copy() for k, _ in _SA_ENT} if host_outputs else {k: arrs[k] for k, _ in _SA_ENT}
-        out.update(ent_off=arrs["ent_off"][:nc + 1] if host_outputs else np.zeros(0, np.int64), read_len=arrs["read_len"][:nc if host_outputs else 0],
-                   call_rec=arrs["call_rec"][:nc], status=arrs["status"][:nc], n_calls=nc, n_entries=ne, n_flagged=int(sout.n_flagged),
-                   ms_device=float(sout.ms_device))
-        return out
-    raise RuntimeError("csv_bam_split_inputs: capacity retry failed")
+    cols_out = _SA_CALL + _SA_ENT
+    out, sout = _negotiate(lib().csv_bam_split_inputs, ctx._h, sin, SaOut, cols_out, dict(c=("cap_calls", "n_calls", cap_calls, 0), e=("cap_entries", "n_entries", cap_ent, 0)),
+                           [k for k, _, _ in cols_out] if host_outputs else ("call_rec", "status"), ctx._check, "csv_bam_split_inputs", longer=("ent_off",))
+    if host_outputs:
+        out.update({k: out[k].copy() for k, _, _ in _SA_ENT})
+    out.update(n_calls=int(sout.n_calls), n_entries=int(sout.n_entries), n_flagged=int(sout.n_flagged), ms_device=float(sout.ms_device))
+    return out
 
 
 def _flagged_reads(chunk, cols, si, sel, chrom, min_mapq):
@@ -325,31 +281,16 @@ def _run_split(fn, handle, enc, sv_size, min_mapq, max_split_parts, max_size, ch
                       f1=ptr(a["f1"]), chr=ptr(a["chr"]), mapq=ptr(a["mapq"]), strand=ptr(a["strand"]), primary=ptr(a["primary"]),
                       sv_size=int(sv_size), max_size=int(max_size), min_mapq=int(min_mapq), max_split_parts=int(max_split_parts))
     qlen = None
-    if pool is not None:                                  # CSV_CG_TO_POOL: the candidates also become rows of the context's pool
-        qlen = None if pool.get("query_len") is None else np.ascontiguousarray(pool["query_len"], np.int32)
-        sin.flags |= _abi.CG_TO_POOL
+    if pool is not None:                                  # the candidates also become rows of the context's pool
+        qlen = _to_pool(sin, pool)
         sin.pool_seg_base = (C.c_int32 * 5)(*[int(x) for x in pool["seg_base"]])
-        sin.read_base = int(pool["read_base"])
-        sin.query_len = None if qlen is None else qlen.ctypes.data
-    cap = max(16, 2 * n)
-    for _ in range(2):
-        if host_outputs or pool is None:
-            arrs = {name: np.zeros(cap, dt) for name, dt in _SPLIT_OUT}
-            sout = SplitOut(cap=cap, **{k: v.ctypes.data for k, v in arrs.items()})
-        else:                                             # pool only: nothing but the count comes back; no entry yields more than 12 candidates
-            arrs = {name: np.zeros(0, dt) for name, dt in _SPLIT_OUT}
-            sout = SplitOut(cap=12 * n_ent)
-        rc = fn(handle, C.byref(sin), C.byref(sout)) if handle is not None else fn(C.byref(sin), C.byref(sout))
-        if rc == _abi.E_CAPACITY:
-            cap = int(sout.n) + 1
-            continue
-        check(rc)
-        out = {name: arrs[name][:int(sout.n)] for name, _ in _SPLIT_OUT}
-        out["ms_device"] = float(sout.ms_device)
-        if not (host_outputs or pool is None):
-            out["n"] = int(sout.n)
-        return out
-    raise RuntimeError("csv_split_signatures: capacity retry failed")
+    to_host = host_outputs or pool is None                # (pool only: nothing but the count comes back; no entry yields more than 12 candidates)
+    out, sout = _negotiate(fn, handle, sin, SplitOut, _SPLIT_OUT, dict(n=("cap", "n", max(16, 2 * n) if to_host else 12 * n_ent, 1)),
+                           [name for name, _, _ in _SPLIT_OUT] if to_host else (), check, "csv_split_signatures")
+    out["ms_device"] = float(sout.ms_device)
+    if not to_host:
+        out["n"] = int(sout.n)
+    return out
 
 
 def split_signatures(ctx, enc, sv_size=30, min_mapq=20, max_split_parts=7, max_size=100000, pool=None, from_bam=None, host_outputs=True):
@@ -361,10 +302,7 @@ def split_signatures(ctx, enc, sv_size=30, min_mapq=20, max_split_parts=7, max_s
     from_bam = the dict `split_inputs_bam` returned (pass enc=None): the reads are its calls and the entry columns are read where
     it left them on the device (CSV_SP_FROM_BAM); the result's `read` is the call index, a pool row's read index is
     read_base + call_rec[call] and the pool's query_len is the decode's."""
-    L = lib()
-    L.csv_split_signatures.restype = C.c_int
-    L.csv_split_signatures.argtypes = [C.c_void_p, C.POINTER(SplitIn), C.POINTER(SplitOut)]
-    return _run_split(L.csv_split_signatures, ctx._h, enc, sv_size, min_mapq, max_split_parts, max_size, ctx._check, pool=pool, from_bam=from_bam,
+    return _run_split(lib().csv_split_signatures, ctx._h, enc, sv_size, min_mapq, max_split_parts, max_size, ctx._check, pool=pool, from_bam=from_bam,
                       host_outputs=host_outputs)
 
 
@@ -513,6 +451,14 @@ def _merge(sig, names, seqs, c_ins, c_del, ssig, sp_idx, sp_query, chrom_rank):
 
 
 # ------------------------------------------------------------------------------------ single_pipe: one extraction task
+def _in_bed(start, end, bed_regions):
+    """--include_bed (:715-723): the reads [start, end) that overlap one of the chromosome's regions"""
+    in_bed = np.zeros(len(start), bool)
+    for b0, b1 in bed_regions:                               # not (pos_end <= b0 or pos_start >= b1)
+        in_bed |= (end > b0) & (start < b1)
+    return in_bed
+
+
 def single_pipe(alignments, chrom, task_start, chrom_rank, sv_size, min_mapq, max_split_parts, min_read_len, min_siglength, merge_del_threshold,
                 merge_ins_threshold, max_size, cigar_fn, split_fn, bed_regions=None):
     """What the reference's single_pipe (main script :697-743) pickles for one task region: the five candidate lists of the
@@ -528,11 +474,7 @@ def single_pipe(alignments, chrom, task_start, chrom_rank, sv_size, min_mapq, ma
         start = np.fromiter((r.reference_start for r in recs), np.int64, len(recs))
         keep = start >= task_start
         if bed_regions is not None:
-            end = np.fromiter((r.reference_end for r in recs), np.int64, len(recs))
-            in_bed = np.zeros(len(recs), bool)
-            for b0, b1 in bed_regions:                       # not (pos_end <= b0 or pos_start >= b1)
-                in_bed |= (end > b0) & (start < b1)
-            keep &= in_bed
+            keep &= _in_bed(start, np.fromiter((r.reference_end for r in recs), np.int64, len(recs)), bed_regions)
         recs = [r for r, k in zip(recs, keep.tolist()) if k]
     cand = parse_reads(recs, chrom, chrom_rank, sv_size, min_mapq, max_split_parts, min_read_len, min_siglength, merge_del_threshold,
                        merge_ins_threshold, max_size, cigar_fn, split_fn)
@@ -580,14 +522,7 @@ def single_pipe_bam(ctx_or_fns, bamfile, chrom, task_start, task_end, chrom_rank
     chunk = bamfile.records(chrom, task_start, task_end)
     cols = bam_mod.decode(ctx_or_fns, chunk, host_outputs=False) if on_device else bam_mod.decode_host(chunk)
     start, end, flag, mapq, qlen = cols["ref_start"], cols["ref_end"], cols["flag"], cols["mapq"], cols["query_len"]
-    gate = (cols["cls"] != 0) & (start >= task_start)
-    if bed_regions is not None:
-        in_bed = np.zeros(chunk.n, bool)
-        for b0, b1 in bed_regions:                           # not (pos_end <= b0 or pos_start >= b1)
-            in_bed |= (end > b0) & (start < b1)
-        gate &= in_bed
-    parsed = gate & (qlen >= min_read_len)                    # the reads parse_read does not return from at once (:607)
-    use = (parsed & (mapq >= min_mapq)).astype(np.uint8)
+    gate, parsed, use, sel = _gates(cols, task_start, bed_regions, min_read_len, min_mapq)
     kw = dict(min_siglength=min_siglength, merge_ins_threshold=merge_ins_threshold, merge_del_threshold=merge_del_threshold)
     if on_device:
         sig = cigar_signatures(ctx_or_fns, None, None, None, use, from_bam=cols, **kw)
@@ -596,7 +531,6 @@ def single_pipe_bam(ctx_or_fns, bamfile, chrom, task_start, task_end, chrom_rank
         cigar_fn, split_fn = ctx_or_fns
         sig = cigar_fn(cols["cig_off"], cols["cigar"], start, use, **kw)
     names, seqs = _Lazy(chunk.name), _Lazy(chunk.sequence)
-    sel = parsed & (cols["cls"] == 1) & (cols["sa_off"][1:] > cols["sa_off"][:-1])     # primary records with an SA tag: few
     if sa == "device":
         cand = _assemble_device(ctx_or_fns, chunk, cols, sig, names, seqs, sel, chrom, chrom_rank, sv_size, min_mapq, max_split_parts, max_size)
     else:
@@ -610,16 +544,38 @@ def single_pipe_bam(ctx_or_fns, bamfile, chrom, task_start, task_end, chrom_rank
     return cand, reads_info
 
 
-def _assemble_device(ctx, chunk, cols, sig, names, seqs, sel, chrom, chrom_rank, sv_size, min_mapq, max_split_parts, max_size):
-    """_assemble for sa="device": the split-read inputs of the records `sel` are parsed and analysed on the device; the calls
-    it flags go through encode_split_reads and their candidates are merged at their place in call (= read) order"""
-    skw = dict(sv_size=sv_size, min_mapq=min_mapq, max_split_parts=max_split_parts, max_size=max_size)
+def _gates(cols, task_start, bed_regions, min_read_len, min_mapq):
+    """single_pipe's gates on the decoded columns of a task's chunk -> (gate: the records of the task, parsed: those parse_read
+    does not return from at once (:607), use: the `use` column of the CIGAR scan (:614), sel: the primary records with an SA tag)"""
+    gate = (cols["cls"] != 0) & (cols["ref_start"] >= task_start)
+    if bed_regions is not None:
+        gate &= _in_bed(cols["ref_start"], cols["ref_end"], bed_regions)
+    parsed = gate & (cols["query_len"] >= min_read_len)
+    use = (parsed & (cols["mapq"] >= min_mapq)).astype(np.uint8)
+    return gate, parsed, use, parsed & (cols["cls"] == 1) & (cols["sa_off"][1:] > cols["sa_off"][:-1])
+
+
+def _split_on_device(ctx, chunk, cols, sel, chrom, chrom_rank, min_mapq, skw, pool=None):
+    """The split-read analysis of the records `sel` of the context's last decode: their SA tags are parsed on the device and
+    analysed in place (with `pool`: straight to pool rows, only the count comes back); the calls the device flags go through
+    encode_split_reads and the host-fed analysis.  -> (split inputs, device-side result or None when there is no call, indices
+    of the flagged calls, their reads, host-side candidates or None when nothing is flagged)"""
     si = split_inputs_bam(ctx, chunk, cols, sel, chrom_rank, chrom, min_mapq, host_outputs=False)
-    ssig = split_signatures(ctx, None, from_bam=si, **skw) if si["n_calls"] else None
+    dsig = split_signatures(ctx, None, from_bam=si, pool=pool, host_outputs=pool is None, **skw) if si["n_calls"] else None
+    calls, reads, fsig = np.zeros(0, np.int64), [], None
     if si["n_flagged"]:
         calls, reads = _flagged_reads(chunk, cols, si, sel, chrom, min_mapq)
         fsig = split_signatures(ctx, encode_split_reads(reads, chrom_rank), **skw)
-        both = {k: np.concatenate([ssig[k], calls[fsig[k]].astype(np.int32) if k == "read" else fsig[k]]) for k, _ in _SPLIT_OUT}
+    return si, dsig, calls, reads, fsig
+
+
+def _assemble_device(ctx, chunk, cols, sig, names, seqs, sel, chrom, chrom_rank, sv_size, min_mapq, max_split_parts, max_size):
+    """_assemble for sa="device": the split-read inputs of the records `sel` are parsed and analysed on the device; the calls
+    it flags go through encode_split_reads and their candidates are merged at their place in call (= read) order"""
+    si, ssig, calls, _, fsig = _split_on_device(ctx, chunk, cols, sel, chrom, chrom_rank, min_mapq,
+                                                dict(sv_size=sv_size, min_mapq=min_mapq, max_split_parts=max_split_parts, max_size=max_size))
+    if fsig is not None:
+        both = {k: np.concatenate([ssig[k], calls[fsig[k]].astype(np.int32) if k == "read" else fsig[k]]) for k, _, _ in _SPLIT_OUT}
         order = np.argsort(both["read"], kind="stable")      # (a call's candidates all come from one side, in their order)
         ssig = {k: v[order] for k, v in both.items()}
     c_ins, c_del = candidates(sig, names, seqs, chrom)
@@ -644,24 +600,14 @@ def task_to_pool(ctx, bamfile, chrom, task_start, task_end, chrom_rank, sv_size,
     chunk = bamfile.records(chrom, task_start, task_end)
     cols = bam_mod.decode(ctx, chunk, host_outputs=False)
     start, end, mapq, qlen = cols["ref_start"], cols["ref_end"], cols["mapq"], cols["query_len"]
-    gate = (cols["cls"] != 0) & (start >= task_start)
-    if bed_regions is not None:
-        in_bed = np.zeros(chunk.n, bool)
-        for b0, b1 in bed_regions:                           # not (pos_end <= b0 or pos_start >= b1)
-            in_bed |= (end > b0) & (start < b1)
-        gate &= in_bed
-    parsed = gate & (qlen >= min_read_len)
-    use = (parsed & (mapq >= min_mapq)).astype(np.uint8)
+    gate, _, use, sel = _gates(cols, task_start, bed_regions, min_read_len, min_mapq)
     sig = cigar_signatures(ctx, None, None, None, use, min_siglength=min_siglength, merge_ins_threshold=merge_ins_threshold, merge_del_threshold=merge_del_threshold,
                            pool=dict(seg_ins=seg_ins, seg_del=seg_del, read_base=read_base, query_len=qlen), host_outputs=False, from_bam=cols)
-    sel = parsed & (cols["cls"] == 1) & (cols["sa_off"][1:] > cols["sa_off"][:-1])
-    skw = dict(sv_size=sv_size, min_mapq=min_mapq, max_split_parts=max_split_parts, max_size=max_size)
-    si = split_inputs_bam(ctx, chunk, cols, sel, chrom_rank, chrom, min_mapq, host_outputs=False)
-    n_split = split_signatures(ctx, None, from_bam=si, pool=dict(seg_base=seg_base, read_base=read_base), host_outputs=False, **skw)["n"] if si["n_calls"] else 0
-    calls, n_host = np.zeros(0, np.int64), 0
-    if si["n_flagged"]:
-        calls, reads = _flagged_reads(chunk, cols, si, sel, chrom, min_mapq)
-        fsig = split_signatures(ctx, encode_split_reads(reads, chrom_rank), **skw)
+    si, dsig, calls, reads, fsig = _split_on_device(ctx, chunk, cols, sel, chrom, chrom_rank, min_mapq,
+                                                    dict(sv_size=sv_size, min_mapq=min_mapq, max_split_parts=max_split_parts, max_size=max_size),
+                                                    pool=dict(seg_base=seg_base, read_base=read_base))
+    n_split, n_host = 0 if dsig is None else dsig["n"], 0
+    if fsig is not None:
         rows = pool_rows_of_split(fsig, seg_base, 0, [r[2] for r in reads])
         rebuild.pool_append(ctx, rows["seg"], rows["a"], rows["b"], read_base + si["call_rec"][calls][fsig["read"]], rows["aux"])
         n_host = len(fsig["kind"])

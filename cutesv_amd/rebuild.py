@@ -15,25 +15,9 @@ import ctypes as C
 import numpy as np
 
 from . import _abi
+from ._abi import RebuildIn, RebuildOut, TIE_ORDER_FN
 from ._lib import lib
 from .columns import SigStore, NameTable, TYPES
-
-
-class RebuildIn(C.Structure):
-    _fields_ = [("n", C.c_int64), ("n_seg", C.c_int32), ("flags", C.c_int32), ("seg_aux_major", C.c_void_p),
-                ("seg_id", C.c_void_p), ("a", C.c_void_p), ("b", C.c_void_p), ("read_id", C.c_void_p), ("aux", C.c_void_p),
-                ("seg_nodedup", C.c_void_p), ("read_rank", C.c_void_p), ("n_rank", C.c_int64), ("tie_order", C.c_void_p), ("tie_user", C.c_void_p)]
-
-
-# csv_tie_order_fn (include/cutesv_hip.h): int (*)(void* user, int64 n_groups, const int64* group_off, const int32* src_row, int32* order, uint8* drop)
-TIE_ORDER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_uint8))
-
-
-class RebuildOut(C.Structure):
-    _fields_ = [("n_out", C.c_int64), ("seg_id", C.c_void_p), ("a", C.c_void_p), ("b", C.c_void_p), ("read_id", C.c_void_p),
-                ("aux", C.c_void_p), ("src_row", C.c_void_p), ("ms_device", C.c_float), ("n_passes", C.c_int32),
-                ("seg_count", C.c_void_p), ("n_ins_ties", C.c_int64), ("dev_seg_id", C.c_void_p), ("dev_a", C.c_void_p), ("dev_b", C.c_void_p),
-                ("dev_read_id", C.c_void_p), ("dev_aux", C.c_void_p), ("dev_src_row", C.c_void_p), ("n_tie_rows", C.c_int64), ("n_tie_dropped", C.c_int64)]
 
 
 def tie_callback(seq_of_src, half_of_src):
@@ -69,43 +53,70 @@ def rebuild_columns(ctx, seg_id, a, b, read_id, aux, seg_aux_major, seg_nodedup=
     addresses of a / b / read_id / aux, valid until the context's next rebuild / extraction call) and, from the host side,
     only src_row and seg_count - 4 instead of 28 bytes per row cross PCIe.
     src_row_out: an int32 array of at least n entries to receive src_row (a page-locked one lands by DMA)."""
-    L = lib()
-    L.csv_rebuild_signatures.restype = C.c_int
-    L.csv_rebuild_signatures.argtypes = [C.c_void_p, C.POINTER(RebuildIn), C.POINTER(RebuildOut)]
     seg_id = np.ascontiguousarray(seg_id, np.int32); a = np.ascontiguousarray(a, np.int64); b = np.ascontiguousarray(b, np.int64)
     read_id = np.ascontiguousarray(read_id, np.int32); aux = np.ascontiguousarray(aux, np.int32)
-    major = np.ascontiguousarray(seg_aux_major, np.uint8)
-    nodedup = None if seg_nodedup is None else np.ascontiguousarray(seg_nodedup, np.uint8)
     n = len(a)
     if src_row_out is not None and (src_row_out.dtype != np.int32 or len(src_row_out) < n or not src_row_out.flags.c_contiguous):
         raise ValueError("src_row_out must be a contiguous int32 array of at least %d entries" % n)
-    if keep_on_device:                                    # (the five sorted columns stay on the device: no host arrays for them)
-        o = dict(src_row=src_row_out if src_row_out is not None else np.empty(n, np.int32))
-    else:
-        o = dict(seg_id=np.empty(n, np.int32), a=np.empty(n, np.int64), b=np.empty(n, np.int64), read_id=np.empty(n, np.int32),
-                 aux=np.empty(n, np.int32), src_row=src_row_out if src_row_out is not None else np.empty(n, np.int32))
+    return _rebuild(ctx, n, dict(seg_id=seg_id, a=a, b=b, read_id=read_id, aux=aux), None, seg_aux_major, seg_nodedup, keep_on_device, tie_order, src_row_out)
+
+
+def _rebuild(ctx, n_out, cols, read_rank, seg_aux_major, seg_nodedup, keep_on_device, tie_order, src_row_out=None):
+    """The one csv_rebuild_signatures call: over the caller's columns `cols` (converted to the ABI's widths), or, cols=None, over
+    the context's pool with its read indices replaced through `read_rank`.  n_out: rows the result arrays must hold."""
+    major = np.ascontiguousarray(seg_aux_major, np.uint8)
+    nodedup = None if seg_nodedup is None else np.ascontiguousarray(seg_nodedup, np.uint8)
+    rank = None if read_rank is None else np.ascontiguousarray(read_rank, np.int32)
+    o = {}
+    if not keep_on_device:                                # (else the five sorted columns stay on the device: no host arrays for them)
+        o = dict(seg_id=np.empty(n_out, np.int32), a=np.empty(n_out, np.int64), b=np.empty(n_out, np.int64), read_id=np.empty(n_out, np.int32),
+                 aux=np.empty(n_out, np.int32))
+    o["src_row"] = src_row_out if src_row_out is not None else np.empty(n_out, np.int32)
     seg_count = np.zeros(len(major), np.int64)
-    rin = RebuildIn(n=n, n_seg=len(major), flags=_abi.RB_KEEP_ON_DEVICE if keep_on_device else 0, seg_aux_major=major.ctypes.data,
-                    seg_id=seg_id.ctypes.data, a=a.ctypes.data, b=b.ctypes.data, read_id=read_id.ctypes.data, aux=aux.ctypes.data,
-                    seg_nodedup=None if nodedup is None else nodedup.ctypes.data,
-                    tie_order=None if tie_order is None else C.cast(tie_order, C.c_void_p))
-    if keep_on_device:
-        rout = RebuildOut(src_row=o["src_row"].ctypes.data, seg_count=seg_count.ctypes.data)
+    rin = RebuildIn(n_seg=len(major), flags=_abi.RB_KEEP_ON_DEVICE if keep_on_device else 0, seg_aux_major=major.ctypes.data,
+                    seg_nodedup=None if nodedup is None else nodedup.ctypes.data, tie_order=None if tie_order is None else C.cast(tie_order, C.c_void_p))
+    if cols is None:
+        rin.flags |= _abi.RB_FROM_POOL
+        rin.read_rank, rin.n_rank = rank.ctypes.data, len(rank)
     else:
-        rout = RebuildOut(seg_id=o["seg_id"].ctypes.data, a=o["a"].ctypes.data, b=o["b"].ctypes.data, read_id=o["read_id"].ctypes.data,
-                          aux=o["aux"].ctypes.data, src_row=o["src_row"].ctypes.data, seg_count=seg_count.ctypes.data)
-    ctx._check(L.csv_rebuild_signatures(ctx._h, C.byref(rin), C.byref(rout)))
+        rin.n = n_out
+        for k, v in cols.items():
+            setattr(rin, k, v.ctypes.data)
+    rout = RebuildOut(seg_count=seg_count.ctypes.data, **{k: v.ctypes.data for k, v in o.items()})
+    ctx._check(lib().csv_rebuild_signatures(ctx._h, C.byref(rin), C.byref(rout)))
     k = int(rout.n_out)
-    out = {key: v[:k] for key, v in o.items()} if not keep_on_device else {"src_row": o["src_row"][:k]}
-    out["ms_device"] = float(rout.ms_device)
-    out["n_passes"] = int(rout.n_passes)
-    out["seg_count"] = seg_count
-    out["n_ins_ties"] = int(rout.n_ins_ties)
-    out["n_tie_rows"], out["n_tie_dropped"] = int(rout.n_tie_rows), int(rout.n_tie_dropped)
-    out["n_out"] = k
+    out = {key: v[:k] for key, v in o.items()}
+    out.update(ms_device=float(rout.ms_device), n_passes=int(rout.n_passes), seg_count=seg_count, n_ins_ties=int(rout.n_ins_ties),
+               n_tie_rows=int(rout.n_tie_rows), n_tie_dropped=int(rout.n_tie_dropped), n_out=k)
     if keep_on_device:
         out["dev"] = dict(a=rout.dev_a, b=rout.dev_b, read_id=rout.dev_read_id, aux=rout.dev_aux, seg_id=rout.dev_seg_id, src_row=rout.dev_src_row)
     return out
+
+
+def _segments(chroms, ins_nodedup):
+    """Segment s = type index * len(chroms) + rank of the chromosome's name: -> (chromosome indices in name order, rank per
+    chromosome, seg_aux_major: INV / TRA sort on aux first, seg_nodedup: the INS segments keep every row when ins_nodedup)"""
+    order = sorted(range(len(chroms)), key=lambda i: chroms[i])
+    crank = np.zeros(len(chroms), np.int64)
+    crank[order] = np.arange(len(chroms))
+    n = len(chroms)
+    major, nodedup = np.zeros(len(TYPES) * n, np.uint8), np.zeros(len(TYPES) * n, np.uint8)
+    for ti, t in enumerate(TYPES):
+        if t in ("INV", "TRA"):
+            major[ti * n:(ti + 1) * n] = 1
+        if t == "INS" and ins_nodedup:
+            nodedup[ti * n:(ti + 1) * n] = 1
+    return order, crank, major, nodedup
+
+
+def _reads_by_chrom(reads, n_chrom):
+    """the reads table as keyword arguments of SigStore / HostBatch: blocks by chromosome only, as main script :810 leaves them"""
+    if reads is None:
+        return {}
+    rc = np.asarray(reads["chrom"], np.int64)
+    o = np.argsort(rc, kind="stable")
+    return dict(reads_off=np.searchsorted(rc[o], np.arange(n_chrom + 1)).astype(np.int64), r_start=np.asarray(reads["start"], np.int64)[o],
+                r_end=np.asarray(reads["end"], np.int64)[o], r_primary=np.asarray(reads["primary"], np.uint8)[o], r_id=np.asarray(reads["read_id"], np.int32)[o])
 
 
 _STAGE = (("seg", np.int32), ("a", np.int64), ("b", np.int64), ("rid", np.int32), ("aux", np.int32), ("src_row", np.int32))
@@ -148,9 +159,9 @@ def rebuild_to_device_batch(ctx, chroms, per_type, params_segment, reads=None):
     de-duplicated on the whole tuple as the reference does - the few tie rows' indices visit the host through the library's
     tie_order callback, the columns do not (r03 raised on the first tie and sent the whole genome through host memory).
     Without `seq` the integer columns decide."""
-    order = sorted(range(len(chroms)), key=lambda i: chroms[i])
-    crank = np.zeros(len(chroms), np.int64)
-    crank[order] = np.arange(len(chroms))
+    ins = per_type.get("INS")
+    ins_ties = ins is not None and ins.get("seq") is not None and len(ins["a"]) > 0
+    order, crank, major, nodedup = _segments(chroms, ins_ties)
     # The five columns are written ONCE, in the ABI's widths, into page-locked staging arrays the context keeps (no per-type
     # temporaries, no concatenate pass, and the upload is a DMA at the link's rate instead of a staged copy of pageable memory:
     # the 80 MB of a 30x genome's rows took 4 of the chain's 8.6 ms)
@@ -181,16 +192,9 @@ def rebuild_to_device_batch(ctx, chroms, per_type, params_segment, reads=None):
         for fn, args, kw in jobs:
             fn(*args, **kw)
     n_seg = len(TYPES) * len(chroms)
-    major = np.zeros(n_seg, np.uint8)
-    nodedup = np.zeros(n_seg, np.uint8)
-    for ti, t in enumerate(TYPES):
-        if t in ("INV", "TRA"):
-            major[ti * len(chroms):(ti + 1) * len(chroms)] = 1
     ti_ins = TYPES.index("INS")
     cb = None
-    ins = per_type.get("INS")
-    if ins is not None and ins.get("seq") is not None and len(ins["a"]):
-        nodedup[ti_ins * len(chroms):(ti_ins + 1) * len(chroms)] = 1
+    if ins_ties:
         ins_base = sum(len(per_type[t]["a"]) for t in TYPES[:ti_ins] if t in per_type)
         seqs = ins["seq"]
         half = ins.get("half")
@@ -208,13 +212,8 @@ def rebuild_to_device_batch(ctx, chroms, per_type, params_segment, reads=None):
         t, ci = TYPES[s // len(chroms)], order[s % len(chroms)]
         segs.append(params_segment(t, ci, int(off[s]), int(off[s + 1])))
         tasks.append((t, chroms[ci]))
-    kw = {}
-    if reads is not None:
-        rc = np.asarray(reads["chrom"], np.int64)
-        o = np.argsort(rc, kind="stable")
-        kw = dict(reads_off=np.searchsorted(rc[o], np.arange(len(chroms) + 1)).astype(np.int64), r_start=np.asarray(reads["start"], np.int64)[o],
-                  r_end=np.asarray(reads["end"], np.int64)[o], r_primary=np.asarray(reads["primary"], np.uint8)[o], r_id=np.asarray(reads["read_id"], np.int32)[o])
-    batch = _abi.HostBatch.on_device(np.array(segs, dtype=_abi.SEGMENT_DTYPE), r["dev"], r["n_out"], n_chrom=len(chroms), keep=ctx, **kw)
+    batch = _abi.HostBatch.on_device(np.array(segs, dtype=_abi.SEGMENT_DTYPE), r["dev"], r["n_out"], n_chrom=len(chroms), keep=ctx,
+                                     **_reads_by_chrom(reads, len(chroms)))
     return batch, tasks, r["src_row"]
 
 
@@ -241,29 +240,7 @@ def rebuild_pool(ctx, read_rank, seg_aux_major, seg_nodedup=None, keep_on_device
     (extract.cigar_signatures(pool=...)) and those appended with pool_append, sorted and de-duplicated; a row's read index is
     replaced by read_rank[index] (rank of the read's name in Python string order).  Same result dict as rebuild_columns;
     src_row numbers the pool's rows (extraction order)."""
-    L = lib()
-    L.csv_rebuild_signatures.restype = C.c_int
-    L.csv_rebuild_signatures.argtypes = [C.c_void_p, C.POINTER(RebuildIn), C.POINTER(RebuildOut)]
-    rank = np.ascontiguousarray(read_rank, np.int32)
-    major = np.ascontiguousarray(seg_aux_major, np.uint8)
-    nodedup = None if seg_nodedup is None else np.ascontiguousarray(seg_nodedup, np.uint8)
-    n = pool_rows(ctx)
-    o = dict(src_row=np.empty(n, np.int32))
-    if not keep_on_device:
-        o.update(seg_id=np.empty(n, np.int32), a=np.empty(n, np.int64), b=np.empty(n, np.int64), read_id=np.empty(n, np.int32), aux=np.empty(n, np.int32))
-    seg_count = np.zeros(len(major), np.int64)
-    rin = RebuildIn(n=0, n_seg=len(major), flags=_abi.RB_FROM_POOL | (_abi.RB_KEEP_ON_DEVICE if keep_on_device else 0), seg_aux_major=major.ctypes.data,
-                    seg_nodedup=None if nodedup is None else nodedup.ctypes.data, read_rank=rank.ctypes.data, n_rank=len(rank),
-                    tie_order=None if tie_order is None else C.cast(tie_order, C.c_void_p))
-    rout = RebuildOut(seg_count=seg_count.ctypes.data, **{k: v.ctypes.data for k, v in o.items()})
-    ctx._check(L.csv_rebuild_signatures(ctx._h, C.byref(rin), C.byref(rout)))
-    k = int(rout.n_out)
-    r = {name: v[:k] for name, v in o.items()}
-    r.update(ms_device=float(rout.ms_device), n_passes=int(rout.n_passes), seg_count=seg_count, n_ins_ties=int(rout.n_ins_ties), n_out=k,
-             n_tie_rows=int(rout.n_tie_rows), n_tie_dropped=int(rout.n_tie_dropped))
-    if keep_on_device:
-        r["dev"] = dict(a=rout.dev_a, b=rout.dev_b, read_id=rout.dev_read_id, aux=rout.dev_aux, seg_id=rout.dev_seg_id, src_row=rout.dev_src_row)
-    return r
+    return _rebuild(ctx, pool_rows(ctx), None, read_rank, seg_aux_major, seg_nodedup, keep_on_device, tie_order)
 
 
 def finish_ins_ties(r, ins_segs, seq_of_src, half_of_src):
@@ -309,9 +286,8 @@ def store_from_unsorted(ctx, chroms, per_type, names=None, strands=("++", "--"),
     Segments come out in the reference's order: types as main_ctrl submits them, chromosomes by name.
     `reads`: optional dict(chrom, start, end, primary, read_id): blocks keep their input order (csv_cluster_batch orders
     every block by start on the device)."""
-    order = sorted(range(len(chroms)), key=lambda i: chroms[i])
-    crank = np.zeros(len(chroms), np.int64)
-    crank[order] = np.arange(len(chroms))
+    ins_seq_in = per_type.get("INS", {}).get("seq") if "INS" in per_type else None
+    order, crank, major, nodedup = _segments(chroms, ins_seq_in is not None)
     cols = {k: [] for k in ("seg", "a", "b", "rid", "aux")}
     ins_base, ins_n = 0, 0
     n_rows = 0
@@ -327,16 +303,7 @@ def store_from_unsorted(ctx, chroms, per_type, names=None, strands=("++", "--"),
         cols["rid"].append(np.asarray(d["read_id"], np.int32)); cols["aux"].append(np.asarray(d["aux"], np.int32))       # (the ABI's widths: no conversion pass later)
         n_rows += len(ch)
     cat = {k: np.concatenate(v) if v else np.zeros(0, np.int64) for k, v in cols.items()}
-    n_seg = len(TYPES) * len(chroms)
-    major = np.zeros(n_seg, np.uint8)
-    nodedup = np.zeros(n_seg, np.uint8)
-    ins_seq_in = per_type.get("INS", {}).get("seq") if "INS" in per_type else None
     ti_ins = TYPES.index("INS")
-    for ti, t in enumerate(TYPES):
-        if t in ("INV", "TRA"):
-            major[ti * len(chroms):(ti + 1) * len(chroms)] = 1
-    if ins_seq_in is not None:
-        nodedup[ti_ins * len(chroms):(ti_ins + 1) * len(chroms)] = 1
     r = rebuild_columns(ctx, cat["seg"], cat["a"], cat["b"], cat["rid"], cat["aux"], major, nodedup)
     ins_seq = None
     if ins_seq_in is not None:
@@ -354,13 +321,6 @@ def store_from_unsorted(ctx, chroms, per_type, names=None, strands=("++", "--"),
     for i in range(len(bounds) - 1):
         s = int(seg_sorted[bounds[i]])
         seg_index[(TYPES[s // len(chroms)], chroms[order[s % len(chroms)]])] = (int(bounds[i]), int(bounds[i + 1]))
-    kw = {}
-    if reads is not None:
-        rc = np.asarray(reads["chrom"], np.int64)
-        o = np.argsort(rc, kind="stable")                       # by chromosome only, as main script :810 leaves the block
-        off = np.searchsorted(rc[o], np.arange(len(chroms) + 1)).astype(np.int64)
-        kw = dict(reads_off=off, r_start=np.asarray(reads["start"], np.int64)[o], r_end=np.asarray(reads["end"], np.int64)[o],
-                  r_primary=np.asarray(reads["primary"], np.uint8)[o], r_id=np.asarray(reads["read_id"], np.int32)[o])
     st = SigStore(chroms=list(chroms), a=r["a"], b=r["b"], read_id=r["read_id"], aux=r["aux"], seg_index=seg_index,
-                  names=names or NameTable(), strands=tuple(strands), ins_seq=ins_seq, **kw)
+                  names=names or NameTable(), strands=tuple(strands), ins_seq=ins_seq, **_reads_by_chrom(reads, len(chroms)))
     return st, r

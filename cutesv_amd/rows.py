@@ -20,23 +20,11 @@ import weakref
 import numpy as np
 
 from . import _abi
+from ._abi import RowsIn
 from ._lib import lib
 from .genotype import gl_fields, gl_table_blob
 
 _TRA_ALT = ("N[%s[", "N]%s]", "[%s[N", "]%s]N")      # cuteSV_resolveTRA.py:142-153
-
-
-class RowsIn(C.Structure):
-    _fields_ = [
-        ("res", C.POINTER(_abi.BatchOut)), ("seg", C.c_void_p), ("n_seg", C.c_int32), ("n_chrom", C.c_int32),
-        ("chrom_name", C.POINTER(C.c_char_p)),
-        ("read_id", C.c_void_p), ("aux", C.c_void_p),
-        ("name_blob", C.c_char_p), ("name_off", C.c_void_p), ("n_names", C.c_int64),
-        ("name_prefix", C.c_char_p), ("name_width", C.c_int32), ("n_strand", C.c_int32),
-        ("ins_blob", C.c_char_p), ("ins_off", C.c_void_p),
-        ("strand_name", C.POINTER(C.c_char_p)),
-        ("gl_blob", C.c_char_p), ("gl_off", C.c_void_p),
-    ]
 
 
 def _native():
@@ -71,8 +59,6 @@ def _rows_in(store, segments, res):
 def rows_blob(store, segments, res):
     """The C ABI's form of the rows (csv_rows_emit): -> (bytes, number of rows); fields '\\t', rows '\\n'"""
     L = lib()
-    L.csv_rows_emit.restype = C.c_int
-    L.csv_rows_emit.argtypes = [C.POINTER(RowsIn), C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
     rin, keep = _rows_in(store, segments, res)
     need = C.c_int64(0)
     rc = L.csv_rows_emit(C.byref(rin), None, 0, C.byref(need))       # first pass only counts

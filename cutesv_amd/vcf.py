@@ -11,22 +11,9 @@ import ctypes as C
 import numpy as np
 
 from . import _abi
+from ._abi import VcfIn
 from ._lib import lib
 from .genotype import gl_fields
-
-
-class VcfIn(C.Structure):
-    _fields_ = [
-        ("res", C.POINTER(_abi.BatchOut)), ("seg", C.c_void_p), ("n_seg", C.c_int32), ("n_chrom", C.c_int32),
-        ("chrom_name", C.POINTER(C.c_char_p)), ("chrom_seq", C.POINTER(C.c_char_p)), ("chrom_len", C.c_void_p),
-        ("chrom_rank", C.c_void_p),
-        ("ins_alt", C.c_char_p), ("ins_alt_off", C.c_void_p), ("rnames", C.c_char_p), ("rnames_off", C.c_void_p),
-        ("strand_name", C.POINTER(C.c_char_p)),
-        ("gl_key", C.c_void_p), ("gl_str", C.POINTER(C.c_char_p)), ("n_gl", C.c_int32),
-        ("min_size", C.c_int64), ("max_size", C.c_int64),
-        ("genotype", C.c_int32), ("report_readid", C.c_int32), ("ignore_sequence", C.c_int32), ("reserved", C.c_int32),
-        ("chrom_line_bases", C.c_void_p), ("chrom_line_width", C.c_void_p),
-    ]
 
 
 def _csr(strings):
@@ -57,8 +44,6 @@ def emit_records(store, segments, res, reference, min_size=30, max_size=100000, 
                `f.write(view)` needs no copy of the text - with real REF sequences a 30x genome's records are ~30 MB
     """
     L = lib()
-    L.csv_vcf_emit.restype = C.c_int
-    L.csv_vcf_emit.argtypes = [C.POINTER(VcfIn), C.c_char_p, C.c_int64, C.POINTER(C.c_int64), C.c_void_p]
     t = res.trimmed()
     n = res.n_calls
     segs = np.ascontiguousarray(segments, dtype=_abi.SEGMENT_DTYPE)

@@ -34,6 +34,10 @@ def lib():
         _LIB.csvo_cipos.argtypes = [C.c_double, C.c_int64]
         _LIB.csvo_cover_count.restype = C.c_int
         _LIB.csvo_cover_count.argtypes = [C.c_void_p] * 4 + [C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+        _LIB.csvo_cigar_signatures.restype = C.c_int
+        _LIB.csvo_cigar_signatures.argtypes = [C.POINTER(_abi.CigarIn), C.POINTER(_abi.CigarOut)]
+        _LIB.csvo_split_signatures.restype = C.c_int
+        _LIB.csvo_split_signatures.argtypes = [C.POINTER(_abi.SplitIn), C.POINTER(_abi.SplitOut)]
     return _LIB
 
 
@@ -115,27 +119,18 @@ def cover_count(r_start, r_end, r_primary, r_id, L2, R2):
     return out
 
 
+def _check(rc):
+    if rc != _abi.OK:
+        raise RuntimeError("oracle: %s" % _abi.ERR_NAME.get(rc, rc))
+
+
 def cigar_signatures(cig_off, cigar, ref_start, use=None, min_siglength=10, merge_ins_threshold=100, merge_del_threshold=0):
     """the C restatement of the CIGAR scan (csvo_cigar_signatures); same result dict as cutesv_amd.extract.cigar_signatures"""
     from cutesv_amd import extract
-    L = lib()
-    L.csvo_cigar_signatures.restype = C.c_int
-    L.csvo_cigar_signatures.argtypes = [C.POINTER(extract.CigarIn), C.POINTER(extract.CigarOut)]
-
-    def check(rc):
-        if rc != _abi.OK:
-            raise RuntimeError("oracle: %s" % _abi.ERR_NAME.get(rc, rc))
-    return extract._run(L.csvo_cigar_signatures, None, cig_off, cigar, ref_start, use, min_siglength, merge_ins_threshold, merge_del_threshold, check)
+    return extract._run(lib().csvo_cigar_signatures, None, cig_off, cigar, ref_start, use, min_siglength, merge_ins_threshold, merge_del_threshold, _check)
 
 
 def split_signatures(enc, sv_size=30, min_mapq=20, max_split_parts=7, max_size=100000):
     """the C restatement of the split-read analysis (csvo_split_signatures); same result dict as cutesv_amd.extract.split_signatures"""
     from cutesv_amd import extract
-    L = lib()
-    L.csvo_split_signatures.restype = C.c_int
-    L.csvo_split_signatures.argtypes = [C.POINTER(extract.SplitIn), C.POINTER(extract.SplitOut)]
-
-    def check(rc):
-        if rc != _abi.OK:
-            raise RuntimeError("oracle: %s" % _abi.ERR_NAME.get(rc, rc))
-    return extract._run_split(L.csvo_split_signatures, None, enc, sv_size, min_mapq, max_split_parts, max_size, check)
+    return extract._run_split(lib().csvo_split_signatures, None, enc, sv_size, min_mapq, max_split_parts, max_size, _check)
