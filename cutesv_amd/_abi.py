@@ -21,6 +21,7 @@ GL_TABLE_SIZE = 101 * 101 + 2
 IN_PER_SIG, IN_READS_SORTED, IN_SIG_I32, IN_READS_I32, IN_DEVICE_COLUMNS, IN_SIG_DELTA16, IN_READS_DELTA16 = 1, 2, 4, 8, 16, 32, 64     # csv_batch_in.flags
 RB_KEEP_ON_DEVICE = 1
 RB_FROM_POOL = 2                        # ... the rows are the context's device-resident signature pool
+RB_RANK_FROM_NAMES = 4                  # ... with RB_FROM_POOL: the read ranks are those of the context's name pool (csv_name_ranks)
 CG_TO_POOL = 1                         # csv_cigar_in.flags: the signatures also become pool rows                         # csv_rebuild_in.flags
 CG_FROM_BAM = 2                        # csv_cigar_in.flags: scan the device columns of the context's last csv_bam_decode
 SP_FROM_BAM = 4                        # csv_split_in.flags: the reads are the calls of the context's last csv_bam_split_inputs
@@ -100,6 +101,11 @@ class RebuildOut(C.Structure):
                 ("aux", C.c_void_p), ("src_row", C.c_void_p), ("ms_device", C.c_float), ("n_passes", C.c_int32),
                 ("seg_count", C.c_void_p), ("n_ins_ties", C.c_int64), ("dev_seg_id", C.c_void_p), ("dev_a", C.c_void_p), ("dev_b", C.c_void_p),
                 ("dev_read_id", C.c_void_p), ("dev_aux", C.c_void_p), ("dev_src_row", C.c_void_p), ("n_tie_rows", C.c_int64), ("n_tie_dropped", C.c_int64)]
+
+
+class NameRankOut(C.Structure):
+    _fields_ = [("n", C.c_int64), ("n_distinct", C.c_int64), ("rank", C.c_void_p), ("first", C.c_void_p), ("cap_first", C.c_int64),
+                ("ms_device", C.c_float), ("n_passes", C.c_int32), ("max_len", C.c_int32), ("reserved", C.c_int32), ("dev_rank", C.c_void_p)]
 
 
 class VcfIn(C.Structure):
@@ -211,6 +217,7 @@ STRUCT_SIZES = [("csv_segment", SEGMENT_DTYPE.itemsize), ("csv_batch_in", C.size
                 ("csv_cigar_out", C.sizeof(CigarOut)), ("csv_split_in", C.sizeof(SplitIn)), ("csv_split_out", C.sizeof(SplitOut))]
 BAM_STRUCT_SIZES = [("csv_bam_chunk", C.sizeof(ChunkC)), ("csv_bam_in", C.sizeof(BamIn)), ("csv_bam_out", C.sizeof(BamOut))]
 SA_STRUCT_SIZES = [("csv_sa_in", C.sizeof(SaIn)), ("csv_sa_out", C.sizeof(SaOut))]
+NAME_STRUCT_SIZES = [("csv_name_rank_out", C.sizeof(NameRankOut))]
 
 
 def _ptr(arr):

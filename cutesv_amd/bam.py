@@ -56,6 +56,12 @@ class Chunk:
     def _name_len(self, i):
         return int(self.slim[int(self.rec_off[i]) + 8])                       # l_read_name, NUL included
 
+    def name_columns(self):
+        """-> (off int64[n], len int32[n]): name i is host[off[i] : off[i] + len[i]] - the strided form csv_name_pool_append
+        takes, with `host` as its bytes: no name is sliced or copied here"""
+        n_len = self.slim[self.rec_off + 8].astype(np.int32) if self.n else np.zeros(0, np.int32)      # l_read_name, NUL included
+        return np.ascontiguousarray(self.host_off[:self.n], np.int64), np.maximum(n_len - 1, 0)
+
     def name(self, i):
         h0 = int(self.host_off[i])
         return self.host[h0 : h0 + self._name_len(i) - 1].tobytes().decode()

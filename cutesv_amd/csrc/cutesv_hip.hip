@@ -21,6 +21,7 @@
 #include "split.hip.h"
 #include "bam.hip.h"
 #include "sa.hip.h"
+#include "names.hip.h"
 
 using namespace csv;
 
@@ -147,6 +148,16 @@ struct csv_ctx {
     // the device-resident signature pool (stand-alone allocations: it outlives the per-call arenas)
     Buf pool_seg, pool_a, pool_b, pool_read, pool_aux, sp_qlen;
     i64 pool_n = 0, pool_cap = 0;
+    // the device-resident name pool (names.hip.h; stand-alone allocations, grown by copying): nm_blob = the names back to back,
+    // nm_off = nm_n + 1 offsets into it; nm_len = the lengths once more on the host (csv_name_pool_get sizes its blob from them).
+    // nm_rank / nm_first hold the ranks of the first nm_n names while nm_fresh; the sort's scratch is slices of `arena_nm`.
+    Buf nm_blob, nm_off, nm_rank, nm_first, nm_get;
+    Arena arena_nm;
+    Buf nm_words, nm_perm0, nm_perm1, nm_hist, nm_tot, nm_vary, nm_flag, nm_partial;
+    std::vector<uint8_t> nm_len;
+    i64 nm_n = 0, nm_bytes = 0, nm_distinct = 0;
+    bool nm_fresh = false;
+    float nm_ms = 0; int nm_passes = 0, nm_maxlen = 0;
     // CIGAR scan (slices of `arena_rb` as well: the two steps never overlap)
     Buf sp_off, sp_len, sp_c0, sp_c1, sp_f0, sp_f1, sp_chr, sp_mapq, sp_strand, sp_primary, sp_seg, sp_cnt, sp_tiles, sp_tot,
         sp_kind, sp_read, sp_ochr, sp_aux, sp_a, sp_b, sp_c, sp_d;
@@ -463,12 +474,14 @@ void csv_ctx_destroy(csv_ctx* c)
     (void)hipSetDevice(c->device);
     (void)hipDeviceSynchronize();
     Buf* own[] = {&c->pool_seg, &c->pool_a, &c->pool_b, &c->pool_read, &c->pool_aux, &c->sp_qlen, &c->sqrt_tab, &c->rcp_tab, &c->cipk_tab, &c->cnt, &c->rstate, &c->gs_chrom, &c->gs_perm0, &c->gs_perm1, &c->gs_hist, &c->gs_tot, &c->flush, &c->bm_sabeg, &c->bm_saend,
-                  &c->sa_c0, &c->sa_c1, &c->sa_f0, &c->sa_f1, &c->sa_chr, &c->sa_mapq, &c->sa_strand, &c->sa_primary};
+                  &c->sa_c0, &c->sa_c1, &c->sa_f0, &c->sa_f1, &c->sa_chr, &c->sa_mapq, &c->sa_strand, &c->sa_primary,
+                  &c->nm_blob, &c->nm_off, &c->nm_rank, &c->nm_first, &c->nm_get};
     for (Buf* b : own) if (b->p) (void)hipFree(b->p);
     if (c->arena.base) (void)hipFree(c->arena.base);
     if (c->arena_rb.base) (void)hipFree(c->arena_rb.base);
     if (c->arena_bam.base) (void)hipFree(c->arena_bam.base);
     if (c->arena_sa.base) (void)hipFree(c->arena_sa.base);
+    if (c->arena_nm.base) (void)hipFree(c->arena_nm.base);
     if (c->h_pin) (void)hipHostFree(c->h_pin);
     if (c->h_flag) (void)hipHostFree((void*)c->h_flag);
     if (c->h_pub) (void)hipHostFree(c->h_pub);
@@ -1813,6 +1826,182 @@ int csv_pool_append(csv_ctx* c, int64_t n, const int32_t* seg_id, const int64_t*
     return CSV_OK;
 }
 
+
+// ---------------------------------------------------------------------------------------- the name pool and its ranks (names.hip.h)
+// room for `bytes` in a stand-alone buffer whose first `keep` bytes must survive (grows by copying, by half)
+static int grow_keep(csv_ctx* c, Buf& b, size_t bytes, size_t keep)
+{
+    if (bytes <= b.cap) return CSV_OK;
+    const size_t want = bytes + bytes / 2 + 4096;
+    void* p = nullptr;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    hipError_t e = hipMalloc(&p, want);
+    if (e != hipSuccess) return fail(c, CSV_E_NOMEM, "hipMalloc(%zu) for the name pool failed: %s", want, hipGetErrorString(e));
+    if (keep > 0 && b.p) HIP_TRY(c, hipMemcpy(p, b.p, keep, hipMemcpyDeviceToDevice));
+    if (b.p) HIP_TRY(c, hipFree(b.p));
+    b.p = p; b.cap = want;
+    return CSV_OK;
+}
+
+int csv_name_pool_reset(csv_ctx* c)
+{
+    if (!c) return CSV_E_INVALID;
+    c->nm_n = 0; c->nm_bytes = 0; c->nm_maxlen = 0; c->nm_len.clear();
+    c->nm_fresh = false;
+    return CSV_OK;
+}
+
+int csv_name_pool_rows(const csv_ctx* c, int64_t* n)
+{
+    if (!c || !n) return CSV_E_INVALID;
+    *n = c->nm_n;
+    return CSV_OK;
+}
+
+int csv_name_pool_append(csv_ctx* c, int64_t n, const uint8_t* bytes, int64_t n_bytes, const int64_t* off, const int32_t* len, int64_t* first_index)
+{
+    if (!c) return CSV_E_INVALID;
+    if (n < 0 || n_bytes < 0 || (n > 0 && (!off || !len)) || (n_bytes > 0 && !bytes)) return fail(c, CSV_E_INVALID, "bad name pool append");
+    // every range is checked before the pool changes or anything is launched
+    i64 total = 0; int mx = 0;
+    for (i64 i = 0; i < n; i++) {
+        if (len[i] < 0 || len[i] > NAME_MAX_LEN) return fail(c, CSV_E_INVALID, "name %lld: length %d is outside [0, %d]", (long long)i, len[i], NAME_MAX_LEN);
+        if (off[i] < 0 || off[i] > n_bytes || (i64)len[i] > n_bytes - off[i])
+            return fail(c, CSV_E_INVALID, "name %lld: bytes [%lld, %lld) leave the %lld bytes given", (long long)i, (long long)off[i], (long long)off[i] + len[i], (long long)n_bytes);
+        total += len[i];
+        mx = len[i] > mx ? len[i] : mx;
+    }
+    if (c->nm_n + n >= (1ll << 31) - 4096) return fail(c, CSV_E_INVALID, "name pool too large (%lld names)", (long long)(c->nm_n + n));
+    if (first_index) *first_index = c->nm_n;
+    if (n == 0) return CSV_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    // the names back to back and their offsets in the pool's blob: what crosses the link (a chunk's host image also holds the bases)
+    std::vector<uint8_t> blob((size_t)total);
+    std::vector<i64> offs((size_t)n + 1);
+    i64 at = 0;
+    for (i64 i = 0; i < n; i++) {
+        offs[(size_t)i] = c->nm_bytes + at;
+        if (len[i]) memcpy(blob.data() + at, bytes + off[i], (size_t)len[i]);
+        at += len[i];
+    }
+    offs[(size_t)n] = c->nm_bytes + at;
+    { const int rc = grow_keep(c, c->nm_blob, (size_t)(c->nm_bytes + total) + 8, (size_t)c->nm_bytes); if (rc) return rc; }
+    { const int rc = grow_keep(c, c->nm_off, (size_t)(c->nm_n + n + 1) * 8, c->nm_n ? (size_t)(c->nm_n + 1) * 8 : 0); if (rc) return rc; }
+    hipStream_t st = c->stream;
+    if (total) HIP_TRY(c, hipMemcpyAsync((char*)c->nm_blob.p + c->nm_bytes, blob.data(), (size_t)total, hipMemcpyHostToDevice, st));
+    HIP_TRY(c, hipMemcpyAsync(dp<i64>(c->nm_off) + c->nm_n, offs.data(), (size_t)(n + 1) * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(c, hipStreamSynchronize(st));                   // (the vectors are the copies' sources)
+    c->nm_len.reserve((size_t)(c->nm_n + n));
+    for (i64 i = 0; i < n; i++) c->nm_len.push_back((uint8_t)len[i]);
+    c->nm_n += n; c->nm_bytes += total;
+    c->nm_maxlen = mx > c->nm_maxlen ? mx : c->nm_maxlen;
+    c->nm_fresh = false;
+    return CSV_OK;
+}
+
+// the ranks of the pool's names into nm_rank / nm_first (nothing to do while they are fresh)
+static int name_ranks_impl(csv_ctx* c)
+{
+    if (c->nm_fresh) return CSV_OK;
+    const i64 n = c->nm_n;
+    c->nm_ms = 0; c->nm_passes = 0; c->nm_distinct = 0;
+    if (n == 0) { c->nm_fresh = true; return CSV_OK; }
+    const int W = std::max(1, (c->nm_maxlen + 7) / 8);
+    const int nunits = div_up(n, SORT_WTILE), nblk = div_up(nunits, 4), ntile = div_up(n, NAME_TILE);
+    { const int rc = reserve(c, c->nm_rank, (size_t)n * 4); if (rc) return rc; }
+    { const int rc = reserve(c, c->nm_first, (size_t)n * 4); if (rc) return rc; }
+    Plan P;
+    P.add(c->nm_words, (size_t)W * n * 8); P.add(c->nm_perm0, (size_t)n * 4); P.add(c->nm_perm1, (size_t)n * 4);
+    P.add(c->nm_hist, (size_t)256 * nunits * 4); P.add(c->nm_tot, 256 * 4); P.add(c->nm_vary, (NAME_MAX_WORDS + 1) * 8);
+    P.add(c->nm_flag, (size_t)n); P.add(c->nm_partial, ((size_t)ntile + 2) * 4);
+    {
+        if (P.total > c->arena_nm.cap) HIP_TRY(c, hipDeviceSynchronize());
+        const int rc = commit(c, c->arena_nm, P);
+        if (rc) return rc;
+    }
+    hipStream_t st = c->stream;
+    u64* words = dp<u64>(c->nm_words);
+    HIP_TRY(c, hipMemsetAsync(c->nm_vary.p, 0, (NAME_MAX_WORDS + 1) * 8, st));
+    HIP_TRY(c, hipEventRecord(c->ev[0], st));
+    hipLaunchKernelGGL(k_name_pack, dim3(ntile, W), dim3(256), 0, st, dp<uint8_t>(c->nm_blob), dp<i64>(c->nm_off), n, words, dp<unsigned long long>(c->nm_vary));
+    // the byte positions at which any two names differ: one radix pass each, least significant (the last byte of the last word) first
+    unsigned long long vary[NAME_MAX_WORDS] = {};
+    HIP_TRY(c, hipMemcpyAsync(vary, c->nm_vary.p, (size_t)W * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    const int* pin = nullptr;
+    int* pout = dp<int>(c->nm_perm0);
+    int npass = 0;
+    for (int w = W - 1; w >= 0; w--)
+        for (int shift = 0; shift < 64; shift += 8) {
+            if (((vary[w] >> shift) & 255ull) == 0) continue;
+            SortPass SP{words + (i64)w * n, 1, shift, n, nunits, pin, pout, dp<int>(c->nm_hist)};
+            hipLaunchKernelGGL(k_sort_hist, dim3(nblk), dim3(256), 0, st, SP);
+            hipLaunchKernelGGL(k_sort_rowsum, dim3(256), dim3(256), 0, st, dp<int>(c->nm_hist), nunits, dp<int>(c->nm_tot));
+            hipLaunchKernelGGL(k_sort_rowscan, dim3(256), dim3(256), 0, st, dp<int>(c->nm_hist), nunits, dp<int>(c->nm_tot));
+            hipLaunchKernelGGL(k_sort_scatter, dim3(nblk), dim3(256), 0, st, SP);
+            pin = pout;
+            pout = (pout == dp<int>(c->nm_perm0)) ? dp<int>(c->nm_perm1) : dp<int>(c->nm_perm0);
+            npass++;
+        }
+    int* d_n = (int*)((char*)c->nm_vary.p + NAME_MAX_WORDS * 8);
+    NameRank R{n, W, words, pin, dp<uint8_t>(c->nm_flag), dp<int>(c->nm_partial), dp<int>(c->nm_rank), dp<int>(c->nm_first), d_n};
+    hipLaunchKernelGGL(k_name_count, dim3(ntile), dim3(256), 0, st, R);
+    hipLaunchKernelGGL(k_name_apply, dim3(ntile), dim3(256), 0, st, R);
+    HIP_TRY(c, hipEventRecord(c->ev[1], st));
+    HIP_TRY(c, hipGetLastError());
+    int nd = 0;
+    HIP_TRY(c, hipMemcpyAsync(&nd, d_n, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    HIP_TRY(c, hipEventElapsedTime(&c->nm_ms, c->ev[0], c->ev[1]));
+    c->nm_distinct = nd; c->nm_passes = npass;
+    c->nm_fresh = true;
+    return CSV_OK;
+}
+
+int csv_name_ranks(csv_ctx* c, csv_name_rank_out* out)
+{
+    if (!c || !out) return CSV_E_INVALID;
+    HIP_TRY(c, hipSetDevice(c->device));
+    { const int rc = name_ranks_impl(c); if (rc) return rc; }
+    out->n = c->nm_n; out->n_distinct = c->nm_distinct; out->ms_device = c->nm_ms; out->n_passes = c->nm_passes; out->max_len = c->nm_maxlen;
+    out->dev_rank = c->nm_n ? c->nm_rank.p : nullptr;
+    if (out->first && out->cap_first < c->nm_distinct) return fail(c, CSV_E_CAPACITY, "first: %lld entries are needed", (long long)c->nm_distinct);
+    hipStream_t st = c->stream;
+    if (out->rank && c->nm_n) HIP_TRY(c, hipMemcpyAsync(out->rank, c->nm_rank.p, (size_t)c->nm_n * 4, hipMemcpyDeviceToHost, st));
+    if (out->first && c->nm_distinct) HIP_TRY(c, hipMemcpyAsync(out->first, c->nm_first.p, (size_t)c->nm_distinct * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    return CSV_OK;
+}
+
+int csv_name_pool_get(csv_ctx* c, int64_t n, const int32_t* index, char* out, int64_t cap, int64_t* out_off)
+{
+    if (!c) return CSV_E_INVALID;
+    if (n < 0 || cap < 0 || !out_off || (n > 0 && !index) || (cap > 0 && !out)) return fail(c, CSV_E_INVALID, "bad name pool get");
+    out_off[0] = 0;
+    for (i64 k = 0; k < n; k++) {
+        if (index[k] < 0 || index[k] >= c->nm_n) return fail(c, CSV_E_INVALID, "index[%lld] = %d is outside the %lld names of the pool", (long long)k, index[k], (long long)c->nm_n);
+        out_off[k + 1] = out_off[k] + c->nm_len[(size_t)index[k]];
+    }
+    const i64 total = out_off[n];
+    if (total > cap) return fail(c, CSV_E_CAPACITY, "out: %lld bytes are needed", (long long)total);
+    if (n == 0 || total == 0) return CSV_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    // one buffer: the gathered bytes, then (8-byte aligned) the offsets and the indices
+    const size_t o_off = ((size_t)total + 7) & ~(size_t)7, o_idx = o_off + (size_t)(n + 1) * 8;
+    { const int rc = grow_keep(c, c->nm_get, o_idx + (size_t)n * 4, 0); if (rc) return rc; }
+    hipStream_t st = c->stream;
+    char* g = (char*)c->nm_get.p;
+    HIP_TRY(c, hipMemcpyAsync(g + o_off, out_off, (size_t)(n + 1) * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(c, hipMemcpyAsync(g + o_idx, index, (size_t)n * 4, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_name_gather, dim3(div_up(n, 4)), dim3(256), 0, st, dp<uint8_t>(c->nm_blob), dp<i64>(c->nm_off), (const int*)(g + o_idx), (const i64*)(g + o_off), n, (uint8_t*)g);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(out, g, (size_t)total, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    return CSV_OK;
+}
+
+size_t csv_name_struct_size(int which) { return which == 0 ? sizeof(csv_name_rank_out) : 0; }
+
 int csv_rebuild_signatures(csv_ctx* c, const csv_rebuild_in* in, csv_rebuild_out* out)
 {
     if (!c || !in || !out) return CSV_E_INVALID;
@@ -1821,8 +2010,18 @@ int csv_rebuild_signatures(csv_ctx* c, const csv_rebuild_in* in, csv_rebuild_out
     const i64 n = from_pool ? c->pool_n : in->n;
     out->n_out = 0; out->ms_device = 0; out->n_passes = 0;
     if (n < 0 || n >= (1ll << 31) - 4096 || in->n_seg <= 0) return fail(c, CSV_E_INVALID, "bad rebuild input");
-    if (from_pool && (!in->read_rank || in->n_rank <= 0 || !in->seg_aux_major)) return fail(c, CSV_E_INVALID, "CSV_RB_FROM_POOL needs read_rank");
+    // CSV_RB_RANK_FROM_NAMES: the ranks are the name pool's, in device memory already (computed now if an append made them stale)
+    const bool by_name = from_pool && (in->flags & CSV_RB_RANK_FROM_NAMES) != 0;
+    if ((in->flags & CSV_RB_RANK_FROM_NAMES) && !from_pool) return fail(c, CSV_E_INVALID, "CSV_RB_RANK_FROM_NAMES needs CSV_RB_FROM_POOL");
+    if (from_pool && ((!by_name && (!in->read_rank || in->n_rank <= 0)) || !in->seg_aux_major)) return fail(c, CSV_E_INVALID, "CSV_RB_FROM_POOL needs read_rank");
     if (n == 0) return CSV_OK;
+    if (by_name) {
+        if (c->nm_n == 0) return fail(c, CSV_E_INVALID, "CSV_RB_RANK_FROM_NAMES: the name pool is empty");
+        const int rc = name_ranks_impl(c);
+        if (rc) return rc;
+    }
+    const int* d_rank = by_name ? dp<int>(c->nm_rank) : nullptr;
+    const i64 n_rank = by_name ? c->nm_n : in->n_rank;
     // key widths (bits that are non-zero somewhere) and the validity of every row: found on the device, behind the upload (r04
     // walked the columns on the host first: ~3 ms for a 30x genome's 2.85 M rows, in front of a 0.5 ms sort)
     i64 mx_a = 0, mx_b = 0; int mx_rid = 0, mx_aux = 0, mx_seg = 0, mx_aux_all = 0;
@@ -1836,7 +2035,7 @@ int csv_rebuild_signatures(csv_ctx* c, const csv_rebuild_in* in, csv_rebuild_out
     PL(rb_tot, RS_RADIX * 4); PL(rb_partial, (ntile + 2) * 4);
     PL(rb_el0, (size_t)n * 32); PL(rb_el1, (size_t)n * 32);          // composite-key elements (16 or 32 bytes each; sized for either)
     PL(rb_oseg, n * 4); PL(rb_oa, n * 8); PL(rb_ob, n * 8); PL(rb_orid, n * 4); PL(rb_oaux, n * 4); PL(rb_osrc, n * 4); PL(rb_segcnt, ((size_t)in->n_seg + 2) * 8);
-    if (from_pool) PL(rb_rank, (size_t)in->n_rank * 4);
+    if (from_pool && !by_name) PL(rb_rank, (size_t)in->n_rank * 4);
     PL(rb_mx, 64);
     if (in->tie_order && in->seg_nodedup) PL(rb_drop, n + 64);
 #undef PL
@@ -1857,11 +2056,14 @@ int csv_rebuild_signatures(csv_ctx* c, const csv_rebuild_in* in, csv_rebuild_out
     }
     {
         // the rows -> the input columns (pool rows: read index -> name rank; host rows: in place), the key widths from the device
-        if (from_pool) HIP_TRY(c, hipMemcpyAsync(c->rb_rank.p, in->read_rank, (size_t)in->n_rank * 4, hipMemcpyHostToDevice, st));
+        if (from_pool && !by_name) {
+            HIP_TRY(c, hipMemcpyAsync(c->rb_rank.p, in->read_rank, (size_t)in->n_rank * 4, hipMemcpyHostToDevice, st));
+            d_rank = dp<int>(c->rb_rank);
+        }
         HIP_TRY(c, hipMemsetAsync(c->rb_mx.p, 0, 64, st));
         if (from_pool)
             hipLaunchKernelGGL(k_pool_to_rows, dim3(div_up(n, 2048)), dim3(256), 0, st, dp<int>(c->pool_seg), dp<i64>(c->pool_a), dp<i64>(c->pool_b),
-                               dp<int>(c->pool_read), dp<int>(c->pool_aux), n, dp<int>(c->rb_rank), (i64)in->n_rank, in->n_seg, dp<uint8_t>(c->rb_major),
+                               dp<int>(c->pool_read), dp<int>(c->pool_aux), n, d_rank, n_rank, in->n_seg, dp<uint8_t>(c->rb_major),
                                dp<int>(c->rb_seg), dp<i64>(c->rb_a), dp<i64>(c->rb_b), dp<int>(c->rb_rid), dp<int>(c->rb_aux), dp<unsigned long long>(c->rb_mx));
         else
             hipLaunchKernelGGL(k_pool_to_rows, dim3(div_up(n, 2048)), dim3(256), 0, st, dp<int>(c->rb_seg), dp<i64>(c->rb_a), dp<i64>(c->rb_b),

@@ -584,7 +584,7 @@ def _assemble_device(ctx, chunk, cols, sig, names, seqs, sel, chrom, chrom_rank,
 
 # ------------------------------------------------------------------------------------ a task's region -> rows of the pool
 def task_to_pool(ctx, bamfile, chrom, task_start, task_end, chrom_rank, sv_size, min_mapq, max_split_parts, min_read_len, min_siglength,
-                 merge_del_threshold, merge_ins_threshold, max_size, seg_ins, seg_del, seg_base, read_base, bed_regions=None):
+                 merge_del_threshold, merge_ins_threshold, max_size, seg_ins, seg_del, seg_base, read_base, bed_regions=None, name_pool=False):
     """The body of an extraction task without a candidate tuple, a name string or a sequence: the records of the region
     (`bamfile.records`) are decoded on the device, the CIGAR scan appends its signatures to the context's pool from the decoded
     columns (CSV_CG_FROM_BAM | CSV_CG_TO_POOL), the SA tags are parsed there (split_inputs_bam) and the split-read analysis appends
@@ -595,10 +595,26 @@ def task_to_pool(ctx, bamfile, chrom, task_start, task_end, chrom_rank, sv_size,
 
     -> dict: n_records, n_sig_ins, n_sig_del, n_calls, n_entries, n_split (candidates of the device path), n_split_host (of the
     flagged calls), n_flagged, flagged_calls / flagged_records (indices of the flagged calls and of their records), and the
-    columns of the reads table rows (:729-733) reads_start, reads_end, reads_primary, reads_index (index in the chunk)."""
+    columns of the reads table rows (:729-733) reads_start, reads_end, reads_primary, reads_index (index in the chunk).
+
+    name_pool=True: the chunk's read names are appended to the context's name pool (rebuild.name_pool_append_chunk) after the
+    decode, so that a row's read index IS its name's index: read_base must equal the name pool's row count (ValueError before
+    anything is appended) or be None to take it.  The result gains name_base (= that read_base); with `ranks` =
+    rebuild.name_ranks(ctx)["rank"] the read ids of the task's reads-table rows are ranks[name_base + reads_index], the id
+    space of rebuild.rebuild_pool_by_name's read_id column."""
     from . import bam as bam_mod, rebuild
+    if name_pool:
+        n_names = rebuild.name_pool_rows(ctx)
+        if read_base is None:
+            read_base = n_names
+        elif read_base != n_names:
+            raise ValueError("read_base is %d but the name pool holds %d names: a row's read index must be its name's index" % (read_base, n_names))
+    elif read_base is None:
+        raise ValueError("read_base=None needs name_pool=True")
     chunk = bamfile.records(chrom, task_start, task_end)
     cols = bam_mod.decode(ctx, chunk, host_outputs=False)
+    if name_pool:
+        rebuild.name_pool_append_chunk(ctx, chunk)
     start, end, mapq, qlen = cols["ref_start"], cols["ref_end"], cols["mapq"], cols["query_len"]
     gate, _, use, sel = _gates(cols, task_start, bed_regions, min_read_len, min_mapq)
     sig = cigar_signatures(ctx, None, None, None, use, min_siglength=min_siglength, merge_ins_threshold=merge_ins_threshold, merge_del_threshold=merge_del_threshold,
@@ -612,6 +628,7 @@ def task_to_pool(ctx, bamfile, chrom, task_start, task_end, chrom_rank, sv_size,
         rebuild.pool_append(ctx, rows["seg"], rows["a"], rows["b"], read_base + si["call_rec"][calls][fsig["read"]], rows["aux"])
         n_host = len(fsig["kind"])
     keep = np.flatnonzero(gate & (mapq >= min_mapq))
-    return dict(n_records=chunk.n, n_sig_ins=sig["n_sig_ins"], n_sig_del=sig["n_sig_del"], n_calls=si["n_calls"], n_entries=si["n_entries"], n_split=n_split,
+    extra = dict(name_base=read_base) if name_pool else {}
+    return dict(**extra, n_records=chunk.n, n_sig_ins=sig["n_sig_ins"], n_sig_del=sig["n_sig_del"], n_calls=si["n_calls"], n_entries=si["n_entries"], n_split=n_split,
                 n_split_host=n_host, n_flagged=si["n_flagged"], flagged_calls=calls, flagged_records=si["call_rec"][calls],
                 reads_start=start[keep], reads_end=end[keep], reads_primary=(cols["cls"][keep] == 1).astype(np.uint8), reads_index=keep)

@@ -15,7 +15,7 @@ import ctypes as C
 import numpy as np
 
 from . import _abi
-from ._abi import RebuildIn, RebuildOut, TIE_ORDER_FN
+from ._abi import RebuildIn, RebuildOut, TIE_ORDER_FN, NameRankOut
 from ._lib import lib
 from .columns import SigStore, NameTable, TYPES
 
@@ -63,7 +63,8 @@ def rebuild_columns(ctx, seg_id, a, b, read_id, aux, seg_aux_major, seg_nodedup=
 
 def _rebuild(ctx, n_out, cols, read_rank, seg_aux_major, seg_nodedup, keep_on_device, tie_order, src_row_out=None):
     """The one csv_rebuild_signatures call: over the caller's columns `cols` (converted to the ABI's widths), or, cols=None, over
-    the context's pool with its read indices replaced through `read_rank`.  n_out: rows the result arrays must hold."""
+    the context's pool with its read indices replaced through `read_rank` (None: through the ranks of the context's name pool,
+    CSV_RB_RANK_FROM_NAMES).  n_out: rows the result arrays must hold."""
     major = np.ascontiguousarray(seg_aux_major, np.uint8)
     nodedup = None if seg_nodedup is None else np.ascontiguousarray(seg_nodedup, np.uint8)
     rank = None if read_rank is None else np.ascontiguousarray(read_rank, np.int32)
@@ -77,7 +78,10 @@ def _rebuild(ctx, n_out, cols, read_rank, seg_aux_major, seg_nodedup, keep_on_de
                     seg_nodedup=None if nodedup is None else nodedup.ctypes.data, tie_order=None if tie_order is None else C.cast(tie_order, C.c_void_p))
     if cols is None:
         rin.flags |= _abi.RB_FROM_POOL
-        rin.read_rank, rin.n_rank = rank.ctypes.data, len(rank)
+        if rank is None:                                  # (the ranks of the context's name pool, on the device already)
+            rin.flags |= _abi.RB_RANK_FROM_NAMES
+        else:
+            rin.read_rank, rin.n_rank = rank.ctypes.data, len(rank)
     else:
         rin.n = n_out
         for k, v in cols.items():
@@ -241,6 +245,88 @@ def rebuild_pool(ctx, read_rank, seg_aux_major, seg_nodedup=None, keep_on_device
     replaced by read_rank[index] (rank of the read's name in Python string order).  Same result dict as rebuild_columns;
     src_row numbers the pool's rows (extraction order)."""
     return _rebuild(ctx, pool_rows(ctx), None, read_rank, seg_aux_major, seg_nodedup, keep_on_device, tie_order)
+
+
+# ------------------------------------------------------------------------------------ the device-resident name pool
+def name_pool_reset(ctx):
+    ctx._check(lib().csv_name_pool_reset(ctx._h))
+
+
+def name_pool_rows(ctx):
+    n = C.c_int64(0)
+    ctx._check(lib().csv_name_pool_rows(ctx._h, C.byref(n)))
+    return int(n.value)
+
+
+def name_pool_append(ctx, data, off, length):
+    """csv_name_pool_append: name i = data[off[i] : off[i] + length[i]] (data: uint8 array or bytes) -> the index of the first
+    appended name; the others follow it.  The ranges are checked by the library (CsvError E_INVALID, pool unchanged)."""
+    data = np.frombuffer(data, np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else np.ascontiguousarray(data, np.uint8)
+    off = np.ascontiguousarray(off, np.int64); length = np.ascontiguousarray(length, np.int32)
+    if len(off) != len(length):
+        raise ValueError("one offset and one length per name are expected")
+    first = C.c_int64(0)
+    ctx._check(lib().csv_name_pool_append(ctx._h, len(off), data.ctypes.data if len(data) else None, len(data), off.ctypes.data if len(off) else None,
+                                          length.ctypes.data if len(off) else None, C.byref(first)))
+    return int(first.value)
+
+
+def name_pool_append_chunk(ctx, chunk):
+    """the read names of a bam.Chunk, straight out of its host image: name index = returned base + record index"""
+    off, length = chunk.name_columns()
+    return name_pool_append(ctx, chunk.host, off, length)
+
+
+def name_ranks(ctx, host=True):
+    """csv_name_ranks -> dict(rank, first, n, n_distinct, ms_device, n_passes, max_len): rank[i] = index of name i in
+    sorted(set(names)) (unsigned bytes; Python's str order for ASCII names), first[r] = smallest index holding the name of rank
+    r.  The ranks stay on the device for rebuild_pool_by_name; host=False leaves them there (rank / first are None)."""
+    n = name_pool_rows(ctx)
+    rank = np.empty(n, np.int32) if host else None
+    first = np.empty(n, np.int32) if host else None
+    o = NameRankOut(rank=rank.ctypes.data if host and n else None, first=first.ctypes.data if host and n else None, cap_first=n if host else 0)
+    ctx._check(lib().csv_name_ranks(ctx._h, C.byref(o)))
+    return dict(rank=rank, first=first[:int(o.n_distinct)] if host else None, n=int(o.n), n_distinct=int(o.n_distinct), ms_device=float(o.ms_device),
+                n_passes=int(o.n_passes), max_len=int(o.max_len))
+
+
+def name_pool_get(ctx, index, raw=False):
+    """csv_name_pool_get: the names at `index` (gathered on the device) -> list of str (raw=True: of bytes)"""
+    index = np.ascontiguousarray(index, np.int32)
+    n = len(index)
+    out = np.empty(max(1, 255 * n), np.uint8)
+    off = np.zeros(n + 1, np.int64)
+    ctx._check(lib().csv_name_pool_get(ctx._h, n, index.ctypes.data if n else None, out.ctypes.data, len(out), off.ctypes.data))
+    blob, o = out[:int(off[-1])].tobytes(), off.tolist()
+    names = [blob[o[k]:o[k + 1]] for k in range(n)]
+    return names if raw else [x.decode() for x in names]
+
+
+def name_ranks_host(data, off, length):
+    """What csv_name_ranks computes, in numpy: -> (rank int32[n], first int32[n_distinct]).  The names become rows of a
+    zero-padded fixed-width bytes column (NUL cannot occur inside a BAM name, so the padding orders a prefix first) and
+    np.unique does the rest.  The CPU path and the checker of the kernels, like bam.decode_host."""
+    data = np.frombuffer(data, np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else np.asarray(data, np.uint8)
+    off = np.asarray(off, np.int64); length = np.asarray(length, np.int64)
+    n = len(off)
+    if n == 0:
+        return np.zeros(0, np.int32), np.zeros(0, np.int32)
+    if (length < 0).any() or (length > 255).any() or (off < 0).any() or (off + length > len(data)).any():
+        raise ValueError("a name lies outside the bytes given or is longer than 255 bytes")
+    width = max(1, int(length.max()))
+    mat = np.zeros((n, width), np.uint8)
+    row = np.repeat(np.arange(n), length)
+    col = np.arange(int(length.sum())) - np.repeat(np.cumsum(length) - length, length)
+    mat[row, col] = data[np.repeat(off, length) + col]
+    _, first, rank = np.unique(mat.view("S%d" % width).ravel(), return_index=True, return_inverse=True)
+    return rank.astype(np.int32).ravel(), first.astype(np.int32)
+
+
+def rebuild_pool_by_name(ctx, seg_aux_major, seg_nodedup=None, keep_on_device=True, tie_order=None):
+    """rebuild_pool with a row's read index replaced by the rank of that index in the context's NAME pool
+    (CSV_RB_FROM_POOL | CSV_RB_RANK_FROM_NAMES): the ranks are computed on the device when an append made them stale and never
+    visit the host.  A pool row whose read index has no name fails the call (CsvError E_INVALID).  Same result dict."""
+    return _rebuild(ctx, pool_rows(ctx), None, None, seg_aux_major, seg_nodedup, keep_on_device, tie_order)
 
 
 def finish_ins_ties(r, ins_segs, seq_of_src, half_of_src):

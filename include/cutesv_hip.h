@@ -22,6 +22,7 @@
 #ifndef CUTESV_HIP_H
 #define CUTESV_HIP_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -359,9 +360,14 @@ enum {
     CSV_RB_KEEP_ON_DEVICE = 1,       /* csv_rebuild_in.flags: the sorted columns stay in device memory (csv_rebuild_out.dev_*, valid
                                         until the context's next csv_rebuild_signatures / csv_cigar_signatures / csv_split_signatures
                                         call); host output arrays that are NULL are not written */
-    CSV_RB_FROM_POOL = 2             /* the rows are the context's device-resident signature pool (below): n, seg_id, a, b, read_id and
+    CSV_RB_FROM_POOL = 2,            /* the rows are the context's device-resident signature pool (below): n, seg_id, a, b, read_id and
                                         aux of csv_rebuild_in are ignored; a row's read index is replaced by read_rank[index] (the
-                                        rank of the read's NAME: string order is the caller's business); src_row numbers pool rows */
+                                        rank of the read's NAME: string order is the caller's business, or the library's with
+                                        CSV_RB_RANK_FROM_NAMES below); src_row numbers pool rows */
+    CSV_RB_RANK_FROM_NAMES = 4       /* with CSV_RB_FROM_POOL: read_rank / n_rank are ignored; a row's read index is replaced by the rank
+                                        of that index in the context's NAME pool (csv_name_ranks below; computed first when an append
+                                        made the cached ranks stale).  A row whose read index is >= the name count fails the call with
+                                        CSV_E_INVALID, like every other row the sort cannot take; the context stays usable */
 };
 /* The rows of the keep-every-row segments (seg_nodedup) whose integer keys tie - (segment, a, b, read_id) equal - are ordered
  * by data only the caller has: the reference sorts INS rows by (chr, int(pos), len, read, SEQUENCE) and drops a row only when
@@ -429,6 +435,49 @@ int csv_rebuild_signatures(csv_ctx* ctx, const csv_rebuild_in* in, csv_rebuild_o
 int csv_pool_reset(csv_ctx* ctx);
 int csv_pool_rows(const csv_ctx* ctx, int64_t* n_rows);
 int csv_pool_append(csv_ctx* ctx, int64_t n, const int32_t* seg_id, const int64_t* a, const int64_t* b, const int32_t* read, const int32_t* aux);
+
+/* The device-resident name pool: the read names behind the pool rows' read indices, and their ranks (names.hip.h, DESIGN.md
+ * section 15).  The rebuild order ends in the read name (MAIN:764-802: rows that tie on (pos, len) order by name; :958-969: a row
+ * repeats when its name repeats too), so the read-id column of the sorted rows must be an integer whose order is the names'
+ * string order.  A caller appends the names of every chunk it extracts - name index = the read index its pool rows carry - and
+ * CSV_RB_RANK_FROM_NAMES makes the rebuild use their ranks: no name is sorted, hashed or looked up on the host.
+ *
+ * csv_name_pool_append: name i of the call = bytes[off[i] .. off[i] + len[i]); the names get the indices first_index ..
+ *   first_index + n - 1.  The strided form is exactly a csv_bam_chunk's host image: bytes = host, off = host_off, len =
+ *   l_read_name - 1.  Every [off, off + len) is checked against n_bytes and 0 <= len <= 255 on the host before anything is
+ *   launched: CSV_E_INVALID otherwise, and the pool is unchanged.  The names are kept compact in a grow-only arena of the
+ *   context (a blob plus offsets); the pool lives until csv_name_pool_reset / csv_ctx_destroy.
+ * csv_name_ranks: rank[i] = index of name i in sorted(set(names)), the names compared as unsigned bytes - a name that is a prefix
+ *   of another sorts first, equal names get equal ranks; for ASCII names this is Python's str order.  first[r] = the smallest
+ *   index that holds the name of rank r (n_distinct entries; CSV_E_CAPACITY when cap_first is smaller, n_distinct holds the
+ *   need).  `rank` (n entries, n = csv_name_pool_rows) and `first` may be NULL.  The ranks stay in device memory (dev_rank, int32,
+ *   valid until the next append / reset) and are cached: a second call without an append in between launches nothing and
+ *   reports the figures of the run that made them.  n_passes: radix passes executed = byte positions at which any two names
+ *   differ (names that share a prefix or have fixed separators cost nothing there); max_len: the longest name.
+ * csv_name_pool_get: the names at index[0 .. n) gathered into one blob on the device and downloaded: name k = out[out_off[k] ..
+ *   out_off[k + 1]), no terminator.  Turns ids back into text (support lists, --report_readid: GT:263-458), typically for the
+ *   names at first[...] of the few thousand reads that support calls.  CSV_E_CAPACITY: cap is too small, out_off[n] holds the
+ *   need.  CSV_E_INVALID: an index outside the pool. */
+typedef struct csv_name_rank_out {
+    int64_t  n;                     /* out: names in the pool */
+    int64_t  n_distinct;            /* out */
+    int32_t* rank;                  /* n or NULL */
+    int32_t* first;                 /* cap_first or NULL */
+    int64_t  cap_first;
+    float    ms_device;             /* out: kernels only (HIP events) */
+    int32_t  n_passes;              /* out */
+    int32_t  max_len;               /* out */
+    int32_t  reserved;
+    void*    dev_rank;              /* out: int32 ranks in device memory, n entries */
+} csv_name_rank_out;
+
+int csv_name_pool_reset(csv_ctx* ctx);
+int csv_name_pool_rows(const csv_ctx* ctx, int64_t* n);
+int csv_name_pool_append(csv_ctx* ctx, int64_t n, const uint8_t* bytes, int64_t n_bytes, const int64_t* off, const int32_t* len, int64_t* first_index);
+int csv_name_ranks(csv_ctx* ctx, csv_name_rank_out* out);
+int csv_name_pool_get(csv_ctx* ctx, int64_t n, const int32_t* index, char* out, int64_t cap, int64_t* out_off /* n + 1 */);
+/* sizeof of 0 csv_name_rank_out; 0 otherwise */
+size_t csv_name_struct_size(int which);
 
 /* ---------------------------------------------------------------------------------------------
  * The CIGAR scan of the extraction step on the GPU.  Restates the CIGAR part of parse_read
