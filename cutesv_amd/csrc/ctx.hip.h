@@ -1,0 +1,303 @@
+// ctx.hip.h — the context of libcutesv_hip.so and the host helpers every entry shares: buffers and arenas, error reporting, the copy / timing /
+// sort skeleton of the extraction stages.  Host code only; included by cutesv_hip.hip behind the kernel headers (one translation unit).
+namespace {
+
+struct Buf { void* p = nullptr; size_t cap = 0; };      // a slice of an arena (or, for the few stand-alone buffers, its own allocation)
+
+// One device allocation for everything a batch needs: the buffers are planned (sizes -> offsets), the arena grows
+// only when the plan does not fit, and every Buf becomes a pointer into it.  (The first version reserved ~90 buffers
+// with one hipMalloc each: 2.7 ms on the first upload, and a larger batch re-allocated them one by one.)
+struct Arena { char* base = nullptr; size_t cap = 0; };
+struct Plan {
+    std::vector<std::pair<Buf*, size_t>> items;
+    size_t total = 0;
+    void add(Buf& b, size_t bytes)
+    {
+        items.emplace_back(&b, total);
+        b.cap = bytes;
+        total += (bytes + 255) & ~(size_t)255;
+    }
+};
+
+// ---- The state of the extraction-side stages (stage_*.hip.h), one struct each, with the rule that says how long its buffers
+// live and who may read them after the call returns.  `own` lists the stand-alone allocations for csv_ctx_destroy (slices
+// of an arena go with their arena).
+
+// The device-resident signature pool: stand-alone, grown by copying.  The rows live until csv_pool_reset; the CIGAR and
+// split entries append to them (CSV_CG_TO_POOL), the rebuild reads them (CSV_RB_FROM_POOL).
+struct PoolState {
+    Buf seg, a, b, read, aux;
+    i64 n = 0, cap = 0;
+    void own(std::vector<Buf*>& v) { v.insert(v.end(), {&seg, &a, &b, &read, &aux}); }
+};
+// The device-resident name pool (names.hip.h): blob = the names back to back, off = n + 1 offsets into it (stand-alone, grown
+// by copying), len = the lengths once more on the host (csv_name_pool_get sizes its blob from them).  rank / first hold the
+// ranks of the first n names while `fresh`, until the next append or reset: the rebuild reads rank in place
+// (CSV_RB_RANK_FROM_NAMES).  The sort's scratch is slices of `arena`, dead when the ranks are made.
+struct NameState {
+    Buf blob, off, rank, first, get;
+    Arena arena;
+    Buf words, perm0, perm1, hist, tot, vary, flag, partial;
+    std::vector<uint8_t> len;
+    i64 n = 0, bytes = 0, distinct = 0;
+    bool fresh = false;
+    float ms = 0; int passes = 0, maxlen = 0;
+    void own(std::vector<Buf*>& v) { v.insert(v.end(), {&blob, &off, &rank, &first, &get}); }
+};
+// Rebuild, CIGAR scan and split analysis: slices of csv_ctx::scratch, which every call of the three plans afresh.  Dead when
+// the call returns, with one exception: the caller of a CSV_RB_KEEP_ON_DEVICE rebuild may read oseg .. osrc (the dev_*
+// pointers of csv_rebuild_out) until the next call of ANY of the three.  The rebuild counts into the engine's counter block
+// (cnt + 768), so it clears `uploaded` and `ran`.  sp.qlen (the query lengths of a CSV_CG_TO_POOL call) stands alone.
+struct RebuildState {
+    Buf seg, a, b, rid, aux, auxk, major, nodedup, perm0, perm1, hist, tot, partial;
+    Buf oseg, oa, ob, orid, oaux, osrc, segcnt, rank, mx, drop, el0, el1;
+};
+struct CigarState { Buf qlen, off, ops, start, use, cnt, tiles, tot, iread, ipos, ilen, ip0, inp, pq, pl, dread, dpos, dlen; };
+struct SplitState {
+    Buf off, len, c0, c1, f0, f1, chr, mapq, strand, primary, seg, cnt, tiles, tot, kind, read, ochr, aux, a, b, c, d, qlen;
+    void own(std::vector<Buf*>& v) { v.push_back(&qlen); }
+};
+// BAM decode: slices of `arena`; the SA ranges are sized after the scan, so they stand alone.  Everything lives until the next
+// decode: csv_cigar_signatures with CSV_CG_FROM_BAM scans cigoff / cigar / start in place, csv_bam_split_inputs reads slim
+// and the record columns, the caller the dev_* pointers of csv_bam_out.
+struct BamState {
+    Arena arena;
+    Buf slim, recoff, reclen, start, end, flag, mapq, qlen, cl, cr, cls, status, cigoff, saoff, cigsrc, cgb, cge, cigar, long_list, cnt, tot;
+    Buf sabeg, saend;
+    i64 n = -1, nops = 0, nsa = 0;             // records / operations / SA tags of the last successful decode (-1: none)
+    void own(std::vector<Buf*>& v) { v.insert(v.end(), {&sabeg, &saend}); }
+};
+// Split inputs of the last decode (sa.hip.h): the tables sized before the kernels run are slices of `arena`, the entry columns
+// are sized by the count pass and stand alone.  They live until the next decode or the next csv_bam_split_inputs:
+// csv_split_signatures with CSV_SP_FROM_BAM reads them in place.
+struct SaState {
+    Arena arena;
+    Buf sel, names, nameoff, namerank, calloff, callrec, callsa, entoff, readlen, status, tot;
+    Buf c0, c1, f0, f1, chr, mapq, strand, primary;
+    i64 calls = -1, entries = 0;               // calls / entries the context holds (-1: no split inputs)
+    void own(std::vector<Buf*>& v) { v.insert(v.end(), {&c0, &c1, &f0, &f1, &chr, &mapq, &strand, &primary}); }
+};
+
+}  // namespace
+
+struct csv_ctx {
+    int         device = 0;
+    hipStream_t stream = nullptr;
+    hipStream_t side[3] = {};         // side streams: [0] mid + workgroup tier, [1] DUP/INV/TRA wavefront tier, [2] reads order + prefix max
+    hipStream_t copy[N_COPY_STREAMS] = {};    // host -> device column copies (one DMA engine each)
+    hipEvent_t  ev_init = nullptr, ev_sel = nullptr, ev_aux[3] = {}, ev_copy[N_COPY_STREAMS] = {}, ev_reads = nullptr, ev_anc = nullptr, ev_rd[5] = {};
+    std::string err;
+    hipEvent_t  ev[CSV_N_STAGES + 2] = {};
+    Arena       arena;
+    // batch buffers (slices of `arena`)
+    Buf seg, woff, seg_drop, a, b, rid, aux, a32, b32;
+    Buf tile_lead, tabs;
+    Buf ad16, anc;                             // CSV_IN_SIG_DELTA16: the gaps in w space; the anchor tables {per-tile offsets, w, value}
+    Buf rd16, ranc, rl16, rlesc;               // CSV_IN_READS_DELTA16: start gaps + their anchors, lengths + their escape rows / values
+    int  reads_delta = 0;                      // bit 0: the last upload's reads starts crossed as gaps, bit 1: its ends as lengths (csv_batch_info 3)
+    bool delta16 = false;                      // the last upload rebuilt its position column from gaps (csv_batch_info 2)
+    bool rstate_dirty = true;                  // the reads-order state may hold an earlier upload's verdict
+    bool reads_early = false;                  // the last upload decoded the reads table's start column on side[1] (upload_impl)
+    bool unpack_pending = false; UnpackArgs unpack_args{}; int unpack_tiles = 0;      // ... and k_unpack_a16 is still to be queued (one-shot calls: by the run)
+    Buf cluster_id, partial, tile_cnt, item_rec, list_small, list_big, list_tiny, list_wide, seg_gate, tile_info, ch_masks, tile_items, seg_err;
+    Buf item_cnt, item_base, item_chunk, sup_tmp;
+    Buf t_rec, t_rec0;
+    Buf sc_k, sc_x, sc_v1, sc_v2, sc_v3, sc_v4, sc_v5;
+    Buf o_rec, o_supsig, o_suprid, allele_id;
+    Buf o_rec2, o_supsig2;                     // the second result arena (runs alternate: a publish may still read the other one)
+    Buf reads_off, r_start, r_end, r_primary, r_id, s_start, s_end, s_idp, cmax, cfirst, bfirst, span_len, maxlen, gt_over, gt_huge, gt_pool, contig_len;
+    Buf ro_tcnt, ro_ent, ro_table, ro_tblk;
+    std::vector<int> h_tblk;                   // per tile of the reads table: the first chromosome block that begins at or after it
+    // stand-alone
+    Buf sqrt_tab, rcp_tab, cipk_tab, cnt, rstate;
+    Buf gs_chrom, gs_perm0, gs_perm1, gs_hist, gs_tot;          // general reads sort (fallback), allocated on first use
+    Buf flush;                                                   // csv_cache_flush scratch
+    // the extraction-side stages (their lifetime rules: at the structs)
+    PoolState pool; NameState nm; BamState bm; SaState sa;
+    Arena scratch;                             // per-call scratch of the rebuild, the CIGAR scan and the split analysis
+    RebuildState rb; CigarState cg; SplitState sp;
+    // page-locked host staging: small tables on the way in, counters + call records + support lists on the way out
+    char*  h_pin = nullptr;
+    size_t h_pin_cap = 0;
+    // two page-locked 64-bit words the device writes {run sequence, count}: items above 64 signatures (k_chain_apply), calls that
+    // overflowed the first genotype pass (k_genotype<8192>); read when a LATER run of the same upload is planned
+    // CSV_* environment switches of the run path (timing / debugging aids), read once per upload: csv_batch_run - a 36 us
+    // step - looks nothing up in the environment
+    struct RunOpts {
+        bool debug = false, debug_counters = false, no_fork = false, fork_always = false, no_swap = false, no_peek = false;
+        bool no_pair_in_mid = false, no_publish = false;
+        int  iw_grid = 0, gt_grid = 0, tier_fork_min = 1 << 30, mid_grid = 0, big_grid = 0;
+        bool pub_inplace = false, no_reads_overlap = false;
+    } opt;
+    volatile int* h_flag = nullptr;
+    int*          d_flag = nullptr;
+    int           run_seq = 0;
+    int           upload_seq0 = 0;          // run_seq when the resident batch was uploaded: later sequence numbers are runs of it
+    int           n_cu = 256;              // compute units of the device
+    // host copies
+    std::vector<csv_segment> h_seg;
+    std::vector<i64>         h_woff;
+    bool     uploaded = false, ran = false, any_genotype = false, any_pair = false, any_tra_gt = false, lds_set = false;
+    bool     reads_ready = false;              // the packed start-ordered reads table of this upload exists (a completed reads stage)
+    bool     reuse_reads = true;               // ... and resident re-runs keep it (csv_batch_option CSV_OPT_REUSE_READS_ORDER)
+    bool     have_tab = false;                 // this upload issued copies of the reads table frame (reads_off, contig_len, columns) on side[2]
+    bool     reads_general = false;            // this batch's reads table needs the general sort (found out by a first run)
+    i64      sqrt_n = 0;                       // entries of sqrt_tab (grown to the longest segment seen: an allele is never larger)
+    bool     copies_pending = false;           // csv_cluster_batch: the column copies are still in flight behind ev_copy[0] / [1]
+    // pipelined delivery (csv_batch_publish_async): runs alternate between two result arenas {call records, support list,
+    // counters}; the k_publish of run k reads arena k & 1 on its own stream while run k + 1 fills the other one
+    hipStream_t pub = nullptr;
+    hipEvent_t  ev_run[2] = {}, ev_pub[2] = {};
+    int         parity = 0;                    // arena of the last run
+    struct Pend { csv_batch_out* out = nullptr; bool live = false; } pend[2];
+    int         pend_order[2] = {0, 0}, n_pend = 0;      // arenas with a publish in flight, oldest first
+    bool        settled = false;               // a run of this upload has been downloaded synchronously (reads mode final, capacities known)
+    char*       h_pub = nullptr;               // page-locked landing zones of the asynchronous publishes: 2 x {counters 256 B, status words}
+    size_t      h_pub_cap = 0;
+    // block delivery: when the caller's result arrays sit back to back in page-locked memory (at most PUB_MAX_SPANS runs of
+    // adjacent arrays), k_publish writes them into a device image of those runs and the copy engine moves each run in one piece
+    void*       pub_stage[2] = {nullptr, nullptr};
+    size_t      pub_stage_cap[2] = {0, 0};
+    bool     lazy_pending = false;             // gate-first call: this upload's first run still has to fetch the gated rows from the caller's columns
+    bool     partial_cols = false;             // ... and its device columns hold only the rows the kernels read (csv_batch_validate refuses)
+    i64      lazy_bytes = 0;                   // bytes the bulk copy of this upload did NOT send (measurement aid: csv_batch_lazy_info)
+    i64      n_sig_host = 0, n_reads = 0;
+    DevBatch B;
+    DevCounters h_cnt;
+};
+
+namespace {
+
+int fail(csv_ctx* c, int code, const char* fmt, ...)
+{
+    char buf[512];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof buf, fmt, ap);
+    va_end(ap);
+    if (c) c->err = buf;
+    return code;
+}
+
+#define HIP_TRY(c, call)                                                                                   \
+    do {                                                                                                   \
+        hipError_t e_ = (call);                                                                            \
+        if (e_ != hipSuccess) return fail((c), CSV_E_HIP, "%s failed: %s", #call, hipGetErrorString(e_));   \
+    } while (0)
+
+// a helper's status passed on (the helpers below set the error text themselves)
+#define TRY(expr) do { const int rc_ = (expr); if (rc_) return rc_; } while (0)
+
+int reserve(csv_ctx* c, Buf& b, size_t bytes)            // stand-alone grow-only buffer
+{
+    if (bytes <= b.cap) return CSV_OK;
+    if (b.p) { HIP_TRY(c, hipFree(b.p)); b.p = nullptr; b.cap = 0; }
+    size_t want = bytes + bytes / 4 + 256;
+    hipError_t e = hipMalloc(&b.p, want);
+    if (e != hipSuccess) { b.p = nullptr; return fail(c, CSV_E_NOMEM, "hipMalloc(%zu) failed: %s", want, hipGetErrorString(e)); }
+    b.cap = want;
+    return CSV_OK;
+}
+
+// room for `bytes` in a stand-alone buffer whose first `keep` bytes must survive (grows by copying, by half)
+int grow_keep(csv_ctx* c, Buf& b, size_t bytes, size_t keep)
+{
+    if (bytes <= b.cap) return CSV_OK;
+    const size_t want = bytes + bytes / 2 + 4096;
+    void* p = nullptr;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    hipError_t e = hipMalloc(&p, want);
+    if (e != hipSuccess) return fail(c, CSV_E_NOMEM, "hipMalloc(%zu) for the name pool failed: %s", want, hipGetErrorString(e));
+    if (keep > 0 && b.p) HIP_TRY(c, hipMemcpy(p, b.p, keep, hipMemcpyDeviceToDevice));
+    if (b.p) HIP_TRY(c, hipFree(b.p));
+    b.p = p; b.cap = want;
+    return CSV_OK;
+}
+
+int commit(csv_ctx* c, Arena& A, const Plan& P)
+{
+    if (P.total > A.cap) {
+        if (A.base) { HIP_TRY(c, hipFree(A.base)); A.base = nullptr; A.cap = 0; }
+        const size_t want = P.total + P.total / 8 + 4096;
+        void* p = nullptr;
+        hipError_t e = hipMalloc(&p, want);
+        if (e != hipSuccess) return fail(c, CSV_E_NOMEM, "hipMalloc(%zu) for the batch arena failed: %s", want, hipGetErrorString(e));
+        A.base = (char*)p; A.cap = want;
+    }
+    for (const auto& it : P.items) it.first->p = A.base + it.second;
+    return CSV_OK;
+}
+
+// commit, waiting for the device first when the arena has to move: nothing may still be running out of the old one
+int commit_synced(csv_ctx* c, Arena& A, const Plan& P)
+{
+    if (P.total > A.cap) HIP_TRY(c, hipDeviceSynchronize());
+    return commit(c, A, P);
+}
+
+template <class T> T* dp(const Buf& b) { return (T*)b.p; }
+int div_up(i64 a, i64 b) { return (int)((a + b - 1) / b); }
+
+// a result column on its way to the caller: the rows of the copy tables of the stage entries
+struct HostCol { void* host; const Buf* dev; i64 bytes; };
+
+// host -> device on the context's stream; nothing to do for zero bytes
+int h2d(csv_ctx* c, const Buf& b, const void* src, i64 bytes)
+{
+    if (bytes > 0) HIP_TRY(c, hipMemcpyAsync(b.p, src, (size_t)bytes, hipMemcpyHostToDevice, c->stream));
+    return CSV_OK;
+}
+
+// device -> host on the context's stream.  A NULL `dst` is an output the caller did not ask for when `required` is false; when it is true the
+// copy goes to HIP as it is, which reports the NULL.  Zero bytes are skipped either way (the HIP runtime's copy returns hipSuccess for no bytes before it checks a pointer).
+int d2h(csv_ctx* c, void* dst, const Buf& b, i64 bytes, bool required)
+{
+    if (bytes > 0 && (dst || required)) HIP_TRY(c, hipMemcpyAsync(dst, b.p, (size_t)bytes, hipMemcpyDeviceToHost, c->stream));
+    return CSV_OK;
+}
+
+// The device time of an entry in two phases around a host decision (count kernels, totals back and capacity check, emit
+// kernels): events c->ev[0..3] on the context's stream; every *_end also collects launch errors.
+struct TwoPhaseTimer {
+    csv_ctx* c;
+    bool emitted = false;
+    int count_begin() { HIP_TRY(c, hipEventRecord(c->ev[0], c->stream)); return CSV_OK; }
+    int count_end() { HIP_TRY(c, hipEventRecord(c->ev[1], c->stream)); HIP_TRY(c, hipGetLastError()); return CSV_OK; }
+    int emit_begin() { HIP_TRY(c, hipEventRecord(c->ev[2], c->stream)); emitted = true; return CSV_OK; }
+    int emit_end() { HIP_TRY(c, hipEventRecord(c->ev[3], c->stream)); HIP_TRY(c, hipGetLastError()); return CSV_OK; }
+    int elapsed(float* ms)            // ms1 + ms2 once the stream is idle; ms1 alone while (or when) no emit phase ran
+    {
+        float ms1 = 0, ms2 = 0;
+        HIP_TRY(c, hipEventElapsedTime(&ms1, c->ev[0], c->ev[1]));
+        if (emitted) HIP_TRY(c, hipEventElapsedTime(&ms2, c->ev[2], c->ev[3]));
+        *ms = emitted ? ms1 + ms2 : ms1;
+        return CSV_OK;
+    }
+};
+
+// One key column of the LSD permutation sort (sort.hip.h): a pass per byte k < n_bytes whose bit is set in `mask`, over the bits first_shift + [8 k, 8 k + 8)
+struct SortField { const void* col; int elem64; int first_shift; int n_bytes; unsigned mask; };
+
+// The radix passes over `fields`, least significant field first: histogram, row sums, row scan, scatter; the permutation
+// goes back and forth between perm0 and perm1.  Returns the final permutation (nullptr: no pass ran, the order is the rows').
+const int* sort_passes(hipStream_t st, const SortField* fields, int n_fields, i64 n, int nunits, int* perm0, int* perm1, int* hist, int* tot, int* npass)
+{
+    const int nblk = div_up(nunits, 4);
+    const int* pin = nullptr;
+    int* pout = perm0;
+    for (int f = 0; f < n_fields; f++)
+        for (int byte = 0; byte < fields[f].n_bytes; byte++) {
+            if (!((fields[f].mask >> byte) & 1u)) continue;
+            SortPass SP{fields[f].col, fields[f].elem64, fields[f].first_shift + byte * 8, n, nunits, pin, pout, hist};
+            hipLaunchKernelGGL(k_sort_hist, dim3(nblk), dim3(256), 0, st, SP);
+            hipLaunchKernelGGL(k_sort_rowsum, dim3(256), dim3(256), 0, st, hist, nunits, tot);
+            hipLaunchKernelGGL(k_sort_rowscan, dim3(256), dim3(256), 0, st, hist, nunits, tot);
+            hipLaunchKernelGGL(k_sort_scatter, dim3(nblk), dim3(256), 0, st, SP);
+            pin = pout;
+            pout = (pout == perm0) ? perm1 : perm0;
+            if (npass) ++*npass;
+        }
+    return pin;
+}
+
+}  // namespace

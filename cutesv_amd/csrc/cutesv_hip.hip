@@ -1,5 +1,5 @@
-// cutesv_hip.hip — host side of libcutesv_hip.so: context, device arena, the C ABI of
-// include/cutesv_hip.h and the launch sequence of one batch.  gfx950 only.
+// cutesv_hip.hip — libcutesv_hip.so's one translation unit: context create / destroy and the cluster engine of include/cutesv_hip.h
+// (upload, run, validate, download, publish).  ctx.hip.h: the context and shared helpers; stage_*.hip.h (included last): the extraction stages.  gfx950 only.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdarg.h>
@@ -75,29 +75,6 @@ void* pinned_device_address(const void* p, size_t bytes)
     return at.devicePointer;
 }
 
-struct Buf {                      // a slice of an arena (or, for the few stand-alone buffers, its own allocation)
-    void*  p = nullptr;
-    size_t cap = 0;
-};
-
-// One device allocation for everything a batch needs: the buffers are planned (sizes -> offsets), the arena grows
-// only when the plan does not fit, and every Buf becomes a pointer into it.  (The first version reserved ~90 buffers
-// with one hipMalloc each: 2.7 ms on the first upload, and a larger batch re-allocated them one by one.)
-struct Arena {
-    char*  base = nullptr;
-    size_t cap = 0;
-};
-struct Plan {
-    std::vector<std::pair<Buf*, size_t>> items;
-    size_t total = 0;
-    void add(Buf& b, size_t bytes)
-    {
-        items.emplace_back(&b, total);
-        b.cap = bytes;
-        total += (bytes + 255) & ~(size_t)255;
-    }
-};
-
 // one timing slot per launch (group), in launch order
 const char* kStageName[CSV_N_STAGES] = {"init", "k_chain_count", "k_chain_apply", "k_refine_indel_wave", "k_refine_wave", "k_refine_mid",
                                         "k_refine_block", "k_items_scan", "k_emit", "k_reads_order", "k_reads_gather", "k_reads_maxlen",
@@ -110,162 +87,9 @@ constexpr int RO_CAP = 4096;                 // sorted runs the reads_order stag
 
 }  // namespace
 
-struct csv_ctx {
-    int         device = 0;
-    hipStream_t stream = nullptr;
-    hipStream_t side[3] = {};         // side streams: [0] mid + workgroup tier, [1] DUP/INV/TRA wavefront tier, [2] reads order + prefix max
-    hipStream_t copy[N_COPY_STREAMS] = {};    // host -> device column copies (one DMA engine each)
-    hipEvent_t  ev_init = nullptr, ev_sel = nullptr, ev_aux[3] = {}, ev_copy[N_COPY_STREAMS] = {}, ev_reads = nullptr, ev_anc = nullptr, ev_rd[5] = {};
-    std::string err;
-    hipEvent_t  ev[CSV_N_STAGES + 2] = {};
-    Arena       arena, arena_rb, arena_bam, arena_sa;
-    // batch buffers (slices of `arena`)
-    Buf seg, woff, seg_drop, a, b, rid, aux, a32, b32;
-    Buf tile_lead, tabs;
-    Buf ad16, anc;                             // CSV_IN_SIG_DELTA16: the gaps in w space; the anchor tables {per-tile offsets, w, value}
-    Buf rd16, ranc, rl16, rlesc;               // CSV_IN_READS_DELTA16: start gaps + their anchors, lengths + their escape rows / values
-    int  reads_delta = 0;                      // bit 0: the last upload's reads starts crossed as gaps, bit 1: its ends as lengths (csv_batch_info 3)
-    bool delta16 = false;                      // the last upload rebuilt its position column from gaps (csv_batch_info 2)
-    bool rstate_dirty = true;                  // the reads-order state may hold an earlier upload's verdict
-    bool reads_early = false;                  // the last upload decoded the reads table's start column on side[1] (upload_impl)
-    bool unpack_pending = false; UnpackArgs unpack_args{}; int unpack_tiles = 0;      // ... and k_unpack_a16 is still to be queued (one-shot calls: by the run)
-    Buf cluster_id, partial, tile_cnt, item_rec, list_small, list_big, list_tiny, list_wide, seg_gate, tile_info, ch_masks, tile_items, seg_err;
-    Buf item_cnt, item_base, item_chunk, sup_tmp;
-    Buf t_rec, t_rec0;
-    Buf sc_k, sc_x, sc_v1, sc_v2, sc_v3, sc_v4, sc_v5;
-    Buf o_rec, o_supsig, o_suprid, allele_id;
-    Buf o_rec2, o_supsig2;                     // the second result arena (runs alternate: a publish may still read the other one)
-    Buf reads_off, r_start, r_end, r_primary, r_id, s_start, s_end, s_idp, cmax, cfirst, bfirst, span_len, maxlen, gt_over, gt_huge, gt_pool, contig_len;
-    Buf ro_tcnt, ro_ent, ro_table, ro_tblk;
-    std::vector<int> h_tblk;                   // per tile of the reads table: the first chromosome block that begins at or after it
-    // stand-alone
-    Buf sqrt_tab, rcp_tab, cipk_tab, cnt, rstate;
-    Buf gs_chrom, gs_perm0, gs_perm1, gs_hist, gs_tot;          // general reads sort (fallback), allocated on first use
-    Buf flush;                                                   // csv_cache_flush scratch
-    // rebuild step (slices of `arena_rb`)
-    Buf rb_seg, rb_a, rb_b, rb_rid, rb_aux, rb_auxk, rb_major, rb_nodedup, rb_perm0, rb_perm1, rb_hist, rb_tot, rb_partial;
-    Buf rb_oseg, rb_oa, rb_ob, rb_orid, rb_oaux, rb_osrc, rb_segcnt, rb_rank, rb_mx, rb_drop, rb_el0, rb_el1;
-    // the device-resident signature pool (stand-alone allocations: it outlives the per-call arenas)
-    Buf pool_seg, pool_a, pool_b, pool_read, pool_aux, sp_qlen;
-    i64 pool_n = 0, pool_cap = 0;
-    // the device-resident name pool (names.hip.h; stand-alone allocations, grown by copying): nm_blob = the names back to back,
-    // nm_off = nm_n + 1 offsets into it; nm_len = the lengths once more on the host (csv_name_pool_get sizes its blob from them).
-    // nm_rank / nm_first hold the ranks of the first nm_n names while nm_fresh; the sort's scratch is slices of `arena_nm`.
-    Buf nm_blob, nm_off, nm_rank, nm_first, nm_get;
-    Arena arena_nm;
-    Buf nm_words, nm_perm0, nm_perm1, nm_hist, nm_tot, nm_vary, nm_flag, nm_partial;
-    std::vector<uint8_t> nm_len;
-    i64 nm_n = 0, nm_bytes = 0, nm_distinct = 0;
-    bool nm_fresh = false;
-    float nm_ms = 0; int nm_passes = 0, nm_maxlen = 0;
-    // CIGAR scan (slices of `arena_rb` as well: the two steps never overlap)
-    Buf sp_off, sp_len, sp_c0, sp_c1, sp_f0, sp_f1, sp_chr, sp_mapq, sp_strand, sp_primary, sp_seg, sp_cnt, sp_tiles, sp_tot,
-        sp_kind, sp_read, sp_ochr, sp_aux, sp_a, sp_b, sp_c, sp_d;
-    Buf cg_qlen, cg_off, cg_ops, cg_start, cg_use, cg_cnt, cg_tiles, cg_tot, cg_iread, cg_ipos, cg_ilen, cg_ip0, cg_inp, cg_pq, cg_pl, cg_dread, cg_dpos, cg_dlen;
-    // BAM decode (slices of `arena_bam`, which lives until the next decode: csv_cigar_signatures with CSV_CG_FROM_BAM scans
-    // bm_cigoff / bm_cigar / bm_start in place; the SA ranges are sized after the scan, so they stand alone)
-    Buf bm_slim, bm_recoff, bm_reclen, bm_start, bm_end, bm_flag, bm_mapq, bm_qlen, bm_cl, bm_cr, bm_cls, bm_status, bm_cigoff, bm_saoff, bm_cigsrc,
-        bm_cgb, bm_cge, bm_cigar, bm_long, bm_cnt, bm_tot, bm_sabeg, bm_saend;
-    i64 bam_n = -1, bam_nops = 0, bam_nsa = 0; // records / operations / SA tags of the last successful decode (-1: none)
-    // split inputs of the last decode (csv_bam_split_inputs; sa.hip.h): the tables sized before the kernels run are slices of
-    // `arena_sa`, the entry columns are sized by the count pass and stand alone.  They live until the next decode or the next
-    // csv_bam_split_inputs: csv_split_signatures with CSV_SP_FROM_BAM reads them in place.
-    Buf sa_sel, sa_names, sa_nameoff, sa_namerank, sa_calloff, sa_callrec, sa_callsa, sa_entoff, sa_readlen, sa_status, sa_tot;
-    Buf sa_c0, sa_c1, sa_f0, sa_f1, sa_chr, sa_mapq, sa_strand, sa_primary;
-    i64 sa_calls = -1, sa_entries = 0;         // calls / entries the context holds (-1: no split inputs)
-    // page-locked host staging: small tables on the way in, counters + call records + support lists on the way out
-    char*  h_pin = nullptr;
-    size_t h_pin_cap = 0;
-    // two page-locked 64-bit words the device writes {run sequence, count}: items above 64 signatures (k_chain_apply), calls that
-    // overflowed the first genotype pass (k_genotype<8192>); read when a LATER run of the same upload is planned
-    // CSV_* environment switches of the run path (timing / debugging aids), read once per upload: csv_batch_run - a 36 us
-    // step - looks nothing up in the environment
-    struct RunOpts {
-        bool debug = false, debug_counters = false, no_fork = false, fork_always = false, no_swap = false, no_peek = false;
-        bool no_pair_in_mid = false, no_publish = false;
-        int  iw_grid = 0, gt_grid = 0, tier_fork_min = 1 << 30, mid_grid = 0, big_grid = 0;
-        bool pub_inplace = false, no_reads_overlap = false;
-    } opt;
-    volatile int* h_flag = nullptr;
-    int*          d_flag = nullptr;
-    int           run_seq = 0;
-    int           upload_seq0 = 0;          // run_seq when the resident batch was uploaded: later sequence numbers are runs of it
-    int           n_cu = 256;              // compute units of the device
-    // host copies
-    std::vector<csv_segment> h_seg;
-    std::vector<i64>         h_woff;
-    bool     uploaded = false, ran = false, any_genotype = false, any_pair = false, any_tra_gt = false, lds_set = false;
-    bool     reads_ready = false;              // the packed start-ordered reads table of this upload exists (a completed reads stage)
-    bool     reuse_reads = true;               // ... and resident re-runs keep it (csv_batch_option CSV_OPT_REUSE_READS_ORDER)
-    bool     have_tab = false;                 // this upload issued copies of the reads table frame (reads_off, contig_len, columns) on side[2]
-    bool     reads_general = false;            // this batch's reads table needs the general sort (found out by a first run)
-    i64      sqrt_n = 0;                       // entries of sqrt_tab (grown to the longest segment seen: an allele is never larger)
-    bool     copies_pending = false;           // csv_cluster_batch: the column copies are still in flight behind ev_copy[0] / [1]
-    // pipelined delivery (csv_batch_publish_async): runs alternate between two result arenas {call records, support list,
-    // counters}; the k_publish of run k reads arena k & 1 on its own stream while run k + 1 fills the other one
-    hipStream_t pub = nullptr;
-    hipEvent_t  ev_run[2] = {}, ev_pub[2] = {};
-    int         parity = 0;                    // arena of the last run
-    struct Pend { csv_batch_out* out = nullptr; bool live = false; } pend[2];
-    int         pend_order[2] = {0, 0}, n_pend = 0;      // arenas with a publish in flight, oldest first
-    bool        settled = false;               // a run of this upload has been downloaded synchronously (reads mode final, capacities known)
-    char*       h_pub = nullptr;               // page-locked landing zones of the asynchronous publishes: 2 x {counters 256 B, status words}
-    size_t      h_pub_cap = 0;
-    // block delivery: when the caller's result arrays sit back to back in page-locked memory (at most PUB_MAX_SPANS runs of
-    // adjacent arrays), k_publish writes them into a device image of those runs and the copy engine moves each run in one piece
-    void*       pub_stage[2] = {nullptr, nullptr};
-    size_t      pub_stage_cap[2] = {0, 0};
-    bool     lazy_pending = false;             // gate-first call: this upload's first run still has to fetch the gated rows from the caller's columns
-    bool     partial_cols = false;             // ... and its device columns hold only the rows the kernels read (csv_batch_validate refuses)
-    i64      lazy_bytes = 0;                   // bytes the bulk copy of this upload did NOT send (measurement aid: csv_batch_lazy_info)
-    i64      n_sig_host = 0, n_reads = 0;
-    DevBatch B;
-    DevCounters h_cnt;
-};
+#include "ctx.hip.h"
 
 namespace {
-
-int fail(csv_ctx* c, int code, const char* fmt, ...)
-{
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    if (c) c->err = buf;
-    return code;
-}
-
-#define HIP_TRY(c, call)                                                                                   \
-    do {                                                                                                   \
-        hipError_t e_ = (call);                                                                            \
-        if (e_ != hipSuccess) return fail((c), CSV_E_HIP, "%s failed: %s", #call, hipGetErrorString(e_));   \
-    } while (0)
-
-int reserve(csv_ctx* c, Buf& b, size_t bytes)            // stand-alone grow-only buffer
-{
-    if (bytes <= b.cap) return CSV_OK;
-    if (b.p) { HIP_TRY(c, hipFree(b.p)); b.p = nullptr; b.cap = 0; }
-    size_t want = bytes + bytes / 4 + 256;
-    hipError_t e = hipMalloc(&b.p, want);
-    if (e != hipSuccess) { b.p = nullptr; return fail(c, CSV_E_NOMEM, "hipMalloc(%zu) failed: %s", want, hipGetErrorString(e)); }
-    b.cap = want;
-    return CSV_OK;
-}
-
-int commit(csv_ctx* c, Arena& A, const Plan& P)
-{
-    if (P.total > A.cap) {
-        if (A.base) { HIP_TRY(c, hipFree(A.base)); A.base = nullptr; A.cap = 0; }
-        const size_t want = P.total + P.total / 8 + 4096;
-        void* p = nullptr;
-        hipError_t e = hipMalloc(&p, want);
-        if (e != hipSuccess) return fail(c, CSV_E_NOMEM, "hipMalloc(%zu) for the batch arena failed: %s", want, hipGetErrorString(e));
-        A.base = (char*)p; A.cap = want;
-    }
-    for (const auto& it : P.items) it.first->p = A.base + it.second;
-    return CSV_OK;
-}
 
 int pin_reserve(csv_ctx* c, size_t bytes)
 {
@@ -278,10 +102,6 @@ int pin_reserve(csv_ctx* c, size_t bytes)
     c->h_pin = (char*)p; c->h_pin_cap = want;
     return CSV_OK;
 }
-
-template <class T> T* dp(const Buf& b) { return (T*)b.p; }
-
-int div_up(i64 a, i64 b) { return (int)((a + b - 1) / b); }
 
 int env_int(const char* name, int dflt)
 {
@@ -473,15 +293,10 @@ void csv_ctx_destroy(csv_ctx* c)
     if (!c) return;
     (void)hipSetDevice(c->device);
     (void)hipDeviceSynchronize();
-    Buf* own[] = {&c->pool_seg, &c->pool_a, &c->pool_b, &c->pool_read, &c->pool_aux, &c->sp_qlen, &c->sqrt_tab, &c->rcp_tab, &c->cipk_tab, &c->cnt, &c->rstate, &c->gs_chrom, &c->gs_perm0, &c->gs_perm1, &c->gs_hist, &c->gs_tot, &c->flush, &c->bm_sabeg, &c->bm_saend,
-                  &c->sa_c0, &c->sa_c1, &c->sa_f0, &c->sa_f1, &c->sa_chr, &c->sa_mapq, &c->sa_strand, &c->sa_primary,
-                  &c->nm_blob, &c->nm_off, &c->nm_rank, &c->nm_first, &c->nm_get};
+    std::vector<Buf*> own = {&c->sqrt_tab, &c->rcp_tab, &c->cipk_tab, &c->cnt, &c->rstate, &c->gs_chrom, &c->gs_perm0, &c->gs_perm1, &c->gs_hist, &c->gs_tot, &c->flush};
+    c->pool.own(own); c->sp.own(own); c->bm.own(own); c->sa.own(own); c->nm.own(own);
     for (Buf* b : own) if (b->p) (void)hipFree(b->p);
-    if (c->arena.base) (void)hipFree(c->arena.base);
-    if (c->arena_rb.base) (void)hipFree(c->arena_rb.base);
-    if (c->arena_bam.base) (void)hipFree(c->arena_bam.base);
-    if (c->arena_sa.base) (void)hipFree(c->arena_sa.base);
-    if (c->arena_nm.base) (void)hipFree(c->arena_nm.base);
+    for (Arena* a : {&c->arena, &c->scratch, &c->bm.arena, &c->sa.arena, &c->nm.arena}) if (a->base) (void)hipFree(a->base);
     if (c->h_pin) (void)hipHostFree(c->h_pin);
     if (c->h_flag) (void)hipHostFree((void*)c->h_flag);
     if (c->h_pub) (void)hipHostFree(c->h_pub);
@@ -713,12 +528,7 @@ int upload_impl(csv_ctx* c, const csv_batch_in* in, bool per_sig_forced, bool sy
         if (reorder) { PL(ro_tcnt, (div_up(R, RO_TILE) + 1) * 4); PL(ro_ent, (div_up(R, RO_TILE) + 1) * (size_t)RO_TCAP * 16); PL(ro_tblk, (div_up(R, RO_TILE) + 2) * 4); PL(ro_table, RO_CAP * 16); }
     }
 #undef PL
-    {
-        // the arena may move: nothing may still be running out of the old one
-        if (P.total > c->arena.cap) HIP_TRY(c, hipDeviceSynchronize());
-        const int rc = commit(c, c->arena, P);
-        if (rc) return rc;
-    }
+    TRY(commit_synced(c, c->arena, P));
 
     // ---- small tables: staged in page-locked memory, one copy
     {
@@ -1084,30 +894,18 @@ int upload_impl(csv_ctx* c, const csv_batch_in* in, bool per_sig_forced, bool sy
 int general_reads_sort(csv_ctx* c, hipStream_t st)
 {
     const i64 R = c->n_reads;
-    const int nunits = div_up(R, SORT_WTILE), nblk = div_up(nunits, 4);
+    const int nunits = div_up(R, SORT_WTILE);
     int rc;
     if ((rc = reserve(c, c->gs_chrom, R * 4)) || (rc = reserve(c, c->gs_perm0, R * 4)) || (rc = reserve(c, c->gs_perm1, R * 4)) ||
         (rc = reserve(c, c->gs_hist, (size_t)256 * nunits * 4)) || (rc = reserve(c, c->gs_tot, 256 * 4))) return rc;
     hipLaunchKernelGGL(k_reads_chromcol, dim3(div_up(R, 256)), dim3(256), 0, st, c->B, dp<int>(c->gs_chrom));
     int cbytes = 0;
     for (u64 v = (u64)(c->B.n_chrom > 0 ? c->B.n_chrom - 1 : 0); v; v >>= 8) cbytes++;
-    const int* pin = nullptr;
-    int* pout = dp<int>(c->gs_perm0);
-    for (int f = 0; f < 2; f++) {
-        const int nb = f == 0 ? 5 : cbytes;                // starts < 2^40 (checked with the ends by k_reads_gather)
-        for (int byte = 0; byte < nb; byte++) {
-            const bool rn = c->B.r_start.p32 != nullptr;
-            if (f == 0 && rn && byte >= 4) continue;         // (int32 starts have four key bytes)
-            SortPass P{f == 0 ? (rn ? (const void*)c->B.r_start.p32 : (const void*)c->B.r_start.p64) : (const void*)c->gs_chrom.p, (f == 0 && !rn) ? 1 : 0, byte * 8, R, nunits, pin, pout, dp<int>(c->gs_hist)};
-            hipLaunchKernelGGL(k_sort_hist, dim3(nblk), dim3(256), 0, st, P);
-            hipLaunchKernelGGL(k_sort_rowsum, dim3(256), dim3(256), 0, st, dp<int>(c->gs_hist), nunits, dp<int>(c->gs_tot));
-            hipLaunchKernelGGL(k_sort_rowscan, dim3(256), dim3(256), 0, st, dp<int>(c->gs_hist), nunits, dp<int>(c->gs_tot));
-            hipLaunchKernelGGL(k_sort_scatter, dim3(nblk), dim3(256), 0, st, P);
-            pin = pout;
-            pout = (pout == dp<int>(c->gs_perm0)) ? dp<int>(c->gs_perm1) : dp<int>(c->gs_perm0);
-        }
-    }
-    c->B.ro_perm = pin;
+    // starts < 2^40 (checked with the ends by k_reads_gather): five key bytes, of which int32 starts have four
+    const bool rn = c->B.r_start.p32 != nullptr;
+    const SortField fields[2] = {{rn ? (const void*)c->B.r_start.p32 : (const void*)c->B.r_start.p64, rn ? 0 : 1, 0, 5, rn ? 0x0fu : 0x1fu},
+                                 {c->gs_chrom.p, 0, 0, cbytes, ~0u}};
+    c->B.ro_perm = sort_passes(st, fields, 2, R, nunits, dp<int>(c->gs_perm0), dp<int>(c->gs_perm1), dp<int>(c->gs_hist), dp<int>(c->gs_tot), nullptr);
     HIP_TRY(c, hipGetLastError());
     return CSV_OK;
 }
@@ -1772,908 +1570,6 @@ int csv_batch_publish_wait(csv_ctx* c, csv_batch_out** done)
     return result_status(c, k, out, (out->flags & CSV_OUT_NO_SUPPORT_LIST) != 0);
 }
 
-// room for `extra` more rows in the pool (grows by copying: the pool is not in an arena)
-static int pool_reserve(csv_ctx* c, i64 extra)
-{
-    const i64 need = c->pool_n + extra;
-    if (need <= c->pool_cap) return CSV_OK;
-    if (need >= (1ll << 31) - 4096) return fail(c, CSV_E_INVALID, "signature pool too large (%lld rows)", (long long)need);
-    const i64 cap = need + need / 2 + 4096;
-    Buf* cols[5] = {&c->pool_seg, &c->pool_a, &c->pool_b, &c->pool_read, &c->pool_aux};
-    const size_t w[5] = {4, 8, 8, 4, 4};
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    for (int k = 0; k < 5; k++) {
-        void* p = nullptr;
-        hipError_t e = hipMalloc(&p, (size_t)cap * w[k]);
-        if (e != hipSuccess) return fail(c, CSV_E_NOMEM, "hipMalloc(%zu) for the signature pool failed: %s", (size_t)cap * w[k], hipGetErrorString(e));
-        if (c->pool_n > 0) HIP_TRY(c, hipMemcpy(p, cols[k]->p, (size_t)c->pool_n * w[k], hipMemcpyDeviceToDevice));
-        if (cols[k]->p) HIP_TRY(c, hipFree(cols[k]->p));
-        cols[k]->p = p; cols[k]->cap = (size_t)cap * w[k];
-    }
-    c->pool_cap = cap;
-    return CSV_OK;
-}
-
-int csv_pool_reset(csv_ctx* c)
-{
-    if (!c) return CSV_E_INVALID;
-    c->pool_n = 0;
-    return CSV_OK;
-}
-
-int csv_pool_rows(const csv_ctx* c, int64_t* n_rows)
-{
-    if (!c || !n_rows) return CSV_E_INVALID;
-    *n_rows = c->pool_n;
-    return CSV_OK;
-}
-
-int csv_pool_append(csv_ctx* c, int64_t n, const int32_t* seg_id, const int64_t* a, const int64_t* b, const int32_t* read, const int32_t* aux)
-{
-    if (!c || n < 0 || (n > 0 && (!seg_id || !a || !b || !read || !aux))) return CSV_E_INVALID;
-    if (n == 0) return CSV_OK;
-    HIP_TRY(c, hipSetDevice(c->device));
-    { const int rc = pool_reserve(c, n); if (rc) return rc; }
-    hipStream_t st = c->stream;
-    const i64 o = c->pool_n;
-    HIP_TRY(c, hipMemcpyAsync(dp<int>(c->pool_seg) + o, seg_id, (size_t)n * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(c, hipMemcpyAsync(dp<i64>(c->pool_a) + o, a, (size_t)n * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(c, hipMemcpyAsync(dp<i64>(c->pool_b) + o, b, (size_t)n * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(c, hipMemcpyAsync(dp<int>(c->pool_read) + o, read, (size_t)n * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(c, hipMemcpyAsync(dp<int>(c->pool_aux) + o, aux, (size_t)n * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(c, hipStreamSynchronize(st));                   // (the caller's arrays may be pageable and are free again on return)
-    c->pool_n += n;
-    return CSV_OK;
-}
-
-
-// ---------------------------------------------------------------------------------------- the name pool and its ranks (names.hip.h)
-// room for `bytes` in a stand-alone buffer whose first `keep` bytes must survive (grows by copying, by half)
-static int grow_keep(csv_ctx* c, Buf& b, size_t bytes, size_t keep)
-{
-    if (bytes <= b.cap) return CSV_OK;
-    const size_t want = bytes + bytes / 2 + 4096;
-    void* p = nullptr;
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    hipError_t e = hipMalloc(&p, want);
-    if (e != hipSuccess) return fail(c, CSV_E_NOMEM, "hipMalloc(%zu) for the name pool failed: %s", want, hipGetErrorString(e));
-    if (keep > 0 && b.p) HIP_TRY(c, hipMemcpy(p, b.p, keep, hipMemcpyDeviceToDevice));
-    if (b.p) HIP_TRY(c, hipFree(b.p));
-    b.p = p; b.cap = want;
-    return CSV_OK;
-}
-
-int csv_name_pool_reset(csv_ctx* c)
-{
-    if (!c) return CSV_E_INVALID;
-    c->nm_n = 0; c->nm_bytes = 0; c->nm_maxlen = 0; c->nm_len.clear();
-    c->nm_fresh = false;
-    return CSV_OK;
-}
-
-int csv_name_pool_rows(const csv_ctx* c, int64_t* n)
-{
-    if (!c || !n) return CSV_E_INVALID;
-    *n = c->nm_n;
-    return CSV_OK;
-}
-
-int csv_name_pool_append(csv_ctx* c, int64_t n, const uint8_t* bytes, int64_t n_bytes, const int64_t* off, const int32_t* len, int64_t* first_index)
-{
-    if (!c) return CSV_E_INVALID;
-    if (n < 0 || n_bytes < 0 || (n > 0 && (!off || !len)) || (n_bytes > 0 && !bytes)) return fail(c, CSV_E_INVALID, "bad name pool append");
-    // every range is checked before the pool changes or anything is launched
-    i64 total = 0; int mx = 0;
-    for (i64 i = 0; i < n; i++) {
-        if (len[i] < 0 || len[i] > NAME_MAX_LEN) return fail(c, CSV_E_INVALID, "name %lld: length %d is outside [0, %d]", (long long)i, len[i], NAME_MAX_LEN);
-        if (off[i] < 0 || off[i] > n_bytes || (i64)len[i] > n_bytes - off[i])
-            return fail(c, CSV_E_INVALID, "name %lld: bytes [%lld, %lld) leave the %lld bytes given", (long long)i, (long long)off[i], (long long)off[i] + len[i], (long long)n_bytes);
-        total += len[i];
-        mx = len[i] > mx ? len[i] : mx;
-    }
-    if (c->nm_n + n >= (1ll << 31) - 4096) return fail(c, CSV_E_INVALID, "name pool too large (%lld names)", (long long)(c->nm_n + n));
-    if (first_index) *first_index = c->nm_n;
-    if (n == 0) return CSV_OK;
-    HIP_TRY(c, hipSetDevice(c->device));
-    // the names back to back and their offsets in the pool's blob: what crosses the link (a chunk's host image also holds the bases)
-    std::vector<uint8_t> blob((size_t)total);
-    std::vector<i64> offs((size_t)n + 1);
-    i64 at = 0;
-    for (i64 i = 0; i < n; i++) {
-        offs[(size_t)i] = c->nm_bytes + at;
-        if (len[i]) memcpy(blob.data() + at, bytes + off[i], (size_t)len[i]);
-        at += len[i];
-    }
-    offs[(size_t)n] = c->nm_bytes + at;
-    { const int rc = grow_keep(c, c->nm_blob, (size_t)(c->nm_bytes + total) + 8, (size_t)c->nm_bytes); if (rc) return rc; }
-    { const int rc = grow_keep(c, c->nm_off, (size_t)(c->nm_n + n + 1) * 8, c->nm_n ? (size_t)(c->nm_n + 1) * 8 : 0); if (rc) return rc; }
-    hipStream_t st = c->stream;
-    if (total) HIP_TRY(c, hipMemcpyAsync((char*)c->nm_blob.p + c->nm_bytes, blob.data(), (size_t)total, hipMemcpyHostToDevice, st));
-    HIP_TRY(c, hipMemcpyAsync(dp<i64>(c->nm_off) + c->nm_n, offs.data(), (size_t)(n + 1) * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(c, hipStreamSynchronize(st));                   // (the vectors are the copies' sources)
-    c->nm_len.reserve((size_t)(c->nm_n + n));
-    for (i64 i = 0; i < n; i++) c->nm_len.push_back((uint8_t)len[i]);
-    c->nm_n += n; c->nm_bytes += total;
-    c->nm_maxlen = mx > c->nm_maxlen ? mx : c->nm_maxlen;
-    c->nm_fresh = false;
-    return CSV_OK;
-}
-
-// the ranks of the pool's names into nm_rank / nm_first (nothing to do while they are fresh)
-static int name_ranks_impl(csv_ctx* c)
-{
-    if (c->nm_fresh) return CSV_OK;
-    const i64 n = c->nm_n;
-    c->nm_ms = 0; c->nm_passes = 0; c->nm_distinct = 0;
-    if (n == 0) { c->nm_fresh = true; return CSV_OK; }
-    const int W = std::max(1, (c->nm_maxlen + 7) / 8);
-    const int nunits = div_up(n, SORT_WTILE), nblk = div_up(nunits, 4), ntile = div_up(n, NAME_TILE);
-    { const int rc = reserve(c, c->nm_rank, (size_t)n * 4); if (rc) return rc; }
-    { const int rc = reserve(c, c->nm_first, (size_t)n * 4); if (rc) return rc; }
-    Plan P;
-    P.add(c->nm_words, (size_t)W * n * 8); P.add(c->nm_perm0, (size_t)n * 4); P.add(c->nm_perm1, (size_t)n * 4);
-    P.add(c->nm_hist, (size_t)256 * nunits * 4); P.add(c->nm_tot, 256 * 4); P.add(c->nm_vary, (NAME_MAX_WORDS + 1) * 8);
-    P.add(c->nm_flag, (size_t)n); P.add(c->nm_partial, ((size_t)ntile + 2) * 4);
-    {
-        if (P.total > c->arena_nm.cap) HIP_TRY(c, hipDeviceSynchronize());
-        const int rc = commit(c, c->arena_nm, P);
-        if (rc) return rc;
-    }
-    hipStream_t st = c->stream;
-    u64* words = dp<u64>(c->nm_words);
-    HIP_TRY(c, hipMemsetAsync(c->nm_vary.p, 0, (NAME_MAX_WORDS + 1) * 8, st));
-    HIP_TRY(c, hipEventRecord(c->ev[0], st));
-    hipLaunchKernelGGL(k_name_pack, dim3(ntile, W), dim3(256), 0, st, dp<uint8_t>(c->nm_blob), dp<i64>(c->nm_off), n, words, dp<unsigned long long>(c->nm_vary));
-    // the byte positions at which any two names differ: one radix pass each, least significant (the last byte of the last word) first
-    unsigned long long vary[NAME_MAX_WORDS] = {};
-    HIP_TRY(c, hipMemcpyAsync(vary, c->nm_vary.p, (size_t)W * 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, hipStreamSynchronize(st));
-    const int* pin = nullptr;
-    int* pout = dp<int>(c->nm_perm0);
-    int npass = 0;
-    for (int w = W - 1; w >= 0; w--)
-        for (int shift = 0; shift < 64; shift += 8) {
-            if (((vary[w] >> shift) & 255ull) == 0) continue;
-            SortPass SP{words + (i64)w * n, 1, shift, n, nunits, pin, pout, dp<int>(c->nm_hist)};
-            hipLaunchKernelGGL(k_sort_hist, dim3(nblk), dim3(256), 0, st, SP);
-            hipLaunchKernelGGL(k_sort_rowsum, dim3(256), dim3(256), 0, st, dp<int>(c->nm_hist), nunits, dp<int>(c->nm_tot));
-            hipLaunchKernelGGL(k_sort_rowscan, dim3(256), dim3(256), 0, st, dp<int>(c->nm_hist), nunits, dp<int>(c->nm_tot));
-            hipLaunchKernelGGL(k_sort_scatter, dim3(nblk), dim3(256), 0, st, SP);
-            pin = pout;
-            pout = (pout == dp<int>(c->nm_perm0)) ? dp<int>(c->nm_perm1) : dp<int>(c->nm_perm0);
-            npass++;
-        }
-    int* d_n = (int*)((char*)c->nm_vary.p + NAME_MAX_WORDS * 8);
-    NameRank R{n, W, words, pin, dp<uint8_t>(c->nm_flag), dp<int>(c->nm_partial), dp<int>(c->nm_rank), dp<int>(c->nm_first), d_n};
-    hipLaunchKernelGGL(k_name_count, dim3(ntile), dim3(256), 0, st, R);
-    hipLaunchKernelGGL(k_name_apply, dim3(ntile), dim3(256), 0, st, R);
-    HIP_TRY(c, hipEventRecord(c->ev[1], st));
-    HIP_TRY(c, hipGetLastError());
-    int nd = 0;
-    HIP_TRY(c, hipMemcpyAsync(&nd, d_n, 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, hipStreamSynchronize(st));
-    HIP_TRY(c, hipEventElapsedTime(&c->nm_ms, c->ev[0], c->ev[1]));
-    c->nm_distinct = nd; c->nm_passes = npass;
-    c->nm_fresh = true;
-    return CSV_OK;
-}
-
-int csv_name_ranks(csv_ctx* c, csv_name_rank_out* out)
-{
-    if (!c || !out) return CSV_E_INVALID;
-    HIP_TRY(c, hipSetDevice(c->device));
-    { const int rc = name_ranks_impl(c); if (rc) return rc; }
-    out->n = c->nm_n; out->n_distinct = c->nm_distinct; out->ms_device = c->nm_ms; out->n_passes = c->nm_passes; out->max_len = c->nm_maxlen;
-    out->dev_rank = c->nm_n ? c->nm_rank.p : nullptr;
-    if (out->first && out->cap_first < c->nm_distinct) return fail(c, CSV_E_CAPACITY, "first: %lld entries are needed", (long long)c->nm_distinct);
-    hipStream_t st = c->stream;
-    if (out->rank && c->nm_n) HIP_TRY(c, hipMemcpyAsync(out->rank, c->nm_rank.p, (size_t)c->nm_n * 4, hipMemcpyDeviceToHost, st));
-    if (out->first && c->nm_distinct) HIP_TRY(c, hipMemcpyAsync(out->first, c->nm_first.p, (size_t)c->nm_distinct * 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, hipStreamSynchronize(st));
-    return CSV_OK;
-}
-
-int csv_name_pool_get(csv_ctx* c, int64_t n, const int32_t* index, char* out, int64_t cap, int64_t* out_off)
-{
-    if (!c) return CSV_E_INVALID;
-    if (n < 0 || cap < 0 || !out_off || (n > 0 && !index) || (cap > 0 && !out)) return fail(c, CSV_E_INVALID, "bad name pool get");
-    out_off[0] = 0;
-    for (i64 k = 0; k < n; k++) {
-        if (index[k] < 0 || index[k] >= c->nm_n) return fail(c, CSV_E_INVALID, "index[%lld] = %d is outside the %lld names of the pool", (long long)k, index[k], (long long)c->nm_n);
-        out_off[k + 1] = out_off[k] + c->nm_len[(size_t)index[k]];
-    }
-    const i64 total = out_off[n];
-    if (total > cap) return fail(c, CSV_E_CAPACITY, "out: %lld bytes are needed", (long long)total);
-    if (n == 0 || total == 0) return CSV_OK;
-    HIP_TRY(c, hipSetDevice(c->device));
-    // one buffer: the gathered bytes, then (8-byte aligned) the offsets and the indices
-    const size_t o_off = ((size_t)total + 7) & ~(size_t)7, o_idx = o_off + (size_t)(n + 1) * 8;
-    { const int rc = grow_keep(c, c->nm_get, o_idx + (size_t)n * 4, 0); if (rc) return rc; }
-    hipStream_t st = c->stream;
-    char* g = (char*)c->nm_get.p;
-    HIP_TRY(c, hipMemcpyAsync(g + o_off, out_off, (size_t)(n + 1) * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(c, hipMemcpyAsync(g + o_idx, index, (size_t)n * 4, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_name_gather, dim3(div_up(n, 4)), dim3(256), 0, st, dp<uint8_t>(c->nm_blob), dp<i64>(c->nm_off), (const int*)(g + o_idx), (const i64*)(g + o_off), n, (uint8_t*)g);
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipMemcpyAsync(out, g, (size_t)total, hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, hipStreamSynchronize(st));
-    return CSV_OK;
-}
-
-size_t csv_name_struct_size(int which) { return which == 0 ? sizeof(csv_name_rank_out) : 0; }
-
-int csv_rebuild_signatures(csv_ctx* c, const csv_rebuild_in* in, csv_rebuild_out* out)
-{
-    if (!c || !in || !out) return CSV_E_INVALID;
-    HIP_TRY(c, hipSetDevice(c->device));
-    const bool from_pool = (in->flags & CSV_RB_FROM_POOL) != 0;
-    const i64 n = from_pool ? c->pool_n : in->n;
-    out->n_out = 0; out->ms_device = 0; out->n_passes = 0;
-    if (n < 0 || n >= (1ll << 31) - 4096 || in->n_seg <= 0) return fail(c, CSV_E_INVALID, "bad rebuild input");
-    // CSV_RB_RANK_FROM_NAMES: the ranks are the name pool's, in device memory already (computed now if an append made them stale)
-    const bool by_name = from_pool && (in->flags & CSV_RB_RANK_FROM_NAMES) != 0;
-    if ((in->flags & CSV_RB_RANK_FROM_NAMES) && !from_pool) return fail(c, CSV_E_INVALID, "CSV_RB_RANK_FROM_NAMES needs CSV_RB_FROM_POOL");
-    if (from_pool && ((!by_name && (!in->read_rank || in->n_rank <= 0)) || !in->seg_aux_major)) return fail(c, CSV_E_INVALID, "CSV_RB_FROM_POOL needs read_rank");
-    if (n == 0) return CSV_OK;
-    if (by_name) {
-        if (c->nm_n == 0) return fail(c, CSV_E_INVALID, "CSV_RB_RANK_FROM_NAMES: the name pool is empty");
-        const int rc = name_ranks_impl(c);
-        if (rc) return rc;
-    }
-    const int* d_rank = by_name ? dp<int>(c->nm_rank) : nullptr;
-    const i64 n_rank = by_name ? c->nm_n : in->n_rank;
-    // key widths (bits that are non-zero somewhere) and the validity of every row: found on the device, behind the upload (r04
-    // walked the columns on the host first: ~3 ms for a 30x genome's 2.85 M rows, in front of a 0.5 ms sort)
-    i64 mx_a = 0, mx_b = 0; int mx_rid = 0, mx_aux = 0, mx_seg = 0, mx_aux_all = 0;
-    auto nbytes = [](u64 v) { int k = 0; while (v) { k++; v >>= 8; } return k; };
-    auto nbits = [](u64 v) { int k = 0; while (v) { k++; v >>= 1; } return k; };
-    const int nunits = div_up(n, SORT_WTILE), nblk = div_up(nunits, 4), ntile = div_up(n, 2048);
-    Plan P;
-#define PL(buf, bytes) P.add(c->buf, (size_t)(bytes))
-    PL(rb_seg, n * 4); PL(rb_a, n * 8); PL(rb_b, n * 8); PL(rb_rid, n * 4); PL(rb_aux, n * 4); PL(rb_auxk, n * 4);
-    PL(rb_major, in->n_seg); PL(rb_nodedup, in->n_seg); PL(rb_perm0, n * 4); PL(rb_perm1, n * 4); PL(rb_hist, (size_t)RS_RADIX * nunits * 4);
-    PL(rb_tot, RS_RADIX * 4); PL(rb_partial, (ntile + 2) * 4);
-    PL(rb_el0, (size_t)n * 32); PL(rb_el1, (size_t)n * 32);          // composite-key elements (16 or 32 bytes each; sized for either)
-    PL(rb_oseg, n * 4); PL(rb_oa, n * 8); PL(rb_ob, n * 8); PL(rb_orid, n * 4); PL(rb_oaux, n * 4); PL(rb_osrc, n * 4); PL(rb_segcnt, ((size_t)in->n_seg + 2) * 8);
-    if (from_pool && !by_name) PL(rb_rank, (size_t)in->n_rank * 4);
-    PL(rb_mx, 64);
-    if (in->tie_order && in->seg_nodedup) PL(rb_drop, n + 64);
-#undef PL
-    {
-        if (P.total > c->arena_rb.cap) HIP_TRY(c, hipDeviceSynchronize());
-        const int rc = commit(c, c->arena_rb, P);
-        if (rc) return rc;
-    }
-    hipStream_t st = c->stream;
-    HIP_TRY(c, hipMemcpyAsync(c->rb_major.p, in->seg_aux_major, in->n_seg, hipMemcpyHostToDevice, st));
-    if (in->seg_nodedup) HIP_TRY(c, hipMemcpyAsync(c->rb_nodedup.p, in->seg_nodedup, in->n_seg, hipMemcpyHostToDevice, st));
-    if (!from_pool) {
-        HIP_TRY(c, hipMemcpyAsync(c->rb_seg.p, in->seg_id, n * 4, hipMemcpyHostToDevice, st));
-        HIP_TRY(c, hipMemcpyAsync(c->rb_a.p, in->a, n * 8, hipMemcpyHostToDevice, st));
-        HIP_TRY(c, hipMemcpyAsync(c->rb_b.p, in->b, n * 8, hipMemcpyHostToDevice, st));
-        HIP_TRY(c, hipMemcpyAsync(c->rb_rid.p, in->read_id, n * 4, hipMemcpyHostToDevice, st));
-        HIP_TRY(c, hipMemcpyAsync(c->rb_aux.p, in->aux, n * 4, hipMemcpyHostToDevice, st));
-    }
-    {
-        // the rows -> the input columns (pool rows: read index -> name rank; host rows: in place), the key widths from the device
-        if (from_pool && !by_name) {
-            HIP_TRY(c, hipMemcpyAsync(c->rb_rank.p, in->read_rank, (size_t)in->n_rank * 4, hipMemcpyHostToDevice, st));
-            d_rank = dp<int>(c->rb_rank);
-        }
-        HIP_TRY(c, hipMemsetAsync(c->rb_mx.p, 0, 64, st));
-        if (from_pool)
-            hipLaunchKernelGGL(k_pool_to_rows, dim3(div_up(n, 2048)), dim3(256), 0, st, dp<int>(c->pool_seg), dp<i64>(c->pool_a), dp<i64>(c->pool_b),
-                               dp<int>(c->pool_read), dp<int>(c->pool_aux), n, d_rank, n_rank, in->n_seg, dp<uint8_t>(c->rb_major),
-                               dp<int>(c->rb_seg), dp<i64>(c->rb_a), dp<i64>(c->rb_b), dp<int>(c->rb_rid), dp<int>(c->rb_aux), dp<unsigned long long>(c->rb_mx));
-        else
-            hipLaunchKernelGGL(k_pool_to_rows, dim3(div_up(n, 2048)), dim3(256), 0, st, dp<int>(c->rb_seg), dp<i64>(c->rb_a), dp<i64>(c->rb_b),
-                               dp<int>(c->rb_rid), dp<int>(c->rb_aux), n, (const int*)nullptr, (i64)0, in->n_seg, dp<uint8_t>(c->rb_major),
-                               dp<int>(c->rb_seg), dp<i64>(c->rb_a), dp<i64>(c->rb_b), dp<int>(c->rb_rid), dp<int>(c->rb_aux), dp<unsigned long long>(c->rb_mx));
-        unsigned long long mx[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        HIP_TRY(c, hipMemcpyAsync(mx, c->rb_mx.p, 56, hipMemcpyDeviceToHost, st));
-        HIP_TRY(c, hipStreamSynchronize(st));
-        if (mx[5]) return fail(c, CSV_E_INVALID, from_pool ? "a pool row has a negative key, a segment out of range or a read without a rank"
-                                                          : "a row has a negative key or a segment out of range");
-        mx_a = (i64)mx[0]; mx_b = (i64)mx[1]; mx_rid = (int)mx[2]; mx_aux = (int)mx[3]; mx_seg = (int)mx[4]; mx_aux_all = (int)mx[6];
-    }
-    HIP_TRY(c, hipEventRecord(c->ev[0], st));
-    // the composite-key sort (sort.hip.h) whenever the key fits 128 bits; CSV_RB_PERM_SORT=1 forces the permutation sort
-    KeyLayout KL{};
-    KL.ib = nbits((u64)(n - 1)) > 0 ? nbits((u64)(n - 1)) : 1;
-    KL.rb = nbits((u64)mx_rid) > 0 ? nbits((u64)mx_rid) : 1; KL.bb = nbits((u64)mx_b) > 0 ? nbits((u64)mx_b) : 1;
-    KL.ab = nbits((u64)mx_a) > 0 ? nbits((u64)mx_a) : 1; KL.xb = nbits((u64)mx_aux); KL.sb = nbits((u64)mx_seg) > 0 ? nbits((u64)mx_seg) : 1;
-    KL.pb = nbits((u64)mx_aux_all);
-    KL.T = KL.rb + KL.bb + KL.ab + KL.xb + KL.sb;
-    // (the compact element holds aux | key | index in 128 bits; with no aux bits and ib + T == 128 its shifts would be by 128: wide then)
-    KL.wide = (KL.ib + KL.T + KL.pb <= 128 && KL.ib + KL.T < 128) ? 0 : 1;
-    const bool composite = KL.T <= 128 && !getenv("CSV_RB_PERM_SORT");
-    RebuildArgs R{};
-    R.n = n;
-    R.seg = dp<int>(c->rb_seg); R.a = dp<i64>(c->rb_a); R.b = dp<i64>(c->rb_b); R.rid = dp<int>(c->rb_rid); R.aux = dp<int>(c->rb_aux);
-    R.auxk = dp<int>(c->rb_auxk); R.keep = nullptr; R.partial = dp<int>(c->rb_partial);
-    R.nodedup = in->seg_nodedup ? dp<uint8_t>(c->rb_nodedup) : nullptr;
-    R.o_seg = dp<int>(c->rb_oseg); R.o_a = dp<i64>(c->rb_oa); R.o_b = dp<i64>(c->rb_ob); R.o_rid = dp<int>(c->rb_orid);
-    R.o_aux = dp<int>(c->rb_oaux); R.o_src = dp<int>(c->rb_osrc); R.n_out = (int*)((char*)c->cnt.p + 768);      // (a word of its own: the run arenas at +0 / +256 may have a publish in flight)
-    R.drop = nullptr;
-    out->n_tie_rows = 0; out->n_tie_dropped = 0;
-    bool ties_settled = false;
-    int npass = 0;
-    // the tie groups' round trip to the caller (csv_tie_order_fn): `lst` = {position | continues << 31, source row}, any order
-    std::vector<int> tie_pos, tie_src; std::vector<uint8_t> tie_flag;
-    auto ask_caller = [&](std::vector<int2>& lst) -> int {
-        const int n_list = (int)lst.size();
-        std::sort(lst.begin(), lst.end(), [](const int2& x, const int2& y) { return (x.x & 0x7fffffff) < (y.x & 0x7fffffff); });
-        std::vector<int64_t> goff;
-        std::vector<int> src((size_t)n_list), order((size_t)n_list, -1);
-        std::vector<uint8_t> drop((size_t)n_list, 0);
-        tie_pos.assign((size_t)n_list, 0); tie_src.assign((size_t)n_list, 0); tie_flag.assign((size_t)n_list, 0);
-        for (int k = 0; k < n_list; k++) {
-            if (!(lst[k].x & (int)0x80000000)) goff.push_back(k);               // a group's head
-            tie_pos[k] = lst[k].x & 0x7fffffff; src[k] = lst[k].y;
-        }
-        goff.push_back(n_list);
-        const int rc = in->tie_order(in->tie_user, (int64_t)goff.size() - 1, goff.data(), src.data(), order.data(), drop.data());
-        if (rc != 0) return fail(c, CSV_E_INVALID, "tie_order returned %d", rc);
-        std::vector<uint8_t> seen((size_t)n_list, 0);
-        int64_t dropped = 0;
-        for (size_t g = 0; g + 1 < goff.size(); g++) {                            // order[] must be a permutation inside every group
-            const int64_t g0 = goff[g], g1 = goff[g + 1];
-            for (int64_t k = g0; k < g1; k++) {
-                const int64_t o = order[k];
-                if (o < 0 || o >= g1 - g0 || seen[g0 + o]) return fail(c, CSV_E_INVALID, "tie_order: order[] is not a permutation inside group %zu", g);
-                seen[g0 + o] = 1;
-                tie_src[g0 + o] = src[k]; tie_flag[g0 + o] = drop[k] ? 1 : 0;
-                dropped += drop[k] ? 1 : 0;
-            }
-        }
-        out->n_tie_rows = n_list; out->n_tie_dropped = dropped;
-        return CSV_OK;
-    };
-    if (composite) {
-        RsCols C{dp<int>(c->rb_seg), dp<i64>(c->rb_a), dp<i64>(c->rb_b), dp<int>(c->rb_rid), dp<int>(c->rb_aux), dp<uint8_t>(c->rb_major)};
-        void* e_in = c->rb_el0.p; void* e_out = c->rb_el1.p;
-        auto run_sort = [&](auto wide_tag) -> int {
-            constexpr bool W = decltype(wide_tag)::value;
-            typedef RsElem<W> E;
-            hipLaunchKernelGGL(k_rs_pack<W>, dim3(div_up(n, 256)), dim3(256), 0, st, C, n, KL, (E*)e_in);
-            for (int shift = 0; shift < KL.T; shift += RS_BITS) {
-                const int dbits = KL.T - shift < RS_BITS ? KL.T - shift : RS_BITS;
-                hipLaunchKernelGGL(k_rs_hist<W>, dim3(nblk), dim3(256), 0, st, (const E*)e_in, n, nunits, KL, shift, dbits, dp<int>(c->rb_hist));
-                hipLaunchKernelGGL(k_sort_rowsum, dim3(RS_RADIX), dim3(256), 0, st, dp<int>(c->rb_hist), nunits, dp<int>(c->rb_tot));
-                hipLaunchKernelGGL(k_sort_rowscan, dim3(RS_RADIX), dim3(256), 0, st, dp<int>(c->rb_hist), nunits, dp<int>(c->rb_tot));
-                hipLaunchKernelGGL(k_rs_scatter<W>, dim3(nblk), dim3(256), 0, st, (const E*)e_in, (E*)e_out, n, nunits, KL, shift, dbits, dp<int>(c->rb_hist));
-                std::swap(e_in, e_out);
-                npass++;
-            }
-            RsTail T{};
-            T.n = n; T.L = KL; T.nodedup = R.nodedup; T.drop = nullptr; T.partial = R.partial;
-            T.o_seg = R.o_seg; T.o_a = R.o_a; T.o_b = R.o_b; T.o_rid = R.o_rid; T.o_aux = R.o_aux; T.o_src = R.o_src; T.n_out = R.n_out;
-            if (in->tie_order && R.nodedup) {
-                int* d_n = (int*)((char*)c->cnt.p + 768);
-                HIP_TRY(c, hipMemsetAsync(d_n, 0, 4, st));
-                HIP_TRY(c, hipMemsetAsync(c->rb_drop.p, 0, (size_t)n, st));
-                hipLaunchKernelGGL(k_rs_ties<W>, dim3(div_up(n, 256)), dim3(256), 0, st, T, (const E*)e_in, (int2*)c->rb_oa.p, d_n);
-                int n_list = 0;
-                HIP_TRY(c, hipMemcpyAsync(&n_list, d_n, 4, hipMemcpyDeviceToHost, st));
-                HIP_TRY(c, hipStreamSynchronize(st));
-                if (n_list > 0) {
-                    std::vector<int2> lst((size_t)n_list);
-                    HIP_TRY(c, hipMemcpy(lst.data(), c->rb_oa.p, (size_t)n_list * 8, hipMemcpyDeviceToHost));
-                    const int rc = ask_caller(lst);
-                    if (rc) return rc;
-                    HIP_TRY(c, hipMemcpyAsync(c->rb_oseg.p, tie_pos.data(), (size_t)n_list * 4, hipMemcpyHostToDevice, st));
-                    HIP_TRY(c, hipMemcpyAsync(c->rb_orid.p, tie_src.data(), (size_t)n_list * 4, hipMemcpyHostToDevice, st));
-                    HIP_TRY(c, hipMemcpyAsync(c->rb_ob.p, tie_flag.data(), (size_t)n_list, hipMemcpyHostToDevice, st));
-                    hipLaunchKernelGGL(k_rs_tie_apply<W>, dim3(div_up(n_list, 256)), dim3(256), 0, st, n_list, dp<int>(c->rb_oseg), dp<int>(c->rb_orid),
-                                       dp<uint8_t>(c->rb_ob), dp<int>(c->rb_aux), KL, (E*)e_in, dp<uint8_t>(c->rb_drop));
-                    HIP_TRY(c, hipStreamSynchronize(st));                                   // (the host vectors are the copies' sources)
-                }
-                T.drop = dp<uint8_t>(c->rb_drop);
-                ties_settled = true;
-            }
-            hipLaunchKernelGGL(k_rs_count<W>, dim3(ntile), dim3(256), 0, st, T, (const E*)e_in);
-            hipLaunchKernelGGL(k_rs_apply<W>, dim3(ntile), dim3(256), 0, st, T, (const E*)e_in);
-            return CSV_OK;
-        };
-        const int rc = KL.wide ? run_sort(std::true_type{}) : run_sort(std::false_type{});
-        if (rc) return rc;
-    } else {
-        hipLaunchKernelGGL(k_rebuild_auxkey, dim3(div_up(n, 256)), dim3(256), 0, st, n, dp<int>(c->rb_seg), dp<int>(c->rb_aux),
-                           dp<uint8_t>(c->rb_major), dp<int>(c->rb_auxk));
-        // least significant key first: read_id, b, a, [aux], segment
-        struct Field { const void* col; int elem64; int bytes; };
-        const Field fields[5] = {{c->rb_rid.p, 0, nbytes((u64)mx_rid)}, {c->rb_b.p, 1, nbytes((u64)mx_b)}, {c->rb_a.p, 1, nbytes((u64)mx_a)},
-                                 {c->rb_auxk.p, 0, nbytes((u64)mx_aux)}, {c->rb_seg.p, 0, nbytes((u64)mx_seg) > 0 ? nbytes((u64)mx_seg) : 1}};
-        const int* pin = nullptr;
-        int* pout = dp<int>(c->rb_perm0);
-        for (const Field& f : fields)
-            for (int byte = 0; byte < f.bytes; byte++) {
-                SortPass SP{f.col, f.elem64, byte * 8, n, nunits, pin, pout, dp<int>(c->rb_hist)};
-                hipLaunchKernelGGL(k_sort_hist, dim3(nblk), dim3(256), 0, st, SP);
-                hipLaunchKernelGGL(k_sort_rowsum, dim3(256), dim3(256), 0, st, dp<int>(c->rb_hist), nunits, dp<int>(c->rb_tot));
-                hipLaunchKernelGGL(k_sort_rowscan, dim3(256), dim3(256), 0, st, dp<int>(c->rb_hist), nunits, dp<int>(c->rb_tot));
-                hipLaunchKernelGGL(k_sort_scatter, dim3(nblk), dim3(256), 0, st, SP);
-                pin = pout;
-                pout = (pout == dp<int>(c->rb_perm0)) ? dp<int>(c->rb_perm1) : dp<int>(c->rb_perm0);
-                npass++;
-            }
-        R.perm = pin;
-        if (in->tie_order && R.nodedup) {
-            // INS rows that tie on their integer keys: the caller orders them (by sequence) and names the duplicates; the answer is
-            // written into the permutation / a drop map on the device, and the gather below never knows.  The output buffers are
-            // free until the gather: rb_oa holds the list, rb_oseg / rb_orid / rb_ob the answer on its way back.
-            int* d_n = (int*)((char*)c->cnt.p + 768);
-            HIP_TRY(c, hipMemsetAsync(d_n, 0, 4, st));
-            HIP_TRY(c, hipMemsetAsync(c->rb_drop.p, 0, (size_t)n, st));
-            hipLaunchKernelGGL(k_rebuild_ties, dim3(div_up(n, 256)), dim3(256), 0, st, R, (int2*)c->rb_oa.p, d_n);
-            int n_list = 0;
-            HIP_TRY(c, hipMemcpyAsync(&n_list, d_n, 4, hipMemcpyDeviceToHost, st));
-            HIP_TRY(c, hipStreamSynchronize(st));
-            if (n_list > 0) {
-                std::vector<int2> lst((size_t)n_list);
-                HIP_TRY(c, hipMemcpy(lst.data(), c->rb_oa.p, (size_t)n_list * 8, hipMemcpyDeviceToHost));
-                const int rc = ask_caller(lst);
-                if (rc) return rc;
-                HIP_TRY(c, hipMemcpyAsync(c->rb_oseg.p, tie_pos.data(), (size_t)n_list * 4, hipMemcpyHostToDevice, st));
-                HIP_TRY(c, hipMemcpyAsync(c->rb_orid.p, tie_src.data(), (size_t)n_list * 4, hipMemcpyHostToDevice, st));
-                HIP_TRY(c, hipMemcpyAsync(c->rb_ob.p, tie_flag.data(), (size_t)n_list, hipMemcpyHostToDevice, st));
-                hipLaunchKernelGGL(k_rebuild_tie_apply, dim3(div_up(n_list, 256)), dim3(256), 0, st, n_list, dp<int>(c->rb_oseg), dp<int>(c->rb_orid),
-                                   dp<uint8_t>(c->rb_ob), const_cast<int*>(R.perm), dp<uint8_t>(c->rb_drop));
-                HIP_TRY(c, hipStreamSynchronize(st));                                       // (the host vectors are the copies' sources)
-            }
-            R.drop = dp<uint8_t>(c->rb_drop);
-            ties_settled = true;
-        }
-        hipLaunchKernelGGL(k_rebuild_count, dim3(ntile), dim3(256), 0, st, R);
-        hipLaunchKernelGGL(k_rebuild_apply, dim3(ntile), dim3(256), 0, st, R);
-    }
-    // rows per segment and the INS tie count ([n_seg] = ties), from the sorted output
-    HIP_TRY(c, hipMemsetAsync(dp<i64>(c->rb_segcnt) + in->n_seg, 0, 8, st));
-    // (the tie count is a grid-stride loop over the sorted rows: enough workgroups for ~4 rows per thread)
-    const int g_sc = std::max(div_up(in->n_seg, 256), std::min(div_up(n, 1024), 8192));
-    if (ties_settled) R.nodedup = nullptr;                  // (nothing left to count)
-    hipLaunchKernelGGL(k_rebuild_segcount, dim3(g_sc), dim3(256), 0, st, R, in->n_seg,
-                       dp<i64>(c->rb_segcnt), dp<i64>(c->rb_segcnt) + in->n_seg);
-    HIP_TRY(c, hipEventRecord(c->ev[1], st));
-    HIP_TRY(c, hipGetLastError());
-    int n_out = 0;
-    std::vector<i64> segcnt((size_t)in->n_seg + 1);
-    HIP_TRY(c, hipMemcpyAsync(&n_out, (char*)c->cnt.p + 768, 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, hipMemcpyAsync(segcnt.data(), c->rb_segcnt.p, ((size_t)in->n_seg + 1) * 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, hipStreamSynchronize(st));
-    HIP_TRY(c, hipEventElapsedTime(&out->ms_device, c->ev[0], c->ev[1]));
-    out->n_out = n_out; out->n_passes = npass;
-    out->n_ins_ties = ties_settled ? 0 : segcnt[(size_t)in->n_seg];
-    if (out->seg_count) memcpy(out->seg_count, segcnt.data(), (size_t)in->n_seg * 8);
-    const bool keep_dev = (in->flags & CSV_RB_KEEP_ON_DEVICE) != 0;
-    out->dev_seg_id = out->dev_a = out->dev_b = out->dev_read_id = out->dev_aux = out->dev_src_row = nullptr;
-    if (keep_dev) {
-        out->dev_seg_id = c->rb_oseg.p; out->dev_a = c->rb_oa.p; out->dev_b = c->rb_ob.p; out->dev_read_id = c->rb_orid.p;
-        out->dev_aux = c->rb_oaux.p; out->dev_src_row = c->rb_osrc.p;
-    }
-    // (with CSV_RB_KEEP_ON_DEVICE a NULL host array is simply not filled; without the flag all six are required, as before)
-#define RB_D2H(dst, buf, bytes) do { if ((dst) || !keep_dev) HIP_TRY(c, hipMemcpyAsync((dst), c->buf.p, (bytes), hipMemcpyDeviceToHost, st)); } while (0)
-    RB_D2H(out->seg_id, rb_oseg, (size_t)n_out * 4); RB_D2H(out->a, rb_oa, (size_t)n_out * 8); RB_D2H(out->b, rb_ob, (size_t)n_out * 8);
-    RB_D2H(out->read_id, rb_orid, (size_t)n_out * 4); RB_D2H(out->aux, rb_oaux, (size_t)n_out * 4); RB_D2H(out->src_row, rb_osrc, (size_t)n_out * 4);
-#undef RB_D2H
-    HIP_TRY(c, hipStreamSynchronize(st));
-    c->uploaded = c->ran = false;          // cnt was used as scratch
-    return CSV_OK;
-}
-
-int csv_cigar_signatures(csv_ctx* c, const csv_cigar_in* in, csv_cigar_out* out)
-{
-    if (!c || !in || !out) return CSV_E_INVALID;
-    HIP_TRY(c, hipSetDevice(c->device));
-    out->n_sig_ins = out->n_piece_ins = out->n_sig_del = 0; out->ms_device = 0;
-    const i64 n = in->n_reads;
-    // CSV_CG_FROM_BAM: the columns are the ones csv_bam_decode left on the device (offsets from its own scan: they start at 0,
-    // do not decrease and end at its operation count)
-    const bool from_bam = (in->flags & CSV_CG_FROM_BAM) != 0;
-    if (from_bam && (c->bam_n < 0 || n != c->bam_n)) return fail(c, CSV_E_INVALID, "CSV_CG_FROM_BAM: n_reads is not the record count of the context's last csv_bam_decode");
-    if (n < 0 || (n > 0 && !from_bam && (!in->cig_off || !in->ref_start))) return fail(c, CSV_E_INVALID, "bad CIGAR batch header");
-    if (n == 0) return CSV_OK;
-    const i64 nops = from_bam ? c->bam_nops : in->cig_off[n] - in->cig_off[0];
-    if (!from_bam && (in->cig_off[0] != 0 || nops < 0 || (nops > 0 && !in->cigar))) return fail(c, CSV_E_INVALID, "cig_off must start at 0 and not decrease");
-    if (nops >= (1ll << 31) - 4096) return fail(c, CSV_E_INVALID, "CIGAR batch too large (%lld operations): split it", (long long)nops);
-    for (i64 r = 0; r < n && !from_bam; r++)                    // the kernels index `cigar` with these: every offset is checked here
-        if (in->cig_off[r] < 0 || in->cig_off[r + 1] < in->cig_off[r] || in->cig_off[r + 1] > nops)
-            return fail(c, CSV_E_INVALID, "cig_off decreases or leaves the CIGAR array at read %lld", (long long)r);
-    const int ntile = div_up(n, CG_TILE);
-    // every op can be a piece and a signature of its own: size the outputs for the worst case the caller allows, but never
-    // more than the operations there are
-    const i64 cap_i = out->cap_sig_ins < nops ? out->cap_sig_ins : nops, cap_p = out->cap_piece_ins < nops ? out->cap_piece_ins : nops,
-              cap_d = out->cap_sig_del < nops ? out->cap_sig_del : nops;
-    Plan P;
-#define PL(buf, bytes) P.add(c->buf, (size_t)(bytes))
-    const bool to_pool = (in->flags & CSV_CG_TO_POOL) != 0;
-    if (!from_bam) { PL(cg_off, (n + 1) * 8); PL(cg_ops, (nops + 1) * 4); PL(cg_start, n * 8); }
-    PL(cg_use, n); PL(cg_cnt, n * 16);
-    if (to_pool && in->query_len) PL(cg_qlen, n * 4);
-    PL(cg_tiles, (size_t)ntile * 24); PL(cg_tot, 32);
-    PL(cg_iread, (cap_i + 1) * 4); PL(cg_ipos, (cap_i + 1) * 8); PL(cg_ilen, (cap_i + 1) * 8); PL(cg_ip0, (cap_i + 1) * 8); PL(cg_inp, (cap_i + 1) * 4);
-    PL(cg_pq, (cap_p + 1) * 4); PL(cg_pl, (cap_p + 1) * 4);
-    PL(cg_dread, (cap_d + 1) * 4); PL(cg_dpos, (cap_d + 1) * 8); PL(cg_dlen, (cap_d + 1) * 8);
-#undef PL
-    {
-        if (P.total > c->arena_rb.cap) HIP_TRY(c, hipDeviceSynchronize());
-        const int rc = commit(c, c->arena_rb, P);
-        if (rc) return rc;
-    }
-    hipStream_t st = c->stream;
-    if (!from_bam) {
-        HIP_TRY(c, hipMemcpyAsync(c->cg_off.p, in->cig_off, (size_t)(n + 1) * 8, hipMemcpyHostToDevice, st));
-        if (nops) HIP_TRY(c, hipMemcpyAsync(c->cg_ops.p, in->cigar, (size_t)nops * 4, hipMemcpyHostToDevice, st));
-        HIP_TRY(c, hipMemcpyAsync(c->cg_start.p, in->ref_start, (size_t)n * 8, hipMemcpyHostToDevice, st));
-    }
-    if (in->use) HIP_TRY(c, hipMemcpyAsync(c->cg_use.p, in->use, (size_t)n, hipMemcpyHostToDevice, st));
-    CigarArgs A{};
-    A.n_reads = n; A.cig_off = dp<i64>(c->cg_off); A.cigar = dp<unsigned>(c->cg_ops); A.ref_start = dp<i64>(c->cg_start);
-    if (from_bam) { A.cig_off = dp<i64>(c->bm_cigoff); A.cigar = dp<unsigned>(c->bm_cigar); A.ref_start = dp<i64>(c->bm_start); }
-    A.use = in->use ? dp<uint8_t>(c->cg_use) : nullptr;
-    A.min_siglength = in->min_siglength; A.merge_ins = in->merge_ins_threshold; A.merge_del = in->merge_del_threshold;
-    A.cnt = dp<int4>(c->cg_cnt); A.tile_sum = dp<i64>(c->cg_tiles); A.totals = dp<i64>(c->cg_tot);
-    A.ins_read = dp<int>(c->cg_iread); A.ins_pos = dp<i64>(c->cg_ipos); A.ins_len = dp<i64>(c->cg_ilen); A.ins_piece0 = dp<i64>(c->cg_ip0);
-    A.ins_npiece = dp<int>(c->cg_inp); A.piece_qoff = dp<int>(c->cg_pq); A.piece_len = dp<int>(c->cg_pl);
-    A.del_read = dp<int>(c->cg_dread); A.del_pos = dp<i64>(c->cg_dpos); A.del_len = dp<i64>(c->cg_dlen);
-    const int grid = div_up(n, 4) < 4096 ? div_up(n, 4) : 4096;
-    HIP_TRY(c, hipEventRecord(c->ev[0], st));
-    hipLaunchKernelGGL(k_cigar_count, dim3(grid), dim3(256), 0, st, A);
-    hipLaunchKernelGGL(k_cigar_tiles, dim3(ntile), dim3(256), 0, st, A);
-    hipLaunchKernelGGL(k_cigar_offsets, dim3(ntile), dim3(256), 0, st, A);
-    HIP_TRY(c, hipEventRecord(c->ev[1], st));
-    HIP_TRY(c, hipGetLastError());
-    i64 tot[3] = {0, 0, 0};
-    HIP_TRY(c, hipMemcpyAsync(tot, c->cg_tot.p, 24, hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, hipStreamSynchronize(st));
-    out->n_sig_ins = tot[0]; out->n_piece_ins = tot[1]; out->n_sig_del = tot[2];
-    float ms1 = 0, ms2 = 0;
-    HIP_TRY(c, hipEventElapsedTime(&ms1, c->ev[0], c->ev[1]));
-    if (tot[0] > out->cap_sig_ins || tot[1] > out->cap_piece_ins || tot[2] > out->cap_sig_del)
-        return fail(c, CSV_E_CAPACITY, "need %lld INS signatures / %lld INS pieces / %lld DEL signatures", (long long)tot[0], (long long)tot[1], (long long)tot[2]);
-    HIP_TRY(c, hipEventRecord(c->ev[2], st));
-    hipLaunchKernelGGL(k_cigar_emit, dim3(grid), dim3(256), 0, st, A);
-    HIP_TRY(c, hipEventRecord(c->ev[3], st));
-    HIP_TRY(c, hipGetLastError());
-    if (to_pool && tot[0] + tot[2] > 0) {
-        if (in->read_base < 0 || in->read_base + n >= (1ll << 31)) return fail(c, CSV_E_INVALID, "read_base out of range");
-        { const int rc = pool_reserve(c, tot[0] + tot[2]); if (rc) return rc; }
-        if (in->query_len) HIP_TRY(c, hipMemcpyAsync(c->cg_qlen.p, in->query_len, (size_t)n * 4, hipMemcpyHostToDevice, st));
-        PoolCols PC{dp<int>(c->pool_seg), dp<i64>(c->pool_a), dp<i64>(c->pool_b), dp<int>(c->pool_read), dp<int>(c->pool_aux)};
-        hipLaunchKernelGGL(k_pool_from_cigar, dim3(div_up(tot[0] + tot[2], 256)), dim3(256), 0, st, PC, c->pool_n, A, tot[0], tot[2], in->seg_ins, in->seg_del,
-                           in->read_base, in->query_len ? dp<int>(c->cg_qlen) : nullptr);
-        HIP_TRY(c, hipGetLastError());
-        c->pool_n += tot[0] + tot[2];
-    }
-    // (with CSV_CG_TO_POOL an output array that is NULL is not written)
-#define D2H(dst, buf, bytes) do { if ((bytes) > 0 && ((dst) || !to_pool)) HIP_TRY(c, hipMemcpyAsync((dst), c->buf.p, (size_t)(bytes), hipMemcpyDeviceToHost, st)); } while (0)
-    D2H(out->ins_read, cg_iread, tot[0] * 4); D2H(out->ins_pos, cg_ipos, tot[0] * 8); D2H(out->ins_len, cg_ilen, tot[0] * 8);
-    D2H(out->ins_piece0, cg_ip0, tot[0] * 8); D2H(out->ins_npiece, cg_inp, tot[0] * 4);
-    D2H(out->piece_qoff, cg_pq, tot[1] * 4); D2H(out->piece_len, cg_pl, tot[1] * 4);
-    D2H(out->del_read, cg_dread, tot[2] * 4); D2H(out->del_pos, cg_dpos, tot[2] * 8); D2H(out->del_len, cg_dlen, tot[2] * 8);
-#undef D2H
-    HIP_TRY(c, hipStreamSynchronize(st));
-    HIP_TRY(c, hipEventElapsedTime(&ms2, c->ev[2], c->ev[3]));
-    out->ms_device = ms1 + ms2;
-    return CSV_OK;
-}
-
-int csv_split_signatures(csv_ctx* c, const csv_split_in* in, csv_split_out* out)
-{
-    if (!c || !in || !out) return CSV_E_INVALID;
-    HIP_TRY(c, hipSetDevice(c->device));
-    out->n = 0; out->ms_device = 0;
-    // CSV_SP_FROM_BAM: the reads are the calls csv_bam_split_inputs left on the device, with its entry columns (offsets from
-    // its own scan: they start at 0, do not decrease and end at its entry count)
-    const bool from_bam = (in->flags & CSV_SP_FROM_BAM) != 0;
-    if (from_bam && (c->sa_calls < 0 || c->bam_n < 0)) return fail(c, CSV_E_INVALID, "CSV_SP_FROM_BAM: the context holds no split inputs (csv_bam_split_inputs after the last csv_bam_decode)");
-    const i64 n = from_bam ? c->sa_calls : in->n_reads;
-    if (n < 0 || (n > 0 && !from_bam && (!in->ent_off || !in->read_len))) return fail(c, CSV_E_INVALID, "bad split-read batch header");
-    if (n == 0) return CSV_OK;
-    const i64 ne = from_bam ? c->sa_entries : in->ent_off[n] - in->ent_off[0];
-    if (!from_bam) {
-        if (in->ent_off[0] != 0 || ne < 0) return fail(c, CSV_E_INVALID, "ent_off must start at 0 and not decrease");
-        if (ne > 0 && (!in->c0 || !in->c1 || !in->f0 || !in->f1 || !in->chr || !in->mapq || !in->strand || !in->primary))
-            return fail(c, CSV_E_INVALID, "split-read entry columns missing");
-    }
-    if (ne >= (1ll << 31) - 4096 || n >= (1ll << 31) - 4096) return fail(c, CSV_E_INVALID, "split-read batch too large: split it");
-    for (i64 r = 0; r < n && !from_bam; r++)
-        if (in->ent_off[r + 1] < in->ent_off[r]) return fail(c, CSV_E_INVALID, "ent_off decreases at read %lld", (long long)r);
-    const int ntile = div_up(n, CG_TILE);
-    // the candidate columns are sized for what the caller allows, but never for more than the entries can yield: a read of s
-    // segments emits nothing for s < 2, at most 3 candidates for s = 2 and at most 12 per window of three plus 2 for s >= 3
-    // (split_read: the rules of one window that can fire together put 2 + 2 + 6 + 2) - at most 12 per entry either way
-    const i64 cap_max = 12 * ne, cap = out->cap < 0 ? 0 : out->cap < cap_max ? out->cap : cap_max;
-    Plan P;
-#define PL(buf, bytes) P.add(c->buf, (size_t)(bytes))
-    if (!from_bam) {
-        PL(sp_off, (n + 1) * 8); PL(sp_len, n * 8); PL(sp_c0, (ne + 1) * 8); PL(sp_c1, (ne + 1) * 8); PL(sp_f0, (ne + 1) * 8); PL(sp_f1, (ne + 1) * 8);
-        PL(sp_chr, (ne + 1) * 4); PL(sp_mapq, (ne + 1) * 4); PL(sp_strand, ne + 1); PL(sp_primary, ne + 1);
-    }
-    PL(sp_seg, (ne + 1) * sizeof(SpSeg));
-    PL(sp_cnt, n * 16); PL(sp_tiles, (size_t)ntile * 24); PL(sp_tot, 32);
-    PL(sp_kind, cap + 1); PL(sp_read, (cap + 1) * 4); PL(sp_ochr, (cap + 1) * 4); PL(sp_aux, (cap + 1) * 4);
-    PL(sp_a, (cap + 1) * 8); PL(sp_b, (cap + 1) * 8); PL(sp_c, (cap + 1) * 8); PL(sp_d, (cap + 1) * 8);
-#undef PL
-    {
-        if (P.total > c->arena_rb.cap) HIP_TRY(c, hipDeviceSynchronize());
-        const int rc = commit(c, c->arena_rb, P);
-        if (rc) return rc;
-    }
-    hipStream_t st = c->stream;
-#define H2D(buf, src, bytes) do { if ((bytes) > 0 && !from_bam) HIP_TRY(c, hipMemcpyAsync(c->buf.p, (src), (size_t)(bytes), hipMemcpyHostToDevice, st)); } while (0)
-    H2D(sp_off, in->ent_off, (n + 1) * 8); H2D(sp_len, in->read_len, n * 8);
-    H2D(sp_c0, in->c0, ne * 8); H2D(sp_c1, in->c1, ne * 8); H2D(sp_f0, in->f0, ne * 8); H2D(sp_f1, in->f1, ne * 8);
-    H2D(sp_chr, in->chr, ne * 4); H2D(sp_mapq, in->mapq, ne * 4); H2D(sp_strand, in->strand, ne); H2D(sp_primary, in->primary, ne);
-#undef H2D
-    SplitArgs A{};
-    A.n_reads = n; A.ent_off = dp<i64>(c->sp_off); A.read_len = dp<i64>(c->sp_len);
-    A.c0 = dp<i64>(c->sp_c0); A.c1 = dp<i64>(c->sp_c1); A.f0 = dp<i64>(c->sp_f0); A.f1 = dp<i64>(c->sp_f1);
-    A.chr = dp<int>(c->sp_chr); A.mapq = dp<int>(c->sp_mapq); A.strand = dp<uint8_t>(c->sp_strand); A.primary = dp<uint8_t>(c->sp_primary);
-    if (from_bam) {
-        A.ent_off = dp<i64>(c->sa_entoff); A.read_len = dp<i64>(c->sa_readlen);
-        A.c0 = dp<i64>(c->sa_c0); A.c1 = dp<i64>(c->sa_c1); A.f0 = dp<i64>(c->sa_f0); A.f1 = dp<i64>(c->sa_f1);
-        A.chr = dp<int>(c->sa_chr); A.mapq = dp<int>(c->sa_mapq); A.strand = dp<uint8_t>(c->sa_strand); A.primary = dp<uint8_t>(c->sa_primary);
-    }
-    A.sv = in->sv_size; A.max_size = in->max_size; A.min_mapq = in->min_mapq; A.parts = in->max_split_parts;
-    A.seg = dp<SpSeg>(c->sp_seg); A.cnt = dp<int4>(c->sp_cnt); A.cap = cap;
-    A.kind = dp<uint8_t>(c->sp_kind); A.read = dp<int>(c->sp_read); A.o_chr = dp<int>(c->sp_ochr); A.aux = dp<int>(c->sp_aux);
-    A.a = dp<i64>(c->sp_a); A.b = dp<i64>(c->sp_b); A.c = dp<i64>(c->sp_c); A.d = dp<i64>(c->sp_d);
-    CigarArgs SC{};                                         // the per-read prefix is the CIGAR scan's (k_cigar_tiles / k_cigar_offsets)
-    SC.n_reads = n; SC.cnt = A.cnt; SC.tile_sum = dp<i64>(c->sp_tiles); SC.totals = dp<i64>(c->sp_tot);
-    const int grid = div_up(n, 256);
-    HIP_TRY(c, hipEventRecord(c->ev[0], st));
-    hipLaunchKernelGGL(k_split_count, dim3(grid), dim3(256), 0, st, A);
-    hipLaunchKernelGGL(k_cigar_tiles, dim3(ntile), dim3(256), 0, st, SC);
-    hipLaunchKernelGGL(k_cigar_offsets, dim3(ntile), dim3(256), 0, st, SC);
-    HIP_TRY(c, hipEventRecord(c->ev[1], st));
-    HIP_TRY(c, hipGetLastError());
-    i64 tot[3] = {0, 0, 0};
-    HIP_TRY(c, hipMemcpyAsync(tot, c->sp_tot.p, 24, hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, hipStreamSynchronize(st));
-    out->n = tot[0];
-    if (tot[0] > out->cap) return fail(c, CSV_E_CAPACITY, "need %lld candidates", (long long)tot[0]);
-    if (tot[0] < 0 || tot[0] > cap_max) return fail(c, CSV_E_INVALID, "split-read analysis: inconsistent count (%lld candidates of %lld entries)", (long long)tot[0], (long long)ne);
-    HIP_TRY(c, hipEventRecord(c->ev[2], st));
-    hipLaunchKernelGGL(k_split_emit, dim3(grid), dim3(256), 0, st, A);
-    HIP_TRY(c, hipEventRecord(c->ev[3], st));
-    HIP_TRY(c, hipGetLastError());
-    const bool to_pool = (in->flags & CSV_CG_TO_POOL) != 0;
-    if (to_pool && tot[0] > 0) {
-        // (CSV_SP_FROM_BAM: a row's read is the call's RECORD - the index space of the CIGAR scan's rows of the chunk - and the
-        // query length is the decode's, which is what read_len holds per call)
-        if (in->read_base < 0 || in->read_base + (from_bam ? c->bam_n : n) >= (1ll << 31)) return fail(c, CSV_E_INVALID, "read_base out of range");
-        { const int rc = pool_reserve(c, tot[0]); if (rc) return rc; }
-        const bool own_qlen = in->query_len && !from_bam;
-        if (own_qlen) { const int rc = reserve(c, c->sp_qlen, (size_t)n * 4); if (rc) return rc; HIP_TRY(c, hipMemcpyAsync(c->sp_qlen.p, in->query_len, (size_t)n * 4, hipMemcpyHostToDevice, st)); }
-        PoolCols PC{dp<int>(c->pool_seg), dp<i64>(c->pool_a), dp<i64>(c->pool_b), dp<int>(c->pool_read), dp<int>(c->pool_aux)};
-        PoolSegBase SB{};
-        for (int k = 0; k < 5; k++) SB.b[k] = in->pool_seg_base[k];
-        hipLaunchKernelGGL(k_pool_from_split, dim3(div_up(tot[0], 256)), dim3(256), 0, st, PC, c->pool_n, A, tot[0], SB, in->read_base,
-                           own_qlen ? dp<int>(c->sp_qlen) : nullptr, from_bam ? dp<int>(c->sa_callrec) : nullptr);
-        HIP_TRY(c, hipGetLastError());
-        c->pool_n += tot[0];
-    }
-#define D2H(dst, buf, bytes) do { if ((bytes) > 0 && ((dst) || !to_pool)) HIP_TRY(c, hipMemcpyAsync((dst), c->buf.p, (size_t)(bytes), hipMemcpyDeviceToHost, st)); } while (0)
-    D2H(out->kind, sp_kind, tot[0]); D2H(out->read, sp_read, tot[0] * 4); D2H(out->chr, sp_ochr, tot[0] * 4); D2H(out->aux, sp_aux, tot[0] * 4);
-    D2H(out->a, sp_a, tot[0] * 8); D2H(out->b, sp_b, tot[0] * 8); D2H(out->c, sp_c, tot[0] * 8); D2H(out->d, sp_d, tot[0] * 8);
-#undef D2H
-    HIP_TRY(c, hipStreamSynchronize(st));
-    float ms1 = 0, ms2 = 0;
-    HIP_TRY(c, hipEventElapsedTime(&ms1, c->ev[0], c->ev[1]));
-    HIP_TRY(c, hipEventElapsedTime(&ms2, c->ev[2], c->ev[3]));
-    out->ms_device = ms1 + ms2;
-    return CSV_OK;
-}
-
-int csv_bam_decode(csv_ctx* c, const csv_bam_in* in, csv_bam_out* out)
-{
-    if (!c || !in || !out) return CSV_E_INVALID;
-    HIP_TRY(c, hipSetDevice(c->device));
-    out->n_ops = out->n_sa = out->n_bad = out->bytes_uploaded = 0; out->ms_device = out->ms_upload = 0;
-    out->dev_ref_start = out->dev_ref_end = out->dev_flag = out->dev_mapq = out->dev_query_len = out->dev_clip_left = out->dev_clip_right =
-        out->dev_cls = out->dev_cig_off = out->dev_cigar = nullptr;
-    c->bam_n = -1; c->sa_calls = -1;
-    const i64 n = in->n_records, nb = in->slim_bytes;
-    if (n < 0 || nb < 0 || in->flags != 0 || (n > 0 && (!in->slim || !in->rec_off || !in->rec_len))) return fail(c, CSV_E_INVALID, "bad BAM chunk header");
-    if (n >= (1ll << 31) - 4096) return fail(c, CSV_E_INVALID, "BAM chunk too large (%lld records): split it", (long long)n);
-    // the kernels read [rec_off, rec_off + rec_len) of every record and nothing else: each range is checked against the image
-    for (i64 r = 0; r < n; r++) {
-        const i64 o = in->rec_off[r], l = in->rec_len[r];
-        if (o < 0 || (o & 15) || l < 32 || o > nb || l > nb - o) return fail(c, CSV_E_INVALID, "record %lld of the BAM chunk leaves the slim image (or is misaligned / shorter than 32 bytes)", (long long)r);
-    }
-    if (n == 0) { c->bam_n = 0; c->bam_nops = 0; c->bam_nsa = 0; if (out->cig_off) out->cig_off[0] = 0; if (out->sa_off) out->sa_off[0] = 0; return CSV_OK; }
-    const i64 max_ops = nb / 4;                              // every operation is 4 bytes of the image
-    Plan P;
-#define PL(buf, bytes) P.add(c->buf, (size_t)(bytes))
-    PL(bm_slim, nb + 16); PL(bm_recoff, n * 8); PL(bm_reclen, n * 4);
-    PL(bm_start, n * 8); PL(bm_end, n * 8); PL(bm_flag, n * 4); PL(bm_mapq, n * 4); PL(bm_qlen, n * 4); PL(bm_cl, n * 4); PL(bm_cr, n * 4);
-    PL(bm_cls, n); PL(bm_status, n); PL(bm_cigoff, (n + 1) * 8); PL(bm_saoff, (n + 1) * 8); PL(bm_cigsrc, n * 8); PL(bm_cgb, n * 8); PL(bm_cge, n * 8);
-    PL(bm_cigar, (max_ops + 1) * 4); PL(bm_long, n * 4); PL(bm_cnt, 16); PL(bm_tot, 16);
-#undef PL
-    {
-        if (P.total > c->arena_bam.cap) HIP_TRY(c, hipDeviceSynchronize());
-        const int rc = commit(c, c->arena_bam, P);
-        if (rc) return rc;
-    }
-    hipStream_t st = c->stream;
-    HIP_TRY(c, hipEventRecord(c->ev[4], st));
-    HIP_TRY(c, hipMemcpyAsync(c->bm_slim.p, in->slim, (size_t)nb, hipMemcpyHostToDevice, st));
-    HIP_TRY(c, hipMemcpyAsync(c->bm_recoff.p, in->rec_off, (size_t)n * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(c, hipMemcpyAsync(c->bm_reclen.p, in->rec_len, (size_t)n * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(c, hipEventRecord(c->ev[5], st));
-    out->bytes_uploaded = nb + n * 12;
-    HIP_TRY(c, hipMemsetAsync(c->bm_cnt.p, 0, 16, st));
-    BamArgs A{};
-    A.n = n; A.slim = dp<uint8_t>(c->bm_slim); A.rec_off = dp<i64>(c->bm_recoff); A.rec_len = dp<unsigned>(c->bm_reclen);
-    A.ref_start = dp<i64>(c->bm_start); A.ref_end = dp<i64>(c->bm_end); A.flag = dp<int>(c->bm_flag); A.mapq = dp<int>(c->bm_mapq); A.qlen = dp<int>(c->bm_qlen);
-    A.clip_l = dp<int>(c->bm_cl); A.clip_r = dp<int>(c->bm_cr); A.cls = dp<uint8_t>(c->bm_cls); A.status = dp<uint8_t>(c->bm_status);
-    A.cig_off = dp<i64>(c->bm_cigoff); A.sa_off = dp<i64>(c->bm_saoff); A.cig_src = dp<i64>(c->bm_cigsrc); A.cg_beg = dp<i64>(c->bm_cgb); A.cg_end = dp<i64>(c->bm_cge);
-    A.cigar = dp<unsigned>(c->bm_cigar); A.long_list = dp<int>(c->bm_long); A.counters = dp<int>(c->bm_cnt); A.totals = dp<i64>(c->bm_tot);
-    HIP_TRY(c, hipEventRecord(c->ev[0], st));
-    hipLaunchKernelGGL(k_bam_fixed, dim3(div_up(n, 256)), dim3(256), 0, st, A);
-    hipLaunchKernelGGL(k_bam_scan, dim3(1), dim3(1024), 0, st, A);
-    HIP_TRY(c, hipEventRecord(c->ev[1], st));
-    HIP_TRY(c, hipGetLastError());
-    i64 tot[2] = {0, 0};
-    int cnt[4] = {0, 0, 0, 0};
-    HIP_TRY(c, hipMemcpyAsync(tot, c->bm_tot.p, 16, hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, hipMemcpyAsync(cnt, c->bm_cnt.p, 16, hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, hipStreamSynchronize(st));
-    // (what the kernels counted is bounded by the image they counted it in; anything else would be a bug here, not in the file)
-    if (tot[0] < 0 || tot[0] > max_ops || tot[1] < 0 || tot[1] > nb / 4 || cnt[0] < 0 || cnt[0] > n)
-        return fail(c, CSV_E_INVALID, "BAM decode: inconsistent counts (%lld operations, %lld SA tags)", (long long)tot[0], (long long)tot[1]);
-    out->n_ops = tot[0]; out->n_sa = tot[1]; out->n_bad = cnt[1];
-    if ((out->cigar && tot[0] > out->cap_ops) || ((out->sa_beg || out->sa_end) && tot[1] > out->cap_sa))
-        return fail(c, CSV_E_CAPACITY, "need %lld CIGAR operations / %lld SA ranges", (long long)tot[0], (long long)tot[1]);
-    { int rc = reserve(c, c->bm_sabeg, (size_t)(tot[1] + 1) * 8); if (!rc) rc = reserve(c, c->bm_saend, (size_t)(tot[1] + 1) * 8); if (rc) return rc; }
-    A.sa_beg = dp<i64>(c->bm_sabeg); A.sa_end = dp<i64>(c->bm_saend);
-    HIP_TRY(c, hipEventRecord(c->ev[2], st));
-    const int grid = div_up(n, 4) < 8192 ? div_up(n, 4) : 8192;
-    hipLaunchKernelGGL(k_bam_cigar, dim3(grid), dim3(256), 0, st, A);
-    if (cnt[0] > 0) hipLaunchKernelGGL(k_bam_cigar_long, dim3(cnt[0]), dim3(256), 0, st, A);
-    if (tot[1] > 0) hipLaunchKernelGGL(k_bam_sa, dim3(div_up(n, 256)), dim3(256), 0, st, A);
-    HIP_TRY(c, hipEventRecord(c->ev[3], st));
-    HIP_TRY(c, hipGetLastError());
-#define D2H(dst, buf, bytes) do { if ((dst) && (bytes) > 0) HIP_TRY(c, hipMemcpyAsync((dst), c->buf.p, (size_t)(bytes), hipMemcpyDeviceToHost, st)); } while (0)
-    D2H(out->ref_start, bm_start, n * 8); D2H(out->ref_end, bm_end, n * 8); D2H(out->flag, bm_flag, n * 4); D2H(out->mapq, bm_mapq, n * 4);
-    D2H(out->query_len, bm_qlen, n * 4); D2H(out->clip_left, bm_cl, n * 4); D2H(out->clip_right, bm_cr, n * 4); D2H(out->cls, bm_cls, n);
-    D2H(out->status, bm_status, n); D2H(out->cig_off, bm_cigoff, (n + 1) * 8); D2H(out->cigar, bm_cigar, tot[0] * 4);
-    D2H(out->sa_off, bm_saoff, (n + 1) * 8); D2H(out->sa_beg, bm_sabeg, tot[1] * 8); D2H(out->sa_end, bm_saend, tot[1] * 8);
-    D2H(out->cg_beg, bm_cgb, n * 8); D2H(out->cg_end, bm_cge, n * 8);
-#undef D2H
-    HIP_TRY(c, hipStreamSynchronize(st));
-    float ms1 = 0, ms2 = 0;
-    HIP_TRY(c, hipEventElapsedTime(&ms1, c->ev[0], c->ev[1]));
-    HIP_TRY(c, hipEventElapsedTime(&ms2, c->ev[2], c->ev[3]));
-    HIP_TRY(c, hipEventElapsedTime(&out->ms_upload, c->ev[4], c->ev[5]));
-    out->ms_device = ms1 + ms2;
-    if (cnt[1] > 0) return fail(c, CSV_E_INVALID, "%d record(s) of the BAM chunk have a malformed aux area or CIGAR (see status)", cnt[1]);
-    out->dev_ref_start = c->bm_start.p; out->dev_ref_end = c->bm_end.p; out->dev_flag = c->bm_flag.p; out->dev_mapq = c->bm_mapq.p; out->dev_query_len = c->bm_qlen.p;
-    out->dev_clip_left = c->bm_cl.p; out->dev_clip_right = c->bm_cr.p; out->dev_cls = c->bm_cls.p; out->dev_cig_off = c->bm_cigoff.p; out->dev_cigar = c->bm_cigar.p;
-    c->bam_n = n; c->bam_nops = tot[0]; c->bam_nsa = tot[1];
-    return CSV_OK;
-}
-
-int csv_sa_struct_size(int which)
-{
-    switch (which) {
-    case 0: return (int)sizeof(csv_sa_in);
-    case 1: return (int)sizeof(csv_sa_out);
-    default: return -1;
-    }
-}
-
-int csv_bam_split_inputs(csv_ctx* c, const csv_sa_in* in, csv_sa_out* out)
-{
-    if (!c || !in || !out) return CSV_E_INVALID;
-    HIP_TRY(c, hipSetDevice(c->device));
-    out->n_calls = out->n_entries = out->n_flagged = 0; out->ms_device = 0;
-    c->sa_calls = -1;
-    const i64 n = in->n_records, nn = in->n_names, nbytes = in->name_bytes;
-    if (c->bam_n < 0) return fail(c, CSV_E_INVALID, "csv_bam_split_inputs: the context holds no decoded BAM chunk");
-    if (n != c->bam_n) return fail(c, CSV_E_INVALID, "csv_bam_split_inputs: n_records is not the record count of the context's last csv_bam_decode");
-    if (in->flags != 0 || nn < 0 || nbytes < 0 || (n > 0 && !in->sel) || (nn > 0 && (!in->name_off || !in->name_rank)) || (nbytes > 0 && !in->names))
-        return fail(c, CSV_E_INVALID, "bad split-input header");
-    // the kernels index `names` with these offsets and search the table by halving: both are checked here
-    for (i64 k = 0; k < nn; k++) {
-        const i64 b = in->name_off[k], e = in->name_off[k + 1];
-        if (b < 0 || e < b || e > nbytes) return fail(c, CSV_E_INVALID, "name_off decreases or leaves the name bytes at name %lld", (long long)k);
-        if (k > 0) {
-            const i64 pb = in->name_off[k - 1], pl = b - pb, l = e - b;
-            int cmp = memcmp(in->names + pb, in->names + b, (size_t)(pl < l ? pl : l));
-            if (cmp == 0) cmp = pl < l ? -1 : pl > l ? 1 : 0;
-            if (cmp >= 0) return fail(c, CSV_E_INVALID, "the contig names are not strictly ascending in byte order at name %lld", (long long)k);
-        }
-    }
-    const i64 max_calls = c->bam_nsa;                        // every call is an SA tag of the chunk
-    if (n == 0 || max_calls == 0) {
-        if (out->ent_off) out->ent_off[0] = 0;
-        c->sa_calls = 0; c->sa_entries = 0;
-        return CSV_OK;
-    }
-    Plan P;
-#define PL(buf, bytes) P.add(c->buf, (size_t)(bytes))
-    PL(sa_sel, n); PL(sa_names, nbytes + 1); PL(sa_nameoff, (nn + 1) * 8); PL(sa_namerank, (nn + 1) * 4);
-    PL(sa_calloff, (n + 1) * 8); PL(sa_callrec, (max_calls + 1) * 4); PL(sa_callsa, (max_calls + 1) * 8); PL(sa_entoff, (max_calls + 1) * 8);
-    PL(sa_readlen, (max_calls + 1) * 8); PL(sa_status, max_calls + 1); PL(sa_tot, 32);
-#undef PL
-    {
-        if (P.total > c->arena_sa.cap) HIP_TRY(c, hipDeviceSynchronize());
-        const int rc = commit(c, c->arena_sa, P);
-        if (rc) return rc;
-    }
-    hipStream_t st = c->stream;
-    HIP_TRY(c, hipMemcpyAsync(c->sa_sel.p, in->sel, (size_t)n, hipMemcpyHostToDevice, st));
-    if (nbytes) HIP_TRY(c, hipMemcpyAsync(c->sa_names.p, in->names, (size_t)nbytes, hipMemcpyHostToDevice, st));
-    if (nn) {
-        HIP_TRY(c, hipMemcpyAsync(c->sa_nameoff.p, in->name_off, (size_t)(nn + 1) * 8, hipMemcpyHostToDevice, st));
-        HIP_TRY(c, hipMemcpyAsync(c->sa_namerank.p, in->name_rank, (size_t)nn * 4, hipMemcpyHostToDevice, st));
-    }
-    HIP_TRY(c, hipMemsetAsync(c->sa_tot.p, 0, 32, st));
-    SaArgs A{};
-    A.n = n; A.cap_calls = max_calls; A.cap_entries = 0;
-    A.slim = dp<uint8_t>(c->bm_slim); A.sa_off = dp<i64>(c->bm_saoff); A.sa_beg = dp<i64>(c->bm_sabeg); A.sa_end = dp<i64>(c->bm_saend);
-    A.flag = dp<int>(c->bm_flag); A.mapq = dp<int>(c->bm_mapq); A.qlen = dp<int>(c->bm_qlen); A.clip_l = dp<int>(c->bm_cl); A.clip_r = dp<int>(c->bm_cr);
-    A.ref_start = dp<i64>(c->bm_start); A.ref_end = dp<i64>(c->bm_end);
-    A.sel = dp<uint8_t>(c->sa_sel); A.min_mapq = in->min_mapq; A.task_rank = in->task_rank;
-    A.names = dp<uint8_t>(c->sa_names); A.name_off = dp<i64>(c->sa_nameoff); A.name_rank = dp<int>(c->sa_namerank); A.n_names = (int)nn;
-    A.call_off = dp<i64>(c->sa_calloff); A.call_rec = dp<int>(c->sa_callrec); A.call_sa = dp<i64>(c->sa_callsa); A.ent_off = dp<i64>(c->sa_entoff);
-    A.read_len = dp<i64>(c->sa_readlen); A.status = dp<uint8_t>(c->sa_status); A.tot = dp<i64>(c->sa_tot);
-    HIP_TRY(c, hipEventRecord(c->ev[0], st));
-    hipLaunchKernelGGL(k_sa_mark, dim3(div_up(n, 256)), dim3(256), 0, st, A);
-    hipLaunchKernelGGL(k_sa_scan, dim3(1), dim3(1024), 0, st, A.call_off, n, (const i64*)nullptr, n, A.tot);
-    hipLaunchKernelGGL(k_sa_calls, dim3(div_up(n, 256)), dim3(256), 0, st, A);
-    hipLaunchKernelGGL(k_sa_parse<false>, dim3(max_calls < 8192 ? (int)max_calls : 8192), dim3(64), 0, st, A);
-    hipLaunchKernelGGL(k_sa_scan, dim3(1), dim3(1024), 0, st, A.ent_off, (i64)0, (const i64*)A.tot, max_calls, A.tot + 1);
-    HIP_TRY(c, hipEventRecord(c->ev[1], st));
-    HIP_TRY(c, hipGetLastError());
-    i64 tot[3] = {0, 0, 0};
-    HIP_TRY(c, hipMemcpyAsync(tot, c->sa_tot.p, 24, hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, hipStreamSynchronize(st));
-    // (what the kernels counted is bounded by the text they counted it in; anything else would be a bug here, not in the file)
-    if (tot[0] < 0 || tot[0] > max_calls || tot[1] < 0 || tot[1] > c->bm_slim.cap + max_calls || tot[2] < 0 || tot[2] > tot[0])
-        return fail(c, CSV_E_INVALID, "split inputs: inconsistent counts (%lld calls, %lld entries)", (long long)tot[0], (long long)tot[1]);
-    const i64 nc = tot[0], ne = tot[1];
-    out->n_calls = nc; out->n_entries = ne; out->n_flagged = tot[2];
-    float ms1 = 0, ms2 = 0;
-    HIP_TRY(c, hipEventElapsedTime(&ms1, c->ev[0], c->ev[1]));
-    out->ms_device = ms1;
-    const bool want_calls = out->ent_off || out->read_len || out->call_rec || out->status;
-    const bool want_entries = out->c0 || out->c1 || out->f0 || out->f1 || out->chr || out->mapq || out->strand || out->primary;
-    if ((want_calls && nc > out->cap_calls) || (want_entries && ne > out->cap_entries))
-        return fail(c, CSV_E_CAPACITY, "need %lld calls / %lld entries", (long long)nc, (long long)ne);
-    {
-        int rc = reserve(c, c->sa_c0, (size_t)(ne + 1) * 8);
-        if (!rc) rc = reserve(c, c->sa_c1, (size_t)(ne + 1) * 8);
-        if (!rc) rc = reserve(c, c->sa_f0, (size_t)(ne + 1) * 8);
-        if (!rc) rc = reserve(c, c->sa_f1, (size_t)(ne + 1) * 8);
-        if (!rc) rc = reserve(c, c->sa_chr, (size_t)(ne + 1) * 4);
-        if (!rc) rc = reserve(c, c->sa_mapq, (size_t)(ne + 1) * 4);
-        if (!rc) rc = reserve(c, c->sa_strand, (size_t)ne + 1);
-        if (!rc) rc = reserve(c, c->sa_primary, (size_t)ne + 1);
-        if (rc) return rc;
-    }
-    A.cap_entries = ne;
-    A.c0 = dp<i64>(c->sa_c0); A.c1 = dp<i64>(c->sa_c1); A.f0 = dp<i64>(c->sa_f0); A.f1 = dp<i64>(c->sa_f1);
-    A.chr = dp<int>(c->sa_chr); A.emapq = dp<int>(c->sa_mapq); A.strand = dp<uint8_t>(c->sa_strand); A.primary = dp<uint8_t>(c->sa_primary);
-    if (nc > 0 && ne > 0) {
-        HIP_TRY(c, hipEventRecord(c->ev[2], st));
-        hipLaunchKernelGGL(k_sa_parse<true>, dim3(nc < 8192 ? (int)nc : 8192), dim3(64), 0, st, A);
-        HIP_TRY(c, hipEventRecord(c->ev[3], st));
-        HIP_TRY(c, hipGetLastError());
-    }
-#define D2H(dst, buf, bytes) do { if ((dst) && (bytes) > 0) HIP_TRY(c, hipMemcpyAsync((dst), c->buf.p, (size_t)(bytes), hipMemcpyDeviceToHost, st)); } while (0)
-    D2H(out->ent_off, sa_entoff, (nc + 1) * 8); D2H(out->read_len, sa_readlen, nc * 8); D2H(out->call_rec, sa_callrec, nc * 4); D2H(out->status, sa_status, nc);
-    D2H(out->c0, sa_c0, ne * 8); D2H(out->c1, sa_c1, ne * 8); D2H(out->f0, sa_f0, ne * 8); D2H(out->f1, sa_f1, ne * 8);
-    D2H(out->chr, sa_chr, ne * 4); D2H(out->mapq, sa_mapq, ne * 4); D2H(out->strand, sa_strand, ne); D2H(out->primary, sa_primary, ne);
-#undef D2H
-    HIP_TRY(c, hipStreamSynchronize(st));
-    if (nc > 0 && ne > 0) { HIP_TRY(c, hipEventElapsedTime(&ms2, c->ev[2], c->ev[3])); out->ms_device = ms1 + ms2; }
-    c->sa_calls = nc; c->sa_entries = ne;
-    return CSV_OK;
-}
-
 int csv_cluster_batch(csv_ctx* c, const csv_batch_in* in, csv_batch_out* out)
 {
     if (!c || !in || !out) return CSV_E_INVALID;
@@ -2695,3 +1591,10 @@ int csv_cluster_batch(csv_ctx* c, const csv_batch_in* in, csv_batch_out* out)
 }
 
 }  // extern "C"
+
+// the extraction-side stages: host code over the kernel headers above, one file per stage
+#include "stage_pool.hip.h"
+#include "stage_names.hip.h"
+#include "stage_rebuild.hip.h"
+#include "stage_extract.hip.h"
+#include "stage_bam.hip.h"

@@ -3,7 +3,8 @@
 
     python scripts/isa_valu_by_line.py k_refine_indel_waveILb1E [top] [v|s]
 
-Compiles cutesv_amd/csrc/cutesv_hip.hip for gfx950 with line tables (-gline-tables-only -S), walks the kernel's assembly and
+Compiles cutesv_amd/csrc/cutesv_hip.hip - the library's one translation unit: the kernel headers, ctx.hip.h and the stage_*.hip.h
+it includes - for gfx950 with line tables (-gline-tables-only -S), walks the kernel's assembly and
 charges every v_* instruction to the source line of the last .loc directive.  The kernels of this library run at 55 - 86 % of the
 vector ALUs' issue rate (profiles/r04_cfg*_insts.txt), so the instruction count is the time; this lists
 where the instructions are (all template instantiations inlined into the kernel together, rare paths included: static, not

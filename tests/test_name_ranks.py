@@ -425,3 +425,84 @@ def test_gpu_rebuilt_device_columns_feed_the_clustering_stage(ctx, tmp_path):
     for k in ("call_seg", "bp1", "bp2", "support", "support_off", "support_sig"):
         assert np.array_equal(res_dev[k], res_host[k]), k
     rebuild.pool_reset(ctx); rebuild.name_pool_reset(ctx)
+
+
+# ---- one context through the whole chain, three times: every stage's buffers grow, are reused smaller, are reused at size
+def host_rebuilt(case, path, t0, t1):
+    """The region's rebuilt columns with nothing run on the device: single_pipe_bam's host path (decode_host + the oracle's
+    CIGAR / split engines), its candidate tuples as pool rows (the mapping test_oracle_golden checks), read ids from
+    name_ranks_host over the names of the region's records, then the rebuild's contract in numpy: lexsort by (segment,
+    [aux where it is major], a, b, read id) and adjacent de-duplication outside the INS segments.  Rows that tie on the
+    whole key are ordered by aux here (the device keeps them in pool order).  -> (columns, rank, first)"""
+    from cutesv_amd.columns import BND_CODE
+    from oracle import oracle
+    p, chrom = case["params"], case["task"][0]
+    crank = {c: i for i, c in enumerate(case["chroms"])}
+    seg_of, _, major, nodedup = segments_of(case)
+    with bam.BamFile(path) as bf:
+        ch = bf.records(chrom, t0, t1)
+        cand, _ = extract.single_pipe_bam((oracle.cigar_signatures, oracle.split_signatures), bf, chrom, t0, t1, crank, *pipe_args(p), bed_regions=case["bed"])
+    off, ln = ch.name_columns()
+    rank, first = rebuild.name_ranks_host(ch.host, off, ln)
+    rank_of = {ch.name(i): int(rank[i]) for i in range(ch.n)}
+    rows = []
+    for t, lst in cand.items():
+        for x in lst:
+            seg = seg_of(t, crank[x[-1]])
+            if t in ("DEL", "DUP"):
+                a, b, aux = x[0], x[1], 0
+            elif t == "INS":
+                a, b, aux = int(x[0]), x[1], len(x[3])
+            elif t == "INV":
+                a, b, aux = x[1], x[2], {"++": 0, "--": 1}[x[0]]
+            else:
+                a, b, aux = x[1], x[3], crank[x[2]] * 8 + BND_CODE[x[0]]
+            rows.append((seg, aux if major[seg] else 0, a, b, rank_of[x[2] if t == "INS" else x[-3]], aux))
+    rows = np.array(sorted(rows), np.int64).reshape(-1, 6)
+    same = np.r_[False, (rows[1:, :5] == rows[:-1, :5]).all(axis=1)]
+    rows = rows[~(same & (nodedup[rows[:, 0]] == 0))]
+    cols = dict(seg_id=rows[:, 0].astype(np.int32), a=rows[:, 2], b=rows[:, 3], read_id=rows[:, 4].astype(np.int32), aux=rows[:, 5].astype(np.int32),
+                seg_count=np.bincount(rows[:, 0], minlength=len(major)).astype(np.int64))
+    return cols, rank, first
+
+
+@pytest.mark.gpu
+def test_gpu_one_context_through_growing_shrinking_and_refilled_stages(ctx, tmp_path):
+    from cutesv_amd.columns import Params
+    from oracle import oracle
+    case = load_json("single_pipe.json.gz")[0]
+    p, chrom = case["params"], case["task"][0]
+    crank = {c: i for i, c in enumerate(case["chroms"])}
+    seg_of, seg_base, major, nodedup = segments_of(case)
+    refs, recs = golden_records(case, chrom)
+    path = str(tmp_path / "g.bam")
+    bam_writer.write_bam(path, refs, recs)
+    sizes = []
+    for k, (t0, t1) in enumerate(((0, 3000000), (0, 220000), (0, 3000000))):
+        if k == 2:
+            # the rebuild counted into the engine's counter block and cleared `uploaded`: the engine comes back clean
+            st = synth.small_mixed(seed=2026, n_sites=24)
+            hb = st.host_batch(st.tasks(), Params.ont(genotype=True))
+            got = ctx.cluster_batch(hb, per_sig=True).trimmed()
+            want = oracle.cluster_batch(hb, per_sig=True).trimmed()
+            assert got["n_clusters"] == want["n_clusters"]
+            for key in ("call_seg", "call_cluster", "bp1", "bp2", "support", "cipos", "cilen", "search_pos", "seq_pick", "dr", "dv", "gl_idx",
+                        "support_off", "support_sig", "cluster_id", "allele_id"):
+                assert np.array_equal(got[key], want[key]), key
+        rebuild.pool_reset(ctx); rebuild.name_pool_reset(ctx)
+        with bam.BamFile(path) as bf:
+            res = extract.task_to_pool(ctx, bf, chrom, t0, t1, crank, *pipe_args(p), seg_of("INS", crank[chrom]), seg_of("DEL", crank[chrom]), seg_base, None,
+                                       bed_regions=case["bed"], name_pool=True)
+        got = rebuild.rebuild_pool_by_name(ctx, major, nodedup, keep_on_device=False)
+        want, rank, first = host_rebuilt(case, path, t0, t1)
+        assert res["n_flagged"] == 0 and res["n_records"] == len(rank) == rebuild.name_pool_rows(ctx)
+        ranks = rebuild.name_ranks(ctx)
+        assert np.array_equal(ranks["rank"], rank) and np.array_equal(ranks["first"], first)
+        for key in ("seg_id", "a", "b", "read_id", "seg_count"):
+            assert np.array_equal(got[key], want[key]), (k, key)
+        auxk = np.where(major[got["seg_id"]] != 0, got["aux"], 0)
+        tie_order = np.lexsort((got["aux"], got["read_id"], got["b"], got["a"], auxk, got["seg_id"]))
+        assert np.array_equal(got["aux"][tie_order], want["aux"]), k
+        sizes.append((res["n_records"], len(got["a"])))
+    assert sizes[0] == sizes[2] and sizes[0][0] > 250 and 10 < sizes[1][0] < 40 and sizes[1][1] > 0
+    rebuild.pool_reset(ctx); rebuild.name_pool_reset(ctx)
