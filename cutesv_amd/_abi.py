@@ -22,9 +22,12 @@ IN_PER_SIG, IN_READS_SORTED, IN_SIG_I32, IN_READS_I32, IN_DEVICE_COLUMNS, IN_SIG
 RB_KEEP_ON_DEVICE = 1
 RB_FROM_POOL = 2                        # ... the rows are the context's device-resident signature pool
 RB_RANK_FROM_NAMES = 4                  # ... with RB_FROM_POOL: the read ranks are those of the context's name pool (csv_name_ranks)
+RB_TIES_FROM_SEQS = 8                   # ... with RB_FROM_POOL and seg_nodedup: the INS tie groups are settled from the context's sequence pool
 CG_TO_POOL = 1                         # csv_cigar_in.flags: the signatures also become pool rows                         # csv_rebuild_in.flags
 CG_FROM_BAM = 2                        # csv_cigar_in.flags: scan the device columns of the context's last csv_bam_decode
 SP_FROM_BAM = 4                        # csv_split_in.flags: the reads are the calls of the context's last csv_bam_split_inputs
+SEQ_OPT_WHOLE_IMAGE = 1                # csv_seq_option: send the host image whole (measurement aid)
+CG_SEQ_TO_POOL = 8                     # both flags words, with CG_TO_POOL: the INS rows' bases go to the context's sequence pool
 BAM_RESTART, BAM_COUNT_ONLY = 1, 2     # csv_bam_read flags
 SEG_KEY_RANGE = 1                             # csv_batch_out.seg_status bits
 OUT_NO_SUPPORT_LIST, OUT_COORD_I32 = 1, 2     # csv_batch_out.flags (ABI v7)
@@ -106,6 +109,11 @@ class RebuildOut(C.Structure):
 class NameRankOut(C.Structure):
     _fields_ = [("n", C.c_int64), ("n_distinct", C.c_int64), ("rank", C.c_void_p), ("first", C.c_void_p), ("cap_first", C.c_int64),
                 ("ms_device", C.c_float), ("n_passes", C.c_int32), ("max_len", C.c_int32), ("reserved", C.c_int32), ("dev_rank", C.c_void_p)]
+
+
+class SeqInfo(C.Structure):
+    _fields_ = [("reads_uploaded", C.c_int64), ("bytes_uploaded", C.c_int64), ("rows_gathered", C.c_int64), ("bytes_gathered", C.c_int64),
+                ("ms_upload", C.c_float), ("ms_gather", C.c_float), ("packed", C.c_int32), ("reserved", C.c_int32), ("device_bytes", C.c_int64)]
 
 
 class VcfIn(C.Structure):
@@ -218,6 +226,7 @@ STRUCT_SIZES = [("csv_segment", SEGMENT_DTYPE.itemsize), ("csv_batch_in", C.size
 BAM_STRUCT_SIZES = [("csv_bam_chunk", C.sizeof(ChunkC)), ("csv_bam_in", C.sizeof(BamIn)), ("csv_bam_out", C.sizeof(BamOut))]
 SA_STRUCT_SIZES = [("csv_sa_in", C.sizeof(SaIn)), ("csv_sa_out", C.sizeof(SaOut))]
 NAME_STRUCT_SIZES = [("csv_name_rank_out", C.sizeof(NameRankOut))]
+SEQ_STRUCT_SIZES = [("csv_seq_info", C.sizeof(SeqInfo))]
 
 
 def _ptr(arr):

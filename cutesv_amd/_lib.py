@@ -51,6 +51,15 @@ SYMBOLS = [
     ("csv_name_ranks", C.c_int, [C.c_void_p, C.POINTER(_abi.NameRankOut)]),
     ("csv_name_pool_get", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     ("csv_name_struct_size", C.c_size_t, [C.c_int]),
+    ("csv_seq_reads_upload", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("csv_seq_option", C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    ("csv_seq_query_reverse", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p]),
+    ("csv_seq_pool_rows", C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    ("csv_seq_pool_put", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("csv_seq_pool_get", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    ("csv_seq_pool_half", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    ("csv_seq_info_get", C.c_int, [C.c_void_p, C.POINTER(_abi.SeqInfo)]),
+    ("csv_seq_struct_size", C.c_int, [C.c_int]),
     ("csv_vcf_emit", C.c_int, [C.POINTER(_abi.VcfIn), C.c_char_p, C.c_int64, C.POINTER(C.c_int64), C.c_void_p]),
     ("csv_bam_open", C.c_int, [C.c_char_p, C.c_int, C.POINTER(C.c_void_p), C.c_char_p, C.c_int]),
     ("csv_bam_close", None, [C.c_void_p]),
@@ -84,7 +93,7 @@ def lib():
             raise ExtensionMissing("libcutesv_hip.so ABI %d != python side %d" % (L.csv_abi_version(), _abi.ABI_VERSION))
         # a stale build with the same ABI number: every struct must have the size of its mirror
         for size_of, table in ((L.csv_struct_size, _abi.STRUCT_SIZES), (L.csv_bam_struct_size, _abi.BAM_STRUCT_SIZES), (L.csv_sa_struct_size, _abi.SA_STRUCT_SIZES),
-                               (L.csv_name_struct_size, _abi.NAME_STRUCT_SIZES)):
+                               (L.csv_name_struct_size, _abi.NAME_STRUCT_SIZES), (L.csv_seq_struct_size, _abi.SEQ_STRUCT_SIZES)):
             for i, (name, size) in enumerate(table):
                 if size_of(i) != size:
                     raise ExtensionMissing("%s: sizeof(%s) is %d, its python mirror has %d bytes: rebuild the library" % (LIB_PATH, name, size_of(i), size))

@@ -62,6 +62,16 @@ class Chunk:
         n_len = self.slim[self.rec_off + 8].astype(np.int32) if self.n else np.zeros(0, np.int32)      # l_read_name, NUL included
         return np.ascontiguousarray(self.host_off[:self.n], np.int64), np.maximum(n_len - 1, 0)
 
+    def sequence_columns(self):
+        """-> (off int64[n], l_seq int32[n]): the bases of record i are the (l_seq[i] + 1) // 2 bytes at host[off[i]:], 4 bits per
+        base, high nibble first - the strided form csv_seq_reads_upload takes, with `host` as its bytes: nothing is decoded here"""
+        if not self.n:
+            return np.zeros(0, np.int64), np.zeros(0, np.int32)
+        fixed = self.rec_off[:, None] + np.arange(16, 20)                      # l_seq: bytes 16 .. 19 of a record, little endian
+        l_seq = np.ascontiguousarray(self.slim[fixed]).view("<u4").ravel().astype(np.int32)
+        n_len = self.slim[self.rec_off + 8].astype(np.int64)                   # l_read_name, NUL included
+        return np.ascontiguousarray(self.host_off[:self.n], np.int64) + n_len, l_seq
+
     def name(self, i):
         h0 = int(self.host_off[i])
         return self.host[h0 : h0 + self._name_len(i) - 1].tobytes().decode()

@@ -77,6 +77,26 @@ struct SaState {
     i64 calls = -1, entries = 0;               // calls / entries the context holds (-1: no split inputs)
     void own(std::vector<Buf*>& v) { v.insert(v.end(), {&c0, &c1, &f0, &f1, &chr, &mapq, &strand, &primary}); }
 };
+// The INS sequence pool (seqs.hip.h), in two parts, all stand-alone.  (1) The read sequences of the current batch: the packed
+// 4-bit image csv_seq_reads_upload made, with per read its offset and length (-1: not uploaded), indexed by the batch's read
+// index; they live until the next upload or the next csv_bam_decode (n_reads = -1: none).  qrev: the strand byte per read of a
+// host-fed split analysis (csv_seq_query_reverse), dead with the upload.  (2) The shadow of the signature pool: blob = the ASCII
+// bases back to back (grows only, by copying), off / half = per POOL ROW the first byte (-1: no sequence) and the x.5 flag; the
+// row arrays grow with the pool (pool_reserve) and hold values for the rows [0, rows) - seq_sync fills up to the pool's count.
+// They live until csv_pool_reset.  Per-call scratch, dead when the call returns: plan (lengths and their scan of an attach), tie (group tables and
+// the answer of k_seq_tie_order), get (row / offset tables of put and get), out (the gathered bases of a get on their way to the host).
+// whole: csv_seq_option(CSV_SEQ_OPT_WHOLE_IMAGE), the measurement aid.
+struct SeqState {
+    Buf rbytes, roff, rlen, qrev;
+    i64 n_reads = -1, n_qrev = -1;
+    Buf blob, off, half;
+    i64 rows = 0, rows_cap = 0, bytes = 0, n_with = 0;
+    Buf plan, tie, get, out;
+    bool whole = false;
+    csv_seq_info info{};
+    i64 device_bytes() { std::vector<Buf*> v; own(v); i64 t = 0; for (Buf* b : v) t += (i64)b->cap; return t; }
+    void own(std::vector<Buf*>& v) { v.insert(v.end(), {&rbytes, &roff, &rlen, &qrev, &blob, &off, &half, &plan, &tie, &get, &out}); }
+};
 
 }  // namespace
 
@@ -113,7 +133,7 @@ struct csv_ctx {
     Buf gs_chrom, gs_perm0, gs_perm1, gs_hist, gs_tot;          // general reads sort (fallback), allocated on first use
     Buf flush;                                                   // csv_cache_flush scratch
     // the extraction-side stages (their lifetime rules: at the structs)
-    PoolState pool; NameState nm; BamState bm; SaState sa;
+    PoolState pool; NameState nm; BamState bm; SaState sa; SeqState seq;
     Arena scratch;                             // per-call scratch of the rebuild, the CIGAR scan and the split analysis
     RebuildState rb; CigarState cg; SplitState sp;
     // page-locked host staging: small tables on the way in, counters + call records + support lists on the way out

@@ -9,7 +9,7 @@ int csv_bam_decode(csv_ctx* c, const csv_bam_in* in, csv_bam_out* out)
     out->n_ops = out->n_sa = out->n_bad = out->bytes_uploaded = 0; out->ms_device = out->ms_upload = 0;
     out->dev_ref_start = out->dev_ref_end = out->dev_flag = out->dev_mapq = out->dev_query_len = out->dev_clip_left = out->dev_clip_right =
         out->dev_cls = out->dev_cig_off = out->dev_cigar = nullptr;
-    c->bm.n = -1; c->sa.calls = -1;
+    c->bm.n = -1; c->sa.calls = -1; c->seq.n_reads = -1; c->seq.n_qrev = -1;      // (the uploaded read sequences belong to the previous batch)
     const i64 n = in->n_records, nb = in->slim_bytes;
     if (n < 0 || nb < 0 || in->flags != 0 || (n > 0 && (!in->slim || !in->rec_off || !in->rec_len))) return fail(c, CSV_E_INVALID, "bad BAM chunk header");
     if (n >= (1ll << 31) - 4096) return fail(c, CSV_E_INVALID, "BAM chunk too large (%lld records): split it", (long long)n);

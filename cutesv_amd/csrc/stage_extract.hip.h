@@ -13,6 +13,10 @@ int csv_cigar_signatures(csv_ctx* c, const csv_cigar_in* in, csv_cigar_out* out)
     const bool from_bam = (in->flags & CSV_CG_FROM_BAM) != 0;
     if (from_bam && (c->bm.n < 0 || n != c->bm.n)) return fail(c, CSV_E_INVALID, "CSV_CG_FROM_BAM: n_reads is not the record count of the context's last csv_bam_decode");
     if (n < 0 || (n > 0 && !from_bam && (!in->cig_off || !in->ref_start))) return fail(c, CSV_E_INVALID, "bad CIGAR batch header");
+    // CSV_CG_SEQ_TO_POOL: the INS rows' bases are cut out of the uploaded read sequences, whose index space is this batch's
+    const bool seq_to_pool = (in->flags & CSV_CG_SEQ_TO_POOL) != 0;
+    if (seq_to_pool && !(in->flags & CSV_CG_TO_POOL)) return fail(c, CSV_E_INVALID, "CSV_CG_SEQ_TO_POOL needs CSV_CG_TO_POOL");
+    if (seq_to_pool && c->seq.n_reads != n) return fail(c, CSV_E_INVALID, "CSV_CG_SEQ_TO_POOL: the context holds no read sequences for this batch (csv_seq_reads_upload with n_reads = %lld)", (long long)n);
     if (n == 0) return CSV_OK;
     const i64 nops = from_bam ? c->bm.nops : in->cig_off[n] - in->cig_off[0];
     if (!from_bam && (in->cig_off[0] != 0 || nops < 0 || (nops > 0 && !in->cigar))) return fail(c, CSV_E_INVALID, "cig_off must start at 0 and not decrease");
@@ -68,8 +72,15 @@ int csv_cigar_signatures(csv_ctx* c, const csv_cigar_in* in, csv_cigar_out* out)
         TRY(pool_attach(c, in->read_base, n, tot[0] + tot[2], &PC));
         if (in->query_len) TRY(h2d(c, c->cg.qlen, in->query_len, n * 4));
         hipLaunchKernelGGL(k_pool_from_cigar, dim3(div_up(tot[0] + tot[2], 256)), dim3(256), 0, st, PC, c->pool.n, A, tot[0], tot[2], in->seg_ins, in->seg_del,
-                           in->read_base, in->query_len ? dp<int>(c->cg.qlen) : nullptr);
+                           in->read_base, in->query_len ? dp<int>(c->cg.qlen) : seq_to_pool ? dp<int>(c->seq.rlen) : nullptr);
         HIP_TRY(c, hipGetLastError());
+        if (seq_to_pool) {
+            const SeqReads SR{dp<uint8_t>(c->seq.rbytes), dp<i64>(c->seq.roff), dp<int>(c->seq.rlen), c->seq.n_reads};
+            const i64 base = c->pool.n;
+            TRY(seq_attach(c, tot[0] + tot[2], tot[0],
+                           [&](int4* cnt, int* err) { hipLaunchKernelGGL(k_seq_plan_cigar, dim3(div_up(tot[0], 256)), dim3(256), 0, st, SR, A, tot[0], dp<int>(c->pool.aux) + base, cnt, err); },
+                           [&](const int4* cnt, SeqPool SP, i64 blob_base) { hipLaunchKernelGGL(k_seq_gather_cigar, dim3(div_up(tot[0], 4)), dim3(256), 0, st, SR, SP, A, tot[0], cnt, base, blob_base); }));
+        }
         c->pool.n += tot[0] + tot[2];
     }
     // (with CSV_CG_TO_POOL an output array that is NULL is not written)
@@ -94,6 +105,11 @@ int csv_split_signatures(csv_ctx* c, const csv_split_in* in, csv_split_out* out)
     if (from_bam && (c->sa.calls < 0 || c->bm.n < 0)) return fail(c, CSV_E_INVALID, "CSV_SP_FROM_BAM: the context holds no split inputs (csv_bam_split_inputs after the last csv_bam_decode)");
     const i64 n = from_bam ? c->sa.calls : in->n_reads;
     if (n < 0 || (n > 0 && !from_bam && (!in->ent_off || !in->read_len))) return fail(c, CSV_E_INVALID, "bad split-read batch header");
+    const bool seq_to_pool = (in->flags & CSV_CG_SEQ_TO_POOL) != 0;
+    if (seq_to_pool && !(in->flags & CSV_CG_TO_POOL)) return fail(c, CSV_E_INVALID, "CSV_CG_SEQ_TO_POOL needs CSV_CG_TO_POOL");
+    if (seq_to_pool && c->seq.n_reads != (from_bam ? c->bm.n : n))
+        return fail(c, CSV_E_INVALID, "CSV_CG_SEQ_TO_POOL: the context holds no read sequences for this batch (csv_seq_reads_upload with n_reads = %lld)", (long long)(from_bam ? c->bm.n : n));
+    if (seq_to_pool && !from_bam && c->seq.n_qrev != n) return fail(c, CSV_E_INVALID, "CSV_CG_SEQ_TO_POOL: the reads' strands are missing (csv_seq_query_reverse)");
     if (n == 0) return CSV_OK;
     const i64 ne = from_bam ? c->sa.entries : in->ent_off[n] - in->ent_off[0];
     if (!from_bam) {
@@ -169,6 +185,14 @@ int csv_split_signatures(csv_ctx* c, const csv_split_in* in, csv_split_out* out)
         hipLaunchKernelGGL(k_pool_from_split, dim3(div_up(tot[0], 256)), dim3(256), 0, st, PC, c->pool.n, A, tot[0], SB, in->read_base,
                            own_qlen ? dp<int>(c->sp.qlen) : nullptr, from_bam ? dp<int>(c->sa.callrec) : nullptr);
         HIP_TRY(c, hipGetLastError());
+        if (seq_to_pool) {
+            const SeqReads SR{dp<uint8_t>(c->seq.rbytes), dp<i64>(c->seq.roff), dp<int>(c->seq.rlen), c->seq.n_reads};
+            const SeqSplitSrc Q{from_bam ? dp<int>(c->sa.callrec) : nullptr, from_bam ? dp<int>(c->bm.flag) : nullptr, from_bam ? nullptr : dp<uint8_t>(c->seq.qrev)};
+            const i64 base = c->pool.n;
+            TRY(seq_attach(c, tot[0], tot[0],
+                           [&](int4* cnt, int* err) { hipLaunchKernelGGL(k_seq_plan_split, dim3(div_up(tot[0], 256)), dim3(256), 0, st, SR, A, Q, tot[0], dp<int>(c->pool.aux) + base, cnt, err); },
+                           [&](const int4* cnt, SeqPool SP, i64 blob_base) { hipLaunchKernelGGL(k_seq_gather_split, dim3(div_up(tot[0], 4)), dim3(256), 0, st, SR, SP, A, Q, tot[0], cnt, base, blob_base); }));
+        }
         c->pool.n += tot[0];
     }
     // (with CSV_CG_TO_POOL an output array that is NULL is not written)

@@ -2,6 +2,16 @@
 // entries that append rows on the device.  Host code; included by cutesv_hip.hip.
 extern "C" {
 
+// the row arrays of the sequence pool (SeqState: off, half) with room for `rows` pool rows; the first c->seq.rows entries survive
+static int seq_rows_reserve(csv_ctx* c, i64 rows)
+{
+    if (rows <= c->seq.rows_cap) return CSV_OK;
+    TRY(grow_keep(c, c->seq.off, (size_t)rows * 8, (size_t)c->seq.rows * 8));
+    TRY(grow_keep(c, c->seq.half, (size_t)rows, (size_t)c->seq.rows));
+    c->seq.rows_cap = rows;
+    return CSV_OK;
+}
+
 // room for `extra` more rows in the pool (grows by copying: the pool is not in an arena)
 static int pool_reserve(csv_ctx* c, i64 extra)
 {
@@ -21,6 +31,7 @@ static int pool_reserve(csv_ctx* c, i64 extra)
         cols[k]->p = p; cols[k]->cap = (size_t)cap * w[k];
     }
     c->pool.cap = cap;
+    if (c->seq.off.p) TRY(seq_rows_reserve(c, cap));         // (a context that never held a sequence pays nothing)
     return CSV_OK;
 }
 
@@ -38,6 +49,7 @@ int csv_pool_reset(csv_ctx* c)
 {
     if (!c) return CSV_E_INVALID;
     c->pool.n = 0;
+    c->seq.rows = 0; c->seq.bytes = 0; c->seq.n_with = 0;    // the sequence pool shadows the rows
     return CSV_OK;
 }
 

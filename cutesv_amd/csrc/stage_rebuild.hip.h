@@ -15,6 +15,11 @@ int csv_rebuild_signatures(csv_ctx* c, const csv_rebuild_in* in, csv_rebuild_out
     const bool by_name = from_pool && (in->flags & CSV_RB_RANK_FROM_NAMES) != 0;
     if ((in->flags & CSV_RB_RANK_FROM_NAMES) && !from_pool) return fail(c, CSV_E_INVALID, "CSV_RB_RANK_FROM_NAMES needs CSV_RB_FROM_POOL");
     if (from_pool && ((!by_name && (!in->read_rank || in->n_rank <= 0)) || !in->seg_aux_major)) return fail(c, CSV_E_INVALID, "CSV_RB_FROM_POOL needs read_rank");
+    // CSV_RB_TIES_FROM_SEQS: the INS tie groups are settled from the context's sequence pool instead of by the caller
+    const bool ties_from_seqs = (in->flags & CSV_RB_TIES_FROM_SEQS) != 0;
+    if (ties_from_seqs && (!from_pool || !in->seg_nodedup || in->tie_order))
+        return fail(c, CSV_E_INVALID, "CSV_RB_TIES_FROM_SEQS needs CSV_RB_FROM_POOL and seg_nodedup, and excludes tie_order");
+    const bool want_ties = (in->tie_order || ties_from_seqs) && in->seg_nodedup;
     if (n == 0) return CSV_OK;
     if (by_name) {
         if (c->nm.n == 0) return fail(c, CSV_E_INVALID, "CSV_RB_RANK_FROM_NAMES: the name pool is empty");
@@ -36,7 +41,7 @@ int csv_rebuild_signatures(csv_ctx* c, const csv_rebuild_in* in, csv_rebuild_out
     P.add(rb.oseg, n * 4); P.add(rb.oa, n * 8); P.add(rb.ob, n * 8); P.add(rb.orid, n * 4); P.add(rb.oaux, n * 4); P.add(rb.osrc, n * 4); P.add(rb.segcnt, ((size_t)in->n_seg + 2) * 8);
     if (from_pool && !by_name) P.add(rb.rank, (size_t)in->n_rank * 4);
     P.add(rb.mx, 64);
-    if (in->tie_order && in->seg_nodedup) P.add(rb.drop, n + 64);
+    if (want_ties) P.add(rb.drop, n + 64);
     TRY(commit_synced(c, c->scratch, P));
     hipStream_t st = c->stream;
     TRY(h2d(c, rb.major, in->seg_aux_major, in->n_seg));
@@ -83,7 +88,7 @@ int csv_rebuild_signatures(csv_ctx* c, const csv_rebuild_in* in, csv_rebuild_out
     out->n_tie_rows = 0; out->n_tie_dropped = 0;
     bool ties_settled = false;
     int npass = 0;
-    // the tie groups' round trip to the caller (csv_tie_order_fn): `lst` = {position | continues << 31, source row}, any order
+    // the tie groups' round trip to the caller (csv_tie_order_fn) or, CSV_RB_TIES_FROM_SEQS, to k_seq_tie_order: `lst` = {position | continues << 31, source row}, any order
     std::vector<int> tie_pos, tie_src; std::vector<uint8_t> tie_flag;
     auto ask_caller = [&](std::vector<int2>& lst) -> int {
         const int n_list = (int)lst.size();
@@ -97,8 +102,11 @@ int csv_rebuild_signatures(csv_ctx* c, const csv_rebuild_in* in, csv_rebuild_out
             tie_pos[k] = lst[k].x & 0x7fffffff; src[k] = lst[k].y;
         }
         goff.push_back(n_list);
-        const int rc = in->tie_order(in->tie_user, (int64_t)goff.size() - 1, goff.data(), src.data(), order.data(), drop.data());
-        if (rc != 0) return fail(c, CSV_E_INVALID, "tie_order returned %d", rc);
+        if (ties_from_seqs) TRY(seq_tie_order(c, (i64)goff.size() - 1, goff.data(), src.data(), n_list, order.data(), drop.data()));
+        else {
+            const int rc = in->tie_order(in->tie_user, (int64_t)goff.size() - 1, goff.data(), src.data(), order.data(), drop.data());
+            if (rc != 0) return fail(c, CSV_E_INVALID, "tie_order returned %d", rc);
+        }
         std::vector<uint8_t> seen((size_t)n_list, 0);
         int64_t dropped = 0;
         for (size_t g = 0; g + 1 < goff.size(); g++) {                            // order[] must be a permutation inside every group
@@ -155,7 +163,7 @@ int csv_rebuild_signatures(csv_ctx* c, const csv_rebuild_in* in, csv_rebuild_out
             RsTail T{};
             T.n = n; T.L = KL; T.nodedup = R.nodedup; T.drop = nullptr; T.partial = R.partial;
             T.o_seg = R.o_seg; T.o_a = R.o_a; T.o_b = R.o_b; T.o_rid = R.o_rid; T.o_aux = R.o_aux; T.o_src = R.o_src; T.n_out = R.n_out;
-            if (in->tie_order && R.nodedup) {
+            if (want_ties) {
                 TRY(settle_ties([&](int2* lst, int* d_n) { hipLaunchKernelGGL(k_rs_ties<W>, dim3(div_up(n, 256)), dim3(256), 0, st, T, (const E*)e_in, lst, d_n); },
                                 [&](int n_list) { hipLaunchKernelGGL(k_rs_tie_apply<W>, dim3(div_up(n_list, 256)), dim3(256), 0, st, n_list, dp<int>(rb.oseg), dp<int>(rb.orid),
                                                                      dp<uint8_t>(rb.ob), dp<int>(rb.aux), KL, (E*)e_in, dp<uint8_t>(rb.drop)); }));
@@ -173,7 +181,7 @@ int csv_rebuild_signatures(csv_ctx* c, const csv_rebuild_in* in, csv_rebuild_out
         const SortField fields[5] = {{rb.rid.p, 0, 0, nbytes((u64)mx_rid), ~0u}, {rb.b.p, 1, 0, nbytes((u64)mx_b), ~0u}, {rb.a.p, 1, 0, nbytes((u64)mx_a), ~0u},
                                      {rb.auxk.p, 0, 0, nbytes((u64)mx_aux), ~0u}, {rb.seg.p, 0, 0, nbytes((u64)mx_seg) > 0 ? nbytes((u64)mx_seg) : 1, ~0u}};
         R.perm = sort_passes(st, fields, 5, n, nunits, dp<int>(rb.perm0), dp<int>(rb.perm1), dp<int>(rb.hist), dp<int>(rb.tot), &npass);
-        if (in->tie_order && R.nodedup) {
+        if (want_ties) {
             TRY(settle_ties([&](int2* lst, int* d_n) { hipLaunchKernelGGL(k_rebuild_ties, dim3(div_up(n, 256)), dim3(256), 0, st, R, lst, d_n); },
                             [&](int n_list) { hipLaunchKernelGGL(k_rebuild_tie_apply, dim3(div_up(n_list, 256)), dim3(256), 0, st, n_list, dp<int>(rb.oseg), dp<int>(rb.orid),
                                                                  dp<uint8_t>(rb.ob), const_cast<int*>(R.perm), dp<uint8_t>(rb.drop)); }));

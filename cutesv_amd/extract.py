@@ -61,11 +61,41 @@ def _negotiate(fn, handle, cin, out_type, table, classes, give, check, what, lon
     raise RuntimeError("%s: capacity retry failed" % what)
 
 
+def upload_read_sequences(ctx, data, off, l_seq, want=None):
+    """csv_seq_reads_upload: the 4-bit sequences of the current batch's reads - read i = the (l_seq[i] + 1) // 2 bytes at
+    data[off[i]:], high nibble first (data: uint8 array or bytes; for a bam.Chunk: chunk.host and chunk.sequence_columns()) - go to
+    the device, where the calls with pool=dict(..., seqs=True) cut the INS rows' bases out of them.  want: per read, 0 = its bases
+    are not needed (and are not sent).  They stay until the next upload or bam.decode.  The library checks every range
+    (CsvError E_INVALID, nothing changes)."""
+    data = np.frombuffer(data, np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else np.ascontiguousarray(data, np.uint8)
+    off = np.ascontiguousarray(off, np.int64); l_seq = np.ascontiguousarray(l_seq, np.int32)
+    want = None if want is None else np.ascontiguousarray(want, np.uint8)
+    if len(off) != len(l_seq) or (want is not None and len(want) != len(off)):
+        raise ValueError("one offset, one length and (with `want`) one flag per read are expected")
+    n = len(off)
+    ctx._check(lib().csv_seq_reads_upload(ctx._h, n, data.ctypes.data if len(data) else None, len(data), off.ctypes.data if n else None,
+                                          l_seq.ctypes.data if n else None, None if want is None or not n else want.ctypes.data))
+
+
+def seq_option(ctx, whole_image):
+    """csv_seq_option(CSV_SEQ_OPT_WHOLE_IMAGE): a measurement aid - upload_read_sequences sends the image whole instead of packing
+    the wanted reads (scripts/ins_seq_stage.py compares the two)"""
+    ctx._check(lib().csv_seq_option(ctx._h, _abi.SEQ_OPT_WHOLE_IMAGE, 1 if whole_image else 0))
+
+
+def seq_info(ctx):
+    """figures of the context's last sequence upload and last seqs=True call (csv_seq_info)"""
+    o = _abi.SeqInfo()
+    ctx._check(lib().csv_seq_info_get(ctx._h, C.byref(o)))
+    return {k: getattr(o, k) for k, _ in _abi.SeqInfo._fields_ if k != "reserved"}
+
+
 def _to_pool(cin, pool):
-    """CSV_CG_TO_POOL on a csv_cigar_in / csv_split_in: the results also become rows of the context's pool.
+    """CSV_CG_TO_POOL on a csv_cigar_in / csv_split_in: the results also become rows of the context's pool; with seqs=True the INS
+    rows' bases go to its sequence pool (CSV_CG_SEQ_TO_POOL).
     -> the converted query_len column (or None): the caller holds it until the call has returned"""
     qlen = None if pool.get("query_len") is None else np.ascontiguousarray(pool["query_len"], np.int32)
-    cin.flags |= _abi.CG_TO_POOL
+    cin.flags |= _abi.CG_TO_POOL | (_abi.CG_SEQ_TO_POOL if pool.get("seqs") else 0)
     cin.read_base = int(pool["read_base"])
     cin.query_len = None if qlen is None else qlen.ctypes.data
     return qlen
@@ -100,10 +130,12 @@ def _run(fn, handle, cig_off, cigar, ref_start, use, min_siglength, merge_ins_th
 def cigar_signatures(ctx, cig_off, cigar, ref_start, use=None, min_siglength=10, merge_ins_threshold=100, merge_del_threshold=0, pool=None, host_outputs=True,
                      from_bam=None):
     """flat CIGARs of a batch of reads -> dict of the signature arrays of csv_cigar_out (defaults: cuteSV_Description.py:123-152).
-    pool = dict(seg_ins, seg_del, read_base, query_len=None): the signatures ALSO become rows of the context's device-resident
+    pool = dict(seg_ins, seg_del, read_base, query_len=None, seqs=False): the signatures ALSO become rows of the context's device-resident
     pool (CSV_CG_TO_POOL; INS rows in segment seg_ins, DEL rows in seg_del, read index = read_base + index in this batch), in the
     order INS then DEL - what `rebuild.rebuild_pool` sorts without the rows ever crossing PCIe; host_outputs=False (with a pool):
-    the arrays of the result stay empty, only the counts come back.
+    the arrays of the result stay empty, only the counts come back.  seqs=True: the INS rows' inserted bases are cut out of the
+    sequences `upload_read_sequences` left on the device (one per read of this batch; query_len must be their l_seq) into the
+    context's sequence pool (`rebuild.seq_pool_get`).
     from_bam = the columns `bam.decode(ctx, chunk)` returned: cig_off / cigar / ref_start are not taken from the arguments (pass
     None) but scanned where that decode left them on the device (CSV_CG_FROM_BAM); `use` is still the caller's."""
     return _run(lib().csv_cigar_signatures, ctx._h, cig_off, cigar, ref_start, use, min_siglength, merge_ins_threshold, merge_del_threshold, ctx._check, pool=pool,
@@ -284,6 +316,11 @@ def _run_split(fn, handle, enc, sv_size, min_mapq, max_split_parts, max_size, ch
     if pool is not None:                                  # the candidates also become rows of the context's pool
         qlen = _to_pool(sin, pool)
         sin.pool_seg_base = (C.c_int32 * 5)(*[int(x) for x in pool["seg_base"]])
+        if pool.get("seqs") and from_bam is None:         # the strand of every read, beside the uploaded sequences (from_bam: the decode's flags)
+            rev = np.zeros(n, np.uint8) if pool.get("query_reverse") is None else np.ascontiguousarray(pool["query_reverse"], np.uint8)
+            if len(rev) != n:
+                raise ValueError("query_reverse: one entry per read is expected")
+            check(lib().csv_seq_query_reverse(handle, n, rev.ctypes.data if n else None))
     to_host = host_outputs or pool is None                # (pool only: nothing but the count comes back; no entry yields more than 12 candidates)
     out, sout = _negotiate(fn, handle, sin, SplitOut, _SPLIT_OUT, dict(n=("cap", "n", max(16, 2 * n) if to_host else 12 * n_ent, 1)),
                            [name for name, _, _ in _SPLIT_OUT] if to_host else (), check, "csv_split_signatures")
@@ -296,12 +333,16 @@ def _run_split(fn, handle, enc, sv_size, min_mapq, max_split_parts, max_size, ch
 def split_signatures(ctx, enc, sv_size=30, min_mapq=20, max_split_parts=7, max_size=100000, pool=None, from_bam=None, host_outputs=True):
     """flat split-read entries of a batch of reads (encode_split_reads) -> dict of the candidate arrays of csv_split_out
     (defaults: cuteSV_Description.py: --min_size 30, --min_mapq 20, --max_split_parts 7, --max_size 100000).
-    pool = dict(seg_base=[segment of chromosome rank 0 for kind DEL, INS, DUP, INV, TRA], read_base, query_len=None): the
-    candidates ALSO become rows of the context's device-resident pool (`pool_rows_of_split` is the same mapping on the host);
-    host_outputs=False (with a pool): the arrays of the result stay empty and the result gains the key `n`, the number of candidates.
+    pool = dict(seg_base=[segment of chromosome rank 0 for kind DEL, INS, DUP, INV, TRA], read_base, query_len=None, seqs=False,
+    query_reverse=None): the candidates ALSO become rows of the context's device-resident pool (`pool_rows_of_split` is the same
+    mapping on the host); host_outputs=False (with a pool): the arrays of the result stay empty and the result gains the key `n`,
+    the number of candidates.  seqs=True: the INS candidates' bases and x.5 flags go to the context's sequence pool, cut out of the
+    sequences `upload_read_sequences` left on the device (one per read of `enc`); query_reverse[r] = 1: read r's record has flag 16,
+    so the query parse_read analyses is the reverse complement of the uploaded sequence (None: no read is reversed).
     from_bam = the dict `split_inputs_bam` returned (pass enc=None): the reads are its calls and the entry columns are read where
     it left them on the device (CSV_SP_FROM_BAM); the result's `read` is the call index, a pool row's read index is
-    read_base + call_rec[call] and the pool's query_len is the decode's."""
+    read_base + call_rec[call] and the pool's query_len is the decode's; with seqs=True the uploaded sequences are the chunk's
+    records' and the strands are the decode's flags."""
     return _run_split(lib().csv_split_signatures, ctx._h, enc, sv_size, min_mapq, max_split_parts, max_size, ctx._check, pool=pool, from_bam=from_bam,
                       host_outputs=host_outputs)
 
@@ -346,6 +387,38 @@ def split_candidates(sig, read_names, queries, chrom_names):
         else:
             cand["TRA"].append(("ABCD"[aux], a, chrom_names[c], b, name, "TRA", chrom))
     return cand
+
+
+def pool_ins_sequences_host(queries, query_reverse, sig, ssig, call_read=None):
+    """What the sequence pool holds for the INS rows a batch appends, on the host: -> [(bytes, half)] in pool order, the CIGAR
+    scan's INS signatures `sig` first, then the kind-1 candidates of the split analysis `ssig` (either may be None).  queries[r]:
+    the STORED sequence of read r (str or bytes, as the BAM record has it); query_reverse[r]: the record's flag is 16 (None: no
+    read is); call_read[k]: the read of split-read call k (None: the call index is the read index).  CIGAR rows: the pieces
+    query[qoff : qoff + len] (extract.candidates).  Split rows: q[c:d] as split_candidates cuts it - q the stored sequence or,
+    reversed read, its reverse complement, reverse-complemented once more when aux bit 0 is set - as Python slices; half = aux
+    bit 1 and an odd position numerator.  The CPU checker of seqs.hip.h, like name_ranks_host and decode_host."""
+    text = lambda q: q.decode() if isinstance(q, (bytes, bytearray)) else str(q)      # noqa: E731
+    out = []
+    if sig is not None:
+        qo, ql = sig["piece_qoff"].tolist(), sig["piece_len"].tolist()
+        for r, p0, npc in zip(sig["ins_read"].tolist(), sig["ins_piece0"].tolist(), sig["ins_npiece"].tolist()):
+            q = text(queries[r])
+            out.append(("".join(q[qo[p]:qo[p] + ql[p]] for p in range(p0, p0 + npc)).encode(), 0))
+    if ssig is not None:
+        flipped = {}
+        for kind, k, aux, a, c, d in zip(ssig["kind"].tolist(), ssig["read"].tolist(), ssig["aux"].tolist(), ssig["a"].tolist(), ssig["c"].tolist(), ssig["d"].tolist()):
+            if kind != 1:
+                continue
+            r = k if call_read is None else int(call_read[k])
+            rev = bool(query_reverse[r]) if query_reverse is not None else False
+            if rev != bool(aux & 1):
+                if r not in flipped:
+                    flipped[r] = text(queries[r]).translate(_COMP)[::-1]
+                q = flipped[r]
+            else:
+                q = text(queries[r])
+            out.append((q[c:d].encode(), 1 if (aux & 2) and (a & 1) else 0))
+    return out
 
 
 # ------------------------------------------------------------------------------------ parse_read for a batch of reads
@@ -584,7 +657,7 @@ def _assemble_device(ctx, chunk, cols, sig, names, seqs, sel, chrom, chrom_rank,
 
 # ------------------------------------------------------------------------------------ a task's region -> rows of the pool
 def task_to_pool(ctx, bamfile, chrom, task_start, task_end, chrom_rank, sv_size, min_mapq, max_split_parts, min_read_len, min_siglength,
-                 merge_del_threshold, merge_ins_threshold, max_size, seg_ins, seg_del, seg_base, read_base, bed_regions=None, name_pool=False):
+                 merge_del_threshold, merge_ins_threshold, max_size, seg_ins, seg_del, seg_base, read_base, bed_regions=None, name_pool=False, seq_pool=False):
     """The body of an extraction task without a candidate tuple, a name string or a sequence: the records of the region
     (`bamfile.records`) are decoded on the device, the CIGAR scan appends its signatures to the context's pool from the decoded
     columns (CSV_CG_FROM_BAM | CSV_CG_TO_POOL), the SA tags are parsed there (split_inputs_bam) and the split-read analysis appends
@@ -601,7 +674,13 @@ def task_to_pool(ctx, bamfile, chrom, task_start, task_end, chrom_rank, sv_size,
     decode, so that a row's read index IS its name's index: read_base must equal the name pool's row count (ValueError before
     anything is appended) or be None to take it.  The result gains name_base (= that read_base); with `ranks` =
     rebuild.name_ranks(ctx)["rank"] the read ids of the task's reads-table rows are ranks[name_base + reads_index], the id
-    space of rebuild.rebuild_pool_by_name's read_id column."""
+    space of rebuild.rebuild_pool_by_name's read_id column.
+
+    seq_pool=True: the 4-bit sequences of the records the scans look at (use | sel) are uploaded out of the chunk's host image
+    (upload_read_sequences) and both calls run with seqs=True: every INS row gets its inserted bases and its x.5 flag in the
+    context's sequence pool, cut on the device.  The INS rows of flagged calls get theirs through rebuild.seq_pool_put, cut on
+    the host as single_pipe_bam cuts them.  The pool rows are the same either way; the result gains n_seq_rows / n_seq_bytes
+    (the sequence pool's counts after the task)."""
     from . import bam as bam_mod, rebuild
     if name_pool:
         n_names = rebuild.name_pool_rows(ctx)
@@ -617,18 +696,29 @@ def task_to_pool(ctx, bamfile, chrom, task_start, task_end, chrom_rank, sv_size,
         rebuild.name_pool_append_chunk(ctx, chunk)
     start, end, mapq, qlen = cols["ref_start"], cols["ref_end"], cols["mapq"], cols["query_len"]
     gate, _, use, sel = _gates(cols, task_start, bed_regions, min_read_len, min_mapq)
+    if seq_pool:
+        s_off, l_seq = chunk.sequence_columns()
+        upload_read_sequences(ctx, chunk.host, s_off, l_seq, want=(use != 0) | sel)
     sig = cigar_signatures(ctx, None, None, None, use, min_siglength=min_siglength, merge_ins_threshold=merge_ins_threshold, merge_del_threshold=merge_del_threshold,
-                           pool=dict(seg_ins=seg_ins, seg_del=seg_del, read_base=read_base, query_len=qlen), host_outputs=False, from_bam=cols)
+                           pool=dict(seg_ins=seg_ins, seg_del=seg_del, read_base=read_base, query_len=qlen, seqs=seq_pool), host_outputs=False, from_bam=cols)
     si, dsig, calls, reads, fsig = _split_on_device(ctx, chunk, cols, sel, chrom, chrom_rank, min_mapq,
                                                     dict(sv_size=sv_size, min_mapq=min_mapq, max_split_parts=max_split_parts, max_size=max_size),
-                                                    pool=dict(seg_base=seg_base, read_base=read_base))
+                                                    pool=dict(seg_base=seg_base, read_base=read_base, seqs=seq_pool))
     n_split, n_host = 0 if dsig is None else dsig["n"], 0
     if fsig is not None:
         rows = pool_rows_of_split(fsig, seg_base, 0, [r[2] for r in reads])
-        rebuild.pool_append(ctx, rows["seg"], rows["a"], rows["b"], read_base + si["call_rec"][calls][fsig["read"]], rows["aux"])
+        first_row = rebuild.pool_rows(ctx)
+        rec = si["call_rec"][calls]                          # the record of every flagged call
+        rebuild.pool_append(ctx, rows["seg"], rows["a"], rows["b"], read_base + rec[fsig["read"]], rows["aux"])
         n_host = len(fsig["kind"])
+        ins = np.flatnonzero(fsig["kind"] == 1)
+        if seq_pool and len(ins):                             # their INS rows: cut on the host, as single_pipe_bam does
+            cut = pool_ins_sequences_host(_Lazy(chunk.sequence), cols["flag"] == 16, None, fsig, call_read=rec)
+            rebuild.seq_pool_put(ctx, first_row + ins, [b for b, _ in cut], [h for _, h in cut])
     keep = np.flatnonzero(gate & (mapq >= min_mapq))
     extra = dict(name_base=read_base) if name_pool else {}
+    if seq_pool:
+        extra["n_seq_rows"], extra["n_seq_bytes"] = rebuild.seq_pool_rows(ctx)
     return dict(**extra, n_records=chunk.n, n_sig_ins=sig["n_sig_ins"], n_sig_del=sig["n_sig_del"], n_calls=si["n_calls"], n_entries=si["n_entries"], n_split=n_split,
                 n_split_host=n_host, n_flagged=si["n_flagged"], flagged_calls=calls, flagged_records=si["call_rec"][calls],
                 reads_start=start[keep], reads_end=end[keep], reads_primary=(cols["cls"][keep] == 1).astype(np.uint8), reads_index=keep)

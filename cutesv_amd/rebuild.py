@@ -61,10 +61,20 @@ def rebuild_columns(ctx, seg_id, a, b, read_id, aux, seg_aux_major, seg_nodedup=
     return _rebuild(ctx, n, dict(seg_id=seg_id, a=a, b=b, read_id=read_id, aux=aux), None, seg_aux_major, seg_nodedup, keep_on_device, tie_order, src_row_out)
 
 
-def _rebuild(ctx, n_out, cols, read_rank, seg_aux_major, seg_nodedup, keep_on_device, tie_order, src_row_out=None):
+def _check_ties(ties, from_pool, seg_nodedup, tie_order):
+    """the argument rules of ties="seqs" (CSV_RB_TIES_FROM_SEQS), before anything is asked of the context"""
+    if ties not in (None, "seqs"):
+        raise ValueError("ties must be None or 'seqs', not %r" % (ties,))
+    if ties == "seqs" and (not from_pool or seg_nodedup is None or tie_order is not None):
+        raise ValueError("ties='seqs' settles the tie groups of the pool's keep-every-row segments from the sequence pool: it needs the pool and "
+                         "seg_nodedup, and excludes tie_order")
+
+
+def _rebuild(ctx, n_out, cols, read_rank, seg_aux_major, seg_nodedup, keep_on_device, tie_order, src_row_out=None, ties=None):
     """The one csv_rebuild_signatures call: over the caller's columns `cols` (converted to the ABI's widths), or, cols=None, over
     the context's pool with its read indices replaced through `read_rank` (None: through the ranks of the context's name pool,
-    CSV_RB_RANK_FROM_NAMES).  n_out: rows the result arrays must hold."""
+    CSV_RB_RANK_FROM_NAMES).  n_out: rows the result arrays must hold.  ties="seqs" (pool only): CSV_RB_TIES_FROM_SEQS."""
+    _check_ties(ties, cols is None, seg_nodedup, tie_order)
     major = np.ascontiguousarray(seg_aux_major, np.uint8)
     nodedup = None if seg_nodedup is None else np.ascontiguousarray(seg_nodedup, np.uint8)
     rank = None if read_rank is None else np.ascontiguousarray(read_rank, np.int32)
@@ -77,7 +87,7 @@ def _rebuild(ctx, n_out, cols, read_rank, seg_aux_major, seg_nodedup, keep_on_de
     rin = RebuildIn(n_seg=len(major), flags=_abi.RB_KEEP_ON_DEVICE if keep_on_device else 0, seg_aux_major=major.ctypes.data,
                     seg_nodedup=None if nodedup is None else nodedup.ctypes.data, tie_order=None if tie_order is None else C.cast(tie_order, C.c_void_p))
     if cols is None:
-        rin.flags |= _abi.RB_FROM_POOL
+        rin.flags |= _abi.RB_FROM_POOL | (_abi.RB_TIES_FROM_SEQS if ties == "seqs" else 0)
         if rank is None:                                  # (the ranks of the context's name pool, on the device already)
             rin.flags |= _abi.RB_RANK_FROM_NAMES
         else:
@@ -239,12 +249,65 @@ def pool_append(ctx, seg_id, a, b, read, aux):
     ctx._check(lib().csv_pool_append(ctx._h, len(a), seg_id.ctypes.data, a.ctypes.data, b.ctypes.data, read.ctypes.data, aux.ctypes.data))
 
 
-def rebuild_pool(ctx, read_rank, seg_aux_major, seg_nodedup=None, keep_on_device=True, tie_order=None):
+def seq_pool_rows(ctx):
+    """-> (pool rows that hold a sequence, bytes of the sequence pool's blob)"""
+    n, b = C.c_int64(0), C.c_int64(0)
+    ctx._check(lib().csv_seq_pool_rows(ctx._h, C.byref(n), C.byref(b)))
+    return int(n.value), int(b.value)
+
+
+def seq_pool_put(ctx, rows, seqs, half=None):
+    """csv_seq_pool_put: host-made sequences (str or bytes, one per entry of `rows`) and their x.5 flags for EXISTING pool rows -
+    the INS rows appended with pool_append.  A sequence's length must be its row's aux, and a row takes one sequence only
+    (CsvError E_INVALID, nothing changes)."""
+    rows = np.ascontiguousarray(rows, np.int32)
+    raw = [s.encode() if isinstance(s, str) else bytes(s) for s in seqs]
+    if len(raw) != len(rows) or (half is not None and len(half) != len(rows)):
+        raise ValueError("one sequence and (with `half`) one flag per row are expected")
+    n = len(rows)
+    length = np.fromiter((len(s) for s in raw), np.int32, n)
+    off = np.zeros(n, np.int64)
+    if n:
+        np.cumsum(length[:-1], out=off[1:])
+    blob = np.frombuffer(b"".join(raw), np.uint8)
+    hv = None if half is None else np.ascontiguousarray(half, np.uint8)
+    ctx._check(lib().csv_seq_pool_put(ctx._h, n, rows.ctypes.data if n else None, blob.ctypes.data if len(blob) else None, len(blob), off.ctypes.data if n else None,
+                                      length.ctypes.data if n else None, None if hv is None or not n else hv.ctypes.data))
+
+
+def seq_pool_get(ctx, rows, raw=False):
+    """csv_seq_pool_get: the inserted bases of the pool rows `rows` (gathered on the device) -> list of str (raw=True: of bytes).
+    A row without a sequence fails the call (CsvError E_INVALID)."""
+    rows = np.ascontiguousarray(rows, np.int32)
+    n = len(rows)
+    off = np.zeros(n + 1, np.int64)
+    out = np.empty(1, np.uint8)
+    rc = lib().csv_seq_pool_get(ctx._h, n, rows.ctypes.data if n else None, out.ctypes.data, 0, off.ctypes.data)
+    if rc == _abi.E_CAPACITY:                             # (the lengths live on the device: the first call reports the need)
+        out = np.empty(int(off[-1]), np.uint8)
+        rc = lib().csv_seq_pool_get(ctx._h, n, rows.ctypes.data, out.ctypes.data, len(out), off.ctypes.data)
+    ctx._check(rc)
+    blob, o = out[:int(off[-1])].tobytes(), off.tolist()
+    seqs = [blob[o[k]:o[k + 1]] for k in range(n)]
+    return seqs if raw else [x.decode() for x in seqs]
+
+
+def seq_pool_half(ctx, rows):
+    """the x.5 flags of the pool rows `rows` (0 for a row without a sequence) -> uint8 array"""
+    rows = np.ascontiguousarray(rows, np.int32)
+    out = np.zeros(len(rows), np.uint8)
+    ctx._check(lib().csv_seq_pool_half(ctx._h, len(rows), rows.ctypes.data if len(rows) else None, out.ctypes.data if len(rows) else None))
+    return out
+
+
+def rebuild_pool(ctx, read_rank, seg_aux_major, seg_nodedup=None, keep_on_device=True, tie_order=None, ties=None):
     """csv_rebuild_signatures over the context's pool (CSV_RB_FROM_POOL): the rows the extraction kernels left on the device
     (extract.cigar_signatures(pool=...)) and those appended with pool_append, sorted and de-duplicated; a row's read index is
     replaced by read_rank[index] (rank of the read's name in Python string order).  Same result dict as rebuild_columns;
-    src_row numbers the pool's rows (extraction order)."""
-    return _rebuild(ctx, pool_rows(ctx), None, read_rank, seg_aux_major, seg_nodedup, keep_on_device, tie_order)
+    src_row numbers the pool's rows (extraction order).  ties="seqs": the INS tie groups are settled on the device from the
+    context's sequence pool under tie_callback's contract (CSV_RB_TIES_FROM_SEQS; needs seg_nodedup, excludes tie_order)."""
+    _check_ties(ties, True, seg_nodedup, tie_order)
+    return _rebuild(ctx, pool_rows(ctx), None, read_rank, seg_aux_major, seg_nodedup, keep_on_device, tie_order, ties=ties)
 
 
 # ------------------------------------------------------------------------------------ the device-resident name pool
@@ -322,11 +385,13 @@ def name_ranks_host(data, off, length):
     return rank.astype(np.int32).ravel(), first.astype(np.int32)
 
 
-def rebuild_pool_by_name(ctx, seg_aux_major, seg_nodedup=None, keep_on_device=True, tie_order=None):
+def rebuild_pool_by_name(ctx, seg_aux_major, seg_nodedup=None, keep_on_device=True, tie_order=None, ties=None):
     """rebuild_pool with a row's read index replaced by the rank of that index in the context's NAME pool
     (CSV_RB_FROM_POOL | CSV_RB_RANK_FROM_NAMES): the ranks are computed on the device when an append made them stale and never
-    visit the host.  A pool row whose read index has no name fails the call (CsvError E_INVALID).  Same result dict."""
-    return _rebuild(ctx, pool_rows(ctx), None, None, seg_aux_major, seg_nodedup, keep_on_device, tie_order)
+    visit the host.  A pool row whose read index has no name fails the call (CsvError E_INVALID).  Same result dict; ties="seqs" as
+    in rebuild_pool."""
+    _check_ties(ties, True, seg_nodedup, tie_order)
+    return _rebuild(ctx, pool_rows(ctx), None, None, seg_aux_major, seg_nodedup, keep_on_device, tie_order, ties=ties)
 
 
 def finish_ins_ties(r, ins_segs, seq_of_src, half_of_src):

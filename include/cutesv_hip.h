@@ -364,10 +364,18 @@ enum {
                                         aux of csv_rebuild_in are ignored; a row's read index is replaced by read_rank[index] (the
                                         rank of the read's NAME: string order is the caller's business, or the library's with
                                         CSV_RB_RANK_FROM_NAMES below); src_row numbers pool rows */
-    CSV_RB_RANK_FROM_NAMES = 4       /* with CSV_RB_FROM_POOL: read_rank / n_rank are ignored; a row's read index is replaced by the rank
+    CSV_RB_RANK_FROM_NAMES = 4,      /* with CSV_RB_FROM_POOL: read_rank / n_rank are ignored; a row's read index is replaced by the rank
                                         of that index in the context's NAME pool (csv_name_ranks below; computed first when an append
                                         made the cached ranks stale).  A row whose read index is >= the name count fails the call with
                                         CSV_E_INVALID, like every other row the sort cannot take; the context stays usable */
+    CSV_RB_TIES_FROM_SEQS = 8        /* with CSV_RB_FROM_POOL and seg_nodedup, without tie_order (CSV_E_INVALID otherwise): the tie groups of
+                                        the keep-every-row segments are settled on the device from the context's sequence pool
+                                        (csv_seq_pool_* below) under exactly the contract of csv_tie_order_fn as extract's INS rows
+                                        need it - inside a group rows order by sequence (unsigned bytes, a prefix first, equal
+                                        sequences in input order) and a row is dropped when the row before it in that order has the
+                                        same sequence and the same x.5 flag.  Only the groups' row numbers and the answer cross the
+                                        link; n_tie_rows / n_tie_dropped are filled as with the callback.  A group row without a
+                                        sequence fails the call with CSV_E_INVALID; the context stays usable */
 };
 /* The rows of the keep-every-row segments (seg_nodedup) whose integer keys tie - (segment, a, b, read_id) equal - are ordered
  * by data only the caller has: the reference sorts INS rows by (chr, int(pos), len, read, SEQUENCE) and drops a row only when
@@ -479,6 +487,60 @@ int csv_name_pool_get(csv_ctx* ctx, int64_t n, const int32_t* index, char* out, 
 /* sizeof of 0 csv_name_rank_out; 0 otherwise */
 size_t csv_name_struct_size(int which);
 
+/* The device-resident INS sequence pool (seqs.hip.h): beside every INS row of the signature pool its
+ * inserted bases (ASCII) and the x.5 flag of a split-read position - the fourth element of the reference's INS tuple (MAIN:537,
+ * :639-640, :228) - made where the rows are made, compared there for the rebuild (CSV_RB_TIES_FROM_SEQS) and returned by pool row.
+ *
+ * csv_seq_reads_upload: the sequences of the current batch's reads in the BAM 4-bit encoding - read i = (l_seq[i] + 1) / 2 bytes
+ *   at bytes + off[i], high nibble first, code -> "=ACMGRSVTWYHKDBN".  This is the strided form of a csv_bam_chunk's host image
+ *   (bytes = host, off = host_off + l_read_name).  want: n_reads bytes or NULL; want[i] = 0: read i's bases are not needed and
+ *   not sent.  Every range is checked against n_bytes before anything is launched (CSV_E_INVALID, state unchanged).  The wanted
+ *   reads are packed back to back on the host and cross the link once.  Index space: the batch's read index (what is added to
+ *   read_base).  The bases live in a buffer of their own until the next upload or the next csv_bam_decode.
+ * csv_seq_query_reverse: for a csv_split_signatures call WITHOUT CSV_SP_FROM_BAM, per read of the last upload 1 when the record's
+ *   flag is 16 - the query parse_read hands on is then the reverse complement of the stored sequence (MAIN:673-675).
+ * CSV_CG_SEQ_TO_POOL (csv_cigar_in.flags and csv_split_in.flags, only with CSV_CG_TO_POOL): the INS rows the call appends get
+ *   their bases.  CIGAR scan: the pieces query[qoff : qoff + len], each clipped to the read like a Python slice, concatenated.
+ *   Split analysis (kind 1): q[c:d], clipped likewise, q = the stored sequence (flag != 16) or its reverse complement (flag == 16;
+ *   CSV_SP_FROM_BAM: the decode's flag of the call's record), reverse-complemented once more when aux bit 0 is set; the
+ *   complement is A <-> T, C <-> G, everything else unchanged; x.5 flag = aux bit 1 AND the low bit of a.  The length of a row's
+ *   bases equals its aux (query_len, when given, must be the uploaded l_seq; NULL in csv_cigar_in: l_seq is used).  A row whose
+ *   read has no uploaded sequence, a negative slice bound or a length that is not the row's aux fails the call with
+ *   CSV_E_INVALID: the pool and the sequence pool keep their row counts.
+ * csv_seq_pool_rows: INS rows that hold a sequence, bytes of the blob.  csv_pool_reset empties the sequence pool, too.
+ * csv_seq_pool_put: host-made ASCII sequences for EXISTING pool rows (the INS rows a caller appended with csv_pool_append):
+ *   sequence k = bytes[off[k] .. off[k] + len[k]), half[k] (NULL: 0) its x.5 flag.  A row out of range, named twice or with a
+ *   sequence already, or len[k] != the row's aux: CSV_E_INVALID and nothing changes.
+ * csv_seq_pool_get: the bases of pool_row[0 .. n) gathered into one blob on the device (one wavefront per row) and downloaded:
+ *   row k = out[out_off[k] .. out_off[k + 1]).  CSV_E_CAPACITY: cap is too small, out_off[n] holds the need.  CSV_E_INVALID: a row
+ *   out of range or without a sequence.  csv_seq_pool_half: the rows' x.5 flags (0 for a row without a sequence). */
+typedef struct csv_seq_info {
+    int64_t reads_uploaded;         /* of the last csv_seq_reads_upload: wanted reads, bytes that crossed the link */
+    int64_t bytes_uploaded;
+    int64_t rows_gathered;          /* of the last CSV_CG_SEQ_TO_POOL call: rows that got bases, their bytes */
+    int64_t bytes_gathered;
+    float   ms_upload;              /* host wall time of the last upload: packing, copies, wait */
+    float   ms_gather;              /* kernels of the last CSV_CG_SEQ_TO_POOL call: lengths, scan, gather (HIP events) */
+    int32_t packed;                 /* 1: the wanted reads were packed before the copy */
+    int32_t reserved;
+    int64_t device_bytes;           /* device memory the sequence pool holds now: uploaded reads, blob, row arrays, per-call scratch */
+} csv_seq_info;
+
+int csv_seq_reads_upload(csv_ctx* ctx, int64_t n_reads, const uint8_t* bytes, int64_t n_bytes, const int64_t* off, const int32_t* l_seq, const uint8_t* want);
+/* CSV_SEQ_OPT_WHOLE_IMAGE (a measurement aid, per context, default 0): value 1 makes csv_seq_reads_upload send `bytes` whole instead of
+ * packing the wanted reads first - the form scripts/ins_seq_stage.py times against the packed one; results are
+ * the same either way. */
+enum { CSV_SEQ_OPT_WHOLE_IMAGE = 1 };
+int csv_seq_option(csv_ctx* ctx, int which, int value);
+int csv_seq_query_reverse(csv_ctx* ctx, int64_t n_reads, const uint8_t* reverse);
+int csv_seq_pool_rows(const csv_ctx* ctx, int64_t* n_with_seq, int64_t* n_bytes);
+int csv_seq_pool_put(csv_ctx* ctx, int64_t n, const int32_t* pool_row, const uint8_t* bytes, int64_t n_bytes, const int64_t* off, const int32_t* len, const uint8_t* half);
+int csv_seq_pool_get(csv_ctx* ctx, int64_t n, const int32_t* pool_row, char* out, int64_t cap, int64_t* out_off /* n + 1 */);
+int csv_seq_pool_half(csv_ctx* ctx, int64_t n, const int32_t* pool_row, uint8_t* half);
+int csv_seq_info_get(const csv_ctx* ctx, csv_seq_info* out);
+/* sizeof of 0 csv_seq_info; -1 past the end */
+int csv_seq_struct_size(int which);
+
 /* ---------------------------------------------------------------------------------------------
  * The CIGAR scan of the extraction step on the GPU.  Restates the CIGAR part of parse_read
  * (cuteSV main script :606-655: every I / D operation of at least min_siglength bases is a piece at the reference position
@@ -513,7 +575,10 @@ typedef struct csv_cigar_in {
 enum { CSV_CG_TO_POOL = 1,
        /* cig_off, cigar and ref_start are NOT read from `in`: they are the device columns the context's last csv_bam_decode
         * made (n_reads must be its record count).  `use` is still the caller's host array.  The CIGARs never cross PCIe. */
-       CSV_CG_FROM_BAM = 2 };
+       CSV_CG_FROM_BAM = 2,
+       /* only with CSV_CG_TO_POOL, in csv_cigar_in.flags and csv_split_in.flags alike (there 4 is CSV_SP_FROM_BAM): the INS rows'
+        * bases go to the context's sequence pool (csv_seq_* above) */
+       CSV_CG_SEQ_TO_POOL = 8 };
 
 typedef struct csv_cigar_out {
     int64_t  cap_sig_ins, cap_piece_ins, cap_sig_del;
@@ -567,7 +632,7 @@ typedef struct csv_split_in {
      * query_len[read] - NULL: read_len - like a Python slice), (pos1, pos2) for DUP, aux = strand code for INV, aux = chr2 * 8 +
      * type for TRA; read index = read_base + the read's index in this batch.  Output arrays of csv_split_out that are NULL are
      * then not written. */
-    int32_t         flags;          /* CSV_CG_TO_POOL, CSV_SP_FROM_BAM */
+    int32_t         flags;          /* CSV_CG_TO_POOL, CSV_SP_FROM_BAM, CSV_CG_SEQ_TO_POOL */
     int32_t         pool_seg_base[5];
     int64_t         read_base;
     const int32_t*  query_len;      /* n_reads or NULL */
