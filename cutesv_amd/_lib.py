@@ -60,6 +60,8 @@ SYMBOLS = [
     ("csv_seq_pool_half", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     ("csv_seq_info_get", C.c_int, [C.c_void_p, C.POINTER(_abi.SeqInfo)]),
     ("csv_seq_struct_size", C.c_int, [C.c_int]),
+    ("csv_seq_alt_gather", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),
+    ("csv_name_support_join", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     ("csv_vcf_emit", C.c_int, [C.POINTER(_abi.VcfIn), C.c_char_p, C.c_int64, C.POINTER(C.c_int64), C.c_void_p]),
     ("csv_bam_open", C.c_int, [C.c_char_p, C.c_int, C.POINTER(C.c_void_p), C.c_char_p, C.c_int]),
     ("csv_bam_close", None, [C.c_void_p]),

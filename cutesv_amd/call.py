@@ -1,0 +1,205 @@
+"""BAM -> VCF body in one call: the chain the earlier stages built, connected.
+
+    text, svid = call_bam("in.bam", fasta.Reference("ref.fa"), CallParams(Params.ont(min_support=3)))
+    python -m cutesv_amd.call in.bam ref.fa -o out.body.vcf [--genotype] [--report_readid] [--min_support N] [--batch B]
+
+Per task region the records are decoded, scanned and analysed on the device and their signatures, read names and inserted
+bases stay there (extract.task_to_pool with the name pool and the sequence pool); one rebuild sorts and de-duplicates the pool
+by read NAME with the INS tie groups settled from the sequences (rebuild.rebuild_pool_by_name, ties="seqs") and keeps the
+columns on the device; csv_cluster_batch clusters them in place; the ALT bases of the INS calls and - with report_readid - the
+RNAMES text are gathered on the device (rebuild.alt_gather / support_join) and handed to the native emitter as they are.
+Nothing here loops in Python over records, signatures or supports: only over tasks, segments and contigs.
+
+The text is the VCF BODY: the records of main script :1208-1237 in its order.  The header stays the driver's (DESIGN.md
+section 11)."""
+import dataclasses
+import os
+import time
+from dataclasses import dataclass, field
+
+import numpy as np
+
+from . import _abi
+from .columns import Params, TYPES, segment_record
+
+
+@dataclass
+class CallParams:
+    """resolve's Params plus the extraction gates of single_pipe (cuteSV_Description.py defaults): what call_bam needs to know"""
+    resolve: Params = field(default_factory=Params)
+    min_mapq: int = 20
+    max_split_parts: int = 7
+    min_read_len: int = 500
+    min_siglength: int = 10
+    merge_del_threshold: int = 0
+    merge_ins_threshold: int = 100
+
+    def pipe_args(self):
+        """the positional tail single_pipe_bam / task_to_pool take: sv_size .. max_size"""
+        return (self.resolve.min_size, self.min_mapq, self.max_split_parts, self.min_read_len, self.min_siglength, self.merge_del_threshold,
+                self.merge_ins_threshold, self.resolve.max_size)
+
+
+def cut_tasks(length, batch):
+    """the task regions of a contig of `length` bases with -b `batch`: [(start, end)] as main_ctrl cuts them - one task for a contig
+    shorter than the batch, else int(length / batch) full ones and the rest.  (The reference also shrinks the batch of a contig
+    that holds many reads, from the index statistics: a matter of load balance - the calls do not depend on the cut.)"""
+    if batch <= 0:
+        raise ValueError("batch must be positive")
+    if length < batch:
+        return [(0, length)]
+    tasks = [(k * batch, (k + 1) * batch) for k in range(length // batch)]
+    if tasks[-1][1] < length:
+        tasks.append((tasks[-1][1], length))
+    return tasks
+
+
+def tra_gt_mode(genotype):
+    """CUTESV_AMD_TRA_GT as call_bam honours it -> "reads_table" | "off"; "bam" (resolve's default) is refused: tra_bam reads the
+    BAM through pysam, not through bam.BamFile"""
+    mode = os.environ.get("CUTESV_AMD_TRA_GT", "bam") if genotype else "off"
+    if mode not in ("reads_table", "off"):
+        raise ValueError("call_bam genotypes TRA calls with CUTESV_AMD_TRA_GT=reads_table or leaves them with CUTESV_AMD_TRA_GT=off; %r is not available here "
+                         "(the BAM-based mode needs resolve.phase3 with bam=)" % (mode,))
+    return mode
+
+
+class _Shim:
+    """what vcf.emit_records reads of a store when the strings come with ins_alt= / rnames="""
+
+    def __init__(self, chroms, strands=("++", "--")):
+        self.chroms, self.strands = list(chroms), tuple(strands)
+
+
+def call_bam(bam, reference, params, ctx=None, chroms=None, batch=10_000_000, report_readid=False, ignore_sequence=False, threads=None, svid=None,
+             as_bytes=False, timings=None):
+    """-> (VCF body text, svid counters [INS, DEL, BND, DUP, INV]).
+
+    bam        a path or an open bam.BamFile (coordinate-sorted; no index is needed)
+    reference  a fasta.Reference or {contig: sequence}: the REF bases
+    params     a CallParams, or a columns.Params (the gates then take the reference's defaults)
+    ctx        an engine.Context (default: one on device 0 for the call); its pool, name pool and sequence pool are reset
+    chroms     the contigs to call on (default: all of the header); TRA mates may lie on any contig of the header
+    batch      reference bases per extraction task (the reference's -b)
+    timings    a dict that receives the wall milliseconds of the stages (tasks, rebuild, cluster, gather, emit)
+    TRA genotyping follows CUTESV_AMD_TRA_GT: reads_table or off (ValueError for bam, see tra_gt_mode)."""
+    from . import bam as bam_mod, engine, extract, rebuild, vcf
+    cp = params if isinstance(params, CallParams) else CallParams(resolve=params)
+    mode = tra_gt_mode(cp.resolve.genotype)
+    p = dataclasses.replace(cp.resolve, genotype_tra=(mode == "reads_table"))
+    own_bam = not isinstance(bam, bam_mod.BamFile)
+    bf = bam_mod.BamFile(bam, threads=threads) if own_bam else bam
+    own_ctx = ctx is None
+    if own_ctx:
+        ctx = engine.Context(0)
+    clock = [time.perf_counter()]
+
+    def lap(key):
+        now = time.perf_counter()
+        if timings is not None:
+            timings[key] = timings.get(key, 0.0) + (now - clock[0]) * 1e3
+        clock[0] = now
+    try:
+        # the chromosome table in name order: a chromosome's index is its name rank, the numbering of rebuild._segments and of a TRA row's mate
+        names = sorted(bf.references)
+        length = dict(zip(bf.references, bf.lengths))
+        crank = {c: i for i, c in enumerate(names)}
+        n_chrom = len(names)
+        wanted = names if chroms is None else [c for c in names if c in set(chroms)]
+        if chroms is not None and len(wanted) != len(set(chroms)):
+            raise KeyError("no reference %r in the BAM header" % sorted(set(chroms) - set(names))[0])
+        seg_of = {t: ti * n_chrom for ti, t in enumerate(TYPES)}
+        seg_base = [seg_of[t] for t in ("DEL", "INS", "DUP", "INV", "TRA")]
+        rebuild.pool_reset(ctx)
+        rebuild.name_pool_reset(ctx)
+        tables = []                                           # per task: (chromosome index, its reads-table columns)
+        for c in wanted:
+            for t0, t1 in cut_tasks(length[c], batch):
+                r = extract.task_to_pool(ctx, bf, c, t0, t1, crank, *cp.pipe_args(), seg_of["INS"] + crank[c], seg_of["DEL"] + crank[c], seg_base, None,
+                                         name_pool=True, seq_pool=True)
+                if p.genotype:
+                    tables.append((crank[c], r))
+        lap("ms_tasks")
+        if rebuild.pool_rows(ctx) == 0:
+            return (b"" if as_bytes else ""), (np.zeros(5, np.int64) if svid is None else svid)
+        order, _, major, nodedup = rebuild._segments(names, True)
+        rb = rebuild.rebuild_pool_by_name(ctx, major, nodedup, keep_on_device=True, ties="seqs")
+        if rb["n_ins_ties"]:
+            raise ValueError("%d INS rows were not settled on the device" % rb["n_ins_ties"])
+        lap("ms_rebuild")
+        off = np.r_[0, np.cumsum(rb["seg_count"])]
+        have_len = p.genotype_tra
+        segs = [segment_record(TYPES[s // n_chrom], order[s % n_chrom], int(off[s]), int(off[s + 1]), p, have_contig_len=have_len)
+                for s in np.flatnonzero(rb["seg_count"]).tolist()]
+        segs = np.array(segs, dtype=_abi.SEGMENT_DTYPE)
+        reads = {}
+        if p.genotype and tables:
+            ranks = rebuild.name_ranks(ctx)["rank"]
+            rd = dict(chrom=np.concatenate([np.full(len(r["reads_index"]), ci, np.int64) for ci, r in tables]),
+                      start=np.concatenate([r["reads_start"] for _, r in tables]), end=np.concatenate([r["reads_end"] for _, r in tables]),
+                      primary=np.concatenate([r["reads_primary"] for _, r in tables]),
+                      read_id=ranks[np.concatenate([r["name_base"] + r["reads_index"] for _, r in tables])])
+            reads = rebuild._reads_by_chrom(rd, n_chrom)
+            if p.genotype_tra:
+                reads["contig_len"] = np.array([length[c] for c in names], np.int64)
+        hb = _abi.HostBatch.on_device(segs, rb["dev"], rb["n_out"], n_chrom=n_chrom, keep=ctx, **reads)
+        res = ctx.cluster_batch(hb)
+        lap("ms_cluster")
+        t = res.trimmed()
+        ins_alt = rnames = None
+        if not ignore_sequence:
+            ins = np.flatnonzero(segs["svtype"][t["call_seg"]] == _abi.INS) if res.n_calls else np.zeros(0, np.int64)
+            blob, aoff = rebuild.alt_gather(ctx, t["seq_pick"][ins], t["bp2"][ins])
+            ins_alt = (blob, np.diff(aoff))
+        lap("ms_alt_gather")
+        if report_readid:
+            rnames = rebuild.support_join(ctx, t["support_off"], t["support_sig"])
+        lap("ms_support_join")
+        out = vcf.emit_records(_Shim(names), segs, res, reference, min_size=p.min_size, max_size=p.max_size, genotype=p.genotype, report_readid=report_readid,
+                               ignore_sequence=ignore_sequence, svid=svid, as_bytes=as_bytes, ins_alt=ins_alt, rnames=rnames)
+        lap("ms_emit")
+        return out
+    finally:
+        if own_ctx:
+            ctx.close()
+        if own_bam:
+            bf.close()
+
+
+def main(argv=None):
+    import argparse
+    from . import fasta
+    ap = argparse.ArgumentParser(prog="python -m cutesv_amd.call", description="SV calls of a BAM file as VCF records (the body; no header)")
+    ap.add_argument("bam")
+    ap.add_argument("reference", help="reference FASTA (an .fai beside it is used, or built in memory)")
+    ap.add_argument("-o", "--out", required=True)
+    ap.add_argument("--preset", default="clr", choices=["ont", "hifi", "clr"], help="cluster bias / merging ratio of INS and DEL as the README of cuteSV suggests")
+    ap.add_argument("--genotype", action="store_true")
+    ap.add_argument("--report_readid", action="store_true")
+    ap.add_argument("--ignore_sequence", action="store_true", help="<INS> instead of the inserted bases")
+    ap.add_argument("--min_support", type=int, default=10)
+    ap.add_argument("--min_size", type=int, default=30)
+    ap.add_argument("--max_size", type=int, default=100000)
+    ap.add_argument("--min_mapq", type=int, default=20)
+    ap.add_argument("--min_read_len", type=int, default=500)
+    ap.add_argument("--max_split_parts", type=int, default=7)
+    ap.add_argument("--min_siglength", type=int, default=10)
+    ap.add_argument("--merge_del_threshold", type=int, default=0)
+    ap.add_argument("--merge_ins_threshold", type=int, default=100)
+    ap.add_argument("--batch", type=int, default=10_000_000, help="reference bases per extraction task")
+    ap.add_argument("--threads", type=int, default=None, help="host threads that inflate the BAM")
+    ap.add_argument("--chroms", default=None, help="comma-separated contigs (default: all)")
+    a = ap.parse_args(argv)
+    p = getattr(Params, a.preset)(min_support=a.min_support, min_size=a.min_size, max_size=a.max_size, genotype=a.genotype)
+    cp = CallParams(p, min_mapq=a.min_mapq, max_split_parts=a.max_split_parts, min_read_len=a.min_read_len, min_siglength=a.min_siglength,
+                    merge_del_threshold=a.merge_del_threshold, merge_ins_threshold=a.merge_ins_threshold)
+    text, svid = call_bam(a.bam, fasta.Reference(a.reference), cp, chroms=a.chroms.split(",") if a.chroms else None, batch=a.batch,
+                          report_readid=a.report_readid, ignore_sequence=a.ignore_sequence, threads=a.threads, as_bytes=True)
+    with open(a.out, "wb") as f:
+        f.write(text)
+    print("%d records: INS %d, DEL %d, BND %d, DUP %d, INV %d" % (text.count(b"\n"), *svid.tolist()))
+    return 0
+
+
+if __name__ == "__main__":
+    raise SystemExit(main())

@@ -349,6 +349,38 @@ class _Block:
         return cls(n, buf, ints, spans, buf.isascii())
 
 
+def segment_record(svtype, chrom_index, beg, end, p: Params, have_contig_len=True):
+    """csv_segment record of the signatures [beg, end) of one (type, chromosome) task, scalars as main script :1117-1188 passes
+    them: what SigStore.segment makes, for a caller that holds no store (call.call_bam: the rows are on the device).
+    have_contig_len: the batch will carry the reference lengths (TRA genotyping needs them)."""
+    c = chrom_index
+    if svtype in ("DEL", "INS"):
+        bias = p.max_cluster_bias_DEL if svtype == "DEL" else p.max_cluster_bias_INS
+        ratio = p.diff_ratio_merging_DEL if svtype == "DEL" else p.diff_ratio_merging_INS
+        return _abi.make_segment(svtype, c, beg, end, bias, p.min_support, diff_ratio=ratio,
+                                 remain_reads_ratio=p.remain_reads_ratio,
+                                 gt_bias=bias if svtype == "DEL" else 1000,
+                                 min_support_reads=min(p.min_support, 5), genotype=p.genotype)
+    if svtype == "INV":
+        return _abi.make_segment(svtype, c, beg, end, p.max_cluster_bias_INV, p.min_support,
+                                 sv_size=p.min_size, max_size=p.max_size, gt_bias=p.max_cluster_bias_INV,
+                                 genotype=p.genotype)
+    if svtype == "DUP":
+        return _abi.make_segment(svtype, c, beg, end, p.max_cluster_bias_DUP, p.min_support,
+                                 sv_size=p.min_size, max_size=p.max_size, gt_bias=p.max_cluster_bias_DUP,
+                                 genotype=p.genotype)
+    if svtype == "TRA":
+        # TRA genotyping (cuteSV_resolveTRA.py:258-309) runs over the reads table when asked for; the
+        # reference re-fetches the BAM there, see include/cutesv_hip.h
+        gt = bool(p.genotype and p.genotype_tra)
+        if gt and not have_contig_len:
+            raise ValueError("TRA genotyping needs the reference lengths (SigStore.contig_len)")
+        return _abi.make_segment(svtype, c, beg, end, p.max_cluster_bias_TRA, p.min_support,
+                                 diff_ratio=p.diff_ratio_filtering_TRA, gt_bias=p.max_cluster_bias_TRA,
+                                 genotype=gt, gt_round=p.gt_round)
+    raise ValueError(svtype)
+
+
 @dataclass
 class SigStore:
     chroms: list                                  # chromosome names; index = chrom id (also the chr2 rank for TRA)
@@ -510,32 +542,7 @@ class SigStore:
     def segment(self, svtype, chrom, p: Params):
         """csv_segment record for one reference task, scalars as main script :1117-1188 passes them."""
         beg, end = self.seg_index[(svtype, chrom)]
-        c = self.chroms.index(chrom)
-        if svtype in ("DEL", "INS"):
-            bias = p.max_cluster_bias_DEL if svtype == "DEL" else p.max_cluster_bias_INS
-            ratio = p.diff_ratio_merging_DEL if svtype == "DEL" else p.diff_ratio_merging_INS
-            return _abi.make_segment(svtype, c, beg, end, bias, p.min_support, diff_ratio=ratio,
-                                     remain_reads_ratio=p.remain_reads_ratio,
-                                     gt_bias=bias if svtype == "DEL" else 1000,
-                                     min_support_reads=min(p.min_support, 5), genotype=p.genotype)
-        if svtype == "INV":
-            return _abi.make_segment(svtype, c, beg, end, p.max_cluster_bias_INV, p.min_support,
-                                     sv_size=p.min_size, max_size=p.max_size, gt_bias=p.max_cluster_bias_INV,
-                                     genotype=p.genotype)
-        if svtype == "DUP":
-            return _abi.make_segment(svtype, c, beg, end, p.max_cluster_bias_DUP, p.min_support,
-                                     sv_size=p.min_size, max_size=p.max_size, gt_bias=p.max_cluster_bias_DUP,
-                                     genotype=p.genotype)
-        if svtype == "TRA":
-            # TRA genotyping (cuteSV_resolveTRA.py:258-309) runs over the reads table when asked for; the
-            # reference re-fetches the BAM there, see include/cutesv_hip.h
-            gt = bool(p.genotype and p.genotype_tra)
-            if gt and self.contig_len is None:
-                raise ValueError("TRA genotyping needs the reference lengths (SigStore.contig_len)")
-            return _abi.make_segment(svtype, c, beg, end, p.max_cluster_bias_TRA, p.min_support,
-                                     diff_ratio=p.diff_ratio_filtering_TRA, gt_bias=p.max_cluster_bias_TRA,
-                                     genotype=gt, gt_round=p.gt_round)
-        raise ValueError(svtype)
+        return segment_record(svtype, self.chroms.index(chrom), beg, end, p, have_contig_len=self.contig_len is not None)
 
     def tasks(self, types=TYPES, chroms=None):
         """(type, chrom) pairs in the reference's submission order (main script :1116-1189)."""

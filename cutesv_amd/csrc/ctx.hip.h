@@ -97,6 +97,20 @@ struct SeqState {
     i64 device_bytes() { std::vector<Buf*> v; own(v); i64 t = 0; for (Buf* b : v) t += (i64)b->cap; return t; }
     void own(std::vector<Buf*>& v) { v.insert(v.end(), {&rbytes, &roff, &rlen, &qrev, &blob, &off, &half, &plan, &tie, &get, &out}); }
 };
+// The VCF strings (vcf_strings.hip.h): csv_seq_alt_gather and csv_name_support_join read the sorted columns of the last KEPT pool
+// rebuild (CSV_RB_FROM_POOL | CSV_RB_KEEP_ON_DEVICE: rb.osrc / orid / oaux, n_out rows) together with the pools those columns
+// number.  gen counts the events after which they no longer belong together - a pool reset or append, a name-pool reset or
+// append, any rebuild, any call that plans csv_ctx::scratch afresh; kept = gen when that rebuild finished (0: none): the two
+// entries run only while kept == gen.  work (picks / supports, lengths, scan tables) and out (the blob on its way to the host)
+// stand alone and are dead when a call returns.
+struct VcfStrState {
+    uint64_t gen = 1, kept = 0;
+    i64 n_out = 0;
+    bool by_name = false;
+    Buf work, out;
+    void stale() { gen++; }
+    void own(std::vector<Buf*>& v) { v.insert(v.end(), {&work, &out}); }
+};
 
 }  // namespace
 
@@ -133,7 +147,7 @@ struct csv_ctx {
     Buf gs_chrom, gs_perm0, gs_perm1, gs_hist, gs_tot;          // general reads sort (fallback), allocated on first use
     Buf flush;                                                   // csv_cache_flush scratch
     // the extraction-side stages (their lifetime rules: at the structs)
-    PoolState pool; NameState nm; BamState bm; SaState sa; SeqState seq;
+    PoolState pool; NameState nm; BamState bm; SaState sa; SeqState seq; VcfStrState vs;
     Arena scratch;                             // per-call scratch of the rebuild, the CIGAR scan and the split analysis
     RebuildState rb; CigarState cg; SplitState sp;
     // page-locked host staging: small tables on the way in, counters + call records + support lists on the way out

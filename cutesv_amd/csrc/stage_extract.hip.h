@@ -38,6 +38,7 @@ int csv_cigar_signatures(csv_ctx* c, const csv_cigar_in* in, csv_cigar_out* out)
     P.add(c->cg.iread, (cap_i + 1) * 4); P.add(c->cg.ipos, (cap_i + 1) * 8); P.add(c->cg.ilen, (cap_i + 1) * 8); P.add(c->cg.ip0, (cap_i + 1) * 8); P.add(c->cg.inp, (cap_i + 1) * 4);
     P.add(c->cg.pq, (cap_p + 1) * 4); P.add(c->cg.pl, (cap_p + 1) * 4);
     P.add(c->cg.dread, (cap_d + 1) * 4); P.add(c->cg.dpos, (cap_d + 1) * 8); P.add(c->cg.dlen, (cap_d + 1) * 8);
+    c->vs.stale();                                          // (the scratch arena is planned afresh: a kept rebuild's columns are gone)
     TRY(commit_synced(c, c->scratch, P));
     hipStream_t st = c->stream;
     if (!from_bam) { TRY(h2d(c, c->cg.off, in->cig_off, (n + 1) * 8)); TRY(h2d(c, c->cg.ops, in->cigar, nops * 4)); TRY(h2d(c, c->cg.start, in->ref_start, n * 8)); }
@@ -134,6 +135,7 @@ int csv_split_signatures(csv_ctx* c, const csv_split_in* in, csv_split_out* out)
     P.add(c->sp.cnt, n * 16); P.add(c->sp.tiles, (size_t)ntile * 24); P.add(c->sp.tot, 32);
     P.add(c->sp.kind, cap + 1); P.add(c->sp.read, (cap + 1) * 4); P.add(c->sp.ochr, (cap + 1) * 4); P.add(c->sp.aux, (cap + 1) * 4);
     P.add(c->sp.a, (cap + 1) * 8); P.add(c->sp.b, (cap + 1) * 8); P.add(c->sp.c, (cap + 1) * 8); P.add(c->sp.d, (cap + 1) * 8);
+    c->vs.stale();                                          // (the scratch arena is planned afresh: a kept rebuild's columns are gone)
     TRY(commit_synced(c, c->scratch, P));
     hipStream_t st = c->stream;
     if (!from_bam) {

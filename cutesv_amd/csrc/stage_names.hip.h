@@ -7,6 +7,7 @@ int csv_name_pool_reset(csv_ctx* c)
     if (!c) return CSV_E_INVALID;
     c->nm.n = 0; c->nm.bytes = 0; c->nm.maxlen = 0; c->nm.len.clear();
     c->nm.fresh = false;
+    c->vs.stale();
     return CSV_OK;
 }
 
@@ -33,6 +34,7 @@ int csv_name_pool_append(csv_ctx* c, int64_t n, const uint8_t* bytes, int64_t n_
     if (c->nm.n + n >= (1ll << 31) - 4096) return fail(c, CSV_E_INVALID, "name pool too large (%lld names)", (long long)(c->nm.n + n));
     if (first_index) *first_index = c->nm.n;
     if (n == 0) return CSV_OK;
+    c->vs.stale();
     HIP_TRY(c, hipSetDevice(c->device));
     // the names back to back and their offsets in the pool's blob: what crosses the link (a chunk's host image also holds the bases)
     std::vector<uint8_t> blob((size_t)total);

@@ -49,6 +49,7 @@ int csv_pool_reset(csv_ctx* c)
 {
     if (!c) return CSV_E_INVALID;
     c->pool.n = 0;
+    c->vs.stale();
     c->seq.rows = 0; c->seq.bytes = 0; c->seq.n_with = 0;    // the sequence pool shadows the rows
     return CSV_OK;
 }
@@ -65,6 +66,7 @@ int csv_pool_append(csv_ctx* c, int64_t n, const int32_t* seg_id, const int64_t*
     if (!c || n < 0 || (n > 0 && (!seg_id || !a || !b || !read || !aux))) return CSV_E_INVALID;
     if (n == 0) return CSV_OK;
     HIP_TRY(c, hipSetDevice(c->device));
+    c->vs.stale();
     TRY(pool_reserve(c, n));
     hipStream_t st = c->stream;
     const i64 o = c->pool.n;

@@ -6,6 +6,7 @@ int csv_rebuild_signatures(csv_ctx* c, const csv_rebuild_in* in, csv_rebuild_out
 {
     if (!c || !in || !out) return CSV_E_INVALID;
     RebuildState& rb = c->rb;
+    c->vs.stale();                                          // (whatever an earlier rebuild kept is no longer this call's)
     HIP_TRY(c, hipSetDevice(c->device));
     const bool from_pool = (in->flags & CSV_RB_FROM_POOL) != 0;
     const i64 n = from_pool ? c->pool.n : in->n;
@@ -220,6 +221,7 @@ int csv_rebuild_signatures(csv_ctx* c, const csv_rebuild_in* in, csv_rebuild_out
     for (const HostCol& o : cols) TRY(d2h(c, o.host, *o.dev, o.bytes, !keep_dev));
     HIP_TRY(c, hipStreamSynchronize(st));
     c->uploaded = c->ran = false;          // cnt was used as scratch
+    if (from_pool && keep_dev) { c->vs.kept = c->vs.gen; c->vs.n_out = n_out; c->vs.by_name = by_name; }      // (csv_seq_alt_gather / csv_name_support_join)
     return CSV_OK;
 }
 

@@ -394,6 +394,108 @@ def rebuild_pool_by_name(ctx, seg_aux_major, seg_nodedup=None, keep_on_device=Tr
     return _rebuild(ctx, pool_rows(ctx), None, None, seg_aux_major, seg_nodedup, keep_on_device, tie_order, ties=ties)
 
 
+# ------------------------------------------------------------------------------------ the VCF strings of a kept pool rebuild
+def _negotiated(ctx, call, n_off, guess):
+    """one of the two gathers below: call(out pointer, cap, off pointer) -> status; a first try with `guess` bytes, a second one with
+    the need the library reported (CSV_E_CAPACITY) -> (blob bytes, off int64[n_off + 1])"""
+    off = np.zeros(n_off + 1, np.int64)
+    out = np.empty(max(1, int(guess)), np.uint8)
+    rc = call(out.ctypes.data, len(out), off.ctypes.data)
+    if rc == _abi.E_CAPACITY:
+        out = np.empty(int(off[-1]), np.uint8)
+        rc = call(out.ctypes.data, len(out), off.ctypes.data)
+    ctx._check(rc)
+    return out[:int(off[-1])].tobytes(), off
+
+
+def _int_column(x):
+    """a pick / clip / support column in one of the ABI's two widths: int32 stays (CSV_OUT_COORD_I32 results), everything else is int64"""
+    x = np.asarray(x)
+    return np.ascontiguousarray(x, np.int32 if x.dtype == np.int32 else np.int64)
+
+
+def alt_gather(ctx, pick, clip, raw=False):
+    """csv_seq_alt_gather: entry k = bases(pool row src_row[pick[k]])[:clip[k]] over the context's last kept pool rebuild
+    (rebuild_pool / rebuild_pool_by_name with keep_on_device=True) - pick = the seq_pick of INS calls, clip = their SVLEN (bp2),
+    int64 or both int32 -> (blob: bytes, off: int64[n + 1]); raw=True: the blob as a uint8 array.  CsvError E_INVALID: no kept
+    rebuild or the pools changed since, a pick outside the rebuilt rows, a negative clip, a picked row without a sequence."""
+    pick, clip = _int_column(pick), _int_column(clip)
+    if pick.shape != clip.shape or pick.ndim != 1:
+        raise ValueError("one clip per pick is expected")
+    if pick.dtype != clip.dtype:
+        pick, clip = pick.astype(np.int64), clip.astype(np.int64)
+    n = len(pick)
+    flags = _abi.OUT_COORD_I32 if pick.dtype == np.int32 else 0
+    guess = int(np.clip(clip, 0, None).sum()) if n else 0
+    blob, off = _negotiated(ctx, lambda o, cap, po: lib().csv_seq_alt_gather(ctx._h, n, pick.ctypes.data if n else None, clip.ctypes.data if n else None, flags, o, cap, po), n, guess)
+    return (np.frombuffer(blob, np.uint8) if raw else blob), off
+
+
+def support_join(ctx, support_off, support_sig, raw=False):
+    """csv_name_support_join: entry c = ",".join(name(first[read_id[s]]) for s in support_sig[support_off[c]:support_off[c + 1]])
+    over the context's last kept rebuild_pool_by_name - the RNAMES text of the calls of a result (its support_off / support_sig,
+    int64 or int32) -> (blob: bytes, off: int64[n_calls + 1]); raw=True: the blob as a uint8 array.  CsvError E_INVALID: no kept
+    rebuild by name or the pools changed since, a support outside the rebuilt rows, offsets that do not start at 0 or decrease."""
+    support_off = np.ascontiguousarray(support_off, np.int64)
+    sup = _int_column(support_sig)
+    if support_off.ndim != 1 or len(support_off) < 1:
+        raise ValueError("support_off needs n_calls + 1 entries")
+    if len(support_off) and int(support_off[-1]) > len(sup):
+        raise ValueError("support_off names %d supports, %d are given" % (int(support_off[-1]), len(sup)))
+    n = len(support_off) - 1
+    p64, p32 = (None, sup.ctypes.data) if sup.dtype == np.int32 else (sup.ctypes.data, None)
+    if not len(sup):
+        p64 = p32 = None
+    blob, off = _negotiated(ctx, lambda o, cap, po: lib().csv_name_support_join(ctx._h, n, support_off.ctypes.data, p64, p32, o, cap, po), n, 64 * len(sup) + 4096)
+    return (np.frombuffer(blob, np.uint8) if raw else blob), off
+
+
+def alt_gather_host(seqs_by_pool_row, src_row, pick, clip):
+    """What csv_seq_alt_gather computes, in numpy and Python slices: seqs_by_pool_row[r] = the bases of pool row r (str or bytes;
+    None or missing: the row has no sequence), src_row = the rebuild's column -> (blob, off).  The checker of the kernels and the
+    statement of the contract: ValueError for what the entry refuses."""
+    src_row = np.asarray(src_row, np.int64); pick = np.asarray(pick, np.int64); clip = np.asarray(clip, np.int64)
+    if pick.shape != clip.shape or pick.ndim != 1:
+        raise ValueError("one clip per pick is expected")
+    if len(pick) and (int(pick.min()) < 0 or int(pick.max()) >= len(src_row)):
+        raise ValueError("a pick lies outside the %d rebuilt rows" % len(src_row))
+    if (clip < 0).any():
+        raise ValueError("a clip is negative")
+    get = seqs_by_pool_row.get if hasattr(seqs_by_pool_row, "get") else (lambda r: seqs_by_pool_row[r] if 0 <= r < len(seqs_by_pool_row) else None)
+    parts = []
+    for r, c in zip(src_row[pick].tolist(), clip.tolist()):
+        s = get(r)
+        if s is None:
+            raise ValueError("pool row %d has no sequence" % r)
+        parts.append((s.encode() if isinstance(s, str) else bytes(s))[:c])
+    off = np.zeros(len(parts) + 1, np.int64)
+    if parts:
+        np.cumsum([len(x) for x in parts], out=off[1:])
+    return b"".join(parts), off
+
+
+def support_join_host(names, first, read_id, support_off, support_sig):
+    """What csv_name_support_join computes: names[i] = name i of the name pool (str or bytes), first = name_ranks()["first"],
+    read_id = the rebuild's column (ranks) -> (blob, off); ValueError for what the entry refuses."""
+    first = np.asarray(first, np.int64); read_id = np.asarray(read_id, np.int64)
+    support_off = np.asarray(support_off, np.int64); sup = np.asarray(support_sig, np.int64)
+    if len(support_off) < 1 or support_off[0] != 0 or (np.diff(support_off) < 0).any() or support_off[-1] > len(sup):
+        raise ValueError("support_off must start at 0, not decrease and stay inside the support list")
+    sup = sup[:int(support_off[-1])]
+    if len(sup) and (int(sup.min()) < 0 or int(sup.max()) >= len(read_id)):
+        raise ValueError("a support lies outside the %d rebuilt rows" % len(read_id))
+    rk = read_id[sup]
+    if len(rk) and (int(rk.min()) < 0 or int(rk.max()) >= len(first)):
+        raise ValueError("a read id is no rank of the name pool")
+    nm = [names[i].encode() if isinstance(names[i], str) else bytes(names[i]) for i in first[rk].tolist()]
+    so = support_off.tolist()
+    parts = [b",".join(nm[so[c]:so[c + 1]]) for c in range(len(so) - 1)]
+    off = np.zeros(len(parts) + 1, np.int64)
+    if parts:
+        np.cumsum([len(x) for x in parts], out=off[1:])
+    return b"".join(parts), off
+
+
 def finish_ins_ties(r, ins_segs, seq_of_src, half_of_src):
     """The INS tie groups of a sorted (not de-duplicated) row set `r` (dict of arrays from rebuild_columns): rows that agree
     in (segment, a, b, read_id).  Each group is ordered by sequence (stable: equal sequences keep the concatenation order

@@ -31,7 +31,7 @@ _TLS = threading.local()          # the recycled output buffer is per thread: cs
 
 
 def emit_records(store, segments, res, reference, min_size=30, max_size=100000, genotype=False, report_readid=False,
-                 ignore_sequence=False, svid=None, as_bytes=False, as_view=False):
+                 ignore_sequence=False, svid=None, as_bytes=False, as_view=False, ins_alt=None, rnames=None):
     """calls of one batch -> (VCF body text, svid counters).
 
     segments   the csv_segment records the batch was run with (HostBatch.segments)
@@ -42,6 +42,12 @@ def emit_records(store, segments, res, reference, min_size=30, max_size=100000, 
     as_bytes   return the text as `bytes` (what a file is written from) instead of decoding it to `str`
     as_view    return a memoryview of this thread's output buffer instead (valid until the thread's next emit_records call):
                `f.write(view)` needs no copy of the text - with real REF sequences a 30x genome's records are ~30 MB
+    ins_alt    (blob, bytes taken per INS call): the ALT bases of the INS calls, in call order, made elsewhere
+               (rebuild.alt_gather: the bases live in the device's sequence pool) - `store.ins_seq` is not looked at.
+               ValueError unless there is one length per INS call and the lengths add up to the blob
+    rnames     (blob, off int64[n_calls + 1]): the RNAMES text of every call (rebuild.support_join) - `store.names` is not
+               looked at; only read with report_readid.  ValueError unless the offsets cover exactly the calls and the blob
+    With ins_alt / rnames `store` needs nothing but `chroms` and `strands`.
     """
     L = lib()
     t = res.trimmed()
@@ -69,11 +75,28 @@ def emit_records(store, segments, res, reference, min_size=30, max_size=100000, 
     rank[order] = np.arange(nch, dtype=np.int32)
     # inserted sequences of INS calls, sliced to SVLEN
     alt_blob, alt_off = None, None
-    if n and not ignore_sequence and (call_type == _abi.INS).any() and t["seq_pick"] is None:
+    rn_blob, rn_off = None, None
+    if ins_alt is not None and not ignore_sequence:
+        ins = np.flatnonzero(call_type == _abi.INS)
+        alt_blob, took = ins_alt
+        took = np.asarray(took, np.int64)
+        if took.shape != (len(ins),) or (took < 0).any() or int(took.sum()) != len(alt_blob):
+            raise ValueError("emit_records: ins_alt must hold one length per INS call (%d) that add up to its blob (%d bytes)" % (len(ins), len(alt_blob)))
+        alt_blob = bytes(alt_blob)
+        alt_off = np.zeros(n + 1, np.int64)
+        alt_off[ins + 1] = took
+        np.cumsum(alt_off, out=alt_off)
+    elif n and not ignore_sequence and (call_type == _abi.INS).any() and t["seq_pick"] is None:
         raise ValueError("emit_records: the result carries no seq_pick (a slim result without that field): INS records need it unless ignore_sequence")
-    if n and report_readid and (t["support_sig"] is None or t["support_off"] is None):
+    if rnames is not None and report_readid:
+        rn_blob, rn_off = rnames
+        rn_off = np.ascontiguousarray(rn_off, np.int64)
+        if rn_off.shape != (n + 1,) or rn_off[0] != 0 or (np.diff(rn_off) < 0).any() or int(rn_off[-1]) != len(rn_blob):
+            raise ValueError("emit_records: rnames must hold n_calls + 1 = %d offsets that start at 0, do not decrease and end at its blob (%d bytes)" % (n + 1, len(rn_blob)))
+        rn_blob = bytes(rn_blob)
+    elif n and report_readid and (t["support_sig"] is None or t["support_off"] is None):
         raise ValueError("emit_records: report_readid needs the support lists (the result was made with CSV_OUT_NO_SUPPORT_LIST)")
-    if n and not ignore_sequence and (call_type == _abi.INS).any():
+    if ins_alt is None and n and not ignore_sequence and (call_type == _abi.INS).any():
         from . import _cols_native as cn                     # (built by the same make as the library; no Python fallback)
         ins = np.flatnonzero(call_type == _abi.INS)
         pick = np.ascontiguousarray(t["seq_pick"][ins], np.int64)
@@ -92,8 +115,7 @@ def emit_records(store, segments, res, reference, min_size=30, max_size=100000, 
         alt_off = np.zeros(n + 1, np.int64)
         alt_off[ins + 1] = took
         np.cumsum(alt_off, out=alt_off)
-    rn_blob, rn_off = None, None
-    if n and report_readid:
+    if rnames is None and n and report_readid:
         nm = store.names.take(store.read_id[t["support_sig"]])
         so = t["support_off"].tolist()
         rn_blob, rn_off = _csr([",".join(nm[so[c]:so[c + 1]]) for c in range(n)])

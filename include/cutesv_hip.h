@@ -541,6 +541,30 @@ int csv_seq_info_get(const csv_ctx* ctx, csv_seq_info* out);
 /* sizeof of 0 csv_seq_info; -1 past the end */
 int csv_seq_struct_size(int which);
 
+/* The two strings a VCF record takes from the pools, gathered on the device (vcf_strings.hip.h).  Both
+ * read the sorted columns of the context's last KEPT pool rebuild - csv_rebuild_signatures with CSV_RB_FROM_POOL |
+ * CSV_RB_KEEP_ON_DEVICE: dev_src_row, dev_read_id, dev_aux, n_out rows - and produce the CSR blobs csv_vcf_in takes.  They
+ * return CSV_E_INVALID and launch nothing when the context holds no such rebuild, or when csv_pool_reset, csv_pool_append,
+ * csv_name_pool_reset, csv_name_pool_append, another csv_rebuild_signatures, csv_cigar_signatures or csv_split_signatures was
+ * called since (the columns and the pools no longer belong together: rebuild again).  csv_cluster_batch on those columns
+ * (CSV_IN_DEVICE_COLUMNS) changes nothing.  After any failure the context stays usable and the pools are unchanged.
+ *
+ * csv_seq_alt_gather: entry k = bases(pool row dev_src_row[pick[k]])[0 .. clip[k]) - the ALT of an INS call whose seq_pick is
+ *   pick[k] and whose SVLEN (bp2) is clip[k] (cuteSV_resolveINDEL.py:402); its length is min(aux, clip).  pick and clip are
+ *   int64_t arrays, or int32_t arrays with flags = CSV_OUT_COORD_I32 (the seq_pick / bp2 of such a result).  CSV_E_INVALID, with
+ *   nothing written to `out`: a pick outside [0, n_out), a clip < 0 (the reference has none, and a Python slice would count
+ *   from the end), a picked row without a sequence.  out_off (n + 1 entries) is filled first; CSV_E_CAPACITY: cap is too
+ *   small, out_off[n] holds the need.
+ * csv_name_support_join: entry c = the names of the reads first[dev_read_id[s]], s = support[support_off[c] ..
+ *   support_off[c + 1]), joined with ',' in the order of the list - the RNAMES text of cuteSV_genotype.py:263-458; a call
+ *   without supports is an empty entry.  The support list is support_sig (int64_t) or support_sig32 (int32_t), the other
+ *   NULL, as in csv_batch_out.  Needs a rebuild made with CSV_RB_RANK_FROM_NAMES (CSV_E_INVALID otherwise); a support
+ *   outside [0, n_out) or offsets that do not start at 0 or decrease: CSV_E_INVALID.  out_off (n_calls + 1 entries) and
+ *   CSV_E_CAPACITY as above. */
+int csv_seq_alt_gather(csv_ctx* ctx, int64_t n, const void* pick, const void* clip, int32_t flags, char* out, int64_t cap, int64_t* out_off /* n + 1 */);
+int csv_name_support_join(csv_ctx* ctx, int64_t n_calls, const int64_t* support_off /* n_calls + 1 */, const int64_t* support_sig, const int32_t* support_sig32, char* out,
+                          int64_t cap, int64_t* out_off /* n_calls + 1 */);
+
 /* ---------------------------------------------------------------------------------------------
  * The CIGAR scan of the extraction step on the GPU.  Restates the CIGAR part of parse_read
  * (cuteSV main script :606-655: every I / D operation of at least min_siglength bases is a piece at the reference position
