@@ -31,6 +31,7 @@ CG_SEQ_TO_POOL = 8                     # both flags words, with CG_TO_POOL: the 
 BAM_RESTART, BAM_COUNT_ONLY = 1, 2     # csv_bam_read flags
 SEG_KEY_RANGE = 1                             # csv_batch_out.seg_status bits
 OUT_NO_SUPPORT_LIST, OUT_COORD_I32 = 1, 2     # csv_batch_out.flags (ABI v7)
+ALN_FROM_KEPT_REBUILD, ALN_SUPPORT_I32 = 1, 2  # csv_aln_tra_genotype flags
 OPTIONAL_CALL_FIELDS = ("call_cluster", "call_aux", "cipos", "cilen", "search_pos", "seq_pick", "dr", "dv", "gl_idx")
 COORD_FIELDS = ("bp1", "bp2", "search_pos", "seq_pick")
 

@@ -62,6 +62,15 @@ SYMBOLS = [
     ("csv_seq_struct_size", C.c_int, [C.c_int]),
     ("csv_seq_alt_gather", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),
     ("csv_name_support_join", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    ("csv_aln_reset", C.c_int, [C.c_void_p, C.c_int32]),
+    ("csv_aln_rows", C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
+    ("csv_aln_append_decoded", C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_int64)]),
+    ("csv_aln_append", C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("csv_aln_get", C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("csv_aln_layout", C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    ("csv_aln_timing", C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    ("csv_aln_tra_genotype", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
+                                       C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
     ("csv_vcf_emit", C.c_int, [C.POINTER(_abi.VcfIn), C.c_char_p, C.c_int64, C.POINTER(C.c_int64), C.c_void_p]),
     ("csv_bam_open", C.c_int, [C.c_char_p, C.c_int, C.POINTER(C.c_void_p), C.c_char_p, C.c_int]),
     ("csv_bam_close", None, [C.c_void_p]),

@@ -1,7 +1,7 @@
 """BAM -> VCF body in one call: the chain the earlier stages built, connected.
 
     text, svid = call_bam("in.bam", fasta.Reference("ref.fa"), CallParams(Params.ont(min_support=3)))
-    python -m cutesv_amd.call in.bam ref.fa -o out.body.vcf [--genotype] [--report_readid] [--min_support N] [--batch B]
+    python -m cutesv_amd.call in.bam ref.fa -o out.body.vcf [--genotype] [--tra_gt MODE] [--report_readid] [--min_support N] [--batch B]
 
 Per task region the records are decoded, scanned and analysed on the device and their signatures, read names and inserted
 bases stay there (extract.task_to_pool with the name pool and the sequence pool); one rebuild sorts and de-duplicates the pool
@@ -54,14 +54,46 @@ def cut_tasks(length, batch):
     return tasks
 
 
-def tra_gt_mode(genotype):
-    """CUTESV_AMD_TRA_GT as call_bam honours it -> "reads_table" | "off"; "bam" (resolve's default) is refused: tra_bam reads the
-    BAM through pysam, not through bam.BamFile"""
-    mode = os.environ.get("CUTESV_AMD_TRA_GT", "bam") if genotype else "off"
-    if mode not in ("reads_table", "off"):
-        raise ValueError("call_bam genotypes TRA calls with CUTESV_AMD_TRA_GT=reads_table or leaves them with CUTESV_AMD_TRA_GT=off; %r is not available here "
-                         "(the BAM-based mode needs resolve.phase3 with bam=)" % (mode,))
+TRA_GT_MODES = ("alignments", "reads_table", "off")
+
+
+def tra_gt_mode(genotype, tra_gt=None):
+    """The TRA genotyping of call_bam -> "alignments" | "reads_table" | "off": `tra_gt` when given, else CUTESV_AMD_TRA_GT.
+    alignments: every alignment of the BAM counts, as in the reference (aln.tra_genotype over the table the tasks fill);
+    reads_table: the engine's walk over the gated reads table; off: the fields stay '.'.  "bam" (resolve's default) is refused:
+    tra_bam reads the BAM through pysam, not through bam.BamFile"""
+    mode = (os.environ.get("CUTESV_AMD_TRA_GT", "bam") if tra_gt is None else tra_gt) if genotype else "off"
+    if mode not in TRA_GT_MODES:
+        raise ValueError("call_bam genotypes TRA calls with CUTESV_AMD_TRA_GT=alignments (from every alignment, as the reference does) or "
+                         "CUTESV_AMD_TRA_GT=reads_table, or leaves them with CUTESV_AMD_TRA_GT=off; %r is not available here "
+                         "(the pysam-based mode needs resolve.phase3 with bam=)" % (mode,))
     return mode
+
+
+def _genotype_tra_from_alignments(ctx, segs, res, contig_len, p):
+    """alignments mode: the TRA calls of the result genotyped over the context's alignment table (aln.tra_genotype on the
+    support_sig rows of the kept rebuild) and the answer written into the result - DR, and the GL table index of (DR, DV), -1
+    where count_coverage gave up - with the TRA segments marked as genotyped: resolve._genotype_tra_from_bam's write-back"""
+    from . import aln
+    from .genotype import gl_index
+    n = res.n_calls
+    tra_seg = np.flatnonzero(segs["svtype"] == _abi.TRA)
+    arr = res.arrays
+    idx = np.flatnonzero(np.isin(arr["call_seg"][:n], tra_seg))
+    if len(idx):
+        soff = arr["support_off"][:n + 1]
+        cnt = (soff[idx + 1] - soff[idx]).astype(np.int64)
+        off = np.r_[0, np.cumsum(cnt)]
+        pick = np.repeat(soff[idx] - off[:-1], cnt) + np.arange(int(off[-1]))          # the calls' support lists, back to back
+        dr, status = aln.tra_genotype(ctx, segs["chrom"][arr["call_seg"][idx]], arr["bp1"][idx], arr["call_aux"][idx] >> 3, arr["bp2"][idx], off,
+                                      arr["support_sig"][pick], contig_len, p.max_cluster_bias_TRA, p.gt_round, flags=aln.FROM_KEPT_REBUILD)
+        for c, d, s, dv in zip(idx.tolist(), dr.tolist(), status.tolist(), arr["support"][idx].tolist()):
+            if s == -1:
+                arr["gl_idx"][c] = -1
+            else:
+                arr["dr"][c] = d
+                arr["gl_idx"][c] = gl_index(d, dv)
+    segs["genotype"][tra_seg] = 1
 
 
 class _Shim:
@@ -72,7 +104,7 @@ class _Shim:
 
 
 def call_bam(bam, reference, params, ctx=None, chroms=None, batch=10_000_000, report_readid=False, ignore_sequence=False, threads=None, svid=None,
-             as_bytes=False, timings=None):
+             as_bytes=False, timings=None, tra_gt=None):
     """-> (VCF body text, svid counters [INS, DEL, BND, DUP, INV]).
 
     bam        a path or an open bam.BamFile (coordinate-sorted; no index is needed)
@@ -81,11 +113,12 @@ def call_bam(bam, reference, params, ctx=None, chroms=None, batch=10_000_000, re
     ctx        an engine.Context (default: one on device 0 for the call); its pool, name pool and sequence pool are reset
     chroms     the contigs to call on (default: all of the header); TRA mates may lie on any contig of the header
     batch      reference bases per extraction task (the reference's -b)
-    timings    a dict that receives the wall milliseconds of the stages (tasks, rebuild, cluster, gather, emit)
-    TRA genotyping follows CUTESV_AMD_TRA_GT: reads_table or off (ValueError for bam, see tra_gt_mode)."""
-    from . import bam as bam_mod, engine, extract, rebuild, vcf
+    timings    a dict that receives the wall milliseconds of the stages (tasks, rebuild, cluster, tra_gt, gather, emit)
+    tra_gt     how TRA calls are genotyped: "alignments", "reads_table" or "off"; None follows CUTESV_AMD_TRA_GT (ValueError for
+               bam, see tra_gt_mode)"""
+    from . import aln, bam as bam_mod, engine, extract, rebuild, vcf
     cp = params if isinstance(params, CallParams) else CallParams(resolve=params)
-    mode = tra_gt_mode(cp.resolve.genotype)
+    mode = tra_gt_mode(cp.resolve.genotype, tra_gt)
     p = dataclasses.replace(cp.resolve, genotype_tra=(mode == "reads_table"))
     own_bam = not isinstance(bam, bam_mod.BamFile)
     bf = bam_mod.BamFile(bam, threads=threads) if own_bam else bam
@@ -112,11 +145,13 @@ def call_bam(bam, reference, params, ctx=None, chroms=None, batch=10_000_000, re
         seg_base = [seg_of[t] for t in ("DEL", "INS", "DUP", "INV", "TRA")]
         rebuild.pool_reset(ctx)
         rebuild.name_pool_reset(ctx)
+        if mode == "alignments":
+            aln.reset(ctx, n_chrom)
         tables = []                                           # per task: (chromosome index, its reads-table columns)
         for c in wanted:
             for t0, t1 in cut_tasks(length[c], batch):
                 r = extract.task_to_pool(ctx, bf, c, t0, t1, crank, *cp.pipe_args(), seg_of["INS"] + crank[c], seg_of["DEL"] + crank[c], seg_base, None,
-                                         name_pool=True, seq_pool=True)
+                                         name_pool=True, seq_pool=True, aln=(mode == "alignments"))
                 if p.genotype:
                     tables.append((crank[c], r))
         lap("ms_tasks")
@@ -145,6 +180,9 @@ def call_bam(bam, reference, params, ctx=None, chroms=None, batch=10_000_000, re
         hb = _abi.HostBatch.on_device(segs, rb["dev"], rb["n_out"], n_chrom=n_chrom, keep=ctx, **reads)
         res = ctx.cluster_batch(hb)
         lap("ms_cluster")
+        if mode == "alignments":
+            _genotype_tra_from_alignments(ctx, segs, res, np.array([length[c] for c in names], np.int64), p)
+        lap("ms_tra_gt")
         t = res.trimmed()
         ins_alt = rnames = None
         if not ignore_sequence:
@@ -189,12 +227,17 @@ def main(argv=None):
     ap.add_argument("--batch", type=int, default=10_000_000, help="reference bases per extraction task")
     ap.add_argument("--threads", type=int, default=None, help="host threads that inflate the BAM")
     ap.add_argument("--chroms", default=None, help="comma-separated contigs (default: all)")
+    ap.add_argument("--tra_gt", default=None, choices=list(TRA_GT_MODES),
+                    help="with --genotype: how BND records are genotyped (default: CUTESV_AMD_TRA_GT, else alignments - every alignment counts, as in cuteSV)")
     a = ap.parse_args(argv)
+    tra_gt = a.tra_gt
+    if tra_gt is None and a.genotype and "CUTESV_AMD_TRA_GT" not in os.environ:
+        tra_gt = "alignments"
     p = getattr(Params, a.preset)(min_support=a.min_support, min_size=a.min_size, max_size=a.max_size, genotype=a.genotype)
     cp = CallParams(p, min_mapq=a.min_mapq, max_split_parts=a.max_split_parts, min_read_len=a.min_read_len, min_siglength=a.min_siglength,
                     merge_del_threshold=a.merge_del_threshold, merge_ins_threshold=a.merge_ins_threshold)
     text, svid = call_bam(a.bam, fasta.Reference(a.reference), cp, chroms=a.chroms.split(",") if a.chroms else None, batch=a.batch,
-                          report_readid=a.report_readid, ignore_sequence=a.ignore_sequence, threads=a.threads, as_bytes=True)
+                          report_readid=a.report_readid, ignore_sequence=a.ignore_sequence, threads=a.threads, as_bytes=True, tra_gt=tra_gt)
     with open(a.out, "wb") as f:
         f.write(text)
     print("%d records: INS %d, DEL %d, BND %d, DUP %d, INV %d" % (text.count(b"\n"), *svid.tolist()))

@@ -111,6 +111,20 @@ struct VcfStrState {
     void stale() { gen++; }
     void own(std::vector<Buf*>& v) { v.insert(v.end(), {&work, &out}); }
 };
+// The alignment table (aln.hip.h): one row per BAM record - start, end, name id | primary << 31 - grouped by chromosome, in
+// file order; all stand-alone.  start / end / idp grow by copying and hold n rows; maxlen = per chromosome the longest
+// end - start, kept on the device (atomicMax as rows arrive); h_off = the row offsets per chromosome, kept on the host (it learns
+// every append's count) and sent with the tables of a genotype call; last_chrom / max_id: the chromosome of the last row and the largest name id seen, for the
+// host checks.  The rows live until csv_aln_reset.  Dead when a call returns: work (an append's flags, scan tables and pending
+// words; a host append's columns), gt (the tables of a csv_aln_tra_genotype call, its results, the global sets of its large calls).
+struct AlnState {
+    Buf start, end, idp, maxlen, work, gt;
+    std::vector<i64> h_off;
+    i64 n = 0, max_id = -1;
+    int n_chrom = 0, last_chrom = -1;
+    float ms_append = 0, ms_genotype = 0;
+    void own(std::vector<Buf*>& v) { v.insert(v.end(), {&start, &end, &idp, &maxlen, &work, &gt}); }
+};
 
 }  // namespace
 
@@ -147,7 +161,7 @@ struct csv_ctx {
     Buf gs_chrom, gs_perm0, gs_perm1, gs_hist, gs_tot;          // general reads sort (fallback), allocated on first use
     Buf flush;                                                   // csv_cache_flush scratch
     // the extraction-side stages (their lifetime rules: at the structs)
-    PoolState pool; NameState nm; BamState bm; SaState sa; SeqState seq; VcfStrState vs;
+    PoolState pool; NameState nm; BamState bm; SaState sa; SeqState seq; VcfStrState vs; AlnState al;
     Arena scratch;                             // per-call scratch of the rebuild, the CIGAR scan and the split analysis
     RebuildState rb; CigarState cg; SplitState sp;
     // page-locked host staging: small tables on the way in, counters + call records + support lists on the way out

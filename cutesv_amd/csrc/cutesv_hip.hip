@@ -24,6 +24,7 @@
 #include "names.hip.h"
 #include "seqs.hip.h"
 #include "vcf_strings.hip.h"
+#include "aln.hip.h"
 
 using namespace csv;
 
@@ -296,7 +297,7 @@ void csv_ctx_destroy(csv_ctx* c)
     (void)hipSetDevice(c->device);
     (void)hipDeviceSynchronize();
     std::vector<Buf*> own = {&c->sqrt_tab, &c->rcp_tab, &c->cipk_tab, &c->cnt, &c->rstate, &c->gs_chrom, &c->gs_perm0, &c->gs_perm1, &c->gs_hist, &c->gs_tot, &c->flush};
-    c->pool.own(own); c->sp.own(own); c->bm.own(own); c->sa.own(own); c->nm.own(own); c->seq.own(own); c->vs.own(own);
+    c->pool.own(own); c->sp.own(own); c->bm.own(own); c->sa.own(own); c->nm.own(own); c->seq.own(own); c->vs.own(own); c->al.own(own);
     for (Buf* b : own) if (b->p) (void)hipFree(b->p);
     for (Arena* a : {&c->arena, &c->scratch, &c->bm.arena, &c->sa.arena, &c->nm.arena}) if (a->base) (void)hipFree(a->base);
     if (c->h_pin) (void)hipHostFree(c->h_pin);
@@ -1602,3 +1603,4 @@ int csv_cluster_batch(csv_ctx* c, const csv_batch_in* in, csv_batch_out* out)
 #include "stage_vcf_strings.hip.h"
 #include "stage_extract.hip.h"
 #include "stage_bam.hip.h"
+#include "stage_aln.hip.h"

@@ -657,7 +657,7 @@ def _assemble_device(ctx, chunk, cols, sig, names, seqs, sel, chrom, chrom_rank,
 
 # ------------------------------------------------------------------------------------ a task's region -> rows of the pool
 def task_to_pool(ctx, bamfile, chrom, task_start, task_end, chrom_rank, sv_size, min_mapq, max_split_parts, min_read_len, min_siglength,
-                 merge_del_threshold, merge_ins_threshold, max_size, seg_ins, seg_del, seg_base, read_base, bed_regions=None, name_pool=False, seq_pool=False):
+                 merge_del_threshold, merge_ins_threshold, max_size, seg_ins, seg_del, seg_base, read_base, bed_regions=None, name_pool=False, seq_pool=False, aln=False):
     """The body of an extraction task without a candidate tuple, a name string or a sequence: the records of the region
     (`bamfile.records`) are decoded on the device, the CIGAR scan appends its signatures to the context's pool from the decoded
     columns (CSV_CG_FROM_BAM | CSV_CG_TO_POOL), the SA tags are parsed there (split_inputs_bam) and the split-read analysis appends
@@ -680,8 +680,15 @@ def task_to_pool(ctx, bamfile, chrom, task_start, task_end, chrom_rank, sv_size,
     (upload_read_sequences) and both calls run with seqs=True: every INS row gets its inserted bases and its x.5 flag in the
     context's sequence pool, cut on the device.  The INS rows of flagged calls get theirs through rebuild.seq_pool_put, cut on
     the host as single_pipe_bam cuts them.  The pool rows are the same either way; the result gains n_seq_rows / n_seq_bytes
-    (the sequence pool's counts after the task)."""
+    (the sequence pool's counts after the task).
+
+    aln=True (needs name_pool=True): the records that START in [task_start, task_end) - all of them, whatever their flag or MAPQ -
+    become rows of the context's alignment table (aln.append_decoded, on the device, right after the decode) with their name-pool
+    indices as ids: what aln.tra_genotype walks.  The caller resets the table (aln.reset) and runs a contig's tasks in order; the
+    result gains n_aln_rows."""
     from . import bam as bam_mod, rebuild
+    if aln and not name_pool:
+        raise ValueError("aln=True needs name_pool=True: a row's id is its name's index")
     if name_pool:
         n_names = rebuild.name_pool_rows(ctx)
         if read_base is None:
@@ -694,6 +701,10 @@ def task_to_pool(ctx, bamfile, chrom, task_start, task_end, chrom_rank, sv_size,
     cols = bam_mod.decode(ctx, chunk, host_outputs=False)
     if name_pool:
         rebuild.name_pool_append_chunk(ctx, chunk)
+    n_aln = 0
+    if aln:
+        from . import aln as aln_mod
+        n_aln = aln_mod.append_decoded(ctx, chrom_rank[chrom], task_start, task_end, read_base)
     start, end, mapq, qlen = cols["ref_start"], cols["ref_end"], cols["mapq"], cols["query_len"]
     gate, _, use, sel = _gates(cols, task_start, bed_regions, min_read_len, min_mapq)
     if seq_pool:
@@ -719,6 +730,8 @@ def task_to_pool(ctx, bamfile, chrom, task_start, task_end, chrom_rank, sv_size,
     extra = dict(name_base=read_base) if name_pool else {}
     if seq_pool:
         extra["n_seq_rows"], extra["n_seq_bytes"] = rebuild.seq_pool_rows(ctx)
+    if aln:
+        extra["n_aln_rows"] = n_aln
     return dict(**extra, n_records=chunk.n, n_sig_ins=sig["n_sig_ins"], n_sig_del=sig["n_sig_del"], n_calls=si["n_calls"], n_entries=si["n_entries"], n_split=n_split,
                 n_split_host=n_host, n_flagged=si["n_flagged"], flagged_calls=calls, flagged_records=si["call_rec"][calls],
                 reads_start=start[keep], reads_end=end[keep], reads_primary=(cols["cls"][keep] == 1).astype(np.uint8), reads_index=keep)

@@ -565,6 +565,56 @@ int csv_seq_alt_gather(csv_ctx* ctx, int64_t n, const void* pick, const void* cl
 int csv_name_support_join(csv_ctx* ctx, int64_t n_calls, const int64_t* support_off /* n_calls + 1 */, const int64_t* support_sig, const int32_t* support_sig32, char* out,
                           int64_t cap, int64_t* out_off /* n_calls + 1 */);
 
+/* The alignment table and the TRA genotyping over it (aln.hip.h).  The reference genotypes a TRA call from
+ * the BAM itself (call_gt, cuteSV_resolveTRA.py:258-309; count_coverage, cuteSV_genotype.py:72-93): every alignment fetch()
+ * yields counts - secondary, supplementary, low-MAPQ and placed-unmapped records too - and a record is primary when its flag is
+ * 0 or 16, whatever its MAPQ.  The table holds one row per BAM record, grouped by chromosome, in file order:
+ *   start    pos
+ *   end      pos + max(reference span, 1); pos + 1 for a record without CIGAR, with a zero span or with flag bit 4 (htslib's
+ *            bam_endpos); a CG-tag record takes its span from the CG array; saturates at INT32_MAX
+ *   primary  flag == 0 || flag == 16
+ *   id       the name id of the record
+ * (12 bytes per record in device memory), and per chromosome the longest end - start.  It belongs to the context and lives
+ * until csv_aln_reset / csv_ctx_destroy.
+ *
+ * csv_aln_reset: empties the table and fixes the number of chromosomes.  csv_aln_rows: its row count.
+ * csv_aln_append_decoded: the records of the context's last successful csv_bam_decode (CSV_E_INVALID: there is none) with
+ *   beg <= pos < end become rows of `chrom`, in chunk order, each with the name id name_base + its index in the chunk - the
+ *   reference_start >= task start rule of the reads table (MAIN:711): tasks partition a contig, so every record lands in the
+ *   table once.  Filter, scan, compaction and conversion run on the device; nothing but the count comes back.
+ * csv_aln_append: the same from host arrays (0 <= start < end, id >= 0: CSV_E_INVALID otherwise).
+ * Ordering contract of both: chrom must be at least the chromosome of the last row, and the starts must not decrease inside a
+ *   chromosome, across appends too: CSV_E_UNSORTED.  A chrom outside [0, n_chrom): CSV_E_INVALID.  The order of the starts is
+ *   checked on the device (a flag word that comes back with the count).  After a failed append the table is unchanged.
+ * csv_aln_get: rows [first, first + n) back to the host (any array may be NULL).  csv_aln_layout: off[n_chrom + 1] = first row of
+ *   every chromosome, maxlen[n_chrom] = its longest record (0: no rows).  csv_aln_timing: the kernels of the last append / the last
+ *   genotype call in milliseconds (HIP events).
+ * csv_aln_tra_genotype: call_gt for n_calls calls, one wavefront each.  Window 1 = [max(pos1 - bias, 0), min(pos1 + bias,
+ *   contig_len[chrom1])); count_coverage's walk over the rows with start < e and end > s, with its two exits - A: the row is
+ *   primary, starts before s, ends after e, and the distinct names of such rows reach up_bound -> 1; B: the row is primary and
+ *   it is at least the gt_round-th of the walk -> 1 when 5 * primaries <= rows so far, else -1.  Window 2 (pos2 on chrom2) is
+ *   walked only when window 1 gave 0, and its status is not looked at.  out_status = window 1's status; out_dr = the spanning
+ *   names that are not among the call's supports, -1 when the status is -1.  up_bound = threshold_ref_count
+ *   (cuteSV_genotype.py:62-70) of the call's support count.  A window that is empty after the clamp walks nothing.
+ *   support: int64_t, or int32_t with CSV_ALN_SUPPORT_I32.  Without CSV_ALN_FROM_KEPT_REBUILD it holds ids (>= 0), compared with
+ *   the rows' ids as they are.  With it, it holds rows of the context's last kept pool rebuild (the support_sig of a result),
+ *   under the contract of csv_name_support_join: a support's id is dev_read_id[row], a name rank; a table row's id is the rank
+ *   of its name id in the name pool, whose ranks must be current - both looked up on the device.
+ *   CSV_E_INVALID, with nothing launched and the context usable: offsets that do not start at 0 or decrease, a support outside
+ *   its range, a chromosome outside [0, n_chrom), n_chrom that is not the table's, in rank mode a name id of the table outside
+ *   the name pool, no kept rebuild by name, or pools that changed since. */
+enum { CSV_ALN_FROM_KEPT_REBUILD = 1, CSV_ALN_SUPPORT_I32 = 2 };
+int csv_aln_reset(csv_ctx* ctx, int32_t n_chrom);
+int csv_aln_rows(const csv_ctx* ctx, int64_t* n);
+int csv_aln_append_decoded(csv_ctx* ctx, int32_t chrom, int64_t beg, int64_t end, int64_t name_base, int64_t* n_appended);
+int csv_aln_append(csv_ctx* ctx, int32_t chrom, int64_t n, const int32_t* start, const int32_t* end, const uint8_t* primary, const int32_t* id);
+int csv_aln_get(csv_ctx* ctx, int64_t first, int64_t n, int32_t* start, int32_t* end, uint8_t* primary, int32_t* id);
+int csv_aln_layout(csv_ctx* ctx, int32_t n_chrom, int64_t* off /* n_chrom + 1 */, int32_t* maxlen /* n_chrom */);
+int csv_aln_timing(const csv_ctx* ctx, float* ms_append, float* ms_genotype);
+int csv_aln_tra_genotype(csv_ctx* ctx, int64_t n_calls, const int32_t* chrom1, const int64_t* pos1, const int32_t* chrom2, const int64_t* pos2,
+                         const int64_t* support_off /* n_calls + 1 */, const void* support, int32_t flags, int32_t n_chrom, const int64_t* contig_len, int64_t bias,
+                         int64_t gt_round, int32_t* out_dr, int32_t* out_status);
+
 /* ---------------------------------------------------------------------------------------------
  * The CIGAR scan of the extraction step on the GPU.  Restates the CIGAR part of parse_read
  * (cuteSV main script :606-655: every I / D operation of at least min_siglength bases is a piece at the reference position
