@@ -28,6 +28,10 @@ CG_FROM_BAM = 2                        # csv_cigar_in.flags: scan the device col
 SP_FROM_BAM = 4                        # csv_split_in.flags: the reads are the calls of the context's last csv_bam_split_inputs
 SEQ_OPT_WHOLE_IMAGE = 1                # csv_seq_option: send the host image whole (measurement aid)
 CG_SEQ_TO_POOL = 8                     # both flags words, with CG_TO_POOL: the INS rows' bases go to the context's sequence pool
+CG_USE_FROM_GATES = 16                 # csv_cigar_in.flags, with CG_FROM_BAM and use = NULL: use[r] = bit GATE_USE of the context's gates
+SA_SEL_FROM_GATES = 1                  # csv_sa_in.flags, with sel = NULL: sel[i] = bit GATE_SEL of the context's gates
+GT_BED = 1                             # csv_bam_task_gates flags: a record must overlap one of the regions
+GATE_TASK, GATE_PARSED, GATE_USE, GATE_SEL, GATE_READS = 1, 2, 4, 8, 16      # the bits of a gates byte
 BAM_RESTART, BAM_COUNT_ONLY = 1, 2     # csv_bam_read flags
 SEG_KEY_RANGE = 1                             # csv_batch_out.seg_status bits
 OUT_NO_SUPPORT_LIST, OUT_COORD_I32 = 1, 2     # csv_batch_out.flags (ABI v7)

@@ -71,6 +71,8 @@ SYMBOLS = [
     ("csv_aln_timing", C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     ("csv_aln_tra_genotype", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
                                        C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
+    ("csv_bam_task_gates", C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.POINTER(C.c_float)]),
     ("csv_vcf_emit", C.c_int, [C.POINTER(_abi.VcfIn), C.c_char_p, C.c_int64, C.POINTER(C.c_int64), C.c_void_p]),
     ("csv_bam_open", C.c_int, [C.c_char_p, C.c_int, C.POINTER(C.c_void_p), C.c_char_p, C.c_int]),
     ("csv_bam_close", None, [C.c_void_p]),

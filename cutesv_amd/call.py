@@ -2,6 +2,7 @@
 
     text, svid = call_bam("in.bam", fasta.Reference("ref.fa"), CallParams(Params.ont(min_support=3)))
     python -m cutesv_amd.call in.bam ref.fa -o out.body.vcf [--genotype] [--tra_gt MODE] [--report_readid] [--min_support N] [--batch B]
+                               [--include_bed FILE]
 
 Per task region the records are decoded, scanned and analysed on the device and their signatures, read names and inserted
 bases stay there (extract.task_to_pool with the name pool and the sequence pool); one rebuild sorts and de-duplicates the pool
@@ -43,7 +44,8 @@ class CallParams:
 def cut_tasks(length, batch):
     """the task regions of a contig of `length` bases with -b `batch`: [(start, end)] as main_ctrl cuts them - one task for a contig
     shorter than the batch, else int(length / batch) full ones and the rest.  (The reference also shrinks the batch of a contig
-    that holds many reads, from the index statistics: a matter of load balance - the calls do not depend on the cut.)"""
+    that holds many reads, from the index statistics: a matter of load balance - the calls do not depend on the cut, except with
+    include_bed: a task's reads are tested against the regions of THAT task only, see bed.py.)"""
     if batch <= 0:
         raise ValueError("batch must be positive")
     if length < batch:
@@ -54,6 +56,7 @@ def cut_tasks(length, batch):
     return tasks
 
 
+DEFAULT_GATES = "device"        # where call_bam evaluates the task gates without a BED (decided by its measurement)
 TRA_GT_MODES = ("alignments", "reads_table", "off")
 
 
@@ -104,7 +107,7 @@ class _Shim:
 
 
 def call_bam(bam, reference, params, ctx=None, chroms=None, batch=10_000_000, report_readid=False, ignore_sequence=False, threads=None, svid=None,
-             as_bytes=False, timings=None, tra_gt=None):
+             as_bytes=False, timings=None, tra_gt=None, include_bed=None, gates=None):
     """-> (VCF body text, svid counters [INS, DEL, BND, DUP, INV]).
 
     bam        a path or an open bam.BamFile (coordinate-sorted; no index is needed)
@@ -115,8 +118,17 @@ def call_bam(bam, reference, params, ctx=None, chroms=None, batch=10_000_000, re
     batch      reference bases per extraction task (the reference's -b)
     timings    a dict that receives the wall milliseconds of the stages (tasks, rebuild, cluster, tra_gt, gather, emit)
     tra_gt     how TRA calls are genotyped: "alignments", "reads_table" or "off"; None follows CUTESV_AMD_TRA_GT (ValueError for
-               bam, see tra_gt_mode)"""
-    from . import aln, bam as bam_mod, engine, extract, rebuild, vcf
+               bam, see tra_gt_mode)
+    include_bed  a BED file's path or a bed.Regions: only call where these regions are (the reference's -include_bed).  Every task
+               gets `regions.for_task(contig, start, end)` - the reference's rule, under which a read that starts in one task and
+               reaches only a region that begins in the next is dropped: with a BED the calls depend on `batch`.  TRA genotyping
+               from every alignment (tra_gt="alignments") is not restricted, as in the reference.  None: no gate.
+    gates      "host" or "device": where the task gates are evaluated (extract.task_to_pool); None: "device" with include_bed,
+               else DEFAULT_GATES (also "device": DESIGN.md section 19 has the measurement that decided it)"""
+    from . import aln, bam as bam_mod, bed as bed_mod, engine, extract, rebuild, vcf
+    regions = None if include_bed is None else include_bed if isinstance(include_bed, bed_mod.Regions) else bed_mod.load_bed(include_bed)
+    if gates is None:
+        gates = "device" if regions is not None else DEFAULT_GATES
     cp = params if isinstance(params, CallParams) else CallParams(resolve=params)
     mode = tra_gt_mode(cp.resolve.genotype, tra_gt)
     p = dataclasses.replace(cp.resolve, genotype_tra=(mode == "reads_table"))
@@ -151,7 +163,8 @@ def call_bam(bam, reference, params, ctx=None, chroms=None, batch=10_000_000, re
         for c in wanted:
             for t0, t1 in cut_tasks(length[c], batch):
                 r = extract.task_to_pool(ctx, bf, c, t0, t1, crank, *cp.pipe_args(), seg_of["INS"] + crank[c], seg_of["DEL"] + crank[c], seg_base, None,
-                                         name_pool=True, seq_pool=True, aln=(mode == "alignments"))
+                                         name_pool=True, seq_pool=True, aln=(mode == "alignments"), gates=gates,
+                                         bed_regions=None if regions is None else regions.for_task(c, t0, t1))
                 if p.genotype:
                     tables.append((crank[c], r))
         lap("ms_tasks")
@@ -227,6 +240,8 @@ def main(argv=None):
     ap.add_argument("--batch", type=int, default=10_000_000, help="reference bases per extraction task")
     ap.add_argument("--threads", type=int, default=None, help="host threads that inflate the BAM")
     ap.add_argument("--chroms", default=None, help="comma-separated contigs (default: all)")
+    ap.add_argument("--include_bed", "-include_bed", default=None, metavar="FILE",
+                    help="only call where the regions of this BED file are (padded by 1000 bases, as in cuteSV); the calls then depend on --batch")
     ap.add_argument("--tra_gt", default=None, choices=list(TRA_GT_MODES),
                     help="with --genotype: how BND records are genotyped (default: CUTESV_AMD_TRA_GT, else alignments - every alignment counts, as in cuteSV)")
     a = ap.parse_args(argv)
@@ -237,7 +252,8 @@ def main(argv=None):
     cp = CallParams(p, min_mapq=a.min_mapq, max_split_parts=a.max_split_parts, min_read_len=a.min_read_len, min_siglength=a.min_siglength,
                     merge_del_threshold=a.merge_del_threshold, merge_ins_threshold=a.merge_ins_threshold)
     text, svid = call_bam(a.bam, fasta.Reference(a.reference), cp, chroms=a.chroms.split(",") if a.chroms else None, batch=a.batch,
-                          report_readid=a.report_readid, ignore_sequence=a.ignore_sequence, threads=a.threads, as_bytes=True, tra_gt=tra_gt)
+                          report_readid=a.report_readid, ignore_sequence=a.ignore_sequence, threads=a.threads, as_bytes=True, tra_gt=tra_gt,
+                          include_bed=a.include_bed)
     with open(a.out, "wb") as f:
         f.write(text)
     print("%d records: INS %d, DEL %d, BND %d, DUP %d, INV %d" % (text.count(b"\n"), *svid.tolist()))

@@ -28,6 +28,7 @@ struct CigarArgs {
     const unsigned* cigar;          // BAM encoding: oplen << 4 | op  (M I D N S H P = X B: 0..9)
     const i64* ref_start;
     const uint8_t* use;             // nullable
+    int use_mask;                   // the bits of use[read] that count: 255, or CSV_GATE_USE when `use` is the gates column
     int min_siglength;
     i64 merge_ins, merge_del;
     // per read counts (pass 1) / exclusive offsets (after the scan): x = INS signatures, y = INS pieces, z = DEL signatures
@@ -46,7 +47,7 @@ constexpr int CG_TILE = 1024;       // reads per scan tile
 template <bool EMIT> __device__ __forceinline__ int4 cigar_read(const CigarArgs& A, i64 read, i64 o_isig, i64 o_piece, i64 o_dsig)
 {
     const i64 c0 = A.cig_off[read], c1 = A.cig_off[read + 1];
-    if (c1 <= c0 || (A.use && !A.use[read])) return make_int4(0, 0, 0, 0);
+    if (c1 <= c0 || (A.use && !(A.use[read] & A.use_mask))) return make_int4(0, 0, 0, 0);
     const int lane = lane_id();
     const unsigned first = A.cigar[c0];
     i64 refpos = A.ref_start[read];                          // sig_start before the chunk

@@ -59,13 +59,17 @@ struct SplitState {
 };
 // BAM decode: slices of `arena`; the SA ranges are sized after the scan, so they stand alone.  Everything lives until the next
 // decode: csv_cigar_signatures with CSV_CG_FROM_BAM scans cigoff / cigar / start in place, csv_bam_split_inputs reads slim
-// and the record columns, the caller the dev_* pointers of csv_bam_out.
+// and the record columns, the caller the dev_* pointers of csv_bam_out.  gates (csv_bam_task_gates: a byte of CSV_GATE_* bits per
+// record) and gtab (its region table, dead when that call returns) stand alone; the gates belong to the decode they were made
+// from (gates_ok) and die with it: CSV_CG_USE_FROM_GATES and CSV_SA_SEL_FROM_GATES read them in place.
 struct BamState {
     Arena arena;
     Buf slim, recoff, reclen, start, end, flag, mapq, qlen, cl, cr, cls, status, cigoff, saoff, cigsrc, cgb, cge, cigar, long_list, cnt, tot;
-    Buf sabeg, saend;
+    Buf sabeg, saend, gates, gtab;
     i64 n = -1, nops = 0, nsa = 0;             // records / operations / SA tags of the last successful decode (-1: none)
-    void own(std::vector<Buf*>& v) { v.insert(v.end(), {&sabeg, &saend}); }
+    bool gates_ok = false;                     // `gates` holds the gates of that decode
+    std::vector<i64> gtab_h;                   // the host image of gtab: the source of an asynchronous upload, so it lives here and not on a stack
+    void own(std::vector<Buf*>& v) { v.insert(v.end(), {&sabeg, &saend, &gates, &gtab}); }
 };
 // Split inputs of the last decode (sa.hip.h): the tables sized before the kernels run are slices of `arena`, the entry columns
 // are sized by the count pass and stand alone.  They live until the next decode or the next csv_bam_split_inputs:

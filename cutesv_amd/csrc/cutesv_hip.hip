@@ -25,6 +25,7 @@
 #include "seqs.hip.h"
 #include "vcf_strings.hip.h"
 #include "aln.hip.h"
+#include "gates.hip.h"
 
 using namespace csv;
 
@@ -1604,3 +1605,4 @@ int csv_cluster_batch(csv_ctx* c, const csv_batch_in* in, csv_batch_out* out)
 #include "stage_extract.hip.h"
 #include "stage_bam.hip.h"
 #include "stage_aln.hip.h"
+#include "stage_gates.hip.h"

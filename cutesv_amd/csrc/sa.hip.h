@@ -43,6 +43,7 @@ struct SaArgs {
     const i64* sa_off; const i64* sa_beg; const i64* sa_end;
     const int* flag; const int* mapq; const int* qlen; const int* clip_l; const int* clip_r; const i64* ref_start; const i64* ref_end;
     const uint8_t* sel;
+    int sel_mask;                   // the bits of sel[i] that count: 255, or CSV_GATE_SEL when `sel` is the gates column
     int min_mapq, task_rank;
     const uint8_t* names; const i64* name_off; const int* name_rank; int n_names;      // name k = names[name_off[k] .. name_off[k + 1]), ascending
     i64* call_off;                  // n + 1: calls per record, then exclusive offsets
@@ -56,7 +57,7 @@ struct SaArgs {
 __global__ __launch_bounds__(256) void k_sa_mark(SaArgs A)
 {
     const i64 i = (i64)blockIdx.x * 256 + threadIdx.x;
-    if (i < A.n) A.call_off[i] = A.sel[i] ? A.sa_off[i + 1] - A.sa_off[i] : 0;
+    if (i < A.n) A.call_off[i] = (A.sel[i] & A.sel_mask) ? A.sa_off[i + 1] - A.sa_off[i] : 0;
 }
 
 // v[0 .. n): counts -> exclusive offsets in place, v[n] = *total = their sum; n = *n_dev when given (a count an earlier

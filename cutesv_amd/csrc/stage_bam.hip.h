@@ -9,7 +9,7 @@ int csv_bam_decode(csv_ctx* c, const csv_bam_in* in, csv_bam_out* out)
     out->n_ops = out->n_sa = out->n_bad = out->bytes_uploaded = 0; out->ms_device = out->ms_upload = 0;
     out->dev_ref_start = out->dev_ref_end = out->dev_flag = out->dev_mapq = out->dev_query_len = out->dev_clip_left = out->dev_clip_right =
         out->dev_cls = out->dev_cig_off = out->dev_cigar = nullptr;
-    c->bm.n = -1; c->sa.calls = -1; c->seq.n_reads = -1; c->seq.n_qrev = -1;      // (the uploaded read sequences belong to the previous batch)
+    c->bm.n = -1; c->bm.gates_ok = false; c->sa.calls = -1; c->seq.n_reads = -1; c->seq.n_qrev = -1;      // (the uploaded read sequences belong to the previous batch)
     const i64 n = in->n_records, nb = in->slim_bytes;
     if (n < 0 || nb < 0 || in->flags != 0 || (n > 0 && (!in->slim || !in->rec_off || !in->rec_len))) return fail(c, CSV_E_INVALID, "bad BAM chunk header");
     if (n >= (1ll << 31) - 4096) return fail(c, CSV_E_INVALID, "BAM chunk too large (%lld records): split it", (long long)n);
@@ -90,7 +90,11 @@ int csv_bam_split_inputs(csv_ctx* c, const csv_sa_in* in, csv_sa_out* out)
     const i64 n = in->n_records, nn = in->n_names, nbytes = in->name_bytes;
     if (c->bm.n < 0) return fail(c, CSV_E_INVALID, "csv_bam_split_inputs: the context holds no decoded BAM chunk");
     if (n != c->bm.n) return fail(c, CSV_E_INVALID, "csv_bam_split_inputs: n_records is not the record count of the context's last csv_bam_decode");
-    if (in->flags != 0 || nn < 0 || nbytes < 0 || (n > 0 && !in->sel) || (nn > 0 && (!in->name_off || !in->name_rank)) || (nbytes > 0 && !in->names))
+    // CSV_SA_SEL_FROM_GATES: sel[i] is the CSV_GATE_SEL bit of the column csv_bam_task_gates left beside the decode
+    const bool sel_gates = (in->flags & CSV_SA_SEL_FROM_GATES) != 0;
+    if (sel_gates && (in->sel || !c->bm.gates_ok))
+        return fail(c, CSV_E_INVALID, "CSV_SA_SEL_FROM_GATES needs sel = NULL and the gates of the context's last csv_bam_decode (csv_bam_task_gates)");
+    if ((in->flags & ~CSV_SA_SEL_FROM_GATES) != 0 || nn < 0 || nbytes < 0 || (n > 0 && !in->sel && !sel_gates) || (nn > 0 && (!in->name_off || !in->name_rank)) || (nbytes > 0 && !in->names))
         return fail(c, CSV_E_INVALID, "bad split-input header");
     // the kernels index `names` with these offsets and search the table by halving: both are checked here
     for (i64 k = 0; k < nn; k++) {
@@ -115,7 +119,8 @@ int csv_bam_split_inputs(csv_ctx* c, const csv_sa_in* in, csv_sa_out* out)
     P.add(c->sa.readlen, (max_calls + 1) * 8); P.add(c->sa.status, max_calls + 1); P.add(c->sa.tot, 32);
     TRY(commit_synced(c, c->sa.arena, P));
     hipStream_t st = c->stream;
-    TRY(h2d(c, c->sa.sel, in->sel, n)); TRY(h2d(c, c->sa.names, in->names, nbytes));
+    if (!sel_gates) TRY(h2d(c, c->sa.sel, in->sel, n));
+    TRY(h2d(c, c->sa.names, in->names, nbytes));
     if (nn) { TRY(h2d(c, c->sa.nameoff, in->name_off, (nn + 1) * 8)); TRY(h2d(c, c->sa.namerank, in->name_rank, nn * 4)); }
     HIP_TRY(c, hipMemsetAsync(c->sa.tot.p, 0, 32, st));
     SaArgs A{};
@@ -123,7 +128,7 @@ int csv_bam_split_inputs(csv_ctx* c, const csv_sa_in* in, csv_sa_out* out)
     A.slim = dp<uint8_t>(c->bm.slim); A.sa_off = dp<i64>(c->bm.saoff); A.sa_beg = dp<i64>(c->bm.sabeg); A.sa_end = dp<i64>(c->bm.saend);
     A.flag = dp<int>(c->bm.flag); A.mapq = dp<int>(c->bm.mapq); A.qlen = dp<int>(c->bm.qlen); A.clip_l = dp<int>(c->bm.cl); A.clip_r = dp<int>(c->bm.cr);
     A.ref_start = dp<i64>(c->bm.start); A.ref_end = dp<i64>(c->bm.end);
-    A.sel = dp<uint8_t>(c->sa.sel); A.min_mapq = in->min_mapq; A.task_rank = in->task_rank;
+    A.sel = sel_gates ? dp<uint8_t>(c->bm.gates) : dp<uint8_t>(c->sa.sel); A.sel_mask = sel_gates ? CSV_GATE_SEL : 255; A.min_mapq = in->min_mapq; A.task_rank = in->task_rank;
     A.names = dp<uint8_t>(c->sa.names); A.name_off = dp<i64>(c->sa.nameoff); A.name_rank = dp<int>(c->sa.namerank); A.n_names = (int)nn;
     A.call_off = dp<i64>(c->sa.calloff); A.call_rec = dp<int>(c->sa.callrec); A.call_sa = dp<i64>(c->sa.callsa); A.ent_off = dp<i64>(c->sa.entoff);
     A.read_len = dp<i64>(c->sa.readlen); A.status = dp<uint8_t>(c->sa.status); A.tot = dp<i64>(c->sa.tot);

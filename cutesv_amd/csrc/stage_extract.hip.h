@@ -13,6 +13,10 @@ int csv_cigar_signatures(csv_ctx* c, const csv_cigar_in* in, csv_cigar_out* out)
     const bool from_bam = (in->flags & CSV_CG_FROM_BAM) != 0;
     if (from_bam && (c->bm.n < 0 || n != c->bm.n)) return fail(c, CSV_E_INVALID, "CSV_CG_FROM_BAM: n_reads is not the record count of the context's last csv_bam_decode");
     if (n < 0 || (n > 0 && !from_bam && (!in->cig_off || !in->ref_start))) return fail(c, CSV_E_INVALID, "bad CIGAR batch header");
+    // CSV_CG_USE_FROM_GATES: use[r] is the CSV_GATE_USE bit of the column csv_bam_task_gates left beside that decode
+    const bool use_gates = (in->flags & CSV_CG_USE_FROM_GATES) != 0;
+    if (use_gates && (!from_bam || in->use || !c->bm.gates_ok))
+        return fail(c, CSV_E_INVALID, "CSV_CG_USE_FROM_GATES needs CSV_CG_FROM_BAM, use = NULL and the gates of the context's last csv_bam_decode (csv_bam_task_gates)");
     // CSV_CG_SEQ_TO_POOL: the INS rows' bases are cut out of the uploaded read sequences, whose index space is this batch's
     const bool seq_to_pool = (in->flags & CSV_CG_SEQ_TO_POOL) != 0;
     if (seq_to_pool && !(in->flags & CSV_CG_TO_POOL)) return fail(c, CSV_E_INVALID, "CSV_CG_SEQ_TO_POOL needs CSV_CG_TO_POOL");
@@ -46,7 +50,8 @@ int csv_cigar_signatures(csv_ctx* c, const csv_cigar_in* in, csv_cigar_out* out)
     CigarArgs A{};
     A.n_reads = n; A.cig_off = dp<i64>(c->cg.off); A.cigar = dp<unsigned>(c->cg.ops); A.ref_start = dp<i64>(c->cg.start);
     if (from_bam) { A.cig_off = dp<i64>(c->bm.cigoff); A.cigar = dp<unsigned>(c->bm.cigar); A.ref_start = dp<i64>(c->bm.start); }
-    A.use = in->use ? dp<uint8_t>(c->cg.use) : nullptr;
+    A.use = in->use ? dp<uint8_t>(c->cg.use) : use_gates ? dp<uint8_t>(c->bm.gates) : nullptr;
+    A.use_mask = use_gates ? CSV_GATE_USE : 255;
     A.min_siglength = in->min_siglength; A.merge_ins = in->merge_ins_threshold; A.merge_del = in->merge_del_threshold;
     A.cnt = dp<int4>(c->cg.cnt); A.tile_sum = dp<i64>(c->cg.tiles); A.totals = dp<i64>(c->cg.tot);
     A.ins_read = dp<int>(c->cg.iread); A.ins_pos = dp<i64>(c->cg.ipos); A.ins_len = dp<i64>(c->cg.ilen); A.ins_piece0 = dp<i64>(c->cg.ip0);

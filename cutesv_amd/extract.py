@@ -12,6 +12,8 @@ reads, make one call here, and extend candidate["INS"] / candidate["DEL"] with t
 body fed from a BAM file by the native reader (cutesv_amd/bam.py): no pysam and no object per record.  With sa="device" the
 SA text is parsed where the decode left it (`split_inputs_bam`, the face of `csv_bam_split_inputs`, sa.hip.h) and
 `task_to_pool` takes a task's region of the file to rows of the context's device-resident pool with no Python per record.
+With gates="device" the task gates - `_gates`: secondary records, the task's start, --include_bed, read length, MAPQ - are evaluated
+by one kernel where the decoded columns are (`task_gates`, the face of `csv_bam_task_gates`, gates.hip.h) and the scans read them there.
 """
 import ctypes as C
 
@@ -103,10 +105,13 @@ def _to_pool(cin, pool):
 
 def _run(fn, handle, cig_off, cigar, ref_start, use, min_siglength, merge_ins_threshold, merge_del_threshold, check, pool=None, host_outputs=True,
          from_bam=None):
-    use = None if use is None else np.ascontiguousarray(use, np.uint8)
+    use_gates = isinstance(use, str)
+    if use_gates and (use != "gates" or from_bam is None):
+        raise ValueError("use: an array, None or - with from_bam - 'gates', not %r" % (use,))
+    use = None if use is None or use_gates else np.ascontiguousarray(use, np.uint8)
     if from_bam is not None:                              # CSV_CG_FROM_BAM: the three columns are on the device already (bam.decode)
         n, n_ops = int(from_bam["n"]), int(from_bam["n_ops"])
-        cin = CigarIn(n_reads=n, flags=_abi.CG_FROM_BAM)
+        cin = CigarIn(n_reads=n, flags=_abi.CG_FROM_BAM | (_abi.CG_USE_FROM_GATES if use_gates else 0))
     else:
         cig_off = np.ascontiguousarray(cig_off, np.int64); cigar = np.ascontiguousarray(cigar, np.uint32)
         ref_start = np.ascontiguousarray(ref_start, np.int64)
@@ -137,7 +142,8 @@ def cigar_signatures(ctx, cig_off, cigar, ref_start, use=None, min_siglength=10,
     sequences `upload_read_sequences` left on the device (one per read of this batch; query_len must be their l_seq) into the
     context's sequence pool (`rebuild.seq_pool_get`).
     from_bam = the columns `bam.decode(ctx, chunk)` returned: cig_off / cigar / ref_start are not taken from the arguments (pass
-    None) but scanned where that decode left them on the device (CSV_CG_FROM_BAM); `use` is still the caller's."""
+    None) but scanned where that decode left them on the device (CSV_CG_FROM_BAM); `use` is still the caller's - or "gates": the
+    USE bit of the column `task_gates` left beside that decode (CSV_CG_USE_FROM_GATES), which then never leaves the device."""
     return _run(lib().csv_cigar_signatures, ctx._h, cig_off, cigar, ref_start, use, min_siglength, merge_ins_threshold, merge_del_threshold, ctx._check, pool=pool,
                 host_outputs=host_outputs, from_bam=None if from_bam is None else dict(n=len(from_bam["ref_start"]), n_ops=from_bam["n_ops"]))
 
@@ -258,21 +264,28 @@ def _name_table(chrom_rank):
     return blob, off, np.asarray([r for _, r in items], np.int32)
 
 
-def split_inputs_bam(ctx, chunk, cols, sel, chrom_rank, chrom, min_mapq, host_outputs=True):
+def split_inputs_bam(ctx, chunk, cols, sel, chrom_rank, chrom, min_mapq, host_outputs=True, gate_bits=None):
     """csv_bam_split_inputs on the context's last `bam.decode(ctx, chunk)` (= cols): the SA tags of the records with sel != 0,
     parsed where the decode left them -> the dict `encode_split_reads` returns for those reads built the old way
     (_primary_info + Chunk.sa_values; same keys, same dtypes), one call per (selected record, SA tag), plus call_rec (the
     call's record in the chunk), status (per call, see sa_status: a flagged call has NO entries here and is the caller's to
     send through encode_split_reads), n_calls, n_entries, n_flagged, ms_device.  The columns also stay on the device until
     the context's next decode / split inputs: split_signatures(ctx, None, from_bam=<this dict>) analyses them there.
-    host_outputs=False: only call_rec and status come back (the entry columns and ent_off / read_len stay empty)."""
+    host_outputs=False: only call_rec and status come back (the entry columns and ent_off / read_len stay empty).
+    sel="gates": the selection is the SEL bit of the column `task_gates` left beside the decode (CSV_SA_SEL_FROM_GATES) and is not
+    sent; gate_bits = the bytes task_gates returned, for the one look the host takes at the selection (a contig without a rank)."""
     n = chunk.n
+    sel_gates = isinstance(sel, str)
+    if sel_gates:
+        if sel != "gates" or gate_bits is None:
+            raise ValueError("sel: an array or 'gates' with gate_bits=, not %r" % (sel,))
+        sel = (np.asarray(gate_bits) & _abi.GATE_SEL) != 0
     sel = np.ascontiguousarray(sel, np.uint8)
     assert len(sel) == n
     if chrom not in chrom_rank and bool(np.any((sel != 0) & (np.asarray(cols["mapq"]) >= min_mapq))):
         raise KeyError(chrom)                              # (encode_split_reads looks the primary's contig up, too)
     blob, name_off, name_rank = _name_table(chrom_rank)
-    sin = SaIn(n_records=n, sel=sel.ctypes.data if n else None, min_mapq=int(min_mapq), task_rank=int(chrom_rank.get(chrom, -1)), n_names=len(name_rank),
+    sin = SaIn(n_records=n, sel=sel.ctypes.data if n and not sel_gates else None, flags=_abi.SA_SEL_FROM_GATES if sel_gates else 0, min_mapq=int(min_mapq), task_rank=int(chrom_rank.get(chrom, -1)), n_names=len(name_rank),
                names=blob.ctypes.data if len(blob) else None, name_bytes=len(blob), name_off=name_off.ctypes.data, name_rank=name_rank.ctypes.data if len(name_rank) else None)
     cap_calls = int(cols["n_sa"])
     # an entry the device accepts has at least ten bytes ("a,1,+,*,0;"), a flagged call has none: plus one primary entry per call
@@ -569,7 +582,7 @@ class _Lazy:
 
 
 def single_pipe_bam(ctx_or_fns, bamfile, chrom, task_start, task_end, chrom_rank, sv_size, min_mapq, max_split_parts, min_read_len, min_siglength,
-                    merge_del_threshold, merge_ins_threshold, max_size, bed_regions=None, sa="host"):
+                    merge_del_threshold, merge_ins_threshold, max_size, bed_regions=None, sa="host", gates="host"):
     """`single_pipe` for the records `fetch(chrom, task_start, task_end)` would yield, read from `bamfile` (a bam.BamFile)
     without an object per record: -> (cand, reads_info) exactly as `single_pipe` returns them.
 
@@ -585,17 +598,23 @@ def single_pipe_bam(ctx_or_fns, bamfile, chrom, task_start, task_end, chrom_rank
     sa: "host" - the SA values are sliced out of the chunk and parsed by encode_split_reads - or "device" (needs a Context): they
     are parsed where the decode left them (split_inputs_bam) and analysed in place; only the calls the device flags (text
     outside its strict grammar) go through encode_split_reads, and their candidates are merged at their place in read order.
-    Same result either way."""
+    Same result either way.
+
+    gates: "host" - `_gates` on the downloaded columns, `use` (and `sel`) uploaded again - or "device" (needs a Context): one kernel
+    evaluates them where the columns are (`task_gates`), the scans read its byte column in place, and the host takes the reads rows
+    and the selection from the bytes it returns.  Same result either way.  bed_regions: None, or the regions OF THIS TASK
+    (bed.Regions.for_task) - an empty list passes no read."""
     from . import bam as bam_mod
     on_device = not isinstance(ctx_or_fns, (tuple, list))
     if sa not in ("host", "device"):
         raise ValueError("sa must be 'host' or 'device', not %r" % (sa,))
     if sa == "device" and not on_device:
         raise ValueError("sa='device' needs an engine.Context: a (cigar_fn, split_fn) pair has no device to parse on")
+    _check_gates(gates, on_device)
     chunk = bamfile.records(chrom, task_start, task_end)
     cols = bam_mod.decode(ctx_or_fns, chunk, host_outputs=False) if on_device else bam_mod.decode_host(chunk)
     start, end, flag, mapq, qlen = cols["ref_start"], cols["ref_end"], cols["flag"], cols["mapq"], cols["query_len"]
-    gate, parsed, use, sel = _gates(cols, task_start, bed_regions, min_read_len, min_mapq)
+    _, use, sel, in_table, bits = _task_gates(ctx_or_fns, cols, task_start, bed_regions, min_read_len, min_mapq, gates)
     kw = dict(min_siglength=min_siglength, merge_ins_threshold=merge_ins_threshold, merge_del_threshold=merge_del_threshold)
     if on_device:
         sig = cigar_signatures(ctx_or_fns, None, None, None, use, from_bam=cols, **kw)
@@ -605,7 +624,7 @@ def single_pipe_bam(ctx_or_fns, bamfile, chrom, task_start, task_end, chrom_rank
         sig = cigar_fn(cols["cig_off"], cols["cigar"], start, use, **kw)
     names, seqs = _Lazy(chunk.name), _Lazy(chunk.sequence)
     if sa == "device":
-        cand = _assemble_device(ctx_or_fns, chunk, cols, sig, names, seqs, sel, chrom, chrom_rank, sv_size, min_mapq, max_split_parts, max_size)
+        cand = _assemble_device(ctx_or_fns, chunk, cols, sig, names, seqs, sel, chrom, chrom_rank, sv_size, min_mapq, max_split_parts, max_size, gate_bits=bits)
     else:
         sp = []
         for i in np.flatnonzero(sel).tolist():
@@ -613,7 +632,7 @@ def single_pipe_bam(ctx_or_fns, bamfile, chrom, task_start, task_end, chrom_rank
                                     int(start[i]), int(end[i]), chrom)
             sp.append((i, primary, chunk.sa_values(cols, i), int(qlen[i]), int(flag[i]) == 16))
         cand = _assemble(sig, names, seqs, sp, chrom, chrom_rank, sv_size, min_mapq, max_split_parts, max_size, split_fn)
-    reads_info = [(int(start[i]), int(end[i]), 1 if cols["cls"][i] == 1 else 0, names[i], chrom) for i in np.flatnonzero(gate & (mapq >= min_mapq)).tolist()]
+    reads_info = [(int(start[i]), int(end[i]), 1 if cols["cls"][i] == 1 else 0, names[i], chrom) for i in np.flatnonzero(in_table).tolist()]
     return cand, reads_info
 
 
@@ -628,12 +647,60 @@ def _gates(cols, task_start, bed_regions, min_read_len, min_mapq):
     return gate, parsed, use, parsed & (cols["cls"] == 1) & (cols["sa_off"][1:] > cols["sa_off"][:-1])
 
 
-def _split_on_device(ctx, chunk, cols, sel, chrom, chrom_rank, min_mapq, skw, pool=None):
+def gate_bits_host(cols, task_start, regions, min_read_len, min_mapq):
+    """The byte column csv_bam_task_gates makes, on the host: `_gates` as CSV_GATE_* bits per record (TASK = gate, PARSED, USE, SEL,
+    READS = gate & mapq >= min_mapq: the rows of the reads table).  regions: None or the task's (k, 2) list (bed.Regions.for_task).
+    The CPU checker of gates.hip.h and the statement of its contract."""
+    gate, parsed, use, sel = _gates(cols, task_start, regions, min_read_len, min_mapq)
+    reads = gate & (cols["mapq"] >= min_mapq)
+    return (gate * _abi.GATE_TASK + parsed * _abi.GATE_PARSED + (use != 0) * _abi.GATE_USE + sel * _abi.GATE_SEL + reads * _abi.GATE_READS).astype(np.uint8)
+
+
+def task_gates(ctx, n, task_start, min_read_len, min_mapq, regions=None, timing=None):
+    """csv_bam_task_gates on the context's last `bam.decode` (n = its record count): the gates of a task evaluated where the columns
+    are -> bits, uint8 per record (`gate_bits_host` is the same on the host).  regions: None - no BED gate - or the task's list of
+    (b0, b1) (bed.Regions.for_task; any order: the call wants the starts ascending, so an unsorted list is sorted here, which
+    changes no answer); an empty list passes no record.  The column also stays on the device until the next decode:
+    cigar_signatures(use="gates") and split_inputs_bam(sel="gates") read it there.  timing: a dict that receives ms_device."""
+    flags, nr, beg, end = 0, 0, None, None
+    if regions is not None:
+        r = np.asarray(regions, np.int64).reshape(-1, 2)
+        if len(r) > 1 and bool(np.any(r[1:, 0] < r[:-1, 0])):
+            r = r[np.argsort(r[:, 0], kind="stable")]
+        flags, nr, beg, end = _abi.GT_BED, len(r), np.ascontiguousarray(r[:, 0]), np.ascontiguousarray(r[:, 1])
+    bits = np.zeros(int(n), np.uint8)
+    ms = C.c_float(0)
+    ctx._check(lib().csv_bam_task_gates(ctx._h, int(n), int(task_start), int(min_read_len), int(min_mapq), flags, nr, beg.ctypes.data if nr else None,
+                                        end.ctypes.data if nr else None, bits.ctypes.data if n else None, C.byref(ms)))
+    if timing is not None:
+        timing["ms_device"] = float(ms.value)
+    return bits
+
+
+def _task_gates(ctx, cols, task_start, bed_regions, min_read_len, min_mapq, gates):
+    """the gates of a task, on the host (`_gates`) or on the device (`task_gates`) -> (gate, use, sel, reads rows, bits or None):
+    the same arrays either way; with "device" `use` is the string "gates" - the column stays where the scans read it"""
+    if gates == "host":
+        gate, _, use, sel = _gates(cols, task_start, bed_regions, min_read_len, min_mapq)
+        return gate, use, sel, gate & (cols["mapq"] >= min_mapq), None
+    bits = task_gates(ctx, len(cols["ref_start"]), task_start, min_read_len, min_mapq, bed_regions)
+    return (bits & _abi.GATE_TASK) != 0, "gates", (bits & _abi.GATE_SEL) != 0, (bits & _abi.GATE_READS) != 0, bits
+
+
+def _check_gates(gates, on_device):
+    if gates not in ("host", "device"):
+        raise ValueError("gates must be 'host' or 'device', not %r" % (gates,))
+    if gates == "device" and not on_device:
+        raise ValueError("gates='device' needs an engine.Context: a (cigar_fn, split_fn) pair has no device to evaluate them on")
+
+
+def _split_on_device(ctx, chunk, cols, sel, chrom, chrom_rank, min_mapq, skw, pool=None, gate_bits=None):
     """The split-read analysis of the records `sel` of the context's last decode: their SA tags are parsed on the device and
     analysed in place (with `pool`: straight to pool rows, only the count comes back); the calls the device flags go through
     encode_split_reads and the host-fed analysis.  -> (split inputs, device-side result or None when there is no call, indices
-    of the flagged calls, their reads, host-side candidates or None when nothing is flagged)"""
-    si = split_inputs_bam(ctx, chunk, cols, sel, chrom_rank, chrom, min_mapq, host_outputs=False)
+    of the flagged calls, their reads, host-side candidates or None when nothing is flagged).  gate_bits (the bytes of task_gates):
+    the device takes the selection from its own gates column; `sel` is the same selection on the host, for the flagged calls"""
+    si = split_inputs_bam(ctx, chunk, cols, sel if gate_bits is None else "gates", chrom_rank, chrom, min_mapq, host_outputs=False, gate_bits=gate_bits)
     dsig = split_signatures(ctx, None, from_bam=si, pool=pool, host_outputs=pool is None, **skw) if si["n_calls"] else None
     calls, reads, fsig = np.zeros(0, np.int64), [], None
     if si["n_flagged"]:
@@ -642,11 +709,11 @@ def _split_on_device(ctx, chunk, cols, sel, chrom, chrom_rank, min_mapq, skw, po
     return si, dsig, calls, reads, fsig
 
 
-def _assemble_device(ctx, chunk, cols, sig, names, seqs, sel, chrom, chrom_rank, sv_size, min_mapq, max_split_parts, max_size):
+def _assemble_device(ctx, chunk, cols, sig, names, seqs, sel, chrom, chrom_rank, sv_size, min_mapq, max_split_parts, max_size, gate_bits=None):
     """_assemble for sa="device": the split-read inputs of the records `sel` are parsed and analysed on the device; the calls
     it flags go through encode_split_reads and their candidates are merged at their place in call (= read) order"""
     si, ssig, calls, _, fsig = _split_on_device(ctx, chunk, cols, sel, chrom, chrom_rank, min_mapq,
-                                                dict(sv_size=sv_size, min_mapq=min_mapq, max_split_parts=max_split_parts, max_size=max_size))
+                                                dict(sv_size=sv_size, min_mapq=min_mapq, max_split_parts=max_split_parts, max_size=max_size), gate_bits=gate_bits)
     if fsig is not None:
         both = {k: np.concatenate([ssig[k], calls[fsig[k]].astype(np.int32) if k == "read" else fsig[k]]) for k, _, _ in _SPLIT_OUT}
         order = np.argsort(both["read"], kind="stable")      # (a call's candidates all come from one side, in their order)
@@ -657,7 +724,8 @@ def _assemble_device(ctx, chunk, cols, sig, names, seqs, sel, chrom, chrom_rank,
 
 # ------------------------------------------------------------------------------------ a task's region -> rows of the pool
 def task_to_pool(ctx, bamfile, chrom, task_start, task_end, chrom_rank, sv_size, min_mapq, max_split_parts, min_read_len, min_siglength,
-                 merge_del_threshold, merge_ins_threshold, max_size, seg_ins, seg_del, seg_base, read_base, bed_regions=None, name_pool=False, seq_pool=False, aln=False):
+                 merge_del_threshold, merge_ins_threshold, max_size, seg_ins, seg_del, seg_base, read_base, bed_regions=None, name_pool=False, seq_pool=False, aln=False,
+                 gates="host"):
     """The body of an extraction task without a candidate tuple, a name string or a sequence: the records of the region
     (`bamfile.records`) are decoded on the device, the CIGAR scan appends its signatures to the context's pool from the decoded
     columns (CSV_CG_FROM_BAM | CSV_CG_TO_POOL), the SA tags are parsed there (split_inputs_bam) and the split-read analysis appends
@@ -685,8 +753,13 @@ def task_to_pool(ctx, bamfile, chrom, task_start, task_end, chrom_rank, sv_size,
     aln=True (needs name_pool=True): the records that START in [task_start, task_end) - all of them, whatever their flag or MAPQ -
     become rows of the context's alignment table (aln.append_decoded, on the device, right after the decode) with their name-pool
     indices as ids: what aln.tra_genotype walks.  The caller resets the table (aln.reset) and runs a contig's tasks in order; the
-    result gains n_aln_rows."""
+    result gains n_aln_rows.  The table is filled in front of the gates: a BED does not restrict it (the reference's call_gt reads the BAM
+    whatever the BED says).
+
+    gates="device": the gates are evaluated by a kernel where the columns are (`task_gates`) and `use` / `sel` never leave the
+    device; the reads rows and the `want` flags of the sequence upload come from the bytes it returns.  Same rows either way."""
     from . import bam as bam_mod, rebuild
+    _check_gates(gates, True)
     if aln and not name_pool:
         raise ValueError("aln=True needs name_pool=True: a row's id is its name's index")
     if name_pool:
@@ -706,15 +779,15 @@ def task_to_pool(ctx, bamfile, chrom, task_start, task_end, chrom_rank, sv_size,
         from . import aln as aln_mod
         n_aln = aln_mod.append_decoded(ctx, chrom_rank[chrom], task_start, task_end, read_base)
     start, end, mapq, qlen = cols["ref_start"], cols["ref_end"], cols["mapq"], cols["query_len"]
-    gate, _, use, sel = _gates(cols, task_start, bed_regions, min_read_len, min_mapq)
+    _, use, sel, in_table, bits = _task_gates(ctx, cols, task_start, bed_regions, min_read_len, min_mapq, gates)
     if seq_pool:
         s_off, l_seq = chunk.sequence_columns()
-        upload_read_sequences(ctx, chunk.host, s_off, l_seq, want=(use != 0) | sel)
+        upload_read_sequences(ctx, chunk.host, s_off, l_seq, want=(use != 0) | sel if bits is None else (bits & (_abi.GATE_USE | _abi.GATE_SEL)) != 0)
     sig = cigar_signatures(ctx, None, None, None, use, min_siglength=min_siglength, merge_ins_threshold=merge_ins_threshold, merge_del_threshold=merge_del_threshold,
                            pool=dict(seg_ins=seg_ins, seg_del=seg_del, read_base=read_base, query_len=qlen, seqs=seq_pool), host_outputs=False, from_bam=cols)
     si, dsig, calls, reads, fsig = _split_on_device(ctx, chunk, cols, sel, chrom, chrom_rank, min_mapq,
                                                     dict(sv_size=sv_size, min_mapq=min_mapq, max_split_parts=max_split_parts, max_size=max_size),
-                                                    pool=dict(seg_base=seg_base, read_base=read_base, seqs=seq_pool))
+                                                    pool=dict(seg_base=seg_base, read_base=read_base, seqs=seq_pool), gate_bits=bits)
     n_split, n_host = 0 if dsig is None else dsig["n"], 0
     if fsig is not None:
         rows = pool_rows_of_split(fsig, seg_base, 0, [r[2] for r in reads])
@@ -726,7 +799,7 @@ def task_to_pool(ctx, bamfile, chrom, task_start, task_end, chrom_rank, sv_size,
         if seq_pool and len(ins):                             # their INS rows: cut on the host, as single_pipe_bam does
             cut = pool_ins_sequences_host(_Lazy(chunk.sequence), cols["flag"] == 16, None, fsig, call_read=rec)
             rebuild.seq_pool_put(ctx, first_row + ins, [b for b, _ in cut], [h for _, h in cut])
-    keep = np.flatnonzero(gate & (mapq >= min_mapq))
+    keep = np.flatnonzero(in_table)
     extra = dict(name_base=read_base) if name_pool else {}
     if seq_pool:
         extra["n_seq_rows"], extra["n_seq_bytes"] = rebuild.seq_pool_rows(ctx)

@@ -648,11 +648,15 @@ typedef struct csv_cigar_in {
 } csv_cigar_in;
 enum { CSV_CG_TO_POOL = 1,
        /* cig_off, cigar and ref_start are NOT read from `in`: they are the device columns the context's last csv_bam_decode
-        * made (n_reads must be its record count).  `use` is still the caller's host array.  The CIGARs never cross PCIe. */
+        * made (n_reads must be its record count).  `use` is still the caller's host array (or CSV_CG_USE_FROM_GATES).  The CIGARs never cross PCIe. */
        CSV_CG_FROM_BAM = 2,
        /* only with CSV_CG_TO_POOL, in csv_cigar_in.flags and csv_split_in.flags alike (there 4 is CSV_SP_FROM_BAM): the INS rows'
         * bases go to the context's sequence pool (csv_seq_* above) */
-       CSV_CG_SEQ_TO_POOL = 8 };
+       CSV_CG_SEQ_TO_POOL = 8,
+       /* only with CSV_CG_FROM_BAM and use == NULL: use[r] is bit CSV_GATE_USE of the gates csv_bam_task_gates left in device memory
+        * beside that decode.  CSV_E_INVALID, nothing launched: CSV_CG_FROM_BAM is missing, `use` is given as well, or the context
+        * holds no gates of its last csv_bam_decode. */
+       CSV_CG_USE_FROM_GATES = 16 };
 
 typedef struct csv_cigar_out {
     int64_t  cap_sig_ins, cap_piece_ins, cap_sig_del;
@@ -932,7 +936,7 @@ typedef struct csv_sa_in {
     int32_t         min_mapq;
     int32_t         task_rank;       /* rank of the contig the chunk lies on */
     int32_t         n_names;
-    int32_t         flags;           /* 0 */
+    int32_t         flags;           /* 0 or CSV_SA_SEL_FROM_GATES */
     const uint8_t*  names;   int64_t name_bytes;
     const int64_t*  name_off;        /* n_names + 1 */
     const int32_t*  name_rank;       /* n_names */
@@ -947,9 +951,36 @@ typedef struct csv_sa_out {
     int32_t  reserved;
 } csv_sa_out;
 
+/* csv_sa_in.flags: sel must be NULL, sel[i] is bit CSV_GATE_SEL of the gates csv_bam_task_gates left beside the decode.  CSV_E_INVALID,
+ * nothing launched: `sel` is given as well, or the context holds no gates of its last csv_bam_decode. */
+enum { CSV_SA_SEL_FROM_GATES = 1 };
+
 int csv_bam_split_inputs(csv_ctx* ctx, const csv_sa_in* in, csv_sa_out* out);
 /* sizeof of 0 csv_sa_in, 1 csv_sa_out; -1 otherwise */
 int csv_sa_struct_size(int which);
+
+/* The gates of an extraction task on the records of the context's last csv_bam_decode (gates.hip.h): one
+ * byte of CSV_GATE_* bits per record, as single_pipe (cuteSV main script :711, :715-725) and parse_read (:607, :614) apply them.
+ *   TASK    cls != 0 && ref_start >= task_start && in_bed        (in_bed is true without CSV_GT_BED)
+ *   PARSED  TASK && query_len >= min_read_len
+ *   USE     PARSED && mapq >= min_mapq                           (the `use` column of csv_cigar_signatures)
+ *   SEL     PARSED && cls == 1 && the record has an SA tag       (the `sel` column of csv_bam_split_inputs)
+ *   READS   TASK && mapq >= min_mapq                             (the rows of the reads table, :729-733)
+ * CSV_GT_BED: in_bed = some region k has region_end[k] > ref_start && region_beg[k] < ref_end - the reference's
+ * `not (pos_end <= b0 or pos_start >= b1)` on the list of the record's TASK (load_bed, cuteSV_genotype.py:704-726), applied as
+ * written: a zero-span record (ref_end == ref_start) lies in no region it merely touches, regions are not merged, a region with
+ * end < beg is legal.  region_beg must not decrease (load_bed sorts by (start, end)); 0 regions: no record passes.
+ * The column stays in device memory of the context until its next csv_bam_decode - CSV_CG_USE_FROM_GATES and CSV_SA_SEL_FROM_GATES
+ * read it there - and is copied to `bits` when that is not NULL; a later call on the same decode replaces it.  ms_device
+ * (nullable): the kernel alone (HIP events).  n_records == 0 succeeds and launches nothing.
+ * CSV_E_INVALID, before anything is launched, the context (and gates it already holds) unchanged: no decode in the context,
+ * n_records is not the decode's, n_regions < 0, regions without CSV_GT_BED, CSV_GT_BED with n_regions > 0 and a NULL array,
+ * region_beg that decreases, unknown flag bits. */
+enum { CSV_GT_BED = 1 };
+enum { CSV_GATE_TASK = 1, CSV_GATE_PARSED = 2, CSV_GATE_USE = 4, CSV_GATE_SEL = 8, CSV_GATE_READS = 16 };
+int csv_bam_task_gates(csv_ctx* ctx, int64_t n_records, int64_t task_start, int32_t min_read_len, int32_t min_mapq, int32_t flags,
+                       int64_t n_regions, const int64_t* region_beg, const int64_t* region_end,
+                       uint8_t* bits /* n_records, nullable */, float* ms_device /* nullable */);
 
 #ifdef __cplusplus
 }

@@ -1,7 +1,7 @@
 """What call.call_bam costs, stage by stage, against the route the same file took before it, on the input
 of scripts/bam_stage.py (one synthetic contig of long reads).
 
-    python scripts/call_stage.py [--reads N] [--reps R] [--warmup W] [--bam PATH] [--out profiles/call_bam.json]
+    python scripts/call_stage.py [--reads N] [--reps R] [--warmup W] [--bam PATH] [--gates host|device] [--out profiles/call_bam.json]
 
 Per pass, in one process and on one context: call_bam (wall, and its stages: tasks, rebuild, cluster, the two gathers, emit) with
 report_readid, and the earlier route - single_pipe_bam per task, store_from_unsorted with sequences, x.5 flags and names,
@@ -34,6 +34,7 @@ def main():
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--bam", default=None, help="reuse / write the input here (default: a temporary file)")
+    ap.add_argument("--gates", default=None, choices=["host", "device"], help="where call_bam evaluates the task gates (default: call_bam's own choice)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     import bam_writer
@@ -55,7 +56,7 @@ def main():
         for it in range(a.warmup + a.reps):
             t, tp = {}, {}
             t0 = time.perf_counter()
-            text, svid = call.call_bam(bf, reference, cp, ctx=ctx, batch=CONTIG_LEN, report_readid=True, timings=t)
+            text, svid = call.call_bam(bf, reference, cp, ctx=ctx, batch=CONTIG_LEN, report_readid=True, timings=t, gates=a.gates)
             t["ms_call_bam_wall"] = (time.perf_counter() - t0) * 1e3
             t0 = time.perf_counter()
             want = call_helpers.parent_route(ctx, bf, reference, cp, batch=CONTIG_LEN, report_readid=True, timings=tp)
@@ -66,7 +67,7 @@ def main():
                 for k in keys:
                     runs[k].append(t[k])
             info = dict(n_records_text=text.count("\n"), text_bytes=len(text), svid=svid.tolist())
-    out = dict(input=dict(reads=a.reads, seed=a.seed, reps=a.reps, warmup=a.warmup, min_support=1, report_readid=True), **info, **{k: spread(v) for k, v in runs.items()})
+    out = dict(input=dict(reads=a.reads, seed=a.seed, reps=a.reps, warmup=a.warmup, min_support=1, report_readid=True, gates=a.gates or call.DEFAULT_GATES), **info, **{k: spread(v) for k, v in runs.items()})
     out["call_bam_over_parent"] = out["ms_call_bam_wall"]["median"] / out["ms_parent_wall"]["median"]
     out["gathers_share_of_call_bam"] = (out["ms_alt_gather"]["median"] + out["ms_support_join"]["median"]) / out["ms_call_bam_wall"]["median"]
     print(json.dumps(out, indent=1))
