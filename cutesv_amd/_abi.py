@@ -19,6 +19,7 @@ ERR_NAME = {OK: "CSV_OK", E_INVALID: "CSV_E_INVALID", E_CAPACITY: "CSV_E_CAPACIT
 N_STAGES = 24
 GL_TABLE_SIZE = 101 * 101 + 2
 IN_PER_SIG, IN_READS_SORTED, IN_SIG_I32, IN_READS_I32, IN_DEVICE_COLUMNS, IN_SIG_DELTA16, IN_READS_DELTA16 = 1, 2, 4, 8, 16, 32, 64     # csv_batch_in.flags
+IN_READS_DEVICE = 128                  # ... r_start / r_end / r_primary / r_id are device addresses (with IN_READS_I32)
 RB_KEEP_ON_DEVICE = 1
 RB_FROM_POOL = 2                        # ... the rows are the context's device-resident signature pool
 RB_RANK_FROM_NAMES = 4                  # ... with RB_FROM_POOL: the read ranks are those of the context's name pool (csv_name_ranks)
@@ -36,6 +37,7 @@ BAM_RESTART, BAM_COUNT_ONLY = 1, 2     # csv_bam_read flags
 SEG_KEY_RANGE = 1                             # csv_batch_out.seg_status bits
 OUT_NO_SUPPORT_LIST, OUT_COORD_I32 = 1, 2     # csv_batch_out.flags (ABI v7)
 ALN_FROM_KEPT_REBUILD, ALN_SUPPORT_I32 = 1, 2  # csv_aln_tra_genotype flags
+RD_RANK_FROM_NAMES = 1                 # csv_reads_batch_columns flags: r_id = the name pool's rank of the row's name id
 OPTIONAL_CALL_FIELDS = ("call_cluster", "call_aux", "cipos", "cilen", "search_pos", "seq_pick", "dr", "dv", "gl_idx")
 COORD_FIELDS = ("bp1", "bp2", "search_pos", "seq_pick")
 
@@ -119,6 +121,11 @@ class NameRankOut(C.Structure):
 class SeqInfo(C.Structure):
     _fields_ = [("reads_uploaded", C.c_int64), ("bytes_uploaded", C.c_int64), ("rows_gathered", C.c_int64), ("bytes_gathered", C.c_int64),
                 ("ms_upload", C.c_float), ("ms_gather", C.c_float), ("packed", C.c_int32), ("reserved", C.c_int32), ("device_bytes", C.c_int64)]
+
+
+class ReadsDev(C.Structure):
+    """csv_reads_dev: the device addresses of the reads table's columns (csv_reads_batch_columns)"""
+    _fields_ = [("n_reads", C.c_int64), ("r_start", C.c_void_p), ("r_end", C.c_void_p), ("r_primary", C.c_void_p), ("r_id", C.c_void_p)]
 
 
 class VcfIn(C.Structure):
@@ -232,6 +239,7 @@ BAM_STRUCT_SIZES = [("csv_bam_chunk", C.sizeof(ChunkC)), ("csv_bam_in", C.sizeof
 SA_STRUCT_SIZES = [("csv_sa_in", C.sizeof(SaIn)), ("csv_sa_out", C.sizeof(SaOut))]
 NAME_STRUCT_SIZES = [("csv_name_rank_out", C.sizeof(NameRankOut))]
 SEQ_STRUCT_SIZES = [("csv_seq_info", C.sizeof(SeqInfo))]
+READS_STRUCT_SIZES = [("csv_reads_dev", C.sizeof(ReadsDev))]
 
 
 def _ptr(arr):
@@ -325,7 +333,13 @@ class HostBatch:
     def on_device(cls, segments, dev, n_sig, n_chrom=0, keep=None, **reads):
         """A batch whose signature columns already live in device memory (CSV_IN_DEVICE_COLUMNS): `dev` = dict(a=, b=, read_id=,
         aux=) of device addresses (int64 a / b, int32 read_id / aux: what csv_rebuild_signatures leaves with
-        CSV_RB_KEEP_ON_DEVICE); `keep`: objects that own that memory.  The reads table, if any, comes from the host as usual."""
+        CSV_RB_KEEP_ON_DEVICE); `keep`: objects that own that memory.  The reads table, if any, comes from the host as usual
+        (reads_off=, r_start=, ...) or - reads_dev=dict(reads_off=, r_start=, r_end=, r_primary=, r_id=, n_reads=), what
+        reads.batch_columns returns - from device memory as well (CSV_IN_READS_DEVICE | CSV_IN_READS_I32: int32 columns; reads_off
+        stays a host array).  Both at once: ValueError."""
+        reads_dev = reads.pop("reads_dev", None)
+        if reads_dev is not None and any(reads.get(k) is not None for k in ("reads_off", "r_start", "r_end", "r_primary", "r_id")):
+            raise ValueError("the reads table comes from the host (reads_off=, r_start=, ...) or from the device (reads_dev=), not both")
         self = cls.__new__(cls)
         self.segments = np.ascontiguousarray(segments, dtype=SEGMENT_DTYPE)
         self.a = self.b = self.read_id = self.aux = None
@@ -339,13 +353,20 @@ class HostBatch:
             self.r_primary = _col(reads["r_primary"], np.uint8); self.r_id = _col(reads["r_id"], np.int32)
         if reads.get("contig_len") is not None:
             self.contig_len = _col(reads["contig_len"], np.int64)
+        # the reads columns as the struct takes them: host arrays, or the device addresses of reads_dev
+        n_reads = 0 if self.r_start is None else self.r_start.shape[0]
+        cols = [_ptr(self.r_start), _ptr(self.r_end), _ptr(self.r_primary), _ptr(self.r_id)]
+        rflags = IN_READS_I32 if self.r_start is not None and self.r_start.dtype == np.int32 else 0
+        if reads_dev is not None:
+            self.reads_off = _col(reads_dev["reads_off"], np.int64)
+            if self.reads_off.shape[0] != self.n_chrom + 1:
+                raise ValueError("reads_off must have n_chrom + 1 entries")
+            n_reads, cols = int(reads_dev["n_reads"]), [reads_dev[k] for k in ("r_start", "r_end", "r_primary", "r_id")]
+            rflags = IN_READS_DEVICE | IN_READS_I32
         self.c = BatchIn(
             n_seg=len(self.segments), n_chrom=self.n_chrom, seg=_ptr(self.segments), n_sig=self._n_sig,
-            a=dev["a"], b=dev["b"], read_id=dev["read_id"], aux=dev["aux"], reads_off=_ptr(self.reads_off),
-            n_reads=0 if self.r_start is None else self.r_start.shape[0],
-            r_start=_ptr(self.r_start), r_end=_ptr(self.r_end), r_primary=_ptr(self.r_primary), r_id=_ptr(self.r_id),
-            contig_len=_ptr(self.contig_len),
-            flags=IN_DEVICE_COLUMNS | (IN_READS_I32 if self.r_start is not None and self.r_start.dtype == np.int32 else 0))
+            a=dev["a"], b=dev["b"], read_id=dev["read_id"], aux=dev["aux"], reads_off=_ptr(self.reads_off), n_reads=n_reads,
+            r_start=cols[0], r_end=cols[1], r_primary=cols[2], r_id=cols[3], contig_len=_ptr(self.contig_len), flags=IN_DEVICE_COLUMNS | rflags)
         return self
 
     def widened(self):

@@ -71,6 +71,14 @@ SYMBOLS = [
     ("csv_aln_timing", C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     ("csv_aln_tra_genotype", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
                                        C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
+    ("csv_reads_reset", C.c_int, [C.c_void_p, C.c_int32]),
+    ("csv_reads_rows", C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
+    ("csv_reads_append_decoded", C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]),
+    ("csv_reads_append", C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("csv_reads_get", C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("csv_reads_batch_columns", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(_abi.ReadsDev)]),
+    ("csv_reads_timing", C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    ("csv_reads_struct_size", C.c_int, [C.c_int]),
     ("csv_bam_task_gates", C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.POINTER(C.c_float)]),
     ("csv_vcf_emit", C.c_int, [C.POINTER(_abi.VcfIn), C.c_char_p, C.c_int64, C.POINTER(C.c_int64), C.c_void_p]),
@@ -106,7 +114,8 @@ def lib():
             raise ExtensionMissing("libcutesv_hip.so ABI %d != python side %d" % (L.csv_abi_version(), _abi.ABI_VERSION))
         # a stale build with the same ABI number: every struct must have the size of its mirror
         for size_of, table in ((L.csv_struct_size, _abi.STRUCT_SIZES), (L.csv_bam_struct_size, _abi.BAM_STRUCT_SIZES), (L.csv_sa_struct_size, _abi.SA_STRUCT_SIZES),
-                               (L.csv_name_struct_size, _abi.NAME_STRUCT_SIZES), (L.csv_seq_struct_size, _abi.SEQ_STRUCT_SIZES)):
+                               (L.csv_name_struct_size, _abi.NAME_STRUCT_SIZES), (L.csv_seq_struct_size, _abi.SEQ_STRUCT_SIZES),
+                               (L.csv_reads_struct_size, _abi.READS_STRUCT_SIZES)):
             for i, (name, size) in enumerate(table):
                 if size_of(i) != size:
                     raise ExtensionMissing("%s: sizeof(%s) is %d, its python mirror has %d bytes: rebuild the library" % (LIB_PATH, name, size_of(i), size))

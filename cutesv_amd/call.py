@@ -2,7 +2,7 @@
 
     text, svid = call_bam("in.bam", fasta.Reference("ref.fa"), CallParams(Params.ont(min_support=3)))
     python -m cutesv_amd.call in.bam ref.fa -o out.body.vcf [--genotype] [--tra_gt MODE] [--report_readid] [--min_support N] [--batch B]
-                               [--include_bed FILE]
+                               [--include_bed FILE] [--reads_table {host,device}]
 
 Per task region the records are decoded, scanned and analysed on the device and their signatures, read names and inserted
 bases stay there (extract.task_to_pool with the name pool and the sequence pool); one rebuild sorts and de-duplicates the pool
@@ -57,6 +57,8 @@ def cut_tasks(length, batch):
 
 
 DEFAULT_GATES = "device"        # where call_bam evaluates the task gates without a BED (decided by its measurement)
+DEFAULT_READS_TABLE = "host"    # where call_bam builds the genotyping reads table: not measured yet, so it stays "host" until scripts/reads_stage.py has been run
+                                # on an MI355X (DESIGN.md section 20 has the rule that decides)
 TRA_GT_MODES = ("alignments", "reads_table", "off")
 
 
@@ -107,7 +109,7 @@ class _Shim:
 
 
 def call_bam(bam, reference, params, ctx=None, chroms=None, batch=10_000_000, report_readid=False, ignore_sequence=False, threads=None, svid=None,
-             as_bytes=False, timings=None, tra_gt=None, include_bed=None, gates=None):
+             as_bytes=False, timings=None, tra_gt=None, include_bed=None, gates=None, reads_table=None):
     """-> (VCF body text, svid counters [INS, DEL, BND, DUP, INV]).
 
     bam        a path or an open bam.BamFile (coordinate-sorted; no index is needed)
@@ -124,8 +126,16 @@ def call_bam(bam, reference, params, ctx=None, chroms=None, batch=10_000_000, re
                reaches only a region that begins in the next is dropped: with a BED the calls depend on `batch`.  TRA genotyping
                from every alignment (tra_gt="alignments") is not restricted, as in the reference.  None: no gate.
     gates      "host" or "device": where the task gates are evaluated (extract.task_to_pool); None: "device" with include_bed,
-               else DEFAULT_GATES (also "device": DESIGN.md section 19 has the measurement that decided it)"""
-    from . import aln, bam as bam_mod, bed as bed_mod, engine, extract, rebuild, vcf
+               else DEFAULT_GATES (also "device": DESIGN.md section 19 has the measurement that decided it)
+    reads_table  "host" or "device": where the genotyping reads table is built (only with params.genotype; None: DEFAULT_READS_TABLE).
+               host: every task's rows are cut out of the downloaded columns and the table is assembled with numpy (reads.table_host);
+               device: the tasks append their rows to the context's device-resident table (reads.append_decoded), the name ranks are
+               gathered there and the engine copies the columns device to device.  Same text either way."""
+    from . import aln, bam as bam_mod, bed as bed_mod, engine, extract, reads as reads_mod, rebuild, vcf
+    if reads_table is None:
+        reads_table = DEFAULT_READS_TABLE
+    if reads_table not in ("host", "device"):
+        raise ValueError("reads_table must be 'host' or 'device', not %r" % (reads_table,))
     regions = None if include_bed is None else include_bed if isinstance(include_bed, bed_mod.Regions) else bed_mod.load_bed(include_bed)
     if gates is None:
         gates = "device" if regions is not None else DEFAULT_GATES
@@ -159,13 +169,16 @@ def call_bam(bam, reference, params, ctx=None, chroms=None, batch=10_000_000, re
         rebuild.name_pool_reset(ctx)
         if mode == "alignments":
             aln.reset(ctx, n_chrom)
-        tables = []                                           # per task: (chromosome index, its reads-table columns)
+        reads_dev = reads_table == "device" and p.genotype
+        if reads_dev:
+            reads_mod.reset(ctx, n_chrom)
+        tables = []                                           # reads_table="host", per task: (chromosome index, its reads-table columns)
         for c in wanted:
             for t0, t1 in cut_tasks(length[c], batch):
                 r = extract.task_to_pool(ctx, bf, c, t0, t1, crank, *cp.pipe_args(), seg_of["INS"] + crank[c], seg_of["DEL"] + crank[c], seg_base, None,
-                                         name_pool=True, seq_pool=True, aln=(mode == "alignments"), gates=gates,
+                                         name_pool=True, seq_pool=True, aln=(mode == "alignments"), gates=gates, reads="device" if reads_dev else "host",
                                          bed_regions=None if regions is None else regions.for_task(c, t0, t1))
-                if p.genotype:
+                if p.genotype and not reads_dev:
                     tables.append((crank[c], r))
         lap("ms_tasks")
         if rebuild.pool_rows(ctx) == 0:
@@ -181,15 +194,13 @@ def call_bam(bam, reference, params, ctx=None, chroms=None, batch=10_000_000, re
                 for s in np.flatnonzero(rb["seg_count"]).tolist()]
         segs = np.array(segs, dtype=_abi.SEGMENT_DTYPE)
         reads = {}
-        if p.genotype and tables:
-            ranks = rebuild.name_ranks(ctx)["rank"]
-            rd = dict(chrom=np.concatenate([np.full(len(r["reads_index"]), ci, np.int64) for ci, r in tables]),
-                      start=np.concatenate([r["reads_start"] for _, r in tables]), end=np.concatenate([r["reads_end"] for _, r in tables]),
-                      primary=np.concatenate([r["reads_primary"] for _, r in tables]),
-                      read_id=ranks[np.concatenate([r["name_base"] + r["reads_index"] for _, r in tables])])
-            reads = rebuild._reads_by_chrom(rd, n_chrom)
-            if p.genotype_tra:
-                reads["contig_len"] = np.array([length[c] for c in names], np.int64)
+        if reads_dev:
+            # (`wanted` is in name-rank order and a contig's tasks ran in order: the appends arrived grouped by chromosome)
+            reads = dict(reads_dev=reads_mod.batch_columns(ctx, n_chrom, reads_mod.RANK_FROM_NAMES))
+        elif p.genotype and tables:
+            reads = reads_mod.table_host(tables, rebuild.name_ranks(ctx)["rank"], n_chrom)
+        if reads and p.genotype_tra:
+            reads["contig_len"] = np.array([length[c] for c in names], np.int64)
         hb = _abi.HostBatch.on_device(segs, rb["dev"], rb["n_out"], n_chrom=n_chrom, keep=ctx, **reads)
         res = ctx.cluster_batch(hb)
         lap("ms_cluster")
@@ -242,6 +253,8 @@ def main(argv=None):
     ap.add_argument("--chroms", default=None, help="comma-separated contigs (default: all)")
     ap.add_argument("--include_bed", "-include_bed", default=None, metavar="FILE",
                     help="only call where the regions of this BED file are (padded by 1000 bases, as in cuteSV); the calls then depend on --batch")
+    ap.add_argument("--reads_table", default=None, choices=["host", "device"],
+                    help="with --genotype: where the genotyping reads table is built (default: %s)" % DEFAULT_READS_TABLE)
     ap.add_argument("--tra_gt", default=None, choices=list(TRA_GT_MODES),
                     help="with --genotype: how BND records are genotyped (default: CUTESV_AMD_TRA_GT, else alignments - every alignment counts, as in cuteSV)")
     a = ap.parse_args(argv)
@@ -253,7 +266,7 @@ def main(argv=None):
                     merge_del_threshold=a.merge_del_threshold, merge_ins_threshold=a.merge_ins_threshold)
     text, svid = call_bam(a.bam, fasta.Reference(a.reference), cp, chroms=a.chroms.split(",") if a.chroms else None, batch=a.batch,
                           report_readid=a.report_readid, ignore_sequence=a.ignore_sequence, threads=a.threads, as_bytes=True, tra_gt=tra_gt,
-                          include_bed=a.include_bed)
+                          include_bed=a.include_bed, reads_table=a.reads_table)
     with open(a.out, "wb") as f:
         f.write(text)
     print("%d records: INS %d, DEL %d, BND %d, DUP %d, INV %d" % (text.count(b"\n"), *svid.tolist()))

@@ -129,6 +129,20 @@ struct AlnState {
     float ms_append = 0, ms_genotype = 0;
     void own(std::vector<Buf*>& v) { v.insert(v.end(), {&start, &end, &idp, &maxlen, &work, &gt}); }
 };
+// The genotyping reads table (reads.hip.h): one row per gated record - start, end, primary, name id - grouped by chromosome, in
+// append order; all stand-alone.  start / end / primary / id grow by copying and hold n rows; h_off = the row offsets per chromosome,
+// kept on the host (it learns every append's count) and handed to the engine as reads_off; last_chrom / max_id: the chromosome of
+// the last row and the largest name id seen, for the host checks; n_chrom = -1 until the first csv_reads_reset.  The rows live until
+// csv_reads_reset.  Dead when a call returns: work (an append's keep bytes, scan tables and totals; a host append's columns).  rid
+// (the rank column of a csv_reads_batch_columns call) lives until the next such call or reset: the engine copies it at upload.
+struct ReadsTabState {
+    Buf start, end, primary, id, work, rid;
+    std::vector<i64> h_off;
+    i64 n = 0, max_id = -1;
+    int n_chrom = -1, last_chrom = -1;
+    float ms_append = 0, ms_columns = 0;
+    void own(std::vector<Buf*>& v) { v.insert(v.end(), {&start, &end, &primary, &id, &work, &rid}); }
+};
 
 }  // namespace
 
@@ -165,7 +179,7 @@ struct csv_ctx {
     Buf gs_chrom, gs_perm0, gs_perm1, gs_hist, gs_tot;          // general reads sort (fallback), allocated on first use
     Buf flush;                                                   // csv_cache_flush scratch
     // the extraction-side stages (their lifetime rules: at the structs)
-    PoolState pool; NameState nm; BamState bm; SaState sa; SeqState seq; VcfStrState vs; AlnState al;
+    PoolState pool; NameState nm; BamState bm; SaState sa; SeqState seq; VcfStrState vs; AlnState al; ReadsTabState rt;
     Arena scratch;                             // per-call scratch of the rebuild, the CIGAR scan and the split analysis
     RebuildState rb; CigarState cg; SplitState sp;
     // page-locked host staging: small tables on the way in, counters + call records + support lists on the way out

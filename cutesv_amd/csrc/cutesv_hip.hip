@@ -26,6 +26,7 @@
 #include "vcf_strings.hip.h"
 #include "aln.hip.h"
 #include "gates.hip.h"
+#include "reads.hip.h"
 
 using namespace csv;
 
@@ -298,7 +299,7 @@ void csv_ctx_destroy(csv_ctx* c)
     (void)hipSetDevice(c->device);
     (void)hipDeviceSynchronize();
     std::vector<Buf*> own = {&c->sqrt_tab, &c->rcp_tab, &c->cipk_tab, &c->cnt, &c->rstate, &c->gs_chrom, &c->gs_perm0, &c->gs_perm1, &c->gs_hist, &c->gs_tot, &c->flush};
-    c->pool.own(own); c->sp.own(own); c->bm.own(own); c->sa.own(own); c->nm.own(own); c->seq.own(own); c->vs.own(own); c->al.own(own);
+    c->pool.own(own); c->sp.own(own); c->bm.own(own); c->sa.own(own); c->nm.own(own); c->seq.own(own); c->vs.own(own); c->al.own(own); c->rt.own(own);
     for (Buf* b : own) if (b->p) (void)hipFree(b->p);
     for (Arena* a : {&c->arena, &c->scratch, &c->bm.arena, &c->sa.arena, &c->nm.arena}) if (a->base) (void)hipFree(a->base);
     if (c->h_pin) (void)hipHostFree(c->h_pin);
@@ -375,6 +376,11 @@ int upload_impl(csv_ctx* c, const csv_batch_in* in, bool per_sig_forced, bool sy
     if (in->n_seg < 0 || in->n_sig < 0 || (in->n_seg > 0 && !in->seg)) return fail(c, CSV_E_INVALID, "bad batch header");
     // (support lists and seq_pick name signatures by their global index in 32 bits on the device)
     if (in->n_sig >= (1ll << 31)) return fail(c, CSV_E_INVALID, "n_sig = %lld: a batch indexes at most 2^31 - 1 signature rows (split the store)", (long long)in->n_sig);
+    // CSV_IN_READS_DEVICE: the plain int32 columns only - the 16-bit and packed forms read r_start on the host (reads_anchors)
+    const bool rd_dev = (in->flags & CSV_IN_READS_DEVICE) != 0;
+    if (rd_dev && (!(in->flags & CSV_IN_READS_I32) || (in->flags & CSV_IN_READS_DELTA16) || in->r_delta || in->r_len16 || in->r_idp))
+        return fail(c, CSV_E_INVALID, "CSV_IN_READS_DEVICE needs CSV_IN_READS_I32 and takes no r_delta / r_len16 / r_idp");
+    const hipMemcpyKind rd_kind = rd_dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;      // (reads_off and contig_len stay host arrays)
     const int S = in->n_seg;
     c->h_seg.assign(in->seg, in->seg + S);
     c->h_woff.assign(S + 1, 0);
@@ -787,9 +793,9 @@ int upload_impl(csv_ctx* c, const csv_batch_in* in, bool per_sig_forced, bool sy
     } else if (R > 0) {
         const size_t cw = rd32 ? 4 : 8;
         if (r_gaps) HIP_TRY(c, hipMemcpyAsync(c->rd16.p, in->r_delta, (size_t)R * 2, hipMemcpyHostToDevice, sr));
-        else HIP_TRY(c, hipMemcpyAsync(c->r_start.p, in->r_start, R * cw, hipMemcpyHostToDevice, sr));
+        else HIP_TRY(c, hipMemcpyAsync(c->r_start.p, in->r_start, R * cw, rd_kind, sr));
         if (r_lens) HIP_TRY(c, hipMemcpyAsync(c->rl16.p, in->r_len16, (size_t)R * 2, hipMemcpyHostToDevice, sr));
-        else HIP_TRY(c, hipMemcpyAsync(c->r_end.p, in->r_end, R * cw, hipMemcpyHostToDevice, sr));
+        else HIP_TRY(c, hipMemcpyAsync(c->r_end.p, in->r_end, R * cw, rd_kind, sr));
         if (r_packed) {
             // (the packed word lands where the packed start-ordered table will be built - s_idp is not written before k_reads_gather -
             // and is split into the two columns the reads stage reads)
@@ -797,8 +803,8 @@ int upload_impl(csv_ctx* c, const csv_batch_in* in, bool per_sig_forced, bool sy
             hipLaunchKernelGGL(k_reads_split_idp, dim3(div_up(R, 256)), dim3(256), 0, sr, (const unsigned*)c->s_idp.p, dp<int>(c->r_id), dp<uint8_t>(c->r_primary), R);
             c->reads_delta |= 4;
         } else {
-            HIP_TRY(c, hipMemcpyAsync(c->r_primary.p, in->r_primary, R, hipMemcpyHostToDevice, sr));
-            HIP_TRY(c, hipMemcpyAsync(c->r_id.p, in->r_id, R * 4, hipMemcpyHostToDevice, sr));
+            HIP_TRY(c, hipMemcpyAsync(c->r_primary.p, in->r_primary, R, rd_kind, sr));
+            HIP_TRY(c, hipMemcpyAsync(c->r_id.p, in->r_id, R * 4, rd_kind, sr));
         }
         if (r_gaps) {
             int* h_off = reads_anchors();
@@ -1606,3 +1612,4 @@ int csv_cluster_batch(csv_ctx* c, const csv_batch_in* in, csv_batch_out* out)
 #include "stage_bam.hip.h"
 #include "stage_aln.hip.h"
 #include "stage_gates.hip.h"
+#include "stage_reads.hip.h"

@@ -725,7 +725,7 @@ def _assemble_device(ctx, chunk, cols, sig, names, seqs, sel, chrom, chrom_rank,
 # ------------------------------------------------------------------------------------ a task's region -> rows of the pool
 def task_to_pool(ctx, bamfile, chrom, task_start, task_end, chrom_rank, sv_size, min_mapq, max_split_parts, min_read_len, min_siglength,
                  merge_del_threshold, merge_ins_threshold, max_size, seg_ins, seg_del, seg_base, read_base, bed_regions=None, name_pool=False, seq_pool=False, aln=False,
-                 gates="host"):
+                 gates="host", reads="host"):
     """The body of an extraction task without a candidate tuple, a name string or a sequence: the records of the region
     (`bamfile.records`) are decoded on the device, the CIGAR scan appends its signatures to the context's pool from the decoded
     columns (CSV_CG_FROM_BAM | CSV_CG_TO_POOL), the SA tags are parsed there (split_inputs_bam) and the split-read analysis appends
@@ -736,7 +736,8 @@ def task_to_pool(ctx, bamfile, chrom, task_start, task_end, chrom_rank, sv_size,
 
     -> dict: n_records, n_sig_ins, n_sig_del, n_calls, n_entries, n_split (candidates of the device path), n_split_host (of the
     flagged calls), n_flagged, flagged_calls / flagged_records (indices of the flagged calls and of their records), and the
-    columns of the reads table rows (:729-733) reads_start, reads_end, reads_primary, reads_index (index in the chunk).
+    columns of the reads table rows (:729-733) reads_start, reads_end, reads_primary, reads_index (index in the chunk) - or, with
+    reads="device", n_reads_rows.
 
     name_pool=True: the chunk's read names are appended to the context's name pool (rebuild.name_pool_append_chunk) after the
     decode, so that a row's read index IS its name's index: read_base must equal the name pool's row count (ValueError before
@@ -757,9 +758,20 @@ def task_to_pool(ctx, bamfile, chrom, task_start, task_end, chrom_rank, sv_size,
     whatever the BED says).
 
     gates="device": the gates are evaluated by a kernel where the columns are (`task_gates`) and `use` / `sel` never leave the
-    device; the reads rows and the `want` flags of the sequence upload come from the bytes it returns.  Same rows either way."""
+    device; the reads rows and the `want` flags of the sequence upload come from the bytes it returns.  Same rows either way.
+
+    reads="device" (needs name_pool=True): the rows of the reads table are not cut out of the downloaded columns but appended to the
+    context's device-resident reads table (reads.append_decoded, right after the gates) with their name-pool indices as ids - under
+    gates="device" straight from the gates column (GATE_READS), under gates="host" from the host's mask.  The caller resets the
+    table (reads.reset) and runs the chromosomes in ascending index order; the result carries n_reads_rows instead of the four
+    reads_* arrays."""
     from . import bam as bam_mod, rebuild
     _check_gates(gates, True)
+    if reads not in ("host", "device"):
+        raise ValueError("reads must be 'host' or 'device', not %r" % (reads,))
+    if reads == "device" and not name_pool:
+        raise ValueError("reads='device' needs name_pool=True: a row's id is its name's index")
+    table_on_device = reads == "device"                       # (`reads` below: the flagged calls' reads)
     if aln and not name_pool:
         raise ValueError("aln=True needs name_pool=True: a row's id is its name's index")
     if name_pool:
@@ -780,6 +792,9 @@ def task_to_pool(ctx, bamfile, chrom, task_start, task_end, chrom_rank, sv_size,
         n_aln = aln_mod.append_decoded(ctx, chrom_rank[chrom], task_start, task_end, read_base)
     start, end, mapq, qlen = cols["ref_start"], cols["ref_end"], cols["mapq"], cols["query_len"]
     _, use, sel, in_table, bits = _task_gates(ctx, cols, task_start, bed_regions, min_read_len, min_mapq, gates)
+    if table_on_device:
+        from . import reads as reads_mod
+        n_rows = reads_mod.append_decoded(ctx, chrom_rank[chrom], chunk.n, read_base, keep=None if bits is not None else in_table)
     if seq_pool:
         s_off, l_seq = chunk.sequence_columns()
         upload_read_sequences(ctx, chunk.host, s_off, l_seq, want=(use != 0) | sel if bits is None else (bits & (_abi.GATE_USE | _abi.GATE_SEL)) != 0)
@@ -799,12 +814,15 @@ def task_to_pool(ctx, bamfile, chrom, task_start, task_end, chrom_rank, sv_size,
         if seq_pool and len(ins):                             # their INS rows: cut on the host, as single_pipe_bam does
             cut = pool_ins_sequences_host(_Lazy(chunk.sequence), cols["flag"] == 16, None, fsig, call_read=rec)
             rebuild.seq_pool_put(ctx, first_row + ins, [b for b, _ in cut], [h for _, h in cut])
-    keep = np.flatnonzero(in_table)
     extra = dict(name_base=read_base) if name_pool else {}
+    if table_on_device:
+        extra["n_reads_rows"] = n_rows
+    else:
+        keep = np.flatnonzero(in_table)
+        extra.update(reads_start=start[keep], reads_end=end[keep], reads_primary=(cols["cls"][keep] == 1).astype(np.uint8), reads_index=keep)
     if seq_pool:
         extra["n_seq_rows"], extra["n_seq_bytes"] = rebuild.seq_pool_rows(ctx)
     if aln:
         extra["n_aln_rows"] = n_aln
     return dict(**extra, n_records=chunk.n, n_sig_ins=sig["n_sig_ins"], n_sig_del=sig["n_sig_del"], n_calls=si["n_calls"], n_entries=si["n_entries"], n_split=n_split,
-                n_split_host=n_host, n_flagged=si["n_flagged"], flagged_calls=calls, flagged_records=si["call_rec"][calls],
-                reads_start=start[keep], reads_end=end[keep], reads_primary=(cols["cls"][keep] == 1).astype(np.uint8), reads_index=keep)
+                n_split_host=n_host, n_flagged=si["n_flagged"], flagged_calls=calls, flagged_records=si["call_rec"][calls])

@@ -105,6 +105,11 @@ enum {
                                  crosses the link as 16-bit gaps (a block is a concatenation of start-sorted runs, MAIN:697-735, 810: a 30x
                                  genome's neighbours are ~0.5 kb apart) and its end column as 16-bit lengths (HiFi reads are < 64 kb), both
                                  rebuilt on the device: 13 -> 9 bytes per read, the bulk of a genotyping call's upload */
+    CSV_IN_READS_DEVICE = 128, /* (with CSV_IN_READS_I32) r_start, r_end, r_primary and r_id are DEVICE pointers (memory of this context's GPU,
+                                 e.g. what csv_reads_batch_columns hands out): the four columns move device to device at upload, so the
+                                 caller may change its memory once the upload (or the one-shot call) has returned.  reads_off and
+                                 contig_len stay host arrays.  CSV_E_INVALID without CSV_IN_READS_I32, or together with
+                                 CSV_IN_READS_DELTA16, r_delta, r_len16 or r_idp: those forms read r_start on the host */
     CSV_IN_SIG_DELTA16 = 32   /* (ABI v8, with CSV_IN_SIG_I32, host columns) a_delta / a_esc_* are given: the position column crosses
                                  the link as 16-bit gaps - the rebuild order (MAIN:764-802) makes it non-decreasing inside a segment,
                                  a 30x genome's neighbours are ~1 kb apart - and is rebuilt on the device (k_unpack_a16): 11.1 -> 5.6 MB
@@ -981,6 +986,55 @@ enum { CSV_GATE_TASK = 1, CSV_GATE_PARSED = 2, CSV_GATE_USE = 4, CSV_GATE_SEL = 
 int csv_bam_task_gates(csv_ctx* ctx, int64_t n_records, int64_t task_start, int32_t min_read_len, int32_t min_mapq, int32_t flags,
                        int64_t n_regions, const int64_t* region_beg, const int64_t* region_end,
                        uint8_t* bits /* n_records, nullable */, float* ms_device /* nullable */);
+
+/* The genotyping reads table in device memory (reads.hip.h).  The reference's reads table (cuteSV main
+ * script :729-733) has one row per record that passed the gates of its task with mapq >= min_mapq; every column of it exists on
+ * the device once the task's chunk is decoded, so the table is cut out of them there and handed to the engine where it lies:
+ *   start    ref_start (int32: BAM positions are int32 fields)        end      ref_end, saturating at INT32_MAX
+ *   primary  cls == 1 (flag 0 or 16)                                  id       the name pool's index of the record's name
+ * (13 bytes per row in device memory), grouped by chromosome in append order.  It belongs to the context and lives until
+ * csv_reads_reset / csv_ctx_destroy.
+ *
+ * csv_reads_reset: empties the table and fixes the number of chromosomes.  csv_reads_rows: its row count.
+ * csv_reads_append_decoded: the records of the context's last csv_bam_decode that belong in the table, in record order -
+ *   keep == NULL: those whose byte in the gates column of THAT decode has CSV_GATE_READS (csv_bam_task_gates must have run on it);
+ *   keep != NULL: n_records host bytes, non-zero = keep (the host-gated path).
+ *   row = { ref_start, ref_end, cls == 1, name_base + record index }.  Flags, scan, compaction and conversion run on the device;
+ *   nothing but the count comes back (n_appended, nullable).  n_records == 0 launches nothing; when no record is kept nothing is
+ *   launched after the count.
+ * csv_reads_append: rows from host arrays (0 <= start <= end, id >= 0).
+ * Ordering contract of both: chrom must be at least the chromosome of the last row.  Inside a chromosome the rows may come in any
+ *   order (csv_batch_in's reads table: "rows in ANY order inside a block").  After a failed append the table is unchanged.
+ * csv_reads_get: rows [first, first + n) back to the host (any array may be NULL).
+ * csv_reads_batch_columns: the table as csv_batch_in wants it with CSV_IN_READS_DEVICE | CSV_IN_READS_I32: reads_off[n_chrom + 1]
+ *   to the host, the DEVICE addresses of the four columns into `out` (NULL for an empty table).  CSV_RD_RANK_FROM_NAMES: r_id[i] =
+ *   rank[id[i]], the ranks of the context's name pool (csv_name_ranks' device column, computed first when an append made it stale,
+ *   as CSV_RB_RANK_FROM_NAMES does), written to a column of its own: the table is not changed and the call can be repeated.  The
+ *   addresses are valid until the next append, reset or csv_reads_batch_columns; csv_batch_upload / csv_cluster_batch copy the
+ *   columns, so the table may change once they have returned.
+ * csv_reads_timing: the kernels of the last append / the rank gather of the last csv_reads_batch_columns in milliseconds (HIP events).
+ * CSV_E_INVALID, before anything is launched, the context and the table unchanged: a NULL context; no csv_reads_reset yet; chrom
+ *   outside [0, n_chrom) or below the chromosome of the last row; no successful decode, or n_records that is not the decode's;
+ *   keep == NULL while the context holds no gates of its current decode; name_base < 0 or name_base + n_records beyond INT32_MAX;
+ *   a host row with start < 0, end < start or id < 0; csv_reads_get outside the table; csv_reads_batch_columns with an n_chrom that is
+ *   not the table's or with unknown flag bits; CSV_RD_RANK_FROM_NAMES with an id at or beyond the name pool's row count. */
+enum { CSV_RD_RANK_FROM_NAMES = 1 };
+typedef struct csv_reads_dev {
+    int64_t        n_reads;
+    const int32_t* r_start;         /* DEVICE addresses: n_reads entries each */
+    const int32_t* r_end;
+    const uint8_t* r_primary;
+    const int32_t* r_id;
+} csv_reads_dev;
+int csv_reads_reset(csv_ctx* ctx, int32_t n_chrom);
+int csv_reads_rows(const csv_ctx* ctx, int64_t* n);
+int csv_reads_append_decoded(csv_ctx* ctx, int32_t chrom, int64_t n_records, const uint8_t* keep /* nullable */, int64_t name_base, int64_t* n_appended);
+int csv_reads_append(csv_ctx* ctx, int32_t chrom, int64_t n, const int32_t* start, const int32_t* end, const uint8_t* primary, const int32_t* id);
+int csv_reads_get(csv_ctx* ctx, int64_t first, int64_t n, int32_t* start, int32_t* end, uint8_t* primary, int32_t* id);
+int csv_reads_batch_columns(csv_ctx* ctx, int32_t flags, int32_t n_chrom, int64_t* reads_off /* n_chrom + 1 */, csv_reads_dev* out);
+int csv_reads_timing(const csv_ctx* ctx, float* ms_append, float* ms_columns);
+/* sizeof of 0 csv_reads_dev; -1 otherwise */
+int csv_reads_struct_size(int which);
 
 #ifdef __cplusplus
 }
