@@ -1,5 +1,7 @@
-// ctx.hip.h — the context of libcutesv_hip.so and the host helpers every entry shares: buffers and arenas, error reporting, the copy / timing /
-// sort skeleton of the extraction stages.  Host code only; included by cutesv_hip.hip behind the kernel headers (one translation unit).
+// ctx.hip.h — the context of libcutesv_hip.so: one state struct per stage, of the extraction side and of the engine, each with the
+// rule that says how long its buffers live; csv_ctx itself, which holds them next to what every entry shares (device, streams, events,
+// arenas, staging, options); and the host helpers every entry shares: buffers and arenas, error reporting, the copy / timing / sort
+// skeleton of the extraction stages.  Host code only; included by cutesv_hip.hip behind the kernel headers (one translation unit).
 namespace {
 
 struct Buf { void* p = nullptr; size_t cap = 0; };      // a slice of an arena (or, for the few stand-alone buffers, its own allocation)
@@ -47,7 +49,7 @@ struct NameState {
 // Rebuild, CIGAR scan and split analysis: slices of csv_ctx::scratch, which every call of the three plans afresh.  Dead when
 // the call returns, with one exception: the caller of a CSV_RB_KEEP_ON_DEVICE rebuild may read oseg .. osrc (the dev_*
 // pointers of csv_rebuild_out) until the next call of ANY of the three.  The rebuild counts into the engine's counter block
-// (cnt + 768), so it clears `uploaded` and `ran`.  sp.qlen (the query lengths of a CSV_CG_TO_POOL call) stands alone.
+// (ResultState cnt + 768), so it clears the batch's `uploaded` and `ran`.  sp.qlen (the query lengths of a CSV_CG_TO_POOL call) stands alone.
 struct RebuildState {
     Buf seg, a, b, rid, aux, auxk, major, nodedup, perm0, perm1, hist, tot, partial;
     Buf oseg, oa, ob, orid, oaux, osrc, segcnt, rank, mx, drop, el0, el1;
@@ -144,9 +146,115 @@ struct ReadsTabState {
     void own(std::vector<Buf*>& v) { v.insert(v.end(), {&start, &end, &primary, &id, &work, &rid}); }
 };
 
+// ---- The state of the engine (stage_upload / stage_run / stage_results.hip.h): the path csv_batch_upload -> csv_batch_run ->
+// csv_batch_download / csv_batch_publish_* and the one-shot csv_cluster_batch.  One struct per concern, with the same kind of rule.
+
+// CSV_* environment switches of the engine (timing / debugging aids), read by load_run_opts at the top of EVERY upload and
+// nowhere else: csv_batch_run - a 36 us step - looks nothing up in the environment, and neither do the phases of an upload.
+struct RunOpts {
+    bool debug = false, debug_counters = false, debug_timing = false, no_fork = false, fork_always = false, no_swap = false, no_peek = false;
+    bool no_pair_in_mid = false, no_publish = false;
+    int  iw_grid = 0, gt_grid = 0, tier_fork_min = 1 << 30, mid_grid = 0, big_grid = 0;
+    bool pub_inplace = false, no_reads_overlap = false;
+    // the forms an upload may choose
+    bool no_lazy = false, no_rows8 = false, no_delta16 = false, copy_stream = false, no_tiny = false;
+    int  lazy_min = 64 << 10, delta16_min = 32 << 10, delta16_esc = 64, reads_gap = 1000000;
+};
+
+// The resident batch.  Every Buf is a slice of csv_ctx::arena that upload_impl plans and fills; the run's kernels read and write
+// them through B (the DevBatch every kernel takes).  They live until the next upload - which re-plans the arena, after waiting
+// for the device when the arena has to move - and nobody outside the engine reads them.  seg .. tile_info are slices of `tabs`
+// (the small tables: one block, one copy).  h_seg / h_woff: the host copies of the segments and their prefix in w space, read
+// by the downloads.  The flags are set by the upload and cleared by the next one, except: `ran` (set by a run, cleared by
+// csv_batch_validate and by a rebuild, which also clears `uploaded`: it counts into the engine's counter block),
+// copies_pending / unpack_pending / lazy_pending (a one-shot call's first run consumes them).
+struct BatchState {
+    Buf seg, woff, seg_drop, seg_gate, seg_err, tile_info, tabs;
+    Buf a, b, rid, aux, a32, b32;
+    Buf tile_lead;
+    Buf ad16, anc;                             // CSV_IN_SIG_DELTA16: the gaps in w space; the anchor tables {per-tile offsets, w, value}
+    Buf cluster_id, allele_id, partial, tile_cnt, item_rec, list_small, list_big, list_tiny, list_wide, ch_masks, tile_items;
+    Buf item_cnt, item_base, item_chunk, sup_tmp;
+    Buf t_rec, t_rec0;
+    Buf sc_k, sc_x, sc_v1, sc_v2, sc_v3, sc_v4, sc_v5;
+    Buf o_suprid;
+    // the reads table as uploaded (r_*; its 16-bit forms rd16 .. rlesc) and its packed start-ordered form (s_* .. maxlen), the genotype scratch
+    Buf reads_off, contig_len, r_start, r_end, r_primary, r_id;
+    Buf rd16, ranc, rl16, rlesc;               // CSV_IN_READS_DELTA16: start gaps + their anchors, lengths + their escape rows / values
+    Buf s_start, s_end, s_idp, cmax, cfirst, bfirst, span_len, maxlen, gt_over, gt_huge, gt_pool;
+    std::vector<csv_segment> h_seg;
+    std::vector<i64>         h_woff;
+    DevBatch B;
+    bool uploaded = false, ran = false, any_genotype = false, any_pair = false, any_tra_gt = false;
+    bool delta16 = false;                      // the last upload rebuilt its position column from gaps (csv_batch_info 2)
+    bool copies_pending = false;               // csv_cluster_batch: the column copies are still in flight behind ev_copy[0] / [1]
+    bool unpack_pending = false; UnpackArgs unpack_args{}; int unpack_tiles = 0;      // k_unpack_a16 of the position column is still to be queued (one-shot calls: by the run)
+    bool lazy_pending = false;                 // gate-first call: this upload's first run still has to fetch the gated rows from the caller's columns
+    bool partial_cols = false;                 // ... and its device columns hold only the rows the kernels read (csv_batch_validate refuses)
+    i64  lazy_bytes = 0;                       // bytes the bulk copy of this upload did NOT send (measurement aid: csv_batch_lazy_info)
+    i64  n_sig_host = 0, n_reads = 0;
+    int  upload_seq0 = 0;                      // run_seq when the resident batch was uploaded: later sequence numbers are runs of it
+};
+
+// The reads stage: the order of the uploaded reads table.  tcnt .. tblk are slices of csv_ctx::arena, planned by an upload
+// whose table is not sorted (dead at the next upload); rstate (the stage's verdict on the table, on the device) and the gs_*
+// buffers of the general sort (allocated on first use) stand alone and live as long as the context.  The flags belong to one
+// upload and are reset by the next; reads_ready is also cleared when a run finds that the table needs the general sort.
+// reuse_reads is the caller's (csv_batch_option) and survives uploads.
+struct ReadsOrderState {
+    Buf tcnt, ent, table, tblk;
+    std::vector<int> h_tblk;                   // per tile of the reads table: the first chromosome block that begins at or after it (the source of an asynchronous copy)
+    Buf rstate;
+    Buf gs_chrom, gs_perm0, gs_perm1, gs_hist, gs_tot;          // general reads sort (fallback), allocated on first use
+    bool rstate_dirty = true;                  // the reads-order state may hold an earlier upload's verdict
+    int  reads_delta = 0;                      // bit 0: the last upload's reads starts crossed as gaps, bit 1: its ends as lengths, bit 2: id | primary packed (csv_batch_info 3)
+    bool reads_early = false;                  // the last upload decoded the reads table's start column on side[1] (upload_reads)
+    bool reads_ready = false;                  // the packed start-ordered reads table of this upload exists (a completed reads stage)
+    bool reuse_reads = true;                   // ... and resident re-runs keep it (csv_batch_option CSV_OPT_REUSE_READS_ORDER)
+    bool have_tab = false;                     // this upload issued copies of the reads table frame (reads_off, contig_len, columns) on side[2]
+    bool reads_general = false;                // this batch's reads table needs the general sort (found out by a first run)
+    void own(std::vector<Buf*>& v) { v.insert(v.end(), {&rstate, &gs_chrom, &gs_perm0, &gs_perm1, &gs_hist, &gs_tot}); }
+};
+
+// Results and their delivery.  o_rec / o_supsig and o_rec2 / o_supsig2 are the two result arenas (slices of csv_ctx::arena, dead
+// at the next upload): runs alternate between them (`parity` = the arena of the last run), so that the k_publish of run k reads
+// arena k & 1 on the publish stream `pub` while run k + 1 fills the other one.  cnt (stand-alone, 1024 bytes): the counters of
+// arena 0 / 1 at +0 / +256, csv_batch_validate's at +512, the rebuild's row count at +768; h_cnt: the counters of the last
+// download or instrumented run.  pend / pend_order / n_pend: the publishes in flight, oldest first; an upload waits for them and
+// forgets them.  settled: a run of this upload has been downloaded synchronously (reads mode final, capacities known).  h_pub:
+// the page-locked landing zones of the asynchronous publishes, 2 x {counters 256 B, status words}; pub_stage: per arena the
+// device image of a block delivery (when the caller's result arrays sit back to back in page-locked memory, k_publish writes
+// them into this image and the copy engine moves each run of adjacent arrays in one piece).  Both grow only, while no publish
+// is in flight, and go with the context.
+struct ResultState {
+    Buf o_rec, o_supsig, o_rec2, o_supsig2;
+    Buf cnt;
+    DevCounters h_cnt;
+    int  parity = 0;
+    struct Pend { csv_batch_out* out = nullptr; bool live = false; } pend[2];
+    int  pend_order[2] = {0, 0}, n_pend = 0;
+    bool settled = false;
+    hipStream_t pub = nullptr;
+    hipEvent_t  ev_run[2] = {}, ev_pub[2] = {};
+    char*  h_pub = nullptr;
+    size_t h_pub_cap = 0;
+    void*  pub_stage[2] = {nullptr, nullptr};
+    size_t pub_stage_cap[2] = {0, 0};
+    void own(std::vector<Buf*>& v) { v.push_back(&cnt); }
+};
+
+// The libm tables of cal_CIPOS (sqrt_table): stand-alone, sqrt_n entries each, grown - after a device synchronisation - to the
+// longest segment any upload has seen, never shrunk; every batch's kernels read them.
+struct TableState {
+    Buf sqrt_tab, rcp_tab, cipk_tab;
+    i64 sqrt_n = 0;
+    void own(std::vector<Buf*>& v) { v.insert(v.end(), {&sqrt_tab, &rcp_tab, &cipk_tab}); }
+};
+
 }  // namespace
 
 struct csv_ctx {
+    // ---- what every entry shares
     int         device = 0;
     hipStream_t stream = nullptr;
     hipStream_t side[3] = {};         // side streams: [0] mid + workgroup tier, [1] DUP/INV/TRA wavefront tier, [2] reads order + prefix max
@@ -154,82 +262,25 @@ struct csv_ctx {
     hipEvent_t  ev_init = nullptr, ev_sel = nullptr, ev_aux[3] = {}, ev_copy[N_COPY_STREAMS] = {}, ev_reads = nullptr, ev_anc = nullptr, ev_rd[5] = {};
     std::string err;
     hipEvent_t  ev[CSV_N_STAGES + 2] = {};
-    Arena       arena;
-    // batch buffers (slices of `arena`)
-    Buf seg, woff, seg_drop, a, b, rid, aux, a32, b32;
-    Buf tile_lead, tabs;
-    Buf ad16, anc;                             // CSV_IN_SIG_DELTA16: the gaps in w space; the anchor tables {per-tile offsets, w, value}
-    Buf rd16, ranc, rl16, rlesc;               // CSV_IN_READS_DELTA16: start gaps + their anchors, lengths + their escape rows / values
-    int  reads_delta = 0;                      // bit 0: the last upload's reads starts crossed as gaps, bit 1: its ends as lengths (csv_batch_info 3)
-    bool delta16 = false;                      // the last upload rebuilt its position column from gaps (csv_batch_info 2)
-    bool rstate_dirty = true;                  // the reads-order state may hold an earlier upload's verdict
-    bool reads_early = false;                  // the last upload decoded the reads table's start column on side[1] (upload_impl)
-    bool unpack_pending = false; UnpackArgs unpack_args{}; int unpack_tiles = 0;      // ... and k_unpack_a16 is still to be queued (one-shot calls: by the run)
-    Buf cluster_id, partial, tile_cnt, item_rec, list_small, list_big, list_tiny, list_wide, seg_gate, tile_info, ch_masks, tile_items, seg_err;
-    Buf item_cnt, item_base, item_chunk, sup_tmp;
-    Buf t_rec, t_rec0;
-    Buf sc_k, sc_x, sc_v1, sc_v2, sc_v3, sc_v4, sc_v5;
-    Buf o_rec, o_supsig, o_suprid, allele_id;
-    Buf o_rec2, o_supsig2;                     // the second result arena (runs alternate: a publish may still read the other one)
-    Buf reads_off, r_start, r_end, r_primary, r_id, s_start, s_end, s_idp, cmax, cfirst, bfirst, span_len, maxlen, gt_over, gt_huge, gt_pool, contig_len;
-    Buf ro_tcnt, ro_ent, ro_table, ro_tblk;
-    std::vector<int> h_tblk;                   // per tile of the reads table: the first chromosome block that begins at or after it
-    // stand-alone
-    Buf sqrt_tab, rcp_tab, cipk_tab, cnt, rstate;
-    Buf gs_chrom, gs_perm0, gs_perm1, gs_hist, gs_tot;          // general reads sort (fallback), allocated on first use
-    Buf flush;                                                   // csv_cache_flush scratch
-    // the extraction-side stages (their lifetime rules: at the structs)
-    PoolState pool; NameState nm; BamState bm; SaState sa; SeqState seq; VcfStrState vs; AlnState al; ReadsTabState rt;
-    Arena scratch;                             // per-call scratch of the rebuild, the CIGAR scan and the split analysis
-    RebuildState rb; CigarState cg; SplitState sp;
+    Arena       arena;                         // the batch arena: planned afresh by every upload (BatchState, ReadsOrderState, ResultState slice it)
+    Arena       scratch;                       // per-call scratch of the rebuild, the CIGAR scan and the split analysis
+    Buf         flush;                         // csv_cache_flush scratch (stand-alone)
     // page-locked host staging: small tables on the way in, counters + call records + support lists on the way out
     char*  h_pin = nullptr;
     size_t h_pin_cap = 0;
+    RunOpts opt;
     // two page-locked 64-bit words the device writes {run sequence, count}: items above 64 signatures (k_chain_apply), calls that
     // overflowed the first genotype pass (k_genotype<8192>); read when a LATER run of the same upload is planned
-    // CSV_* environment switches of the run path (timing / debugging aids), read once per upload: csv_batch_run - a 36 us
-    // step - looks nothing up in the environment
-    struct RunOpts {
-        bool debug = false, debug_counters = false, no_fork = false, fork_always = false, no_swap = false, no_peek = false;
-        bool no_pair_in_mid = false, no_publish = false;
-        int  iw_grid = 0, gt_grid = 0, tier_fork_min = 1 << 30, mid_grid = 0, big_grid = 0;
-        bool pub_inplace = false, no_reads_overlap = false;
-    } opt;
     volatile int* h_flag = nullptr;
     int*          d_flag = nullptr;
     int           run_seq = 0;
-    int           upload_seq0 = 0;          // run_seq when the resident batch was uploaded: later sequence numbers are runs of it
     int           n_cu = 256;              // compute units of the device
-    // host copies
-    std::vector<csv_segment> h_seg;
-    std::vector<i64>         h_woff;
-    bool     uploaded = false, ran = false, any_genotype = false, any_pair = false, any_tra_gt = false, lds_set = false;
-    bool     reads_ready = false;              // the packed start-ordered reads table of this upload exists (a completed reads stage)
-    bool     reuse_reads = true;               // ... and resident re-runs keep it (csv_batch_option CSV_OPT_REUSE_READS_ORDER)
-    bool     have_tab = false;                 // this upload issued copies of the reads table frame (reads_off, contig_len, columns) on side[2]
-    bool     reads_general = false;            // this batch's reads table needs the general sort (found out by a first run)
-    i64      sqrt_n = 0;                       // entries of sqrt_tab (grown to the longest segment seen: an allele is never larger)
-    bool     copies_pending = false;           // csv_cluster_batch: the column copies are still in flight behind ev_copy[0] / [1]
-    // pipelined delivery (csv_batch_publish_async): runs alternate between two result arenas {call records, support list,
-    // counters}; the k_publish of run k reads arena k & 1 on its own stream while run k + 1 fills the other one
-    hipStream_t pub = nullptr;
-    hipEvent_t  ev_run[2] = {}, ev_pub[2] = {};
-    int         parity = 0;                    // arena of the last run
-    struct Pend { csv_batch_out* out = nullptr; bool live = false; } pend[2];
-    int         pend_order[2] = {0, 0}, n_pend = 0;      // arenas with a publish in flight, oldest first
-    bool        settled = false;               // a run of this upload has been downloaded synchronously (reads mode final, capacities known)
-    char*       h_pub = nullptr;               // page-locked landing zones of the asynchronous publishes: 2 x {counters 256 B, status words}
-    size_t      h_pub_cap = 0;
-    // block delivery: when the caller's result arrays sit back to back in page-locked memory (at most PUB_MAX_SPANS runs of
-    // adjacent arrays), k_publish writes them into a device image of those runs and the copy engine moves each run in one piece
-    void*       pub_stage[2] = {nullptr, nullptr};
-    size_t      pub_stage_cap[2] = {0, 0};
-    bool     lazy_pending = false;             // gate-first call: this upload's first run still has to fetch the gated rows from the caller's columns
-    bool     partial_cols = false;             // ... and its device columns hold only the rows the kernels read (csv_batch_validate refuses)
-    i64      lazy_bytes = 0;                   // bytes the bulk copy of this upload did NOT send (measurement aid: csv_batch_lazy_info)
-    i64      n_sig_host = 0, n_reads = 0;
-    DevBatch B;
-    DevCounters h_cnt;
+    bool          lds_set = false;         // the dynamic-LDS limits of the run's kernels are set (once per context)
+    // ---- the engine (stage_upload / stage_run / stage_results; their lifetime rules: at the structs)
+    BatchState bt; ReadsOrderState ro; ResultState res; TableState tab;
+    // ---- the extraction-side stages (their lifetime rules: at the structs)
+    PoolState pool; NameState nm; BamState bm; SaState sa; SeqState seq; VcfStrState vs; AlnState al; ReadsTabState rt;
+    RebuildState rb; CigarState cg; SplitState sp;
 };
 
 namespace {
@@ -262,6 +313,19 @@ int reserve(csv_ctx* c, Buf& b, size_t bytes)            // stand-alone grow-onl
     hipError_t e = hipMalloc(&b.p, want);
     if (e != hipSuccess) { b.p = nullptr; return fail(c, CSV_E_NOMEM, "hipMalloc(%zu) failed: %s", want, hipGetErrorString(e)); }
     b.cap = want;
+    return CSV_OK;
+}
+
+// room for `bytes` in the page-locked staging block (grow-only; the caller makes sure no copy still uses the old one)
+int pin_reserve(csv_ctx* c, size_t bytes)
+{
+    if (bytes <= c->h_pin_cap) return CSV_OK;
+    if (c->h_pin) { HIP_TRY(c, hipHostFree(c->h_pin)); c->h_pin = nullptr; c->h_pin_cap = 0; }
+    const size_t want = bytes + bytes / 4 + 4096;
+    void* p = nullptr;
+    hipError_t e = hipHostMalloc(&p, want, hipHostMallocDefault);
+    if (e != hipSuccess) return fail(c, CSV_E_NOMEM, "hipHostMalloc(%zu) failed: %s", want, hipGetErrorString(e));
+    c->h_pin = (char*)p; c->h_pin_cap = want;
     return CSV_OK;
 }
 

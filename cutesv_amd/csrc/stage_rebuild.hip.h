@@ -84,7 +84,7 @@ int csv_rebuild_signatures(csv_ctx* c, const csv_rebuild_in* in, csv_rebuild_out
     R.auxk = dp<int>(rb.auxk); R.keep = nullptr; R.partial = dp<int>(rb.partial);
     R.nodedup = in->seg_nodedup ? dp<uint8_t>(rb.nodedup) : nullptr;
     R.o_seg = dp<int>(rb.oseg); R.o_a = dp<i64>(rb.oa); R.o_b = dp<i64>(rb.ob); R.o_rid = dp<int>(rb.orid);
-    R.o_aux = dp<int>(rb.oaux); R.o_src = dp<int>(rb.osrc); R.n_out = (int*)((char*)c->cnt.p + 768);      // (a word of its own: the run arenas at +0 / +256 may have a publish in flight)
+    R.o_aux = dp<int>(rb.oaux); R.o_src = dp<int>(rb.osrc); R.n_out = (int*)((char*)c->res.cnt.p + 768);      // (a word of its own: the run arenas at +0 / +256 may have a publish in flight)
     R.drop = nullptr;
     out->n_tie_rows = 0; out->n_tie_dropped = 0;
     bool ties_settled = false;
@@ -202,7 +202,7 @@ int csv_rebuild_signatures(csv_ctx* c, const csv_rebuild_in* in, csv_rebuild_out
     HIP_TRY(c, hipGetLastError());
     int n_out = 0;
     std::vector<i64> segcnt((size_t)in->n_seg + 1);
-    HIP_TRY(c, hipMemcpyAsync(&n_out, (char*)c->cnt.p + 768, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipMemcpyAsync(&n_out, (char*)c->res.cnt.p + 768, 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(c, hipMemcpyAsync(segcnt.data(), rb.segcnt.p, ((size_t)in->n_seg + 1) * 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(c, hipStreamSynchronize(st));
     HIP_TRY(c, hipEventElapsedTime(&out->ms_device, c->ev[0], c->ev[1]));
@@ -220,7 +220,7 @@ int csv_rebuild_signatures(csv_ctx* c, const csv_rebuild_in* in, csv_rebuild_out
                             {out->read_id, &rb.orid, (i64)n_out * 4}, {out->aux, &rb.oaux, (i64)n_out * 4}, {out->src_row, &rb.osrc, (i64)n_out * 4}};
     for (const HostCol& o : cols) TRY(d2h(c, o.host, *o.dev, o.bytes, !keep_dev));
     HIP_TRY(c, hipStreamSynchronize(st));
-    c->uploaded = c->ran = false;          // cnt was used as scratch
+    c->bt.uploaded = c->bt.ran = false;          // cnt was used as scratch
     if (from_pool && keep_dev) { c->vs.kept = c->vs.gen; c->vs.n_out = n_out; c->vs.by_name = by_name; }      // (csv_seq_alt_gather / csv_name_support_join)
     return CSV_OK;
 }

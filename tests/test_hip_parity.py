@@ -1585,3 +1585,37 @@ def test_reads_table_as_16_bit_gaps_and_lengths(ctx, monkeypatch, order):
         assert_soa_equal(ctx.cluster_batch(hb, per_sig=True, reuse=True).trimmed(), want, st)
         assert ctx.reads_delta_info() == 0
         monkeypatch.delenv("CSV_NO_DELTA16")
+
+
+def test_reads_16_bit_forms_decoded_behind_the_copies(ctx, monkeypatch):
+    """CSV_NO_READS_OVERLAP: all three narrow forms of the reads table on offer (start gaps, 16-bit lengths, id | primary in one
+    word), copied and decoded in ONE stream - copies, then the anchors, then the decode kernels - instead of the decode of one column
+    under the copy of the next: the same calls as the oracle's, one-shot and resident, and as the overlapped decode.  The store
+    spans two whole chain tiles and a partial one, the reads table two chromosome blocks in extraction order."""
+    monkeypatch.setenv("CSV_DELTA16_MIN", "0")
+    monkeypatch.setenv("CSV_DELTA16_ESC", "0")
+    monkeypatch.setenv("CSV_LAZY_MIN", "0")
+    monkeypatch.setenv("CSV_READS_GAP", "30000")
+    p = Params.ont(genotype=True, min_support=3)
+    st = synth.small_mixed(seed=74, genotype=True, n_sites=60, coverage=30, n_contigs=2)
+    st, _ = synth.extraction_order(st, seed=74, region=150_000, workers=5)
+    pst = st.pinned()
+    hb = pst.host_batch(pst.tasks(), p)
+    W = int((hb.segments["sig_end"] - hb.segments["sig_begin"]).sum())
+    assert 2 * 2048 < W < 3 * 2048                                       # (CH_TILE = 2048 signatures)
+    assert len(st.chroms) == 2 and (np.diff(st.reads_off) > 0).all()
+    assert hb.r_delta is not None and hb.r_len16 is not None and hb.r_idp is not None and hb.c.flags & _abi.IN_READS_DELTA16
+    want = _oracle().cluster_batch(st.host_batch(st.tasks(), p), per_sig=True).trimmed()
+    for overlap in (False, True):
+        if overlap:
+            monkeypatch.delenv("CSV_NO_READS_OVERLAP")
+        else:
+            monkeypatch.setenv("CSV_NO_READS_OVERLAP", "1")
+        got = ctx.cluster_batch(hb, per_sig=True, reuse=True).trimmed()
+        assert ctx.reads_delta_info() == 7
+        assert_soa_equal(got, want, st)
+        assert (got["dr"] > 0).any()
+        ctx.upload(hb, per_sig=True)
+        assert ctx.reads_delta_info() == 7
+        ctx.run(); ctx.run()
+        assert_soa_equal(ctx.download(per_sig=True).trimmed(), want, st)
