@@ -24,6 +24,7 @@ RB_KEEP_ON_DEVICE = 1
 RB_FROM_POOL = 2                        # ... the rows are the context's device-resident signature pool
 RB_RANK_FROM_NAMES = 4                  # ... with RB_FROM_POOL: the read ranks are those of the context's name pool (csv_name_ranks)
 RB_TIES_FROM_SEQS = 8                   # ... with RB_FROM_POOL and seg_nodedup: the INS tie groups are settled from the context's sequence pool
+RB_ROUTE_NONE, RB_ROUTE_COMPACT, RB_ROUTE_WIDE, RB_ROUTE_PERM = 0, 1, 2, 3      # csv_rebuild_route: the sort the last rebuild took
 CG_TO_POOL = 1                         # csv_cigar_in.flags: the signatures also become pool rows                         # csv_rebuild_in.flags
 CG_FROM_BAM = 2                        # csv_cigar_in.flags: scan the device columns of the context's last csv_bam_decode
 SP_FROM_BAM = 4                        # csv_split_in.flags: the reads are the calls of the context's last csv_bam_split_inputs

@@ -42,6 +42,7 @@ SYMBOLS = [
     ("csv_cigar_signatures", C.c_int, [C.c_void_p, C.POINTER(_abi.CigarIn), C.POINTER(_abi.CigarOut)]),
     ("csv_split_signatures", C.c_int, [C.c_void_p, C.POINTER(_abi.SplitIn), C.POINTER(_abi.SplitOut)]),
     ("csv_rebuild_signatures", C.c_int, [C.c_void_p, C.POINTER(_abi.RebuildIn), C.POINTER(_abi.RebuildOut)]),
+    ("csv_rebuild_route", C.c_int, [C.c_void_p]),
     ("csv_pool_reset", C.c_int, [C.c_void_p]),
     ("csv_pool_rows", C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
     ("csv_pool_append", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -53,6 +53,7 @@ struct NameState {
 struct RebuildState {
     Buf seg, a, b, rid, aux, auxk, major, nodedup, perm0, perm1, hist, tot, partial;
     Buf oseg, oa, ob, orid, oaux, osrc, segcnt, rank, mx, drop, el0, el1;
+    int route = 0;          // csv_rebuild_route: the sort the last successful call took
 };
 struct CigarState { Buf qlen, off, ops, start, use, cnt, tiles, tot, iread, ipos, ilen, ip0, inp, pq, pl, dread, dpos, dlen; };
 struct SplitState {

@@ -1,4 +1,4 @@
-// stage_rebuild.hip.h — csv_rebuild_signatures: rows (the caller's or the pool's) -> sorted, de-duplicated signature
+// stage_rebuild.hip.h — csv_rebuild_signatures (and csv_rebuild_route): rows (the caller's or the pool's) -> sorted, de-duplicated signature
 // columns (RebuildState in ctx.hip.h, kernels in sort.hip.h).  Host code; included by cutesv_hip.hip.
 extern "C" {
 
@@ -221,8 +221,11 @@ int csv_rebuild_signatures(csv_ctx* c, const csv_rebuild_in* in, csv_rebuild_out
     for (const HostCol& o : cols) TRY(d2h(c, o.host, *o.dev, o.bytes, !keep_dev));
     HIP_TRY(c, hipStreamSynchronize(st));
     c->bt.uploaded = c->bt.ran = false;          // cnt was used as scratch
+    rb.route = !composite ? 3 : KL.wide ? 2 : 1;
     if (from_pool && keep_dev) { c->vs.kept = c->vs.gen; c->vs.n_out = n_out; c->vs.by_name = by_name; }      // (csv_seq_alt_gather / csv_name_support_join)
     return CSV_OK;
 }
+
+int csv_rebuild_route(const csv_ctx* c) { return c ? c->rb.route : 0; }
 
 }  // extern "C"

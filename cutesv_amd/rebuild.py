@@ -61,6 +61,12 @@ def rebuild_columns(ctx, seg_id, a, b, read_id, aux, seg_aux_major, seg_nodedup=
     return _rebuild(ctx, n, dict(seg_id=seg_id, a=a, b=b, read_id=read_id, aux=aux), None, seg_aux_major, seg_nodedup, keep_on_device, tie_order, src_row_out)
 
 
+def last_route(ctx):
+    """csv_rebuild_route: the sort the context's last successful rebuild took - _abi.RB_ROUTE_COMPACT (16-byte composite-key
+    elements), RB_ROUTE_WIDE (32-byte ones), RB_ROUTE_PERM (the permutation sort); RB_ROUTE_NONE before any rebuild"""
+    return int(lib().csv_rebuild_route(ctx._h))
+
+
 def _check_ties(ties, from_pool, seg_nodedup, tie_order):
     """the argument rules of ties="seqs" (CSV_RB_TIES_FROM_SEQS), before anything is asked of the context"""
     if ties not in (None, "seqs"):

@@ -439,6 +439,10 @@ typedef struct csv_rebuild_out {
 } csv_rebuild_out;
 
 int csv_rebuild_signatures(csv_ctx* ctx, const csv_rebuild_in* in, csv_rebuild_out* out);
+/* Which sort the context's last successful csv_rebuild_signatures took (chosen per call from the widths of the key columns):
+ * 1 = composite key in 16-byte elements, 2 = composite key in 32-byte elements, 3 = the permutation sort (keys beyond 128 bits,
+ * or CSV_RB_PERM_SORT set); 0 = no rebuild has sorted anything on this context yet (a call with no rows does not count). */
+int csv_rebuild_route(const csv_ctx* ctx);
 
 /* The device-resident signature pool: the reference's dataflow extraction -> rebuild (MAIN:697-743 -> 750-857) without a trip
  * through host memory.  csv_cigar_signatures with CSV_CG_TO_POOL appends the signatures it finds as rows (segment, position,
