@@ -8,8 +8,8 @@
 //   idp    name id | primary << 31, primary = flag is 0 or 16
 // one row per record, grouped by chromosome, in file order (starts ascend inside a chromosome).
 //
-//   k_aln_keep      one thread per decoded record: cnt = {beg <= pos < end, 0, 0, 0}; the scan is the CIGAR scan's
-//                   (k_cigar_tiles / k_cigar_offsets)
+//   k_aln_keep      one thread per decoded record: cnt = {beg <= pos < end, 0, 0, 0}; the exclusive scan is scan.hip.h's
+//                   (scan_counts: k_scan_tiles / k_scan_offsets)
 //   k_aln_store     one thread per decoded record: the kept ones become rows behind the table's last row (three int32 stores)
 //   k_aln_put       the same for rows that came from host arrays
 //   k_aln_check     one thread per NEW row: the order against the row before it (the table's last row for the first one) and
@@ -25,9 +25,14 @@
 //                   the calls of big_list, whose set the host gave a slice of global memory (tra_bits_for slots each).
 // In rank mode (CSV_ALN_FROM_KEPT_REBUILD) a support is a row of the kept rebuild and its id rid[row], a table row's id is
 // rank[name id]: both are looked up where they are used.  Every index is host-checked: chromosomes, supports, name ids.
+//
+// Includes kernels.hip.h: k_tra_aln calls partition_point_wave, tg_find_or_insert, tra_up_bound and tra_bits_for (and takes
+// TG_HASH) from its TRA genotyping section.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "wave.hip.h"
+#include "kernels.hip.h"
 
 namespace csv {
 
@@ -177,9 +182,9 @@ template <bool BIG> __device__ __forceinline__ int aln_window(const TraAln& A, i
         dr += __popcll(__ballot(commit && !(flags & 1)));
         if (BIG) __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "agent");           // the next step's lanes read these flags from global memory
         if (stop) {
-            nq = readlane_i64x(nq_i, t);
+            nq = readlane_i64(nq_i, t);
             const int a_t = __builtin_amdgcn_readlane((int)exitA, t);
-            const i64 it_t = readlane_i64x(it_i, t), pn_t = readlane_i64x(pn_i, t);
+            const i64 it_t = readlane_i64(it_i, t), pn_t = readlane_i64(pn_i, t);
             if (a_t) return 1;
             return (5 * pn_t <= it_t) ? 1 : -1;                                // float(primary_num / iteration) <= 0.2
         }

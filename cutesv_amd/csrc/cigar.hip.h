@@ -14,11 +14,12 @@
 //   generate_combine_sigs: INS distance = pos - previous piece's pos; DEL distance = pos - (end of the previous piece
 //   when that piece was merged or was the read's first, else its START: `temp_sig.append(i[0])`, :569)
 //
-// One wavefront per read, 64 operations per step (a 256-byte coalesced load); two passes (count, prefix over reads,
-// emit) because the outputs are dense and in read order.  HBM-bound: 4 bytes per operation, read twice.
+// One wavefront per read, 64 operations per step (a 256-byte coalesced load); two passes (count, prefix over reads by
+// scan.hip.h, emit) because the outputs are dense and in read order.  HBM-bound: 4 bytes per operation, read twice.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "wave.hip.h"
 
 namespace csv {
 
@@ -31,17 +32,13 @@ struct CigarArgs {
     int use_mask;                   // the bits of use[read] that count: 255, or CSV_GATE_USE when `use` is the gates column
     int min_siglength;
     i64 merge_ins, merge_del;
-    // per read counts (pass 1) / exclusive offsets (after the scan): x = INS signatures, y = INS pieces, z = DEL signatures
+    // per read counts (pass 1) / exclusive offsets (after the scan of scan.hip.h): x = INS signatures, y = INS pieces, z = DEL signatures
     int4* cnt;
-    i64* tile_sum;                  // 3 per tile of CG_TILE reads
-    i64* totals;                    // 3
     // outputs
     int* ins_read; i64* ins_pos; i64* ins_len; i64* ins_piece0; int* ins_npiece;
     int* piece_qoff; int* piece_len;
     int* del_read; i64* del_pos; i64* del_len;
 };
-
-constexpr int CG_TILE = 1024;       // reads per scan tile
 
 // the walk over one read; EMIT = false: count only.  Returns {INS signatures, INS pieces, DEL signatures}.
 template <bool EMIT> __device__ __forceinline__ int4 cigar_read(const CigarArgs& A, i64 read, i64 o_isig, i64 o_piece, i64 o_dsig)
@@ -72,9 +69,9 @@ template <bool EMIT> __device__ __forceinline__ int4 cigar_read(const CigarArgs&
         for (u64 mk = __ballot(piece); mk; mk &= mk - 1) {   // pieces in order; everything below is wave-uniform
             const int l = __ffsll((long long)mk) - 1;
             const int pop = __builtin_amdgcn_readlane(op, l);
-            const i64 ppos = readlane_i64x(my_ref, l), plen = readlane_i64x(len, l);
+            const i64 ppos = readlane_i64(my_ref, l), plen = readlane_i64(len, l);
             if (pop == 1) {
-                const i64 qoff = readlane_i64x(my_shift, l) - plen;
+                const i64 qoff = readlane_i64(my_shift, l) - plen;
                 if (i_open && ppos - i_last <= A.merge_ins) { i_len += plen; i_np++; }       // (:535-538)
                 else {
                     if (i_open) {
@@ -99,8 +96,8 @@ template <bool EMIT> __device__ __forceinline__ int4 cigar_read(const CigarArgs&
                 }
             }
         }
-        refpos += readlane_i64x(rinc, 63);
-        shift += readlane_i64x(qinc, 63);
+        refpos += readlane_i64(rinc, 63);
+        shift += readlane_i64(qinc, 63);
     }
     if (i_open) {
         if (EMIT && lane == 0) { const i64 k = o_isig + n_isig; A.ins_read[k] = (int)read; A.ins_pos[k] = i_pos; A.ins_len[k] = i_len; A.ins_piece0[k] = i_p0; A.ins_npiece[k] = i_np; }
@@ -120,58 +117,6 @@ __global__ __launch_bounds__(256) void k_cigar_count(CigarArgs A)
         const int4 c = cigar_read<false>(A, r, 0, 0, 0);
         if (lane_id() == 0) A.cnt[r] = c;
     }
-}
-
-// per tile of CG_TILE reads: sums of the three counts
-__global__ __launch_bounds__(256) void k_cigar_tiles(CigarArgs A)
-{
-    const i64 base = (i64)blockIdx.x * CG_TILE;
-    i64 s0 = 0, s1 = 0, s2 = 0;
-    for (int i = threadIdx.x; i < CG_TILE; i += 256) {
-        const i64 r = base + i;
-        if (r < A.n_reads) { const int4 c = A.cnt[r]; s0 += c.x; s1 += c.y; s2 += c.z; }
-    }
-    s0 = wave_sum_i64(s0); s1 = wave_sum_i64(s1); s2 = wave_sum_i64(s2);
-    __shared__ i64 sh[12];
-    if (lane_id() == 0) { sh[(threadIdx.x >> 6)] = s0; sh[4 + (threadIdx.x >> 6)] = s1; sh[8 + (threadIdx.x >> 6)] = s2; }
-    __syncthreads();
-    if (threadIdx.x < 3) A.tile_sum[(i64)blockIdx.x * 3 + threadIdx.x] = sh[4 * threadIdx.x] + sh[4 * threadIdx.x + 1] + sh[4 * threadIdx.x + 2] + sh[4 * threadIdx.x + 3];
-}
-
-// counts -> exclusive offsets, in place (the tile's prefix is recomputed from the tile sums: a few thousand values)
-__global__ __launch_bounds__(256) void k_cigar_offsets(CigarArgs A)
-{
-    __shared__ i64 sh[12], carry[3];
-    __shared__ i64 ws[3][4];
-    i64 p[3] = {0, 0, 0};
-    for (int t = threadIdx.x; t < (int)blockIdx.x; t += 256)
-        for (int k = 0; k < 3; k++) p[k] += A.tile_sum[(i64)t * 3 + k];
-    for (int k = 0; k < 3; k++) { p[k] = wave_sum_i64(p[k]); if (lane_id() == 0) sh[4 * k + (threadIdx.x >> 6)] = p[k]; }
-    __syncthreads();
-    if (threadIdx.x < 3) carry[threadIdx.x] = sh[4 * threadIdx.x] + sh[4 * threadIdx.x + 1] + sh[4 * threadIdx.x + 2] + sh[4 * threadIdx.x + 3];
-    __syncthreads();
-    const i64 base = (i64)blockIdx.x * CG_TILE;
-    for (int b0 = 0; b0 < CG_TILE; b0 += 256) {
-        const i64 r = base + b0 + threadIdx.x;
-        int4 c = make_int4(0, 0, 0, 0);
-        if (r < A.n_reads) c = A.cnt[r];
-        const i64 v[3] = {c.x, c.y, c.z};
-        i64 inc[3];
-        for (int k = 0; k < 3; k++) { inc[k] = wave_incl_scan_i64(v[k]); if (lane_id() == 63) ws[k][threadIdx.x >> 6] = inc[k]; }
-        __syncthreads();
-        i64 off[3];
-        for (int k = 0; k < 3; k++) {
-            off[k] = carry[k];
-            for (int q = 0; q < (int)(threadIdx.x >> 6); q++) off[k] += ws[k][q];
-            off[k] += inc[k] - v[k];
-        }
-        // offsets can exceed 32 bits only beyond 2^31 signatures per batch: rejected by the host
-        if (r < A.n_reads) A.cnt[r] = make_int4((int)off[0], (int)off[1], (int)off[2], 0);
-        __syncthreads();
-        if (threadIdx.x == 255) for (int k = 0; k < 3; k++) carry[k] = off[k] + v[k];
-        __syncthreads();
-    }
-    if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) for (int k = 0; k < 3; k++) A.totals[k] = carry[k];
 }
 
 __global__ __launch_bounds__(256) void k_cigar_emit(CigarArgs A)

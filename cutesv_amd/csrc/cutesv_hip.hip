@@ -17,6 +17,8 @@
 #include <utility>
 #include <vector>
 
+#include "wave.hip.h"
+#include "scan.hip.h"
 #include "kernels.hip.h"
 #include "sort.hip.h"
 #include "cigar.hip.h"

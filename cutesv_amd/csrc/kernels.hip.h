@@ -25,6 +25,7 @@
 #include <stdint.h>
 #include <type_traits>
 #include "../../include/cutesv_hip.h"
+#include "wave.hip.h"
 
 // Measurement aid (scripts/ablate.sh): -DCSV_ABLATE=<bit mask> drops a section of a kernel so that its share of the
 // kernel time can be read off a same-box A/B run.  The results are wrong then; never defined in a product build.
@@ -33,15 +34,9 @@
 #else
 #define CSV_ABL(bit) 0
 #endif
-#define CSV_LIKELY(x) __builtin_expect(!!(x), 1)
-#define CSV_UNLIKELY(x) __builtin_expect(!!(x), 0)
 
 namespace csv {
 
-typedef unsigned long long u64;
-typedef long long i64;
-
-constexpr int WAVE = 64;
 constexpr u64 PAD_KEY = ~0ull;
 constexpr int IDX_BITS = 21;                       // local-index bits inside a sort key: (value << 21 | index), values < 2^42 ...
 constexpr int IDX_BITS_HUGE = 31;                  // ... and (value << 31 | index), values < 2^32, for chained clusters above 2^21 signatures
@@ -224,31 +219,6 @@ struct DevBatch {
 };
 
 // ------------------------------------------------------------------------------------ small helpers
-__device__ __forceinline__ int lane_id() { return threadIdx.x & 63; }
-__device__ __forceinline__ u64 lanemask_lt() { return (1ull << lane_id()) - 1ull; }
-
-__device__ __forceinline__ i64 shfl_i64(i64 v, int src)
-{
-    int lo = __shfl((int)(v & 0xffffffffll), src), hi = __shfl((int)(v >> 32), src);
-    return ((i64)hi << 32) | (unsigned)lo;
-}
-__device__ __forceinline__ i64 shfl_up_i64(i64 v, int d)
-{
-    int lo = __shfl_up((int)(v & 0xffffffffll), d), hi = __shfl_up((int)(v >> 32), d);
-    return ((i64)hi << 32) | (unsigned)lo;
-}
-__device__ __forceinline__ i64 shfl_xor_i64(i64 v, int m)
-{
-    int lo = __shfl_xor((int)(v & 0xffffffffll), m), hi = __shfl_xor((int)(v >> 32), m);
-    return ((i64)hi << 32) | (unsigned)lo;
-}
-__device__ __forceinline__ double shfl_xor_f64(double v, int m) { return __longlong_as_double(shfl_xor_i64(__double_as_longlong(v), m)); }
-__device__ __forceinline__ i64 readlane_i64x(i64 v, int l)
-{
-    const int lo = __builtin_amdgcn_readlane((int)(v & 0xffffffffll), l);
-    const int hi = __builtin_amdgcn_readlane((int)(v >> 32), l);
-    return ((i64)hi << 32) | (unsigned)lo;
-}
 // a / b for a double a and a divisor b whose correctly rounded reciprocal y = RN(1 / b) is at hand (rcp_tab): q = a y is
 // within an ulp or two of the quotient, the residual r = a - b q is exact in one FMA, and RN(q + r y) is the correctly rounded
 // quotient - bit for bit what the float64 division of numpy / CPython returns (Markstein's theorem: it only fails for a
@@ -260,90 +230,6 @@ __device__ __forceinline__ double div_by(double a, double b, double y)
     const double r = __builtin_fma(-b, q, a);
     return __builtin_fma(r, y, q);
 }
-// ---- wave64 scans / reductions on DPP (data-parallel primitives: row_shr inside rows of 16 lanes, then
-// row_bcast:15 / row_bcast:31 across rows): 6 VALU moves per 32-bit word, no LDS round trips, no waitcnt.
-template <int CTRL, int RM> __device__ __forceinline__ int dpp_i32(int old, int v)
-{
-    return __builtin_amdgcn_update_dpp(old, v, CTRL, RM, 0xf, false);       // lanes without a source keep `old`
-}
-template <int CTRL, int RM> __device__ __forceinline__ i64 dpp_i64(i64 old, i64 v)
-{
-    const int lo = dpp_i32<CTRL, RM>((int)(old & 0xffffffffll), (int)(v & 0xffffffffll));
-    const int hi = dpp_i32<CTRL, RM>((int)(old >> 32), (int)(v >> 32));
-    return ((i64)hi << 32) | (unsigned)lo;
-}
-// One step of a 64-bit DPP scan: v + (v moved by the pattern; lanes without a source and rows outside the mask add nothing),
-// as the carry pair the hardware has for it - v_add_co_u32_dpp / v_addc_co_u32_dpp.  Written through dpp_i64 the compiler
-// builds the moved value as two 64-bit numbers (lo | 0 and 0 | hi), each from a zeroed register and a v_mov_b32_dpp, and adds
-// them with two v_lshl_add_u64: seven vector instructions a step where two do - and these kernels run at 60 - 86 % of the vector
-// ALUs' issue rate (profiles/r04_cfg3_insts.txt), so the count is the time.  s_nop 4: a DPP read needs two wait states after
-// the VALU write of its source and FIVE after a VALU write of EXEC (v_cmpx), and the hazard recogniser does not look inside an
-// asm block: the wait covers the longer of the two whatever precedes the block.
-template <int CTRL, int RM> __device__ __forceinline__ i64 dpp_add_i64(i64 v);
-#define CSV_DPP_ADD64(CTRL, RM, TXT)                                                                                              \
-    template <> __device__ __forceinline__ i64 dpp_add_i64<CTRL, RM>(i64 v)                                                       \
-    {                                                                                                                             \
-        unsigned lo = (unsigned)((u64)v & 0xffffffffull), hi = (unsigned)((u64)v >> 32);                                          \
-        asm volatile("s_nop 4\n\tv_add_co_u32_dpp %0, vcc, %0, %0 " TXT "\n\tv_addc_co_u32_dpp %1, vcc, %1, %1, vcc " TXT         \
-                     : "+v"(lo), "+v"(hi) : : "vcc");                                                                             \
-        return (i64)(((u64)hi << 32) | lo);                                                                                       \
-    }
-CSV_DPP_ADD64(0x111, 0xf, "row_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:1")
-CSV_DPP_ADD64(0x112, 0xf, "row_shr:2 row_mask:0xf bank_mask:0xf bound_ctrl:1")
-CSV_DPP_ADD64(0x114, 0xf, "row_shr:4 row_mask:0xf bank_mask:0xf bound_ctrl:1")
-CSV_DPP_ADD64(0x118, 0xf, "row_shr:8 row_mask:0xf bank_mask:0xf bound_ctrl:1")
-CSV_DPP_ADD64(0x142, 0xa, "row_bcast:15 row_mask:0xa bank_mask:0xf")
-CSV_DPP_ADD64(0x143, 0xc, "row_bcast:31 row_mask:0xc bank_mask:0xf")
-#undef CSV_DPP_ADD64
-__device__ __forceinline__ i64 wave_incl_scan_i64(i64 v)
-{
-    v = dpp_add_i64<0x111, 0xf>(v);     // row_shr:1
-    v = dpp_add_i64<0x112, 0xf>(v);     // row_shr:2
-    v = dpp_add_i64<0x114, 0xf>(v);     // row_shr:4
-    v = dpp_add_i64<0x118, 0xf>(v);     // row_shr:8
-    v = dpp_add_i64<0x142, 0xa>(v);     // row_bcast:15 into rows 1 and 3
-    v = dpp_add_i64<0x143, 0xc>(v);     // row_bcast:31 into rows 2 and 3
-    return v;
-}
-__device__ __forceinline__ int wave_incl_scan_i32(int v)
-{
-    v += dpp_i32<0x111, 0xf>(0, v);
-    v += dpp_i32<0x112, 0xf>(0, v);
-    v += dpp_i32<0x114, 0xf>(0, v);
-    v += dpp_i32<0x118, 0xf>(0, v);
-    v += dpp_i32<0x142, 0xa>(0, v);
-    v += dpp_i32<0x143, 0xc>(0, v);
-    return v;
-}
-__device__ __forceinline__ i64 wave_incl_max_i64(i64 v)
-{
-    i64 t;
-    t = dpp_i64<0x111, 0xf>(INT64_MIN, v); v = t > v ? t : v;
-    t = dpp_i64<0x112, 0xf>(INT64_MIN, v); v = t > v ? t : v;
-    t = dpp_i64<0x114, 0xf>(INT64_MIN, v); v = t > v ? t : v;
-    t = dpp_i64<0x118, 0xf>(INT64_MIN, v); v = t > v ? t : v;
-    t = dpp_i64<0x142, 0xa>(INT64_MIN, v); v = t > v ? t : v;
-    t = dpp_i64<0x143, 0xc>(INT64_MIN, v); v = t > v ? t : v;
-    return v;
-}
-// totals come back through v_readlane of lane 63: wave-uniform (SGPR) results
-__device__ __forceinline__ i64 wave_sum_i64(i64 v)
-{
-    v = wave_incl_scan_i64(v);
-    const int lo = __builtin_amdgcn_readlane((int)(v & 0xffffffffll), 63), hi = __builtin_amdgcn_readlane((int)(v >> 32), 63);
-    return ((i64)hi << 32) | (unsigned)lo;
-}
-__device__ __forceinline__ int wave_sum_i32(int v)
-{
-    return __builtin_amdgcn_readlane(wave_incl_scan_i32(v), 63);
-}
-__device__ __forceinline__ i64 lane63_i64(i64 v)
-{
-    const int lo = __builtin_amdgcn_readlane((int)(v & 0xffffffffll), 63), hi = __builtin_amdgcn_readlane((int)(v >> 32), 63);
-    return ((i64)hi << 32) | (unsigned)lo;
-}
-// value of the lane to the left (lane 0 gets 0): DPP wave_shr:1
-__device__ __forceinline__ i64 wave_shr1_i64(i64 v) { return dpp_i64<0x138, 0xf>(0, v); }
 
 // segment of compact index w (woff is tiny; lives in L1/L2)
 __device__ __forceinline__ int seg_of(const DevBatch& B, i64 w)
@@ -445,30 +331,6 @@ template <bool NARROW> __device__ __forceinline__ void chain_bytes_general(const
 }
 constexpr int EM_TILE = 8;                          // items per emit wavefront
 constexpr int EM_SUPER = 512;                       // items per second-level sum
-
-// sum of p[0 .. n) over the workgroup (256 threads); every thread gets the result
-__device__ __forceinline__ i64 block_prefix_of(const int* p, int n, i64* sh)
-{
-    i64 v = 0;
-    for (int i = threadIdx.x; i < n; i += 256) v += p[i];
-    v = wave_sum_i64(v);
-    if (lane_id() == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    const i64 t = sh[0] + sh[1] + sh[2] + sh[3];
-    __syncthreads();
-    return t;
-}
-__device__ __forceinline__ i64 block_prefix_of64(const i64* p, int n, i64* sh)
-{
-    i64 v = 0;
-    for (int i = threadIdx.x; i < n; i += 256) v += p[i];
-    v = wave_sum_i64(v);
-    if (lane_id() == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    const i64 t = sh[0] + sh[1] + sh[2] + sh[3];
-    __syncthreads();
-    return t;
-}
 
 // ------------------------------------------------------------------------------------ chain + work list in two kernels
 // k_chain_count: one workgroup per tile of 2048 signatures.  A chained cluster belongs to the tile it STARTS in.
@@ -891,7 +753,7 @@ __global__ __launch_bounds__(256) void k_chain_ids(DevBatch B)
     run += (int)(sh[0] + sh[1] + sh[2] + sh[3]);
 #pragma unroll
     for (int r = 0; r < CH_ITEMS; r++) {
-        const u64 m = (u64)readlane_i64x((i64)mw, wv * CH_ITEMS + r);
+        const u64 m = (u64)readlane_i64((i64)mw, wv * CH_ITEMS + r);
         const i64 w = base + r * WAVE + lane_id();
         if (w < B.W) { B.cluster_id[w] = run + __popcll(m & (lanemask_lt() | (1ull << lane_id()))) - 1; B.allele_id[w] = -1; }
         run += __popcll(m);
@@ -1470,9 +1332,9 @@ template <class VP> __device__ __forceinline__ int cipos_wave(VP v, int n, i64 s
         if (!__ballot(act && j == 0 && start + e < len)) break;
         if (act && j == 0 && start + e < len) { const double x = (double)v[off + start + e] - mean; res += x * x; }
     }
-    const double l0 = __longlong_as_double(readlane_i64x(__double_as_longlong(res), 0));
-    const double l1 = __longlong_as_double(readlane_i64x(__double_as_longlong(res), 8));
-    const double l2 = __longlong_as_double(readlane_i64x(__double_as_longlong(res), 16));
+    const double l0 = __longlong_as_double(readlane_i64(__double_as_longlong(res), 0));
+    const double l1 = __longlong_as_double(readlane_i64(__double_as_longlong(res), 8));
+    const double l2 = __longlong_as_double(readlane_i64(__double_as_longlong(res), 16));
     const double tot = cnt == 1 ? l0 : (cnt == 2 ? l0 + l1 : l0 + (l1 + l2));
     const double sd = sqrt(tot / (double)n);
     return (int)(1.96 * sd / sqrt_tab[n]);
@@ -2102,12 +1964,6 @@ template <int BLOCK, int CAP, bool BIG> __global__ __launch_bounds__(BLOCK, (BLO
 //            instruction count per cluster;  SW = 64: one cluster of 32 < m <= 64 per wavefront.
 // Scalars of a cluster (segment flags, sizes) are per-lane values that are uniform inside a sub-wave; every
 // cross-lane operation is executed by all 64 lanes in wave-uniform control flow.
-__device__ __forceinline__ i64 readlane_i64(i64 v, int l)
-{
-    const int lo = __builtin_amdgcn_readlane((int)(v & 0xffffffffll), l);
-    const int hi = __builtin_amdgcn_readlane((int)(v >> 32), l);
-    return ((i64)hi << 32) | (unsigned)lo;
-}
 __device__ __forceinline__ double shfl_f64(double v, int src) { return __longlong_as_double(shfl_i64(__double_as_longlong(v), src)); }
 __device__ __forceinline__ i64 permute_i64(int dest_lane, i64 v)      // lane i sends v to lane dest_lane (a bijection)
 {
@@ -3425,7 +3281,7 @@ template <bool RN> __global__ __launch_bounds__(256) void k_reads_gather(DevBatc
         } else {
             cm = lane63_i64(wave_incl_max_i64(vmax)); cl = lane63_i64(wave_incl_max_i64(vlen));
         }
-        const i64 f0 = readlane_i64x(st[r], 0);                                // (lane 0 of a chunk is always a row of the table)
+        const i64 f0 = readlane_i64(st[r], 0);                                // (lane 0 of a chunk is always a row of the table)
         if (lane == 0) { ((rd_t<RN>*)B.cmax)[c0 >> 6] = (rd_t<RN>)cm; ((rd_t<RN>*)B.cfirst)[c0 >> 6] = (rd_t<RN>)f0; if (((c0 >> 6) & 63) == 0) ((rd_t<RN>*)B.bfirst)[c0 >> 12] = (rd_t<RN>)f0; }
         span_len = cl > span_len ? cl : span_len;
     }
@@ -3973,7 +3829,7 @@ __device__ __forceinline__ int tg_find_or_insert(int* ids, int bits, int id, int
     }
 }
 
-__device__ __forceinline__ i64 tra_up_bound(i64 num)     // threshold_ref_count, cuteSV_genotype.py:62-70
+__host__ __device__ __forceinline__ i64 tra_up_bound(i64 num)     // threshold_ref_count, cuteSV_genotype.py:62-70
 {
     if (num <= 2) return 20 * num;
     if (num <= 5) return 9 * num;
@@ -4079,8 +3935,9 @@ template <bool RN> __device__ bool tra_call(const DevBatch& B, int c, int* ids, 
     return true;
 }
 
-// table bits that surely hold a TRA call: supports + at most up_bound querydata names per window + one chunk
-__device__ __forceinline__ int tra_bits_for(i64 ns)
+// table bits that surely hold a TRA call: supports + at most up_bound querydata names per window + one chunk (the host sizes
+// the name sets of csv_aln_tra_genotype with it too)
+__host__ __device__ __forceinline__ int tra_bits_for(i64 ns)
 {
     const i64 need = ns + 2 * (tra_up_bound(ns) + 64) + 128;
     int bits = 10;

@@ -11,8 +11,8 @@
 // one row per kept record, grouped by chromosome, in append order (inside an append: record order).
 //
 //   k_reads_keep    one thread per decoded record: cnt = {flag byte & mask != 0, 0, 0, 0}; the flag bytes are the gates column
-//                   (mask = CSV_GATE_READS) or the caller's keep bytes (mask = 0xff); the scan is the CIGAR scan's
-//                   (k_cigar_tiles / k_cigar_offsets)
+//                   (mask = CSV_GATE_READS) or the caller's keep bytes (mask = 0xff); the exclusive scan is
+//                   scan.hip.h's (scan_counts: k_scan_tiles / k_scan_offsets)
 //   k_reads_store   one thread per decoded record: the kept ones become rows behind the table's last row (four stores); the
 //                   thread of the last kept record also leaves its id - the largest of the append - in last_id
 //   k_reads_put     the same for rows that came from host arrays
@@ -23,6 +23,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "wave.hip.h"
 
 namespace csv {
 

@@ -10,7 +10,7 @@
 //                    off[i], high nibble first; len[i] = -1: not uploaded
 //   k_seq_plan_*     one thread per new row: the length of its bases (the pieces / the slice, clipped to the read like a
 //                    Python slice) - it must equal the pool row's aux - and the reasons a row cannot be cut (no uploaded read,
-//                    a negative bound); the lengths go through the scan of cigar.hip.h (k_cigar_tiles / k_cigar_offsets)
+//                    a negative bound); the lengths go through the scan of scan.hip.h (k_scan_tiles / k_scan_offsets)
 //   k_seq_gather_*   one wavefront per row: lanes stride over the output, 4 ASCII bytes from 2 (odd start: 3) packed bytes,
 //                    one 32-bit store per lane and step; the bytes before the first aligned word and behind the last one are
 //                    written one by one.  A split-read slice of the reverse complement is index arithmetic on the stored read.
@@ -22,6 +22,9 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "wave.hip.h"
+#include "cigar.hip.h"
+#include "split.hip.h"
 
 namespace csv {
 

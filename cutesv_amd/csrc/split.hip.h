@@ -16,6 +16,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "wave.hip.h"
+#include "cigar.hip.h"
 
 namespace csv {
 

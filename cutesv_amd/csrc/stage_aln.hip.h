@@ -50,16 +50,6 @@ static int aln_commit(csv_ctx* c, const char* what, const AlnAppend& A, i64 uppe
     return CSV_OK;
 }
 
-// slots (as a power of two) of the name set that surely holds a call with ns supports: tra_bits_for of kernels.hip.h on the host
-static int aln_bits_for(i64 ns)
-{
-    const i64 up = ns <= 2 ? 20 * ns : ns <= 5 ? 9 * ns : ns <= 15 ? 7 * ns : 5 * ns;
-    const i64 need = ns + 2 * (up + 64) + 128;
-    int bits = 10;
-    while ((3ll << bits) / 4 < need + 64) bits++;
-    return bits;
-}
-
 extern "C" {
 
 int csv_aln_reset(csv_ctx* c, int32_t n_chrom)
@@ -95,20 +85,16 @@ int csv_aln_append_decoded(csv_ctx* c, int32_t chrom, int64_t beg, int64_t end, 
     if (n == 0) return CSV_OK;
     HIP_TRY(c, hipSetDevice(c->device));
     hipStream_t st = c->stream;
-    const int ntile = div_up(n, CG_TILE);
     // work: pending words and the scan's totals (128 bytes, cleared), per record {keep -> offset}, the tile sums
     const size_t o_cnt = 128, o_tiles = o_cnt + (((size_t)(n + 1) * 16 + 255) & ~(size_t)255);
     AlnAppend A{};
-    TRY(aln_begin(c, chrom, n, o_tiles + (size_t)ntile * 24 + 64, &A));
+    TRY(aln_begin(c, chrom, n, o_tiles + scan_tile_bytes(n) + 64, &A));
     char* g = (char*)c->al.work.p;
     i64* tot = (i64*)(g + 64);
     int4* cnt = (int4*)(g + o_cnt);
     HIP_TRY(c, hipEventRecord(c->ev[0], st));
     hipLaunchKernelGGL(k_aln_keep, dim3(div_up(n, 256)), dim3(256), 0, st, dp<i64>(c->bm.start), n, (i64)beg, (i64)end, cnt);
-    CigarArgs SC{};                                             // the keep flags' prefix is the CIGAR scan's (k_cigar_tiles / k_cigar_offsets)
-    SC.n_reads = n; SC.cnt = cnt; SC.tile_sum = (i64*)(g + o_tiles); SC.totals = tot;
-    hipLaunchKernelGGL(k_cigar_tiles, dim3(ntile), dim3(256), 0, st, SC);
-    hipLaunchKernelGGL(k_cigar_offsets, dim3(ntile), dim3(256), 0, st, SC);
+    scan_counts(st, ScanArgs{n, cnt, (i64*)(g + o_tiles), tot});   // the keep flags' exclusive prefix
     hipLaunchKernelGGL(k_aln_store, dim3(div_up(n, 256)), dim3(256), 0, st, A, dp<i64>(c->bm.start), dp<i64>(c->bm.end), dp<int>(c->bm.flag), n, (i64)beg, (i64)end, (int)name_base,
                        cnt, tot);
     return aln_commit(c, "csv_aln_append_decoded", A, n, name_base + n - 1, n_appended);
@@ -212,7 +198,7 @@ int csv_aln_tra_genotype(csv_ctx* c, int64_t n_calls, const int32_t* chrom1, con
     std::vector<i64> big_off;
     i64 gset = 0;
     for (i64 k = 0; k < n_calls; k++) {
-        const int bits = aln_bits_for(support_off[k + 1] - support_off[k]);
+        const int bits = tra_bits_for(support_off[k + 1] - support_off[k]);
         if (bits <= 12) continue;
         big.push_back((int)k); big_off.push_back(gset);
         gset += 2ll << bits;

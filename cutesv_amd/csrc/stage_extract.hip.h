@@ -28,7 +28,6 @@ int csv_cigar_signatures(csv_ctx* c, const csv_cigar_in* in, csv_cigar_out* out)
     for (i64 r = 0; r < n && !from_bam; r++)                    // the kernels index `cigar` with these: every offset is checked here
         if (in->cig_off[r] < 0 || in->cig_off[r + 1] < in->cig_off[r] || in->cig_off[r + 1] > nops)
             return fail(c, CSV_E_INVALID, "cig_off decreases or leaves the CIGAR array at read %lld", (long long)r);
-    const int ntile = div_up(n, CG_TILE);
     // every op can be a piece and a signature of its own: size the outputs for the worst case the caller allows, but never
     // more than the operations there are
     const i64 cap_i = out->cap_sig_ins < nops ? out->cap_sig_ins : nops, cap_p = out->cap_piece_ins < nops ? out->cap_piece_ins : nops,
@@ -38,7 +37,7 @@ int csv_cigar_signatures(csv_ctx* c, const csv_cigar_in* in, csv_cigar_out* out)
     if (!from_bam) { P.add(c->cg.off, (n + 1) * 8); P.add(c->cg.ops, (nops + 1) * 4); P.add(c->cg.start, n * 8); }
     P.add(c->cg.use, n); P.add(c->cg.cnt, n * 16);
     if (to_pool && in->query_len) P.add(c->cg.qlen, n * 4);
-    P.add(c->cg.tiles, (size_t)ntile * 24); P.add(c->cg.tot, 32);
+    P.add(c->cg.tiles, scan_tile_bytes(n)); P.add(c->cg.tot, 32);
     P.add(c->cg.iread, (cap_i + 1) * 4); P.add(c->cg.ipos, (cap_i + 1) * 8); P.add(c->cg.ilen, (cap_i + 1) * 8); P.add(c->cg.ip0, (cap_i + 1) * 8); P.add(c->cg.inp, (cap_i + 1) * 4);
     P.add(c->cg.pq, (cap_p + 1) * 4); P.add(c->cg.pl, (cap_p + 1) * 4);
     P.add(c->cg.dread, (cap_d + 1) * 4); P.add(c->cg.dpos, (cap_d + 1) * 8); P.add(c->cg.dlen, (cap_d + 1) * 8);
@@ -53,7 +52,7 @@ int csv_cigar_signatures(csv_ctx* c, const csv_cigar_in* in, csv_cigar_out* out)
     A.use = in->use ? dp<uint8_t>(c->cg.use) : use_gates ? dp<uint8_t>(c->bm.gates) : nullptr;
     A.use_mask = use_gates ? CSV_GATE_USE : 255;
     A.min_siglength = in->min_siglength; A.merge_ins = in->merge_ins_threshold; A.merge_del = in->merge_del_threshold;
-    A.cnt = dp<int4>(c->cg.cnt); A.tile_sum = dp<i64>(c->cg.tiles); A.totals = dp<i64>(c->cg.tot);
+    A.cnt = dp<int4>(c->cg.cnt);
     A.ins_read = dp<int>(c->cg.iread); A.ins_pos = dp<i64>(c->cg.ipos); A.ins_len = dp<i64>(c->cg.ilen); A.ins_piece0 = dp<i64>(c->cg.ip0);
     A.ins_npiece = dp<int>(c->cg.inp); A.piece_qoff = dp<int>(c->cg.pq); A.piece_len = dp<int>(c->cg.pl);
     A.del_read = dp<int>(c->cg.dread); A.del_pos = dp<i64>(c->cg.dpos); A.del_len = dp<i64>(c->cg.dlen);
@@ -61,8 +60,7 @@ int csv_cigar_signatures(csv_ctx* c, const csv_cigar_in* in, csv_cigar_out* out)
     TwoPhaseTimer T{c};
     TRY(T.count_begin());
     hipLaunchKernelGGL(k_cigar_count, dim3(grid), dim3(256), 0, st, A);
-    hipLaunchKernelGGL(k_cigar_tiles, dim3(ntile), dim3(256), 0, st, A);
-    hipLaunchKernelGGL(k_cigar_offsets, dim3(ntile), dim3(256), 0, st, A);
+    scan_counts(st, ScanArgs{n, A.cnt, dp<i64>(c->cg.tiles), dp<i64>(c->cg.tot)});
     TRY(T.count_end());
     i64 tot[3] = {0, 0, 0};
     HIP_TRY(c, hipMemcpyAsync(tot, c->cg.tot.p, 24, hipMemcpyDeviceToHost, st));
@@ -126,7 +124,6 @@ int csv_split_signatures(csv_ctx* c, const csv_split_in* in, csv_split_out* out)
     if (ne >= (1ll << 31) - 4096 || n >= (1ll << 31) - 4096) return fail(c, CSV_E_INVALID, "split-read batch too large: split it");
     for (i64 r = 0; r < n && !from_bam; r++)
         if (in->ent_off[r + 1] < in->ent_off[r]) return fail(c, CSV_E_INVALID, "ent_off decreases at read %lld", (long long)r);
-    const int ntile = div_up(n, CG_TILE);
     // the candidate columns are sized for what the caller allows, but never for more than the entries can yield: a read of s
     // segments emits nothing for s < 2, at most 3 candidates for s = 2 and at most 12 per window of three plus 2 for s >= 3
     // (split_read: the rules of one window that can fire together put 2 + 2 + 6 + 2) - at most 12 per entry either way
@@ -137,7 +134,7 @@ int csv_split_signatures(csv_ctx* c, const csv_split_in* in, csv_split_out* out)
         P.add(c->sp.chr, (ne + 1) * 4); P.add(c->sp.mapq, (ne + 1) * 4); P.add(c->sp.strand, ne + 1); P.add(c->sp.primary, ne + 1);
     }
     P.add(c->sp.seg, (ne + 1) * sizeof(SpSeg));
-    P.add(c->sp.cnt, n * 16); P.add(c->sp.tiles, (size_t)ntile * 24); P.add(c->sp.tot, 32);
+    P.add(c->sp.cnt, n * 16); P.add(c->sp.tiles, scan_tile_bytes(n)); P.add(c->sp.tot, 32);
     P.add(c->sp.kind, cap + 1); P.add(c->sp.read, (cap + 1) * 4); P.add(c->sp.ochr, (cap + 1) * 4); P.add(c->sp.aux, (cap + 1) * 4);
     P.add(c->sp.a, (cap + 1) * 8); P.add(c->sp.b, (cap + 1) * 8); P.add(c->sp.c, (cap + 1) * 8); P.add(c->sp.d, (cap + 1) * 8);
     c->vs.stale();                                          // (the scratch arena is planned afresh: a kept rebuild's columns are gone)
@@ -161,14 +158,11 @@ int csv_split_signatures(csv_ctx* c, const csv_split_in* in, csv_split_out* out)
     A.seg = dp<SpSeg>(c->sp.seg); A.cnt = dp<int4>(c->sp.cnt); A.cap = cap;
     A.kind = dp<uint8_t>(c->sp.kind); A.read = dp<int>(c->sp.read); A.o_chr = dp<int>(c->sp.ochr); A.aux = dp<int>(c->sp.aux);
     A.a = dp<i64>(c->sp.a); A.b = dp<i64>(c->sp.b); A.c = dp<i64>(c->sp.c); A.d = dp<i64>(c->sp.d);
-    CigarArgs SC{};                                         // the per-read prefix is the CIGAR scan's (k_cigar_tiles / k_cigar_offsets)
-    SC.n_reads = n; SC.cnt = A.cnt; SC.tile_sum = dp<i64>(c->sp.tiles); SC.totals = dp<i64>(c->sp.tot);
     const int grid = div_up(n, 256);
     TwoPhaseTimer T{c};
     TRY(T.count_begin());
     hipLaunchKernelGGL(k_split_count, dim3(grid), dim3(256), 0, st, A);
-    hipLaunchKernelGGL(k_cigar_tiles, dim3(ntile), dim3(256), 0, st, SC);
-    hipLaunchKernelGGL(k_cigar_offsets, dim3(ntile), dim3(256), 0, st, SC);
+    scan_counts(st, ScanArgs{n, A.cnt, dp<i64>(c->sp.tiles), dp<i64>(c->sp.tot)});
     TRY(T.count_end());
     i64 tot[3] = {0, 0, 0};
     HIP_TRY(c, hipMemcpyAsync(tot, c->sp.tot.p, 24, hipMemcpyDeviceToHost, st));

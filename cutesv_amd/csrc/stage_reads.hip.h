@@ -67,9 +67,8 @@ int csv_reads_append_decoded(csv_ctx* c, int32_t chrom, int64_t n_records, const
     HIP_TRY(c, hipSetDevice(c->device));
     hipStream_t st = c->stream;
     ReadsTabState& t = c->rt;
-    const int ntile = div_up(n, CG_TILE);
     // work: the last id and the scan's totals (128 bytes, cleared), per record {keep -> offset}, the tile sums, the caller's keep bytes
-    const size_t o_cnt = 128, o_tiles = o_cnt + (((size_t)(n + 1) * 16 + 255) & ~(size_t)255), o_keep = (o_tiles + (size_t)ntile * 24 + 64 + 255) & ~(size_t)255;
+    const size_t o_cnt = 128, o_tiles = o_cnt + (((size_t)(n + 1) * 16 + 255) & ~(size_t)255), o_keep = (o_tiles + scan_tile_bytes(n) + 64 + 255) & ~(size_t)255;
     TRY(reserve(c, t.work, o_keep + (keep ? (size_t)n : 0) + 64));
     char* g = (char*)t.work.p;
     int* last_id = (int*)g;
@@ -82,10 +81,7 @@ int csv_reads_append_decoded(csv_ctx* c, int32_t chrom, int64_t n_records, const
     TwoPhaseTimer T{c};
     TRY(T.count_begin());
     hipLaunchKernelGGL(k_reads_keep, dim3(div_up(n, 256)), dim3(256), 0, st, flags, mask, n, cnt);
-    CigarArgs SC{};                                             // the keep flags' prefix is the CIGAR scan's (k_cigar_tiles / k_cigar_offsets)
-    SC.n_reads = n; SC.cnt = cnt; SC.tile_sum = (i64*)(g + o_tiles); SC.totals = tot;
-    hipLaunchKernelGGL(k_cigar_tiles, dim3(ntile), dim3(256), 0, st, SC);
-    hipLaunchKernelGGL(k_cigar_offsets, dim3(ntile), dim3(256), 0, st, SC);
+    scan_counts(st, ScanArgs{n, cnt, (i64*)(g + o_tiles), tot});   // the keep flags' exclusive prefix
     TRY(T.count_end());
     i64 m = 0;
     HIP_TRY(c, hipMemcpyAsync(&m, tot, 8, hipMemcpyDeviceToHost, st));

@@ -96,8 +96,7 @@ template <class PlanFn, class GatherFn> static int seq_attach(csv_ctx* c, i64 ro
 {
     SeqState& s = c->seq;
     hipStream_t st = c->stream;
-    const int ntile = div_up(n_plan > 0 ? n_plan : 1, CG_TILE);
-    const size_t o_tiles = ((size_t)(n_plan + 1) * 16 + 255) & ~(size_t)255, o_tot = o_tiles + (size_t)ntile * 24 + 8;
+    const size_t o_tiles = ((size_t)(n_plan + 1) * 16 + 255) & ~(size_t)255, o_tot = o_tiles + scan_tile_bytes(n_plan > 0 ? n_plan : 1) + 8;
     TRY(reserve(c, s.plan, o_tot + 64));
     int4* cnt = (int4*)s.plan.p;
     i64* tot = (i64*)((char*)s.plan.p + ((o_tot + 7) & ~(size_t)7));
@@ -107,10 +106,7 @@ template <class PlanFn, class GatherFn> static int seq_attach(csv_ctx* c, i64 ro
     i64 got[5] = {0, 0, 0, 0, 0};
     if (n_plan > 0) {
         plan(cnt, err);
-        CigarArgs SC{};                                         // the lengths' prefix is the CIGAR scan's (k_cigar_tiles / k_cigar_offsets)
-        SC.n_reads = n_plan; SC.cnt = cnt; SC.tile_sum = (i64*)((char*)s.plan.p + o_tiles); SC.totals = tot;
-        hipLaunchKernelGGL(k_cigar_tiles, dim3(ntile), dim3(256), 0, st, SC);
-        hipLaunchKernelGGL(k_cigar_offsets, dim3(ntile), dim3(256), 0, st, SC);
+        scan_counts(st, ScanArgs{n_plan, cnt, (i64*)((char*)s.plan.p + o_tiles), tot});   // the lengths' exclusive prefix
     }
     HIP_TRY(c, hipEventRecord(c->ev[7], st));
     HIP_TRY(c, hipGetLastError());

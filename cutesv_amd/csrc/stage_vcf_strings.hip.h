@@ -20,8 +20,7 @@ static int vs_gather(csv_ctx* c, const char* what, i64 n_items, i64 n_off, size_
 {
     VcfStrState& v = c->vs;
     hipStream_t st = c->stream;
-    const int ntile = div_up(n_items, CG_TILE);
-    const size_t o_cnt = (front + 255) & ~(size_t)255, o_tiles = o_cnt + (((size_t)(n_items + 1) * 16 + 255) & ~(size_t)255), o_tot = o_tiles + (((size_t)ntile * 24 + 255) & ~(size_t)255),
+    const size_t o_cnt = (front + 255) & ~(size_t)255, o_tiles = o_cnt + (((size_t)(n_items + 1) * 16 + 255) & ~(size_t)255), o_tot = o_tiles + ((scan_tile_bytes(n_items) + 255) & ~(size_t)255),
                  o_off = o_tot + 64;
     TRY(reserve(c, v.work, o_off + (size_t)(n_off + 1) * 8 + 64));
     char* g = (char*)v.work.p;
@@ -31,10 +30,7 @@ static int vs_gather(csv_ctx* c, const char* what, i64 n_items, i64 n_off, size_
     TRY(upload(g));
     HIP_TRY(c, hipMemsetAsync(tot, 0, 40, st));
     plan(g, cnt, err);
-    CigarArgs SC{};                                             // the lengths' prefix is the CIGAR scan's (k_cigar_tiles / k_cigar_offsets)
-    SC.n_reads = n_items; SC.cnt = cnt; SC.tile_sum = (i64*)(g + o_tiles); SC.totals = tot;
-    hipLaunchKernelGGL(k_cigar_tiles, dim3(ntile), dim3(256), 0, st, SC);
-    hipLaunchKernelGGL(k_cigar_offsets, dim3(ntile), dim3(256), 0, st, SC);
+    scan_counts(st, ScanArgs{n_items, cnt, (i64*)(g + o_tiles), tot});   // the lengths' exclusive prefix
     offsets(g, cnt, tot, (i64*)(g + o_off));
     HIP_TRY(c, hipGetLastError());
     i64 got[5] = {0, 0, 0, 0, 0};

@@ -7,7 +7,7 @@
 //   k_alt_plan      one thread per pick: length = min(aux, clip), status (the row has no sequence)
 //   k_join_plan     one thread per support: length of its name + 1 (the comma, or the slot the last name of a call leaves
 //                   unused), status (a rank outside the name pool's)
-//   scan            the lengths go through the scan of cigar.hip.h (k_cigar_tiles / k_cigar_offsets), as seqs.hip.h's do
+//   scan            the lengths go through the scan of scan.hip.h (k_scan_tiles / k_scan_offsets), as seqs.hip.h's do
 //   k_vs_offsets    the scanned lengths as the caller's 64-bit offsets;  k_join_call_off  the same per call: byte position
 //                   of support j of call c = P[j] - (non-empty calls in front of c), P = the exclusive scan of len + 1
 //   k_alt_copy      one wavefront per pick, lanes stride over the output: single bytes up to the first aligned word and behind
@@ -18,6 +18,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "wave.hip.h"
+#include "names.hip.h"
 
 namespace csv {
 

@@ -1,7 +1,9 @@
 """The Python face of the C ABI: every prototype is bound when the library loads, every struct has one mirror (in _abi), the
 library's struct sizes are checked at load, and the one capacity-negotiating call of extract.py really negotiates: batches
-that overrun the first capacity guess, through the oracle (CPU) and through a Context (gpu), host arrays and pool rows."""
+that overrun the first capacity guess, through the oracle (CPU) and through a Context (gpu), host arrays and pool rows.  Also
+the rule of the library's device headers: each compiles as the only include of a translation unit."""
 import os
+import shutil
 import subprocess
 import sys
 
@@ -65,6 +67,31 @@ def test_a_struct_of_another_size_fails_the_load(monkeypatch):
     with pytest.raises(_lib.ExtensionMissing, match="csv_sa_out"):
         _lib.lib()
     assert _lib._LIB is None
+
+
+# ------------------------------------------------------------------------------------ device headers stand alone
+CSRC = os.path.join(ROOT, "cutesv_amd", "csrc")
+HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+# the device headers: every *.hip.h that is not host code of the one translation unit (ctx.hip.h, stage_*.hip.h)
+DEVICE_HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith(".hip.h") and f != "ctx.hip.h" and not f.startswith("stage_"))
+
+
+def test_the_makefile_checks_the_same_device_headers():
+    """`make headers` walks DEV_HDRS: the list is the directory's"""
+    with open(os.path.join(CSRC, "Makefile")) as f:
+        line = [ln for ln in f if ln.startswith("DEV_HDRS")]
+    assert len(line) == 1 and sorted(line[0].split("=", 1)[1].split()) == DEVICE_HEADERS
+    assert len(DEVICE_HEADERS) == 14
+
+
+@pytest.mark.skipif(not os.path.exists(HIPCC), reason="no hipcc")
+@pytest.mark.parametrize("header", DEVICE_HEADERS)
+def test_a_device_header_compiles_alone(header, tmp_path):
+    """a device header includes what it uses: a translation unit of that one include passes the compiler's front end"""
+    tu = tmp_path / "alone.hip"
+    tu.write_text('#include "%s"\n' % header)
+    p = subprocess.run([HIPCC, "-std=c++17", "--offload-arch=gfx950", "-fsyntax-only", "-I", CSRC, str(tu)], capture_output=True, text=True)
+    assert p.returncode == 0, p.stderr[-2000:]
 
 
 # ------------------------------------------------------------------------------------ CIGAR retry

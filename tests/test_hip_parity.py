@@ -925,6 +925,38 @@ def test_cigar_scan_identical_to_reference_and_oracle(ctx):
     assert len(empty["ins_pos"]) == 0 and len(empty["del_pos"]) == 0
 
 
+def _scan_seam_batch(n):
+    """n short reads (0 .. 4 operations of M / I / D) whose INS signature, INS piece and DEL signature counts all differ"""
+    if n == 1:                                                          # one I and one D of at least 10 bases
+        cigar = np.array([20 << 4 | 0, 15 << 4 | 1, 8 << 4 | 0, 12 << 4 | 2, 30 << 4 | 0], np.uint32)
+        return np.array([0, 5], np.int64), cigar, np.array([1000], np.int64), np.ones(1, np.uint8)
+    rng = np.random.default_rng(n)
+    off = np.zeros(n + 1, np.int64); np.cumsum(rng.integers(0, 5, n), out=off[1:])
+    tot = int(off[-1])
+    op = rng.choice(np.array([0, 1, 2], np.uint32), tot, p=[0.3, 0.4, 0.3])
+    ln = np.where(op == 0, rng.integers(1, 40, tot), rng.integers(5, 60, tot)).astype(np.uint32)
+    return off, (ln << np.uint32(4)) | op, rng.integers(0, 200_000_000, n).astype(np.int64), (rng.random(n) < 0.9).astype(np.uint8)
+
+
+@pytest.mark.parametrize("n", [1, 255, 256, 257, 1023, 1024, 1025, 2047, 2048, 2049, 262144, 262145, 263169])
+def test_count_scan_seams(ctx, n):
+    """the three-column count scan (scan.hip.h) at its seams, through csv_cigar_signatures against the oracle: the 256-thread
+    step, the 1 024-entry tile, 256 tiles exactly (one trip of the carry loop, which strides by 256 tiles), 256 tiles + 1 and
+    257 tiles + 1.  The three scanned columns have different totals, so that a swapped or dropped column cannot cancel out."""
+    from cutesv_amd import extract
+    off, cigar, start, use = _scan_seam_batch(n)
+    kw = dict(min_siglength=10, merge_ins_threshold=100, merge_del_threshold=0)
+    want = _oracle().cigar_signatures(off, cigar, start, use, **kw)
+    totals = (len(want["ins_pos"]), len(want["piece_len"]), len(want["del_pos"]))
+    assert min(totals) > 0
+    if n >= 255:
+        assert len(set(totals)) == 3, totals
+    got = extract.cigar_signatures(ctx, off, cigar, start, use, **kw)
+    for k in want:
+        if k != "ms_device":
+            assert np.array_equal(got[k], want[k]), (k, n)
+
+
 def test_run_tra_shim_genotypes_like_the_reference(ctx, tmp_path, monkeypatch):
     """run_tra(action=True): clustering on the GPU + the reference's call_gt loop over the BAM (default), or everything on
     the GPU from the reads table (CUTESV_AMD_TRA_GT=reads_table); both give the reference's rows on the golden cases
