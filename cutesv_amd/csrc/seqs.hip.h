@@ -8,9 +8,9 @@
 //
 //   read sequences   SeqReads: the packed image csv_seq_reads_upload checked on the host, read i = (len[i] + 1) / 2 bytes at
 //                    off[i], high nibble first; len[i] = -1: not uploaded
-//   k_seq_plan_*     one thread per new row: the length of its bases (the pieces / the slice, clipped to the read like a
-//                    Python slice) - it must equal the pool row's aux - and the reasons a row cannot be cut (no uploaded read,
-//                    a negative bound); the lengths go through the scan of scan.hip.h (k_scan_tiles / k_scan_offsets)
+//   k_seq_plan_*     one thread per new row: the length of its bases (the pieces / the slice, cut like a Python slice:
+//                    py_slice of split.hip.h) - it must equal the pool row's aux - and the reasons a row cannot be cut (no
+//                    uploaded read, a negative CIGAR piece); the lengths go through the scan of scan.hip.h (k_scan_tiles / k_scan_offsets)
 //   k_seq_gather_*   one wavefront per row: lanes stride over the output, 4 ASCII bytes from 2 (odd start: 3) packed bytes,
 //                    one 32-bit store per lane and step; the bytes before the first aligned word and behind the last one are
 //                    written one by one.  A split-read slice of the reverse complement is index arithmetic on the stored read.
@@ -18,7 +18,9 @@
 //                    j < i; drop[i] = the nearest equal row in front of i has the same x.5 flag (rebuild.tie_callback's contract)
 //   k_seq_get*       bases by pool row into one blob (csv_seq_pool_get); k_seq_put* attach host-made sequences
 // Every loop is bounded by a row's length, its piece count or the group size; every byte read lies inside the range the host
-// checked on upload (a slice is clipped to [0, len) of its read first) or inside the blob the offsets were made for.
+// checked on upload or inside the blob the offsets were made for: a slice c:d goes through py_slice first - a negative bound
+// counts from the read's end, both are clamped to [0, len], start >= stop is empty - so that first >= 0 and first + length <= len,
+// and the gather reads bases first .. first + length - 1 (reversed: len - 1 - first down to len - first - length) of [0, len).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -30,7 +32,7 @@ namespace csv {
 
 struct SeqReads { const uint8_t* bytes; const i64* off; const int* len; i64 n; };
 struct SeqPool { uint8_t* blob; i64* off; uint8_t* half; };          // off[pool row] = first byte in blob, -1: the row has no sequence
-enum { SEQ_ERR_NO_READ = 1, SEQ_ERR_NEGATIVE = 2, SEQ_ERR_LENGTH = 4, SEQ_ERR_TAKEN = 8 };
+enum { SEQ_ERR_NO_READ = 1, SEQ_ERR_NEGATIVE = 2 /* a CIGAR piece; a split-read slice may have negative bounds */, SEQ_ERR_LENGTH = 4, SEQ_ERR_TAKEN = 8 };
 
 // "=ACMGRSVTWYHKDBN"[code], or its complement as extract._COMP has it: A <-> T, C <-> G, everything else unchanged
 __device__ __forceinline__ unsigned seq_ascii(unsigned code, bool comp)
@@ -72,13 +74,8 @@ __device__ __forceinline__ void seq_copy(const uint8_t* src, i64 start, i64 L, b
     if (lane < L - t0) dst[t0 + lane] = (uint8_t)seq_char(src, rev ? start - (t0 + lane) : start + t0 + lane, rev);
 }
 
-// a Python slice [q, e) of a sequence of l >= 0 bases, both bounds >= 0: -> {first, length}
-__device__ __forceinline__ i64 seq_clip(i64 q, i64 e, i64 l, i64* first)
-{
-    const i64 lo = q < l ? q : l, hi = e < l ? e : l;
-    *first = lo;
-    return hi > lo ? hi - lo : 0;
-}
+// a Python slice [q, e) of a sequence of l >= 0 bases: -> {first, length}
+__device__ __forceinline__ i64 seq_clip(i64 q, i64 e, i64 l, i64* first) { return py_slice(q, e, l, first); }
 
 // ------------------------------------------------------------------------------------ the CIGAR scan's INS rows
 // cnt[i] = {bytes of row i, 1, 0, 0} (zeros when the row cannot be cut: *err says why)
@@ -141,7 +138,6 @@ __global__ __launch_bounds__(256) void k_seq_plan_split(SeqReads S, SplitArgs A,
     int e = 0;
     i64 len = 0, first;
     if (l < 0) e = SEQ_ERR_NO_READ;
-    else if (A.c[i] < 0 || A.d[i] < 0) e = SEQ_ERR_NEGATIVE;
     else len = seq_clip(A.c[i], A.d[i], l, &first);
     if (!e && len != (i64)pool_aux[i]) e = SEQ_ERR_LENGTH;
     if (e) atomicOr(err, e);

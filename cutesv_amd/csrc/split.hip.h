@@ -192,6 +192,19 @@ __global__ __launch_bounds__(256) void k_split_emit(SplitArgs A)
     if (r < A.n_reads) split_read<true>(A, r, A.cnt[r].x);
 }
 
+// A kind-1 candidate's c:d is a Python slice of the read's l >= 0 bases (query[c:d], :231 / :247 / :455), and every place that turns
+// it into a length or into bytes gives it Python's meaning: a negative bound counts from the end (+ l), then both are clamped to
+// [0, l], and the slice is empty when start >= stop.  -> {first base, length}: first + length <= l.
+__device__ __forceinline__ i64 py_slice(i64 c, i64 d, i64 l, i64* first)
+{
+    if (c < 0) c += l;
+    if (d < 0) d += l;
+    c = c < 0 ? 0 : c > l ? l : c;
+    d = d < 0 ? 0 : d > l ? l : d;
+    *first = c;
+    return d > c ? d - c : 0;
+}
+
 // CSV_CG_TO_POOL: the candidates as rows of the device-resident signature pool (cigar.hip.h PoolCols), in the columns the rebuild
 // sorts on (cutesv_amd/columns.py from_tuple_lists has the same encoding: INV aux = strand code, TRA aux = chr2 * 8 + type)
 struct PoolSegBase { int b[5]; };
@@ -205,9 +218,9 @@ __global__ __launch_bounds__(256) void k_pool_from_split(PoolCols P, i64 base, S
     int ax = 0;
     if (kind == 1) {
         if (aux & 2) a >>= 1;                               // an x.5 position travels doubled: its integer part sorts
-        const i64 ql = query_len ? (i64)query_len[r] : A.read_len[r], c = A.c[i], d = A.d[i];
-        const i64 lo = c < ql ? c : ql, hi = d < ql ? d : ql;
-        ax = (int)(hi > lo ? hi - lo : 0);
+        const i64 ql = query_len ? (i64)query_len[r] : A.read_len[r];
+        i64 first;
+        ax = (int)py_slice(A.c[i], A.d[i], ql, &first);
     } else if (kind == 3) ax = aux;
     else if (kind == 4) ax = (int)(A.c[i] * 8 + aux);
     const i64 o = base + i;

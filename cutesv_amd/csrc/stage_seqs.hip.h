@@ -19,7 +19,7 @@ static int seq_sync(csv_ctx* c, i64 upto)
 static const char* seq_why(int err)
 {
     return (err & SEQ_ERR_NO_READ) ? "a row's read has no uploaded sequence (csv_seq_reads_upload; the `want` column)"
-         : (err & SEQ_ERR_NEGATIVE) ? "a slice bound is negative: such a row is cut on the host"
+         : (err & SEQ_ERR_NEGATIVE) ? "a CIGAR piece has a negative offset or length"
          : (err & SEQ_ERR_TAKEN) ? "a row has a sequence already"
          : "the length of a row's bases is not its aux (query_len must be the uploaded l_seq)";
 }

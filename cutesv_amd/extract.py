@@ -352,6 +352,9 @@ def split_signatures(ctx, enc, sv_size=30, min_mapq=20, max_split_parts=7, max_s
     the number of candidates.  seqs=True: the INS candidates' bases and x.5 flags go to the context's sequence pool, cut out of the
     sequences `upload_read_sequences` left on the device (one per read of `enc`); query_reverse[r] = 1: read r's record has flag 16,
     so the query parse_read analyses is the reverse complement of the uploaded sequence (None: no read is reversed).
+    An INS candidate's c:d is the reference's query[c:d] and has Python's slice meaning wherever it becomes a length (the pool row's
+    aux) or bytes (the sequence pool): a negative bound counts from the read's end, both are clamped to [0, read length], start >= stop
+    is empty.  A short first segment that overlaps the next one on the reference gives c < 0; such a batch is not refused.
     from_bam = the dict `split_inputs_bam` returned (pass enc=None): the reads are its calls and the entry columns are read where
     it left them on the device (CSV_SP_FROM_BAM); the result's `read` is the call index, a pool row's read index is
     read_base + call_rec[call] and the pool's query_len is the decode's; with seqs=True the uploaded sequences are the chunk's
@@ -366,7 +369,8 @@ def pool_rows_of_split(sig, seg_base, read_base, query_len):
     kind = sig["kind"].astype(np.int64); aux = sig["aux"].astype(np.int64)
     a = np.where((kind == 1) & ((aux & 2) != 0), sig["a"] >> 1, sig["a"])
     ql = np.asarray(query_len, np.int64)[sig["read"]]
-    lo, hi = np.minimum(sig["c"], ql), np.minimum(sig["d"], ql)
+    # q[c:d] as Python cuts it (py_slice in split.hip.h): a negative bound counts from the end, then [0, len], empty when start >= stop
+    lo, hi = (np.clip(np.where(x < 0, x + ql, x), 0, ql) for x in (sig["c"].astype(np.int64), sig["d"].astype(np.int64)))
     ax = np.where(kind == 1, np.maximum(hi - lo, 0), np.where(kind == 3, aux, np.where(kind == 4, sig["c"] * 8 + aux, 0)))
     return dict(seg=(np.asarray(seg_base, np.int64)[kind] + sig["chr"]).astype(np.int32), a=a.astype(np.int64), b=sig["b"].astype(np.int64),
                 read=(read_base + sig["read"]).astype(np.int32), aux=ax.astype(np.int32))

@@ -18,6 +18,8 @@ Outputs
                             what a whole task's extraction appends to the five candidate lists (8f row 4)
     split_sigs.json.gz      organize_split_signal / analysis_split_read (main script :50-513) driven with synthetic primary
                             alignments and SA-tag texts: the candidates of all five SV types each read yields (8f row 4)
+    split_edges.json.gz     the same functions on crafted reads, one family per rule of the analysis with one quantity moved across
+                            the rule's threshold, and on small-coordinate random reads whose INS slices leave [0, read length]
 """
 import gzip
 import importlib.machinery
@@ -154,8 +156,9 @@ def main_():
         try:
             from make_golden_cigar import cigar_golden
             cigar_golden(main)
-            from make_golden_split import split_golden
+            from make_golden_split import split_golden, split_edges
             split_golden(main)
+            split_edges(main)
             from make_golden_parse import parse_golden, single_pipe_golden
             parse_golden(main)
             single_pipe_golden(main)
