@@ -63,6 +63,8 @@ SYMBOLS = [
     ("csv_seq_struct_size", C.c_int, [C.c_int]),
     ("csv_seq_alt_gather", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),
     ("csv_name_support_join", C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    ("csv_pool_sigs_text", C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_char_p, C.c_char_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64),
+                                     C.POINTER(C.c_float)]),
     ("csv_aln_reset", C.c_int, [C.c_void_p, C.c_int32]),
     ("csv_aln_rows", C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
     ("csv_aln_append_decoded", C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_int64)]),

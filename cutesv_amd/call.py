@@ -2,7 +2,9 @@
 
     text, svid = call_bam("in.bam", fasta.Reference("ref.fa"), CallParams(Params.ont(min_support=3)))
     python -m cutesv_amd.call in.bam ref.fa -o out.body.vcf [--genotype] [--tra_gt MODE] [--report_readid] [--min_support N] [--batch B]
-                               [--include_bed FILE] [--reads_table {host,device}]
+                               [--include_bed FILE] [--reads_table {host,device}] [--sigs_dir DIR]
+
+(cuteSV's own command line - BAM REF OUT.vcf WORK_DIR and its flags, a VCF with header - is cutesv_amd/cli.py: python -m cutesv_amd.)
 
 Per task region the records are decoded, scanned and analysed on the device and their signatures, read names and inserted
 bases stay there (extract.task_to_pool with the name pool and the sequence pool); one rebuild sorts and de-duplicates the pool
@@ -109,7 +111,7 @@ class _Shim:
 
 
 def call_bam(bam, reference, params, ctx=None, chroms=None, batch=10_000_000, report_readid=False, ignore_sequence=False, threads=None, svid=None,
-             as_bytes=False, timings=None, tra_gt=None, include_bed=None, gates=None, reads_table=None):
+             as_bytes=False, timings=None, tra_gt=None, include_bed=None, gates=None, reads_table=None, sigs_dir=None):
     """-> (VCF body text, svid counters [INS, DEL, BND, DUP, INV]).
 
     bam        a path or an open bam.BamFile (coordinate-sorted; no index is needed)
@@ -118,7 +120,7 @@ def call_bam(bam, reference, params, ctx=None, chroms=None, batch=10_000_000, re
     ctx        an engine.Context (default: one on device 0 for the call); its pool, name pool and sequence pool are reset
     chroms     the contigs to call on (default: all of the header); TRA mates may lie on any contig of the header
     batch      reference bases per extraction task (the reference's -b)
-    timings    a dict that receives the wall milliseconds of the stages (tasks, rebuild, cluster, tra_gt, gather, emit)
+    timings    a dict that receives the wall milliseconds of the stages (tasks, rebuild, sigs, cluster, tra_gt, gather, emit)
     tra_gt     how TRA calls are genotyped: "alignments", "reads_table" or "off"; None follows CUTESV_AMD_TRA_GT (ValueError for
                bam, see tra_gt_mode)
     include_bed  a BED file's path or a bed.Regions: only call where these regions are (the reference's -include_bed).  Every task
@@ -130,7 +132,10 @@ def call_bam(bam, reference, params, ctx=None, chroms=None, batch=10_000_000, re
     reads_table  "host" or "device": where the genotyping reads table is built (only with params.genotype; None: DEFAULT_READS_TABLE).
                host: every task's rows are cut out of the downloaded columns and the table is assembled with numpy (reads.table_host);
                device: the tasks append their rows to the context's device-resident table (reads.append_decoded), the name ranks are
-               gathered there and the engine copies the columns device to device.  Same text either way."""
+               gathered there and the engine copies the columns device to device.  Same text either way.
+    sigs_dir   a directory that receives the rebuilt signatures as cuteSV's --write_old_sigs files (DEL.sigs .. TRA.sigs, made on the
+               device by rebuild.write_sigs right after the rebuild; empty files when the BAM yields no signature).  The
+               returned text and svid do not depend on it.  None: no files."""
     from . import aln, bam as bam_mod, bed as bed_mod, engine, extract, reads as reads_mod, rebuild, vcf
     if reads_table is None:
         reads_table = DEFAULT_READS_TABLE
@@ -182,12 +187,18 @@ def call_bam(bam, reference, params, ctx=None, chroms=None, batch=10_000_000, re
                     tables.append((crank[c], r))
         lap("ms_tasks")
         if rebuild.pool_rows(ctx) == 0:
+            if sigs_dir is not None:                           # (no signature at all: five empty files, as the reference's open(..., "w") leaves them)
+                for t in TYPES:
+                    open(os.path.join(sigs_dir, t + ".sigs"), "wb").close()
             return (b"" if as_bytes else ""), (np.zeros(5, np.int64) if svid is None else svid)
         order, _, major, nodedup = rebuild._segments(names, True)
         rb = rebuild.rebuild_pool_by_name(ctx, major, nodedup, keep_on_device=True, ties="seqs")
         if rb["n_ins_ties"]:
             raise ValueError("%d INS rows were not settled on the device" % rb["n_ins_ties"])
         lap("ms_rebuild")
+        if sigs_dir is not None:
+            rebuild.write_sigs(ctx, rb, names, sigs_dir)
+            lap("ms_sigs")
         off = np.r_[0, np.cumsum(rb["seg_count"])]
         have_len = p.genotype_tra
         segs = [segment_record(TYPES[s // n_chrom], order[s % n_chrom], int(off[s]), int(off[s + 1]), p, have_contig_len=have_len)
@@ -257,6 +268,7 @@ def main(argv=None):
                     help="with --genotype: where the genotyping reads table is built (default: %s)" % DEFAULT_READS_TABLE)
     ap.add_argument("--tra_gt", default=None, choices=list(TRA_GT_MODES),
                     help="with --genotype: how BND records are genotyped (default: CUTESV_AMD_TRA_GT, else alignments - every alignment counts, as in cuteSV)")
+    ap.add_argument("--sigs_dir", default=None, metavar="DIR", help="also write the rebuilt signatures there as cuteSV's --write_old_sigs files (DEL.sigs .. TRA.sigs)")
     a = ap.parse_args(argv)
     tra_gt = a.tra_gt
     if tra_gt is None and a.genotype and "CUTESV_AMD_TRA_GT" not in os.environ:
@@ -266,7 +278,7 @@ def main(argv=None):
                     merge_del_threshold=a.merge_del_threshold, merge_ins_threshold=a.merge_ins_threshold)
     text, svid = call_bam(a.bam, fasta.Reference(a.reference), cp, chroms=a.chroms.split(",") if a.chroms else None, batch=a.batch,
                           report_readid=a.report_readid, ignore_sequence=a.ignore_sequence, threads=a.threads, as_bytes=True, tra_gt=tra_gt,
-                          include_bed=a.include_bed, reads_table=a.reads_table)
+                          include_bed=a.include_bed, reads_table=a.reads_table, sigs_dir=a.sigs_dir)
     with open(a.out, "wb") as f:
         f.write(text)
     print("%d records: INS %d, DEL %d, BND %d, DUP %d, INV %d" % (text.count(b"\n"), *svid.tolist()))

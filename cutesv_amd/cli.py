@@ -1,0 +1,166 @@
+"""cuteSV's command line on this project's chain:
+
+    python -m cutesv_amd BAM REF OUT.vcf WORK_DIR [cuteSV's flags] [--reads_table {host,device}] [--tra_gt MODE]
+
+`parse_args` accepts every option of cuteSV v2.1.4 under the same short and long spellings, with the same destination, type
+and default, so a command line written for cuteSV runs here unchanged; `main` maps them onto call.call_bam and writes a complete
+VCF file: vcf.header_text followed by the records.  With --write_old_sigs the work directory receives DEL.sigs, INS.sigs,
+DUP.sigs, INV.sigs and TRA.sigs, made on the device (rebuild.write_sigs); without --retain_work_dir they are removed again at
+the end, as cuteSV's cleanup removes its own.
+
+What differs from cuteSV, on purpose:
+  * The extraction tasks are call.cut_tasks' uniform cut of every contig by -b.  cuteSV shrinks the batch of a contig that holds
+    many reads, from the BAM index statistics.  The calls do not depend on the cut - except with -include_bed, where a task's
+    reads are tested against the regions of that task only: there the calls can differ from cuteSV's on contigs whose batch it
+    would have shrunk.  (That cut needs a .bai reader, which this project does not have.)
+  * reads.sigs is not written (its row order in cuteSV depends on which worker process wrote which task).
+  * Force calling (-Ivcf) is not available, as in cuteSV v2.1.4 itself.
+  * --read_range is accepted and unused, as on cuteSV's calling path.  -t sizes the BAM reader's inflate threads.
+"""
+import argparse
+import os
+import sys
+import time
+
+from .columns import Params, TYPES
+
+VERSION = "2.1.4"                      # the cuteSV version whose command line and output this restates
+
+# (flags, options of add_argument) per group, in cuteSV's order; every default and type is cuteSV v2.1.4's
+_SWITCH = dict(action="store_true")
+_GENERAL = (
+    (("-t", "--threads"), dict(type=int, default=16, help="host threads (here: the BAM reader's inflate threads) [%(default)s]")),
+    (("-b", "--batches"), dict(type=int, default=10000000, help="reference bases per extraction task [%(default)s]")),
+    (("-S", "--sample"), dict(type=str, default="NULL", help="sample name of the VCF's last column [%(default)s]")),
+    (("--retain_work_dir",), dict(help="keep the files written into WORK_DIR", **_SWITCH)),
+    (("--write_old_sigs",), dict(help="write the rebuilt signatures as <TYPE>.sigs text files into WORK_DIR", **_SWITCH)),
+    (("--report_readid",), dict(help="report the names of the supporting reads (RNAMES)", **_SWITCH)),
+    (("--ignore_sequence",), dict(help="write <INS> / <DEL> instead of the bases", **_SWITCH)),
+)
+_COLLECT = (
+    (("-p", "--max_split_parts"), dict(type=int, default=7, help="a read split into more alignments is ignored; -1: none is [%(default)s]")),
+    (("-q", "--min_mapq"), dict(type=int, default=20, help="smallest mapping quality of an alignment that counts [%(default)s]")),
+    (("-r", "--min_read_len"), dict(type=int, default=500, help="shorter reads are ignored [%(default)s]")),
+    (("-md", "--merge_del_threshold"), dict(type=int, default=0, help="deletion signals at most this far apart are merged [%(default)s]")),
+    (("-mi", "--merge_ins_threshold"), dict(type=int, default=100, help="insertion signals at most this far apart are merged [%(default)s]")),
+    (("-include_bed",), dict(type=str, default=None, help="only call where the regions of this BED file are; the calls then depend on the task cut (see above)")),
+)
+_CLUSTER = (
+    (("-s", "--min_support"), dict(type=int, default=10, help="reads that must support a call [%(default)s]")),
+    (("-l", "--min_size"), dict(type=int, default=30, help="smallest SV reported [%(default)s]")),
+    (("-L", "--max_size"), dict(type=int, default=100000, help="largest SV reported; -1: no limit [%(default)s]")),
+    (("-sl", "--min_siglength"), dict(type=int, default=10, help="smallest signal extracted [%(default)s]")),
+)
+_GENOTYPE = (
+    (("--genotype",), dict(help="compute genotypes", **_SWITCH)),
+    (("--gt_round",), dict(type=int, default=500, help="rounds of the search for covering reads [%(default)s]")),
+    (("--read_range",), dict(type=int, default=1000, help="accepted, unused [%(default)s]")),
+)
+_FORCE = (
+    (("-Ivcf",), dict(type=str, default=None, help="force calling is not available (nor in cuteSV v2.1.4): use cuteFC")),
+)
+_ADVANCED = (
+    (("--max_cluster_bias_INS",), dict(type=int, default=100, help="[%(default)s]")),
+    (("--diff_ratio_merging_INS",), dict(type=float, default=0.3, help="[%(default)s]")),
+    (("--max_cluster_bias_DEL",), dict(type=int, default=200, help="[%(default)s]")),
+    (("--diff_ratio_merging_DEL",), dict(type=float, default=0.5, help="[%(default)s]")),
+    (("--max_cluster_bias_INV",), dict(type=int, default=500, help="[%(default)s]")),
+    (("--max_cluster_bias_DUP",), dict(type=int, default=500, help="[%(default)s]")),
+    (("--max_cluster_bias_TRA",), dict(type=int, default=50, help="[%(default)s]")),
+    (("--diff_ratio_filtering_TRA",), dict(type=float, default=0.6, help="[%(default)s]")),
+    (("--remain_reads_ratio",), dict(type=float, default=1.0, help="[%(default)s]")),
+)
+_GROUPS = ((None, _GENERAL), ("Collection of SV signatures", _COLLECT), ("Generation of SV clusters", _CLUSTER), ("Computing genotypes", _GENOTYPE),
+           ("Force calling", _FORCE), ("Advanced", _ADVANCED))
+
+
+def _parser():
+    ap = argparse.ArgumentParser(prog="cutesv_amd", description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--version", "-v", action="version", version="%(prog)s (cuteSV " + VERSION + ")")
+    ap.add_argument("input", metavar="[BAM]", type=str, help="coordinate-sorted BAM file")
+    ap.add_argument("reference", type=str, help="reference FASTA")
+    ap.add_argument("output", type=str, help="the VCF file to write")
+    ap.add_argument("work_dir", type=str, help="an existing directory; holds the .sigs files of --write_old_sigs")
+    for title, options in _GROUPS:
+        where = ap if title is None else ap.add_argument_group(title)
+        for flags, kw in options:
+            where.add_argument(*flags, **kw)
+    return ap
+
+
+def _own_parser():
+    """the two options cuteSV does not have; parsed apart (split_own), so that they shadow no abbreviation of a cuteSV flag"""
+    from . import call
+    ap = argparse.ArgumentParser(add_help=False, allow_abbrev=False)
+    ap.add_argument("--reads_table", default=None, choices=["host", "device"])
+    ap.add_argument("--tra_gt", default=None, choices=list(call.TRA_GT_MODES))
+    return ap
+
+
+def split_own(argv):
+    """-> (namespace of --reads_table / --tra_gt, argv without them)"""
+    return _own_parser().parse_known_args(list(argv))
+
+
+def parse_args(argv):
+    """argv (cuteSV's options only) -> the namespace cuteSV's own parser gives: same names, types and defaults"""
+    return _parser().parse_args(list(argv))
+
+
+def call_params(a):
+    """the namespace of parse_args -> call.CallParams: the flags are the values, no preset"""
+    from .call import CallParams
+    p = Params(min_support=a.min_support, min_size=a.min_size, max_size=a.max_size, genotype=a.genotype, gt_round=a.gt_round,
+               max_cluster_bias_INS=a.max_cluster_bias_INS, diff_ratio_merging_INS=a.diff_ratio_merging_INS,
+               max_cluster_bias_DEL=a.max_cluster_bias_DEL, diff_ratio_merging_DEL=a.diff_ratio_merging_DEL,
+               max_cluster_bias_INV=a.max_cluster_bias_INV, max_cluster_bias_DUP=a.max_cluster_bias_DUP,
+               max_cluster_bias_TRA=a.max_cluster_bias_TRA, diff_ratio_filtering_TRA=a.diff_ratio_filtering_TRA, remain_reads_ratio=a.remain_reads_ratio)
+    return CallParams(p, min_mapq=a.min_mapq, max_split_parts=a.max_split_parts, min_read_len=a.min_read_len, min_siglength=a.min_siglength,
+                      merge_del_threshold=a.merge_del_threshold, merge_ins_threshold=a.merge_ins_threshold)
+
+
+def _log(msg):
+    print("cutesv_amd: " + msg, file=sys.stderr)
+
+
+def main(argv=None):
+    argv = list(sys.argv[1:] if argv is None else argv)
+    own, rest = split_own(argv)
+    a = parse_args(rest)
+    if a.Ivcf is not None:
+        raise ValueError("force calling is not available here (it is disabled in cuteSV %s as well): use cuteFC to regenotype a given SV set" % VERSION)
+    if not os.path.isfile(a.reference):
+        raise FileNotFoundError("[Errno 2] No such file: '%s'" % a.reference)
+    if not os.path.isdir(a.work_dir):
+        raise FileNotFoundError("[Errno 2] No such directory: '%s'" % a.work_dir)
+    for t in TYPES:
+        path = os.path.join(a.work_dir, t + ".sigs")
+        if os.path.exists(path):
+            raise FileExistsError("[Errno 17] File exists: '%s'" % path)
+    from . import bam as bam_mod, call, fasta, vcf
+    tra_gt = own.tra_gt
+    if tra_gt is None and a.genotype and "CUTESV_AMD_TRA_GT" not in os.environ:
+        tra_gt = "alignments"
+    sigs_dir = a.work_dir if a.write_old_sigs else None
+    t0 = time.perf_counter()
+    timings = {}
+    bf = bam_mod.BamFile(a.input, threads=a.threads)
+    try:
+        contigs = list(zip(bf.references, bf.lengths))
+        _log("%d contigs in %s" % (len(contigs), a.input))
+        body, svid = call.call_bam(bf, fasta.Reference(a.reference), call_params(a), batch=a.batches, report_readid=a.report_readid,
+                                   ignore_sequence=a.ignore_sequence, as_bytes=True, timings=timings, tra_gt=tra_gt, include_bed=a.include_bed,
+                                   reads_table=own.reads_table, sigs_dir=sigs_dir)
+    finally:
+        bf.close()
+    for key, ms in timings.items():
+        _log("%-16s %10.1f ms" % (key[3:] if key.startswith("ms_") else key, ms))
+    with open(a.output, "wb") as f:
+        f.write(vcf.header_text(contigs, a.sample, argv).encode() + body)
+    if sigs_dir is not None and not a.retain_work_dir:
+        for t in TYPES:
+            path = os.path.join(sigs_dir, t + ".sigs")
+            if os.path.exists(path):
+                os.remove(path)
+    _log("%d records (INS %d, DEL %d, BND %d, DUP %d, INV %d) in %.2f s" % (body.count(b"\n"), *svid.tolist(), time.perf_counter() - t0))
+    return 0

@@ -311,6 +311,7 @@ int csv_cache_flush(csv_ctx* c, int64_t bytes)
 #include "stage_seqs.hip.h"
 #include "stage_rebuild.hip.h"
 #include "stage_vcf_strings.hip.h"
+#include "stage_sigs_text.hip.h"
 #include "stage_extract.hip.h"
 #include "stage_bam.hip.h"
 #include "stage_aln.hip.h"

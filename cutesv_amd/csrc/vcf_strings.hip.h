@@ -15,6 +15,7 @@
 //   k_join_copy     one wavefront per support: a name is at most 255 bytes, four steps of 64 lanes (k_name_gather), then the comma
 // Every kernel walks its entries with a grid-stride loop (the host caps the grid).  Every byte read lies inside the row's
 // [seq_off, seq_off + aux) resp. inside the name's [off[i], off[i + 1]); picks and supports were range-checked on the host.
+// The same columns and pools also give the lines of cuteSV's <TYPE>.sigs files (k_sigs_plan / k_sigs_write, at the end of this file).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -112,6 +113,152 @@ __global__ __launch_bounds__(256) void k_join_copy(VsRows R, VsNames N, const in
             if (x < len) out[o + x] = N.blob[b + x];
         }
         if (lane == 0 && !(adj[j] & 1)) out[o + len] = (uint8_t)',';
+    }
+}
+
+
+// ------------------------------------------------------------------------------------ the text signature files
+// The legacy text signature files of cuteSV's --write_old_sigs (main script :763-808), made where the rebuilt
+// signatures are: rows [row_begin, row_begin + n) of a kept pool rebuild become one text line each
+//   DEL / DUP   TYPE \t chr \t a \t b \t read \n                       INS   TYPE \t chr \t a \t b \t read \t bases \n
+//   INV         TYPE \t chr \t strand \t a \t b \t read \n             TRA   TYPE \t chr \t A|B|C|D \t a \t chr2 \t b \t read \n
+// with segment s = type TYPES[s / n_chrom] on chromosome s % n_chrom (rebuild._segments), read = name(first[read_id]), bases = the
+// sequence-pool entry of the row's pool row (aux bytes), strand = strands[aux], TRA: type = aux & 7, chr2 = chromosome aux >> 3.
+//
+//   k_sigs_plan     one thread per row: the line's length into cnt[k].x, and a status bit for what the entry refuses
+//   scan            the lengths go through the scan of scan.hip.h (k_scan_tiles / k_scan_offsets)
+//   k_sigs_write    one wavefront per row: lanes write the fixed pieces, one lane per decimal digit, the name in four steps of 64
+//                   lanes (k_join_copy), the chromosome names in steps of 64, the bases with vs_copy's aligned words
+// Both kernels walk their rows with a grid-stride loop (the host caps the grid).  Every byte read lies inside the row's own name
+// [off[i], off[i + 1]), its own sequence [seq_off, seq_off + aux) or a chromosome name of the caller's table; the write kernel is
+// launched only when the plan found nothing wrong, so it repeats none of the plan's checks.
+
+enum { ST_ERR_COORD = 1, ST_ERR_RANK = 2, ST_ERR_NO_SEQ = 4, ST_ERR_TRA = 8, ST_ERR_STRAND = 16, ST_ERR_SEG = 32 };
+enum { ST_DEL = 0, ST_INS = 1, ST_INV = 2, ST_DUP = 3, ST_TRA = 4 };          // columns.TYPES
+constexpr i64 ST_COORD_END = 1ll << 42;                                        // coordinates live in [0, 2^42)
+constexpr int ST_STRAND_MAX = 15;
+
+struct StRows { const int* seg; const i64* a; const i64* b; const int* rid; const int* aux; const int* src; };
+struct StTables {
+    const uint8_t* chrom; const int* chrom_off; int n_chrom;                   // chromosome names in name-rank order: blob + n_chrom + 1 offsets
+    const uint8_t* seq_blob; const i64* seq_off;                               // the sequence pool by pool row (seq_off NULL: the context holds none)
+    uint8_t strand[2][ST_STRAND_MAX + 1]; int strand_len[2];
+};
+
+__device__ __forceinline__ u64 st_pow10(int k)
+{
+    static const u64 P[14] = {1ull, 10ull, 100ull, 1000ull, 10000ull, 100000ull, 1000000ull, 10000000ull, 100000000ull, 1000000000ull, 10000000000ull,
+                              100000000000ull, 1000000000000ull, 10000000000000ull};
+    return P[k];
+}
+// decimal digits of v in [0, 2^42): 1 .. 13
+__device__ __forceinline__ int st_digits(i64 v)
+{
+    int d = 1;
+    while (d < 13 && (u64)v >= st_pow10(d)) d++;
+    return d;
+}
+
+__global__ __launch_bounds__(256) void k_sigs_plan(StRows R, VsNames N, StTables T, i64 row0, i64 n, int4* cnt, int* err)
+{
+    for (i64 k = (i64)blockIdx.x * 256 + threadIdx.x; k < n; k += (i64)gridDim.x * 256) {
+        const i64 r = row0 + k;
+        const int seg = R.seg[r], aux = R.aux[r], rk = R.rid[r];
+        const i64 a = R.a[r], b = R.b[r];
+        int bad = 0, len = 0;
+        if (seg < 0 || seg >= 5 * T.n_chrom) bad |= ST_ERR_SEG;
+        if (a < 0 || a >= ST_COORD_END || b < 0 || b >= ST_COORD_END) bad |= ST_ERR_COORD;
+        if (rk < 0 || rk >= N.n_distinct) bad |= ST_ERR_RANK;
+        if (!bad) {
+            const int type = seg / T.n_chrom, ch = seg - type * T.n_chrom;
+            const int i = N.first[rk];
+            // "TYP\t" chr "\t" a "\t" b "\t" read "\n"
+            len = 4 + (T.chrom_off[ch + 1] - T.chrom_off[ch]) + 1 + st_digits(a) + 1 + st_digits(b) + 1 + (int)(N.off[i + 1] - N.off[i]) + 1;
+            if (type == ST_INS) {
+                if (!T.seq_off || aux < 0 || T.seq_off[R.src[r]] < 0) bad |= ST_ERR_NO_SEQ;
+                else len += 1 + aux;
+            } else if (type == ST_INV) {
+                if (aux < 0 || aux > 1) bad |= ST_ERR_STRAND;
+                else len += T.strand_len[aux] + 1;
+            } else if (type == ST_TRA) {
+                const int c2 = aux >> 3;
+                if (aux < 0 || (aux & 7) > 3 || c2 >= T.n_chrom) bad |= ST_ERR_TRA;
+                else len += 2 + (T.chrom_off[c2 + 1] - T.chrom_off[c2]) + 1;
+            }
+        }
+        if (bad) atomicOr(err, bad);
+        cnt[k] = make_int4(bad ? 0 : len, 0, 0, 0);
+    }
+}
+
+// the pieces of a line, each written by the whole wavefront at o; every one returns the position behind it
+__device__ __forceinline__ i64 st_put_byte(uint8_t* out, i64 o, int lane, uint8_t ch)
+{
+    if (lane == 0) out[o] = ch;
+    return o + 1;
+}
+__device__ __forceinline__ i64 st_put_bytes(uint8_t* out, i64 o, int lane, const uint8_t* src, int len)
+{
+    for (int x = lane; x < len; x += 64) out[o + x] = src[x];
+    return o + len;
+}
+// v in [0, 2^42) in decimal, one lane per digit (the quotient by a power of ten in 32 bits where the value has them)
+__device__ __forceinline__ i64 st_put_number(uint8_t* out, i64 o, int lane, i64 v)
+{
+    const int nd = st_digits(v);
+    if (lane < nd) {
+        const u64 p = st_pow10(nd - 1 - lane);
+        const unsigned q = (u64)v < (1ull << 32) ? (unsigned)v / (unsigned)p : (unsigned)(((u64)v / p) % 10ull);
+        out[o + lane] = (uint8_t)('0' + q % 10u);
+    }
+    return o + nd;
+}
+
+// one wavefront per row (only launched when the plan found nothing wrong); cnt holds the exclusive offsets
+__global__ __launch_bounds__(256) void k_sigs_write(StRows R, VsNames N, StTables T, i64 row0, i64 n, const int4* cnt, uint8_t* out)
+{
+    const int lane = threadIdx.x & 63;
+    for (i64 k = (i64)blockIdx.x * 4 + (threadIdx.x >> 6); k < n; k += (i64)gridDim.x * 4) {
+        const i64 r = row0 + k;
+        const int seg = R.seg[r], aux = R.aux[r];
+        const int type = seg / T.n_chrom, ch = seg - type * T.n_chrom;
+        i64 o = (i64)cnt[k].x;
+        // "DEL\t" .. "TRA\t" as little-endian words
+        const unsigned tag = type == ST_DEL ? 0x094c4544u : type == ST_INS ? 0x09534e49u : type == ST_INV ? 0x09564e49u : type == ST_DUP ? 0x09505544u : 0x09415254u;
+        if (lane < 4) out[o + lane] = (uint8_t)(tag >> (8 * lane));
+        o += 4;
+        o = st_put_bytes(out, o, lane, T.chrom + T.chrom_off[ch], T.chrom_off[ch + 1] - T.chrom_off[ch]);
+        o = st_put_byte(out, o, lane, '\t');
+        if (type == ST_INV) {
+            o = st_put_bytes(out, o, lane, T.strand[aux], T.strand_len[aux]);
+            o = st_put_byte(out, o, lane, '\t');
+        } else if (type == ST_TRA) {
+            if (lane == 0) { out[o] = (uint8_t)('A' + (aux & 7)); out[o + 1] = '\t'; }
+            o += 2;
+        }
+        o = st_put_number(out, o, lane, R.a[r]);
+        o = st_put_byte(out, o, lane, '\t');
+        if (type == ST_TRA) {
+            const int c2 = aux >> 3;
+            o = st_put_bytes(out, o, lane, T.chrom + T.chrom_off[c2], T.chrom_off[c2 + 1] - T.chrom_off[c2]);
+            o = st_put_byte(out, o, lane, '\t');
+        }
+        o = st_put_number(out, o, lane, R.b[r]);
+        o = st_put_byte(out, o, lane, '\t');
+        const int i = N.first[R.rid[r]];
+        const i64 nb = N.off[i];
+        const int nlen = (int)(N.off[i + 1] - nb);
+        for (int s = 0; s < (NAME_MAX_LEN + 63) / 64; s++) {
+            const int x = s * 64 + lane;
+            if (x < nlen) out[o + x] = N.blob[nb + x];
+        }
+        o += nlen;
+        if (type == ST_INS) {
+            o = st_put_byte(out, o, lane, '\t');
+            if (aux > 0) vs_copy(T.seq_blob + T.seq_off[R.src[r]], aux, out + o, lane);
+            o += aux;
+        }
+        st_put_byte(out, o, lane, '\n');
     }
 }
 

@@ -502,6 +502,119 @@ def support_join_host(names, first, read_id, support_off, support_sig):
     return b"".join(parts), off
 
 
+# ------------------------------------------------------------------------------------ the text signature files of a kept pool rebuild
+_COORD_END = 1 << 42                                    # positions and lengths live in [0, 2^42)
+
+
+def _chrom_table(chroms):
+    """chromosome names in name-rank order (the numbering of _segments) as the blob + offsets csv_pool_sigs_text takes"""
+    enc = [c.encode() if isinstance(c, str) else bytes(c) for c in sorted(chroms)]
+    off = np.zeros(len(enc) + 1, np.int64)
+    if enc:
+        np.cumsum([len(x) for x in enc], out=off[1:])
+    return b"".join(enc), off
+
+
+def sigs_text(ctx, chroms, row_begin, row_end, strands=("++", "--"), raw=False, timing=None):
+    """csv_pool_sigs_text: rows [row_begin, row_end) of the context's last kept rebuild_pool_by_name as the lines of cuteSV's
+    <TYPE>.sigs files (main script :763-808), made on the device -> bytes (raw=True: a uint8 array).  chroms: the chromosome
+    names the segments were numbered over (rebuild._segments: rank = position in sorted(chroms)).  timing: a dict whose
+    "ms_kernels" grows by the kernels' HIP-event time.  CsvError E_INVALID: no kept rebuild by name or the pools changed since,
+    a row range outside the rebuilt rows, and every row sigs_text_host raises ValueError for."""
+    if len(strands) != 2:
+        raise ValueError("two strand strings are expected")
+    blob, off = _chrom_table(chroms)
+    s0, s1 = [s.encode() if isinstance(s, str) else bytes(s) for s in strands]
+    row_begin, row_end = int(row_begin), int(row_end)
+    need, ms = C.c_int64(0), C.c_float(0)
+    out = np.empty(max(1, 96 * max(0, row_end - row_begin)), np.uint8)
+
+    def call():
+        return lib().csv_pool_sigs_text(ctx._h, row_begin, row_end, blob, off.ctypes.data, len(off) - 1, s0, s1, out.ctypes.data, len(out), C.byref(need), C.byref(ms))
+    rc = call()
+    if rc == _abi.E_CAPACITY:                             # (the lengths live on the device: the first call reports the need)
+        out = np.empty(int(need.value), np.uint8)
+        rc = call()
+    ctx._check(rc)
+    if timing is not None:
+        timing["ms_kernels"] = timing.get("ms_kernels", 0.0) + float(ms.value)
+    return out[:int(need.value)] if raw else out[:int(need.value)].tobytes()
+
+
+def sigs_text_host(cols, names, first, seqs_by_pool_row, chroms, row_begin, row_end, strands=("++", "--")):
+    """What csv_pool_sigs_text computes, in Python: cols = the rebuild's sorted columns (seg_id, a, b, read_id, aux, src_row),
+    names[i] = name i of the name pool (str or bytes), first = name_ranks()["first"], seqs_by_pool_row[r] = the bases of pool row r
+    (None or missing: no sequence) -> bytes.  The checker of the kernels and the statement of the contract: ValueError for what
+    the entry refuses."""
+    from .columns import BND_NAME
+    ch = [c.encode() if isinstance(c, str) else bytes(c) for c in sorted(chroms)]
+    st = [s.encode() if isinstance(s, str) else bytes(s) for s in strands]
+    n_chrom = len(ch)
+    row_begin, row_end = int(row_begin), int(row_end)
+    n = len(cols["a"])
+    if not 0 <= row_begin <= row_end <= n:
+        raise ValueError("rows [%d, %d) lie outside the %d rebuilt rows" % (row_begin, row_end, n))
+    sl = slice(row_begin, row_end)
+    seg, a, b, rid, aux, src = (np.asarray(cols[k], np.int64)[sl].tolist() for k in ("seg_id", "a", "b", "read_id", "aux", "src_row"))
+    first = np.asarray(first, np.int64)
+    get = seqs_by_pool_row.get if hasattr(seqs_by_pool_row, "get") else (lambda r: seqs_by_pool_row[r] if 0 <= r < len(seqs_by_pool_row) else None)
+    as_bytes = lambda s: s.encode() if isinstance(s, str) else bytes(s)
+    lines = []
+    for k in range(row_end - row_begin):
+        if not 0 <= seg[k] < len(TYPES) * n_chrom:
+            raise ValueError("row %d: segment %d lies outside 5 * n_chrom" % (row_begin + k, seg[k]))
+        if not (0 <= a[k] < _COORD_END and 0 <= b[k] < _COORD_END):
+            raise ValueError("row %d: a position or length is negative or at least 2^42" % (row_begin + k))
+        if not 0 <= rid[k] < len(first):
+            raise ValueError("row %d: read id %d is no rank of the name pool" % (row_begin + k, rid[k]))
+        t, c = TYPES[seg[k] // n_chrom], ch[seg[k] % n_chrom]
+        name = as_bytes(names[int(first[rid[k]])])
+        head = [t.encode(), c]
+        tail = []
+        if t == "INS":
+            s = get(src[k])
+            if s is None or aux[k] < 0:
+                raise ValueError("row %d: the INS row has no sequence" % (row_begin + k))
+            tail = [as_bytes(s)[:aux[k]]]
+        elif t == "INV":
+            if not 0 <= aux[k] <= 1:
+                raise ValueError("row %d: strand code %d is above 1" % (row_begin + k, aux[k]))
+            head.append(st[aux[k]])
+        elif t == "TRA":
+            if aux[k] < 0 or (aux[k] & 7) > 3 or (aux[k] >> 3) >= n_chrom:
+                raise ValueError("row %d: TRA type code above 3 or a mate chromosome outside the table" % (row_begin + k))
+            lines.append(b"\t".join(head + [BND_NAME[aux[k] & 7].encode(), b"%d" % a[k], ch[aux[k] >> 3], b"%d" % b[k], name]) + b"\n")
+            continue
+        lines.append(b"\t".join(head + [b"%d" % a[k], b"%d" % b[k], name] + tail) + b"\n")
+    return b"".join(lines)
+
+
+def type_row_ranges(seg_count, n_chrom):
+    """{TYPE: (first row, end row)} of a rebuild over rebuild._segments' numbering, from its seg_count"""
+    off = np.r_[0, np.cumsum(np.asarray(seg_count, np.int64))]
+    return {t: (int(off[ti * n_chrom]), int(off[(ti + 1) * n_chrom])) for ti, t in enumerate(TYPES)}
+
+
+def write_sigs(ctx, rb, chroms, out_dir, rows_per_chunk=1 << 20, strands=("++", "--"), timing=None):
+    """The five files cuteSV leaves under --write_old_sigs (DEL.sigs, INS.sigs, DUP.sigs, INV.sigs, TRA.sigs in `out_dir`) from the
+    kept rebuild `rb` (the dict rebuild_pool_by_name returned), each the rows of its type in the rebuild's order, made by
+    sigs_text in chunks of rows_per_chunk rows - no buffer scales with the genome.  A type without rows gives an empty file, as
+    the reference's open(..., "w") does.  -> {TYPE: bytes written}"""
+    import os
+    if rows_per_chunk < 1:
+        raise ValueError("rows_per_chunk must be positive")
+    written = {}
+    for t, (r0, r1) in type_row_ranges(rb["seg_count"], len(chroms)).items():
+        total = 0
+        with open(os.path.join(out_dir, t + ".sigs"), "wb") as f:
+            for c0 in range(r0, r1, rows_per_chunk):
+                part = sigs_text(ctx, chroms, c0, min(r1, c0 + rows_per_chunk), strands, raw=True, timing=timing)
+                f.write(memoryview(part))
+                total += len(part)
+        written[t] = total
+    return written
+
+
 def finish_ins_ties(r, ins_segs, seq_of_src, half_of_src):
     """The INS tie groups of a sorted (not de-duplicated) row set `r` (dict of arrays from rebuild_columns): rows that agree
     in (segment, a, b, read_id).  Each group is ordered by sequence (stable: equal sequences keep the concatenation order

@@ -155,6 +155,56 @@ def emit_records(store, segments, res, reference, min_size=30, max_size=100000, 
     raise RuntimeError("csv_vcf_emit: capacity retry failed")
 
 
+# ------------------------------------------------------------------------------------ the header
+SOURCE = "cutesv_amd (cuteSV-2.1.4)"
+FILE_DATE_FORMAT = "%Y-%m-%d %H:%M:%S %w-%Z"              # the reference's fileDate (cuteSV_Description.py:270)
+COLUMNS = ("#CHROM", "POS", "ID", "REF", "ALT", "QUAL", "FILTER", "INFO", "FORMAT")
+
+# (kind, ID, Number, Type, Description) in the order cuteSV v2.1.4 declares them; Number / Type None: the kind has none
+HEADER_FIELDS = (
+    ("ALT", "INS", None, None, "Insertion of novel sequence relative to the reference"),
+    ("ALT", "DEL", None, None, "Deletion relative to the reference"),
+    ("ALT", "DUP", None, None, "Region of elevated copy number relative to the reference"),
+    ("ALT", "INV", None, None, "Inversion of reference sequence"),
+    ("ALT", "BND", None, None, "Breakend of translocation"),
+    ("INFO", "PRECISE", "0", "Flag", "Precise structural variant"),
+    ("INFO", "IMPRECISE", "0", "Flag", "Imprecise structural variant"),
+    ("INFO", "SVTYPE", "1", "String", "Type of structural variant"),
+    ("INFO", "SVLEN", "1", "Integer", "Difference in length between REF and ALT alleles"),
+    ("INFO", "CHR2", "1", "String", "Chromosome for END coordinate in case of a translocation"),
+    ("INFO", "END", "1", "Integer", "End position of the variant described in this record"),
+    ("INFO", "CIPOS", "2", "Integer", "Confidence interval around POS for imprecise variants"),
+    ("INFO", "CILEN", "2", "Integer", "Confidence interval around inserted/deleted material between breakends"),
+    ("INFO", "RE", "1", "Integer", "Number of read support this record"),
+    ("INFO", "STRAND", "A", "String", "Strand orientation of the adjacency in BEDPE format (DEL:+-, DUP:-+, INV:++/--)"),
+    ("INFO", "RNAMES", ".", "String", "Supporting read names of SVs (comma separated)"),
+    ("INFO", "AF", "A", "Float", "Allele Frequency."),
+    ("FILTER", "q5", None, None, "Quality below 5"),
+    ("FORMAT", "GT", "1", "String", "Genotype"),
+    ("FORMAT", "DR", "1", "Integer", "# High-quality reference reads"),
+    ("FORMAT", "DV", "1", "Integer", "# High-quality variant reads"),
+    ("FORMAT", "PL", "G", "Integer", "# Phred-scaled genotype likelihoods rounded to the closest integer"),
+    ("FORMAT", "GQ", "1", "Integer", "# Genotype quality"),
+)
+
+
+def header_text(contigs, sample, argv, now=None):
+    """The VCF header cuteSV v2.1.4 writes in front of the records (cuteSV_Description.py:265-305 and the column line of main
+    script :1217) -> str.  contigs: [(name, length)] in the BAM header's order; sample: the last column's name; argv: the command
+    line's arguments; now: a time.struct_time (default: the local time).  Line for line the reference's, except ##source (this
+    project, and the version it restates), ##fileDate (the reference's format, this run's time) and ##CommandLine (this program's
+    name)."""
+    import time
+    lines = ["##fileformat=VCFv4.2", "##source=" + SOURCE, "##fileDate=" + time.strftime(FILE_DATE_FORMAT, time.localtime() if now is None else now)]
+    lines += ["##contig=<ID=%s,length=%d>" % (name, length) for name, length in contigs]
+    for kind, ident, number, typ, desc in HEADER_FIELDS:
+        typed = "" if number is None else "Number=%s,Type=%s," % (number, typ)
+        lines.append('##%s=<ID=%s,%sDescription="%s">' % (kind, ident, typed, desc))
+    lines.append('##CommandLine="cutesv_amd %s"' % " ".join(argv))
+    lines.append("\t".join(COLUMNS + (sample,)))
+    return "\n".join(lines) + "\n"
+
+
 def emit_stage(results, reference, **kw):
     """VCF body text of a `resolve.cluster_stage(..., lazy=True)` result ({chr: rows.LazyRows}): the native emitter reads the
     structure of arrays the lazy rows are backed by - no row strings are created on the way (GT:242-467, main script

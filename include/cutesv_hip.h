@@ -574,6 +574,25 @@ int csv_seq_alt_gather(csv_ctx* ctx, int64_t n, const void* pick, const void* cl
 int csv_name_support_join(csv_ctx* ctx, int64_t n_calls, const int64_t* support_off /* n_calls + 1 */, const int64_t* support_sig, const int32_t* support_sig32, char* out,
                           int64_t cap, int64_t* out_off /* n_calls + 1 */);
 
+/* The text signature files of cuteSV's --write_old_sigs (main script :763-808) from the same kept rebuild (vcf_strings.hip.h,
+ * DESIGN.md section 24): rows [row_begin, row_end) of its sorted columns - dev_seg_id, dev_a, dev_b, dev_read_id, dev_aux,
+ * dev_src_row - become one line each, back to back in `out`.  Segment s has type {DEL, INS, INV, DUP, TRA}[s / n_chrom] and
+ * chromosome s % n_chrom of the caller's table: chromosome k's name = chrom_names[chrom_off[k] .. chrom_off[k + 1]), in name-rank
+ * order (the numbering of a TRA row's mate too).
+ *   DEL / DUP   TYPE \t chr \t a \t b \t read \n
+ *   INS         TYPE \t chr \t a \t b \t read \t bases \n              bases = the sequence-pool entry of pool row dev_src_row (aux bytes)
+ *   INV         TYPE \t chr \t strand \t a \t b \t read \n            strand = strand0 / strand1 for aux 0 / 1 (at most 15 bytes each)
+ *   TRA         TYPE \t chr \t A|B|C|D \t a \t chr2 \t b \t read \n    type = aux & 7, chr2 = chromosome aux >> 3
+ * read = the name first[dev_read_id] of the name pool (the rebuild must have been made with CSV_RB_RANK_FROM_NAMES); a and b in
+ * decimal.  *need receives the bytes of the lines whenever the rows are in order; CSV_E_CAPACITY: cap is smaller, nothing is
+ * stored.  CSV_E_INVALID, with nothing stored: no kept rebuild or the pools changed since (as above), a row range outside
+ * [0, n_out], a malformed table, and any row with a or b outside [0, 2^42), a read id outside the name pool's ranks, an INS row
+ * without a sequence, a TRA type above 3 or a mate outside the table, an INV strand code above 1, a segment outside
+ * 5 * n_chrom; also more than 2^31 - 4096 bytes in one call (ask for fewer rows).  ms_kernels (may be NULL): the kernels' time
+ * from HIP events. */
+int csv_pool_sigs_text(csv_ctx* ctx, int64_t row_begin, int64_t row_end, const char* chrom_names, const int64_t* chrom_off /* n_chrom + 1 */, int32_t n_chrom,
+                       const char* strand0, const char* strand1, char* out, int64_t cap, int64_t* need, float* ms_kernels);
+
 /* The alignment table and the TRA genotyping over it (aln.hip.h).  The reference genotypes a TRA call from
  * the BAM itself (call_gt, cuteSV_resolveTRA.py:258-309; count_coverage, cuteSV_genotype.py:72-93): every alignment fetch()
  * yields counts - secondary, supplementary, low-MAPQ and placed-unmapped records too - and a record is primary when its flag is

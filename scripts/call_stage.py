@@ -35,6 +35,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--bam", default=None, help="reuse / write the input here (default: a temporary file)")
     ap.add_argument("--gates", default=None, choices=["host", "device"], help="where call_bam evaluates the task gates (default: call_bam's own choice)")
+    ap.add_argument("--sigs", action="store_true", help="also write the <TYPE>.sigs files (call_bam(sigs_dir=...), DESIGN.md section 24) and report ms_sigs")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     import bam_writer
@@ -50,13 +51,16 @@ def main():
     cp = call.CallParams(Params.ont(min_support=1))
     keys = ("ms_call_bam_wall", "ms_tasks", "ms_rebuild", "ms_cluster", "ms_alt_gather", "ms_support_join", "ms_emit", "ms_parent_wall", "ms_parent_tasks",
             "ms_parent_rebuild", "ms_parent_cluster", "ms_parent_emit")
+    sigs_dir = __import__("tempfile").mkdtemp() if a.sigs else None
+    if a.sigs:
+        keys += ("ms_sigs",)
     runs = {k: [] for k in keys}
     info = {}
     with engine.Context(0) as ctx, bam.BamFile(path) as bf:
         for it in range(a.warmup + a.reps):
             t, tp = {}, {}
             t0 = time.perf_counter()
-            text, svid = call.call_bam(bf, reference, cp, ctx=ctx, batch=CONTIG_LEN, report_readid=True, timings=t, gates=a.gates)
+            text, svid = call.call_bam(bf, reference, cp, ctx=ctx, batch=CONTIG_LEN, report_readid=True, timings=t, gates=a.gates, sigs_dir=sigs_dir)
             t["ms_call_bam_wall"] = (time.perf_counter() - t0) * 1e3
             t0 = time.perf_counter()
             want = call_helpers.parent_route(ctx, bf, reference, cp, batch=CONTIG_LEN, report_readid=True, timings=tp)
@@ -70,6 +74,9 @@ def main():
     out = dict(input=dict(reads=a.reads, seed=a.seed, reps=a.reps, warmup=a.warmup, min_support=1, report_readid=True, gates=a.gates or call.DEFAULT_GATES), **info, **{k: spread(v) for k, v in runs.items()})
     out["call_bam_over_parent"] = out["ms_call_bam_wall"]["median"] / out["ms_parent_wall"]["median"]
     out["gathers_share_of_call_bam"] = (out["ms_alt_gather"]["median"] + out["ms_support_join"]["median"]) / out["ms_call_bam_wall"]["median"]
+    if a.sigs:
+        out["sigs_share_of_call_bam"] = out["ms_sigs"]["median"] / out["ms_call_bam_wall"]["median"]
+        out["sigs_bytes"] = sum(os.path.getsize(os.path.join(sigs_dir, f)) for f in os.listdir(sigs_dir))
     print(json.dumps(out, indent=1))
     if a.out:
         with open(a.out, "w") as f:
