@@ -1,5 +1,6 @@
 """cigar_sigs.json.gz: the reference's parse_read (main script :606-681) driven with stub read objects (see
-make_golden_main.py, which imports the main script and calls cigar_golden)."""
+make_golden_main.py, which imports the main script and calls cigar_golden).
+cigar_edges.json.gz: the same function on the crafted families and dense random reads of tests/cigar_helpers.py (cigar_edges)."""
 import gzip
 import json
 import os
@@ -78,3 +79,52 @@ def cigar_golden(main):
     with gzip.open(os.path.join(HERE, "cigar_sigs.json.gz"), "wt") as f:
         json.dump(cases, f)
     print("cigar_sigs.json.gz: %d cases, %d INS + %d DEL signatures" % (len(cases), sum(len(c["INS"]) for c in cases), sum(len(c["DEL"]) for c in cases)))
+
+
+# ------------------------------------------------------------------------------------------------ cigar_edges.json.gz
+def _run(main, reads, params, min_mapq, min_read_len):
+    """parse_read on every read -> per read {"INS": rows, "DEL": rows}"""
+    out = []
+    for r in reads:
+        cand = {t: [] for t in ("DEL", "INS", "DUP", "INV", "TRA")}
+        rd = _Read(r["name"], r["flag"], r["mapq"], r["start"], [tuple(x) for x in r["cigar"]], synth.pseudo_sequence(r["seq_len"], r["seq_key"]))
+        main.parse_read(rd, cand, "chr7", 30, min_mapq, 7, min_read_len, params["min_siglength"], params["md"], params["mi"], 100000)
+        assert not cand["DUP"] and not cand["INV"] and not cand["TRA"]
+        out.append(dict(INS=[list(x) for x in cand["INS"]], DEL=[list(x) for x in cand["DEL"]]))
+    return out
+
+
+def cigar_edges(main):
+    """crafted families (tests/cigar_helpers.py) and dense random reads through the reference's parse_read -> cigar_edges.json.gz"""
+    import hashlib
+    sys.path.insert(0, os.path.dirname(HERE))
+    import cigar_helpers as ch
+    cases = []
+    for k, (set_name, params) in enumerate(ch.PARAM_SETS.items()):
+        for name, reads, gates, expect in (("edges_" + set_name, ch.families(set_name, params, 7000000 + 10000 * k), dict(min_mapq=20, min_read_len=0), ch.expectations(params)),
+                                           ("host_" + set_name, ch.host_family(set_name, params, 7500000 + 10000 * k), dict(ch.HOST_PARAMS), ch.HOST_EXPECTATIONS)):
+            per_read = _run(main, reads, params, gates["min_mapq"], gates["min_read_len"])
+            # self-check, on the reference alone and free of names and bases: every family is there and does what it is there to show
+            ch.check_families(reads, [(o["INS"], o["DEL"]) for o in per_read], expect)
+            # (this tests the table; it speaks for the reads because check_families has just required their families to be the table's keys)
+            assert {ch.kind_of(f) for f in expect} == set(ch.FAMILY_KINDS if name.startswith("edges_") else ("host",)), "a family kind is missing for %s" % set_name
+            cases.append(dict(name=name, params=dict(params, **gates), reads=reads, INS=[x for o in per_read for x in o["INS"]],
+                              DEL=[x for o in per_read for x in o["DEL"]]))
+    crafted_ins = [x for c in cases for x in c["INS"]]
+    assert any(x[3] == "" for x in crafted_ins) and any(0 < len(x[3]) < x[1] for x in crafted_ins), "no INS slice is cut by the query's end"
+    for k, params in enumerate(ch.DENSE_SETS):
+        seed, n = 8100 + k, 3000
+        reads = ch.dense_reads(seed, n)
+        cnt = ch.counters(reads, params)
+        assert all(v >= 100 for v in cnt.values()), "dense_%d: a decision occurs fewer than 100 times: %s" % (k, cnt)
+        per_read = _run(main, reads, params, 20, 0)
+        ins, dele = [x for o in per_read for x in o["INS"]], [x for o in per_read for x in o["DEL"]]
+        dump = lambda rows: hashlib.sha256(json.dumps(rows, separators=(",", ":")).encode()).hexdigest()      # noqa: E731
+        cases.append(dict(name="dense_%d" % k, params=dict(params, min_mapq=20, min_read_len=0), dense=dict(seed=seed, n=n, checksum=ch.reads_checksum(reads)),
+                          n_ins=len(ins), n_del=len(dele), sha_ins=dump(ins), sha_del=dump(dele), per_read=ch.per_read_digests(reads, ins, dele), counters=cnt))
+        print("  dense_%d %s: %d INS + %d DEL rows; %s" % (k, params, len(ins), len(dele), cnt))
+    path = os.path.join(HERE, "cigar_edges.json.gz")
+    with gzip.GzipFile(path, "wb", mtime=0) as f:
+        f.write(json.dumps(cases).encode())
+    assert os.path.getsize(path) < 400 * 1024
+    print("cigar_edges.json.gz: %d cases, %d crafted reads, %d bytes" % (len(cases), sum(len(c.get("reads", ())) for c in cases), os.path.getsize(path)))

@@ -14,6 +14,8 @@ Outputs
                             lists the rebuild step writes, in its order
     cigar_sigs.json.gz      parse_read (main script :606-681) / generate_combine_sigs (:515-575) driven with stub read
                             objects carrying BAM-encoded CIGARs: the INS / DEL signatures each read yields (8f row 4)
+    cigar_edges.json.gz     the same functions on crafted reads, one family per rule of the scan with one quantity moved across the
+                            rule's threshold or a piece moved across a 64-operation step, and on dense small-coordinate random reads
     parse_reads.json.gz     parse_read (main script :606-681) called read after read on stub records with CIGARs and SA tags:
                             what a whole task's extraction appends to the five candidate lists (8f row 4)
     split_sigs.json.gz      organize_split_signal / analysis_split_read (main script :50-513) driven with synthetic primary
@@ -154,8 +156,9 @@ def main_():
     rebuild_golden(main)
     if "--cigar" in sys.argv or True:
         try:
-            from make_golden_cigar import cigar_golden
+            from make_golden_cigar import cigar_golden, cigar_edges
             cigar_golden(main)
+            cigar_edges(main)
             from make_golden_split import split_golden, split_edges
             split_golden(main)
             split_edges(main)
