@@ -91,6 +91,10 @@ SYMBOLS = [
     ("csv_bam_header", C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]),
     ("csv_bam_read", C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.POINTER(_abi.ChunkC)]),
     ("csv_bam_struct_size", C.c_int, [C.c_int]),
+    ("csv_bgzf_inflate", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32,
+                                   C.c_void_p, C.POINTER(C.c_double)]),
+    ("csv_bam_set_inflate", C.c_int, [C.c_void_p, C.c_void_p, C.c_int32]),
+    ("csv_bam_inflate_stats", C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_double)]),
     ("csv_bam_decode", C.c_int, [C.c_void_p, C.POINTER(_abi.BamIn), C.POINTER(_abi.BamOut)]),
     ("csv_bam_split_inputs", C.c_int, [C.c_void_p, C.POINTER(_abi.SaIn), C.POINTER(_abi.SaOut)]),
     ("csv_sa_struct_size", C.c_int, [C.c_int]),

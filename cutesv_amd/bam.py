@@ -1,17 +1,21 @@
 """Native BAM reader: a coordinate-sorted .bam -> the columns the extraction kernels take, without
 pysam and without a Python object per record.
 
-`BamFile` is the host side (cutesv_amd/csrc/bam_host.cpp: BGZF inflate on host threads with the interpreter lock released,
-header, record framing, region scan without an index).  It hands out `Chunk`s: the slim image that goes to the device (per
+`BamFile` is the host side (cutesv_amd/csrc/bam_host.cpp: BGZF inflate on host threads with the interpreter lock released - or,
+with inflate=<Context>, on the device, one wavefront per block - header, record framing, region scan
+without an index).  It hands out `Chunk`s: the slim image that goes to the device (per
 record the 32 fixed bytes, the CIGAR words and the aux bytes) and the host image that stays behind (read names and 4-bit
 sequences, sliced only for the records somebody asks for).  `decode(ctx, chunk)` is the face of `csv_bam_decode`
 (bam.hip.h); `decode_host(chunk)` is the same function in numpy / Python - the CPU path, and what the tests compare the
 kernels with.
 
-    python -m cutesv_amd.bam FILE [--chrom C] [--dump-columns DIR]
+`inflate_blocks(ctx, payloads, isizes, crcs)` is the face of `csv_bgzf_inflate`, `inflate_blocks_host` its twin on Python's zlib.
+
+    python -m cutesv_amd.bam FILE [--chrom C] [--dump-columns DIR] [--inflate {host,device}]
 """
 import ctypes as C
 import os
+import zlib
 
 import numpy as np
 
@@ -101,9 +105,13 @@ class BamFile:
     order, `.records(chrom, start, end)` returns the records that overlap a region (what pysam's fetch yields), found by
     a forward scan that stops at the first record starting at or after `end`: no index file is needed."""
 
-    def __init__(self, path, threads=None):
+    def __init__(self, path, threads=None, inflate=None):
+        """inflate: None or "host" - the BGZF blocks are inflated on `threads` host threads; an engine.Context - on its device
+        (set_inflate).  The header is read on the host either way."""
+        _inflate_ctx(inflate)                                                 # (refused before the file is opened)
         L = self._L = lib()
         self._h = C.c_void_p()
+        self.inflate, self.last_stats, self.window_blocks = None, {}, 0
         self.threads = default_threads() if threads is None else max(1, int(threads))
         err = C.create_string_buffer(512)
         rc = L.csv_bam_open(os.fsencode(path), self.threads, C.byref(self._h), err, len(err))
@@ -126,6 +134,28 @@ class BamFile:
         if self.sort_order != "coordinate":
             self.close()
             raise BamError("%s: the header says SO:%s; a coordinate-sorted file is needed (samtools sort)" % (path, self.sort_order or "<missing>"))
+        self.set_inflate(inflate)
+
+    def set_inflate(self, inflate, window_blocks=None):
+        """Where the BGZF blocks are inflated from now on: None or "host" - host threads; an engine.Context - csv_bgzf_inflate on
+        its device, window_blocks blocks per call (0: the library's default; None: what this reader was last told), with the host
+        inflating again whatever block the device gives up on.  What a chunk contains does not depend on it.  -> the previous
+        setting (None or the Context).  The Context must stay open as long as it is set here."""
+        ctx = _inflate_ctx(inflate)
+        window_blocks = self.window_blocks if window_blocks is None else window_blocks
+        if not isinstance(window_blocks, (int, np.integer)) or not 0 <= int(window_blocks) <= 16384:
+            raise ValueError("window_blocks must lie in 0 .. 16384, not %r" % (window_blocks,))
+        rc = self._L.csv_bam_set_inflate(self._h, ctx._h if ctx is not None else None, int(window_blocks))
+        if rc:
+            raise BamError("%s: the inflate route cannot be set" % self.path)
+        prev, self.inflate, self.window_blocks = self.inflate, ctx, int(window_blocks)
+        return prev
+
+    def inflate_stats(self):
+        """of the last read: dict(inflate "host" | "device", device_blocks, fallback_blocks, ms_inflate_kernels)"""
+        dev, fb, ms = C.c_int64(), C.c_int64(), C.c_double()
+        self._L.csv_bam_inflate_stats(self._h, C.byref(dev), C.byref(fb), C.byref(ms))
+        return dict(inflate="host" if self.inflate is None else "device", device_blocks=int(dev.value), fallback_blocks=int(fb.value), ms_inflate_kernels=float(ms.value))
 
     def close(self):
         if self._h:
@@ -161,6 +191,8 @@ class BamFile:
         n = int(cc.n_records)
         stats = dict(n_records=n, record_bytes=int(cc.record_bytes), inflated_bytes=int(cc.inflated_bytes), compressed_bytes=int(cc.compressed_bytes),
                      slim_bytes=int(cc.slim_bytes), ms_inflate=float(cc.ms_inflate), ms_frame=float(cc.ms_frame))
+        stats.update(self.inflate_stats())
+        self.last_stats = stats
         if flags & _abi.BAM_COUNT_ONLY:
             return n, bool(cc.more)
         # bytes that cross PCIe per record (image + offset + length) next to the inflated bytes of the record
@@ -192,6 +224,66 @@ class BamFile:
             if not more:
                 return total
             flags = _abi.BAM_COUNT_ONLY
+
+
+# ------------------------------------------------------------------------------------ BGZF inflate
+def _inflate_ctx(inflate):
+    """the `inflate` argument of BamFile -> None (host threads) or the Context"""
+    if inflate is None or (isinstance(inflate, str) and inflate == "host"):
+        return None
+    if isinstance(inflate, str) or not hasattr(inflate, "_h") or not hasattr(inflate, "_check"):
+        raise ValueError("inflate must be None, 'host' or an engine.Context, not %r" % (inflate,))
+    return inflate
+
+
+INFLATE_STATUS = dict(header=1, lengths=2, symbol=4, distance=8, output=16, short=32, input=64, crc=128)      # CSV_INF_E_*
+
+
+def inflate_blocks(ctx, payloads, isizes, crcs, guard=0):
+    """csv_bgzf_inflate on raw-deflate payloads -> ([bytes per block], status uint8[n], ms_kernels).  Block k's bytes are what the
+    device wrote for it - exactly zlib's when status[k] == 0, unspecified otherwise.  guard: that many bytes of 0xA5 stand in front
+    of and behind the output buffer, and they are returned as a fourth item (front + back) for tests of the entry's bounds."""
+    n = len(payloads)
+    in_len = np.array([len(p) for p in payloads], np.int32)
+    in_off = np.zeros(n, np.int64)
+    if n:
+        in_off[1:] = np.cumsum(in_len[:-1], dtype=np.int64)
+    out_len = np.asarray(isizes, np.int32).reshape(n)
+    out_off = np.zeros(n, np.int64)
+    if n:
+        out_off[1:] = np.cumsum(out_len[:-1], dtype=np.int64)
+    comp = np.frombuffer(b"".join(bytes(p) for p in payloads), np.uint8)
+    total = int(out_len.sum(dtype=np.int64)) if n else 0
+    buf = np.full(total + 2 * guard, 0xA5, np.uint8)
+    crc = np.asarray(crcs, np.uint32).reshape(n)
+    status = np.zeros(n, np.uint8)
+    ms = C.c_double()
+    ptr = lambda a: a.ctypes.data if len(a) else None                              # noqa: E731
+    rc = lib().csv_bgzf_inflate(ctx._h, ptr(comp), len(comp), n, ptr(in_off), ptr(in_len), ptr(out_off), ptr(out_len), ptr(crc),
+                                buf.ctypes.data + guard if total else None, total, 0, ptr(status), C.byref(ms))
+    ctx._check(rc)
+    out = buf[guard : guard + total]
+    blocks = [out[int(o) : int(o) + int(ln)].tobytes() for o, ln in zip(out_off, out_len)]
+    if guard:
+        return blocks, status, float(ms.value), np.concatenate([buf[:guard], buf[guard + total:]])
+    return blocks, status, float(ms.value)
+
+
+def inflate_blocks_host(payloads, isizes, crcs):
+    """the twin of inflate_blocks on zlib.decompress(p, -15) and zlib.crc32: ([bytes per block], ok bool[n]).  ok[k]: the payload
+    inflates, to exactly isizes[k] bytes with CRC32 crcs[k] (an empty block is ok as it is); the checker says no more than that."""
+    blocks, ok = [], np.zeros(len(payloads), bool)
+    for k, (p, isize, crc) in enumerate(zip(payloads, isizes, crcs)):
+        if int(isize) == 0:
+            blocks.append(b""); ok[k] = True
+            continue
+        try:
+            data = zlib.decompress(bytes(p), -15)
+        except zlib.error:
+            data = None
+        ok[k] = data is not None and len(data) == int(isize) and (zlib.crc32(data) & 0xFFFFFFFF) == int(crc)
+        blocks.append(data if ok[k] else b"")
+    return blocks, ok
 
 
 # ------------------------------------------------------------------------------------ decode: device
@@ -325,8 +417,21 @@ def main(argv=None):
     ap.add_argument("--chrom", default=None, help="only this contig")
     ap.add_argument("--threads", type=int, default=None, help="host threads of the inflate (default: min(16, CPUs))")
     ap.add_argument("--dump-columns", metavar="DIR", default=None, help="write the decoded columns of --chrom (host decode) as DIR/<column>.npy")
+    ap.add_argument("--inflate", default="host", choices=["host", "device"], help="where the BGZF blocks are inflated: host threads, or the GPU (device 0) [%(default)s]")
     a = ap.parse_args(argv)
-    with BamFile(a.bam, threads=a.threads) as bf:
+    ctx = None
+    if a.inflate == "device":
+        from . import engine
+        ctx = engine.Context(0)
+    try:
+        return _main(a, ap, ctx)
+    finally:
+        if ctx is not None:
+            ctx.close()
+
+
+def _main(a, ap, ctx):
+    with BamFile(a.bam, threads=a.threads, inflate=ctx) as bf:
         print(bf.header_text.rstrip("\n"))
         names = [a.chrom] if a.chrom is not None else list(bf.references) + [None]
         for name in names:

@@ -2,7 +2,7 @@
 
     text, svid = call_bam("in.bam", fasta.Reference("ref.fa"), CallParams(Params.ont(min_support=3)))
     python -m cutesv_amd.call in.bam ref.fa -o out.body.vcf [--genotype] [--tra_gt MODE] [--report_readid] [--min_support N] [--batch B]
-                               [--include_bed FILE] [--reads_table {host,device}] [--sigs_dir DIR]
+                               [--include_bed FILE] [--reads_table {host,device}] [--sigs_dir DIR] [--inflate {host,device}]
 
 (cuteSV's own command line - BAM REF OUT.vcf WORK_DIR and its flags, a VCF with header - is cutesv_amd/cli.py: python -m cutesv_amd.)
 
@@ -61,6 +61,8 @@ def cut_tasks(length, batch):
 DEFAULT_GATES = "device"        # where call_bam evaluates the task gates without a BED (decided by its measurement)
 DEFAULT_READS_TABLE = "host"    # where call_bam builds the genotyping reads table: not measured yet, so it stays "host" until scripts/reads_stage.py has been run
                                 # on an MI355X (DESIGN.md section 20 has the rule that decides)
+DEFAULT_INFLATE = "host"        # where call_bam inflates the BAM's BGZF blocks: "device" is opt-in until scripts/inflate_stage.py has been run on an MI355X
+                                # and its figures pass the rule of DESIGN.md section 27
 TRA_GT_MODES = ("alignments", "reads_table", "off")
 
 
@@ -111,7 +113,7 @@ class _Shim:
 
 
 def call_bam(bam, reference, params, ctx=None, chroms=None, batch=10_000_000, report_readid=False, ignore_sequence=False, threads=None, svid=None,
-             as_bytes=False, timings=None, tra_gt=None, include_bed=None, gates=None, reads_table=None, sigs_dir=None):
+             as_bytes=False, timings=None, tra_gt=None, include_bed=None, gates=None, reads_table=None, sigs_dir=None, inflate=None):
     """-> (VCF body text, svid counters [INS, DEL, BND, DUP, INV]).
 
     bam        a path or an open bam.BamFile (coordinate-sorted; no index is needed)
@@ -120,7 +122,8 @@ def call_bam(bam, reference, params, ctx=None, chroms=None, batch=10_000_000, re
     ctx        an engine.Context (default: one on device 0 for the call); its pool, name pool and sequence pool are reset
     chroms     the contigs to call on (default: all of the header); TRA mates may lie on any contig of the header
     batch      reference bases per extraction task (the reference's -b)
-    timings    a dict that receives the wall milliseconds of the stages (tasks, rebuild, sigs, cluster, tra_gt, gather, emit)
+    timings    a dict that receives the wall milliseconds of the stages (tasks, rebuild, sigs, cluster, tra_gt, gather, emit) and
+               ms_inflate, the part of ms_tasks the reader spent inflating (either route: staging, copies, kernels and fallback included)
     tra_gt     how TRA calls are genotyped: "alignments", "reads_table" or "off"; None follows CUTESV_AMD_TRA_GT (ValueError for
                bam, see tra_gt_mode)
     include_bed  a BED file's path or a bed.Regions: only call where these regions are (the reference's -include_bed).  Every task
@@ -135,12 +138,19 @@ def call_bam(bam, reference, params, ctx=None, chroms=None, batch=10_000_000, re
                gathered there and the engine copies the columns device to device.  Same text either way.
     sigs_dir   a directory that receives the rebuilt signatures as cuteSV's --write_old_sigs files (DEL.sigs .. TRA.sigs, made on the
                device by rebuild.write_sigs right after the rebuild; empty files when the BAM yields no signature).  The
-               returned text and svid do not depend on it.  None: no files."""
+               returned text and svid do not depend on it.  None: no files.
+    inflate    "host" or "device": where the BGZF blocks are inflated (None: DEFAULT_INFLATE).  device: on `ctx`, one wavefront per
+               block; a BamFile that was handed in gets the context for the call and its previous setting back
+               at the end.  Same text either way."""
     from . import aln, bam as bam_mod, bed as bed_mod, engine, extract, reads as reads_mod, rebuild, vcf
     if reads_table is None:
         reads_table = DEFAULT_READS_TABLE
     if reads_table not in ("host", "device"):
         raise ValueError("reads_table must be 'host' or 'device', not %r" % (reads_table,))
+    if inflate is None:
+        inflate = DEFAULT_INFLATE
+    if inflate not in ("host", "device"):
+        raise ValueError("inflate must be 'host' or 'device', not %r" % (inflate,))
     regions = None if include_bed is None else include_bed if isinstance(include_bed, bed_mod.Regions) else bed_mod.load_bed(include_bed)
     if gates is None:
         gates = "device" if regions is not None else DEFAULT_GATES
@@ -152,6 +162,7 @@ def call_bam(bam, reference, params, ctx=None, chroms=None, batch=10_000_000, re
     own_ctx = ctx is None
     if own_ctx:
         ctx = engine.Context(0)
+    restore = None                                            # the reader's inflate route before this call, once it has been changed
     clock = [time.perf_counter()]
 
     def lap(key):
@@ -160,6 +171,7 @@ def call_bam(bam, reference, params, ctx=None, chroms=None, batch=10_000_000, re
             timings[key] = timings.get(key, 0.0) + (now - clock[0]) * 1e3
         clock[0] = now
     try:
+        restore = (bf.set_inflate(ctx if inflate == "device" else None),)
         # the chromosome table in name order: a chromosome's index is its name rank, the numbering of rebuild._segments and of a TRA row's mate
         names = sorted(bf.references)
         length = dict(zip(bf.references, bf.lengths))
@@ -185,6 +197,8 @@ def call_bam(bam, reference, params, ctx=None, chroms=None, batch=10_000_000, re
                                          bed_regions=None if regions is None else regions.for_task(c, t0, t1))
                 if p.genotype and not reads_dev:
                     tables.append((crank[c], r))
+                if timings is not None:
+                    timings["ms_inflate"] = timings.get("ms_inflate", 0.0) + bf.last_stats["ms_inflate"]      # (a task reads its records in one call)
         lap("ms_tasks")
         if rebuild.pool_rows(ctx) == 0:
             if sigs_dir is not None:                           # (no signature at all: five empty files, as the reference's open(..., "w") leaves them)
@@ -233,10 +247,12 @@ def call_bam(bam, reference, params, ctx=None, chroms=None, batch=10_000_000, re
         lap("ms_emit")
         return out
     finally:
+        if restore is not None and not own_bam:
+            bf.set_inflate(restore[0])
+        if own_bam:                                            # (the reader goes before the context it may inflate on)
+            bf.close()
         if own_ctx:
             ctx.close()
-        if own_bam:
-            bf.close()
 
 
 def main(argv=None):
@@ -268,6 +284,7 @@ def main(argv=None):
                     help="with --genotype: where the genotyping reads table is built (default: %s)" % DEFAULT_READS_TABLE)
     ap.add_argument("--tra_gt", default=None, choices=list(TRA_GT_MODES),
                     help="with --genotype: how BND records are genotyped (default: CUTESV_AMD_TRA_GT, else alignments - every alignment counts, as in cuteSV)")
+    ap.add_argument("--inflate", default=None, choices=["host", "device"], help="where the BAM's BGZF blocks are inflated (default: %s)" % DEFAULT_INFLATE)
     ap.add_argument("--sigs_dir", default=None, metavar="DIR", help="also write the rebuilt signatures there as cuteSV's --write_old_sigs files (DEL.sigs .. TRA.sigs)")
     a = ap.parse_args(argv)
     tra_gt = a.tra_gt
@@ -278,7 +295,7 @@ def main(argv=None):
                     merge_del_threshold=a.merge_del_threshold, merge_ins_threshold=a.merge_ins_threshold)
     text, svid = call_bam(a.bam, fasta.Reference(a.reference), cp, chroms=a.chroms.split(",") if a.chroms else None, batch=a.batch,
                           report_readid=a.report_readid, ignore_sequence=a.ignore_sequence, threads=a.threads, as_bytes=True, tra_gt=tra_gt,
-                          include_bed=a.include_bed, reads_table=a.reads_table, sigs_dir=a.sigs_dir)
+                          include_bed=a.include_bed, reads_table=a.reads_table, sigs_dir=a.sigs_dir, inflate=a.inflate)
     with open(a.out, "wb") as f:
         f.write(text)
     print("%d records: INS %d, DEL %d, BND %d, DUP %d, INV %d" % (text.count(b"\n"), *svid.tolist()))

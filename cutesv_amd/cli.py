@@ -1,6 +1,6 @@
 """cuteSV's command line on this project's chain:
 
-    python -m cutesv_amd BAM REF OUT.vcf WORK_DIR [cuteSV's flags] [--reads_table {host,device}] [--tra_gt MODE]
+    python -m cutesv_amd BAM REF OUT.vcf WORK_DIR [cuteSV's flags] [--reads_table {host,device}] [--tra_gt MODE] [--inflate {host,device}]
 
 `parse_args` accepts every option of cuteSV v2.1.4 under the same short and long spellings, with the same destination, type
 and default, so a command line written for cuteSV runs here unchanged; `main` maps them onto call.call_bam and writes a complete
@@ -89,16 +89,17 @@ def _parser():
 
 
 def _own_parser():
-    """the two options cuteSV does not have; parsed apart (split_own), so that they shadow no abbreviation of a cuteSV flag"""
+    """the three options cuteSV does not have; parsed apart (split_own), so that they shadow no abbreviation of a cuteSV flag"""
     from . import call
     ap = argparse.ArgumentParser(add_help=False, allow_abbrev=False)
     ap.add_argument("--reads_table", default=None, choices=["host", "device"])
     ap.add_argument("--tra_gt", default=None, choices=list(call.TRA_GT_MODES))
+    ap.add_argument("--inflate", default=None, choices=["host", "device"])
     return ap
 
 
 def split_own(argv):
-    """-> (namespace of --reads_table / --tra_gt, argv without them)"""
+    """-> (namespace of --reads_table / --tra_gt / --inflate, argv without them)"""
     return _own_parser().parse_known_args(list(argv))
 
 
@@ -150,7 +151,7 @@ def main(argv=None):
         _log("%d contigs in %s" % (len(contigs), a.input))
         body, svid = call.call_bam(bf, fasta.Reference(a.reference), call_params(a), batch=a.batches, report_readid=a.report_readid,
                                    ignore_sequence=a.ignore_sequence, as_bytes=True, timings=timings, tra_gt=tra_gt, include_bed=a.include_bed,
-                                   reads_table=own.reads_table, sigs_dir=sigs_dir)
+                                   reads_table=own.reads_table, sigs_dir=sigs_dir, inflate=own.inflate)
     finally:
         bf.close()
     for key, ms in timings.items():

@@ -14,10 +14,14 @@
 //   k_bam_sa      one thread per record with SA tags: the walk again, now writing the value ranges
 // Every byte a kernel reads lies inside [rec_off, rec_off + rec_len) of its record: the host entry checks those ranges
 // against the image, k_bam_fixed checks the CIGAR and every aux value against the record.
+//
+// At the end of the file, the step in front of all that: k_bgzf_inflate, one wavefront per BGZF block, over the decode core
+// of inflate_core.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "wave.hip.h"
+#include "inflate_core.h"
 
 namespace csv {
 
@@ -225,6 +229,84 @@ __global__ __launch_bounds__(256) void k_bam_sa(BamArgs A)
     AuxTag t;
     while (o < o_end && aux_next(A.slim, p, end, t) == 1)
         if (t.k0 == 'S' && t.k1 == 'A' && t.type == 'Z') { A.sa_beg[o] = t.vbeg; A.sa_end[o] = t.vend; o++; }
+}
+
+// ------------------------------------------------------------------------------------ BGZF inflate
+// The 64-lane form of inflate_core.h's Lanes.  uni: v_readfirstlane, so whatever the decode core decides on lives in scalar
+// registers and every branch on it is a scalar branch: all 64 lanes leave a block together, none waits at a shuffle the others
+// skipped.  sync: a wavefront's LDS and global accesses are issued in order, so a fence of wavefront scope - an ordering for the
+// compiler, no instruction - is all a lane needs to see what another lane of its wave wrote.
+struct InfWave {
+    __device__ __forceinline__ int lane() const { return lane_id(); }
+    __device__ __forceinline__ int width() const { return WAVE; }
+    __device__ __forceinline__ uint32_t uni(uint32_t v) const { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
+    __device__ __forceinline__ void sync() const
+    {
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+    }
+    // a * b in GF(2)[x] modulo the CRC32 polynomial, reflected: bit 31 is x^0
+    static __device__ __forceinline__ uint32_t mul(uint32_t a, uint32_t b)
+    {
+        uint32_t p = 0;
+        for (int k = 0; k < 32; k++) {
+            if (a & (0x80000000u >> k)) p ^= b;
+            b = (b >> 1) ^ ((b & 1u) ? 0xEDB88320u : 0u);
+        }
+        return p;
+    }
+    // CRC32 of out[0 .. len), len >= 1: the bytes are cut into 64 pieces of c = ceil(len / 64) - as if 64 c - len zero bytes stood
+    // in front, which leave a register of zero as it is; the lane that holds byte 0 starts from 0xffffffff there.  Lane l's
+    // register r_l then counts for r_l * x^(8 c (63 - l)): six rounds of "left half times x^(8 c s), plus right half".
+    __device__ __forceinline__ uint32_t crc(const uint8_t* out, int32_t len, const uint32_t* table) const
+    {
+        const int c = (len + 63) >> 6, l = lane_id();
+        int lo = l * c - (64 * c - len);
+        const int hi = lo + c;                                    // (hi <= len: lane 63 ends at 64 c - (64 c - len))
+        uint32_t r = 0;
+        if (hi > 0) {
+            if (lo <= 0) { r = 0xffffffffu; lo = 0; }
+            for (int i = lo; i < hi; i++) r = table[(r ^ out[i]) & 255u] ^ (r >> 8);
+        }
+        uint32_t q = 0x80000000u;                                 // x^0 -> x^(8 c): c zero bytes through the register
+        for (int i = 0; i < c; i++) q = table[q & 255u] ^ (q >> 8);
+        for (int s = 1; s < 64; s <<= 1) {
+            const uint32_t right = (uint32_t)__shfl_down((int)r, s);
+            if ((l & (2 * s - 1)) == 0) r = mul(r, q) ^ right;
+            q = mul(q, q);
+        }
+        return uni(r) ^ 0xffffffffu;
+    }
+};
+
+struct InflateArgs {
+    int n;                          // BGZF blocks
+    const uint8_t* comp;            // block k's raw-deflate payload: comp[in_off[k] .. + in_len[k])
+    const i64* in_off; const int* in_len;
+    const i64* out_off; const int* out_len;     // its bytes: out[out_off[k] .. + out_len[k]), host-checked: inside `out`, disjoint, at most 65536
+    const unsigned* crc;
+    uint8_t* out;
+    uint8_t* status;
+};
+
+constexpr int INF_WAVES = 4;        // wavefronts (BGZF blocks in flight) per workgroup
+
+// One wavefront per BGZF block, a grid-stride loop over the blocks.  No workgroup barrier behind the first: the four waves of a
+// workgroup share nothing but the CRC table.  LDS: 4 * sizeof(InfWork) + 1 KiB = 10 KiB per workgroup.
+__global__ __launch_bounds__(64 * INF_WAVES) void k_bgzf_inflate(InflateArgs A)
+{
+    __shared__ InfWork work[INF_WAVES];
+    __shared__ uint32_t crc_table[256];
+    crc_table[threadIdx.x] = inf_crc_entry(threadIdx.x);
+    __syncthreads();
+    const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const InfWave L;
+    for (i64 k = (i64)blockIdx.x * INF_WAVES + w; k < A.n; k += (i64)gridDim.x * INF_WAVES) {
+        const int out_len = A.out_len[k];
+        int st = 0;
+        if (out_len > 0) st = inf_block(L, work[w], A.comp + A.in_off[k], A.in_len[k], A.out + A.out_off[k], out_len, A.crc[k], crc_table);
+        if (L.lane() == 0) A.status[k] = (uint8_t)st;
+    }
 }
 
 }  // namespace csv

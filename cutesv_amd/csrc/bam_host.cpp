@@ -1,5 +1,7 @@
 // bam_host.cpp — the host side of the native BAM reader: BGZF inflate on host threads, the BAM
-// header, record framing, region scan and the slim image the decode kernels (bam.hip.h) take.
+// header, record framing, region scan and the slim image the decode kernels (bam.hip.h) take.  With csv_bam_set_inflate the
+// windows are inflated on the device instead (csv_bgzf_inflate) and the host inflates only the blocks
+// the device gave up on.
 //
 // Written from the SAM/BAM specification (SAMv1, sections 4.1 "The BGZF compression format" and 4.2 "The BAM format"):
 //   BGZF block  = gzip member with one extra subfield 'B','C' (u16 BSIZE = block size - 1), raw deflate payload, CRC32, ISIZE
@@ -42,6 +44,7 @@ struct Block { i64 coff; int32_t csize, hdr; uint32_t isize; i64 uoff; };      /
 
 constexpr i64 SLIM_ALIGN = 16;               // a slim record starts 16-byte aligned: its CIGAR words (at + 32) are too
 constexpr int REFILL_BLOCKS = 256;           // BGZF blocks inflated per refill of the window (<= 16 MiB inflated)
+constexpr int MAX_WINDOW_BLOCKS = 16384;     // ... on the device route at most (csv_bam_set_inflate; <= 1 GiB inflated)
 
 }  // namespace
 
@@ -59,8 +62,21 @@ struct csv_bam {
     int32_t              n_ref = 0;
     i64                  first_rec = 0;      // uncompressed offset of the first record
     // the inflated window [win_u0, win_u0 + win.size())
-    std::vector<uint8_t> win;
+    std::vector<uint8_t> win;                // (the host route's storage)
+    const uint8_t*       win_p = nullptr;    // the window's bytes: win.data(), or the page-locked window of the device route
+    i64                  win_n = 0;
     i64                  win_u0 = 0;
+    // the device route (csv_bam_set_inflate): the context, blocks per window, the page-locked window, the tables of one call
+    csv_ctx*             dev = nullptr;
+    int                  window_blocks = REFILL_BLOCKS;
+    uint8_t*             pin = nullptr;
+    i64                  pin_cap = 0;
+    std::vector<int64_t> d_in_off, d_out_off;
+    std::vector<int32_t> d_in_len, d_out_len;
+    std::vector<uint32_t> d_crc;
+    std::vector<uint8_t> d_status;
+    i64                  device_blocks = 0, fallback_blocks = 0;
+    double               ms_kernels = 0;
     i64                  cur = 0;            // uncompressed offset of the next record
     std::map<uint32_t, i64> contig_at;       // (uint32)refID -> offset of its first record, as found (-1 sorts last, as in a sorted file)
     uint32_t             scanned_key = 0;    // every contig with a key <= this one that exists is in contig_at
@@ -136,10 +152,56 @@ bool inflate_block(const csv_bam* b, const Block& k, uint8_t* dst)
     return (uint32_t)crc32(crc32(0L, Z_NULL, 0), dst, k.isize) == rd_u32(b->map + k.coff + k.csize - 8);
 }
 
+// the window becomes the inflated blocks [b0, b1), on the device: the mapped file from the first block's header to the last
+// block's trailer is the `comp` of one csv_bgzf_inflate (the payloads lie in it where they are: nothing is gathered), the bytes land
+// in the page-locked window, and every block the device reports is inflated again by inflate_block, whose verdict stands
+int load_window_device(csv_bam* b, size_t b0, size_t b1)
+{
+    const double t0 = now_ms();
+    b->win_n = 0;
+    b->win_u0 = b->blocks[b0].uoff;
+    const i64 bytes = (b1 < b->blocks.size() ? b->blocks[b1].uoff : b->utotal) - b->win_u0;
+    if (bytes > b->pin_cap) {
+        if (b->pin) { csv_host_free(b->pin); b->pin = nullptr; b->pin_cap = 0; }
+        void* p = nullptr;
+        const i64 want = bytes + bytes / 4 + 4096;
+        if (csv_host_alloc(want, &p) != CSV_OK) return fail(b, CSV_E_NOMEM, "%scannot page-lock an inflate window of %lld bytes", "", (long long)want);
+        b->pin = (uint8_t*)p; b->pin_cap = want;
+    }
+    const size_t n = b1 - b0;
+    b->d_in_off.resize(n); b->d_in_len.resize(n); b->d_out_off.resize(n); b->d_out_len.resize(n); b->d_crc.resize(n); b->d_status.resize(n);
+    const i64 base = b->blocks[b0].coff, comp_bytes = b->blocks[b1 - 1].coff + b->blocks[b1 - 1].csize - base;
+    for (size_t j = 0; j < n; j++) {
+        const Block& k = b->blocks[b0 + j];
+        b->d_in_off[j] = k.coff + k.hdr - base; b->d_in_len[j] = k.csize - k.hdr - 8;
+        b->d_out_off[j] = k.uoff - b->win_u0; b->d_out_len[j] = (int32_t)k.isize;
+        b->d_crc[j] = rd_u32(b->map + k.coff + k.csize - 8);
+    }
+    double ms = 0;
+    const int rc = csv_bgzf_inflate(b->dev, b->map + base, comp_bytes, (int32_t)n, b->d_in_off.data(), b->d_in_len.data(), b->d_out_off.data(), b->d_out_len.data(),
+                                    b->d_crc.data(), b->pin, bytes, 0, b->d_status.data(), &ms);
+    if (rc) return fail(b, rc, "the device inflate failed: %s", csv_last_error(b->dev));
+    b->ms_kernels += ms;
+    i64 bad = -1;
+    for (size_t j = 0; j < n; j++) {
+        if (!b->d_status[j]) { b->device_blocks++; continue; }
+        b->fallback_blocks++;
+        if (!inflate_block(b, b->blocks[b0 + j], b->pin + b->d_out_off[j])) bad = (i64)(b0 + j);
+    }
+    for (size_t j = b0; j < b1; j++) b->compressed += b->blocks[j].csize;
+    b->inflated += bytes;
+    b->ms_inflate += now_ms() - t0;
+    if (bad >= 0) return fail(b, CSV_E_INVALID, "%sBGZF block at byte %lld does not inflate (or fails its CRC)", "", (long long)b->blocks[(size_t)bad].coff);
+    b->win_p = b->pin; b->win_n = bytes;
+    return CSV_OK;
+}
+
 // the window becomes the inflated blocks [b0, b1)
 int load_window(csv_bam* b, size_t b0, size_t b1)
 {
+    if (b->dev) return load_window_device(b, b0, b1);
     const double t0 = now_ms();
+    b->win_n = 0;
     b->win_u0 = b->blocks[b0].uoff;
     const i64 bytes = (b1 < b->blocks.size() ? b->blocks[b1].uoff : b->utotal) - b->win_u0;
     b->win.resize((size_t)bytes);
@@ -162,6 +224,7 @@ int load_window(csv_bam* b, size_t b0, size_t b1)
     b->inflated += bytes;
     b->ms_inflate += now_ms() - t0;
     if (bad.load() >= 0) return fail(b, CSV_E_INVALID, "%sBGZF block at byte %lld does not inflate (or fails its CRC)", "", (long long)b->blocks[(size_t)bad.load()].coff);
+    b->win_p = b->win.data(); b->win_n = bytes;
     return CSV_OK;
 }
 
@@ -179,14 +242,14 @@ const uint8_t* at(csv_bam* b, i64 u, i64 need, int* rc)
 {
     *rc = CSV_OK;
     if (u + need > b->utotal) return nullptr;
-    if (u < b->win_u0 || u + need > b->win_u0 + (i64)b->win.size()) {
+    if (u < b->win_u0 || u + need > b->win_u0 + b->win_n) {
         const size_t b0 = block_of(b, u);
-        size_t b1 = std::min(b->blocks.size(), b0 + REFILL_BLOCKS);
+        size_t b1 = std::min(b->blocks.size(), b0 + (size_t)(b->dev ? b->window_blocks : REFILL_BLOCKS));
         while (b1 < b->blocks.size() && b->blocks[b1].uoff < u + need) b1++;
         *rc = load_window(b, b0, b1);
         if (*rc) return nullptr;
     }
-    return b->win.data() + (u - b->win_u0);
+    return b->win_p + (u - b->win_u0);
 }
 
 int read_header(csv_bam* b)
@@ -269,6 +332,7 @@ void csv_bam_close(csv_bam* b)
     if (!b) return;
     if (b->map) munmap(const_cast<uint8_t*>(b->map), (size_t)b->fsize);
     if (b->fd >= 0) close(b->fd);
+    if (b->pin) csv_host_free(b->pin);
     delete b;
 }
 
@@ -285,12 +349,31 @@ int csv_bam_header(const csv_bam* b, int32_t* n_ref, const char** names, const i
     return CSV_OK;
 }
 
+int csv_bam_set_inflate(csv_bam* b, csv_ctx* ctx, int32_t window_blocks)
+{
+    if (!b || window_blocks > MAX_WINDOW_BLOCKS) return CSV_E_INVALID;
+    b->win_n = 0;                                            // the next read fills its window on this route (what open inflated for the header is not kept)
+    b->dev = ctx;
+    b->window_blocks = window_blocks > 0 ? window_blocks : CSV_BAM_WINDOW_BLOCKS;
+    return CSV_OK;
+}
+
+int csv_bam_inflate_stats(const csv_bam* b, int64_t* device_blocks, int64_t* fallback_blocks, double* ms_kernels)
+{
+    if (!b) return CSV_E_INVALID;
+    if (device_blocks) *device_blocks = b->device_blocks;
+    if (fallback_blocks) *fallback_blocks = b->fallback_blocks;
+    if (ms_kernels) *ms_kernels = b->ms_kernels;
+    return CSV_OK;
+}
+
 int csv_bam_read(csv_bam* b, int32_t refid, int64_t beg, int64_t end, int64_t max_records, int32_t flags, csv_bam_chunk* out)
 {
     if (!b || !out || max_records < 1) return CSV_E_INVALID;
     const double t0 = now_ms();
     memset(out, 0, sizeof *out);
     b->ms_inflate = 0; b->inflated = b->compressed = 0;
+    b->device_blocks = b->fallback_blocks = 0; b->ms_kernels = 0;
     b->slim.clear(); b->host.clear(); b->rec_off.clear(); b->host_off.clear(); b->rec_len.clear();
     const bool count_only = (flags & CSV_BAM_COUNT_ONLY) != 0;
     const uint32_t key = (uint32_t)refid;

@@ -147,6 +147,17 @@ struct ReadsTabState {
     void own(std::vector<Buf*>& v) { v.insert(v.end(), {&start, &end, &primary, &id, &work, &rid}); }
 };
 
+// BGZF inflate (stage_inflate.hip.h): the payloads, the block tables, the inflated bytes and the status bytes of ONE csv_bgzf_inflate
+// call, all stand-alone and grow-only; dead when the call returns.  No other stage reads or writes them, and the entry touches nothing
+// else of the context but its stream and its first two timing events.  tab_h / order: the host image of the tables and the blocks in
+// output order (the overlap check, the runs of the download).
+struct InflateState {
+    Buf comp, tab, out, status;
+    std::vector<char> tab_h;
+    std::vector<int32_t> order;
+    void own(std::vector<Buf*>& v) { v.insert(v.end(), {&comp, &tab, &out, &status}); }
+};
+
 // ---- The state of the engine (stage_upload / stage_run / stage_results.hip.h): the path csv_batch_upload -> csv_batch_run ->
 // csv_batch_download / csv_batch_publish_* and the one-shot csv_cluster_batch.  One struct per concern, with the same kind of rule.
 
@@ -281,7 +292,7 @@ struct csv_ctx {
     BatchState bt; ReadsOrderState ro; ResultState res; TableState tab;
     // ---- the extraction-side stages (their lifetime rules: at the structs)
     PoolState pool; NameState nm; BamState bm; SaState sa; SeqState seq; VcfStrState vs; AlnState al; ReadsTabState rt;
-    RebuildState rb; CigarState cg; SplitState sp;
+    RebuildState rb; CigarState cg; SplitState sp; InflateState inf;
 };
 
 namespace {

@@ -894,6 +894,44 @@ int         csv_bam_read(csv_bam* bam, int32_t refid, int64_t beg, int64_t end, 
 /* sizeof of 0 csv_bam_chunk, 1 csv_bam_in, 2 csv_bam_out; -1 otherwise */
 int         csv_bam_struct_size(int which);
 
+/* BGZF inflate on the device: the raw-deflate payloads of n_blocks BGZF blocks -> their bytes, one wavefront
+ * per block.  Block k's payload is comp[in_off[k] .. + in_len[k]), its out_len[k] (= ISIZE) bytes go to out[out_off[k] ..), crc[k]
+ * is the CRC32 of its trailer; comp, out and status are host memory.
+ *   status[k] == 0: out[out_off[k] .. + out_len[k]) holds exactly what zlib's inflate with Z_FINISH gives for the payload, and its
+ *   CRC32 is crc[k].  Otherwise the byte says why (CSV_INF_E_*), the block's bytes are unspecified - but nothing outside its own
+ *   range was written - and the caller inflates it again on the host if it wants a verdict it can report.  Bytes behind the final
+ *   deflate block are ignored, as zlib ignores them.  A block with out_len == 0 is skipped with status 0.  Bytes of `out` that
+ *   belong to no block are not written.
+ * The return value is CSV_OK whenever the call was well-formed: damaged blocks are reported per block.  CSV_E_INVALID, nothing
+ * launched: a payload outside comp, an output outside out, out_len above 65536, in_len < 0, overlapping outputs, n_blocks < 0,
+ * flags != 0 (none is defined).  *ms_kernels (may be NULL): device time of the kernel.
+ * The entry uses device buffers of its own and leaves everything else the context holds as it is: the columns of the last
+ * csv_bam_decode and their gates, the pools, a kept rebuild.
+ * The byte has eight bits for the nine reasons of a damaged block: a bad block type and a stored block whose LEN and NLEN
+ * disagree share CSV_INF_E_HEADER. */
+enum {
+    CSV_INF_E_HEADER = 1,      /* block type 3; stored LEN / NLEN mismatch */
+    CSV_INF_E_LENGTHS = 2,     /* over-subscribed or incomplete code lengths, too many of them, no end-of-block code */
+    CSV_INF_E_SYMBOL = 4,      /* literal/length 286 / 287, distance 30 / 31, a repeat code with nothing before it, bits that are no code */
+    CSV_INF_E_DISTANCE = 8,    /* a distance beyond the bytes produced so far in THIS block */
+    CSV_INF_E_OUTPUT = 16,     /* the output would pass out_len */
+    CSV_INF_E_SHORT = 32,      /* the stream ended (BFINAL done) short of out_len */
+    CSV_INF_E_INPUT = 64,      /* input exhausted */
+    CSV_INF_E_CRC = 128        /* CRC mismatch */
+};
+int csv_bgzf_inflate(csv_ctx* ctx, const uint8_t* comp, int64_t comp_bytes, int32_t n_blocks, const int64_t* in_off, const int32_t* in_len,
+                     const int64_t* out_off, const int32_t* out_len, const uint32_t* crc, uint8_t* out, int64_t out_bytes, int32_t flags,
+                     uint8_t* status, double* ms_kernels);
+/* The reader's inflate route.  ctx != NULL: csv_bam_read inflates its windows with csv_bgzf_inflate on that context, window_blocks
+ * BGZF blocks per call (<= 0: the default, CSV_BAM_WINDOW_BLOCKS; at most 16384), into a page-locked window out of which the records
+ * are framed in place; every block the device reports with a non-zero status is inflated again on the host, whose verdict stands: a
+ * damaged file gives the error text of the host route.  ctx == NULL: back to the host threads.  The context must outlive the reader
+ * or be taken away before it is destroyed.  What a chunk contains does not depend on the route. */
+#define CSV_BAM_WINDOW_BLOCKS 4096
+int csv_bam_set_inflate(csv_bam* bam, csv_ctx* ctx, int32_t window_blocks);
+/* since the start of the last csv_bam_read: blocks the device inflated, blocks the host inflated again, device time of the kernels */
+int csv_bam_inflate_stats(const csv_bam* bam, int64_t* device_blocks, int64_t* fallback_blocks, double* ms_kernels);
+
 /* Device side (bam.hip.h): the slim image of a chunk -> per-record columns, the packed CIGARs and the byte ranges of the
  * SA / CG tags, in device memory of the context (valid until its next csv_bam_decode; csv_cigar_signatures with
  * CSV_CG_FROM_BAM scans them in place, csv_bam_split_inputs parses the SA values there) and, for every host array that is not NULL, in the caller's memory.
