@@ -91,6 +91,11 @@ SYMBOLS = [
     ("csv_bam_header", C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]),
     ("csv_bam_read", C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.POINTER(_abi.ChunkC)]),
     ("csv_bam_struct_size", C.c_int, [C.c_int]),
+    ("csv_bam_index_load", C.c_int, [C.c_void_p, C.c_char_p]),
+    ("csv_bam_index_drop", C.c_int, [C.c_void_p]),
+    ("csv_bam_index_stats", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]),
+    ("csv_bam_index_block", C.c_int64, [C.c_void_p, C.c_int32, C.c_int64]),
+    ("csv_bam_read_ranges", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.POINTER(_abi.ChunkC)]),
     ("csv_bgzf_inflate", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32,
                                    C.c_void_p, C.POINTER(C.c_double)]),
     ("csv_bam_set_inflate", C.c_int, [C.c_void_p, C.c_void_p, C.c_int32]),

@@ -2,8 +2,8 @@
 pysam and without a Python object per record.
 
 `BamFile` is the host side (cutesv_amd/csrc/bam_host.cpp: BGZF inflate on host threads with the interpreter lock released - or,
-with inflate=<Context>, on the device, one wavefront per block - header, record framing, region scan
-without an index).  It hands out `Chunk`s: the slim image that goes to the device (per
+with inflate=<Context>, on the device, one wavefront per block (DESIGN.md section 27) - header, record framing, region scan;
+with a .bai beside the file a region's scan starts at its linear-index entry, without one at the contig).  It hands out `Chunk`s: the slim image that goes to the device (per
 record the 32 fixed bytes, the CIGAR words and the aux bytes) and the host image that stays behind (read names and 4-bit
 sequences, sliced only for the records somebody asks for).  `decode(ctx, chunk)` is the face of `csv_bam_decode`
 (bam.hip.h); `decode_host(chunk)` is the same function in numpy / Python - the CPU path, and what the tests compare the
@@ -11,7 +11,7 @@ kernels with.
 
 `inflate_blocks(ctx, payloads, isizes, crcs)` is the face of `csv_bgzf_inflate`, `inflate_blocks_host` its twin on Python's zlib.
 
-    python -m cutesv_amd.bam FILE [--chrom C] [--dump-columns DIR] [--inflate {host,device}]
+    python -m cutesv_amd.bam FILE [--chrom C] [--dump-columns DIR] [--inflate {host,device}] [--idxstats]
 """
 import ctypes as C
 import os
@@ -103,11 +103,14 @@ class Chunk:
 class BamFile:
     """A coordinate-sorted BAM file.  `.references`, `.lengths`, `.header_text`; `.chunks(chrom)` iterates a contig in file
     order, `.records(chrom, start, end)` returns the records that overlap a region (what pysam's fetch yields), found by
-    a forward scan that stops at the first record starting at or after `end`: no index file is needed."""
+    a forward scan that stops at the first record starting at or after `end`: no index file is needed.  With an index
+    (`has_index`) the scan starts at the linear-index entry of `start`; what it yields is the same, byte for byte."""
 
-    def __init__(self, path, threads=None, inflate=None):
+    def __init__(self, path, threads=None, inflate=None, index=None):
         """inflate: None or "host" - the BGZF blocks are inflated on `threads` host threads; an engine.Context - on its device
-        (set_inflate).  The header is read on the host either way."""
+        (set_inflate).  The header is read on the host either way.
+        index: None - <path>.bai, else <path minus .bam>.bai, is loaded when there is one; a path - that index, which must exist;
+        False - none.  An index that is found and does not validate against this file raises BamError."""
         _inflate_ctx(inflate)                                                 # (refused before the file is opened)
         L = self._L = lib()
         self._h = C.c_void_p()
@@ -135,6 +138,57 @@ class BamFile:
             self.close()
             raise BamError("%s: the header says SO:%s; a coordinate-sorted file is needed (samtools sort)" % (path, self.sort_order or "<missing>"))
         self.set_inflate(inflate)
+        self.has_index = False
+        if index is not False:
+            try:
+                self.load_index(None if index is None or index is True else index, required=index is not None)
+            except BamError:
+                self.close()
+                raise
+
+    def load_index(self, path=None, required=True):
+        """csv_bam_index_load: path None tries <bam>.bai, then <bam minus .bam>.bai.  -> has_index.  BamError: the index does not
+        validate (a reader whose load failed has none), or - with required - there is no such file."""
+        rc = self._L.csv_bam_index_load(self._h, None if path is None else os.fsencode(path))
+        if rc == _abi.E_STATE and not required:
+            return self.has_index
+        if rc:
+            self.has_index = False
+            raise BamError((self._L.csv_bam_error(self._h) or b"").decode(errors="replace") or "%s: the index cannot be loaded" % self.path)
+        self.has_index = True
+        return True
+
+    def index_block(self, chrom, pos):
+        """the number of the BGZF block in which a read of `chrom` from `pos` on starts (its linear-index entry); -1: the index says
+        that nothing is there.  BamError without an index."""
+        k = int(self._L.csv_bam_index_block(self._h, self.refid(chrom), int(pos)))
+        if k < -1:
+            raise BamError("%s: no index is loaded" % self.path)
+        return k
+
+    def drop_index(self):
+        self._L.csv_bam_index_drop(self._h)
+        self.has_index = False
+
+    def _index_counts(self):
+        if not self.has_index:
+            raise BamError("%s: no index is loaded" % self.path)
+        n = len(self.references)
+        mapped, unmapped, nc = np.zeros(n, np.int64), np.zeros(n, np.int64), C.c_int64()
+        self._L.csv_bam_index_stats(self._h, mapped.ctypes.data if n else None, unmapped.ctypes.data if n else None, C.byref(nc))
+        return mapped, unmapped, int(nc.value)
+
+    def index_statistics(self):
+        """[(contig, mapped, unmapped, total)] in header order: the counts of the index's pseudo-bins, what pysam's
+        get_index_statistics gives (zeros for a contig without one)"""
+        mapped, unmapped, _ = self._index_counts()
+        return [(c, int(m), int(u), int(m + u)) for c, m, u in zip(self.references, mapped, unmapped)]
+
+    @property
+    def no_coordinate(self):
+        """n_no_coor of the index: the reads without coordinates (None: the index does not carry it)"""
+        nc = self._index_counts()[2]
+        return None if nc < 0 else nc
 
     def set_inflate(self, inflate, window_blocks=None):
         """Where the BGZF blocks are inflated from now on: None or "host" - host threads; an engine.Context - csv_bgzf_inflate on
@@ -182,10 +236,21 @@ class BamFile:
             raise KeyError("no reference %r in %s" % (chrom, self.path))
         return self._refid[chrom]
 
-    def _read(self, chrom, beg, end, max_records, flags):
+    def _read(self, chrom, beg, end, max_records, flags, ranges=None):
         cc = ChunkC()
         refid = self.refid(chrom)
-        rc = self._L.csv_bam_read(self._h, refid, int(beg), int(end), int(max_records), int(flags), C.byref(cc))
+        if ranges is None:
+            rc = self._L.csv_bam_read(self._h, refid, int(beg), int(end), int(max_records), int(flags), C.byref(cc))
+        elif len(ranges) == 0:                                 # nothing to read: the empty chunk; the library is not asked and no block is touched
+            self.last_stats = dict(n_records=0, record_bytes=0, inflated_bytes=0, compressed_bytes=0, slim_bytes=0, ms_inflate=0.0, ms_frame=0.0,
+                                   inflate="host" if self.inflate is None else "device", device_blocks=0, fallback_blocks=0, ms_inflate_kernels=0.0,
+                                   upload_bytes_per_record=0.0, inflated_bytes_per_record=0.0)
+            if flags & _abi.BAM_COUNT_ONLY:
+                return 0, False
+            return Chunk(chrom, refid, np.zeros(0, np.uint8), np.zeros(0, np.int64), np.zeros(0, np.uint32), np.zeros(0, np.uint8), np.zeros(1, np.int64), False,
+                         self.last_stats)
+        else:
+            rc = self._L.csv_bam_read_ranges(self._h, refid, len(ranges), ranges[:, 0].ctypes.data, ranges[:, 1].ctypes.data, int(max_records), int(flags), C.byref(cc))
         if rc:
             raise BamError("%s: %s" % (self.path, (self._L.csv_bam_error(self._h) or b"").decode(errors="replace")))
         n = int(cc.n_records)
@@ -201,20 +266,33 @@ class BamFile:
         return Chunk(chrom, refid, _from_ptr(cc.slim, int(cc.slim_bytes), np.uint8), _from_ptr(cc.rec_off, n, np.int64), _from_ptr(cc.rec_len, n, np.uint32),
                      _from_ptr(cc.host, int(cc.host_bytes), np.uint8), _from_ptr(cc.host_off, n + 1, np.int64), bool(cc.more), stats)
 
-    def chunks(self, chrom, chunk_records=65536, start=-ALL, end=ALL):
-        """the records of `chrom` (None: the unmapped tail) in file order, at most chunk_records per Chunk"""
+    @staticmethod
+    def _ranges(ranges):
+        """ranges= of chunks / records -> None, or a Fortran-ordered int64 (k, 2) array (each column contiguous), k >= 1"""
+        if ranges is None:
+            return None
+        r = np.asfortranarray(np.asarray(ranges, np.int64).reshape(-1, 2))
+        if bool(np.any(r[:, 0] > r[:, 1])) or bool(np.any(r[1:, 0] < r[:-1, 1])):
+            raise ValueError("ranges must be sorted and disjoint: start <= end <= the next start")
+        return r
+
+    def chunks(self, chrom, chunk_records=65536, start=-ALL, end=ALL, ranges=None):
+        """the records of `chrom` (None: the unmapped tail) in file order, at most chunk_records per Chunk.  ranges: sorted, disjoint
+        (start, end) pairs instead of start / end - every record that overlaps any of them, once, in file order"""
         flags = _abi.BAM_RESTART
+        ranges = self._ranges(ranges)
         while True:
-            ch = self._read(chrom, start, end, chunk_records, flags)
+            ch = self._read(chrom, start, end, chunk_records, flags, ranges)
             if ch.n:
                 yield ch
             if not ch.more:
                 return
             flags = 0
 
-    def records(self, chrom, start, end):
-        """one Chunk with the records of `chrom` that overlap [start, end): what fetch(chrom, start, end) yields, in its order"""
-        return self._read(chrom, start, end, (1 << 31) - 8192, _abi.BAM_RESTART)
+    def records(self, chrom, start=-ALL, end=ALL, ranges=None):
+        """one Chunk with the records of `chrom` that overlap [start, end): what fetch(chrom, start, end) yields, in its order.
+        ranges: sorted, disjoint (start, end) pairs instead - the records that overlap any of them, each once, in file order"""
+        return self._read(chrom, start, end, (1 << 31) - 8192, _abi.BAM_RESTART, self._ranges(ranges))
 
     def count(self, chrom):
         total, flags = 0, _abi.BAM_RESTART | _abi.BAM_COUNT_ONLY
@@ -418,7 +496,14 @@ def main(argv=None):
     ap.add_argument("--threads", type=int, default=None, help="host threads of the inflate (default: min(16, CPUs))")
     ap.add_argument("--dump-columns", metavar="DIR", default=None, help="write the decoded columns of --chrom (host decode) as DIR/<column>.npy")
     ap.add_argument("--inflate", default="host", choices=["host", "device"], help="where the BGZF blocks are inflated: host threads, or the GPU (device 0) [%(default)s]")
+    ap.add_argument("--idxstats", action="store_true", help="print contig, length, mapped and unmapped reads from the index (the table of samtools idxstats) and stop")
     a = ap.parse_args(argv)
+    if a.idxstats:
+        with BamFile(a.bam, threads=a.threads, index=True) as bf:
+            for (name, mapped, unmapped, _), length in zip(bf.index_statistics(), bf.lengths):
+                print("%s\t%d\t%d\t%d" % (name, length, mapped, unmapped))
+            print("*\t0\t0\t%d" % (bf.no_coordinate or 0))
+        return 0
     ctx = None
     if a.inflate == "device":
         from . import engine

@@ -34,7 +34,10 @@ class Regions:
 
     def for_task(self, chrom, t0, t1):
         """the regions of task [chrom, t0, t1), in order: `t0 <= b0 < t1 or b0 <= t0 < b1` (load_bed :719-724) -> int64 (k, 2), k may
-        be 0 - also for a chromosome the BED does not name: with a BED a task without regions passes no read"""
+        be 0 - also for a chromosome the BED does not name: with a BED a task without regions passes no read.  t0 / t1 may be the
+        fractional bounds of call.cut_tasks_index: the comparison is Python's of an int with a float (exact below 2^53, where every
+        coordinate lies), as the reference applies it to its float task list"""
+        t0, t1 = (float(t) if isinstance(t, float) else int(t) for t in (t0, t1))
         a = self.by_chrom.get(chrom)
         if a is None or len(a) == 0:
             return np.zeros((0, 2), np.int64)

@@ -16,6 +16,7 @@ Nothing here loops in Python over records, signatures or supports: only over tas
 The text is the VCF BODY: the records of main script :1208-1237 in its order.  The header stays the driver's (DESIGN.md
 section 11)."""
 import dataclasses
+import math
 import os
 import time
 from dataclasses import dataclass, field
@@ -46,8 +47,8 @@ class CallParams:
 def cut_tasks(length, batch):
     """the task regions of a contig of `length` bases with -b `batch`: [(start, end)] as main_ctrl cuts them - one task for a contig
     shorter than the batch, else int(length / batch) full ones and the rest.  (The reference also shrinks the batch of a contig
-    that holds many reads, from the index statistics: a matter of load balance - the calls do not depend on the cut, except with
-    include_bed: a task's reads are tested against the regions of THAT task only, see bed.py.)"""
+    that holds many reads, from the index statistics - that cut is cut_tasks_index: a matter of load balance - the calls do not
+    depend on the cut, except with include_bed: a task's reads are tested against the regions of THAT task only, see bed.py.)"""
     if batch <= 0:
         raise ValueError("batch must be positive")
     if length < batch:
@@ -56,6 +57,66 @@ def cut_tasks(length, batch):
     if tasks[-1][1] < length:
         tasks.append((tasks[-1][1], length))
     return tasks
+
+
+def cut_tasks_index(stats, lengths, batch, threads):
+    """The reference's task cut from the index statistics (main_ctrl, main script :1022-1044) -> [(contig, start, end)] in the order
+    of `stats`.  stats: [(contig, mapped, ...)] for every contig of the header (BamFile.index_statistics); lengths: {contig: bases};
+    batch: -b; threads: -t.  A contig that holds more than total_mapped / threads / 10 mapped reads is cut into int(mapped / unit) + 1
+    parts of a FRACTIONAL size, and the bounds stay the floats the reference's running sum makes them: pos can fall a rounding error
+    short of the length, and the sliver task that follows is the reference's too.  Every operation below is the reference's, in
+    its order, on Python numbers - nothing is simplified."""
+    tasks = []
+    total_mapped = 0
+    for i in stats:
+        total_mapped += i[1]
+    mapped_unit = total_mapped / threads / 10
+    for i in stats:
+        local_ref_len = lengths[i[0]]
+        if total_mapped == 0 or i[1] <= mapped_unit:
+            batch_size = batch
+        else:
+            batch_size = local_ref_len / (int(i[1] / mapped_unit) + 1)
+        if local_ref_len < batch_size:
+            tasks.append((i[0], 0, local_ref_len))
+        else:
+            pos = 0
+            task_round = int(local_ref_len / batch_size)
+            for j in range(task_round):
+                tasks.append((i[0], pos, pos + batch_size))
+                pos += batch_size
+            if pos < local_ref_len:
+                tasks.append((i[0], pos, local_ref_len))
+    return tasks
+
+
+def task_bounds(t0, t1):
+    """the records a task [t0, t1) owns, in integers: those that START in [ceil(t0), ceil(t1)) - Python's comparison of an int with a
+    float bound (`start >= t0`, `start < t1`), which is what the reference's gate applies.  (What pysam's fetch does with a fractional
+    bound cannot be observed here: see DESIGN.md section 28, open point.)"""
+    return math.ceil(t0), math.ceil(t1)
+
+
+def task_ranges(bf, chrom, regs, t0, t1):
+    """What a task with the BED regions `regs` (bed.Regions.for_task) reads of [t0, t1) (integers): [] - nothing - for an empty list,
+    else the union of the regions clipped to the task as sorted, disjoint (start, end) pairs.  A region written with end < start
+    contributes its hull, one base wider.  Neighbours whose starting positions the index puts into the same or the adjacent BGZF block
+    are merged: seeking between them would save no block.  A superset of what the gates pass - they still decide."""
+    cut = []
+    for b0, b1 in np.asarray(regs, np.int64).reshape(-1, 2).tolist():
+        lo, hi = (b0, b1) if b0 <= b1 else (b1 - 1, b0 + 1)
+        lo, hi = max(lo, t0), min(hi, t1)
+        if lo < hi:
+            cut.append((lo, hi))
+    out, last = [], 0                                         # last: the block in which the range merged last starts (neighbour by neighbour,
+    for lo, hi in sorted(cut):                                # so a chain of adjacent starts becomes one range)
+        block = bf.index_block(chrom, lo)                     # (-1, "nothing from here on", merges as well: a superset is safe)
+        if out and (lo <= out[-1][1] or block - last <= 1):
+            out[-1] = (out[-1][0], max(out[-1][1], hi))
+        else:
+            out.append((lo, hi))
+        last = block
+    return out
 
 
 DEFAULT_GATES = "device"        # where call_bam evaluates the task gates without a BED (DESIGN.md section 19: decided by its measurement)
@@ -113,10 +174,11 @@ class _Shim:
 
 
 def call_bam(bam, reference, params, ctx=None, chroms=None, batch=10_000_000, report_readid=False, ignore_sequence=False, threads=None, svid=None,
-             as_bytes=False, timings=None, tra_gt=None, include_bed=None, gates=None, reads_table=None, sigs_dir=None, inflate=None):
+             as_bytes=False, timings=None, tra_gt=None, include_bed=None, gates=None, reads_table=None, sigs_dir=None, inflate=None, index=None, task_cut=None,
+             cut_threads=16, read_stats=None):
     """-> (VCF body text, svid counters [INS, DEL, BND, DUP, INV]).
 
-    bam        a path or an open bam.BamFile (coordinate-sorted; no index is needed)
+    bam        a path or an open bam.BamFile (coordinate-sorted; no index is needed, one beside the file is used - see `index`)
     reference  a fasta.Reference or {contig: sequence}: the REF bases
     params     a CallParams, or a columns.Params (the gates then take the reference's defaults)
     ctx        an engine.Context (default: one on device 0 for the call); its pool, name pool and sequence pool are reset
@@ -141,7 +203,21 @@ def call_bam(bam, reference, params, ctx=None, chroms=None, batch=10_000_000, re
                returned text and svid do not depend on it.  None: no files.
     inflate    "host" or "device": where the BGZF blocks are inflated (None: DEFAULT_INFLATE).  device: on `ctx`, one wavefront per
                block; a BamFile that was handed in gets the context for the call and its previous setting back
-               at the end.  Same text either way."""
+               at the end.  Same text either way.
+    index      for a path: None - the .bai beside the file is loaded when there is one; a path - that index; False - none
+               (bam.BamFile's `index`).  An open BamFile comes with what it has.  With an index every task's read starts at its
+               linear-index entry, and under include_bed - unless tra_gt="alignments" fills the alignment table, which needs every
+               record - a task reads only the union of its regions (task_ranges), and nothing when it has none.  The gates are
+               unchanged and decide; the text does not depend on the index.
+    task_cut   None or "uniform": cut_tasks, every contig by `batch`.  "index": cut_tasks_index, the reference's cut from the index
+               statistics with `cut_threads` as its -t - under include_bed the cut decides which reads survive, and this is the cut
+               cuteSV makes.  ValueError without an index.
+    read_stats a dict that receives what the tasks' reads cost: compressed_bytes and n_records summed over the tasks, task_records - the
+               records each task read, in task order."""
+    if task_cut not in (None, "uniform", "index"):
+        raise ValueError("task_cut must be None, 'uniform' or 'index', not %r" % (task_cut,))
+    if task_cut == "index" and not (getattr(bam, "has_index", False) if hasattr(bam, "references") else index is not False):
+        raise ValueError("task_cut='index' needs a BAM index (.bai): this reader has none")
     from . import aln, bam as bam_mod, bed as bed_mod, engine, extract, reads as reads_mod, rebuild, vcf
     if reads_table is None:
         reads_table = DEFAULT_READS_TABLE
@@ -158,7 +234,7 @@ def call_bam(bam, reference, params, ctx=None, chroms=None, batch=10_000_000, re
     mode = tra_gt_mode(cp.resolve.genotype, tra_gt)
     p = dataclasses.replace(cp.resolve, genotype_tra=(mode == "reads_table"))
     own_bam = not isinstance(bam, bam_mod.BamFile)
-    bf = bam_mod.BamFile(bam, threads=threads) if own_bam else bam
+    bf = bam_mod.BamFile(bam, threads=threads, index=index) if own_bam else bam
     own_ctx = ctx is None
     if own_ctx:
         ctx = engine.Context(0)
@@ -171,6 +247,8 @@ def call_bam(bam, reference, params, ctx=None, chroms=None, batch=10_000_000, re
             timings[key] = timings.get(key, 0.0) + (now - clock[0]) * 1e3
         clock[0] = now
     try:
+        if task_cut == "index" and not bf.has_index:
+            raise ValueError("task_cut='index' needs a BAM index (.bai): none was found for %s" % bf.path)
         restore = (bf.set_inflate(ctx if inflate == "device" else None),)
         # the chromosome table in name order: a chromosome's index is its name rank, the numbering of rebuild._segments and of a TRA row's mate
         names = sorted(bf.references)
@@ -190,15 +268,29 @@ def call_bam(bam, reference, params, ctx=None, chroms=None, batch=10_000_000, re
         if reads_dev:
             reads_mod.reset(ctx, n_chrom)
         tables = []                                           # reads_table="host", per task: (chromosome index, its reads-table columns)
+        by_contig = {}
+        if task_cut == "index":
+            if not isinstance(cut_threads, (int, np.integer)) or cut_threads < 1:
+                raise ValueError("cut_threads must be a positive integer, not %r" % (cut_threads,))
+            for c, t0, t1 in cut_tasks_index(bf.index_statistics(), length, batch, int(cut_threads)):
+                by_contig.setdefault(c, []).append((t0, t1))
+        # (contigs are visited in name order, which keeps the ordering contracts of the appends; with an index the seeks between them are free)
+        skip = regions is not None and bf.has_index and mode != "alignments"      # a task reads its regions only: the alignment table needs every record
         for c in wanted:
-            for t0, t1 in cut_tasks(length[c], batch):
-                r = extract.task_to_pool(ctx, bf, c, t0, t1, crank, *cp.pipe_args(), seg_of["INS"] + crank[c], seg_of["DEL"] + crank[c], seg_base, None,
+            for t0, t1 in (by_contig.get(c, []) if task_cut == "index" else cut_tasks(length[c], batch)):
+                regs = None if regions is None else regions.for_task(c, t0, t1)                # (the bounds as they are: floats under the index cut)
+                i0, i1 = task_bounds(t0, t1)
+                r = extract.task_to_pool(ctx, bf, c, i0, i1, crank, *cp.pipe_args(), seg_of["INS"] + crank[c], seg_of["DEL"] + crank[c], seg_base, None,
                                          name_pool=True, seq_pool=True, aln=(mode == "alignments"), gates=gates, reads="device" if reads_dev else "host",
-                                         bed_regions=None if regions is None else regions.for_task(c, t0, t1))
+                                         bed_regions=regs, ranges=task_ranges(bf, c, regs, i0, i1) if skip else None)
                 if p.genotype and not reads_dev:
                     tables.append((crank[c], r))
                 if timings is not None:
                     timings["ms_inflate"] = timings.get("ms_inflate", 0.0) + bf.last_stats["ms_inflate"]      # (a task reads its records in one call)
+                if read_stats is not None:
+                    read_stats["compressed_bytes"] = read_stats.get("compressed_bytes", 0) + bf.last_stats["compressed_bytes"]
+                    read_stats["n_records"] = read_stats.get("n_records", 0) + r["n_records"]
+                    read_stats.setdefault("task_records", []).append(r["n_records"])
         lap("ms_tasks")
         if rebuild.pool_rows(ctx) == 0:
             if sigs_dir is not None:                           # (no signature at all: five empty files, as the reference's open(..., "w") leaves them)

@@ -1,6 +1,7 @@
 """cuteSV's command line on this project's chain:
 
     python -m cutesv_amd BAM REF OUT.vcf WORK_DIR [cuteSV's flags] [--reads_table {host,device}] [--tra_gt MODE] [--inflate {host,device}]
+                         [--task_cut {index,uniform}]
 
 `parse_args` accepts every option of cuteSV v2.1.4 under the same short and long spellings, with the same destination, type
 and default, so a command line written for cuteSV runs here unchanged; `main` maps them onto call.call_bam and writes a complete
@@ -9,10 +10,11 @@ DUP.sigs, INV.sigs and TRA.sigs, made on the device (rebuild.write_sigs); withou
 the end, as cuteSV's cleanup removes its own.
 
 What differs from cuteSV, on purpose:
-  * The extraction tasks are call.cut_tasks' uniform cut of every contig by -b.  cuteSV shrinks the batch of a contig that holds
-    many reads, from the BAM index statistics.  The calls do not depend on the cut - except with -include_bed, where a task's
-    reads are tested against the regions of that task only: there the calls can differ from cuteSV's on contigs whose batch it
-    would have shrunk.  (That cut needs a .bai reader, which this project does not have.)
+  * The extraction tasks: with a .bai beside the BAM file (cuteSV cannot run without one) they are cuteSV's own cut from the index
+    statistics (call.cut_tasks_index with -t; --task_cut index).  Without one - or with --task_cut uniform -
+    they are call.cut_tasks' uniform cut of every contig by -b, and one line on stderr says so.  The calls do not depend on the
+    cut - except with -include_bed, where a task's reads are tested against the regions of that task only: there the uniform cut
+    can differ from cuteSV's on contigs whose batch it would have shrunk.
   * reads.sigs is not written (its row order in cuteSV depends on which worker process wrote which task).
   * Force calling (-Ivcf) is not available, as in cuteSV v2.1.4 itself.
   * --read_range is accepted and unused, as on cuteSV's calling path.  -t sizes the BAM reader's inflate threads.
@@ -89,17 +91,18 @@ def _parser():
 
 
 def _own_parser():
-    """the three options cuteSV does not have; parsed apart (split_own), so that they shadow no abbreviation of a cuteSV flag"""
+    """the four options cuteSV does not have; parsed apart (split_own), so that they shadow no abbreviation of a cuteSV flag"""
     from . import call
     ap = argparse.ArgumentParser(add_help=False, allow_abbrev=False)
     ap.add_argument("--reads_table", default=None, choices=["host", "device"])
     ap.add_argument("--tra_gt", default=None, choices=list(call.TRA_GT_MODES))
     ap.add_argument("--inflate", default=None, choices=["host", "device"])
+    ap.add_argument("--task_cut", default=None, choices=["index", "uniform"])
     return ap
 
 
 def split_own(argv):
-    """-> (namespace of --reads_table / --tra_gt / --inflate, argv without them)"""
+    """-> (namespace of --reads_table / --tra_gt / --inflate / --task_cut, argv without them)"""
     return _own_parser().parse_known_args(list(argv))
 
 
@@ -149,9 +152,14 @@ def main(argv=None):
     try:
         contigs = list(zip(bf.references, bf.lengths))
         _log("%d contigs in %s" % (len(contigs), a.input))
+        task_cut = own.task_cut
+        if task_cut is None:
+            task_cut = "index" if bf.has_index else "uniform"
+            if not bf.has_index:
+                _log("no BAM index (.bai) beside %s: the tasks are the uniform cut by -b, not cuteSV's cut from the index statistics" % a.input)
         body, svid = call.call_bam(bf, fasta.Reference(a.reference), call_params(a), batch=a.batches, report_readid=a.report_readid,
                                    ignore_sequence=a.ignore_sequence, as_bytes=True, timings=timings, tra_gt=tra_gt, include_bed=a.include_bed,
-                                   reads_table=own.reads_table, sigs_dir=sigs_dir, inflate=own.inflate)
+                                   reads_table=own.reads_table, sigs_dir=sigs_dir, inflate=own.inflate, task_cut=task_cut, cut_threads=a.threads)
     finally:
         bf.close()
     for key, ms in timings.items():

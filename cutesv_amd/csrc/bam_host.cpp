@@ -8,7 +8,9 @@
 //   BAM         = "BAM\1", l_text, text, n_ref, {l_name, name, l_ref} * n_ref, then records
 //   record      = block_size, then block_size bytes: refID pos l_read_name mapq bin n_cigar_op flag l_seq next_refID
 //                 next_pos tlen (32 bytes), read_name, cigar (u32 * n_cigar_op), seq ((l_seq + 1) / 2), qual (l_seq), aux
-// No index is used: a region is a forward scan over the sorted records with an early exit.  What goes to the device per
+// Without an index a region is a forward scan over the sorted records with an early exit.  With one (csv_bam_index_load,
+// bai_index.h) the scan starts at the linear-index entry of the region's first window; the index moves the
+// starting point and nothing else.  What goes to the device per
 // record is the slim image {32 fixed bytes, CIGAR words, aux bytes}; the read name and the 4-bit sequence stay in a host
 // buffer; the qualities are dropped.
 #include <stdint.h>
@@ -29,6 +31,7 @@
 #include <vector>
 
 #include "../../include/cutesv_hip.h"
+#include "bai_index.h"
 
 namespace {
 
@@ -44,6 +47,7 @@ struct Block { i64 coff; int32_t csize, hdr; uint32_t isize; i64 uoff; };      /
 
 constexpr i64 SLIM_ALIGN = 16;               // a slim record starts 16-byte aligned: its CIGAR words (at + 32) are too
 constexpr int REFILL_BLOCKS = 256;           // BGZF blocks inflated per refill of the window (<= 16 MiB inflated)
+constexpr int AHEAD_STEP_BLOCKS = 16;        // ... past the guessed end of an indexed region
 constexpr int MAX_WINDOW_BLOCKS = 16384;     // ... on the device route at most (csv_bam_set_inflate; <= 1 GiB inflated)
 
 }  // namespace
@@ -52,6 +56,7 @@ struct csv_bam {
     int            fd = -1;
     const uint8_t* map = nullptr;
     i64            fsize = 0;
+    std::string    path;
     int            threads = 1;
     std::string    err;
     std::vector<Block> blocks;
@@ -66,6 +71,7 @@ struct csv_bam {
     const uint8_t*       win_p = nullptr;    // the window's bytes: win.data(), or the page-locked window of the device route
     i64                  win_n = 0;
     i64                  win_u0 = 0;
+    size_t               win_b1 = 0;         // the window holds the blocks up to this one (exclusive)
     // the device route (csv_bam_set_inflate): the context, blocks per window, the page-locked window, the tables of one call
     csv_ctx*             dev = nullptr;
     int                  window_blocks = REFILL_BLOCKS;
@@ -85,6 +91,14 @@ struct csv_bam {
     // contig that begins at or after hint_beg starts its scan there
     uint32_t             hint_key = 0;
     i64                  hint_beg = 0, hint_at = -1;
+    // the index (csv_bam_index_load): the scan of a region starts at its linear-index entry.  seek_key: the contig the running scan
+    // was positioned in by the index - the first record it sees of that contig is not the contig's first
+    bool                 has_index = false;
+    bai::Index           index;
+    bool                 seeked = false;
+    uint32_t             seek_key = 0;
+    i64                  ahead_block = -1;   // with an index: the block where the running region is guessed to end (-1: no guess)
+    size_t               range_i = 0;        // csv_bam_read_ranges: the range the scan is in
     // the chunk handed out last
     std::vector<uint8_t> slim, host;
     std::vector<i64>     rec_off, host_off;
@@ -155,19 +169,22 @@ bool inflate_block(const csv_bam* b, const Block& k, uint8_t* dst)
 // the window becomes the inflated blocks [b0, b1), on the device: the mapped file from the first block's header to the last
 // block's trailer is the `comp` of one csv_bgzf_inflate (the payloads lie in it where they are: nothing is gathered), the bytes land
 // in the page-locked window, and every block the device reports is inflated again by inflate_block, whose verdict stands
-int load_window_device(csv_bam* b, size_t b0, size_t b1)
+int load_window_device(csv_bam* b, size_t b0, size_t b1, size_t bn, i64 keep)
 {
     const double t0 = now_ms();
+    const i64 keep_at = b->blocks[b0].uoff - b->win_u0;      // (only with keep > 0: where the kept bytes lie in the old window)
     b->win_n = 0;
-    b->win_u0 = b->blocks[b0].uoff;
-    const i64 bytes = (b1 < b->blocks.size() ? b->blocks[b1].uoff : b->utotal) - b->win_u0;
+    const i64 bytes = (b1 < b->blocks.size() ? b->blocks[b1].uoff : b->utotal) - b->blocks[b0].uoff;
     if (bytes > b->pin_cap) {
-        if (b->pin) { csv_host_free(b->pin); b->pin = nullptr; b->pin_cap = 0; }
         void* p = nullptr;
         const i64 want = bytes + bytes / 4 + 4096;
         if (csv_host_alloc(want, &p) != CSV_OK) return fail(b, CSV_E_NOMEM, "%scannot page-lock an inflate window of %lld bytes", "", (long long)want);
+        if (keep > 0) memcpy(p, b->pin + keep_at, (size_t)keep);
+        if (b->pin) csv_host_free(b->pin);
         b->pin = (uint8_t*)p; b->pin_cap = want;
-    }
+    } else if (keep > 0 && keep_at > 0) memmove(b->pin, b->pin + keep_at, (size_t)keep);
+    b->win_u0 = b->blocks[b0].uoff;
+    b0 = bn;                                                 // the blocks in front of bn are the kept bytes: inflated already
     const size_t n = b1 - b0;
     b->d_in_off.resize(n); b->d_in_len.resize(n); b->d_out_off.resize(n); b->d_out_len.resize(n); b->d_crc.resize(n); b->d_status.resize(n);
     const i64 base = b->blocks[b0].coff, comp_bytes = b->blocks[b1 - 1].coff + b->blocks[b1 - 1].csize - base;
@@ -178,7 +195,7 @@ int load_window_device(csv_bam* b, size_t b0, size_t b1)
         b->d_crc[j] = rd_u32(b->map + k.coff + k.csize - 8);
     }
     double ms = 0;
-    const int rc = csv_bgzf_inflate(b->dev, b->map + base, comp_bytes, (int32_t)n, b->d_in_off.data(), b->d_in_len.data(), b->d_out_off.data(), b->d_out_len.data(),
+    const int rc = n == 0 ? CSV_OK : csv_bgzf_inflate(b->dev, b->map + base, comp_bytes, (int32_t)n, b->d_in_off.data(), b->d_in_len.data(), b->d_out_off.data(), b->d_out_len.data(),
                                     b->d_crc.data(), b->pin, bytes, 0, b->d_status.data(), &ms);
     if (rc) return fail(b, rc, "the device inflate failed: %s", csv_last_error(b->dev));
     b->ms_kernels += ms;
@@ -189,22 +206,25 @@ int load_window_device(csv_bam* b, size_t b0, size_t b1)
         if (!inflate_block(b, b->blocks[b0 + j], b->pin + b->d_out_off[j])) bad = (i64)(b0 + j);
     }
     for (size_t j = b0; j < b1; j++) b->compressed += b->blocks[j].csize;
-    b->inflated += bytes;
+    b->inflated += bytes - keep;
     b->ms_inflate += now_ms() - t0;
     if (bad >= 0) return fail(b, CSV_E_INVALID, "%sBGZF block at byte %lld does not inflate (or fails its CRC)", "", (long long)b->blocks[(size_t)bad].coff);
-    b->win_p = b->pin; b->win_n = bytes;
+    b->win_p = b->pin; b->win_n = bytes; b->win_b1 = b1;
     return CSV_OK;
 }
 
-// the window becomes the inflated blocks [b0, b1)
-int load_window(csv_bam* b, size_t b0, size_t b1)
+// the window becomes the inflated blocks [b0, b1).  keep > 0: the window already holds the bytes of the blocks [b0, bn) at its end
+// (the scan moved on inside it): they are moved to the front and only [bn, b1) is inflated; else bn == b0
+int load_window(csv_bam* b, size_t b0, size_t b1, size_t bn, i64 keep)
 {
-    if (b->dev) return load_window_device(b, b0, b1);
+    if (b->dev) return load_window_device(b, b0, b1, bn, keep);
     const double t0 = now_ms();
+    const i64 bytes = (b1 < b->blocks.size() ? b->blocks[b1].uoff : b->utotal) - b->blocks[b0].uoff;
+    if (keep > 0) memmove(b->win.data(), b->win.data() + (b->blocks[b0].uoff - b->win_u0), (size_t)keep);      // (in place: no fresh pages per refill)
+    b->win.resize((size_t)bytes);
     b->win_n = 0;
     b->win_u0 = b->blocks[b0].uoff;
-    const i64 bytes = (b1 < b->blocks.size() ? b->blocks[b1].uoff : b->utotal) - b->win_u0;
-    b->win.resize((size_t)bytes);
+    b0 = bn;
     std::atomic<size_t> next(b0);
     std::atomic<i64> bad(-1);
     auto work = [&] {
@@ -221,10 +241,10 @@ int load_window(csv_bam* b, size_t b0, size_t b1)
     work();
     for (auto& t : th) t.join();
     for (size_t j = b0; j < b1; j++) b->compressed += b->blocks[j].csize;
-    b->inflated += bytes;
+    b->inflated += bytes - keep;
     b->ms_inflate += now_ms() - t0;
     if (bad.load() >= 0) return fail(b, CSV_E_INVALID, "%sBGZF block at byte %lld does not inflate (or fails its CRC)", "", (long long)b->blocks[(size_t)bad.load()].coff);
-    b->win_p = b->win.data(); b->win_n = bytes;
+    b->win_p = b->win.data(); b->win_n = bytes; b->win_b1 = b1;
     return CSV_OK;
 }
 
@@ -245,8 +265,18 @@ const uint8_t* at(csv_bam* b, i64 u, i64 need, int* rc)
     if (u < b->win_u0 || u + need > b->win_u0 + b->win_n) {
         const size_t b0 = block_of(b, u);
         size_t b1 = std::min(b->blocks.size(), b0 + (size_t)(b->dev ? b->window_blocks : REFILL_BLOCKS));
+        if (b->ahead_block >= 0)                             // an indexed region: up to where it is guessed to end, then in small steps
+            b1 = std::min(b1, (i64)b0 <= b->ahead_block ? (size_t)b->ahead_block + 1 : b0 + AHEAD_STEP_BLOCKS);
         while (b1 < b->blocks.size() && b->blocks[b1].uoff < u + need) b1++;
-        *rc = load_window(b, b0, b1);
+        // the scan moved on inside the window: the blocks from b0 to the window's end are there already and are not inflated again
+        size_t bn = b0;
+        i64 keep = 0;
+        if (b->win_n > 0 && u >= b->win_u0 && u < b->win_u0 + b->win_n && b->win_b1 > b0) {
+            bn = b->win_b1;
+            keep = b->win_u0 + b->win_n - b->blocks[b0].uoff;
+            if (b1 < bn) b1 = bn;
+        }
+        *rc = load_window(b, b0, b1, bn, keep);
         if (*rc) return nullptr;
     }
     return b->win_p + (u - b->win_u0);
@@ -305,6 +335,7 @@ int csv_bam_open(const char* path, int threads, csv_bam** out, char* err, int er
     *out = nullptr;
     csv_bam* b = new csv_bam;
     b->threads = std::max(1, std::min(threads, 64));
+    b->path = path;
     int rc = CSV_OK;
     struct stat st;
     b->fd = open(path, O_RDONLY);
@@ -367,9 +398,49 @@ int csv_bam_inflate_stats(const csv_bam* b, int64_t* device_blocks, int64_t* fal
     return CSV_OK;
 }
 
-int csv_bam_read(csv_bam* b, int32_t refid, int64_t beg, int64_t end, int64_t max_records, int32_t flags, csv_bam_chunk* out)
+}  // extern "C"
+
+namespace {
+
+// the block a virtual offset of the (validated) index points into -> the offset in the inflated stream
+i64 stream_offset(const csv_bam* b, uint64_t voff, size_t* block)
 {
-    if (!b || !out || max_records < 1) return CSV_E_INVALID;
+    const i64 coff = (i64)(voff >> 16);
+    size_t lo = 0, hi = b->blocks.size();
+    while (hi - lo > 1) { const size_t m = (lo + hi) / 2; if (b->blocks[m].coff <= coff) lo = m; else hi = m; }
+    if (block) *block = lo;
+    return b->blocks[lo].uoff + (i64)(voff & 0xffff);
+}
+
+int voff_check(void* user, uint64_t voff)
+{
+    const csv_bam* b = (const csv_bam*)user;
+    const i64 coff = (i64)(voff >> 16);
+    if (coff == b->fsize) return (voff & 0xffff) ? 2 : 0;     // "behind the last block": where a writer stands after its end-of-file block
+    size_t k;
+    stream_offset(b, voff, &k);
+    if (b->blocks[k].coff != coff) return 1;
+    return (voff & 0xffff) > b->blocks[k].isize ? 2 : 0;
+}
+
+// the index positions the scan for range [beg, end) of contig `key`: the cursor moves forward only (never behind `floor`);
+// -> false: the index says that no record overlaps any window from beg's on
+bool index_seek(csv_bam* b, uint32_t key, i64 beg, i64 end, i64 floor)
+{
+    uint64_t v;
+    if (!bai::start_offset(b->index, (int32_t)key, beg, &v)) return false;
+    const i64 u = (v >> 16) == (uint64_t)b->fsize ? b->utotal : stream_offset(b, v, nullptr);
+    b->cur = u > floor ? u : floor;
+    b->seeked = true; b->seek_key = key;                     // (also from `floor`, a hint: the scan that set it was positioned by the index too)
+    size_t k = b->blocks.size() - 1;
+    if (bai::stop_guess(b->index, (int32_t)key, end, &v) && (v >> 16) != (uint64_t)b->fsize) stream_offset(b, v, &k);
+    b->ahead_block = (i64)k;
+    return true;
+}
+
+// csv_bam_read / csv_bam_read_ranges: the records of contig `refid` that overlap one of the sorted, disjoint ranges, in file order
+int read_ranges(csv_bam* b, int32_t refid, size_t nr, const int64_t* rbeg, const int64_t* rend, int64_t max_records, int32_t flags, csv_bam_chunk* out)
+{
     const double t0 = now_ms();
     memset(out, 0, sizeof *out);
     b->ms_inflate = 0; b->inflated = b->compressed = 0;
@@ -377,18 +448,30 @@ int csv_bam_read(csv_bam* b, int32_t refid, int64_t beg, int64_t end, int64_t ma
     b->slim.clear(); b->host.clear(); b->rec_off.clear(); b->host_off.clear(); b->rec_len.clear();
     const bool count_only = (flags & CSV_BAM_COUNT_ONLY) != 0;
     const uint32_t key = (uint32_t)refid;
+    const bool indexed = b->has_index && refid >= 0 && refid < b->n_ref;
+    const i64 beg = rbeg[0];
+    size_t ri = b->range_i < nr ? b->range_i : nr - 1;
+    bool done = false;                                       // the index says that nothing is left to read
     if (flags & CSV_BAM_RESTART) {                           // start of the contig if it was seen, else the last contig start before it
-        b->cur = b->first_rec;
-        auto it = b->contig_at.upper_bound(key);
-        if (it != b->contig_at.begin()) { --it; b->cur = it->second; }
-        if (b->hint_at >= 0 && b->hint_key == key && beg >= b->hint_beg) b->cur = b->hint_at;
+        ri = 0;
+        b->seeked = false;
+        b->ahead_block = -1;
+        const i64 hint = b->hint_at >= 0 && b->hint_key == key && beg >= b->hint_beg ? b->hint_at : -1;
+        if (indexed) {                                       // the linear-index entry of the first window, or the hint when that lies further on
+            if (!index_seek(b, key, rbeg[0], rend[0], hint >= 0 ? hint : 0)) done = true;
+        } else {
+            b->cur = b->first_rec;
+            auto it = b->contig_at.upper_bound(key);
+            if (it != b->contig_at.begin()) { --it; b->cur = it->second; }
+            if (hint >= 0) b->cur = hint;
+        }
         b->hint_at = -1;
     }
     const bool set_hint = (flags & CSV_BAM_RESTART) != 0;
     i64 n = 0;
     bool more = false;
     int rc = CSV_OK;
-    for (;;) {
+    while (!done) {
         const uint8_t* p = at(b, b->cur, 4, &rc);
         if (rc) return rc;
         if (!p) {
@@ -402,15 +485,25 @@ int csv_bam_read(csv_bam* b, int32_t refid, int64_t beg, int64_t end, int64_t ma
         if (rc) return rc;
         if (!p) return fail(b, CSV_E_INVALID, "%sthe file ends inside a record (at inflated byte %lld)", "", (long long)b->cur);
         const uint32_t rkey = (uint32_t)rd_i32(p);
-        if (!b->contig_at.count(rkey)) b->contig_at[rkey] = b->cur;
-        if (!b->scanned_any || rkey > b->scanned_key) { b->scanned_key = rkey; b->scanned_any = true; }
+        if (!(b->seeked && rkey == b->seek_key)) {           // (a scan the index positioned does not see the first record of its contig)
+            if (!b->contig_at.count(rkey)) b->contig_at[rkey] = b->cur;
+            if (!b->scanned_any || rkey > b->scanned_key) { b->scanned_key = rkey; b->scanned_any = true; }
+        }
         if (rkey > key) break;                               // the next contig (the unmapped tail sorts last): not consumed
         if (rkey < key) { b->cur += 4 + bs; continue; }
         const i64 pos = rd_i32(p + 4), l_name = p[8], n_cig = rd_u16(p + 12), l_seq = rd_u32(p + 16);
         const i64 fixed_to_aux = 32 + l_name + 4 * n_cig + (l_seq + 1) / 2 + l_seq;
         if (fixed_to_aux > bs) return fail(b, CSV_E_INVALID, "%srecord fields exceed its block_size at inflated byte %lld", "", (long long)b->cur);
-        if (pos >= end) break;                               // sorted: nothing later can start before `end`
-        if (pos < beg) {                                     // overlaps the region only if it reaches past `beg`
+        if (pos >= rend[ri]) {                               // sorted: nothing later can start before this range's end - on to the next range
+            while (ri < nr && pos >= rend[ri]) ri++;
+            if (ri == nr) { ri = nr - 1; break; }
+            if (indexed) {
+                if (!index_seek(b, key, rbeg[ri], rend[ri], b->cur)) break;
+                continue;                                    // (the cursor may have moved: the record is read again)
+            }
+        }
+        if (pos < rbeg[ri]) {                                // overlaps the range only if it reaches past its begin (and then no later one: they are disjoint)
+            const i64 beg = rbeg[ri];
             i64 span = 0;
             const uint8_t* cg = p + 32 + l_name;
             for (i64 k = 0; k < n_cig; k++) {
@@ -421,7 +514,9 @@ int csv_bam_read(csv_bam* b, int32_t refid, int64_t beg, int64_t end, int64_t ma
             if (pos + (span ? span : 1) <= beg) { b->cur += 4 + bs; continue; }
         }
         if (n == max_records) { more = true; break; }
-        if (n == 0 && set_hint) { b->hint_key = key; b->hint_beg = beg; b->hint_at = b->cur; }
+        // (every record in front of this one ends at or before the begin of the range it is emitted for: those tested against an
+        // earlier range end before that range's begin, those the index jumped over overlap no window from this range's on)
+        if (n == 0 && set_hint) { b->hint_key = key; b->hint_beg = rbeg[ri]; b->hint_at = b->cur; }
         if (!count_only) {
             const i64 aux_len = bs - fixed_to_aux, slim_len = 32 + 4 * n_cig + aux_len;
             const size_t s0 = b->slim.size();
@@ -443,6 +538,7 @@ int csv_bam_read(csv_bam* b, int32_t refid, int64_t beg, int64_t end, int64_t ma
         out->record_bytes += 4 + bs;
         b->cur += 4 + bs;
     }
+    b->range_i = ri;
     b->host_off.push_back((i64)b->host.size());
     out->n_records = n; out->more = more ? 1 : 0;
     out->slim = b->slim.data(); out->slim_bytes = (int64_t)b->slim.size();
@@ -450,6 +546,97 @@ int csv_bam_read(csv_bam* b, int32_t refid, int64_t beg, int64_t end, int64_t ma
     out->host = b->host.data(); out->host_bytes = (int64_t)b->host.size(); out->host_off = b->host_off.data();
     out->inflated_bytes = b->inflated; out->compressed_bytes = b->compressed;
     out->ms_inflate = b->ms_inflate; out->ms_frame = now_ms() - t0 - b->ms_inflate;
+    return CSV_OK;
+}
+
+bool read_file(const std::string& path, std::vector<uint8_t>* data)
+{
+    FILE* f = fopen(path.c_str(), "rb");
+    if (!f) return false;
+    uint8_t buf[1 << 16];
+    size_t k;
+    while ((k = fread(buf, 1, sizeof buf, f)) > 0) data->insert(data->end(), buf, buf + k);
+    const bool ok = !ferror(f);
+    fclose(f);
+    return ok;
+}
+
+}  // namespace
+
+extern "C" {
+
+int csv_bam_read(csv_bam* b, int32_t refid, int64_t beg, int64_t end, int64_t max_records, int32_t flags, csv_bam_chunk* out)
+{
+    if (!b || !out || max_records < 1) return CSV_E_INVALID;
+    b->range_i = 0;
+    return read_ranges(b, refid, 1, &beg, &end, max_records, flags, out);
+}
+
+int csv_bam_read_ranges(csv_bam* b, int32_t refid, int32_t n_ranges, const int64_t* beg, const int64_t* end, int64_t max_records, int32_t flags, csv_bam_chunk* out)
+{
+    if (!b || !out || max_records < 1 || n_ranges < 1 || !beg || !end) return CSV_E_INVALID;
+    for (int32_t i = 0; i < n_ranges; i++)
+        if (beg[i] > end[i] || (i && beg[i] < end[i - 1])) return fail(b, CSV_E_INVALID, "%sthe ranges of a read must be sorted and disjoint (range %lld)", "", i);
+    return read_ranges(b, refid, (size_t)n_ranges, beg, end, max_records, flags, out);
+}
+
+int csv_bam_index_load(csv_bam* b, const char* path)
+{
+    if (!b) return CSV_E_INVALID;
+    std::vector<std::string> tries;
+    if (path) tries.push_back(path);
+    else {
+        tries.push_back(b->path + ".bai");
+        if (b->path.size() > 4 && b->path.compare(b->path.size() - 4, 4, ".bam") == 0) tries.push_back(b->path.substr(0, b->path.size() - 4) + ".bai");
+    }
+    for (const std::string& t : tries) {
+        std::vector<uint8_t> data;
+        if (!read_file(t, &data)) continue;
+        bai::Index ix;
+        std::string err;
+        if (!bai::parse(data.data(), data.size(), b->n_ref, t.c_str(), voff_check, b, &ix, &err)) {
+            csv_bam_index_drop(b);                           // a reader whose load failed has no index, whatever it had
+            b->err = err;
+            return CSV_E_INVALID;
+        }
+        b->index = std::move(ix);
+        b->has_index = true;
+        b->hint_at = -1; b->ahead_block = -1;
+        return CSV_OK;
+    }
+    b->err = path ? std::string("cannot read the index ") + path : "no index beside " + b->path + " (" + tries[0] + (tries.size() > 1 ? ", " + tries[1] : "") + ")";
+    return CSV_E_STATE;
+}
+
+int64_t csv_bam_index_block(const csv_bam* b, int32_t refid, int64_t beg)
+{
+    if (!b || !b->has_index || refid < 0 || refid >= b->n_ref) return -2;
+    uint64_t v;
+    if (!bai::start_offset(b->index, refid, beg, &v)) return -1;
+    if ((v >> 16) == (uint64_t)b->fsize) return (int64_t)b->blocks.size() - 1;
+    size_t k;
+    stream_offset(b, v, &k);
+    return (int64_t)k;
+}
+
+int csv_bam_index_drop(csv_bam* b)
+{
+    if (!b) return CSV_E_INVALID;
+    b->index = bai::Index();
+    b->has_index = false;
+    b->hint_at = -1; b->ahead_block = -1; b->seeked = false;
+    return CSV_OK;
+}
+
+int csv_bam_index_stats(const csv_bam* b, int64_t* mapped, int64_t* unmapped, int64_t* n_no_coor)
+{
+    if (!b) return CSV_E_INVALID;
+    if (!b->has_index) return CSV_E_STATE;
+    for (int32_t r = 0; r < b->n_ref; r++) {
+        if (mapped) mapped[r] = (int64_t)b->index.refs[(size_t)r].n_mapped;
+        if (unmapped) unmapped[r] = (int64_t)b->index.refs[(size_t)r].n_unmapped;
+    }
+    if (n_no_coor) *n_no_coor = b->index.has_no_coor ? (int64_t)b->index.n_no_coor : -1;
     return CSV_OK;
 }
 

@@ -729,7 +729,7 @@ def _assemble_device(ctx, chunk, cols, sig, names, seqs, sel, chrom, chrom_rank,
 # ------------------------------------------------------------------------------------ a task's region -> rows of the pool
 def task_to_pool(ctx, bamfile, chrom, task_start, task_end, chrom_rank, sv_size, min_mapq, max_split_parts, min_read_len, min_siglength,
                  merge_del_threshold, merge_ins_threshold, max_size, seg_ins, seg_del, seg_base, read_base, bed_regions=None, name_pool=False, seq_pool=False, aln=False,
-                 gates="host", reads="host"):
+                 gates="host", reads="host", ranges=None):
     """The body of an extraction task without a candidate tuple, a name string or a sequence: the records of the region
     (`bamfile.records`) are decoded on the device, the CIGAR scan appends its signatures to the context's pool from the decoded
     columns (CSV_CG_FROM_BAM | CSV_CG_TO_POOL), the SA tags are parsed there (split_inputs_bam) and the split-read analysis appends
@@ -768,9 +768,16 @@ def task_to_pool(ctx, bamfile, chrom, task_start, task_end, chrom_rank, sv_size,
     context's device-resident reads table (reads.append_decoded, right after the gates) with their name-pool indices as ids - under
     gates="device" straight from the gates column (GATE_READS), under gates="host" from the host's mask.  The caller resets the
     table (reads.reset) and runs the chromosomes in ascending index order; the result carries n_reads_rows instead of the four
-    reads_* arrays."""
+    reads_* arrays.
+
+    ranges: None - the task reads `bamfile.records(chrom, task_start, task_end)` - or sorted, disjoint (start, end) pairs inside the
+    task: only the records that overlap one of them are read (bam.BamFile.records(ranges=); an empty list reads nothing).  The
+    gates are unchanged and decide, so any superset of what they pass gives the same rows; not with aln=True, whose table needs
+    every record of the task (ValueError)."""
     from . import bam as bam_mod, rebuild
     _check_gates(gates, True)
+    if ranges is not None and aln:
+        raise ValueError("aln=True needs every record of the task: ranges= cannot be combined with it")
     if reads not in ("host", "device"):
         raise ValueError("reads must be 'host' or 'device', not %r" % (reads,))
     if reads == "device" and not name_pool:
@@ -786,7 +793,7 @@ def task_to_pool(ctx, bamfile, chrom, task_start, task_end, chrom_rank, sv_size,
             raise ValueError("read_base is %d but the name pool holds %d names: a row's read index must be its name's index" % (read_base, n_names))
     elif read_base is None:
         raise ValueError("read_base=None needs name_pool=True")
-    chunk = bamfile.records(chrom, task_start, task_end)
+    chunk = bamfile.records(chrom, task_start, task_end) if ranges is None else bamfile.records(chrom, ranges=ranges)
     cols = bam_mod.decode(ctx, chunk, host_outputs=False)
     if name_pool:
         rebuild.name_pool_append_chunk(ctx, chunk)

@@ -858,8 +858,8 @@ int csv_rows_emit(const csv_rows_in* in, char* out, int64_t cap, int64_t* n_writ
  * Host side (no GPU, no context): csv_bam_open maps the file, indexes its BGZF blocks, reads the BAM header and refuses a
  * file whose blocks are truncated or whose end-of-file block is missing.  csv_bam_read inflates blocks on `threads` host
  * threads, walks the block_size chain and hands out one chunk: the records of reference `refid` (-1: the unmapped tail)
- * that overlap [beg, end) - pos < end and pos + max(reference span, 1) > beg - at most max_records of them.  No index
- * file is used: the scan starts at the contig (or where the previous region of the same contig started) and stops at the
+ * that overlap [beg, end) - pos < end and pos + max(reference span, 1) > beg - at most max_records of them.  Without an index
+ * (csv_bam_index_load, below) the scan starts at the contig (or where the previous region of the same contig started) and stops at the
  * first record with pos >= end.  CSV_BAM_RESTART begins a new scan; without it the call continues behind the previous
  * chunk (more = 1 said there is one).  CSV_BAM_COUNT_ONLY counts records and packs nothing.
  *
@@ -893,6 +893,41 @@ int         csv_bam_header(const csv_bam* bam, int32_t* n_ref, const char** name
 int         csv_bam_read(csv_bam* bam, int32_t refid, int64_t beg, int64_t end, int64_t max_records, int32_t flags, csv_bam_chunk* out);
 /* sizeof of 0 csv_bam_chunk, 1 csv_bam_in, 2 csv_bam_out; -1 otherwise */
 int         csv_bam_struct_size(int which);
+
+/* The BAM index (.bai; parsed by csrc/bai_index.h from the SAM specification, section 5.2).
+ *
+ * csv_bam_index_load reads and validates an index and keeps, per reference, its linear index (one virtual offset per 16 384-base
+ * window) and the counts of the pseudo-bin 37450, and per file n_no_coor.  path == NULL: "<bam path>.bai" is tried, then the BAM
+ * path with ".bam" replaced by ".bai".  CSV_E_STATE: no such file (the reader stays as it was).  CSV_E_INVALID, with a
+ * csv_bam_error text that names the index file: no "BAI\1" magic; n_ref is not the BAM header's; a negative or absurd n_bin,
+ * n_chunk or n_intv; the file ends inside a field; a linear-index entry below the one before it (zeros aside); a virtual offset
+ * whose coffset is not the start of a BGZF block of THIS file or whose uoffset is above that block's ISIZE.  A reader whose load
+ * failed has no index.  csv_bam_index_drop forgets the index.
+ *
+ * With an index loaded a scan of csv_bam_read / csv_bam_read_ranges with CSV_BAM_RESTART starts at the linear-index entry of the
+ * window that holds `beg` (a zero entry means "no record": the next non-zero entry is taken; a window at or behind n_intv, or a
+ * reference with n_bin == 0 and n_intv == 0, has no record: the call returns an empty chunk and touches no block), and blocks are
+ * inflated ahead only up to where the index lets the region be expected to end.  The contract: THE INDEX ONLY MOVES THE
+ * STARTING POINT.  The records of a region, their order and both images are byte for byte those of the forward scan;
+ * compressed_bytes / inflated_bytes of a read that starts with no window inflated are never larger.  The unmapped tail (refid -1) is always found by the forward scan.
+ *
+ * csv_bam_index_stats: mapped[r] / unmapped[r] for every reference of the header (arrays of n_ref; either may be NULL) - zeros
+ * for a reference without the pseudo-bin, as htslib reports - and *n_no_coor, -1 when the file does not carry it.  CSV_E_STATE
+ * without an index.
+ *
+ * csv_bam_read_ranges: csv_bam_read for n_ranges >= 1 ranges [beg[i], end[i]) of one reference, sorted and disjoint (beg[i] <=
+ * end[i] <= beg[i + 1]; CSV_E_INVALID otherwise).  One chunk sequence: every record that overlaps any range appears once, in file
+ * order - the overlap rule, max_records, `more` (the next call without CSV_BAM_RESTART, with the same ranges, continues) and
+ * CSV_BAM_COUNT_ONLY are csv_bam_read's.  With an index the cursor jumps to the entry of the next range's first window when that
+ * lies ahead; inside a call it only moves forward.  Without one the ranges are served by one forward scan. */
+int         csv_bam_index_load(csv_bam* bam, const char* path);
+int         csv_bam_index_drop(csv_bam* bam);
+int         csv_bam_index_stats(const csv_bam* bam, int64_t* mapped, int64_t* unmapped, int64_t* n_no_coor);
+/* the number of the BGZF block (0 = the file's first) a read of `refid` from `beg` on starts in; -1: the index has no record there;
+ * -2: no index, no reader, or a refid outside the header */
+int64_t     csv_bam_index_block(const csv_bam* bam, int32_t refid, int64_t beg);
+int         csv_bam_read_ranges(csv_bam* bam, int32_t refid, int32_t n_ranges, const int64_t* beg, const int64_t* end, int64_t max_records, int32_t flags,
+                                csv_bam_chunk* out);
 
 /* BGZF inflate on the device: the raw-deflate payloads of n_blocks BGZF blocks -> their bytes, one wavefront
  * per block.  Block k's payload is comp[in_off[k] .. + in_len[k]), its out_len[k] (= ISIZE) bytes go to out[out_off[k] ..), crc[k]
