@@ -101,6 +101,13 @@ SYMBOLS = [
     ("csv_bam_set_inflate", C.c_int, [C.c_void_p, C.c_void_p, C.c_int32]),
     ("csv_bam_inflate_stats", C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_double)]),
     ("csv_bam_decode", C.c_int, [C.c_void_p, C.POINTER(_abi.BamIn), C.POINTER(_abi.BamOut)]),
+    ("csv_bam_set_frame", C.c_int, [C.c_void_p, C.c_void_p]),
+    ("csv_bam_chunk_lengths", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("csv_bam_chunk_fetch", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("csv_bam_frame_stats", C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    ("csv_bam_decode_framed", C.c_int, [C.c_void_p, C.POINTER(_abi.BamOut)]),
+    ("csv_name_pool_append_framed", C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
+    ("csv_seq_reads_framed", C.c_int, [C.c_void_p, C.c_void_p]),
     ("csv_bam_split_inputs", C.c_int, [C.c_void_p, C.POINTER(_abi.SaIn), C.POINTER(_abi.SaOut)]),
     ("csv_sa_struct_size", C.c_int, [C.c_int]),
     ("csv_fasta_index", C.c_int64, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -11,7 +11,11 @@ kernels with.
 
 `inflate_blocks(ctx, payloads, isizes, crcs)` is the face of `csv_bgzf_inflate`, `inflate_blocks_host` its twin on Python's zlib.
 
-    python -m cutesv_amd.bam FILE [--chrom C] [--dump-columns DIR] [--inflate {host,device}] [--idxstats]
+With frame="device"  the inflated window stays on the device as well: the records are framed there, a
+`FramedChunk` keeps its two images in the context's device memory (`slim` / `host` fetch them on first access), and `decode`,
+`rebuild.name_pool_append_chunk` and `extract.upload_read_sequences` take them where they lie.
+
+    python -m cutesv_amd.bam FILE [--chrom C] [--dump-columns DIR] [--inflate {host,device}] [--frame {host,device}] [--idxstats]
 """
 import ctypes as C
 import os
@@ -100,21 +104,80 @@ class Chunk:
         return [self.text(cols["sa_beg"][k], cols["sa_end"][k]) for k in range(int(cols["sa_off"][i]), int(cols["sa_off"][i + 1]))]
 
 
+class FramedChunk(Chunk):
+    """a Chunk of the framing route (frame="device"): the two images lie in the context's device memory, where `decode`,
+    `rebuild.name_pool_append_chunk` and `extract.upload_read_sequences` take them.  `slim` and `host` fetch both on first access
+    (csv_bam_chunk_fetch) - for checks and for the rare host fallbacks.  The device images live until the reader's next read or
+    route change: a fetch or a framed consumer after that raises."""
+
+    framed = True
+
+    def __init__(self, bamfile, chrom, refid, rec_off, rec_len, host_off, l_name, l_seq, more, stats, slim_bytes, host_bytes):
+        self._bf, self._serial, self._images = bamfile, bamfile._read_serial, None
+        self._l_name, self._l_seq, self._bytes = l_name, l_seq, (slim_bytes, host_bytes)
+        Chunk.__init__(self, chrom, refid, None, rec_off, rec_len, None, host_off, more, stats)
+
+    @property
+    def ctx(self):
+        return self._bf.frame
+
+    @property
+    def slim_bytes(self):
+        return self._bytes[0]
+
+    def valid(self):
+        """the device images are still this chunk's"""
+        return self._bf._h and self._bf.frame is not None and self._bf._read_serial == self._serial
+
+    def check(self):
+        if not self.valid():
+            raise BamError("%s: the device chunk is gone: it lives until the reader's next read or route change" % self._bf.path)
+
+    def _fetch(self):
+        if self._images is None:
+            self.check()
+            slim, host = np.empty(self._bytes[0], np.uint8), np.empty(self._bytes[1], np.uint8)
+            rc = self._bf._L.csv_bam_chunk_fetch(self._bf._h, slim.ctypes.data if len(slim) else None, host.ctypes.data if len(host) else None)
+            if rc:
+                raise BamError("%s: %s" % (self._bf.path, (self._bf._L.csv_bam_error(self._bf._h) or b"").decode(errors="replace")))
+            self._images = (slim, host)
+        return self._images
+
+    slim = property(lambda self: self._fetch()[0], lambda self, v: None)
+    host = property(lambda self: self._fetch()[1], lambda self, v: None)
+
+    @property
+    def fetched(self):
+        return self._images is not None
+
+    def _name_len(self, i):
+        return int(self._l_name[i])
+
+    def name_columns(self):
+        return np.ascontiguousarray(self.host_off[:self.n], np.int64), np.maximum(self._l_name - 1, 0).astype(np.int32)
+
+    def sequence_columns(self):
+        return np.ascontiguousarray(self.host_off[:self.n], np.int64) + self._l_name.astype(np.int64), self._l_seq.copy()
+
+
 class BamFile:
     """A coordinate-sorted BAM file.  `.references`, `.lengths`, `.header_text`; `.chunks(chrom)` iterates a contig in file
     order, `.records(chrom, start, end)` returns the records that overlap a region (what pysam's fetch yields), found by
     a forward scan that stops at the first record starting at or after `end`: no index file is needed.  With an index
     (`has_index`) the scan starts at the linear-index entry of `start`; what it yields is the same, byte for byte."""
 
-    def __init__(self, path, threads=None, inflate=None, index=None):
-        """inflate: None or "host" - the BGZF blocks are inflated on `threads` host threads; an engine.Context - on its device
+    def __init__(self, path, threads=None, inflate=None, index=None, frame=None):
+        """frame: None or "host" - the records are framed on the host; "device" - on the device of `inflate`, which must be a
+        Context (set_frame).
+        inflate: None or "host" - the BGZF blocks are inflated on `threads` host threads; an engine.Context - on its device
         (set_inflate).  The header is read on the host either way.
         index: None - <path>.bai, else <path minus .bam>.bai, is loaded when there is one; a path - that index, which must exist;
         False - none.  An index that is found and does not validate against this file raises BamError."""
-        _inflate_ctx(inflate)                                                 # (refused before the file is opened)
+        _frame_route(frame, _inflate_ctx(inflate))                           # (refused before the file is opened)
         L = self._L = lib()
         self._h = C.c_void_p()
         self.inflate, self.last_stats, self.window_blocks = None, {}, 0
+        self.frame, self._read_serial = None, 0
         self.threads = default_threads() if threads is None else max(1, int(threads))
         err = C.create_string_buffer(512)
         rc = L.csv_bam_open(os.fsencode(path), self.threads, C.byref(self._h), err, len(err))
@@ -138,6 +201,7 @@ class BamFile:
             self.close()
             raise BamError("%s: the header says SO:%s; a coordinate-sorted file is needed (samtools sort)" % (path, self.sort_order or "<missing>"))
         self.set_inflate(inflate)
+        self.set_frame(frame)
         self.has_index = False
         if index is not False:
             try:
@@ -203,7 +267,29 @@ class BamFile:
         if rc:
             raise BamError("%s: the inflate route cannot be set" % self.path)
         prev, self.inflate, self.window_blocks = self.inflate, ctx, int(window_blocks)
+        self.frame, self._read_serial = None, self._read_serial + 1              # (the library switches back to host framing with the inflate route)
         return prev
+
+    def set_frame(self, frame):
+        """Where the records are framed from now on: None or "host" - on the host, out of the inflated window; "device" - on the
+        device of the inflate route (csv_bam_set_frame; ValueError when the blocks are inflated on the host): the window, the slim
+        image and the host image stay in device memory and the reader hands out FramedChunks.  What a chunk contains does not
+        depend on it.  -> the previous setting ("host" or "device")."""
+        route = _frame_route(frame, self.inflate)
+        rc = self._L.csv_bam_set_frame(self._h, self.inflate._h if route == "device" else None)
+        if rc:
+            self.frame, self._read_serial = None, self._read_serial + 1          # (a reader that was refused frames on the host)
+            raise BamError("%s: %s" % (self.path, (self._L.csv_bam_error(self._h) or b"").decode(errors="replace")))
+        prev, self.frame = "host" if self.frame is None else "device", self.inflate if route == "device" else None
+        self._read_serial += 1
+        return prev
+
+    def frame_stats(self):
+        """of the last read: dict(frame "host" | "device", right_blocks, frame_fallback_blocks, ms_frame_kernels, frame_bytes_down, frame_bytes_up)"""
+        r, f, ms, dn, up = C.c_int64(), C.c_int64(), C.c_double(), C.c_int64(), C.c_int64()
+        self._L.csv_bam_frame_stats(self._h, C.byref(r), C.byref(f), C.byref(ms), C.byref(dn), C.byref(up))
+        return dict(frame="host" if self.frame is None else "device", right_blocks=int(r.value), frame_fallback_blocks=int(f.value), ms_frame_kernels=float(ms.value),
+                    frame_bytes_down=int(dn.value), frame_bytes_up=int(up.value))
 
     def inflate_stats(self):
         """of the last read: dict(inflate "host" | "device", device_blocks, fallback_blocks, ms_inflate_kernels)"""
@@ -213,6 +299,9 @@ class BamFile:
 
     def close(self):
         if self._h:
+            if self.frame is not None and self.frame._h:      # (the context's one framing reader leaves before it goes)
+                self._L.csv_bam_set_frame(self._h, None)
+            self.frame = None
             self._L.csv_bam_close(self._h)
             self._h = C.c_void_p()
 
@@ -239,12 +328,15 @@ class BamFile:
     def _read(self, chrom, beg, end, max_records, flags, ranges=None):
         cc = ChunkC()
         refid = self.refid(chrom)
+        self._read_serial += 1
         if ranges is None:
             rc = self._L.csv_bam_read(self._h, refid, int(beg), int(end), int(max_records), int(flags), C.byref(cc))
         elif len(ranges) == 0:                                 # nothing to read: the empty chunk; the library is not asked and no block is touched
             self.last_stats = dict(n_records=0, record_bytes=0, inflated_bytes=0, compressed_bytes=0, slim_bytes=0, ms_inflate=0.0, ms_frame=0.0,
                                    inflate="host" if self.inflate is None else "device", device_blocks=0, fallback_blocks=0, ms_inflate_kernels=0.0,
                                    upload_bytes_per_record=0.0, inflated_bytes_per_record=0.0)
+            if self.frame is not None:
+                self.last_stats.update(frame="device", right_blocks=0, frame_fallback_blocks=0, ms_frame_kernels=0.0, frame_bytes_down=0, frame_bytes_up=0)
             if flags & _abi.BAM_COUNT_ONLY:
                 return 0, False
             return Chunk(chrom, refid, np.zeros(0, np.uint8), np.zeros(0, np.int64), np.zeros(0, np.uint32), np.zeros(0, np.uint8), np.zeros(1, np.int64), False,
@@ -257,12 +349,19 @@ class BamFile:
         stats = dict(n_records=n, record_bytes=int(cc.record_bytes), inflated_bytes=int(cc.inflated_bytes), compressed_bytes=int(cc.compressed_bytes),
                      slim_bytes=int(cc.slim_bytes), ms_inflate=float(cc.ms_inflate), ms_frame=float(cc.ms_frame))
         stats.update(self.inflate_stats())
+        if self.frame is not None:
+            stats.update(self.frame_stats())
         self.last_stats = stats
         if flags & _abi.BAM_COUNT_ONLY:
             return n, bool(cc.more)
         # bytes that cross PCIe per record (image + offset + length) next to the inflated bytes of the record
         stats["upload_bytes_per_record"] = (int(cc.slim_bytes) + 12 * n) / n if n else 0.0
         stats["inflated_bytes_per_record"] = int(cc.record_bytes) / n if n else 0.0
+        if self.frame is not None:
+            l_name, l_seq = np.zeros(n, np.int32), np.zeros(n, np.int32)
+            self._L.csv_bam_chunk_lengths(self._h, l_name.ctypes.data if n else None, l_seq.ctypes.data if n else None)
+            return FramedChunk(self, chrom, refid, _from_ptr(cc.rec_off, n, np.int64), _from_ptr(cc.rec_len, n, np.uint32), _from_ptr(cc.host_off, n + 1, np.int64),
+                               l_name, l_seq, bool(cc.more), stats, int(cc.slim_bytes), int(cc.host_bytes))
         return Chunk(chrom, refid, _from_ptr(cc.slim, int(cc.slim_bytes), np.uint8), _from_ptr(cc.rec_off, n, np.int64), _from_ptr(cc.rec_len, n, np.uint32),
                      _from_ptr(cc.host, int(cc.host_bytes), np.uint8), _from_ptr(cc.host_off, n + 1, np.int64), bool(cc.more), stats)
 
@@ -312,6 +411,17 @@ def _inflate_ctx(inflate):
     if isinstance(inflate, str) or not hasattr(inflate, "_h") or not hasattr(inflate, "_check"):
         raise ValueError("inflate must be None, 'host' or an engine.Context, not %r" % (inflate,))
     return inflate
+
+
+def _frame_route(frame, inflate_ctx):
+    """the `frame` argument of BamFile -> "host" or "device" (which needs a device inflate route)"""
+    if frame is None or (isinstance(frame, str) and frame == "host"):
+        return "host"
+    if not (isinstance(frame, str) and frame == "device"):
+        raise ValueError("frame must be None, 'host' or 'device', not %r" % (frame,))
+    if inflate_ctx is None:
+        raise ValueError("frame='device' needs the device inflate route: inflate=<engine.Context>")
+    return "device"
 
 
 INFLATE_STATUS = dict(header=1, lengths=2, symbol=4, distance=8, output=16, short=32, input=64, crc=128)      # CSV_INF_E_*
@@ -371,6 +481,8 @@ def decode(ctx, chunk, host_outputs=True):
     scans them there.  host_outputs=False: only the small per-record columns come back (no CIGAR array)."""
     L = lib()
     n = chunk.n
+    if getattr(chunk, "framed", False) and not chunk.fetched and chunk.ctx is ctx:      # (on another context the images are fetched, as for the other two consumers)
+        return _decode_framed(ctx, chunk, host_outputs)
     slim, rec_off, rec_len = np.ascontiguousarray(chunk.slim, np.uint8), np.ascontiguousarray(chunk.rec_off, np.int64), np.ascontiguousarray(chunk.rec_len, np.uint32)
     bin_ = BamIn(n_records=n, slim=slim.ctypes.data if len(slim) else None, slim_bytes=len(slim), rec_off=rec_off.ctypes.data if n else None,
                  rec_len=rec_len.ctypes.data if n else None)
@@ -380,6 +492,22 @@ def decode(ctx, chunk, host_outputs=True):
     out = BamOut(cap_ops=size["o"], cap_sa=size["s"], **{k: (v.ctypes.data if len(v) else None) for k, v in arrs.items()})
     rc = L.csv_bam_decode(ctx._h, C.byref(bin_), C.byref(out))
     ctx._check(rc)
+    cut = dict(n=n, n1=n + 1, o=int(out.n_ops) if host_outputs else 0, s=int(out.n_sa))
+    cols = {name: (arrs[name][:cut[k]].copy() if k in ("o", "s") else arrs[name]) for name, _, k in _OUT}
+    cols.update(n_ops=int(out.n_ops), n_sa=int(out.n_sa), ms_device=float(out.ms_device), ms_upload=float(out.ms_upload),
+                bytes_uploaded=int(out.bytes_uploaded), on_device=True)
+    return cols
+
+
+def _decode_framed(ctx, chunk, host_outputs):
+    """decode on a FramedChunk: csv_bam_decode_framed takes the slim image where it lies; the same dict of columns"""
+    chunk.check()
+    n = chunk.n
+    bound = chunk.slim_bytes // 4 + 1
+    size = dict(n=n, n1=n + 1, o=bound if host_outputs else 0, s=bound)
+    arrs = {name: np.zeros(size[k], dt) if k in ("n", "n1") else np.empty(size[k], dt) for name, dt, k in _OUT}
+    out = BamOut(cap_ops=size["o"], cap_sa=size["s"], **{k: (v.ctypes.data if len(v) else None) for k, v in arrs.items()})
+    ctx._check(lib().csv_bam_decode_framed(ctx._h, C.byref(out)))
     cut = dict(n=n, n1=n + 1, o=int(out.n_ops) if host_outputs else 0, s=int(out.n_sa))
     cols = {name: (arrs[name][:cut[k]].copy() if k in ("o", "s") else arrs[name]) for name, _, k in _OUT}
     cols.update(n_ops=int(out.n_ops), n_sa=int(out.n_sa), ms_device=float(out.ms_device), ms_upload=float(out.ms_upload),
@@ -496,6 +624,7 @@ def main(argv=None):
     ap.add_argument("--threads", type=int, default=None, help="host threads of the inflate (default: min(16, CPUs))")
     ap.add_argument("--dump-columns", metavar="DIR", default=None, help="write the decoded columns of --chrom (host decode) as DIR/<column>.npy")
     ap.add_argument("--inflate", default="host", choices=["host", "device"], help="where the BGZF blocks are inflated: host threads, or the GPU (device 0) [%(default)s]")
+    ap.add_argument("--frame", default="host", choices=["host", "device"], help="where the records are framed: on the host, or on the GPU (needs --inflate device) [%(default)s]")
     ap.add_argument("--idxstats", action="store_true", help="print contig, length, mapped and unmapped reads from the index (the table of samtools idxstats) and stop")
     a = ap.parse_args(argv)
     if a.idxstats:
@@ -504,6 +633,8 @@ def main(argv=None):
                 print("%s\t%d\t%d\t%d" % (name, length, mapped, unmapped))
             print("*\t0\t0\t%d" % (bf.no_coordinate or 0))
         return 0
+    if a.frame == "device" and a.inflate != "device":
+        ap.error("--frame device needs --inflate device")
     ctx = None
     if a.inflate == "device":
         from . import engine
@@ -516,7 +647,7 @@ def main(argv=None):
 
 
 def _main(a, ap, ctx):
-    with BamFile(a.bam, threads=a.threads, inflate=ctx) as bf:
+    with BamFile(a.bam, threads=a.threads, inflate=ctx, frame=a.frame) as bf:
         print(bf.header_text.rstrip("\n"))
         names = [a.chrom] if a.chrom is not None else list(bf.references) + [None]
         for name in names:

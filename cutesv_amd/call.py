@@ -2,7 +2,7 @@
 
     text, svid = call_bam("in.bam", fasta.Reference("ref.fa"), CallParams(Params.ont(min_support=3)))
     python -m cutesv_amd.call in.bam ref.fa -o out.body.vcf [--genotype] [--tra_gt MODE] [--report_readid] [--min_support N] [--batch B]
-                               [--include_bed FILE] [--reads_table {host,device}] [--sigs_dir DIR] [--inflate {host,device}]
+                               [--include_bed FILE] [--reads_table {host,device}] [--sigs_dir DIR] [--inflate {host,device}] [--frame {host,device}]
 
 (cuteSV's own command line - BAM REF OUT.vcf WORK_DIR and its flags, a VCF with header - is cutesv_amd/cli.py: python -m cutesv_amd.)
 
@@ -122,6 +122,7 @@ def task_ranges(bf, chrom, regs, t0, t1):
 DEFAULT_GATES = "device"        # where call_bam evaluates the task gates without a BED (decided by its measurement)
 DEFAULT_READS_TABLE = "host"    # where call_bam builds the genotyping reads table: not measured yet, so it stays "host" until scripts/reads_stage.py has been run
                                 # on an MI355X (DESIGN.md section 20 has the rule that decides)
+DEFAULT_FRAME = "host"          # where call_bam frames the BAM's records: "device" is opt-in; DESIGN.md section 29 has the rule for a change
 DEFAULT_INFLATE = "host"        # where call_bam inflates the BAM's BGZF blocks: "device" is opt-in until scripts/inflate_stage.py has been run on an MI355X
                                 # and its figures pass the rule of DESIGN.md section 27
 TRA_GT_MODES = ("alignments", "reads_table", "off")
@@ -175,7 +176,7 @@ class _Shim:
 
 def call_bam(bam, reference, params, ctx=None, chroms=None, batch=10_000_000, report_readid=False, ignore_sequence=False, threads=None, svid=None,
              as_bytes=False, timings=None, tra_gt=None, include_bed=None, gates=None, reads_table=None, sigs_dir=None, inflate=None, index=None, task_cut=None,
-             cut_threads=16, read_stats=None):
+             cut_threads=16, read_stats=None, frame=None):
     """-> (VCF body text, svid counters [INS, DEL, BND, DUP, INV]).
 
     bam        a path or an open bam.BamFile (coordinate-sorted; no index is needed, one beside the file is used - see `index`)
@@ -204,6 +205,9 @@ def call_bam(bam, reference, params, ctx=None, chroms=None, batch=10_000_000, re
     inflate    "host" or "device": where the BGZF blocks are inflated (None: DEFAULT_INFLATE).  device: on `ctx`, one wavefront per
                block; a BamFile that was handed in gets the context for the call and its previous setting back
                at the end.  Same text either way.
+    frame      "host" or "device": where the records are framed (None: DEFAULT_FRAME).  device: on `ctx`, out of a window that never
+               leaves it; it takes the device inflate when `inflate` is None (ValueError with an explicit
+               inflate="host"); a BamFile that was handed in gets its previous setting back at the end.  Same text either way.
     index      for a path: None - the .bai beside the file is loaded when there is one; a path - that index; False - none
                (bam.BamFile's `index`).  An open BamFile comes with what it has.  With an index every task's read starts at its
                linear-index entry, and under include_bed - unless tra_gt="alignments" fills the alignment table, which needs every
@@ -223,8 +227,14 @@ def call_bam(bam, reference, params, ctx=None, chroms=None, batch=10_000_000, re
         reads_table = DEFAULT_READS_TABLE
     if reads_table not in ("host", "device"):
         raise ValueError("reads_table must be 'host' or 'device', not %r" % (reads_table,))
+    if frame is None:
+        frame = DEFAULT_FRAME
+    if frame not in ("host", "device"):
+        raise ValueError("frame must be 'host' or 'device', not %r" % (frame,))
+    if frame == "device" and inflate == "host":
+        raise ValueError("frame='device' needs the device inflate: inflate='host' cannot be combined with it")
     if inflate is None:
-        inflate = DEFAULT_INFLATE
+        inflate = "device" if frame == "device" else DEFAULT_INFLATE
     if inflate not in ("host", "device"):
         raise ValueError("inflate must be 'host' or 'device', not %r" % (inflate,))
     regions = None if include_bed is None else include_bed if isinstance(include_bed, bed_mod.Regions) else bed_mod.load_bed(include_bed)
@@ -249,7 +259,9 @@ def call_bam(bam, reference, params, ctx=None, chroms=None, batch=10_000_000, re
     try:
         if task_cut == "index" and not bf.has_index:
             raise ValueError("task_cut='index' needs a BAM index (.bai): none was found for %s" % bf.path)
-        restore = (bf.set_inflate(ctx if inflate == "device" else None),)
+        was_framed = bf.frame is not None
+        restore = (bf.set_inflate(ctx if inflate == "device" else None), was_framed)
+        bf.set_frame(frame)
         # the chromosome table in name order: a chromosome's index is its name rank, the numbering of rebuild._segments and of a TRA row's mate
         names = sorted(bf.references)
         length = dict(zip(bf.references, bf.lengths))
@@ -287,6 +299,7 @@ def call_bam(bam, reference, params, ctx=None, chroms=None, batch=10_000_000, re
                     tables.append((crank[c], r))
                 if timings is not None:
                     timings["ms_inflate"] = timings.get("ms_inflate", 0.0) + bf.last_stats["ms_inflate"]      # (a task reads its records in one call)
+                    timings["ms_frame"] = timings.get("ms_frame", 0.0) + bf.last_stats["ms_frame"]
                 if read_stats is not None:
                     read_stats["compressed_bytes"] = read_stats.get("compressed_bytes", 0) + bf.last_stats["compressed_bytes"]
                     read_stats["n_records"] = read_stats.get("n_records", 0) + r["n_records"]
@@ -341,6 +354,8 @@ def call_bam(bam, reference, params, ctx=None, chroms=None, batch=10_000_000, re
     finally:
         if restore is not None and not own_bam:
             bf.set_inflate(restore[0])
+            if restore[1]:
+                bf.set_frame("device")
         if own_bam:                                            # (the reader goes before the context it may inflate on)
             bf.close()
         if own_ctx:
@@ -377,6 +392,7 @@ def main(argv=None):
     ap.add_argument("--tra_gt", default=None, choices=list(TRA_GT_MODES),
                     help="with --genotype: how BND records are genotyped (default: CUTESV_AMD_TRA_GT, else alignments - every alignment counts, as in cuteSV)")
     ap.add_argument("--inflate", default=None, choices=["host", "device"], help="where the BAM's BGZF blocks are inflated (default: %s)" % DEFAULT_INFLATE)
+    ap.add_argument("--frame", default=None, choices=["host", "device"], help="where the BAM's records are framed (default: %s; device takes the device inflate)" % DEFAULT_FRAME)
     ap.add_argument("--sigs_dir", default=None, metavar="DIR", help="also write the rebuilt signatures there as cuteSV's --write_old_sigs files (DEL.sigs .. TRA.sigs)")
     a = ap.parse_args(argv)
     tra_gt = a.tra_gt
@@ -387,7 +403,7 @@ def main(argv=None):
                     merge_del_threshold=a.merge_del_threshold, merge_ins_threshold=a.merge_ins_threshold)
     text, svid = call_bam(a.bam, fasta.Reference(a.reference), cp, chroms=a.chroms.split(",") if a.chroms else None, batch=a.batch,
                           report_readid=a.report_readid, ignore_sequence=a.ignore_sequence, threads=a.threads, as_bytes=True, tra_gt=tra_gt,
-                          include_bed=a.include_bed, reads_table=a.reads_table, sigs_dir=a.sigs_dir, inflate=a.inflate)
+                          include_bed=a.include_bed, reads_table=a.reads_table, sigs_dir=a.sigs_dir, inflate=a.inflate, frame=a.frame)
     with open(a.out, "wb") as f:
         f.write(text)
     print("%d records: INS %d, DEL %d, BND %d, DUP %d, INV %d" % (text.count(b"\n"), *svid.tolist()))

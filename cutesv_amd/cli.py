@@ -1,6 +1,6 @@
 """cuteSV's command line on this project's chain:
 
-    python -m cutesv_amd BAM REF OUT.vcf WORK_DIR [cuteSV's flags] [--reads_table {host,device}] [--tra_gt MODE] [--inflate {host,device}]
+    python -m cutesv_amd BAM REF OUT.vcf WORK_DIR [cuteSV's flags] [--reads_table {host,device}] [--tra_gt MODE] [--inflate {host,device}] [--frame {host,device}]
                          [--task_cut {index,uniform}]
 
 `parse_args` accepts every option of cuteSV v2.1.4 under the same short and long spellings, with the same destination, type
@@ -91,18 +91,19 @@ def _parser():
 
 
 def _own_parser():
-    """the four options cuteSV does not have; parsed apart (split_own), so that they shadow no abbreviation of a cuteSV flag"""
+    """the five options cuteSV does not have; parsed apart (split_own), so that they shadow no abbreviation of a cuteSV flag"""
     from . import call
     ap = argparse.ArgumentParser(add_help=False, allow_abbrev=False)
     ap.add_argument("--reads_table", default=None, choices=["host", "device"])
     ap.add_argument("--tra_gt", default=None, choices=list(call.TRA_GT_MODES))
     ap.add_argument("--inflate", default=None, choices=["host", "device"])
+    ap.add_argument("--frame", default=None, choices=["host", "device"])
     ap.add_argument("--task_cut", default=None, choices=["index", "uniform"])
     return ap
 
 
 def split_own(argv):
-    """-> (namespace of --reads_table / --tra_gt / --inflate / --task_cut, argv without them)"""
+    """-> (namespace of --reads_table / --tra_gt / --inflate / --frame / --task_cut, argv without them)"""
     return _own_parser().parse_known_args(list(argv))
 
 
@@ -159,7 +160,7 @@ def main(argv=None):
                 _log("no BAM index (.bai) beside %s: the tasks are the uniform cut by -b, not cuteSV's cut from the index statistics" % a.input)
         body, svid = call.call_bam(bf, fasta.Reference(a.reference), call_params(a), batch=a.batches, report_readid=a.report_readid,
                                    ignore_sequence=a.ignore_sequence, as_bytes=True, timings=timings, tra_gt=tra_gt, include_bed=a.include_bed,
-                                   reads_table=own.reads_table, sigs_dir=sigs_dir, inflate=own.inflate, task_cut=task_cut, cut_threads=a.threads)
+                                   reads_table=own.reads_table, sigs_dir=sigs_dir, inflate=own.inflate, frame=own.frame, task_cut=task_cut, cut_threads=a.threads)
     finally:
         bf.close()
     for key, ms in timings.items():

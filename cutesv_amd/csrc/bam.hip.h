@@ -16,12 +16,16 @@
 // against the image, k_bam_fixed checks the CIGAR and every aux value against the record.
 //
 // At the end of the file, the step in front of all that: k_bgzf_inflate, one wavefront per BGZF block, over the decode core
-// of inflate_core.h.
+// of inflate_core.h; and behind it the record framing on the device (frame_core.h):
+// k_frame_guess, k_frame_stitch, k_frame_rows find the records of an inflated window that never left the device, k_frame_pack
+// builds the slim and the host image from the records the reader selected.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "wave.hip.h"
+#include "scan.hip.h"
 #include "inflate_core.h"
+#include "frame_core.h"
 
 namespace csv {
 
@@ -307,6 +311,123 @@ __global__ __launch_bounds__(64 * INF_WAVES) void k_bgzf_inflate(InflateArgs A)
         if (out_len > 0) st = inf_block(L, work[w], A.comp + A.in_off[k], A.in_len[k], A.out + A.out_off[k], out_len, A.crc[k], crc_table);
         if (L.lane() == 0) A.status[k] = (uint8_t)st;
     }
+}
+
+// ------------------------------------------------------------------------------------ record framing
+// The 64-lane form of frame_core.h's Lanes.  first / sum are called where the wavefront has converged: fr_guess evaluates the
+// test of every lane before the call, fr_row leaves its strided loop before it.
+struct FrWave {
+    __device__ __forceinline__ int lane() const { return lane_id(); }
+    __device__ __forceinline__ int width() const { return WAVE; }
+    __device__ __forceinline__ int first(bool p) const
+    {
+        const u64 m = __ballot(p ? 1 : 0);
+        return m ? __ffsll((long long)m) - 1 : -1;
+    }
+    __device__ __forceinline__ fr_i64 sum(fr_i64 v) const { return wave_sum_i64(v); }
+};
+
+struct FrameArgs {
+    FrWin W;                        // the window (device memory) and the file's n_ref
+    int n_blocks;                   // BGZF blocks of the window, in stream order
+    i64 c;                          // the cursor: a true record start
+    const i64* blk_off; const int* blk_len;     // host-checked: contiguous from 0, inside [0, W.n], at most 65536 each
+    const i64* slot_off;            // block s's slot in `starts`: fr_slot_size(blk_len[s]) entries
+    i64* g; i64* ex; int* cnt;      // per block: the guess, where its chain landed, the starts it met
+    i64* starts;
+    int* used;                      // per block: the starts that are the true chain's (k_frame_stitch)
+    int4* scan;                     // per block: used -> exclusive row offsets (scan_counts)
+    FrStitch* res;
+    FrRow* rows;
+};
+
+constexpr int FRAME_WAVES = 4;
+
+// one wavefront per BGZF block: the guess (64 offsets a round), then lane 0 chases the chain through the block
+__global__ __launch_bounds__(64 * FRAME_WAVES) void k_frame_guess(FrameArgs A)
+{
+    const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const FrWave L;
+    for (i64 s = (i64)blockIdx.x * FRAME_WAVES + w; s < A.n_blocks; s += (i64)gridDim.x * FRAME_WAVES) {
+        const i64 b = A.blk_off[s], e = b + A.blk_len[s];
+        i64 g = -1, ex = -1;
+        int cnt = 0;
+        if (e > A.c) {                                           // (a block in front of the cursor is never landed in)
+            g = b <= A.c ? A.c : fr_guess(L, A.W, b, e);
+            if (g >= 0 && L.lane() == 0) ex = fr_chase(A.W, g, e, A.starts + A.slot_off[s], fr_slot_size(A.blk_len[s]), &cnt);
+        }
+        if (L.lane() == 0) { A.g[s] = g; A.ex[s] = ex; A.cnt[s] = cnt; }
+    }
+}
+
+// one wavefront: lane 0 walks from the cursor block by block (fr_stitch), then the lanes lay out the counts for the scan
+__global__ __launch_bounds__(64) void k_frame_stitch(FrameArgs A)
+{
+    if (threadIdx.x == 0) fr_stitch(A.W, A.n_blocks, A.blk_off, A.blk_len, A.slot_off, A.g, A.ex, A.cnt, A.starts, A.used, A.c, A.res);
+    __syncthreads();
+    for (int s = threadIdx.x; s < A.n_blocks; s += 64) A.scan[s] = make_int4(A.used[s], 0, 0, 0);
+}
+
+// one wavefront per block: the rows of its records (the lanes share a record's CIGAR sum); scan[s].x = the block's first row
+__global__ __launch_bounds__(64 * FRAME_WAVES) void k_frame_rows(FrameArgs A, i64 n_rows)
+{
+    const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const FrWave L;
+    for (i64 s = (i64)blockIdx.x * FRAME_WAVES + w; s < A.n_blocks; s += (i64)gridDim.x * FRAME_WAVES) {
+        const int n = __builtin_amdgcn_readfirstlane(A.used[s]);
+        const i64 base = A.scan[s].x, slot = A.slot_off[s];
+        for (int j = 0; j < n; j++) {
+            const i64 o = A.starts[slot + j];
+            FrRow r = fr_row(L, A.W, o);
+            if (L.lane() == 0 && base + j < n_rows) A.rows[base + j] = r;
+        }
+    }
+}
+
+// L bytes from src to dst with the lanes of a wavefront: aligned words of dst between a byte head and a byte tail
+__device__ __forceinline__ void frame_copy(const uint8_t* src, i64 L, uint8_t* dst, int lane)
+{
+    i64 head = (i64)((4 - ((uintptr_t)dst & 3)) & 3);
+    head = head < L ? head : L;
+    if (lane < head) dst[lane] = src[lane];
+    const i64 nw = (L - head) >> 2;
+    for (i64 w = lane; w < nw; w += 64) {
+        const i64 j = head + 4 * w;
+        *(unsigned*)(dst + j) = (unsigned)src[j] | ((unsigned)src[j + 1] << 8) | ((unsigned)src[j + 2] << 16) | ((unsigned)src[j + 3] << 24);
+    }
+    const i64 t0 = head + 4 * nw;
+    if (lane < L - t0) dst[t0 + lane] = src[t0 + lane];
+}
+
+// one wavefront per selected record: fixed fields, CIGAR words and aux bytes into the slim image (padded with zeros to 16
+// bytes), name and 4-bit sequence into the host image - the layout bam_host.cpp packs on the host route
+__global__ __launch_bounds__(256) void k_frame_pack(const uint8_t* win, const FrPack* P, i64 n, uint8_t* slim, uint8_t* host)
+{
+    const int lane = lane_id();
+    for (i64 r = ((i64)blockIdx.x * 256 + threadIdx.x) >> 6; r < n; r += ((i64)gridDim.x * 256) >> 6) {
+        const FrPack p = P[r];
+        const i64 l_name = p.l_name, cig = 4 * (i64)p.n_cig, seq = ((i64)p.l_seq + 1) / 2;
+        const i64 fixed_to_aux = 32 + l_name + cig + seq + (i64)p.l_seq, aux_len = (i64)p.bs - fixed_to_aux, slim_len = 32 + cig + aux_len;
+        const uint8_t* s = win + p.src + 4;
+        uint8_t* d = slim + p.rec_off;
+        frame_copy(s, 32, d, lane);
+        frame_copy(s + 32 + l_name, cig, d + 32, lane);
+        frame_copy(s + fixed_to_aux, aux_len, d + 32 + cig, lane);
+        const i64 pad = (slim_len + 15) / 16 * 16 - slim_len;
+        if (lane < pad) d[slim_len + lane] = 0;
+        uint8_t* h = host + p.host_off;
+        frame_copy(s + 32, l_name, h, lane);
+        frame_copy(s + 32 + l_name + cig, seq, h + l_name, lane);
+    }
+}
+
+// one wavefront per item: len[i] bytes at src + src_off[i] -> dst + dst_off[i] (host-checked ranges); the names and the 4-bit
+// sequences of a device chunk on their way into the name pool and the read sequences
+__global__ __launch_bounds__(256) void k_frame_gather(const uint8_t* src, const i64* src_off, const int* len, i64 n, uint8_t* dst, const i64* dst_off)
+{
+    const int lane = lane_id();
+    for (i64 r = ((i64)blockIdx.x * 256 + threadIdx.x) >> 6; r < n; r += ((i64)gridDim.x * 256) >> 6)
+        if (len[r] > 0) frame_copy(src + src_off[r], len[r], dst + dst_off[r], lane);
 }
 
 }  // namespace csv

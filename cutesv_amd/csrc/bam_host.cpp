@@ -13,6 +13,8 @@
 // starting point and nothing else.  What goes to the device per
 // record is the slim image {32 fixed bytes, CIGAR words, aux bytes}; the read name and the 4-bit sequence stay in a host
 // buffer; the qualities are dropped.
+// With csv_bam_set_frame the window never leaves the device: the records are framed there (frame_core.h), the
+// selection loop below runs over the rows of the record table instead of the bytes, and the two images are built in device memory.
 #include <stdint.h>
 #include <stdio.h>
 #include <string.h>
@@ -32,6 +34,7 @@
 
 #include "../../include/cutesv_hip.h"
 #include "bai_index.h"
+#include "frame_core.h"
 
 namespace {
 
@@ -105,6 +108,21 @@ struct csv_bam {
     std::vector<uint32_t> rec_len;
     double               ms_inflate = 0;
     i64                  inflated = 0, compressed = 0;
+    // the framing route (csv_bam_set_frame): the window lies in the context's device memory and is known here by its rows - the
+    // records the chain from fr_from met, up to fr_tail where it stopped (stream offsets).  pending: the selected records of the
+    // current window that are not packed yet; slim_size / host_size: the bytes of the device images with them
+    csv_ctx*             frame = nullptr;
+    uint64_t             fr_serial = 0;
+    size_t               win_b0 = 0;
+    const csv::FrRow*    fr_rows = nullptr;
+    i64                  fr_n = 0, fr_i = 0, fr_from = 0, fr_tail = 0;
+    int32_t              fr_tail_bs = 0;
+    bool                 fr_tail_has_bs = false, fr_valid = false, framed_chunk = false;
+    std::vector<csv::FrPack> pending;
+    std::vector<int32_t> l_name_v, l_seq_v, t_len;
+    std::vector<int64_t> t_off;
+    std::vector<uint8_t> one_block;
+    i64                  slim_size = 0, host_size = 0;
 };
 
 namespace {
@@ -213,10 +231,64 @@ int load_window_device(csv_bam* b, size_t b0, size_t b1, size_t bn, i64 keep)
     return CSV_OK;
 }
 
+int frame_flush(csv_bam* b)
+{
+    if (b->pending.empty()) return CSV_OK;
+    const int rc = csv_frame_pack(b->frame, (int64_t)b->pending.size(), b->pending.data(), b->slim_size, b->host_size);
+    b->pending.clear();
+    if (rc) return fail(b, rc, "the device framing failed: %s", csv_last_error(b->frame));
+    return CSV_OK;
+}
+
+// load_window_device for the framing route: the bytes are inflated into the context's device window and stay there; the kept tail
+// is carried over on the device; a block the device gives up on is inflated by inflate_block, whose verdict stands, and copied up
+int load_window_frame(csv_bam* b, size_t b0, size_t b1, size_t bn, i64 keep)
+{
+    int rc = frame_flush(b);                                 // (the selected records of the old window are packed out of it first)
+    if (rc) return rc;
+    const double t0 = now_ms();
+    const i64 keep_at = keep > 0 ? b->blocks[b0].uoff - b->win_u0 : 0;
+    b->win_n = 0; b->fr_valid = false;
+    const i64 u0 = b->blocks[b0].uoff, bytes = (b1 < b->blocks.size() ? b->blocks[b1].uoff : b->utotal) - u0;
+    const size_t n = b1 > bn ? b1 - bn : 0;
+    b->d_in_off.resize(n); b->d_in_len.resize(n); b->d_out_off.resize(n); b->d_out_len.resize(n); b->d_crc.resize(n); b->d_status.resize(n);
+    const i64 base = n ? b->blocks[bn].coff : 0, comp_bytes = n ? b->blocks[b1 - 1].coff + b->blocks[b1 - 1].csize - base : 0;
+    for (size_t j = 0; j < n; j++) {
+        const Block& k = b->blocks[bn + j];
+        b->d_in_off[j] = k.coff + k.hdr - base; b->d_in_len[j] = k.csize - k.hdr - 8;
+        b->d_out_off[j] = k.uoff - u0; b->d_out_len[j] = (int32_t)k.isize;
+        b->d_crc[j] = rd_u32(b->map + k.coff + k.csize - 8);
+    }
+    double ms = 0;
+    rc = csv_frame_window(b->frame, b->map + base, comp_bytes, (int32_t)n, b->d_in_off.data(), b->d_in_len.data(), b->d_out_off.data(), b->d_out_len.data(), b->d_crc.data(), bytes,
+                          keep, keep_at, b->d_status.data(), &ms);
+    if (rc) return fail(b, rc, "the device inflate failed: %s", csv_last_error(b->frame));
+    b->fr_serial = csv_frame_window_serial(b->frame);
+    b->win_u0 = u0;
+    b->ms_kernels += ms;
+    i64 bad = -1;
+    b->one_block.resize(65536);
+    for (size_t j = 0; j < n; j++) {
+        if (!b->d_status[j]) { b->device_blocks++; continue; }
+        b->fallback_blocks++;
+        if (!inflate_block(b, b->blocks[bn + j], b->one_block.data())) { bad = (i64)(bn + j); continue; }
+        // (the window is not valid to the reader yet, but it is the context's: the block goes where the device would have put it)
+        rc = csv_frame_window_put(b->frame, b->d_out_off[j], b->one_block.data(), b->d_out_len[j]);
+        if (rc) return fail(b, rc, "the device inflate failed: %s", csv_last_error(b->frame));
+    }
+    for (size_t j = bn; j < b1; j++) b->compressed += b->blocks[j].csize;
+    b->inflated += bytes - keep;
+    b->ms_inflate += now_ms() - t0;
+    if (bad >= 0) return fail(b, CSV_E_INVALID, "%sBGZF block at byte %lld does not inflate (or fails its CRC)", "", (long long)b->blocks[(size_t)bad].coff);
+    b->win_p = nullptr; b->win_n = bytes; b->win_b0 = b0; b->win_b1 = b1;
+    return CSV_OK;
+}
+
 // the window becomes the inflated blocks [b0, b1).  keep > 0: the window already holds the bytes of the blocks [b0, bn) at its end
 // (the scan moved on inside it): they are moved to the front and only [bn, b1) is inflated; else bn == b0
 int load_window(csv_bam* b, size_t b0, size_t b1, size_t bn, i64 keep)
 {
+    if (b->frame) return load_window_frame(b, b0, b1, bn, keep);
     if (b->dev) return load_window_device(b, b0, b1, bn, keep);
     const double t0 = now_ms();
     const i64 bytes = (b1 < b->blocks.size() ? b->blocks[b1].uoff : b->utotal) - b->blocks[b0].uoff;
@@ -256,12 +328,12 @@ size_t block_of(const csv_bam* b, i64 u)                  // the block that hold
     return lo;
 }
 
-// a pointer to [u, u + need) of the inflated stream, refilling the window when it does not hold the range; nullptr with
-// *rc = CSV_OK: the stream ends before u + need
-const uint8_t* at(csv_bam* b, i64 u, i64 need, int* rc)
+// the window holds [u, u + need) of the inflated stream afterwards (refilled when it did not); *have = false: the stream ends
+// before u + need
+int ensure(csv_bam* b, i64 u, i64 need, bool* have)
 {
-    *rc = CSV_OK;
-    if (u + need > b->utotal) return nullptr;
+    *have = false;
+    if (u + need > b->utotal) return CSV_OK;
     if (u < b->win_u0 || u + need > b->win_u0 + b->win_n) {
         const size_t b0 = block_of(b, u);
         size_t b1 = std::min(b->blocks.size(), b0 + (size_t)(b->dev ? b->window_blocks : REFILL_BLOCKS));
@@ -276,9 +348,20 @@ const uint8_t* at(csv_bam* b, i64 u, i64 need, int* rc)
             keep = b->win_u0 + b->win_n - b->blocks[b0].uoff;
             if (b1 < bn) b1 = bn;
         }
-        *rc = load_window(b, b0, b1, bn, keep);
-        if (*rc) return nullptr;
+        const int rc = load_window(b, b0, b1, bn, keep);
+        if (rc) return rc;
     }
+    *have = true;
+    return CSV_OK;
+}
+
+// a pointer to [u, u + need) of the inflated stream, refilling the window when it does not hold the range; nullptr with
+// *rc = CSV_OK: the stream ends before u + need
+const uint8_t* at(csv_bam* b, i64 u, i64 need, int* rc)
+{
+    bool have;
+    *rc = ensure(b, u, need, &have);
+    if (*rc || !have) return nullptr;
     return b->win_p + (u - b->win_u0);
 }
 
@@ -384,9 +467,62 @@ int csv_bam_set_inflate(csv_bam* b, csv_ctx* ctx, int32_t window_blocks)
 {
     if (!b || window_blocks > MAX_WINDOW_BLOCKS) return CSV_E_INVALID;
     b->win_n = 0;                                            // the next read fills its window on this route (what open inflated for the header is not kept)
+    if (b->frame) csv_bam_set_frame(b, nullptr);             // (the framing route belongs to the inflate route it was set on)
     b->dev = ctx;
     b->window_blocks = window_blocks > 0 ? window_blocks : CSV_BAM_WINDOW_BLOCKS;
     return CSV_OK;
+}
+
+int csv_bam_set_frame(csv_bam* b, csv_ctx* ctx)
+{
+    if (!b) return CSV_E_INVALID;
+    if (ctx && b->dev != ctx) return fail(b, CSV_E_STATE, "%sframing on the device needs the device inflate route on the same context (csv_bam_set_inflate)", "");
+    if (b->frame) csv_frame_reader(b->frame, b, 0);
+    if (ctx && csv_frame_reader(ctx, b, 1) != CSV_OK) {
+        b->frame = nullptr; b->win_n = 0;
+        return fail(b, CSV_E_STATE, "%sanother reader frames on this context: one framing reader per context (csv_bam_set_frame(other, NULL) first)", "");
+    }
+    b->frame = ctx;
+    b->win_n = 0; b->fr_valid = false; b->framed_chunk = false; b->pending.clear();
+    return CSV_OK;
+}
+
+int csv_bam_chunk_lengths(const csv_bam* b, int32_t* l_read_name, int32_t* l_seq)
+{
+    if (!b) return CSV_E_INVALID;
+    const size_t n = b->rec_off.size();
+    for (size_t i = 0; i < n; i++) {
+        if (b->framed_chunk) {
+            if (l_read_name) l_read_name[i] = b->l_name_v[i];
+            if (l_seq) l_seq[i] = b->l_seq_v[i];
+        } else {
+            const uint8_t* p = b->slim.data() + b->rec_off[i];
+            if (l_read_name) l_read_name[i] = p[8];
+            if (l_seq) l_seq[i] = (int32_t)rd_u32(p + 16);
+        }
+    }
+    return CSV_OK;
+}
+
+int csv_bam_chunk_fetch(csv_bam* b, uint8_t* slim, uint8_t* host)
+{
+    if (!b) return CSV_E_INVALID;
+    if (!b->frame || !b->framed_chunk) return fail(b, CSV_E_STATE, "%sthe reader holds no device chunk (csv_bam_set_frame; it lives until the next read or route change)", "");
+    const int rc = csv_frame_fetch(b->frame, b, slim, host);
+    if (rc) return fail(b, rc, "the device chunk cannot be fetched: %s", csv_last_error(b->frame));
+    return CSV_OK;
+}
+
+int csv_bam_frame_stats(const csv_bam* b, int64_t* right_blocks, int64_t* fallback_blocks, double* ms_kernels, int64_t* bytes_down, int64_t* bytes_up)
+{
+    if (!b) return CSV_E_INVALID;
+    if (right_blocks) *right_blocks = 0;
+    if (fallback_blocks) *fallback_blocks = 0;
+    if (ms_kernels) *ms_kernels = 0;
+    if (bytes_down) *bytes_down = 0;
+    if (bytes_up) *bytes_up = 0;
+    if (!b->frame) return CSV_OK;
+    return csv_frame_counters(b->frame, right_blocks, fallback_blocks, ms_kernels, bytes_down, bytes_up, 0);
 }
 
 int csv_bam_inflate_stats(const csv_bam* b, int64_t* device_blocks, int64_t* fallback_blocks, double* ms_kernels)
@@ -438,6 +574,80 @@ bool index_seek(csv_bam* b, uint32_t key, i64 beg, i64 end, i64 floor)
     return true;
 }
 
+// One record of the scan, as the selection loop of read_ranges sees it, from either source: the bytes in the host window (p), or a
+// row of the device's record table (p == NULL; span is the row's, src the record's offset in the device window)
+struct Rec { i64 bs; uint32_t rkey; i64 pos, l_name, n_cig, l_seq, span, src; const uint8_t* p; };
+
+// the record at b->cur out of the host window.  *end: the stream ends at b->cur.  The checks and their order are the scan's own:
+// the file ends inside the record's block_size, block_size < 32, the file ends inside the record
+int next_host(csv_bam* b, Rec* r, bool* end)
+{
+    int rc;
+    *end = false;
+    const uint8_t* p = at(b, b->cur, 4, &rc);
+    if (rc) return rc;
+    if (!p) {
+        if (b->cur != b->utotal) return fail(b, CSV_E_INVALID, "%sthe file ends inside a record (at inflated byte %lld)", "", (long long)b->cur);
+        *end = true;
+        return CSV_OK;
+    }
+    const i64 bs = rd_i32(p);
+    if (bs < 32) return fail(b, CSV_E_INVALID, "%srecord with block_size < 32 at inflated byte %lld", "", (long long)b->cur);
+    p = at(b, b->cur + 4, bs, &rc);
+    if (rc) return rc;
+    if (!p) return fail(b, CSV_E_INVALID, "%sthe file ends inside a record (at inflated byte %lld)", "", (long long)b->cur);
+    r->bs = bs; r->rkey = (uint32_t)rd_i32(p); r->pos = rd_i32(p + 4); r->l_name = p[8]; r->n_cig = rd_u16(p + 12); r->l_seq = rd_u32(p + 16);
+    r->span = -1; r->src = 0; r->p = p;
+    return CSV_OK;
+}
+
+// the same from the rows of the device window: the window is loaded and framed from b->cur when its rows do not hold that offset
+int next_framed(csv_bam* b, Rec* r, bool* end)
+{
+    *end = false;
+    for (int round = 0; round < 8; round++) {
+        const i64 cur = b->cur;
+        if (b->fr_valid && (b->win_n == 0 || cur < b->fr_from || cur > b->fr_tail || csv_frame_window_serial(b->frame) != b->fr_serial)) b->fr_valid = false;
+        if (b->fr_valid && cur < b->fr_tail) {
+            const i64 o = cur - b->win_u0;
+            i64 k = b->fr_i;
+            if (!(k < b->fr_n && b->fr_rows[k].off == o)) {
+                const csv::FrRow* e = b->fr_rows + b->fr_n;
+                k = std::lower_bound(b->fr_rows, e, o, [](const csv::FrRow& x, i64 v) { return x.off < v; }) - b->fr_rows;
+            }
+            if (k < b->fr_n && b->fr_rows[k].off == o) {
+                const csv::FrRow& w = b->fr_rows[k];
+                b->fr_i = k + 1;
+                r->bs = w.block_size; r->rkey = (uint32_t)w.refid; r->pos = w.pos; r->l_name = w.l_name; r->n_cig = w.n_cigar; r->l_seq = w.l_seq;
+                r->span = w.span; r->src = w.off; r->p = nullptr;
+                return CSV_OK;
+            }
+            b->fr_valid = false;                             // (not a start of the chain framed last: framed again from here)
+        }
+        i64 need = 4;
+        if (cur == b->utotal) { *end = true; return CSV_OK; }
+        if (cur + 4 > b->utotal) return fail(b, CSV_E_INVALID, "%sthe file ends inside a record (at inflated byte %lld)", "", (long long)cur);
+        if (b->fr_valid && b->fr_tail_has_bs) {              // cur == fr_tail: the chain stopped here, at a record it could not step over
+            const i64 bs = b->fr_tail_bs;
+            if (bs < 32) return fail(b, CSV_E_INVALID, "%srecord with block_size < 32 at inflated byte %lld", "", (long long)cur);
+            if (cur + 4 + bs > b->utotal) return fail(b, CSV_E_INVALID, "%sthe file ends inside a record (at inflated byte %lld)", "", (long long)cur);
+            need = 4 + bs;
+        }
+        if (csv_frame_window_serial(b->frame) != b->fr_serial) b->win_n = 0;       // (another reader of the context loaded its window since)
+        bool have;
+        int rc = ensure(b, cur, need, &have);
+        if (rc) return rc;
+        b->t_off.clear(); b->t_len.clear();
+        for (size_t j = b->win_b0; j < b->win_b1; j++) { b->t_off.push_back(b->blocks[j].uoff - b->win_u0); b->t_len.push_back((int32_t)b->blocks[j].isize); }
+        csv::FrStitch R;
+        rc = csv_frame_run(b->frame, (int32_t)b->t_off.size(), b->t_off.data(), b->t_len.data(), b->n_ref, cur - b->win_u0, &b->fr_rows, &R);
+        if (rc) return fail(b, rc, "the device framing failed: %s", csv_last_error(b->frame));
+        b->fr_n = R.n_records; b->fr_i = 0; b->fr_from = cur; b->fr_tail = b->win_u0 + R.tail;
+        b->fr_tail_bs = R.tail_bs; b->fr_tail_has_bs = R.tail_has_bs != 0; b->fr_valid = true;
+    }
+    return fail(b, CSV_E_INVALID, "%sthe device framing made no progress at inflated byte %lld", "", (long long)b->cur);
+}
+
 // csv_bam_read / csv_bam_read_ranges: the records of contig `refid` that overlap one of the sorted, disjoint ranges, in file order
 int read_ranges(csv_bam* b, int32_t refid, size_t nr, const int64_t* rbeg, const int64_t* rend, int64_t max_records, int32_t flags, csv_bam_chunk* out)
 {
@@ -446,6 +656,9 @@ int read_ranges(csv_bam* b, int32_t refid, size_t nr, const int64_t* rbeg, const
     b->ms_inflate = 0; b->inflated = b->compressed = 0;
     b->device_blocks = b->fallback_blocks = 0; b->ms_kernels = 0;
     b->slim.clear(); b->host.clear(); b->rec_off.clear(); b->host_off.clear(); b->rec_len.clear();
+    b->pending.clear(); b->l_name_v.clear(); b->l_seq_v.clear(); b->slim_size = b->host_size = 0; b->framed_chunk = false;
+    const bool framed = b->frame != nullptr;
+    if (framed) { csv_frame_chunk_begin(b->frame, b); csv_frame_counters(b->frame, nullptr, nullptr, nullptr, nullptr, nullptr, 1); }
     const bool count_only = (flags & CSV_BAM_COUNT_ONLY) != 0;
     const uint32_t key = (uint32_t)refid;
     const bool indexed = b->has_index && refid >= 0 && refid < b->n_ref;
@@ -472,26 +685,24 @@ int read_ranges(csv_bam* b, int32_t refid, size_t nr, const int64_t* rbeg, const
     bool more = false;
     int rc = CSV_OK;
     while (!done) {
-        const uint8_t* p = at(b, b->cur, 4, &rc);
+        Rec r;
+        bool at_end;
+        rc = framed ? next_framed(b, &r, &at_end) : next_host(b, &r, &at_end);
         if (rc) return rc;
-        if (!p) {
-            if (b->cur != b->utotal) return fail(b, CSV_E_INVALID, "%sthe file ends inside a record (at inflated byte %lld)", "", (long long)b->cur);
+        if (at_end) {
             b->scanned_key = 0xffffffffu; b->scanned_any = true;
             break;
         }
-        const i64 bs = rd_i32(p);
-        if (bs < 32) return fail(b, CSV_E_INVALID, "%srecord with block_size < 32 at inflated byte %lld", "", (long long)b->cur);
-        p = at(b, b->cur + 4, bs, &rc);
-        if (rc) return rc;
-        if (!p) return fail(b, CSV_E_INVALID, "%sthe file ends inside a record (at inflated byte %lld)", "", (long long)b->cur);
-        const uint32_t rkey = (uint32_t)rd_i32(p);
+        const uint8_t* p = r.p;
+        const i64 bs = r.bs;
+        const uint32_t rkey = r.rkey;
         if (!(b->seeked && rkey == b->seek_key)) {           // (a scan the index positioned does not see the first record of its contig)
             if (!b->contig_at.count(rkey)) b->contig_at[rkey] = b->cur;
             if (!b->scanned_any || rkey > b->scanned_key) { b->scanned_key = rkey; b->scanned_any = true; }
         }
         if (rkey > key) break;                               // the next contig (the unmapped tail sorts last): not consumed
         if (rkey < key) { b->cur += 4 + bs; continue; }
-        const i64 pos = rd_i32(p + 4), l_name = p[8], n_cig = rd_u16(p + 12), l_seq = rd_u32(p + 16);
+        const i64 pos = r.pos, l_name = r.l_name, n_cig = r.n_cig, l_seq = r.l_seq;
         const i64 fixed_to_aux = 32 + l_name + 4 * n_cig + (l_seq + 1) / 2 + l_seq;
         if (fixed_to_aux > bs) return fail(b, CSV_E_INVALID, "%srecord fields exceed its block_size at inflated byte %lld", "", (long long)b->cur);
         if (pos >= rend[ri]) {                               // sorted: nothing later can start before this range's end - on to the next range
@@ -504,12 +715,15 @@ int read_ranges(csv_bam* b, int32_t refid, size_t nr, const int64_t* rbeg, const
         }
         if (pos < rbeg[ri]) {                                // overlaps the range only if it reaches past its begin (and then no later one: they are disjoint)
             const i64 beg = rbeg[ri];
-            i64 span = 0;
-            const uint8_t* cg = p + 32 + l_name;
-            for (i64 k = 0; k < n_cig; k++) {
-                const uint32_t w = rd_u32(cg + 4 * k);
-                const uint32_t op = w & 15u;
-                if (op == 0 || op == 2 || op == 3 || op == 7 || op == 8) span += w >> 4;
+            i64 span = r.span;                               // (the row's on the framing route)
+            if (p) {
+                span = 0;
+                const uint8_t* cg = p + 32 + l_name;
+                for (i64 k = 0; k < n_cig; k++) {
+                    const uint32_t w = rd_u32(cg + 4 * k);
+                    const uint32_t op = w & 15u;
+                    if (op == 0 || op == 2 || op == 3 || op == 7 || op == 8) span += w >> 4;
+                }
             }
             if (pos + (span ? span : 1) <= beg) { b->cur += 4 + bs; continue; }
         }
@@ -517,7 +731,16 @@ int read_ranges(csv_bam* b, int32_t refid, size_t nr, const int64_t* rbeg, const
         // (every record in front of this one ends at or before the begin of the range it is emitted for: those tested against an
         // earlier range end before that range's begin, those the index jumped over overlap no window from this range's on)
         if (n == 0 && set_hint) { b->hint_key = key; b->hint_beg = rbeg[ri]; b->hint_at = b->cur; }
-        if (!count_only) {
+        if (!count_only && framed) {                         // the same layout, in the device images: packed when the window is left
+            const i64 aux_len = bs - fixed_to_aux, slim_len = 32 + 4 * n_cig + aux_len;
+            csv::FrPack q{};
+            q.src = r.src; q.rec_off = b->slim_size; q.host_off = b->host_size; q.bs = (int32_t)bs; q.l_seq = (uint32_t)l_seq; q.n_cig = (uint16_t)n_cig; q.l_name = (uint8_t)l_name;
+            b->pending.push_back(q);
+            b->rec_off.push_back(b->slim_size); b->rec_len.push_back((uint32_t)slim_len); b->host_off.push_back(b->host_size);
+            b->l_name_v.push_back((int32_t)l_name); b->l_seq_v.push_back((int32_t)(uint32_t)l_seq);
+            b->slim_size += (slim_len + SLIM_ALIGN - 1) / SLIM_ALIGN * SLIM_ALIGN;
+            b->host_size += l_name + (l_seq + 1) / 2;
+        } else if (!count_only) {
             const i64 aux_len = bs - fixed_to_aux, slim_len = 32 + 4 * n_cig + aux_len;
             const size_t s0 = b->slim.size();
             b->rec_off.push_back((i64)s0);
@@ -539,11 +762,20 @@ int read_ranges(csv_bam* b, int32_t refid, size_t nr, const int64_t* rbeg, const
         b->cur += 4 + bs;
     }
     b->range_i = ri;
-    b->host_off.push_back((i64)b->host.size());
+    if (framed) {
+        rc = frame_flush(b);
+        if (rc) return rc;
+        if (!count_only) {
+            rc = csv_frame_chunk_end(b->frame, n, b->rec_off.data(), b->rec_len.data(), b->host_off.data(), b->l_name_v.data(), b->l_seq_v.data());
+            if (rc) return fail(b, rc, "the device framing failed: %s", csv_last_error(b->frame));
+            b->framed_chunk = true;
+        }
+    }
+    b->host_off.push_back(framed ? b->host_size : (i64)b->host.size());
     out->n_records = n; out->more = more ? 1 : 0;
-    out->slim = b->slim.data(); out->slim_bytes = (int64_t)b->slim.size();
+    out->slim = framed ? nullptr : b->slim.data(); out->slim_bytes = framed ? b->slim_size : (int64_t)b->slim.size();
     out->rec_off = b->rec_off.data(); out->rec_len = b->rec_len.data();
-    out->host = b->host.data(); out->host_bytes = (int64_t)b->host.size(); out->host_off = b->host_off.data();
+    out->host = framed ? nullptr : b->host.data(); out->host_bytes = framed ? b->host_size : (int64_t)b->host.size(); out->host_off = b->host_off.data();
     out->inflated_bytes = b->inflated; out->compressed_bytes = b->compressed;
     out->ms_inflate = b->ms_inflate; out->ms_frame = now_ms() - t0 - b->ms_inflate;
     return CSV_OK;

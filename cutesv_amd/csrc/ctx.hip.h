@@ -158,6 +158,33 @@ struct InflateState {
     void own(std::vector<Buf*>& v) { v.insert(v.end(), {&comp, &tab, &out, &status}); }
 };
 
+// Record framing on the device (stage_frame.hip.h), all stand-alone and grow-only.  win: the two window
+// buffers of the reader - win[cur] holds the inflated window [0, win_n), the other one receives the next window, whose kept tail is
+// copied over from win[cur] (two buffers: no copy overlaps).  tab (block tables, guesses, exits, counts, the scan's work space, the
+// stitch's verdict), starts, rows, pack: dead when a csv_frame_run / csv_frame_pack returns.  slim / host: the device images of the
+// chunk the reader `owner` handed out last, with the host copies of its offset and length columns; they live until that reader's
+// next read or route change (chunk_ok), and the *_framed consumers read them there (the decode copies the slim image device to
+// device into BamState's arena, where the later stages expect it).  One reader frames on a context at a time (reader).  No other stage reads or writes any of
+// this, and the entries touch nothing else of the context but its stream and its first four timing events.
+struct FrameState {
+    Buf win[2], tab, starts, rows, pack, slim, host, cols;
+    int cur = 0;
+    i64 win_n = 0;
+    uint64_t serial = 0;                       // windows loaded so far (csv_frame_window_serial)
+    std::vector<char> tab_h;
+    std::vector<FrRow> rows_h;
+    const void* reader = nullptr;              // the one reader that frames on this context (csv_bam_set_frame)
+    const void* owner = nullptr;
+    bool chunk_ok = false;
+    i64 n = 0, slim_bytes = 0, host_bytes = 0;
+    std::vector<int64_t> rec_off, host_off;
+    std::vector<uint32_t> rec_len;
+    std::vector<int32_t> l_name, l_seq;
+    i64 right = 0, fallback = 0, bytes_down = 0, bytes_up = 0;
+    double ms_kernels = 0;
+    void own(std::vector<Buf*>& v) { v.insert(v.end(), {&win[0], &win[1], &tab, &starts, &rows, &pack, &slim, &host, &cols}); }
+};
+
 // ---- The state of the engine (stage_upload / stage_run / stage_results.hip.h): the path csv_batch_upload -> csv_batch_run ->
 // csv_batch_download / csv_batch_publish_* and the one-shot csv_cluster_batch.  One struct per concern, with the same kind of rule.
 
@@ -292,7 +319,7 @@ struct csv_ctx {
     BatchState bt; ReadsOrderState ro; ResultState res; TableState tab;
     // ---- the extraction-side stages (their lifetime rules: at the structs)
     PoolState pool; NameState nm; BamState bm; SaState sa; SeqState seq; VcfStrState vs; AlnState al; ReadsTabState rt;
-    RebuildState rb; CigarState cg; SplitState sp; InflateState inf;
+    RebuildState rb; CigarState cg; SplitState sp; InflateState inf; FrameState fr;
 };
 
 namespace {
@@ -395,6 +422,21 @@ int h2d(csv_ctx* c, const Buf& b, const void* src, i64 bytes)
 int d2h(csv_ctx* c, void* dst, const Buf& b, i64 bytes, bool required)
 {
     if (bytes > 0 && (dst || required)) HIP_TRY(c, hipMemcpyAsync(dst, b.p, (size_t)bytes, hipMemcpyDeviceToHost, c->stream));
+    return CSV_OK;
+}
+
+// len[i] bytes at dev_src + src_off[i] -> dst + dst_off[i] for i < n, on the device (k_frame_gather): src_off / len are the caller's
+// host columns (checked by the caller, alive until it synchronises), dst_off lies in device memory; FrameState::cols carries the tables
+int frame_gather(csv_ctx* c, i64 n, const uint8_t* dev_src, const int64_t* src_off, const int32_t* len, uint8_t* dst, const i64* dst_off)
+{
+    if (n <= 0) return CSV_OK;
+    TRY(reserve(c, c->fr.cols, (size_t)n * 12 + 16));
+    char* t = (char*)c->fr.cols.p;
+    HIP_TRY(c, hipMemcpyAsync(t, src_off, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(t + (size_t)n * 8, len, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+    c->fr.bytes_up += n * 12;
+    hipLaunchKernelGGL(k_frame_gather, dim3(std::min(div_up(n, 4), 8192)), dim3(256), 0, c->stream, dev_src, (const i64*)t, (const int*)(t + (size_t)n * 8), n, dst, dst_off);
+    HIP_TRY(c, hipGetLastError());
     return CSV_OK;
 }
 

@@ -2,7 +2,9 @@
 // entry columns of the split-read analysis (BamState / SaState in ctx.hip.h; bam.hip.h, sa.hip.h).  Host code; included by cutesv_hip.hip.
 extern "C" {
 
-int csv_bam_decode(csv_ctx* c, const csv_bam_in* in, csv_bam_out* out)
+// csv_bam_decode; with dev_slim (csv_bam_decode_framed, stage_frame.hip.h) the slim image lies in device memory already and is copied
+// there: what crosses the link is rec_off and rec_len alone
+static int bam_decode_impl(csv_ctx* c, const csv_bam_in* in, csv_bam_out* out, const uint8_t* dev_slim)
 {
     if (!c || !in || !out) return CSV_E_INVALID;
     HIP_TRY(c, hipSetDevice(c->device));
@@ -11,7 +13,7 @@ int csv_bam_decode(csv_ctx* c, const csv_bam_in* in, csv_bam_out* out)
         out->dev_cls = out->dev_cig_off = out->dev_cigar = nullptr;
     c->bm.n = -1; c->bm.gates_ok = false; c->sa.calls = -1; c->seq.n_reads = -1; c->seq.n_qrev = -1;      // (the uploaded read sequences belong to the previous batch)
     const i64 n = in->n_records, nb = in->slim_bytes;
-    if (n < 0 || nb < 0 || in->flags != 0 || (n > 0 && (!in->slim || !in->rec_off || !in->rec_len))) return fail(c, CSV_E_INVALID, "bad BAM chunk header");
+    if (n < 0 || nb < 0 || in->flags != 0 || (n > 0 && ((!in->slim && !dev_slim) || !in->rec_off || !in->rec_len))) return fail(c, CSV_E_INVALID, "bad BAM chunk header");
     if (n >= (1ll << 31) - 4096) return fail(c, CSV_E_INVALID, "BAM chunk too large (%lld records): split it", (long long)n);
     // the kernels read [rec_off, rec_off + rec_len) of every record and nothing else: each range is checked against the image
     for (i64 r = 0; r < n; r++) {
@@ -28,9 +30,11 @@ int csv_bam_decode(csv_ctx* c, const csv_bam_in* in, csv_bam_out* out)
     TRY(commit_synced(c, c->bm.arena, P));
     hipStream_t st = c->stream;
     HIP_TRY(c, hipEventRecord(c->ev[4], st));
-    TRY(h2d(c, c->bm.slim, in->slim, nb)); TRY(h2d(c, c->bm.recoff, in->rec_off, n * 8)); TRY(h2d(c, c->bm.reclen, in->rec_len, n * 4));
+    if (dev_slim) { if (nb > 0) HIP_TRY(c, hipMemcpyAsync(c->bm.slim.p, dev_slim, (size_t)nb, hipMemcpyDeviceToDevice, st)); }
+    else TRY(h2d(c, c->bm.slim, in->slim, nb));
+    TRY(h2d(c, c->bm.recoff, in->rec_off, n * 8)); TRY(h2d(c, c->bm.reclen, in->rec_len, n * 4));
     HIP_TRY(c, hipEventRecord(c->ev[5], st));
-    out->bytes_uploaded = nb + n * 12;
+    out->bytes_uploaded = (dev_slim ? 0 : nb) + n * 12;
     HIP_TRY(c, hipMemsetAsync(c->bm.cnt.p, 0, 16, st));
     BamArgs A{};
     A.n = n; A.slim = dp<uint8_t>(c->bm.slim); A.rec_off = dp<i64>(c->bm.recoff); A.rec_len = dp<unsigned>(c->bm.reclen);
@@ -78,6 +82,8 @@ int csv_bam_decode(csv_ctx* c, const csv_bam_in* in, csv_bam_out* out)
     c->bm.n = n; c->bm.nops = tot[0]; c->bm.nsa = tot[1];
     return CSV_OK;
 }
+
+int csv_bam_decode(csv_ctx* c, const csv_bam_in* in, csv_bam_out* out) { return bam_decode_impl(c, in, out, nullptr); }
 
 int csv_sa_struct_size(int which) { return which == 0 ? (int)sizeof(csv_sa_in) : which == 1 ? (int)sizeof(csv_sa_out) : -1; }
 

@@ -3,16 +3,16 @@
 // (ctx.hip.h): no arena is planned, no generation word moves, and nothing another stage left on the device is touched.
 // Host code; included by cutesv_hip.hip behind stage_bam.hip.h.
 
-extern "C" {
-
-int csv_bgzf_inflate(csv_ctx* c, const uint8_t* comp, int64_t comp_bytes, int32_t n_blocks, const int64_t* in_off, const int32_t* in_len, const int64_t* out_off,
-                     const int32_t* out_len, const uint32_t* crc, uint8_t* out, int64_t out_bytes, int32_t flags, uint8_t* status, double* ms_kernels)
+// csv_bgzf_inflate, and its internal form (dev_out != NULL; stage_frame.hip.h): the bytes are written to dev_out - device memory of
+// out_bytes bytes - and stay there; `out` is not touched.  The checks, the tables and the status bytes are the same.
+static int inflate_impl(csv_ctx* c, const uint8_t* comp, int64_t comp_bytes, int32_t n_blocks, const int64_t* in_off, const int32_t* in_len, const int64_t* out_off,
+                        const int32_t* out_len, const uint32_t* crc, uint8_t* out, uint8_t* dev_out, int64_t out_bytes, int32_t flags, uint8_t* status, double* ms_kernels)
 {
     if (!c) return CSV_E_INVALID;
     if (ms_kernels) *ms_kernels = 0;
     if (n_blocks < 0 || comp_bytes < 0 || out_bytes < 0 || flags != 0) return fail(c, CSV_E_INVALID, "bad bgzf inflate");
     if (n_blocks == 0) return CSV_OK;
-    if (!in_off || !in_len || !out_off || !out_len || !crc || !status || (comp_bytes > 0 && !comp) || (out_bytes > 0 && !out)) return fail(c, CSV_E_INVALID, "bad bgzf inflate");
+    if (!in_off || !in_len || !out_off || !out_len || !crc || !status || (comp_bytes > 0 && !comp) || (out_bytes > 0 && !out && !dev_out)) return fail(c, CSV_E_INVALID, "bad bgzf inflate");
     InflateState& s = c->inf;
     // every range is checked before anything is launched: the kernel trusts them
     s.order.clear();
@@ -41,19 +41,19 @@ int csv_bgzf_inflate(csv_ctx* c, const uint8_t* comp, int64_t comp_bytes, int32_
     memcpy(s.tab_h.data() + o_in_len, in_len, 4 * n); memcpy(s.tab_h.data() + o_out_len, out_len, 4 * n); memcpy(s.tab_h.data() + o_crc, crc, 4 * n);
     TRY(reserve(c, s.comp, (size_t)comp_bytes + 8));
     TRY(reserve(c, s.tab, 28 * n));
-    TRY(reserve(c, s.out, (size_t)out_bytes + 8));
+    if (!dev_out) TRY(reserve(c, s.out, (size_t)out_bytes + 8));
     TRY(reserve(c, s.status, n));
     TRY(h2d(c, s.comp, comp, comp_bytes));
     TRY(h2d(c, s.tab, s.tab_h.data(), (i64)(28 * n)));
     char* t = (char*)s.tab.p;
     const InflateArgs A{(int)n_blocks, dp<uint8_t>(s.comp), (const i64*)t, (const int*)(t + o_in_len), (const i64*)(t + o_out_off), (const int*)(t + o_out_len),
-                        (const unsigned*)(t + o_crc), dp<uint8_t>(s.out), dp<uint8_t>(s.status)};
+                        (const unsigned*)(t + o_crc), dev_out ? dev_out : dp<uint8_t>(s.out), dp<uint8_t>(s.status)};
     HIP_TRY(c, hipEventRecord(c->ev[0], st));
     hipLaunchKernelGGL(k_bgzf_inflate, dim3(std::min(div_up(n_blocks, INF_WAVES), 8192)), dim3(64 * INF_WAVES), 0, st, A);
     HIP_TRY(c, hipEventRecord(c->ev[1], st));
     HIP_TRY(c, hipGetLastError());
     // the bytes come back in runs of adjacent outputs (a reader's window: one run), so that no byte of `out` between two blocks is written
-    for (size_t i = 0; i < s.order.size();) {
+    for (size_t i = 0; !dev_out && i < s.order.size();) {
         size_t j = i + 1;
         while (j < s.order.size() && out_off[s.order[j - 1]] + out_len[s.order[j - 1]] == out_off[s.order[j]]) j++;
         const int64_t b0 = out_off[s.order[i]], b1 = out_off[s.order[j - 1]] + out_len[s.order[j - 1]];
@@ -68,6 +68,14 @@ int csv_bgzf_inflate(csv_ctx* c, const uint8_t* comp, int64_t comp_bytes, int32_
         *ms_kernels = ms;
     }
     return CSV_OK;
+}
+
+extern "C" {
+
+int csv_bgzf_inflate(csv_ctx* c, const uint8_t* comp, int64_t comp_bytes, int32_t n_blocks, const int64_t* in_off, const int32_t* in_len, const int64_t* out_off,
+                     const int32_t* out_len, const uint32_t* crc, uint8_t* out, int64_t out_bytes, int32_t flags, uint8_t* status, double* ms_kernels)
+{
+    return inflate_impl(c, comp, comp_bytes, n_blocks, in_off, in_len, out_off, out_len, crc, out, nullptr, out_bytes, flags, status, ms_kernels);
 }
 
 }  // extern "C"

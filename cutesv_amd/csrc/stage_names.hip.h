@@ -18,10 +18,12 @@ int csv_name_pool_rows(const csv_ctx* c, int64_t* n)
     return CSV_OK;
 }
 
-int csv_name_pool_append(csv_ctx* c, int64_t n, const uint8_t* bytes, int64_t n_bytes, const int64_t* off, const int32_t* len, int64_t* first_index)
+// csv_name_pool_append; with dev_bytes (csv_name_pool_append_framed, stage_frame.hip.h) the n_bytes bytes lie in device memory and the
+// names are gathered there (k_frame_gather): what crosses the link is the offset table alone
+static int name_pool_append_impl(csv_ctx* c, int64_t n, const uint8_t* bytes, const uint8_t* dev_bytes, int64_t n_bytes, const int64_t* off, const int32_t* len, int64_t* first_index)
 {
     if (!c) return CSV_E_INVALID;
-    if (n < 0 || n_bytes < 0 || (n > 0 && (!off || !len)) || (n_bytes > 0 && !bytes)) return fail(c, CSV_E_INVALID, "bad name pool append");
+    if (n < 0 || n_bytes < 0 || (n > 0 && (!off || !len)) || (n_bytes > 0 && !bytes && !dev_bytes)) return fail(c, CSV_E_INVALID, "bad name pool append");
     // every range is checked before the pool changes or anything is launched
     i64 total = 0; int mx = 0;
     for (i64 i = 0; i < n; i++) {
@@ -37,20 +39,21 @@ int csv_name_pool_append(csv_ctx* c, int64_t n, const uint8_t* bytes, int64_t n_
     c->vs.stale();
     HIP_TRY(c, hipSetDevice(c->device));
     // the names back to back and their offsets in the pool's blob: what crosses the link (a chunk's host image also holds the bases)
-    std::vector<uint8_t> blob((size_t)total);
+    std::vector<uint8_t> blob(dev_bytes ? 0 : (size_t)total);
     std::vector<i64> offs((size_t)n + 1);
     i64 at = 0;
     for (i64 i = 0; i < n; i++) {
         offs[(size_t)i] = c->nm.bytes + at;
-        if (len[i]) memcpy(blob.data() + at, bytes + off[i], (size_t)len[i]);
+        if (len[i] && !dev_bytes) memcpy(blob.data() + at, bytes + off[i], (size_t)len[i]);
         at += len[i];
     }
     offs[(size_t)n] = c->nm.bytes + at;
     TRY(grow_keep(c, c->nm.blob, (size_t)(c->nm.bytes + total) + 8, (size_t)c->nm.bytes));
     TRY(grow_keep(c, c->nm.off, (size_t)(c->nm.n + n + 1) * 8, c->nm.n ? (size_t)(c->nm.n + 1) * 8 : 0));
     hipStream_t st = c->stream;
-    if (total) HIP_TRY(c, hipMemcpyAsync((char*)c->nm.blob.p + c->nm.bytes, blob.data(), (size_t)total, hipMemcpyHostToDevice, st));
+    if (total && !dev_bytes) HIP_TRY(c, hipMemcpyAsync((char*)c->nm.blob.p + c->nm.bytes, blob.data(), (size_t)total, hipMemcpyHostToDevice, st));
     HIP_TRY(c, hipMemcpyAsync(dp<i64>(c->nm.off) + c->nm.n, offs.data(), (size_t)(n + 1) * 8, hipMemcpyHostToDevice, st));
+    if (total && dev_bytes) TRY(frame_gather(c, n, dev_bytes, off, len, dp<uint8_t>(c->nm.blob), dp<i64>(c->nm.off) + c->nm.n));
     HIP_TRY(c, hipStreamSynchronize(st));                   // (the vectors are the copies' sources)
     c->nm.len.reserve((size_t)(c->nm.n + n));
     for (i64 i = 0; i < n; i++) c->nm.len.push_back((uint8_t)len[i]);
@@ -58,6 +61,11 @@ int csv_name_pool_append(csv_ctx* c, int64_t n, const uint8_t* bytes, int64_t n_
     c->nm.maxlen = mx > c->nm.maxlen ? mx : c->nm.maxlen;
     c->nm.fresh = false;
     return CSV_OK;
+}
+
+int csv_name_pool_append(csv_ctx* c, int64_t n, const uint8_t* bytes, int64_t n_bytes, const int64_t* off, const int32_t* len, int64_t* first_index)
+{
+    return name_pool_append_impl(c, n, bytes, nullptr, n_bytes, off, len, first_index);
 }
 
 // the ranks of the pool's names into nm.rank / nm.first (nothing to do while they are fresh)

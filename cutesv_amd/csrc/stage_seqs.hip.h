@@ -24,10 +24,12 @@ static const char* seq_why(int err)
          : "the length of a row's bases is not its aux (query_len must be the uploaded l_seq)";
 }
 
-int csv_seq_reads_upload(csv_ctx* c, int64_t n, const uint8_t* bytes, int64_t n_bytes, const int64_t* off, const int32_t* l_seq, const uint8_t* want)
+// csv_seq_reads_upload; with dev_bytes (csv_seq_reads_framed, stage_frame.hip.h) the n_bytes bytes lie in device memory and the wanted
+// reads are packed there (k_frame_gather): what crosses the link is the offset and length tables alone
+static int seq_reads_upload_impl(csv_ctx* c, int64_t n, const uint8_t* bytes, const uint8_t* dev_bytes, int64_t n_bytes, const int64_t* off, const int32_t* l_seq, const uint8_t* want)
 {
     if (!c) return CSV_E_INVALID;
-    if (n < 0 || n_bytes < 0 || (n > 0 && (!off || !l_seq)) || (n_bytes > 0 && !bytes)) return fail(c, CSV_E_INVALID, "bad read sequence upload");
+    if (n < 0 || n_bytes < 0 || (n > 0 && (!off || !l_seq)) || (n_bytes > 0 && !bytes && !dev_bytes)) return fail(c, CSV_E_INVALID, "bad read sequence upload");
     if (n >= (1ll << 31) - 4096) return fail(c, CSV_E_INVALID, "too many reads (%lld): split the batch", (long long)n);
     // every range is checked before the state changes or anything is launched
     i64 total = 0, n_want = 0;
@@ -41,29 +43,38 @@ int csv_seq_reads_upload(csv_ctx* c, int64_t n, const uint8_t* bytes, int64_t n_
     const auto t0 = std::chrono::steady_clock::now();
     SeqState& s = c->seq;
     // the wanted reads are packed back to back first (CSV_SEQ_OPT_WHOLE_IMAGE, a measurement aid: the image goes as it is)
-    const bool whole = s.whole;
+    const bool whole = s.whole && !dev_bytes;
     std::vector<uint8_t> img;
+    std::vector<int> nbs(dev_bytes ? (size_t)n : 0);
     std::vector<i64> offs((size_t)n);
     std::vector<int> lens((size_t)n);
-    if (!whole) img.resize((size_t)total);
+    if (!whole && !dev_bytes) img.resize((size_t)total);
     i64 at = 0;
     for (i64 i = 0; i < n; i++) {
         const bool w = !want || want[i];
         const i64 nb = w ? ((i64)l_seq[i] + 1) / 2 : 0;
         lens[(size_t)i] = w ? l_seq[i] : -1;
         offs[(size_t)i] = whole ? off[i] : at;
-        if (!whole && nb) memcpy(img.data() + at, bytes + off[i], (size_t)nb);
+        if (!whole && nb && !dev_bytes) memcpy(img.data() + at, bytes + off[i], (size_t)nb);
+        if (dev_bytes) nbs[(size_t)i] = (int)nb;
         at += nb;
     }
     const i64 sent = whole ? n_bytes : total;
     s.n_reads = -1; s.n_qrev = -1;
     TRY(reserve(c, s.rbytes, (size_t)sent + 8)); TRY(reserve(c, s.roff, (size_t)n * 8 + 8)); TRY(reserve(c, s.rlen, (size_t)n * 4 + 8));
-    TRY(h2d(c, s.rbytes, whole ? bytes : img.data(), sent)); TRY(h2d(c, s.roff, offs.data(), n * 8)); TRY(h2d(c, s.rlen, lens.data(), n * 4));
+    if (!dev_bytes) TRY(h2d(c, s.rbytes, whole ? bytes : img.data(), sent));
+    TRY(h2d(c, s.roff, offs.data(), n * 8)); TRY(h2d(c, s.rlen, lens.data(), n * 4));
+    if (dev_bytes && total) TRY(frame_gather(c, n, dev_bytes, off, nbs.data(), dp<uint8_t>(s.rbytes), dp<i64>(s.roff)));
     HIP_TRY(c, hipStreamSynchronize(c->stream));             // (the vectors are the copies' sources)
     s.n_reads = n;
-    s.info.reads_uploaded = n_want; s.info.bytes_uploaded = sent + n * 12; s.info.packed = whole ? 0 : 1;
+    s.info.reads_uploaded = n_want; s.info.bytes_uploaded = (dev_bytes ? 0 : sent) + n * 12; s.info.packed = whole ? 0 : 1;
     s.info.ms_upload = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return CSV_OK;
+}
+
+int csv_seq_reads_upload(csv_ctx* c, int64_t n, const uint8_t* bytes, int64_t n_bytes, const int64_t* off, const int32_t* l_seq, const uint8_t* want)
+{
+    return seq_reads_upload_impl(c, n, bytes, nullptr, n_bytes, off, l_seq, want);
 }
 
 int csv_seq_option(csv_ctx* c, int which, int value)

@@ -63,15 +63,26 @@ def _negotiate(fn, handle, cin, out_type, table, classes, give, check, what, lon
     raise RuntimeError("%s: capacity retry failed" % what)
 
 
-def upload_read_sequences(ctx, data, off, l_seq, want=None):
+def upload_read_sequences(ctx, data, off=None, l_seq=None, want=None):
     """csv_seq_reads_upload: the 4-bit sequences of the current batch's reads - read i = the (l_seq[i] + 1) // 2 bytes at
     data[off[i]:], high nibble first (data: uint8 array or bytes; for a bam.Chunk: chunk.host and chunk.sequence_columns()) - go to
     the device, where the calls with pool=dict(..., seqs=True) cut the INS rows' bases out of them.  want: per read, 0 = its bases
     are not needed (and are not sent).  They stay until the next upload or bam.decode.  The library checks every range
-    (CsvError E_INVALID, nothing changes)."""
+    (CsvError E_INVALID, nothing changes).
+    data = a bam.FramedChunk (off and l_seq None): csv_seq_reads_framed takes the sequences out of its device image."""
+    want = None if want is None else np.ascontiguousarray(want, np.uint8)
+    if getattr(data, "framed", False):
+        chunk = data
+        if not chunk.fetched and chunk.ctx is ctx:
+            chunk.check()
+            if want is not None and len(want) != chunk.n:
+                raise ValueError("one offset, one length and (with `want`) one flag per read are expected")
+            ctx._check(lib().csv_seq_reads_framed(ctx._h, None if want is None or not chunk.n else want.ctypes.data))
+            return
+        off, l_seq = chunk.sequence_columns()
+        data = chunk.host
     data = np.frombuffer(data, np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else np.ascontiguousarray(data, np.uint8)
     off = np.ascontiguousarray(off, np.int64); l_seq = np.ascontiguousarray(l_seq, np.int32)
-    want = None if want is None else np.ascontiguousarray(want, np.uint8)
     if len(off) != len(l_seq) or (want is not None and len(want) != len(off)):
         raise ValueError("one offset, one length and (with `want`) one flag per read are expected")
     n = len(off)
@@ -807,8 +818,12 @@ def task_to_pool(ctx, bamfile, chrom, task_start, task_end, chrom_rank, sv_size,
         from . import reads as reads_mod
         n_rows = reads_mod.append_decoded(ctx, chrom_rank[chrom], chunk.n, read_base, keep=None if bits is not None else in_table)
     if seq_pool:
-        s_off, l_seq = chunk.sequence_columns()
-        upload_read_sequences(ctx, chunk.host, s_off, l_seq, want=(use != 0) | sel if bits is None else (bits & (_abi.GATE_USE | _abi.GATE_SEL)) != 0)
+        want = (use != 0) | sel if bits is None else (bits & (_abi.GATE_USE | _abi.GATE_SEL)) != 0
+        if getattr(chunk, "framed", False):
+            upload_read_sequences(ctx, chunk, want=want)
+        else:
+            s_off, l_seq = chunk.sequence_columns()
+            upload_read_sequences(ctx, chunk.host, s_off, l_seq, want=want)
     sig = cigar_signatures(ctx, None, None, None, use, min_siglength=min_siglength, merge_ins_threshold=merge_ins_threshold, merge_del_threshold=merge_del_threshold,
                            pool=dict(seg_ins=seg_ins, seg_del=seg_del, read_base=read_base, query_len=qlen, seqs=seq_pool), host_outputs=False, from_bam=cols)
     si, dsig, calls, reads, fsig = _split_on_device(ctx, chunk, cols, sel, chrom, chrom_rank, min_mapq,

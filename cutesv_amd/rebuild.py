@@ -342,6 +342,11 @@ def name_pool_append(ctx, data, off, length):
 
 def name_pool_append_chunk(ctx, chunk):
     """the read names of a bam.Chunk, straight out of its host image: name index = returned base + record index"""
+    if getattr(chunk, "framed", False) and not chunk.fetched and chunk.ctx is ctx:      # (a device chunk: csv_name_pool_append_framed takes the names where they lie)
+        chunk.check()
+        first = C.c_int64(0)
+        ctx._check(lib().csv_name_pool_append_framed(ctx._h, C.byref(first)))
+        return int(first.value)
     off, length = chunk.name_columns()
     return name_pool_append(ctx, chunk.host, off, length)
 

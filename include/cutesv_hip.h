@@ -967,6 +967,36 @@ int csv_bam_set_inflate(csv_bam* bam, csv_ctx* ctx, int32_t window_blocks);
 /* since the start of the last csv_bam_read: blocks the device inflated, blocks the host inflated again, device time of the kernels */
 int csv_bam_inflate_stats(const csv_bam* bam, int64_t* device_blocks, int64_t* fallback_blocks, double* ms_kernels);
 
+/* Record framing on the device, opt-in.  ctx != NULL: it must be the context of the reader's device inflate
+ * route (csv_bam_set_inflate with the same ctx before; CSV_E_STATE otherwise).  From then on the inflated window stays in device
+ * memory: the records are found there (frame_core.h: one wavefront per BGZF block guesses a record start and chases the chain
+ * through its block, one lane stitches the blocks from the cursor - a guess that is not the offset the true chain arrives at is never
+ * used, that block is chased again serially), only a table of one 40-byte row per framed record comes down, the selection loop of
+ * csv_bam_read runs over the rows - the same checks in the same order, the same error texts - and the slim and the host image of the
+ * selected records are built in device memory.  ctx == NULL: back to host framing.  csv_bam_set_inflate also switches back.
+ * ONE reader frames on a context at a time: the window, the chunk and the *_framed consumers are the context's.  A second reader is
+ * refused with CSV_E_STATE until the first has switched back - which it must do before it is closed (csv_bam_close does not touch
+ * the context).
+ * On this route csv_bam_chunk has slim == NULL and host == NULL; the byte counts, rec_off, rec_len, host_off, the counters and the
+ * timings are filled as on the host route, and the images are, byte for byte, what the host route builds.  The device chunk is
+ * valid until the reader's next read or route change:
+ *   csv_bam_chunk_lengths   l_read_name and l_seq per record of the last chunk (either route; arrays of n_records, may be NULL)
+ *   csv_bam_chunk_fetch     downloads the two images (slim_bytes / host_bytes bytes; either may be NULL) - for checks and for the
+ *                           rare host fallbacks.  CSV_E_STATE: no device chunk of this reader is valid
+ *   csv_bam_frame_stats     since the start of the last read: blocks whose guess was the true chain's, blocks chased again (fallbacks),
+ *                           device time of the framing and pack kernels, bytes copied down and up by the framing route
+ *   csv_bam_decode_framed, csv_name_pool_append_framed, csv_seq_reads_framed   csv_bam_decode (flags 0), csv_name_pool_append (the
+ *                           names without their NUL) and csv_seq_reads_upload (`want` may be NULL) on the context's current device
+ *                           chunk: they behave as their host-pointer twins do on the fetched images, and no image visits the host
+ *                           (the decode copies the slim image device to device to where csv_bam_split_inputs and the gates expect it).
+ *                           CSV_E_STATE: the context holds no valid device chunk */
+int csv_bam_set_frame(csv_bam* bam, csv_ctx* ctx);
+int csv_bam_chunk_lengths(const csv_bam* bam, int32_t* l_read_name, int32_t* l_seq);
+int csv_bam_chunk_fetch(csv_bam* bam, uint8_t* slim, uint8_t* host);
+int csv_bam_frame_stats(const csv_bam* bam, int64_t* right_blocks, int64_t* fallback_blocks, double* ms_kernels, int64_t* bytes_down, int64_t* bytes_up);
+int csv_name_pool_append_framed(csv_ctx* ctx, int64_t* first_index);
+int csv_seq_reads_framed(csv_ctx* ctx, const uint8_t* want);
+
 /* Device side (bam.hip.h): the slim image of a chunk -> per-record columns, the packed CIGARs and the byte ranges of the
  * SA / CG tags, in device memory of the context (valid until its next csv_bam_decode; csv_cigar_signatures with
  * CSV_CG_FROM_BAM scans them in place, csv_bam_split_inputs parses the SA values there) and, for every host array that is not NULL, in the caller's memory.
@@ -1007,6 +1037,8 @@ typedef struct csv_bam_out {
 } csv_bam_out;
 
 int csv_bam_decode(csv_ctx* ctx, const csv_bam_in* in, csv_bam_out* out);
+/* csv_bam_decode on the context's current device chunk (csv_bam_set_frame, above) */
+int csv_bam_decode_framed(csv_ctx* ctx, csv_bam_out* out);
 
 /* The SA tags of the context's last csv_bam_decode -> the entry columns of csv_split_in, parsed on the device (sa.hip.h,
  * DESIGN.md section 14).  A CALL is one (record i with sel[i] != 0, SA tag of that record) pair, in record order and then
