@@ -96,6 +96,10 @@ SYMBOLS = [
     ("csv_bam_index_stats", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]),
     ("csv_bam_index_block", C.c_int64, [C.c_void_p, C.c_int32, C.c_int64]),
     ("csv_bam_read_ranges", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.POINTER(_abi.ChunkC)]),
+    ("csv_bam_index_build", C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int64)]),
+    ("csv_bam_index_bytes", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]),
+    ("csv_bam_index_build_stats", C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                                            C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     ("csv_bgzf_inflate", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32,
                                    C.c_void_p, C.POINTER(C.c_double)]),
     ("csv_bam_set_inflate", C.c_int, [C.c_void_p, C.c_void_p, C.c_int32]),

@@ -15,10 +15,17 @@ With frame="device"  the inflated window stays on the devi
 `FramedChunk` keeps its two images in the context's device memory (`slim` / `host` fetch them on first access), and `decode`,
 `rebuild.name_pool_append_chunk` and `extract.upload_read_sequences` take them where they lie.
 
+A file without a .bai gets one from `BamFile.build_index`: one pass over the file on the reader's routes -
+with frame="device" the index kernels work on the rows of every window, which stay on the device - and the bytes of a .bai
+file (SAMv1 5.2, htslib's conventions).  `BamFile(path, index="build")` loads the index beside the file when there is one and builds one in memory otherwise.
+
     python -m cutesv_amd.bam FILE [--chrom C] [--dump-columns DIR] [--inflate {host,device}] [--frame {host,device}] [--idxstats]
+    python -m cutesv_amd.bam FILE --index [--index_out PATH] [--force] [--inflate {host,device}] [--frame {host,device}]
 """
 import ctypes as C
 import os
+import tempfile
+import time
 import zlib
 
 import numpy as np
@@ -172,7 +179,8 @@ class BamFile:
         inflate: None or "host" - the BGZF blocks are inflated on `threads` host threads; an engine.Context - on its device
         (set_inflate).  The header is read on the host either way.
         index: None - <path>.bai, else <path minus .bam>.bai, is loaded when there is one; a path - that index, which must exist;
-        False - none.  An index that is found and does not validate against this file raises BamError."""
+        False - none; "build" - the index beside the file when there is one, else one is built in memory on the routes given
+        (build_index; nothing is written).  An index that is found and does not validate against this file raises BamError."""
         _frame_route(frame, _inflate_ctx(inflate))                           # (refused before the file is opened)
         L = self._L = lib()
         self._h = C.c_void_p()
@@ -203,9 +211,13 @@ class BamFile:
         self.set_inflate(inflate)
         self.set_frame(frame)
         self.has_index = False
+        self.index_stats = None
+        build = isinstance(index, str) and index == "build"
         if index is not False:
             try:
-                self.load_index(None if index is None or index is True else index, required=index is not None)
+                self.load_index(None if index is None or index is True or build else index, required=index is not None and not build)
+                if build and not self.has_index:
+                    self.build_index()
             except BamError:
                 self.close()
                 raise
@@ -221,6 +233,61 @@ class BamFile:
             raise BamError((self._L.csv_bam_error(self._h) or b"").decode(errors="replace") or "%s: the index cannot be loaded" % self.path)
         self.has_index = True
         return True
+
+    def build_index(self, write=None, overwrite=False):
+        """csv_bam_index_build: one pass over the whole file on the reader's current routes -> the index is installed (has_index)
+        and the stats dict is returned: records, runs, index_bytes, ms (wall), ms_kernels, bytes_up, bytes_down, frame_runs,
+        index_windows, inflate / frame (the routes) and their block counters.  write: True - the bytes also go to <path>.bai; a path
+        - there; through a temporary file beside the target and os.replace.  FileExistsError, before anything is read, when the
+        target exists and overwrite is not set.  BamError: a record the BAI format cannot index or that is out of order (the text
+        names the file and the record's ordinal), or what the reader refuses; nothing is installed and nothing is written.  The
+        build counts as a read: a FramedChunk handed out before it is dead."""
+        target = None
+        if write is not None and write is not False:
+            target = os.fspath(self.path) + ".bai" if write is True else os.fspath(write)
+            if os.path.exists(target) and not overwrite:
+                raise FileExistsError("%s exists (overwrite=True replaces it)" % target)
+        self._read_serial += 1
+        n, t0 = C.c_int64(), time.perf_counter()
+        rc = self._L.csv_bam_index_build(self._h, 0, C.byref(n))
+        ms = (time.perf_counter() - t0) * 1e3
+        if rc:
+            raise BamError("%s: %s" % (self.path, (self._L.csv_bam_error(self._h) or b"").decode(errors="replace")))
+        self.has_index = True
+        v = [C.c_int64() for _ in range(6)]
+        msk = C.c_double()
+        self._L.csv_bam_index_build_stats(self._h, C.byref(v[0]), C.byref(v[1]), C.byref(msk), C.byref(v[2]), C.byref(v[3]), C.byref(v[4]), C.byref(v[5]))
+        stats = dict(records=int(v[0].value), runs=int(v[1].value), index_bytes=int(n.value), ms=ms, ms_kernels=float(msk.value), bytes_up=int(v[2].value),
+                     bytes_down=int(v[3].value), frame_runs=int(v[4].value), index_windows=int(v[5].value), written=None)
+        stats.update(self.inflate_stats())
+        stats.update(self.frame_stats())
+        if target is not None:
+            data = self.index_bytes()
+            fd, tmp = tempfile.mkstemp(prefix=os.path.basename(target) + ".", suffix=".tmp", dir=os.path.dirname(target) or ".")
+            try:
+                with os.fdopen(fd, "wb") as f:
+                    f.write(data)
+                os.replace(tmp, target)
+            except BaseException:
+                if os.path.exists(tmp):
+                    os.unlink(tmp)
+                raise
+            stats["written"] = target
+        self.index_stats = stats
+        return stats
+
+    def index_bytes(self):
+        """the bytes of a BUILT index, as a .bai file holds them (csv_bam_index_bytes).  BamError: the reader has no index, or one
+        loaded from a file (its bins were not kept)"""
+        need = C.c_int64()
+        rc = self._L.csv_bam_index_bytes(self._h, None, 0, C.byref(need))
+        if rc != _abi.E_CAPACITY:
+            raise BamError("%s: the reader holds no built index (build_index; a loaded index keeps no bins)" % self.path)
+        buf = np.empty(int(need.value), np.uint8)
+        rc = self._L.csv_bam_index_bytes(self._h, buf.ctypes.data, len(buf), C.byref(need))
+        if rc:
+            raise BamError("%s: the built index cannot be fetched" % self.path)
+        return buf.tobytes()
 
     def index_block(self, chrom, pos):
         """the number of the BGZF block in which a read of `chrom` from `pos` on starts (its linear-index entry); -1: the index says
@@ -626,7 +693,12 @@ def main(argv=None):
     ap.add_argument("--inflate", default="host", choices=["host", "device"], help="where the BGZF blocks are inflated: host threads, or the GPU (device 0) [%(default)s]")
     ap.add_argument("--frame", default="host", choices=["host", "device"], help="where the records are framed: on the host, or on the GPU (needs --inflate device) [%(default)s]")
     ap.add_argument("--idxstats", action="store_true", help="print contig, length, mapped and unmapped reads from the index (the table of samtools idxstats) and stop")
+    ap.add_argument("--index", action="store_true", help="build the BAM index and write it to FILE.bai (the job of samtools index) on the routes of --inflate / --frame, and stop")
+    ap.add_argument("--index_out", metavar="PATH", default=None, help="with --index: write the index there instead")
+    ap.add_argument("--force", action="store_true", help="with --index: replace an index file that exists")
     a = ap.parse_args(argv)
+    if (a.index_out is not None or a.force) and not a.index:
+        ap.error("--index_out and --force go with --index")
     if a.idxstats:
         with BamFile(a.bam, threads=a.threads, index=True) as bf:
             for (name, mapped, unmapped, _), length in zip(bf.index_statistics(), bf.lengths):
@@ -647,6 +719,15 @@ def main(argv=None):
 
 
 def _main(a, ap, ctx):
+    if a.index:
+        with BamFile(a.bam, threads=a.threads, inflate=ctx, frame=a.frame, index=False) as bf:
+            try:
+                st = bf.build_index(write=a.index_out if a.index_out is not None else True, overwrite=a.force)
+            except FileExistsError as e:
+                ap.error("%s: --force replaces it" % e)
+            print("wrote %s: %d bytes, %d records, %d chunks before joining, %.1f ms (inflate %s, frame %s)"
+                  % (st["written"], st["index_bytes"], st["records"], st["runs"], st["ms"], st["inflate"], st["frame"]))
+        return 0
     with BamFile(a.bam, threads=a.threads, inflate=ctx, frame=a.frame) as bf:
         print(bf.header_text.rstrip("\n"))
         names = [a.chrom] if a.chrom is not None else list(bf.references) + [None]

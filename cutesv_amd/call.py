@@ -209,7 +209,10 @@ def call_bam(bam, reference, params, ctx=None, chroms=None, batch=10_000_000, re
                leaves it; it takes the device inflate when `inflate` is None (ValueError with an explicit
                inflate="host"); a BamFile that was handed in gets its previous setting back at the end.  Same text either way.
     index      for a path: None - the .bai beside the file is loaded when there is one; a path - that index; False - none
-               (bam.BamFile's `index`).  An open BamFile comes with what it has.  With an index every task's read starts at its
+               (bam.BamFile's `index`); "build" - the .bai beside the file when there is one, else an index is built in memory
+               (BamFile.build_index) once the call's inflate and frame routes are set, so on them; nothing is
+               written, timings["ms_index"] says what it took (0 when a file was found), and the file is inflated twice - for the
+               build, then for the tasks.  An open BamFile comes with what it has.  With an index every task's read starts at its
                linear-index entry, and under include_bed - unless tra_gt="alignments" fills the alignment table, which needs every
                record - a task reads only the union of its regions (task_ranges), and nothing when it has none.  The gates are
                unchanged and decide; the text does not depend on the index.
@@ -244,7 +247,8 @@ def call_bam(bam, reference, params, ctx=None, chroms=None, batch=10_000_000, re
     mode = tra_gt_mode(cp.resolve.genotype, tra_gt)
     p = dataclasses.replace(cp.resolve, genotype_tra=(mode == "reads_table"))
     own_bam = not isinstance(bam, bam_mod.BamFile)
-    bf = bam_mod.BamFile(bam, threads=threads, index=index) if own_bam else bam
+    build_index = own_bam and isinstance(index, str) and index == "build"
+    bf = bam_mod.BamFile(bam, threads=threads, index=None if build_index else index) if own_bam else bam
     own_ctx = ctx is None
     if own_ctx:
         ctx = engine.Context(0)
@@ -257,11 +261,15 @@ def call_bam(bam, reference, params, ctx=None, chroms=None, batch=10_000_000, re
             timings[key] = timings.get(key, 0.0) + (now - clock[0]) * 1e3
         clock[0] = now
     try:
-        if task_cut == "index" and not bf.has_index:
+        if task_cut == "index" and not bf.has_index and not build_index:
             raise ValueError("task_cut='index' needs a BAM index (.bai): none was found for %s" % bf.path)
         was_framed = bf.frame is not None
         restore = (bf.set_inflate(ctx if inflate == "device" else None), was_framed)
         bf.set_frame(frame)
+        if build_index:
+            if not bf.has_index:
+                bf.build_index()
+            lap("ms_index")
         # the chromosome table in name order: a chromosome's index is its name rank, the numbering of rebuild._segments and of a TRA row's mate
         names = sorted(bf.references)
         length = dict(zip(bf.references, bf.lengths))

@@ -18,7 +18,8 @@
 // At the end of the file, the step in front of all that: k_bgzf_inflate, one wavefront per BGZF block, over the decode core
 // of inflate_core.h; and behind it the record framing on the device (frame_core.h):
 // k_frame_guess, k_frame_stitch, k_frame_rows find the records of an inflated window that never left the device, k_frame_pack
-// builds the slim and the host image from the records the reader selected.
+// builds the slim and the host image from the records the reader selected; and last the index build (index_core.h, DESIGN.md
+// section 30): k_index_rows and k_index_runs turn the rows of a framed window into the runs and the linear index of a .bai.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -26,6 +27,7 @@
 #include "scan.hip.h"
 #include "inflate_core.h"
 #include "frame_core.h"
+#include "index_core.h"
 
 namespace csv {
 
@@ -428,6 +430,125 @@ __global__ __launch_bounds__(256) void k_frame_gather(const uint8_t* src, const 
     const int lane = lane_id();
     for (i64 r = ((i64)blockIdx.x * 256 + threadIdx.x) >> 6; r < n; r += ((i64)gridDim.x * 256) >> 6)
         if (len[r] > 0) frame_copy(src + src_off[r], len[r], dst + dst_off[r], lane);
+}
+
+// ------------------------------------------------------------------------------------ index build
+// The rows k_frame_rows left in device memory -> the work of a BAM index (index_core.h), window by window: k_index_rows, one thread
+// per record, scan_counts over the head flags, k_index_runs.  What the kernels trust is host-checked: n rows, the tables' sizes.
+struct IxAux { u64 vbeg, vend; int ref; unsigned bin; int pos; int head; };       // per record, between the two kernels (32 bytes)
+
+struct IndexArgs {
+    const uint8_t* win; i64 win_n;  // the window (device memory): the flag of a record is read there
+    i64 win_u0;                     // the stream offset of the window's first byte
+    const FrRow* rows; i64 n;       // the framed records of the window, in file order
+    i64 ordinal0;                   // the ordinal of rows[0] in the file
+    IxCarry carry;                  // the record in front of rows[0]
+    IxBlocks blocks;                // the whole-file block table
+    int n_ref; const i64* l_ref; const i64* lin_off;
+    u64* lin;                       // the linear arrays of the whole build: IX_NONE or the smallest virtual offset so far
+    u64* counts;                    // mapped, unmapped per reference; then the records without coordinates
+    IxAux* aux; int4* scan; const i64* totals;
+    IxVerdict* verdict; IxRun* runs;
+};
+
+// one thread per record: bin, windows, both virtual offsets, the head flag against the predecessor, the refusals, the linear index
+// (a 64-bit atomicMin per touched window: the first IX_LANE_WINDOWS by the record's lane, the rest by the whole wavefront), the
+// counts (one atomic per wavefront and reference).  No lane leaves before the end: the ballots see the whole wavefront.
+__global__ __launch_bounds__(256) void k_index_rows(IndexArgs A)
+{
+    const i64 i = (i64)blockIdx.x * 256 + threadIdx.x;
+    const bool live = i < A.n;
+    const int lane = lane_id();
+    IxAux x;
+    x.vbeg = 0; x.vend = 0; x.ref = -1; x.bin = 0; x.pos = 0; x.head = 0;
+    IxRec r = ix_record(0, 0);
+    bool ok = false, unmapped = false;
+    if (live) {
+        const FrRow w = A.rows[i];
+        IxCarry prev = A.carry;
+        if (i > 0) {
+            const FrRow q = A.rows[i - 1];
+            prev.valid = 1; prev.ref = q.refid; prev.pos = q.pos; prev.bin = ix_record(q.pos, q.span).bin;
+        }
+        r = ix_record(w.pos, w.span);
+        x.ref = w.refid; x.pos = w.pos; x.bin = r.bin;
+        const int why = ix_refuse(w.refid, w.pos, r, A.n_ref, A.l_ref, prev);
+        if (why != IX_OK) atomicMin((u64*)&A.verdict->bad, ((u64)(A.ordinal0 + i) << 3) | (u64)why);
+        ok = why == IX_OK;
+        const i64 u = A.win_u0 + w.off;
+        x.vbeg = ix_voff(A.blocks, u); x.vend = ix_voff(A.blocks, u + 4 + (i64)w.block_size);
+        if (w.off >= 0 && w.off + 20 <= A.win_n) unmapped = ((fr_u32(A.win, w.off + 16) >> 16) & 4u) != 0;      // flag_nc: flag << 16 | n_cigar_op
+        x.head = ok && w.refid >= 0 && (!prev.valid || prev.ref != w.refid || prev.bin != r.bin) ? 1 : 0;
+        if (!ok) x.ref = -1;                                     // (a refused record belongs to no run: the build fails anyway)
+        A.aux[i] = x;
+        A.scan[i] = make_int4(x.head, 0, 0, 0);
+    }
+    const bool mapped_ref = ok && x.ref >= 0;
+    // the linear index: every window of [w0, w1] lies inside the reference's entries (ix_refuse: end <= max(l_ref, 1), end <= 2^29)
+    u64* io = A.lin + (mapped_ref ? A.lin_off[x.ref] : 0);
+    const int nw = mapped_ref ? r.w1 - r.w0 + 1 : 0;
+    for (int k = 0; k < IX_LANE_WINDOWS; k++) if (k < nw) atomicMin(io + r.w0 + k, x.vbeg);
+    u64 wide = __ballot(nw > IX_LANE_WINDOWS ? 1 : 0);
+    while (wide) {
+        const int src = __ffsll((long long)wide) - 1;
+        wide &= wide - 1;
+        const int ref = __shfl(x.ref, src), w0 = __shfl(r.w0, src) + IX_LANE_WINDOWS, w1 = __shfl(r.w1, src);
+        const u64 v = (u64)shfl_i64((i64)x.vbeg, src);
+        u64* row = A.lin + A.lin_off[ref];
+        for (int w = w0 + lane; w <= w1; w += WAVE) atomicMin(row + w, v);
+    }
+    // the counts: the file is sorted, so a wavefront is almost always of one reference
+    u64 todo = __ballot(ok ? 1 : 0);
+    while (todo) {
+        const int src = __ffsll((long long)todo) - 1;
+        const int ref = __shfl(x.ref, src);
+        const u64 same = __ballot(ok && x.ref == ref ? 1 : 0), un = __ballot(ok && x.ref == ref && unmapped ? 1 : 0);
+        if (lane == src) {
+            if (ref < 0) atomicAdd(A.counts + 2 * (i64)A.n_ref, (u64)__popcll(same));
+            else {
+                if (same & ~un) atomicAdd(A.counts + 2 * (i64)ref, (u64)__popcll(same & ~un));
+                if (un) atomicAdd(A.counts + 2 * (i64)ref + 1, (u64)__popcll(un));
+            }
+        }
+        todo &= ~same;
+    }
+}
+
+// one thread per record, behind the scan of the head flags (scan[i].x: the heads in front of record i).  The head of run r writes
+// beg, ref and bin, the run's last record writes end and the record count (the head's row is found in the scan by bisection).  A
+// window whose first record is no head opens with a `continues` row.  Record n - 1 leaves the carry, record 0 the number of rows.
+__global__ __launch_bounds__(256) void k_index_runs(IndexArgs A)
+{
+    const i64 i = (i64)blockIdx.x * 256 + threadIdx.x;
+    if (i >= A.n) return;
+    const IxAux x = A.aux[i];
+    const IxAux x0 = A.aux[0];
+    const int cont = x0.ref >= 0 && !x0.head ? 1 : 0;
+    if (i == 0) A.verdict->n_runs = A.totals[0] + cont;
+    if (i == A.n - 1) {
+        const FrRow w = A.rows[i];                               // (the record as it is in the file, refused or not)
+        A.verdict->last = IxCarry{1, w.refid, w.pos, ix_record(w.pos, w.span).bin};
+    }
+    if (x.ref < 0) return;
+    const i64 heads = (i64)A.scan[i].x + x.head;                 // heads up to and including this record
+    const i64 run = heads - 1 + cont;
+    if (run < 0 || run >= A.n) return;                           // (cannot happen: a record without a head in front of it is under `cont`)
+    if (x.head || i == 0) {
+        IxRun* R = A.runs + run;
+        R->beg = x.vbeg; R->ref = x.ref; R->bin = x.bin; R->continues = x.head ? 0u : 1u;
+    }
+    bool last = i == A.n - 1;
+    if (!last) { const IxAux y = A.aux[i + 1]; last = y.ref < 0 || y.head; }
+    if (last) {
+        i64 lo = 0;                                              // the run's first record: 0, or the row where scan.x reaches heads - 1 last
+        if (heads > 0) {
+            i64 hi = i + 1;                                      // the largest j <= i with scan[j].x == heads - 1
+            lo = 0;
+            while (hi - lo > 1) { const i64 m = (lo + hi) / 2; if ((i64)A.scan[m].x <= heads - 1) lo = m; else hi = m; }
+        }
+        IxRun* R = A.runs + run;
+        R->end = x.vend; R->n_records = (unsigned)(i - lo + 1);
+    }
 }
 
 }  // namespace csv

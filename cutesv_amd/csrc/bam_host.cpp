@@ -13,6 +13,8 @@
 // starting point and nothing else.  What goes to the device per
 // record is the slim image {32 fixed bytes, CIGAR words, aux bytes}; the read name and the 4-bit sequence stay in a host
 // buffer; the qualities are dropped.
+// csv_bam_index_build makes the index a file came without: one whole-file pass on the reader's current routes,
+// through index_core.h - a host loop over the records, or, on the framing route, the index kernels over the rows of every window.
 // With csv_bam_set_frame the window never leaves the device: the records are framed there (frame_core.h), the
 // selection loop below runs over the rows of the record table instead of the bytes, and the two images are built in device memory.
 #include <stdint.h>
@@ -35,6 +37,7 @@
 #include "../../include/cutesv_hip.h"
 #include "bai_index.h"
 #include "frame_core.h"
+#include "index_core.h"
 
 namespace {
 
@@ -98,6 +101,11 @@ struct csv_bam {
     // was positioned in by the index - the first record it sees of that contig is not the contig's first
     bool                 has_index = false;
     bai::Index           index;
+    // a built index (csv_bam_index_build): its bytes, as a .bai file holds them, and the counters of the build
+    bool                 index_built = false;
+    std::vector<uint8_t> index_bytes;
+    i64                  ix_records = 0, ix_runs = 0, ix_frame_runs = 0, ix_windows = 0, ix_up = 0, ix_down = 0;
+    double               ix_ms_kernels = 0;
     bool                 seeked = false;
     uint32_t             seek_key = 0;
     i64                  ahead_block = -1;   // with an index: the block where the running region is guessed to end (-1: no guess)
@@ -793,7 +801,174 @@ bool read_file(const std::string& path, std::vector<uint8_t>* data)
     return ok;
 }
 
+
+// ---- the index build (index_core.h)
+struct IxTables { std::vector<csv::ix_i64> uoff, coff, l_ref; std::vector<uint32_t> isize; };
+
+int index_refuse(csv_bam* b, long long ordinal, int why)
+{
+    char buf[256];
+    snprintf(buf, sizeof buf, "cannot build the index: record %lld %s", ordinal, csv::ix_refusal_text(why));
+    b->err = buf;
+    return CSV_E_INVALID;
+}
+
+// the host routes: every record through the core, one by one
+int index_build_host(csv_bam* b, const IxTables& T, csv::ix::Builder* B)
+{
+    const csv::IxBlocks blocks{T.uoff.data(), T.coff.data(), T.isize.data(), (csv::ix_i64)T.uoff.size()};
+    for (;;) {
+        Rec r;
+        bool at_end;
+        const int rc = next_host(b, &r, &at_end);
+        if (rc) return rc;
+        if (at_end) return CSV_OK;
+        const i64 cg = 32 + r.l_name;                        // the span of the record's own CIGAR words, read inside the record only (fr_row's rule)
+        i64 n_in = cg <= r.bs ? (r.bs - cg) / 4 : 0, span = 0;
+        if (n_in > r.n_cig) n_in = r.n_cig;
+        for (i64 k = 0; k < n_in; k++) {
+            const uint32_t w = rd_u32(r.p + cg + 4 * k), op = w & 15u;
+            if (op == 0 || op == 2 || op == 3 || op == 7 || op == 8) span += w >> 4;
+        }
+        const csv::IxRec x = csv::ix_record(r.pos, span);
+        const int why = csv::ix_refuse((int32_t)r.rkey, r.pos, x, b->n_ref, T.l_ref.data(), B->prev);
+        if (why) return index_refuse(b, B->records, why);
+        B->add_record((int32_t)r.rkey, r.pos, x, (rd_u16(r.p + 14) & 4) != 0, csv::ix_voff(blocks, b->cur), csv::ix_voff(blocks, b->cur + 4 + r.bs));
+        b->cur += 4 + r.bs;
+    }
+}
+
+// the framing route: window by window, the rows stay on the device (csv_frame_run without a row pointer) and the index kernels read
+// them there; the verdict and the runs come down.  The checks of the chain and their texts are next_framed's.
+int index_build_device(csv_bam* b, const IxTables& T, csv::ix::Builder* B)
+{
+    int rc = csv_index_begin(b->frame, b->n_ref, T.l_ref.data(), (int64_t)T.uoff.size(), T.uoff.data(), T.coff.data(), T.isize.data());
+    if (rc) return fail(b, rc, "the device index build failed: %s", csv_last_error(b->frame));
+    csv::IxCarry carry{0, 0, 0, 0};
+    bool tail_has_bs = false;
+    i64 tail_bs = 0;
+    int idle = 0;
+    b->fr_valid = false;
+    for (;;) {
+        const i64 cur = b->cur;
+        if (cur == b->utotal) break;
+        if (cur + 4 > b->utotal) return fail(b, CSV_E_INVALID, "%sthe file ends inside a record (at inflated byte %lld)", "", (long long)cur);
+        i64 need = 4;
+        if (tail_has_bs) {                                   // the chain stopped here, at a record it could not step over
+            if (tail_bs < 32) return fail(b, CSV_E_INVALID, "%srecord with block_size < 32 at inflated byte %lld", "", (long long)cur);
+            if (cur + 4 + tail_bs > b->utotal) return fail(b, CSV_E_INVALID, "%sthe file ends inside a record (at inflated byte %lld)", "", (long long)cur);
+            need = 4 + tail_bs;
+        }
+        if (csv_frame_window_serial(b->frame) != b->fr_serial) b->win_n = 0;
+        bool have;
+        rc = ensure(b, cur, need, &have);
+        if (rc) return rc;
+        b->t_off.clear(); b->t_len.clear();
+        for (size_t j = b->win_b0; j < b->win_b1; j++) { b->t_off.push_back(b->blocks[j].uoff - b->win_u0); b->t_len.push_back((int32_t)b->blocks[j].isize); }
+        csv::FrStitch R;
+        rc = csv_frame_run(b->frame, (int32_t)b->t_off.size(), b->t_off.data(), b->t_len.data(), b->n_ref, cur - b->win_u0, nullptr, &R);
+        if (rc) return fail(b, rc, "the device framing failed: %s", csv_last_error(b->frame));
+        b->ix_frame_runs++;
+        if (R.n_records > 0) {
+            csv::IxVerdict V;
+            const csv::IxRun* runs = nullptr;
+            rc = csv_index_window(b->frame, R.n_records, b->win_u0, B->records, &carry, &V, &runs);
+            if (rc) return fail(b, rc, "the device index build failed: %s", csv_last_error(b->frame));
+            if (V.bad != csv::IX_NONE) return index_refuse(b, (long long)(V.bad >> 3), (int)(V.bad & 7));
+            for (i64 k = 0; k < V.n_runs; k++) B->add_run(runs[k]);
+            b->ix_runs += V.n_runs;
+            B->records += R.n_records;
+            carry = V.last;
+        }
+        const i64 tail = b->win_u0 + R.tail;
+        if (tail > cur) idle = 0;
+        else if (++idle > 4) return fail(b, CSV_E_INVALID, "%sthe device framing made no progress at inflated byte %lld", "", (long long)cur);
+        tail_has_bs = R.tail_has_bs != 0; tail_bs = R.tail_bs;
+        b->cur = tail;
+    }
+    rc = csv_index_end(b->frame, B->lin.data(), (int64_t)B->lin.size(), B->counts.data(), (int64_t)B->counts.size());
+    if (rc) return fail(b, rc, "the device index build failed: %s", csv_last_error(b->frame));
+    return CSV_OK;
+}
+
 }  // namespace
+
+extern "C" {
+
+int csv_bam_index_build(csv_bam* b, int32_t flags, int64_t* n_bytes)
+{
+    if (!b || flags != 0) return CSV_E_INVALID;
+    if (n_bytes) *n_bytes = 0;
+    // the build is a read: the chunk handed out last is dead, the counters start over, the scan state of a region is forgotten
+    b->ms_inflate = 0; b->inflated = b->compressed = 0;
+    b->device_blocks = b->fallback_blocks = 0; b->ms_kernels = 0;
+    b->slim.clear(); b->host.clear(); b->rec_off.clear(); b->host_off.clear(); b->rec_len.clear();
+    b->pending.clear(); b->l_name_v.clear(); b->l_seq_v.clear(); b->slim_size = b->host_size = 0; b->framed_chunk = false;
+    if (b->frame) { csv_frame_chunk_begin(b->frame, b); csv_frame_counters(b->frame, nullptr, nullptr, nullptr, nullptr, nullptr, 1); }
+    b->seeked = false; b->ahead_block = -1; b->hint_at = -1; b->range_i = 0;
+    b->ix_records = b->ix_runs = b->ix_frame_runs = b->ix_windows = b->ix_up = b->ix_down = 0; b->ix_ms_kernels = 0;
+    IxTables T;
+    for (const Block& k : b->blocks) { T.uoff.push_back(k.uoff); T.coff.push_back(k.coff); T.isize.push_back(k.isize); }
+    T.l_ref.assign(b->lengths.begin(), b->lengths.end());
+    csv::ix::Builder B;
+    B.begin(b->n_ref, T.l_ref.data());
+    b->cur = b->first_rec;
+    const int rc = b->frame ? index_build_device(b, T, &B) : index_build_host(b, T, &B);
+    b->ix_ms_kernels = b->ms_kernels;
+    if (b->frame) {
+        double ms_f = 0, ms_x = 0;
+        int64_t dn_f = 0, up_f = 0, dn_x = 0, up_x = 0, wins = 0;
+        csv_frame_counters(b->frame, nullptr, nullptr, &ms_f, &dn_f, &up_f, 0);
+        csv_index_counters(b->frame, &ms_x, &dn_x, &up_x, &wins);
+        b->ix_ms_kernels += ms_f + ms_x; b->ix_down = dn_f + dn_x; b->ix_up = up_f + up_x; b->ix_windows = wins;
+    }
+    b->cur = b->first_rec;
+    b->win_n = 0; b->fr_valid = false;                       // (what a later read costs does not depend on what the build left in the window)
+    if (rc) return rc;
+    b->ix_records = B.records;
+    if (!b->frame) b->ix_runs = (i64)B.runs.size();
+    // the built bytes take the path a file's bytes take: parsed and validated against this file's blocks, then installed
+    std::vector<uint8_t> bytes = B.bytes();
+    bai::Index ix;
+    std::string err;
+    if (!bai::parse(bytes.data(), bytes.size(), b->n_ref, "the built index", voff_check, b, &ix, &err)) {
+        b->err = "cannot build the index: " + err;
+        return CSV_E_INVALID;
+    }
+    b->index = std::move(ix);
+    b->has_index = true;
+    b->index_built = true; b->index_bytes = std::move(bytes);
+    b->hint_at = -1; b->ahead_block = -1;
+    if (n_bytes) *n_bytes = (int64_t)b->index_bytes.size();
+    return CSV_OK;
+}
+
+int csv_bam_index_bytes(const csv_bam* b, uint8_t* out, int64_t cap, int64_t* need)
+{
+    if (!b) return CSV_E_INVALID;
+    if (need) *need = 0;
+    if (!b->has_index || !b->index_built) return CSV_E_STATE;
+    if (need) *need = (int64_t)b->index_bytes.size();
+    if (!out || cap < (int64_t)b->index_bytes.size()) return CSV_E_CAPACITY;
+    memcpy(out, b->index_bytes.data(), b->index_bytes.size());
+    return CSV_OK;
+}
+
+int csv_bam_index_build_stats(const csv_bam* b, int64_t* records, int64_t* runs, double* ms_kernels, int64_t* bytes_up, int64_t* bytes_down, int64_t* frame_runs,
+                              int64_t* index_windows)
+{
+    if (!b) return CSV_E_INVALID;
+    if (records) *records = b->ix_records;
+    if (runs) *runs = b->ix_runs;
+    if (ms_kernels) *ms_kernels = b->ix_ms_kernels;
+    if (bytes_up) *bytes_up = b->ix_up;
+    if (bytes_down) *bytes_down = b->ix_down;
+    if (frame_runs) *frame_runs = b->ix_frame_runs;
+    if (index_windows) *index_windows = b->ix_windows;
+    return CSV_OK;
+}
+
+}  // extern "C"
 
 extern "C" {
 
@@ -833,6 +1008,7 @@ int csv_bam_index_load(csv_bam* b, const char* path)
         }
         b->index = std::move(ix);
         b->has_index = true;
+        b->index_built = false; b->index_bytes.clear();
         b->hint_at = -1; b->ahead_block = -1;
         return CSV_OK;
     }
@@ -856,6 +1032,7 @@ int csv_bam_index_drop(csv_bam* b)
     if (!b) return CSV_E_INVALID;
     b->index = bai::Index();
     b->has_index = false;
+    b->index_built = false; b->index_bytes.clear();
     b->hint_at = -1; b->ahead_block = -1; b->seeked = false;
     return CSV_OK;
 }

@@ -173,6 +173,7 @@ struct FrameState {
     uint64_t serial = 0;                       // windows loaded so far (csv_frame_window_serial)
     std::vector<char> tab_h;
     std::vector<FrRow> rows_h;
+    i64 n_rows = 0;                            // rows of the last csv_frame_run, in `rows` (device)
     const void* reader = nullptr;              // the one reader that frames on this context (csv_bam_set_frame)
     const void* owner = nullptr;
     bool chunk_ok = false;
@@ -183,6 +184,22 @@ struct FrameState {
     i64 right = 0, fallback = 0, bytes_down = 0, bytes_up = 0;
     double ms_kernels = 0;
     void own(std::vector<Buf*>& v) { v.insert(v.end(), {&win[0], &win[1], &tab, &starts, &rows, &pack, &slim, &host, &cols}); }
+};
+
+// The index build (stage_index.hip.h), all stand-alone and grow-only.  blocks (the whole-file block table), refs
+// (reference lengths and the offsets of their linear arrays), lin (the linear arrays) and counts live from csv_index_begin to
+// csv_index_end: one build.  work (per record the two virtual offsets, bin and head flag; the scan's tables; the verdict; the runs) is
+// dead when a csv_index_window returns; runs_h is its host copy of the runs.  The entries READ FrameState's rows and current window,
+// which csv_frame_run left for them, and write nothing outside this struct; of the context they touch the stream and its first two
+// timing events, nothing else.
+struct IndexBuildState {
+    Buf blocks, refs, lin, counts, work;
+    i64 n_blocks = 0, n_lin = 0;
+    int n_ref = -1;                            // -1: no build is open
+    std::vector<IxRun> runs_h;
+    double ms_kernels = 0;
+    i64 bytes_down = 0, bytes_up = 0, windows = 0;
+    void own(std::vector<Buf*>& v) { v.insert(v.end(), {&blocks, &refs, &lin, &counts, &work}); }
 };
 
 // ---- The state of the engine (stage_upload / stage_run / stage_results.hip.h): the path csv_batch_upload -> csv_batch_run ->
@@ -319,7 +336,7 @@ struct csv_ctx {
     BatchState bt; ReadsOrderState ro; ResultState res; TableState tab;
     // ---- the extraction-side stages (their lifetime rules: at the structs)
     PoolState pool; NameState nm; BamState bm; SaState sa; SeqState seq; VcfStrState vs; AlnState al; ReadsTabState rt;
-    RebuildState rb; CigarState cg; SplitState sp; InflateState inf; FrameState fr;
+    RebuildState rb; CigarState cg; SplitState sp; InflateState inf; FrameState fr; IndexBuildState ixb;
 };
 
 namespace {

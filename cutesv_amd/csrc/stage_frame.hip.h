@@ -21,7 +21,7 @@ int csv_frame_window(csv_ctx* c, const uint8_t* comp, int64_t comp_bytes, int32_
         if (out_off[k] < keep) return fail(c, CSV_E_INVALID, "bad frame window: block %d lies in the kept bytes", (int)k);
     if (n_blocks > 0) TRY(inflate_impl(c, comp, comp_bytes, n_blocks, in_off, in_len, out_off, out_len, crc, nullptr, dp<uint8_t>(f.win[nx]), bytes, 0, status, ms_kernels));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    f.cur = nx; f.win_n = bytes; f.serial++;
+    f.cur = nx; f.win_n = bytes; f.serial++; f.n_rows = 0;
     f.bytes_up += comp_bytes + 28ll * n_blocks; f.bytes_down += n_blocks;
     return CSV_OK;
 }
@@ -42,12 +42,14 @@ int csv_frame_window_put(csv_ctx* c, int64_t off, const uint8_t* src, int64_t le
 }
 
 // frame the current window from `cursor` (a true record start): *rows = one row per framed record (host memory of the state, valid
-// until the next call), *res = where the chain stopped
+// until the next call), *res = where the chain stopped.  rows == NULL: the rows stay in device memory (FrameState::rows, for
+// csv_index_window) and do not come down
 int csv_frame_run(csv_ctx* c, int32_t n_blocks, const int64_t* blk_off, const int32_t* blk_len, int32_t n_ref, int64_t cursor, const FrRow** rows, FrStitch* res)
 {
-    if (!c || !rows || !res) return CSV_E_INVALID;
+    if (!c || !res) return CSV_E_INVALID;
     FrameState& f = c->fr;
-    *rows = nullptr;
+    if (rows) *rows = nullptr;
+    f.n_rows = 0;
     if (n_blocks < 1 || !blk_off || !blk_len || cursor < 0 || cursor > f.win_n) return fail(c, CSV_E_INVALID, "bad frame call");
     // the table is checked before anything is launched: the kernels trust it (contiguous from 0 to the window's end)
     const size_t n = (size_t)n_blocks;
@@ -85,7 +87,7 @@ int csv_frame_run(csv_ctx* c, int32_t n_blocks, const int64_t* blk_off, const in
     if (R.n_records < 0 || R.n_records > slots || R.tail < cursor || R.tail > f.win_n) return fail(c, CSV_E_INVALID, "frame: inconsistent counts (%lld records)", (long long)R.n_records);
     float ms = 0, ms2 = 0;
     HIP_TRY(c, hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
-    f.rows_h.resize((size_t)R.n_records);
+    f.rows_h.resize(rows ? (size_t)R.n_records : 0);
     if (R.n_records > 0) {
         TRY(reserve(c, f.rows, (size_t)R.n_records * sizeof(FrRow)));
         A.rows = dp<FrRow>(f.rows);
@@ -93,14 +95,16 @@ int csv_frame_run(csv_ctx* c, int32_t n_blocks, const int64_t* blk_off, const in
         hipLaunchKernelGGL(k_frame_rows, dim3(std::min(div_up(n_blocks, FRAME_WAVES), 8192)), dim3(64 * FRAME_WAVES), 0, st, A, (i64)R.n_records);
         HIP_TRY(c, hipEventRecord(c->ev[3], st));
         HIP_TRY(c, hipGetLastError());
-        HIP_TRY(c, hipMemcpyAsync(f.rows_h.data(), f.rows.p, (size_t)R.n_records * sizeof(FrRow), hipMemcpyDeviceToHost, st));
+        if (rows) HIP_TRY(c, hipMemcpyAsync(f.rows_h.data(), f.rows.p, (size_t)R.n_records * sizeof(FrRow), hipMemcpyDeviceToHost, st));
         HIP_TRY(c, hipStreamSynchronize(st));
         HIP_TRY(c, hipEventElapsedTime(&ms2, c->ev[2], c->ev[3]));
     }
     f.ms_kernels += ms + ms2;
     f.right += R.right_blocks; f.fallback += R.fallback_blocks;
-    f.bytes_up += (i64)o_g; f.bytes_down += (i64)sizeof R + R.n_records * (i64)sizeof(FrRow);
-    *rows = f.rows_h.data(); *res = R;
+    f.bytes_up += (i64)o_g; f.bytes_down += (i64)sizeof R + (rows ? R.n_records * (i64)sizeof(FrRow) : 0);
+    f.n_rows = R.n_records;
+    if (rows) *rows = f.rows_h.data();
+    *res = R;
     return CSV_OK;
 }
 

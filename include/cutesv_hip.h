@@ -929,6 +929,26 @@ int64_t     csv_bam_index_block(const csv_bam* bam, int32_t refid, int64_t beg);
 int         csv_bam_read_ranges(csv_bam* bam, int32_t refid, int32_t n_ranges, const int64_t* beg, const int64_t* end, int64_t max_records, int32_t flags,
                                 csv_bam_chunk* out);
 
+/* Building the index a file came without (csrc/index_core.h).  csv_bam_index_build (flags: 0) runs one pass over
+ * the whole file on the reader's current routes - with csv_bam_set_frame the index kernels work on the rows of every framed window,
+ * which stay in device memory; otherwise a host loop walks the records through the same core - and assembles the bytes of a .bai file:
+ * bins with their chunks, the pseudo-bins 37450, the linear index with empty windows filled from the next one, n_no_coor; byte for byte
+ * what tests/bai_writer.py, the test suite's independent reading of SAMv1 5.2 / 5.3 with htslib's conventions, writes.  The bytes are then parsed and validated as a file's
+ * are (csv_bam_index_load) and installed: from then on the reader has an index.  *n_bytes (may be NULL): their number.
+ * CSV_E_INVALID with a csv_bam_error text "cannot build the index: record <ordinal> ..." and nothing installed (an index the
+ * reader had stays): a record that reaches 2^29 bases or beyond (the BAI format cannot index it); that ends beyond max(l_ref, 1) of
+ * its reference; whose refID the header does not have; or that is out of coordinate order against the record before it (a lower
+ * refID, -1 sorting last, or the same reference and a lower pos).  The texts are the same on every route.  A damaged block or a
+ * broken record chain gives the reader's own error.  The build counts as a read: a device chunk handed out before it is dead.
+ * csv_bam_index_bytes: the bytes of a BUILT index into out[0 .. cap); *need = their number.  CSV_E_STATE: the reader has no index,
+ * or one loaded from a file (whose bins were not kept); CSV_E_CAPACITY: cap is too small, *need says what it takes, nothing is stored.
+ * csv_bam_index_build_stats, of the last build: records indexed, runs (chunks before the join across windows), device time of all
+ * kernels of the pass, bytes copied up and down by the framing route (0 on the host routes), csv_frame_run calls and index windows. */
+int         csv_bam_index_build(csv_bam* bam, int32_t flags, int64_t* n_bytes);
+int         csv_bam_index_bytes(const csv_bam* bam, uint8_t* out, int64_t cap, int64_t* need);
+int         csv_bam_index_build_stats(const csv_bam* bam, int64_t* records, int64_t* runs, double* ms_kernels, int64_t* bytes_up, int64_t* bytes_down,
+                                      int64_t* frame_runs, int64_t* index_windows);
+
 /* BGZF inflate on the device: the raw-deflate payloads of n_blocks BGZF blocks -> their bytes, one wavefront
  * per block.  Block k's payload is comp[in_off[k] .. + in_len[k]), its out_len[k] (= ISIZE) bytes go to out[out_off[k] ..), crc[k]
  * is the CRC32 of its trailer; comp, out and status are host memory.
