@@ -146,7 +146,7 @@ class FramedChunk(Chunk):
             slim, host = np.empty(self._bytes[0], np.uint8), np.empty(self._bytes[1], np.uint8)
             rc = self._bf._L.csv_bam_chunk_fetch(self._bf._h, slim.ctypes.data if len(slim) else None, host.ctypes.data if len(host) else None)
             if rc:
-                raise BamError("%s: %s" % (self._bf.path, (self._bf._L.csv_bam_error(self._bf._h) or b"").decode(errors="replace")))
+                raise BamError("%s: %s" % (self._bf.path, self._bf._error_text()))
             self._images = (slim, host)
         return self._images
 
@@ -222,6 +222,10 @@ class BamFile:
                 self.close()
                 raise
 
+    def _error_text(self):
+        """csv_bam_error: what the reader said about its last failure"""
+        return (self._L.csv_bam_error(self._h) or b"").decode(errors="replace")
+
     def load_index(self, path=None, required=True):
         """csv_bam_index_load: path None tries <bam>.bai, then <bam minus .bam>.bai.  -> has_index.  BamError: the index does not
         validate (a reader whose load failed has none), or - with required - there is no such file."""
@@ -230,7 +234,7 @@ class BamFile:
             return self.has_index
         if rc:
             self.has_index = False
-            raise BamError((self._L.csv_bam_error(self._h) or b"").decode(errors="replace") or "%s: the index cannot be loaded" % self.path)
+            raise BamError(self._error_text() or "%s: the index cannot be loaded" % self.path)
         self.has_index = True
         return True
 
@@ -252,7 +256,7 @@ class BamFile:
         rc = self._L.csv_bam_index_build(self._h, 0, C.byref(n))
         ms = (time.perf_counter() - t0) * 1e3
         if rc:
-            raise BamError("%s: %s" % (self.path, (self._L.csv_bam_error(self._h) or b"").decode(errors="replace")))
+            raise BamError("%s: %s" % (self.path, self._error_text()))
         self.has_index = True
         v = [C.c_int64() for _ in range(6)]
         msk = C.c_double()
@@ -346,22 +350,25 @@ class BamFile:
         rc = self._L.csv_bam_set_frame(self._h, self.inflate._h if route == "device" else None)
         if rc:
             self.frame, self._read_serial = None, self._read_serial + 1          # (a reader that was refused frames on the host)
-            raise BamError("%s: %s" % (self.path, (self._L.csv_bam_error(self._h) or b"").decode(errors="replace")))
+            raise BamError("%s: %s" % (self.path, self._error_text()))
         prev, self.frame = "host" if self.frame is None else "device", self.inflate if route == "device" else None
         self._read_serial += 1
         return prev
 
-    def frame_stats(self):
-        """of the last read: dict(frame "host" | "device", right_blocks, frame_fallback_blocks, ms_frame_kernels, frame_bytes_down, frame_bytes_up)"""
+    def frame_stats(self, zero=False):
+        """of the last read: dict(frame "host" | "device", right_blocks, frame_fallback_blocks, ms_frame_kernels, frame_bytes_down, frame_bytes_up).
+        zero: of a read that did not reach the library - the route and zero counters"""
         r, f, ms, dn, up = C.c_int64(), C.c_int64(), C.c_double(), C.c_int64(), C.c_int64()
-        self._L.csv_bam_frame_stats(self._h, C.byref(r), C.byref(f), C.byref(ms), C.byref(dn), C.byref(up))
+        if not zero:
+            self._L.csv_bam_frame_stats(self._h, C.byref(r), C.byref(f), C.byref(ms), C.byref(dn), C.byref(up))
         return dict(frame="host" if self.frame is None else "device", right_blocks=int(r.value), frame_fallback_blocks=int(f.value), ms_frame_kernels=float(ms.value),
                     frame_bytes_down=int(dn.value), frame_bytes_up=int(up.value))
 
-    def inflate_stats(self):
-        """of the last read: dict(inflate "host" | "device", device_blocks, fallback_blocks, ms_inflate_kernels)"""
+    def inflate_stats(self, zero=False):
+        """of the last read: dict(inflate "host" | "device", device_blocks, fallback_blocks, ms_inflate_kernels); zero: as in frame_stats"""
         dev, fb, ms = C.c_int64(), C.c_int64(), C.c_double()
-        self._L.csv_bam_inflate_stats(self._h, C.byref(dev), C.byref(fb), C.byref(ms))
+        if not zero:
+            self._L.csv_bam_inflate_stats(self._h, C.byref(dev), C.byref(fb), C.byref(ms))
         return dict(inflate="host" if self.inflate is None else "device", device_blocks=int(dev.value), fallback_blocks=int(fb.value), ms_inflate_kernels=float(ms.value))
 
     def close(self):
@@ -396,34 +403,31 @@ class BamFile:
         cc = ChunkC()
         refid = self.refid(chrom)
         self._read_serial += 1
-        if ranges is None:
+        count_only = bool(flags & _abi.BAM_COUNT_ONLY)
+        empty = ranges is not None and len(ranges) == 0        # nothing to read: the library is not asked, no block is touched, `cc` stays zero
+        if empty:
+            rc = 0
+        elif ranges is None:
             rc = self._L.csv_bam_read(self._h, refid, int(beg), int(end), int(max_records), int(flags), C.byref(cc))
-        elif len(ranges) == 0:                                 # nothing to read: the empty chunk; the library is not asked and no block is touched
-            self.last_stats = dict(n_records=0, record_bytes=0, inflated_bytes=0, compressed_bytes=0, slim_bytes=0, ms_inflate=0.0, ms_frame=0.0,
-                                   inflate="host" if self.inflate is None else "device", device_blocks=0, fallback_blocks=0, ms_inflate_kernels=0.0,
-                                   upload_bytes_per_record=0.0, inflated_bytes_per_record=0.0)
-            if self.frame is not None:
-                self.last_stats.update(frame="device", right_blocks=0, frame_fallback_blocks=0, ms_frame_kernels=0.0, frame_bytes_down=0, frame_bytes_up=0)
-            if flags & _abi.BAM_COUNT_ONLY:
-                return 0, False
-            return Chunk(chrom, refid, np.zeros(0, np.uint8), np.zeros(0, np.int64), np.zeros(0, np.uint32), np.zeros(0, np.uint8), np.zeros(1, np.int64), False,
-                         self.last_stats)
         else:
             rc = self._L.csv_bam_read_ranges(self._h, refid, len(ranges), ranges[:, 0].ctypes.data, ranges[:, 1].ctypes.data, int(max_records), int(flags), C.byref(cc))
         if rc:
-            raise BamError("%s: %s" % (self.path, (self._L.csv_bam_error(self._h) or b"").decode(errors="replace")))
+            raise BamError("%s: %s" % (self.path, self._error_text()))
         n = int(cc.n_records)
         stats = dict(n_records=n, record_bytes=int(cc.record_bytes), inflated_bytes=int(cc.inflated_bytes), compressed_bytes=int(cc.compressed_bytes),
                      slim_bytes=int(cc.slim_bytes), ms_inflate=float(cc.ms_inflate), ms_frame=float(cc.ms_frame))
-        stats.update(self.inflate_stats())
+        stats.update(self.inflate_stats(zero=empty))
         if self.frame is not None:
-            stats.update(self.frame_stats())
+            stats.update(self.frame_stats(zero=empty))
         self.last_stats = stats
-        if flags & _abi.BAM_COUNT_ONLY:
+        if count_only and not empty:
             return n, bool(cc.more)
         # bytes that cross PCIe per record (image + offset + length) next to the inflated bytes of the record
         stats["upload_bytes_per_record"] = (int(cc.slim_bytes) + 12 * n) / n if n else 0.0
         stats["inflated_bytes_per_record"] = int(cc.record_bytes) / n if n else 0.0
+        if empty:                                              # the empty chunk (a plain one on every route: it has no image anywhere)
+            return (0, False) if count_only else Chunk(chrom, refid, np.zeros(0, np.uint8), np.zeros(0, np.int64), np.zeros(0, np.uint32), np.zeros(0, np.uint8),
+                                                       np.zeros(1, np.int64), False, stats)
         if self.frame is not None:
             l_name, l_seq = np.zeros(n, np.int32), np.zeros(n, np.int32)
             self._L.csv_bam_chunk_lengths(self._h, l_name.ctypes.data if n else None, l_seq.ctypes.data if n else None)
@@ -548,33 +552,20 @@ def decode(ctx, chunk, host_outputs=True):
     scans them there.  host_outputs=False: only the small per-record columns come back (no CIGAR array)."""
     L = lib()
     n = chunk.n
-    if getattr(chunk, "framed", False) and not chunk.fetched and chunk.ctx is ctx:      # (on another context the images are fetched, as for the other two consumers)
-        return _decode_framed(ctx, chunk, host_outputs)
-    slim, rec_off, rec_len = np.ascontiguousarray(chunk.slim, np.uint8), np.ascontiguousarray(chunk.rec_off, np.int64), np.ascontiguousarray(chunk.rec_len, np.uint32)
-    bin_ = BamIn(n_records=n, slim=slim.ctypes.data if len(slim) else None, slim_bytes=len(slim), rec_off=rec_off.ctypes.data if n else None,
-                 rec_len=rec_len.ctypes.data if n else None)
-    bound = len(slim) // 4 + 1                            # an operation or an SA tag takes at least 4 bytes of the image
+    framed = getattr(chunk, "framed", False) and not chunk.fetched and chunk.ctx is ctx      # (on another context the images are fetched, as for the other two consumers)
+    if framed:                                            # csv_bam_decode_framed takes the slim image where it lies
+        chunk.check()
+        slim_bytes = chunk.slim_bytes
+    else:
+        slim, rec_off, rec_len = np.ascontiguousarray(chunk.slim, np.uint8), np.ascontiguousarray(chunk.rec_off, np.int64), np.ascontiguousarray(chunk.rec_len, np.uint32)
+        slim_bytes = len(slim)
+        bin_ = BamIn(n_records=n, slim=slim.ctypes.data if len(slim) else None, slim_bytes=len(slim), rec_off=rec_off.ctypes.data if n else None,
+                     rec_len=rec_len.ctypes.data if n else None)
+    bound = slim_bytes // 4 + 1                           # an operation or an SA tag takes at least 4 bytes of the image
     size = dict(n=n, n1=n + 1, o=bound if host_outputs else 0, s=bound)
     arrs = {name: np.zeros(size[k], dt) if k in ("n", "n1") else np.empty(size[k], dt) for name, dt, k in _OUT}
     out = BamOut(cap_ops=size["o"], cap_sa=size["s"], **{k: (v.ctypes.data if len(v) else None) for k, v in arrs.items()})
-    rc = L.csv_bam_decode(ctx._h, C.byref(bin_), C.byref(out))
-    ctx._check(rc)
-    cut = dict(n=n, n1=n + 1, o=int(out.n_ops) if host_outputs else 0, s=int(out.n_sa))
-    cols = {name: (arrs[name][:cut[k]].copy() if k in ("o", "s") else arrs[name]) for name, _, k in _OUT}
-    cols.update(n_ops=int(out.n_ops), n_sa=int(out.n_sa), ms_device=float(out.ms_device), ms_upload=float(out.ms_upload),
-                bytes_uploaded=int(out.bytes_uploaded), on_device=True)
-    return cols
-
-
-def _decode_framed(ctx, chunk, host_outputs):
-    """decode on a FramedChunk: csv_bam_decode_framed takes the slim image where it lies; the same dict of columns"""
-    chunk.check()
-    n = chunk.n
-    bound = chunk.slim_bytes // 4 + 1
-    size = dict(n=n, n1=n + 1, o=bound if host_outputs else 0, s=bound)
-    arrs = {name: np.zeros(size[k], dt) if k in ("n", "n1") else np.empty(size[k], dt) for name, dt, k in _OUT}
-    out = BamOut(cap_ops=size["o"], cap_sa=size["s"], **{k: (v.ctypes.data if len(v) else None) for k, v in arrs.items()})
-    ctx._check(lib().csv_bam_decode_framed(ctx._h, C.byref(out)))
+    ctx._check(L.csv_bam_decode_framed(ctx._h, C.byref(out)) if framed else L.csv_bam_decode(ctx._h, C.byref(bin_), C.byref(out)))
     cut = dict(n=n, n1=n + 1, o=int(out.n_ops) if host_outputs else 0, s=int(out.n_sa))
     cols = {name: (arrs[name][:cut[k]].copy() if k in ("o", "s") else arrs[name]) for name, _, k in _OUT}
     cols.update(n_ops=int(out.n_ops), n_sa=int(out.n_sa), ms_device=float(out.ms_device), ms_upload=float(out.ms_upload),

@@ -15,6 +15,7 @@
 //               any other block is chased again from the true offset, serially.  The guess is a heuristic only: a wrong or
 //               missed one costs one serial chase of one block and never changes the result.
 //   fr_row      per framed record: the row the host's selection loop reads instead of the bytes
+//   fr_layout   per selected record: where its parts go in the two images - the reader's emit branches, csv_frame_pack's range check
 //
 // Bounds, by construction.  The offsets are data-dependent and a false guess chases garbage, so every read compares its last
 // byte with n first: fr_u32 is called only behind `o + 4 <= n` (block_size), `o + 36 <= n` (the fixed fields), `name_end <= n`
@@ -61,6 +62,20 @@ struct FrStitch { fr_i64 tail; int32_t tail_bs, tail_has_bs; fr_i64 n_records; i
 // a selected record on its way into the images (k_frame_pack; host-checked: [src, src + 4 + bs) lies inside the window, the
 // fields fit bs, the destinations lie inside the images)
 struct FrPack { fr_i64 src, rec_off, host_off; int32_t bs; uint32_t l_seq; uint16_t n_cig; uint8_t l_name, pad; uint32_t pad2; };
+
+// The layout of an emitted record.  Behind block_size a record holds 32 fixed bytes, the name, the CIGAR words, seq_bytes of bases,
+// l_seq qualities, and the aux bytes from fixed_to_aux to bs (fixed_to_aux > bs: malformed, the caller checks).  Slim image: fixed
+// bytes, CIGAR words, aux bytes = slim_len, zero padded to slim_padded (a slim record starts 16-byte aligned: its CIGAR words, at
+// + 32, are too).  Host image: name and bases = host_len.  k_frame_pack (bam.hip.h) keeps its own statement of this formula.
+struct FrLayout { fr_i64 seq_bytes, fixed_to_aux, slim_len, slim_padded, host_len; };
+FRAME_FN FrLayout fr_layout(fr_i64 bs, fr_i64 l_name, fr_i64 n_cig, fr_i64 l_seq)
+{
+    FrLayout y;
+    y.seq_bytes = (l_seq + 1) / 2; y.fixed_to_aux = 32 + l_name + 4 * n_cig + y.seq_bytes + l_seq;
+    y.slim_len = 32 + 4 * n_cig + (bs - y.fixed_to_aux); y.slim_padded = (y.slim_len + 15) / 16 * 16;
+    y.host_len = l_name + y.seq_bytes;
+    return y;
+}
 
 constexpr fr_i64 FR_MAX_BS = 1ll << 28;
 FRAME_FN fr_i64 fr_slot_size(fr_i64 block_len) { return block_len / 36 + 1; }

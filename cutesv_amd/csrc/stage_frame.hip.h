@@ -127,10 +127,9 @@ int csv_frame_pack(csv_ctx* c, int64_t n, const FrPack* p, int64_t slim_bytes, i
     // every source and destination range is checked before the kernel runs: it trusts the table
     for (i64 r = 0; r < n; r++) {
         const FrPack& q = p[r];
-        const i64 seq = ((i64)q.l_seq + 1) / 2, fixed_to_aux = 32 + (i64)q.l_name + 4 * (i64)q.n_cig + seq + (i64)q.l_seq;
-        const i64 slim_len = 32 + 4 * (i64)q.n_cig + ((i64)q.bs - fixed_to_aux), padded = (slim_len + 15) / 16 * 16;
-        if (q.bs < 32 || fixed_to_aux > q.bs || q.src < 0 || q.src > f.win_n - 4 - (i64)q.bs || q.rec_off < f.slim_bytes || (q.rec_off & 15) || q.rec_off > slim_bytes - padded ||
-            q.host_off < f.host_bytes || q.host_off > host_bytes - (i64)q.l_name - seq)
+        const FrLayout y = fr_layout(q.bs, q.l_name, q.n_cig, q.l_seq);
+        if (q.bs < 32 || y.fixed_to_aux > q.bs || q.src < 0 || q.src > f.win_n - 4 - (i64)q.bs || q.rec_off < f.slim_bytes || (q.rec_off & 15) || q.rec_off > slim_bytes - y.slim_padded ||
+            q.host_off < f.host_bytes || q.host_off > host_bytes - y.host_len)
             return fail(c, CSV_E_INVALID, "bad frame pack: record %lld leaves the window or the images", (long long)r);
     }
     HIP_TRY(c, hipSetDevice(c->device));

@@ -8,15 +8,20 @@ Every record of parse_reads.json.gz and single_pipe.json.gz can be written as BA
 checks the field ranges); none of them has an empty CIGAR (it would become n_cigar_op = 0; test_edge_records has one)."""
 import ctypes as C
 import os
+import shutil
+import struct
 import subprocess
 import sys
+import zlib
 
 import numpy as np
 import pytest
 
 from cutesv_amd import bam, extract, synth, _abi, _lib
 from helpers import load_json, StubRecord
+import bai_writer
 import bam_writer
+import frame_helpers
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REF_LEN = {"1": 248956422, "10": 133797422, "2": 242193529, "7": 159345973, "X": 156040895}
@@ -380,6 +385,105 @@ def test_command_line(tmp_path):
     assert np.load(str(tmp_path / "cols" / "cig_off.npy"))[-1] == sum(len(r["cigar"]) for r in recs)
     out = subprocess.run([sys.executable, "-m", "cutesv_amd.bam", path], cwd=ROOT, env=env, capture_output=True, text=True, check=True).stdout
     assert out.endswith("7\t%d\nX\t0\n*\t0\n" % len(recs))
+
+
+def _host_main_expected(path, ops):
+    """the lines tests/bam_host_main.cpp prints for `ops` on `path`, from BamFile of the product library"""
+    crc = lambda a: zlib.crc32(np.ascontiguousarray(a).tobytes()) & 0xFFFFFFFF       # noqa: E731
+    own = lambda e: str(e)[len(path) + 2:] if str(e).startswith(path + ": ") else str(e)      # noqa: E731  (BamFile puts the path in front)
+    try:
+        bf = bam.BamFile(path, threads=2, index=False)
+    except bam.BamError as e:
+        return ["open: " + own(e)]
+    lines = []
+    with bf:
+        for op in ops:
+            name, _, rest = op.partition(":")
+            f = rest.split(":")
+            chrom = None if not rest or int(f[0]) < 0 else bf.references[int(f[0])]
+            try:
+                if name == "load":
+                    lines.append("load ok" if bf.load_index(required=False) else "load none")
+                elif name == "drop":
+                    bf.drop_index()
+                elif name == "build":
+                    st = bf.build_index()
+                    lines.append("build bytes=%d crc=%08x records=%d" % (st["index_bytes"], crc(np.frombuffer(bf.index_bytes(), np.uint8)), st["records"]))
+                elif name == "count":
+                    lines.append("count %d" % bf.count(chrom))
+                else:
+                    beg, end, k, ranges = {"chunks": lambda: (-bam.ALL, bam.ALL, int(f[1]), None), "region": lambda: (int(f[1]), int(f[2]), (1 << 31) - 8192, None),
+                                           "ranges": lambda: (-bam.ALL, bam.ALL, int(f[1]), bf._ranges([int(x) for x in f[2].split(",")]))}[name]()
+                    flags = _abi.BAM_RESTART
+                    while True:
+                        ch = bf._read(chrom, beg, end, k, flags, ranges)
+                        lines.append("chunk n=%d more=%d slim=%d:%08x rec_off=%08x rec_len=%08x host=%d:%08x host_off=%08x"
+                                     % (ch.n, ch.more, len(ch.slim), crc(ch.slim), crc(ch.rec_off), crc(ch.rec_len), len(ch.host), crc(ch.host), crc(ch.host_off)))
+                        if not ch.more:
+                            break
+                        flags = 0
+            except bam.BamError as e:
+                lines.append(("load error: " if name == "load" else "error: ") + own(e))
+    return lines
+
+
+def test_host_route_under_the_sanitizers(tmp_path):
+    """bam_host.cpp in a stand-alone program (tests/bam_host_main.cpp) built with -fsanitize=address,undefined: the window refills with
+    their kept tail, the packing of both images, index load and build, and the damaged files.  The program exits cleanly - no
+    sanitizer report - and every line it prints is what BamFile of the product library says of the same read on the same file."""
+    gxx = shutil.which("g++")
+    if not gxx:
+        pytest.fail("g++ is needed to build tests/bam_host_main.cpp")
+    exe = str(tmp_path / "bam_host_main")
+    subprocess.run([gxx, "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-static-libasan", "-static-libubsan",
+                    "-o", exe, os.path.join(ROOT, "tests", "bam_host_main.cpp"), os.path.join(ROOT, "cutesv_amd", "csrc", "bam_host.cpp"), "-lz", "-pthread"],
+                   check=True, capture_output=True, text=True)
+    p = lambda n: str(tmp_path / n)                                                # noqa: E731
+    _, case, chrom = all_cases()[0]
+    refs, recs = golden_records(case, chrom)
+    recs.sort(key=lambda d: d["start"])                                            # (the case lists its reads in no order; an index needs a sorted file)
+    refid = case["chroms"].index(chrom)
+    starts = [d["start"] for d in recs]
+    lo, mid, hi = starts[len(starts) // 3], starts[len(starts) // 2], starts[2 * len(starts) // 3]
+    reads = ["chunks:%d:37" % refid, "region:%d:%d:%d" % (refid, lo, hi), "ranges:%d:50:%d,%d,%d,%d,%d,%d" % (refid, starts[3], starts[9] + 1, lo, lo + 1, mid, hi),
+             "count:%d" % refid, "count:-1", "region:%d:%d:%d" % (refid, starts[-1] + 10 ** 7, starts[-1] + 10 ** 7 + 1)]
+    files = []
+    for name, kw in (("default", {}), ("small", dict(block_bytes=512))):
+        for with_bai in (False, True):
+            path = p("%s%d.bam" % (name, with_bai))
+            info = bam_writer.write_bam(path, refs, recs, **kw)
+            if with_bai:
+                bai_writer.write_bai(path)
+            # without a .bai: the forward scan, then a build and the same reads through the built index; with one: the loaded index,
+            # then the forward scan again
+            files.append((path, ["load"] + reads + (["drop"] + reads[:3] if with_bai else ["build"] + reads)))
+        assert name == "default" or info["n_blocks"] > 8 * 256                     # the 256-block window is refilled many times, records crossing its edges
+    # the damaged files: a truncated file, a stream that ends inside a record and inside a block_size word, block_size < 32, fields
+    # that exceed block_size
+    short = frame_helpers.short_records(400)
+    info = bam_writer.write_bam(p("full.bam"), frame_helpers.REFS, short, cuts="record")
+    blob = open(p("full.bam"), "rb").read()
+    bam_writer.write_bam(p("trunc.bam"), refs, recs, eof=False, truncate=1000)
+    tails = {"small.bam": struct.pack("<i", 31) + b"\0" * 40, "short.bam": b"\x40\x00\x00\x00" + b"\0" * 20, "short2.bam": b"\x40\x00"}
+    for name, tail in tails.items():
+        open(p(name), "wb").write(blob[:-28] + bam_writer.bgzf_block(tail) + bam_writer.EOF_BLOCK)
+    stream, lens = frame_helpers.stream_of(p("full.bam"))
+    bad = bytearray(stream)
+    struct.pack_into("<I", bad, info["records"][200]["fixed"] + 16, 1 << 20)        # l_seq of record 200 says more than the record holds
+    cuts = np.r_[0, np.cumsum(lens[:-1])]
+    open(p("fields.bam"), "wb").write(b"".join(bam_writer.bgzf_block(bytes(bad[a:b])) for a, b in zip(cuts[:-1], cuts[1:])) + bam_writer.EOF_BLOCK)
+    files += [(p(n), ["chunks:0:50", "count:0", "build"]) for n in ("trunc.bam", "small.bam", "short.bam", "short2.bam", "fields.bam")]
+    seen = set()
+    for path, ops in files:
+        run = subprocess.run([exe, path, "2"] + ops, capture_output=True, text=True)
+        assert run.returncode == 0 and run.stderr == "", (path, run.returncode, run.stderr[-2000:])
+        got, want = run.stdout.splitlines(), _host_main_expected(path, ops)
+        assert got == want, (path, [(g, w) for g, w in zip(got, want) if g != w][:3], len(got), len(want))
+        if ops[0] == "load":                                                        # the sound files: the index is loaded or built, and every read has records
+            assert got[0] == ("load ok" if "drop" in ops else "load none") and ("drop" in ops or any(ln.startswith("build bytes=") for ln in got))
+            assert not any(ln.startswith("error") for ln in got) and sum(ln.startswith("chunk n=") and " n=0 " not in ln for ln in got) > 2 * 400 // 37
+        seen.update(ln.split(" at ")[0].split(" byte ")[0] for ln in got if ln.startswith(("error", "open")))
+    assert len(seen) >= 4, seen                                                     # the damaged files fail in their different ways
 
 
 # ------------------------------------------------------------------------------------------------ GPU
