@@ -100,6 +100,10 @@ SYMBOLS = [
     ("csv_bam_index_bytes", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]),
     ("csv_bam_index_build_stats", C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_int64),
                                             C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    ("csv_bam_index_format", C.c_int, [C.c_void_p]),
+    ("csv_bam_index_build_csi", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]),
+    ("csv_bam_index_payload", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]),
+    ("csv_bam_index_build_stats_csi", C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_double)]),
     ("csv_bgzf_inflate", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32,
                                    C.c_void_p, C.POINTER(C.c_double)]),
     ("csv_bam_set_inflate", C.c_int, [C.c_void_p, C.c_void_p, C.c_int32]),

@@ -18,9 +18,11 @@ With frame="device"  the inflated window stays on the devi
 A file without a .bai gets one from `BamFile.build_index`: one pass over the file on the reader's routes -
 with frame="device" the index kernels work on the rows of every window, which stay on the device - and the bytes of a .bai
 file (SAMv1 5.2, htslib's conventions).  `BamFile(path, index="build")` loads the index beside the file when there is one and builds one in memory otherwise.
+A .csi beside the file (`index_format`) serves as a .bai does, and `build_index(format="csi")` builds one: the
+index a file with a contig of 2^29 bases or more needs.
 
     python -m cutesv_amd.bam FILE [--chrom C] [--dump-columns DIR] [--inflate {host,device}] [--frame {host,device}] [--idxstats]
-    python -m cutesv_amd.bam FILE --index [--index_out PATH] [--force] [--inflate {host,device}] [--frame {host,device}]
+    python -m cutesv_amd.bam FILE --index [--csi [--min_shift N]] [--index_out PATH] [--force] [--inflate {host,device}] [--frame {host,device}]
 """
 import ctypes as C
 import os
@@ -212,6 +214,7 @@ class BamFile:
         self.set_frame(frame)
         self.has_index = False
         self.index_stats = None
+        self.index_format = None
         build = isinstance(index, str) and index == "build"
         if index is not False:
             try:
@@ -227,42 +230,64 @@ class BamFile:
         return (self._L.csv_bam_error(self._h) or b"").decode(errors="replace")
 
     def load_index(self, path=None, required=True):
-        """csv_bam_index_load: path None tries <bam>.bai, then <bam minus .bam>.bai.  -> has_index.  BamError: the index does not
-        validate (a reader whose load failed has none), or - with required - there is no such file."""
+        """csv_bam_index_load: path None tries <bam>.bai, <bam minus .bam>.bai, then the same two names with .csi.  The format is
+        told by the file's content (index_format: "bai" or "csi").  -> has_index.  BamError: the index does
+        not validate (a reader whose load failed has none), or - with required - there is no such file."""
         rc = self._L.csv_bam_index_load(self._h, None if path is None else os.fsencode(path))
         if rc == _abi.E_STATE and not required:
             return self.has_index
         if rc:
-            self.has_index = False
+            self.has_index, self.index_format = False, None
             raise BamError(self._error_text() or "%s: the index cannot be loaded" % self.path)
         self.has_index = True
+        self._index_format()
         return True
 
-    def build_index(self, write=None, overwrite=False):
-        """csv_bam_index_build: one pass over the whole file on the reader's current routes -> the index is installed (has_index)
+    def _index_format(self):
+        self.index_format = {1: "bai", 2: "csi"}.get(int(self._L.csv_bam_index_format(self._h))) if self.has_index else None
+
+    def build_index(self, write=None, overwrite=False, format="bai", min_shift=14, depth=None):
+        """format "csi": csv_bam_index_build_csi - a CSI index of 2^min_shift-base windows and `depth` levels (None: htslib's rule,
+        the smallest that holds the longest reference), the only kind a file with a contig of 2^29 bases or more can have; write=True
+        then goes to <path>.csi and index_bytes() gives the .csi file, index_payload() what it inflates to; the stats gain `bins` and
+        `ms_loff`, the device time of k_index_loff.
+        csv_bam_index_build: one pass over the whole file on the reader's current routes -> the index is installed (has_index)
         and the stats dict is returned: records, runs, index_bytes, ms (wall), ms_kernels, bytes_up, bytes_down, frame_runs,
         index_windows, inflate / frame (the routes) and their block counters.  write: True - the bytes also go to <path>.bai; a path
         - there; through a temporary file beside the target and os.replace.  FileExistsError, before anything is read, when the
         target exists and overwrite is not set.  BamError: a record the BAI format cannot index or that is out of order (the text
         names the file and the record's ordinal), or what the reader refuses; nothing is installed and nothing is written.  The
         build counts as a read: a FramedChunk handed out before it is dead."""
+        if format not in ("bai", "csi"):
+            raise ValueError("format is \"bai\" or \"csi\", not %r" % (format,))
         target = None
         if write is not None and write is not False:
-            target = os.fspath(self.path) + ".bai" if write is True else os.fspath(write)
+            target = os.fspath(self.path) + "." + format if write is True else os.fspath(write)
             if os.path.exists(target) and not overwrite:
                 raise FileExistsError("%s exists (overwrite=True replaces it)" % target)
         self._read_serial += 1
         n, t0 = C.c_int64(), time.perf_counter()
-        rc = self._L.csv_bam_index_build(self._h, 0, C.byref(n))
+        if format == "csi":
+            rc = self._L.csv_bam_index_build_csi(self._h, int(min_shift), 0 if depth is None else int(depth), C.byref(n))
+        else:
+            rc = self._L.csv_bam_index_build(self._h, 0, C.byref(n))
         ms = (time.perf_counter() - t0) * 1e3
         if rc:
-            raise BamError("%s: %s" % (self.path, self._error_text()))
+            text = self._error_text()
+            if format == "bai" and "which the BAI format cannot index" in text:
+                text += ".  A CSI index has no such limit: build_index(format=\"csi\"), --index --csi on the command line"
+            raise BamError("%s: %s" % (self.path, text))
         self.has_index = True
+        self._index_format()
         v = [C.c_int64() for _ in range(6)]
         msk = C.c_double()
         self._L.csv_bam_index_build_stats(self._h, C.byref(v[0]), C.byref(v[1]), C.byref(msk), C.byref(v[2]), C.byref(v[3]), C.byref(v[4]), C.byref(v[5]))
-        stats = dict(records=int(v[0].value), runs=int(v[1].value), index_bytes=int(n.value), ms=ms, ms_kernels=float(msk.value), bytes_up=int(v[2].value),
+        stats = dict(format=format, records=int(v[0].value), runs=int(v[1].value), index_bytes=int(n.value), ms=ms, ms_kernels=float(msk.value), bytes_up=int(v[2].value),
                      bytes_down=int(v[3].value), frame_runs=int(v[4].value), index_windows=int(v[5].value), written=None)
+        if format == "csi":
+            bins, ms_loff = C.c_int64(), C.c_double()
+            self._L.csv_bam_index_build_stats_csi(self._h, C.byref(bins), C.byref(ms_loff))
+            stats.update(bins=int(bins.value), ms_loff=float(ms_loff.value))
         stats.update(self.inflate_stats())
         stats.update(self.frame_stats())
         if target is not None:
@@ -280,8 +305,19 @@ class BamFile:
         self.index_stats = stats
         return stats
 
+    def index_payload(self):
+        """what the .csi file of a BUILT CSI index inflates to (csv_bam_index_payload).  BamError: the reader holds no built CSI index"""
+        need = C.c_int64()
+        rc = self._L.csv_bam_index_payload(self._h, None, 0, C.byref(need))
+        if rc != _abi.E_CAPACITY:
+            raise BamError("%s: the reader holds no built CSI index (build_index(format=\"csi\"))" % self.path)
+        buf = np.empty(int(need.value), np.uint8)
+        if self._L.csv_bam_index_payload(self._h, buf.ctypes.data, len(buf), C.byref(need)):
+            raise BamError("%s: the built index cannot be fetched" % self.path)
+        return buf.tobytes()
+
     def index_bytes(self):
-        """the bytes of a BUILT index, as a .bai file holds them (csv_bam_index_bytes).  BamError: the reader has no index, or one
+        """the bytes of a BUILT index, as a .bai or .csi file holds them (csv_bam_index_bytes).  BamError: the reader has no index, or one
         loaded from a file (its bins were not kept)"""
         need = C.c_int64()
         rc = self._L.csv_bam_index_bytes(self._h, None, 0, C.byref(need))
@@ -303,7 +339,7 @@ class BamFile:
 
     def drop_index(self):
         self._L.csv_bam_index_drop(self._h)
-        self.has_index = False
+        self.has_index, self.index_format = False, None
 
     def _index_counts(self):
         if not self.has_index:
@@ -685,11 +721,17 @@ def main(argv=None):
     ap.add_argument("--frame", default="host", choices=["host", "device"], help="where the records are framed: on the host, or on the GPU (needs --inflate device) [%(default)s]")
     ap.add_argument("--idxstats", action="store_true", help="print contig, length, mapped and unmapped reads from the index (the table of samtools idxstats) and stop")
     ap.add_argument("--index", action="store_true", help="build the BAM index and write it to FILE.bai (the job of samtools index) on the routes of --inflate / --frame, and stop")
+    ap.add_argument("--csi", action="store_true", help="with --index: build a CSI index and write it to FILE.csi (samtools index -c): the format for contigs of 2^29 bases or more")
+    ap.add_argument("--min_shift", type=int, default=14, metavar="N", help="with --index --csi: 2^N bases per window of the index [14]")
     ap.add_argument("--index_out", metavar="PATH", default=None, help="with --index: write the index there instead")
     ap.add_argument("--force", action="store_true", help="with --index: replace an index file that exists")
     a = ap.parse_args(argv)
     if (a.index_out is not None or a.force) and not a.index:
         ap.error("--index_out and --force go with --index")
+    if (a.csi or a.min_shift != 14) and not a.index:
+        ap.error("--csi and --min_shift go with --index")
+    if a.min_shift != 14 and not a.csi:
+        ap.error("--min_shift goes with --csi")
     if a.idxstats:
         with BamFile(a.bam, threads=a.threads, index=True) as bf:
             for (name, mapped, unmapped, _), length in zip(bf.index_statistics(), bf.lengths):
@@ -713,7 +755,7 @@ def _main(a, ap, ctx):
     if a.index:
         with BamFile(a.bam, threads=a.threads, inflate=ctx, frame=a.frame, index=False) as bf:
             try:
-                st = bf.build_index(write=a.index_out if a.index_out is not None else True, overwrite=a.force)
+                st = bf.build_index(write=a.index_out if a.index_out is not None else True, overwrite=a.force, format="csi" if a.csi else "bai", min_shift=a.min_shift)
             except FileExistsError as e:
                 ap.error("%s: --force replaces it" % e)
             print("wrote %s: %d bytes, %d records, %d chunks before joining, %.1f ms (inflate %s, frame %s)"

@@ -176,7 +176,7 @@ class _Shim:
 
 def call_bam(bam, reference, params, ctx=None, chroms=None, batch=10_000_000, report_readid=False, ignore_sequence=False, threads=None, svid=None,
              as_bytes=False, timings=None, tra_gt=None, include_bed=None, gates=None, reads_table=None, sigs_dir=None, inflate=None, index=None, task_cut=None,
-             cut_threads=16, read_stats=None, frame=None):
+             cut_threads=16, read_stats=None, frame=None, index_format="bai"):
     """-> (VCF body text, svid counters [INS, DEL, BND, DUP, INV]).
 
     bam        a path or an open bam.BamFile (coordinate-sorted; no index is needed, one beside the file is used - see `index`)
@@ -215,12 +215,17 @@ def call_bam(bam, reference, params, ctx=None, chroms=None, batch=10_000_000, re
                build, then for the tasks.  An open BamFile comes with what it has.  With an index every task's read starts at its
                linear-index entry, and under include_bed - unless tra_gt="alignments" fills the alignment table, which needs every
                record - a task reads only the union of its regions (task_ranges), and nothing when it has none.  The gates are
-               unchanged and decide; the text does not depend on the index.
+               unchanged and decide; the text does not depend on the index.  A .csi beside the file serves
+               as well as a .bai.
+    index_format  with index="build": "bai", or "csi" - the format a file with a contig of 2^29 bases or more needs (htslib's
+               min_shift 14 and its rule for the depth).  The text does not depend on it.
     task_cut   None or "uniform": cut_tasks, every contig by `batch`.  "index": cut_tasks_index, the reference's cut from the index
                statistics with `cut_threads` as its -t - under include_bed the cut decides which reads survive, and this is the cut
                cuteSV makes.  ValueError without an index.
     read_stats a dict that receives what the tasks' reads cost: compressed_bytes and n_records summed over the tasks, task_records - the
                records each task read, in task order."""
+    if index_format not in ("bai", "csi"):
+        raise ValueError("index_format must be 'bai' or 'csi', not %r" % (index_format,))
     if task_cut not in (None, "uniform", "index"):
         raise ValueError("task_cut must be None, 'uniform' or 'index', not %r" % (task_cut,))
     if task_cut == "index" and not (getattr(bam, "has_index", False) if hasattr(bam, "references") else index is not False):
@@ -268,7 +273,7 @@ def call_bam(bam, reference, params, ctx=None, chroms=None, batch=10_000_000, re
         bf.set_frame(frame)
         if build_index:
             if not bf.has_index:
-                bf.build_index()
+                bf.build_index(format=index_format)
             lap("ms_index")
         # the chromosome table in name order: a chromosome's index is its name rank, the numbering of rebuild._segments and of a TRA row's mate
         names = sorted(bf.references)

@@ -1,7 +1,7 @@
 """cuteSV's command line on this project's chain:
 
     python -m cutesv_amd BAM REF OUT.vcf WORK_DIR [cuteSV's flags] [--reads_table {host,device}] [--tra_gt MODE] [--inflate {host,device}] [--frame {host,device}]
-                         [--task_cut {index,uniform}] [--build_index]
+                         [--task_cut {index,uniform}] [--build_index] [--index_format {bai,csi}]
 
 `parse_args` accepts every option of cuteSV v2.1.4 under the same short and long spellings, with the same destination, type
 and default, so a command line written for cuteSV runs here unchanged; `main` maps them onto call.call_bam and writes a complete
@@ -13,7 +13,8 @@ What differs from cuteSV, on purpose:
   * The extraction tasks: with a .bai beside the BAM file (cuteSV cannot run without one) they are cuteSV's own cut from the index
     statistics (call.cut_tasks_index with -t; --task_cut index).  Without one - or with --task_cut uniform -
     they are call.cut_tasks' uniform cut of every contig by -b, and one line on stderr says so; with --build_index the missing index
-    is built in memory first (nothing is written) and the cut is cuteSV's.  The calls do not depend on the
+    is built in memory first (nothing is written; --index_format csi for a file with a contig of 2^29 bases or
+    more) and the cut is cuteSV's.  A .csi beside the file serves as a .bai does.  The calls do not depend on the
     cut - except with -include_bed, where a task's reads are tested against the regions of that task only: there the uniform cut
     can differ from cuteSV's on contigs whose batch it would have shrunk.
   * reads.sigs is not written (its row order in cuteSV depends on which worker process wrote which task).
@@ -92,7 +93,7 @@ def _parser():
 
 
 def _own_parser():
-    """the six options cuteSV does not have; parsed apart (split_own), so that they shadow no abbreviation of a cuteSV flag"""
+    """the seven options cuteSV does not have; parsed apart (split_own), so that they shadow no abbreviation of a cuteSV flag"""
     from . import call
     ap = argparse.ArgumentParser(add_help=False, allow_abbrev=False)
     ap.add_argument("--reads_table", default=None, choices=["host", "device"])
@@ -101,11 +102,12 @@ def _own_parser():
     ap.add_argument("--frame", default=None, choices=["host", "device"])
     ap.add_argument("--task_cut", default=None, choices=["index", "uniform"])
     ap.add_argument("--build_index", action="store_true")
+    ap.add_argument("--index_format", default="bai", choices=["bai", "csi"])
     return ap
 
 
 def split_own(argv):
-    """-> (namespace of --reads_table / --tra_gt / --inflate / --frame / --task_cut / --build_index, argv without them)"""
+    """-> (namespace of --reads_table / --tra_gt / --inflate / --frame / --task_cut / --build_index / --index_format, argv without them)"""
     return _own_parser().parse_known_args(list(argv))
 
 
@@ -170,7 +172,7 @@ def main(argv=None):
         body, svid = call.call_bam(source, fasta.Reference(a.reference), call_params(a), batch=a.batches, report_readid=a.report_readid,
                                    ignore_sequence=a.ignore_sequence, as_bytes=True, timings=timings, tra_gt=tra_gt, include_bed=a.include_bed,
                                    reads_table=own.reads_table, sigs_dir=sigs_dir, inflate=own.inflate, frame=own.frame, task_cut=task_cut, cut_threads=a.threads,
-                                   threads=a.threads, index=index)
+                                   threads=a.threads, index=index, index_format=own.index_format)
     finally:
         bf.close()
     for key, ms in timings.items():

@@ -445,6 +445,7 @@ struct IndexArgs {
     IxCarry carry;                  // the record in front of rows[0]
     IxBlocks blocks;                // the whole-file block table
     int n_ref; const i64* l_ref; const i64* lin_off;
+    IxFormat fmt;                   // the binning scheme: BAI's, or a CSI index's own
     u64* lin;                       // the linear arrays of the whole build: IX_NONE or the smallest virtual offset so far
     u64* counts;                    // mapped, unmapped per reference; then the records without coordinates
     IxAux* aux; int4* scan; const i64* totals;
@@ -461,18 +462,18 @@ __global__ __launch_bounds__(256) void k_index_rows(IndexArgs A)
     const int lane = lane_id();
     IxAux x;
     x.vbeg = 0; x.vend = 0; x.ref = -1; x.bin = 0; x.pos = 0; x.head = 0;
-    IxRec r = ix_record(0, 0);
+    IxRec r = ix_record(0, 0, A.fmt);
     bool ok = false, unmapped = false;
     if (live) {
         const FrRow w = A.rows[i];
         IxCarry prev = A.carry;
         if (i > 0) {
             const FrRow q = A.rows[i - 1];
-            prev.valid = 1; prev.ref = q.refid; prev.pos = q.pos; prev.bin = ix_record(q.pos, q.span).bin;
+            prev.valid = 1; prev.ref = q.refid; prev.pos = q.pos; prev.bin = ix_record(q.pos, q.span, A.fmt).bin;
         }
-        r = ix_record(w.pos, w.span);
+        r = ix_record(w.pos, w.span, A.fmt);
         x.ref = w.refid; x.pos = w.pos; x.bin = r.bin;
-        const int why = ix_refuse(w.refid, w.pos, r, A.n_ref, A.l_ref, prev);
+        const int why = ix_refuse(w.refid, w.pos, r, A.n_ref, A.l_ref, prev, A.fmt);
         if (why != IX_OK) atomicMin((u64*)&A.verdict->bad, ((u64)(A.ordinal0 + i) << 3) | (u64)why);
         ok = why == IX_OK;
         const i64 u = A.win_u0 + w.off;
@@ -484,7 +485,7 @@ __global__ __launch_bounds__(256) void k_index_rows(IndexArgs A)
         A.scan[i] = make_int4(x.head, 0, 0, 0);
     }
     const bool mapped_ref = ok && x.ref >= 0;
-    // the linear index: every window of [w0, w1] lies inside the reference's entries (ix_refuse: end <= max(l_ref, 1), end <= 2^29)
+    // the linear index: every window of [w0, w1] lies inside the reference's entries (ix_refuse: end <= max(l_ref, 1), end <= max_pos)
     u64* io = A.lin + (mapped_ref ? A.lin_off[x.ref] : 0);
     const int nw = mapped_ref ? r.w1 - r.w0 + 1 : 0;
     for (int k = 0; k < IX_LANE_WINDOWS; k++) if (k < nw) atomicMin(io + r.w0 + k, x.vbeg);
@@ -527,7 +528,7 @@ __global__ __launch_bounds__(256) void k_index_runs(IndexArgs A)
     if (i == 0) A.verdict->n_runs = A.totals[0] + cont;
     if (i == A.n - 1) {
         const FrRow w = A.rows[i];                               // (the record as it is in the file, refused or not)
-        A.verdict->last = IxCarry{1, w.refid, w.pos, ix_record(w.pos, w.span).bin};
+        A.verdict->last = IxCarry{1, w.refid, w.pos, ix_record(w.pos, w.span, A.fmt).bin};
     }
     if (x.ref < 0) return;
     const i64 heads = (i64)A.scan[i].x + x.head;                 // heads up to and including this record
@@ -548,6 +549,28 @@ __global__ __launch_bounds__(256) void k_index_runs(IndexArgs A)
         }
         IxRun* R = A.runs + run;
         R->end = x.vend; R->n_records = (unsigned)(i - lo + 1);
+    }
+}
+
+// The loffset of a CSI bin: the filled linear entry at the bin's first window, bot - the first touched entry from
+// there on, as empty windows are filled from the next touched one.  One wavefront per (ref, bin) pair reads the reference's array from
+// lin[at[k]] on, 64 entries a step, up to lin + end[k] (the end of the reference's entries), and the lowest lane of the ballot that
+// holds a touched entry writes it; IX_NONE when there is none (the host refuses that: a bin that holds records has a touched window
+// inside its span).  The host checked at[k] <= end[k] <= the array's size.  8 bytes per bin, no dependency between wavefronts.
+struct IndexLoffArgs { const u64* lin; const i64* at; const i64* end; u64* loff; i64 n; };
+
+__global__ __launch_bounds__(256) void k_index_loff(IndexLoffArgs A)
+{
+    const int lane = lane_id();
+    for (i64 k = ((i64)blockIdx.x * 256 + threadIdx.x) >> 6; k < A.n; k += ((i64)gridDim.x * 256) >> 6) {
+        const i64 e = A.end[k];
+        u64 found = IX_NONE;
+        for (i64 w = A.at[k]; w < e; w += WAVE) {                // (k, w and e are the wavefront's: every lane makes the same turns)
+            const u64 v = w + lane < e ? A.lin[w + lane] : IX_NONE;
+            const u64 hit = __ballot(v != IX_NONE ? 1 : 0);
+            if (hit) { found = (u64)shfl_i64((i64)v, __ffsll((long long)hit) - 1); break; }
+        }
+        if (lane == 0) A.loff[k] = found;
     }
 }
 

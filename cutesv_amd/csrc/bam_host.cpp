@@ -5,7 +5,8 @@
 // device inflates, the host only the blocks it gave up on; csv_bam_set_frame (section 29) - the window never leaves the device, the
 // records are framed there (frame_core.h) and the scan runs over the rows of the record table.  With an index (bai_index.h, section
 // 28) a region's scan starts at its linear-index entry; the index moves the starting point and nothing else.  csv_bam_index_build
-// (section 30) makes one in a whole-file pass on the reader's routes, through index_core.h.
+// (section 30) makes one in a whole-file pass on the reader's routes, through index_core.h.  A .csi (csi_index.h, section 32) is read
+// and built as well: index_start / index_stop are the one place that knows which of the two the reader has.
 //
 // Written from the SAM/BAM specification (SAMv1, sections 4.1 "The BGZF compression format" and 4.2 "The BAM format"):
 //   BGZF block  = gzip member with one extra subfield 'B','C' (u16 BSIZE = block size - 1), raw deflate payload, CRC32, ISIZE
@@ -33,6 +34,7 @@
 
 #include "../../include/cutesv_hip.h"
 #include "bai_index.h"
+#include "csi_index.h"
 #include "frame_core.h"
 #include "index_core.h"
 
@@ -50,6 +52,7 @@ struct Block { i64 coff; int32_t csize, hdr; uint32_t isize; i64 uoff; };      /
 
 constexpr int REFILL_BLOCKS = 256;           // BGZF blocks inflated per refill of the window (<= 16 MiB inflated)
 constexpr int AHEAD_STEP_BLOCKS = 16;        // ... past the guessed end of an indexed region
+constexpr int64_t MAX_LIN_ENTRIES = 1ll << 26; // linear entries of one index build over all references (512 MiB of offsets)
 constexpr int MAX_WINDOW_BLOCKS = 16384;     // ... on the device route at most (csv_bam_set_inflate; <= 1 GiB inflated)
 
 }  // namespace
@@ -123,14 +126,21 @@ struct csv_bam {
         i64                  ahead_block = -1;   // with an index: the block where the running region is guessed to end (-1: no guess)
         size_t               range_i = 0;        // csv_bam_read_ranges: the range the scan is in
     } scan;
-    // the index (csv_bam_index_load / csv_bam_index_build): the scan of a region starts at its linear-index entry.  built: it was
-    // built here - its bytes, as a .bai file holds them, and the counters of the build
+    // the index (csv_bam_index_load / csv_bam_index_build): the scan of a region starts at its linear-index entry (a .bai) or at
+    // the loffset of the bin at or in front of it (a .csi); index_start / index_stop ask whichever is there.
+    // The counts of the pseudo-bins are kept here for either.  built: it was built here - its bytes, as the index file holds them
+    // (payload: a .csi's before the BGZF compression), and the counters of the build
     struct Index {
         bool                 has = false, built = false;
+        int                  format = CSV_BAM_INDEX_NONE;
         bai::Index           index;
-        std::vector<uint8_t> bytes;
-        i64                  records = 0, runs = 0, frame_runs = 0, windows = 0, up = 0, down = 0;
-        double               ms_kernels = 0;
+        csi::Index           csi;
+        std::vector<uint64_t> n_mapped, n_unmapped;
+        uint64_t             n_no_coor = 0;
+        bool                 has_no_coor = false;
+        std::vector<uint8_t> bytes, payload;
+        i64                  records = 0, runs = 0, frame_runs = 0, windows = 0, up = 0, down = 0, bins = 0;
+        double               ms_kernels = 0, ms_loff = 0;
     } ix;
     struct Chunk {                               // the chunk handed out last (the host route's images), and what the read cost
         std::vector<uint8_t>  slim, host;
@@ -534,18 +544,29 @@ void begin_read(csv_bam* b)
     if (f.ctx) { csv_frame_chunk_begin(f.ctx, b); csv_frame_counters(f.ctx, nullptr, nullptr, nullptr, nullptr, nullptr, 1); }
 }
 
+// the one place that knows which format the reader's index has
+bool index_start(const csv_bam::Index& x, int32_t ref, i64 beg, uint64_t* voff)
+{
+    return x.format == CSV_BAM_INDEX_CSI ? csi::start_offset(x.csi, ref, beg, voff) : bai::start_offset(x.index, ref, beg, voff);
+}
+bool index_stop(const csv_bam::Index& x, int32_t ref, i64 end, uint64_t* voff)
+{
+    return x.format == CSV_BAM_INDEX_CSI ? csi::stop_guess(x.csi, ref, end, voff) : bai::stop_guess(x.index, ref, end, voff);
+}
+
 // the index positions the scan for range [beg, end) of contig `key`: the cursor moves forward only (never behind `floor`);
 // -> false: the index says that no record overlaps any window from beg's on
 bool index_seek(csv_bam* b, uint32_t key, i64 beg, i64 end, i64 floor)
 {
     csv_bam::Scan& s = b->scan;
     uint64_t v;
-    if (!bai::start_offset(b->ix.index, (int32_t)key, beg, &v)) return false;
+    if (!index_start(b->ix, (int32_t)key, beg, &v)) return false;
     const i64 u = (v >> 16) == (uint64_t)b->file.size ? b->file.utotal : stream_offset(b, v, nullptr);
+    if (floor < b->hdr.first_rec) floor = b->hdr.first_rec;  // (no offset of an index leads into the header)
     s.cur = u > floor ? u : floor;
     s.seeked = true; s.seek_key = key;                       // (also from `floor`, a hint: the scan that set it was positioned by the index too)
     size_t k = b->file.blocks.size() - 1;
-    if (bai::stop_guess(b->ix.index, (int32_t)key, end, &v) && (v >> 16) != (uint64_t)b->file.size) stream_offset(b, v, &k);
+    if (index_stop(b->ix, (int32_t)key, end, &v) && (v >> 16) != (uint64_t)b->file.size) stream_offset(b, v, &k);
     s.ahead_block = (i64)k;
     return true;
 }
@@ -687,20 +708,99 @@ int voff_check(void* user, uint64_t voff)
 
 // a parsed and validated index becomes the reader's (csv_bam_index_drop is the counterpart).  built: the bytes it was parsed from,
 // kept for csv_bam_index_bytes; NULL: it came from a file.  What earlier scans guessed with another index, or none, is forgotten
-void install_index(csv_bam* b, bai::Index&& ix, std::vector<uint8_t>* built)
+void install_common(csv_bam* b, int format, std::vector<uint8_t>* built)
 {
-    b->ix.index = std::move(ix);
+    b->ix.format = format;
     b->ix.has = true; b->ix.built = built != nullptr;
     if (built) b->ix.bytes = std::move(*built); else b->ix.bytes.clear();
+    b->ix.payload.clear();
     b->scan.hint_at = -1; b->scan.ahead_block = -1;
+}
+
+template <class Refs> void keep_counts(csv_bam::Index& x, const Refs& refs, uint64_t n_no_coor, bool has_no_coor)
+{
+    x.n_mapped.clear(); x.n_unmapped.clear();
+    for (const auto& R : refs) { x.n_mapped.push_back(R.n_mapped); x.n_unmapped.push_back(R.n_unmapped); }
+    x.n_no_coor = n_no_coor; x.has_no_coor = has_no_coor;
+}
+
+void install_index(csv_bam* b, bai::Index&& ix, std::vector<uint8_t>* built)
+{
+    keep_counts(b->ix, ix.refs, ix.n_no_coor, ix.has_no_coor);
+    b->ix.index = std::move(ix);
+    b->ix.csi = csi::Index();
+    install_common(b, CSV_BAM_INDEX_BAI, built);
+}
+
+// ... a .csi's: built: the file's bytes, with the payload they inflate to
+void install_index(csv_bam* b, csi::Index&& ix, std::vector<uint8_t>* built, std::vector<uint8_t>* payload)
+{
+    keep_counts(b->ix, ix.refs, ix.n_no_coor, ix.has_no_coor);
+    b->ix.csi = std::move(ix);
+    b->ix.index = bai::Index();
+    install_common(b, CSV_BAM_INDEX_CSI, built);
+    if (payload) b->ix.payload = std::move(*payload);
+}
+
+// an index file that is BGZF-compressed as a whole -> its payload, with the reader's own block walk and inflate
+bool inflate_index_file(const std::vector<uint8_t>& data, const std::string& name, std::vector<uint8_t>* payload, std::string* err)
+{
+    csv_bam f;
+    f.file.map = data.data(); f.file.size = (i64)data.size();
+    if (index_blocks(&f) != CSV_OK) { *err = name + ": " + f.err; return false; }
+    payload->resize((size_t)f.file.utotal);
+    for (const Block& k : f.file.blocks)
+        if (!inflate_block(&f, k, payload->data() + k.uoff)) {
+            *err = name + ": the BGZF block at byte " + std::to_string((long long)k.coff) + " does not inflate";
+            return false;
+        }
+    return true;
+}
+
+// does the file begin like a BGZF block?  A .bai begins "BAI\1"; what is BGZF-compressed as a whole is taken for a .csi, whose parser
+// then asks for the CSI magic in the payload
+bool looks_like_bgzf(const std::vector<uint8_t>& data)
+{
+    return data.size() >= 18 && data[0] == 0x1f && data[1] == 0x8b && data[2] == 8 && (data[3] & 4) && data[12] == 'B' && data[13] == 'C';
+}
+
+// payload -> the bytes of the .csi file: BGZF blocks of at most 0xff00 bytes each, and the end-of-file block
+bool bgzf_compress(const std::vector<uint8_t>& payload, std::vector<uint8_t>* out)
+{
+    static const uint8_t head[16] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0};
+    out->clear();
+    std::vector<uint8_t> z_out(0x10000 + 1024);
+    for (size_t at = 0; at <= payload.size();) {
+        const size_t len = at < payload.size() ? std::min<size_t>(payload.size() - at, 0xff00) : 0;      // (len 0: the end-of-file block)
+        z_stream z;
+        memset(&z, 0, sizeof z);
+        if (deflateInit2(&z, Z_DEFAULT_COMPRESSION, Z_DEFLATED, -15, 8, Z_DEFAULT_STRATEGY) != Z_OK) return false;
+        z.next_in = const_cast<Bytef*>(payload.data() + (len ? at : 0)); z.avail_in = (uInt)len;
+        z.next_out = z_out.data(); z.avail_out = (uInt)z_out.size();
+        const int rc = deflate(&z, Z_FINISH);
+        const size_t clen = z_out.size() - z.avail_out;
+        deflateEnd(&z);
+        if (rc != Z_STREAM_END || clen + 26 > 0x10000) return false;         // (0xff00 bytes never deflate to more than 64 KiB - 26)
+        const uint16_t bsize = (uint16_t)(clen + 25);
+        const uint32_t crc = (uint32_t)crc32(crc32(0L, Z_NULL, 0), payload.data() + (len ? at : 0), (uInt)len), isize = (uint32_t)len;
+        out->insert(out->end(), head, head + 16);
+        out->push_back((uint8_t)(bsize & 0xff)); out->push_back((uint8_t)(bsize >> 8));
+        out->insert(out->end(), z_out.data(), z_out.data() + clen);
+        uint8_t tail[8];
+        memcpy(tail, &crc, 4); memcpy(tail + 4, &isize, 4);
+        out->insert(out->end(), tail, tail + 8);
+        if (len == 0) break;
+        at += len;
+    }
+    return true;
 }
 
 struct IxTables { std::vector<csv::ix_i64> uoff, coff, l_ref; std::vector<uint32_t> isize; };
 
-int index_refuse(csv_bam* b, long long ordinal, int why)
+int index_refuse(csv_bam* b, long long ordinal, int why, const csv::ix::Builder& B)
 {
-    char buf[256];
-    snprintf(buf, sizeof buf, "cannot build the index: record %lld %s", ordinal, csv::ix_refusal_text(why));
+    char buf[384];
+    snprintf(buf, sizeof buf, "cannot build the index: record %lld %s", ordinal, csv::ix::refusal_text(why, B.fmt, B.csi).c_str());
     b->err = buf;
     return CSV_E_INVALID;
 }
@@ -715,20 +815,24 @@ int index_build_host(csv_bam* b, const IxTables& T, csv::ix::Builder* B)
         const int rc = next_host(b, &r, &at_end);
         if (rc) return rc;
         if (at_end) return CSV_OK;
-        const csv::IxRec x = csv::ix_record(r.pos, cigar_span(r.p, r.bs, r.l_name, r.n_cig));
-        const int why = csv::ix_refuse((int32_t)r.rkey, r.pos, x, b->hdr.n_ref, T.l_ref.data(), B->prev);
-        if (why) return index_refuse(b, B->records, why);
+        const csv::IxRec x = csv::ix_record(r.pos, cigar_span(r.p, r.bs, r.l_name, r.n_cig), B->fmt);
+        const int why = csv::ix_refuse((int32_t)r.rkey, r.pos, x, b->hdr.n_ref, T.l_ref.data(), B->prev, B->fmt);
+        if (why) return index_refuse(b, B->records, why, *B);
         B->add_record((int32_t)r.rkey, r.pos, x, (rd_u16(r.p + 14) & 4) != 0, csv::ix_voff(blocks, b->scan.cur), csv::ix_voff(blocks, b->scan.cur + 4 + r.bs));
         b->scan.cur += 4 + r.bs;
     }
 }
 
 // the framing route: window by window, the rows stay on the device (frame_step without rows) and the index kernels read them
-// there; the verdict and the runs come down
+// there; the verdict and the runs come down.  csi: at the end k_index_loff gathers one loffset per bin from the linear arrays, which
+// then stay on the device
 int index_build_device(csv_bam* b, const IxTables& T, csv::ix::Builder* B)
 {
+    const bool csi = B->csi;
     csv_ctx* ctx = b->fr.ctx;
-    int rc = csv_index_begin(ctx, b->hdr.n_ref, T.l_ref.data(), (int64_t)T.uoff.size(), T.uoff.data(), T.coff.data(), T.isize.data());
+    if (csi && (!csv_index_begin_fmt || !csv_index_end_loff)) return fail(b, CSV_E_STATE, "%sthis build of the reader has no device route for a CSI index", "");
+    int rc = csi ? csv_index_begin_fmt(ctx, &B->fmt, b->hdr.n_ref, T.l_ref.data(), (int64_t)T.uoff.size(), T.uoff.data(), T.coff.data(), T.isize.data())
+                 : csv_index_begin(ctx, b->hdr.n_ref, T.l_ref.data(), (int64_t)T.uoff.size(), T.uoff.data(), T.coff.data(), T.isize.data());
     if (rc) return fail(b, rc, "the device index build failed: %s", csv_last_error(ctx));
     csv::IxCarry carry{0, 0, 0, 0};
     bool at_tail = false;
@@ -746,7 +850,7 @@ int index_build_device(csv_bam* b, const IxTables& T, csv::ix::Builder* B)
             const csv::IxRun* runs = nullptr;
             rc = csv_index_window(ctx, b->fr.n, b->win.u0, B->records, &carry, &V, &runs);
             if (rc) return fail(b, rc, "the device index build failed: %s", csv_last_error(ctx));
-            if (V.bad != csv::IX_NONE) return index_refuse(b, (long long)(V.bad >> 3), (int)(V.bad & 7));
+            if (V.bad != csv::IX_NONE) return index_refuse(b, (long long)(V.bad >> 3), (int)(V.bad & 7), *B);
             for (i64 k = 0; k < V.n_runs; k++) B->add_run(runs[k]);
             b->ix.runs += V.n_runs;
             B->records += b->fr.n;
@@ -757,7 +861,15 @@ int index_build_device(csv_bam* b, const IxTables& T, csv::ix::Builder* B)
         at_tail = b->fr.tail_has_bs;
         b->scan.cur = b->fr.tail;
     }
-    rc = csv_index_end(ctx, B->lin.data(), (int64_t)B->lin.size(), B->counts.data(), (int64_t)B->counts.size());
+    if (csi) {
+        const std::vector<uint32_t> pairs = B->pairs();
+        B->loff.assign(pairs.size() / 2, csv::IX_NONE);
+        B->has_loff = true;
+        rc = csv_index_end_loff(ctx, (int64_t)B->loff.size(), pairs.data(), B->loff.data(), B->counts.data(), (int64_t)B->counts.size());
+        if (!rc)
+            for (size_t k = 0; k < B->loff.size(); k++)          // (a bin that holds records has a touched window inside its span)
+                if (B->loff[k] == csv::IX_NONE) return fail(b, CSV_E_INVALID, "%sthe device index build found no linear entry for bin %lld", "", (long long)pairs[2 * k + 1]);
+    } else rc = csv_index_end(ctx, B->lin.data(), (int64_t)B->lin.size(), B->counts.data(), (int64_t)B->counts.size());
     if (rc) return fail(b, rc, "the device index build failed: %s", csv_last_error(ctx));
     return CSV_OK;
 }
@@ -923,19 +1035,27 @@ int csv_bam_index_load(csv_bam* b, const char* path)
     if (path) tries.push_back(path);
     else {
         tries.push_back(bam + ".bai");
-        if (bam.size() > 4 && bam.compare(bam.size() - 4, 4, ".bam") == 0) tries.push_back(bam.substr(0, bam.size() - 4) + ".bai");
+        const bool stem = bam.size() > 4 && bam.compare(bam.size() - 4, 4, ".bam") == 0;
+        if (stem) tries.push_back(bam.substr(0, bam.size() - 4) + ".bai");
+        tries.push_back(bam + ".csi");
+        if (stem) tries.push_back(bam.substr(0, bam.size() - 4) + ".csi");
     }
     for (const std::string& t : tries) {
         std::vector<uint8_t> data;
         if (!read_file(t, &data)) continue;
         bai::Index ix;
+        csi::Index cx;
+        std::vector<uint8_t> payload;
         std::string err;
-        if (!bai::parse(data.data(), data.size(), b->hdr.n_ref, t.c_str(), voff_check, b, &ix, &err)) {
+        const bool is_csi = looks_like_bgzf(data);            // the format is told by content, never by the file's name
+        const bool ok = is_csi ? inflate_index_file(data, t, &payload, &err) && csi::parse(payload.data(), payload.size(), b->hdr.n_ref, t.c_str(), voff_check, b, &cx, &err)
+                               : bai::parse(data.data(), data.size(), b->hdr.n_ref, t.c_str(), voff_check, b, &ix, &err);
+        if (!ok) {
             csv_bam_index_drop(b);                           // a reader whose load failed has no index, whatever it had
             b->err = err;
             return CSV_E_INVALID;
         }
-        install_index(b, std::move(ix), nullptr);
+        if (is_csi) install_index(b, std::move(cx), nullptr, nullptr); else install_index(b, std::move(ix), nullptr);
         return CSV_OK;
     }
     b->err = path ? std::string("cannot read the index ") + path : "no index beside " + bam + " (" + tries[0] + (tries.size() > 1 ? ", " + tries[1] : "") + ")";
@@ -945,8 +1065,10 @@ int csv_bam_index_load(csv_bam* b, const char* path)
 int csv_bam_index_drop(csv_bam* b)
 {
     if (!b) return CSV_E_INVALID;
-    b->ix.index = bai::Index();
-    b->ix.has = b->ix.built = false; b->ix.bytes.clear();
+    b->ix.index = bai::Index(); b->ix.csi = csi::Index();
+    b->ix.format = CSV_BAM_INDEX_NONE;
+    b->ix.n_mapped.clear(); b->ix.n_unmapped.clear(); b->ix.has_no_coor = false;
+    b->ix.has = b->ix.built = false; b->ix.bytes.clear(); b->ix.payload.clear();
     b->scan.hint_at = -1; b->scan.ahead_block = -1; b->scan.seeked = false;
     return CSV_OK;
 }
@@ -956,10 +1078,10 @@ int csv_bam_index_stats(const csv_bam* b, int64_t* mapped, int64_t* unmapped, in
     if (!b) return CSV_E_INVALID;
     if (!b->ix.has) return CSV_E_STATE;
     for (int32_t r = 0; r < b->hdr.n_ref; r++) {
-        if (mapped) mapped[r] = (int64_t)b->ix.index.refs[(size_t)r].n_mapped;
-        if (unmapped) unmapped[r] = (int64_t)b->ix.index.refs[(size_t)r].n_unmapped;
+        if (mapped) mapped[r] = (int64_t)b->ix.n_mapped[(size_t)r];
+        if (unmapped) unmapped[r] = (int64_t)b->ix.n_unmapped[(size_t)r];
     }
-    if (n_no_coor) *n_no_coor = b->ix.index.has_no_coor ? (int64_t)b->ix.index.n_no_coor : -1;
+    if (n_no_coor) *n_no_coor = b->ix.has_no_coor ? (int64_t)b->ix.n_no_coor : -1;
     return CSV_OK;
 }
 
@@ -967,27 +1089,29 @@ int64_t csv_bam_index_block(const csv_bam* b, int32_t refid, int64_t beg)
 {
     if (!b || !b->ix.has || refid < 0 || refid >= b->hdr.n_ref) return -2;
     uint64_t v;
-    if (!bai::start_offset(b->ix.index, refid, beg, &v)) return -1;
+    if (!index_start(b->ix, refid, beg, &v)) return -1;
     if ((v >> 16) == (uint64_t)b->file.size) return (int64_t)b->file.blocks.size() - 1;
     size_t k;
     stream_offset(b, v, &k);
     return (int64_t)k;
 }
 
-int csv_bam_index_build(csv_bam* b, int32_t flags, int64_t* n_bytes)
+int csv_bam_index_format(const csv_bam* b) { return b && b->ix.has ? b->ix.format : CSV_BAM_INDEX_NONE; }
+
+// the build of either format: csi NULL - a .bai
+static int index_build(csv_bam* b, const csv::IxFormat* csi, int64_t* n_bytes)
 {
-    if (!b || flags != 0) return CSV_E_INVALID;
     if (n_bytes) *n_bytes = 0;
     csv_bam::Index& x = b->ix;
     csv_bam::Scan& s = b->scan;
     begin_read(b);                                           // the build is a read; the scan state of a region is forgotten as well
     s.seeked = false; s.ahead_block = -1; s.hint_at = -1; s.range_i = 0;
-    x.records = x.runs = x.frame_runs = x.windows = x.up = x.down = 0; x.ms_kernels = 0;
+    x.records = x.runs = x.frame_runs = x.windows = x.up = x.down = x.bins = 0; x.ms_kernels = x.ms_loff = 0;
     IxTables T;
     for (const Block& k : b->file.blocks) { T.uoff.push_back(k.uoff); T.coff.push_back(k.coff); T.isize.push_back(k.isize); }
     T.l_ref.assign(b->hdr.lengths.begin(), b->hdr.lengths.end());
     csv::ix::Builder B;
-    B.begin(b->hdr.n_ref, T.l_ref.data());
+    B.begin(b->hdr.n_ref, T.l_ref.data(), csi ? *csi : csv::ix_bai(), csi != nullptr);
     s.cur = b->hdr.first_rec;
     const int rc = b->fr.ctx ? index_build_device(b, T, &B) : index_build_host(b, T, &B);
     x.ms_kernels = b->dev.ms_kernels;
@@ -1004,6 +1128,21 @@ int csv_bam_index_build(csv_bam* b, int32_t flags, int64_t* n_bytes)
     x.records = B.records;
     if (!b->fr.ctx) x.runs = (i64)B.runs.size();
     // the built bytes take the path a file's bytes take: parsed and validated against this file's blocks, then installed
+    if (csi) {
+        x.bins = (i64)B.pairs().size() / 2;
+        if (b->fr.ctx && csv_index_loff_ms) x.ms_loff = csv_index_loff_ms(b->fr.ctx);
+        std::vector<uint8_t> payload = B.bytes_csi(), bytes;
+        csi::Index cx;
+        std::string err;
+        if (!csi::parse(payload.data(), payload.size(), b->hdr.n_ref, "the built index", voff_check, b, &cx, &err)) {
+            b->err = "cannot build the index: " + err;
+            return CSV_E_INVALID;
+        }
+        if (!bgzf_compress(payload, &bytes)) return fail(b, CSV_E_INVALID, "%scannot build the index: the payload does not deflate", "");
+        install_index(b, std::move(cx), &bytes, &payload);
+        if (n_bytes) *n_bytes = (int64_t)x.bytes.size();
+        return CSV_OK;
+    }
     std::vector<uint8_t> bytes = B.bytes();
     bai::Index ix;
     std::string err;
@@ -1013,6 +1152,46 @@ int csv_bam_index_build(csv_bam* b, int32_t flags, int64_t* n_bytes)
     }
     install_index(b, std::move(ix), &bytes);
     if (n_bytes) *n_bytes = (int64_t)x.bytes.size();
+    return CSV_OK;
+}
+
+int csv_bam_index_build(csv_bam* b, int32_t flags, int64_t* n_bytes)
+{
+    if (!b || flags != 0) return CSV_E_INVALID;
+    return index_build(b, nullptr, n_bytes);
+}
+
+int csv_bam_index_build_csi(csv_bam* b, int32_t min_shift, int32_t depth, int64_t* n_bytes)
+{
+    if (!b) return CSV_E_INVALID;
+    if (n_bytes) *n_bytes = 0;
+    if (min_shift < 4 || min_shift > 31 || depth < 0) return fail(b, CSV_E_INVALID, "%scannot build the index: min_shift must be 4 .. 31 and depth 0 or more (min_shift %lld)", "", min_shift);
+    const std::vector<csv::ix_i64> l_ref(b->hdr.lengths.begin(), b->hdr.lengths.end());
+    if (depth == 0) depth = csv::ix::auto_depth(min_shift, b->hdr.n_ref, l_ref.data());
+    const csv::IxFormat F = csv::ix_format(min_shift, depth);
+    if (!csv::ix_format_ok(F)) return fail(b, CSV_E_INVALID, "%scannot build the index: min_shift + 3 * depth must stay at or below 62 and depth at or below 9 (depth %lld)", "", depth);
+    csv::ix_i64 entries = 0;
+    for (i64 l : b->hdr.lengths) entries += csv::ix_lin_entries(l, F);
+    if (entries > MAX_LIN_ENTRIES) return fail(b, CSV_E_INVALID, "%scannot build the index: min_shift is too small for these references (%lld windows)", "", (long long)entries);
+    return index_build(b, &F, n_bytes);
+}
+
+int csv_bam_index_payload(const csv_bam* b, uint8_t* out, int64_t cap, int64_t* need)
+{
+    if (!b) return CSV_E_INVALID;
+    if (need) *need = 0;
+    if (!b->ix.has || !b->ix.built || b->ix.format != CSV_BAM_INDEX_CSI) return CSV_E_STATE;
+    if (need) *need = (int64_t)b->ix.payload.size();
+    if (!out || cap < (int64_t)b->ix.payload.size()) return CSV_E_CAPACITY;
+    memcpy(out, b->ix.payload.data(), b->ix.payload.size());
+    return CSV_OK;
+}
+
+int csv_bam_index_build_stats_csi(const csv_bam* b, int64_t* bins, double* ms_loff)
+{
+    if (!b) return CSV_E_INVALID;
+    if (bins) *bins = b->ix.bins;
+    if (ms_loff) *ms_loff = b->ix.ms_loff;
     return CSV_OK;
 }
 

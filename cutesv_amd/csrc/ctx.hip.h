@@ -196,6 +196,9 @@ struct IndexBuildState {
     Buf blocks, refs, lin, counts, work;
     i64 n_blocks = 0, n_lin = 0;
     int n_ref = -1;                            // -1: no build is open
+    IxFormat fmt = ix_bai();                   // the scheme of the open build
+    std::vector<i64> lin_off_h;                // n_ref + 1: the host's copy, for the checks of csv_index_end_loff
+    double ms_loff = 0;                        // k_index_loff of the last CSI build
     std::vector<IxRun> runs_h;
     double ms_kernels = 0;
     i64 bytes_down = 0, bytes_up = 0, windows = 0;

@@ -949,6 +949,32 @@ int         csv_bam_index_bytes(const csv_bam* bam, uint8_t* out, int64_t cap, i
 int         csv_bam_index_build_stats(const csv_bam* bam, int64_t* records, int64_t* runs, double* ms_kernels, int64_t* bytes_up, int64_t* bytes_down,
                                       int64_t* frame_runs, int64_t* index_windows);
 
+/* The CSI index (.csi; parsed by csrc/csi_index.h, which restates the format): what `samtools index -c` writes,
+ * and the only index a BAM with a contig of 2^29 bases or more can have.  csv_bam_index_load tells the format by content - a file
+ * whose first member is a BGZF block with a payload that begins "CSI\1" is a CSI index, inflated with the reader's host BGZF code and
+ * validated like a .bai (the magic; n_ref; negative or absurd counts; min_shift < 1, depth < 0 or min_shift + 3 * depth > 62; a bin
+ * above the pseudo-bin; a pseudo-bin without two chunks; a chunk that ends before it begins; the end of the payload inside a field;
+ * the virtual offsets; a loffset behind a chunk of its own bin or decreasing with the bin's first base).  With path == NULL,
+ * "<bam path>.csi" and the BAM path with ".bam" replaced by ".csi" are tried after the two .bai names.  A region's scan starts at the
+ * loffset of the bin with the greatest first base at or in front of `beg`, else at the reference's first record: coarser than a
+ * .bai's linear index wherever the 2^min_shift-base bin at `beg` is not in the file, and under the same contract.  Everything above
+ * (csv_bam_index_stats, csv_bam_index_block, csv_bam_read_ranges) works unchanged.  csv_bam_index_format says what the reader has.
+ *
+ * csv_bam_index_build_csi is csv_bam_index_build for a CSI index of 2^min_shift-base windows (4 .. 31; htslib's default is 14) and
+ * `depth` levels under the root (0: htslib's rule, the smallest depth with max(l_ref) + 256 <= 2^(min_shift + 3 * depth)): the same
+ * pass on the same routes, the same refusals with the range now 2^(min_shift + 3 * depth), in a text that names min_shift and depth.
+ * On the framing route the linear arrays stay on the device: k_index_loff gathers one loffset per bin.  csv_bam_index_bytes then gives
+ * the bytes of the .csi FILE (BGZF blocks and the end-of-file block), csv_bam_index_payload the payload they inflate to (CSV_E_STATE
+ * unless the reader holds a built CSI index; CSV_E_CAPACITY as csv_bam_index_bytes).  csv_bam_index_build_stats_csi, of the last CSI
+ * build: the bins written (the pseudo-bins aside) and the device time of k_index_loff (0 on the host routes). */
+#define CSV_BAM_INDEX_NONE 0
+#define CSV_BAM_INDEX_BAI  1
+#define CSV_BAM_INDEX_CSI  2
+int         csv_bam_index_format(const csv_bam* bam);
+int         csv_bam_index_build_csi(csv_bam* bam, int32_t min_shift, int32_t depth, int64_t* n_bytes);
+int         csv_bam_index_payload(const csv_bam* bam, uint8_t* out, int64_t cap, int64_t* need);
+int         csv_bam_index_build_stats_csi(const csv_bam* bam, int64_t* bins, double* ms_loff);
+
 /* BGZF inflate on the device: the raw-deflate payloads of n_blocks BGZF blocks -> their bytes, one wavefront
  * per block.  Block k's payload is comp[in_off[k] .. + in_len[k]), its out_len[k] (= ISIZE) bytes go to out[out_off[k] ..), crc[k]
  * is the CRC32 of its trailer; comp, out and status are host memory.
