@@ -1,13 +1,19 @@
 """cuteSV's command line on this project's chain:
 
     python -m cutesv_amd BAM REF OUT.vcf WORK_DIR [cuteSV's flags] [--reads_table {host,device}] [--tra_gt MODE] [--inflate {host,device}] [--frame {host,device}]
-                         [--task_cut {index,uniform}] [--build_index] [--index_format {bai,csi}]
+                         [--task_cut {index,uniform}] [--build_index] [--index_format {bai,csi}] [--bgzf {host,device}]
 
 `parse_args` accepts every option of cuteSV v2.1.4 under the same short and long spellings, with the same destination, type
 and default, so a command line written for cuteSV runs here unchanged; `main` maps them onto call.call_bam and writes a complete
 VCF file: vcf.header_text followed by the records.  With --write_old_sigs the work directory receives DEL.sigs, INS.sigs,
 DUP.sigs, INV.sigs and TRA.sigs, made on the device (rebuild.write_sigs); without --retain_work_dir they are removed again at
-the end, as cuteSV's cleanup removes its own.
+the end, as cuteSV's cleanup removes its own.  An OUT name that ends in .gz or .bgz is written BGZF-compressed - header and records as
+one stream - with its tabix index OUT.tbi beside it (bgzf.py; --bgzf picks the compressor: zlib on host threads
+or csv_bgzf_deflate on the device); any other name receives the plain text, as before.
+
+The files of this chain: cli.py (this command line) -> call.py (call_bam: BAM to VCF records) over bam.py (the reader), extract.py,
+rebuild.py, engine.py and genotype.py; vcf.py (header and records), fasta.py (the reference), bgzf.py (the BGZF writer and the tabix
+index of a compressed OUT).
 
 What differs from cuteSV, on purpose:
   * The extraction tasks: with a .bai beside the BAM file (cuteSV cannot run without one) they are cuteSV's own cut from the index
@@ -93,7 +99,7 @@ def _parser():
 
 
 def _own_parser():
-    """the seven options cuteSV does not have; parsed apart (split_own), so that they shadow no abbreviation of a cuteSV flag"""
+    """the eight options cuteSV does not have; parsed apart (split_own), so that they shadow no abbreviation of a cuteSV flag"""
     from . import call
     ap = argparse.ArgumentParser(add_help=False, allow_abbrev=False)
     ap.add_argument("--reads_table", default=None, choices=["host", "device"])
@@ -103,11 +109,12 @@ def _own_parser():
     ap.add_argument("--task_cut", default=None, choices=["index", "uniform"])
     ap.add_argument("--build_index", action="store_true")
     ap.add_argument("--index_format", default="bai", choices=["bai", "csi"])
+    ap.add_argument("--bgzf", default=None, choices=["host", "device"])
     return ap
 
 
 def split_own(argv):
-    """-> (namespace of --reads_table / --tra_gt / --inflate / --frame / --task_cut / --build_index / --index_format, argv without them)"""
+    """-> (namespace of --reads_table / --tra_gt / --inflate / --frame / --task_cut / --build_index / --index_format / --bgzf, argv without them)"""
     return _own_parser().parse_known_args(list(argv))
 
 
@@ -130,6 +137,23 @@ def call_params(a):
 
 def _log(msg):
     print("cutesv_amd: " + msg, file=sys.stderr)
+
+
+def _write_bgzf(path, text, route):
+    """header and records as one BGZF stream into `path`, its tabix index into path + ".tbi"; one log line each"""
+    from . import bgzf
+    route = bgzf.DEFAULT_ROUTE if route is None else route
+    t0 = time.perf_counter()
+    image, table = bgzf.compress(text, route=route)
+    t1 = time.perf_counter()
+    tbi = bgzf.tabix_vcf(text, table)
+    t2 = time.perf_counter()
+    with open(path, "wb") as f:
+        f.write(image)
+    with open(path + ".tbi", "wb") as f:
+        f.write(tbi)
+    _log("%-16s %10.1f ms  (%s: %d -> %d bytes in %d blocks)" % ("bgzf", 1e3 * (t1 - t0), route, len(text), len(image), len(table[0])))
+    _log("%-16s %10.1f ms  (%s.tbi, %d bytes)" % ("tabix", 1e3 * (t2 - t1), os.path.basename(path), len(tbi)))
 
 
 def main(argv=None):
@@ -177,8 +201,12 @@ def main(argv=None):
         bf.close()
     for key, ms in timings.items():
         _log("%-16s %10.1f ms" % (key[3:] if key.startswith("ms_") else key, ms))
-    with open(a.output, "wb") as f:
-        f.write(vcf.header_text(contigs, a.sample, argv).encode() + body)
+    text = vcf.header_text(contigs, a.sample, argv).encode() + body
+    if a.output.endswith((".gz", ".bgz")):
+        _write_bgzf(a.output, text, own.bgzf)
+    else:
+        with open(a.output, "wb") as f:
+            f.write(text)
     if sigs_dir is not None and not a.retain_work_dir:
         for t in TYPES:
             path = os.path.join(sigs_dir, t + ".sigs")

@@ -19,13 +19,15 @@
 // of inflate_core.h; and behind it the record framing on the device (frame_core.h):
 // k_frame_guess, k_frame_stitch, k_frame_rows find the records of an inflated window that never left the device, k_frame_pack
 // builds the slim and the host image from the records the reader selected; and last the index build (index_core.h, DESIGN.md
-// section 30): k_index_rows and k_index_runs turn the rows of a framed window into the runs and the linear index of a .bai.
+// section 30): k_index_rows and k_index_runs turn the rows of a framed window into the runs and the linear index of a .bai.  Last of all the
+// way back out: k_bgzf_deflate, one wavefront per block over deflate_core.h, and k_deflate_offsets.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "wave.hip.h"
 #include "scan.hip.h"
 #include "inflate_core.h"
+#include "deflate_core.h"
 #include "frame_core.h"
 #include "index_core.h"
 
@@ -572,6 +574,69 @@ __global__ __launch_bounds__(256) void k_index_loff(IndexLoffArgs A)
         }
         if (lane == 0) A.loff[k] = found;
     }
+}
+
+// ------------------------------------------------------------------------------------ BGZF deflate
+// The 64-lane form of deflate_core.h's Lanes, over InfWave.  amax / add / or32: LDS atomics on results that do not depend on the
+// order of arrival; ballot_nz and scan64 are called where the wavefront has converged (the tile loops of the core).
+struct DflWave : InfWave {
+    __device__ __forceinline__ void amax(uint32_t* p, uint32_t v) const { atomicMax(p, v); }
+    __device__ __forceinline__ void add(uint32_t* p, uint32_t v) const { atomicAdd(p, v); }
+    __device__ __forceinline__ void or32(uint32_t* p, uint32_t v) const { atomicOr(p, v); }
+    __device__ __forceinline__ uint64_t ballot_nz(const uint16_t* a) const { return __ballot(a[lane_id()] != 0 ? 1 : 0); }
+    __device__ __forceinline__ uint32_t scan64(uint32_t* a) const
+    {
+        const int v = (int)a[lane_id()], inc = wave_incl_scan_i32(v);
+        a[lane_id()] = (uint32_t)(inc - v);
+        return (uint32_t)__builtin_amdgcn_readlane(inc, 63);
+    }
+};
+
+struct DeflateArgs {
+    int n;                          // input blocks
+    const uint8_t* in;              // block k: in[in_off[k] .. + in_len[k]), host-checked: inside `in`, at most DFL_MAX_IN bytes
+    const i64* in_off; const int* in_len;
+    uint8_t* slots;                 // block k's BGZF block: slots[k * DFL_SLOT ..)
+    uint32_t* tok;                  // DFL_MAX_IN words per wavefront of the grid
+    int* size;                      // per block: the size of its BGZF block
+};
+
+constexpr int DFL_WAVES = 2;        // wavefronts per workgroup: 2 * sizeof(DflWork) + 1 KiB = 45 KiB of LDS, three workgroups on a CU
+
+// One wavefront per input block, a grid-stride loop over the blocks.  No workgroup barrier behind the first.
+__global__ __launch_bounds__(64 * DFL_WAVES) void k_bgzf_deflate(DeflateArgs A)
+{
+    __shared__ DflWork work[DFL_WAVES];
+    __shared__ uint32_t crc_table[256];
+    for (int i = threadIdx.x; i < 256; i += 64 * DFL_WAVES) crc_table[i] = inf_crc_entry((uint32_t)i);
+    __syncthreads();
+    const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const DflWave L;
+    uint32_t* tok = A.tok + ((i64)blockIdx.x * DFL_WAVES + w) * DFL_MAX_IN;
+    for (i64 k = (i64)blockIdx.x * DFL_WAVES + w; k < A.n; k += (i64)gridDim.x * DFL_WAVES) {
+        const int size = dfl_block(L, work[w], A.in + A.in_off[k], A.in_len[k], tok, A.slots + k * DFL_SLOT, crc_table, nullptr);
+        if (L.lane() == 0) A.size[k] = size;
+    }
+}
+
+// one workgroup: the sizes -> where each block starts in the file image (dst_off, and n entries of slot offsets for k_frame_gather);
+// total[0] = the image's size.  Thread t sums a run of ceil(n / 256) blocks, thread 0 scans the 256 sums.
+__global__ __launch_bounds__(256) void k_deflate_offsets(const int* size, i64 n, i64* src_off, i64* dst_off, i64* total)
+{
+    __shared__ i64 part[256];
+    const i64 per = (n + 255) / 256, b = (i64)threadIdx.x * per, e = b + per < n ? b + per : n;
+    i64 s = 0;
+    for (i64 k = b; k < e; k++) s += size[k];
+    part[threadIdx.x] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        i64 run = 0;
+        for (int t = 0; t < 256; t++) { const i64 v = part[t]; part[t] = run; run += v; }
+        total[0] = run;
+    }
+    __syncthreads();
+    s = part[threadIdx.x];
+    for (i64 k = b; k < e; k++) { src_off[k] = k * DFL_SLOT; dst_off[k] = s; s += size[k]; }
 }
 
 }  // namespace csv

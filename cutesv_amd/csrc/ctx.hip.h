@@ -158,6 +158,15 @@ struct InflateState {
     void own(std::vector<Buf*>& v) { v.insert(v.end(), {&comp, &tab, &out, &status}); }
 };
 
+// BGZF deflate (stage_deflate.hip.h): the input bytes, the block table, one 65536-byte slot per block, the token
+// scratch of the grid's wavefronts, the sizes, the offsets and the packed file image of ONE csv_bgzf_deflate call.  Stand-alone and
+// grow-only; dead when the call returns; no other stage reads or writes them.
+struct DeflateState {
+    Buf in, tab, slots, tok, size, offs, image;
+    std::vector<char> tab_h;
+    void own(std::vector<Buf*>& v) { v.insert(v.end(), {&in, &tab, &slots, &tok, &size, &offs, &image}); }
+};
+
 // Record framing on the device (stage_frame.hip.h), all stand-alone and grow-only.  win: the two window
 // buffers of the reader - win[cur] holds the inflated window [0, win_n), the other one receives the next window, whose kept tail is
 // copied over from win[cur] (two buffers: no copy overlaps).  tab (block tables, guesses, exits, counts, the scan's work space, the
@@ -339,7 +348,7 @@ struct csv_ctx {
     BatchState bt; ReadsOrderState ro; ResultState res; TableState tab;
     // ---- the extraction-side stages (their lifetime rules: at the structs)
     PoolState pool; NameState nm; BamState bm; SaState sa; SeqState seq; VcfStrState vs; AlnState al; ReadsTabState rt;
-    RebuildState rb; CigarState cg; SplitState sp; InflateState inf; FrameState fr; IndexBuildState ixb;
+    RebuildState rb; CigarState cg; SplitState sp; InflateState inf; FrameState fr; IndexBuildState ixb; DeflateState dfl;
 };
 
 namespace {

@@ -1013,6 +1013,31 @@ int csv_bam_set_inflate(csv_bam* bam, csv_ctx* ctx, int32_t window_blocks);
 /* since the start of the last csv_bam_read: blocks the device inflated, blocks the host inflated again, device time of the kernels */
 int csv_bam_inflate_stats(const csv_bam* bam, int64_t* device_blocks, int64_t* fallback_blocks, double* ms_kernels);
 
+/* BGZF deflate on the device: n_blocks pieces of at most 65280 bytes -> complete BGZF blocks, packed back to
+ * back into a file image, one wavefront per block (deflate_core.h).  Block k's input is in[in_off[k] .. + in_len[k]); in, out and
+ * block_bytes are host memory.  block_bytes[k]: the size of block k's BGZF block (header, raw-DEFLATE payload, CRC32, ISIZE; at most
+ * in_len[k] + 31: per block the smallest of the stored, the fixed and the dynamic coding is written); *out_bytes: their sum.  When that
+ * sum is at most out_cap the image is in out[0 .. *out_bytes); when it is larger the call still returns CSV_OK, *out_bytes tells the
+ * need and no byte of `out` is written.  The bytes are a pure function of each input block: csv_bgzf_deflate_host, the core's host form,
+ * gives the same bytes; they need not be zlib's, but zlib inflates them to the input.  No end-of-file block is appended.
+ * CSV_E_INVALID, nothing launched: a null pointer, a negative count, in_len[k] > 65280, an input range outside `in`, flags != 0 (none
+ * is defined).  *ms_kernels (may be NULL): device time of the kernels.  The entry uses device buffers of its own and leaves
+ * everything else the context holds as it is. */
+int csv_bgzf_deflate(csv_ctx* ctx, const uint8_t* in, int64_t in_bytes, int32_t n_blocks, const int64_t* in_off, const int32_t* in_len,
+                     uint8_t* out, int64_t out_cap, int32_t* block_bytes, int64_t* out_bytes, int32_t flags, double* ms_kernels);
+/* the same on the host, one thread, no context.  coding_bytes (may be NULL): 3 per block - the payload bytes of the stored, the fixed
+ * and the dynamic coding of the block's tokens, of which the smallest was written */
+int csv_bgzf_deflate_host(const uint8_t* in, int64_t in_bytes, int32_t n_blocks, const int64_t* in_off, const int32_t* in_len,
+                          uint8_t* out, int64_t out_cap, int32_t* block_bytes, int64_t* out_bytes, int32_t* coding_bytes);
+/* The tabix index of VCF text that was compressed in the BGZF blocks {uoff, coff, isize} (n_blocks >= 1 rows, the end-of-file block
+ * included): the bytes of the .tbi BEFORE its own BGZF compression.  Lines that start with '#' are skipped; the names are the distinct
+ * CHROM values in order of first appearance; a line's interval is [POS - 1, END) with END the value of INFO's END= key when that is
+ * greater than POS - 1, else POS - 1 + len(REF); bins, 16 kb windows and virtual offsets as in the BAM index.  *out_bytes: the size;
+ * nothing is written when it exceeds out_cap.  CSV_E_INVALID with a text in err: a line out of coordinate order, a contig that
+ * reappears, a position at or beyond 2^29, a line without a numeric POS - named by the ordinal of the data line, from 0. */
+int csv_tbx_build(const char* text, int64_t text_bytes, int64_t n_blocks, const int64_t* uoff, const int64_t* coff, const uint32_t* isize,
+                  uint8_t* out, int64_t out_cap, int64_t* out_bytes, char* err, int32_t err_cap);
+
 /* Record framing on the device, opt-in.  ctx != NULL: it must be the context of the reader's device inflate
  * route (csv_bam_set_inflate with the same ctx before; CSV_E_STATE otherwise).  From then on the inflated window stays in device
  * memory: the records are found there (frame_core.h: one wavefront per BGZF block guesses a record start and chases the chain
