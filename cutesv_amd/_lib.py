@@ -123,6 +123,23 @@ SYMBOLS = [
     ("csv_bam_split_inputs", C.c_int, [C.c_void_p, C.POINTER(_abi.SaIn), C.POINTER(_abi.SaOut)]),
     ("csv_sa_struct_size", C.c_int, [C.c_int]),
     ("csv_fasta_index", C.c_int64, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("csv_fasta_index_stream_open", C.c_void_p, []),
+    ("csv_fasta_index_stream_feed", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
+    ("csv_fasta_index_stream_finish", C.c_int64, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                  C.c_void_p]),
+    ("csv_fasta_index_stream_close", None, [C.c_void_p]),
+    ("csv_fasta_index_stream_carry", C.c_int, [C.c_void_p, C.c_void_p]),
+    ("csv_fasta_index_stream_rows", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]),
+    ("csv_vcf_ref_ranges", C.c_int, [C.POINTER(_abi.VcfIn), C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("csv_vcf_emit_ref", C.c_int, [C.POINTER(_abi.VcfIn), C.c_void_p, C.c_void_p, C.c_char_p, C.c_int64, C.POINTER(C.c_int64), C.c_void_p]),
+    ("csv_ref_gather", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(C.c_int64), C.c_void_p, C.c_int32, C.c_void_p]),
+    ("csv_ref_gather_host", C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(C.c_int64), C.c_char_p, C.c_int32]),
+    ("csv_fai_events", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
+                                 C.POINTER(C.c_int64), C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.c_void_p, C.c_void_p]),
+    ("csv_fai_events_host", C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.c_void_p, C.c_void_p, C.c_int64,
+                                      C.POINTER(C.c_int64)]),
 ]
 
 

@@ -176,11 +176,11 @@ class _Shim:
 
 def call_bam(bam, reference, params, ctx=None, chroms=None, batch=10_000_000, report_readid=False, ignore_sequence=False, threads=None, svid=None,
              as_bytes=False, timings=None, tra_gt=None, include_bed=None, gates=None, reads_table=None, sigs_dir=None, inflate=None, index=None, task_cut=None,
-             cut_threads=16, read_stats=None, frame=None, index_format="bai"):
+             cut_threads=16, read_stats=None, frame=None, index_format="bai", ref_route=None):
     """-> (VCF body text, svid counters [INS, DEL, BND, DUP, INV]).
 
     bam        a path or an open bam.BamFile (coordinate-sorted; no index is needed, one beside the file is used - see `index`)
-    reference  a fasta.Reference or {contig: sequence}: the REF bases
+    reference  a fasta.Reference, a fasta.BgzfReference (fasta.open_reference gives either) or {contig: sequence}: the REF bases
     params     a CallParams, or a columns.Params (the gates then take the reference's defaults)
     ctx        an engine.Context (default: one on device 0 for the call); its pool, name pool and sequence pool are reset
     chroms     the contigs to call on (default: all of the header); TRA mates may lie on any contig of the header
@@ -222,10 +222,15 @@ def call_bam(bam, reference, params, ctx=None, chroms=None, batch=10_000_000, re
     task_cut   None or "uniform": cut_tasks, every contig by `batch`.  "index": cut_tasks_index, the reference's cut from the index
                statistics with `cut_threads` as its -t - under include_bed the cut decides which reads survive, and this is the cut
                cuteSV makes.  ValueError without an index.
+    ref_route  "host" or "device": where the REF bases of a fasta.BgzfReference are gathered (None: the reference's own route, else
+               fasta.DEFAULT_REF_ROUTE).  device: on `ctx`.  Same text either way; no other kind of reference
+               looks at it.
     read_stats a dict that receives what the tasks' reads cost: compressed_bytes and n_records summed over the tasks, task_records - the
                records each task read, in task order."""
     if index_format not in ("bai", "csi"):
         raise ValueError("index_format must be 'bai' or 'csi', not %r" % (index_format,))
+    if ref_route not in (None, "host", "device"):
+        raise ValueError("ref_route must be 'host' or 'device', not %r" % (ref_route,))
     if task_cut not in (None, "uniform", "index"):
         raise ValueError("task_cut must be None, 'uniform' or 'index', not %r" % (task_cut,))
     if task_cut == "index" and not (getattr(bam, "has_index", False) if hasattr(bam, "references") else index is not False):
@@ -361,7 +366,7 @@ def call_bam(bam, reference, params, ctx=None, chroms=None, batch=10_000_000, re
             rnames = rebuild.support_join(ctx, t["support_off"], t["support_sig"])
         lap("ms_support_join")
         out = vcf.emit_records(_Shim(names), segs, res, reference, min_size=p.min_size, max_size=p.max_size, genotype=p.genotype, report_readid=report_readid,
-                               ignore_sequence=ignore_sequence, svid=svid, as_bytes=as_bytes, ins_alt=ins_alt, rnames=rnames)
+                               ignore_sequence=ignore_sequence, svid=svid, as_bytes=as_bytes, ins_alt=ins_alt, rnames=rnames, ref_ctx=ctx, ref_route=ref_route)
         lap("ms_emit")
         return out
     finally:
@@ -380,7 +385,7 @@ def main(argv=None):
     from . import fasta
     ap = argparse.ArgumentParser(prog="python -m cutesv_amd.call", description="SV calls of a BAM file as VCF records (the body; no header)")
     ap.add_argument("bam")
-    ap.add_argument("reference", help="reference FASTA (an .fai beside it is used, or built in memory)")
+    ap.add_argument("reference", help="reference FASTA, plain or BGZF-compressed (an .fai - and a .gzi - beside it is used, or built in memory)")
     ap.add_argument("-o", "--out", required=True)
     ap.add_argument("--preset", default="clr", choices=["ont", "hifi", "clr"], help="cluster bias / merging ratio of INS and DEL as the README of cuteSV suggests")
     ap.add_argument("--genotype", action="store_true")
@@ -406,6 +411,8 @@ def main(argv=None):
                     help="with --genotype: how BND records are genotyped (default: CUTESV_AMD_TRA_GT, else alignments - every alignment counts, as in cuteSV)")
     ap.add_argument("--inflate", default=None, choices=["host", "device"], help="where the BAM's BGZF blocks are inflated (default: %s)" % DEFAULT_INFLATE)
     ap.add_argument("--frame", default=None, choices=["host", "device"], help="where the BAM's records are framed (default: %s; device takes the device inflate)" % DEFAULT_FRAME)
+    ap.add_argument("--ref_route", default=None, choices=["host", "device"],
+                    help="where the REF bases of a BGZF-compressed reference are gathered (default: %s)" % fasta.DEFAULT_REF_ROUTE)
     ap.add_argument("--sigs_dir", default=None, metavar="DIR", help="also write the rebuilt signatures there as cuteSV's --write_old_sigs files (DEL.sigs .. TRA.sigs)")
     a = ap.parse_args(argv)
     tra_gt = a.tra_gt
@@ -414,9 +421,9 @@ def main(argv=None):
     p = getattr(Params, a.preset)(min_support=a.min_support, min_size=a.min_size, max_size=a.max_size, genotype=a.genotype)
     cp = CallParams(p, min_mapq=a.min_mapq, max_split_parts=a.max_split_parts, min_read_len=a.min_read_len, min_siglength=a.min_siglength,
                     merge_del_threshold=a.merge_del_threshold, merge_ins_threshold=a.merge_ins_threshold)
-    text, svid = call_bam(a.bam, fasta.Reference(a.reference), cp, chroms=a.chroms.split(",") if a.chroms else None, batch=a.batch,
+    text, svid = call_bam(a.bam, fasta.open_reference(a.reference, threads=a.threads), cp, chroms=a.chroms.split(",") if a.chroms else None, batch=a.batch,
                           report_readid=a.report_readid, ignore_sequence=a.ignore_sequence, threads=a.threads, as_bytes=True, tra_gt=tra_gt,
-                          include_bed=a.include_bed, reads_table=a.reads_table, sigs_dir=a.sigs_dir, inflate=a.inflate, frame=a.frame)
+                          include_bed=a.include_bed, reads_table=a.reads_table, sigs_dir=a.sigs_dir, inflate=a.inflate, frame=a.frame, ref_route=a.ref_route)
     with open(a.out, "wb") as f:
         f.write(text)
     print("%d records: INS %d, DEL %d, BND %d, DUP %d, INV %d" % (text.count(b"\n"), *svid.tolist()))

@@ -2,6 +2,7 @@
 
     python -m cutesv_amd BAM REF OUT.vcf WORK_DIR [cuteSV's flags] [--reads_table {host,device}] [--tra_gt MODE] [--inflate {host,device}] [--frame {host,device}]
                          [--task_cut {index,uniform}] [--build_index] [--index_format {bai,csi}] [--bgzf {host,device}]
+                         [--ref_route {host,device}]
 
 `parse_args` accepts every option of cuteSV v2.1.4 under the same short and long spellings, with the same destination, type
 and default, so a command line written for cuteSV runs here unchanged; `main` maps them onto call.call_bam and writes a complete
@@ -99,7 +100,7 @@ def _parser():
 
 
 def _own_parser():
-    """the eight options cuteSV does not have; parsed apart (split_own), so that they shadow no abbreviation of a cuteSV flag"""
+    """the nine options cuteSV does not have; parsed apart (split_own), so that they shadow no abbreviation of a cuteSV flag"""
     from . import call
     ap = argparse.ArgumentParser(add_help=False, allow_abbrev=False)
     ap.add_argument("--reads_table", default=None, choices=["host", "device"])
@@ -110,11 +111,12 @@ def _own_parser():
     ap.add_argument("--build_index", action="store_true")
     ap.add_argument("--index_format", default="bai", choices=["bai", "csi"])
     ap.add_argument("--bgzf", default=None, choices=["host", "device"])
+    ap.add_argument("--ref_route", default=None, choices=["host", "device"])
     return ap
 
 
 def split_own(argv):
-    """-> (namespace of --reads_table / --tra_gt / --inflate / --frame / --task_cut / --build_index / --index_format / --bgzf, argv without them)"""
+    """-> (namespace of --reads_table / --tra_gt / --inflate / --frame / --task_cut / --build_index / --index_format / --bgzf / --ref_route, argv without them)"""
     return _own_parser().parse_known_args(list(argv))
 
 
@@ -193,10 +195,11 @@ def main(argv=None):
             task_cut = "index" if bf.has_index else "uniform"
             if not bf.has_index:
                 _log("no BAM index (.bai) beside %s: the tasks are the uniform cut by -b, not cuteSV's cut from the index statistics" % a.input)
-        body, svid = call.call_bam(source, fasta.Reference(a.reference), call_params(a), batch=a.batches, report_readid=a.report_readid,
+        reference = fasta.open_reference(a.reference, threads=a.threads)            # (plain text or BGZF, as pysam.FastaFile takes either)
+        body, svid = call.call_bam(source, reference, call_params(a), batch=a.batches, report_readid=a.report_readid,
                                    ignore_sequence=a.ignore_sequence, as_bytes=True, timings=timings, tra_gt=tra_gt, include_bed=a.include_bed,
                                    reads_table=own.reads_table, sigs_dir=sigs_dir, inflate=own.inflate, frame=own.frame, task_cut=task_cut, cut_threads=a.threads,
-                                   threads=a.threads, index=index, index_format=own.index_format)
+                                   threads=a.threads, index=index, index_format=own.index_format, ref_route=own.ref_route)
     finally:
         bf.close()
     for key, ms in timings.items():

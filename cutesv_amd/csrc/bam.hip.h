@@ -21,6 +21,9 @@
 // builds the slim and the host image from the records the reader selected; and last the index build (index_core.h, DESIGN.md
 // section 30): k_index_rows and k_index_runs turn the rows of a framed window into the runs and the linear index of a .bai.  Last of all the
 // way back out: k_bgzf_deflate, one wavefront per block over deflate_core.h, and k_deflate_offsets.
+// And k_ref_gather: base ranges of a BGZF-compressed FASTA cut out of the blocks k_bgzf_inflate left on the device, one wavefront per
+// output tile over ref_core.h; and k_fai_tiles / k_fai_events: the lines of such a text as the event rows its .fai
+// is assembled from.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -30,6 +33,7 @@
 #include "deflate_core.h"
 #include "frame_core.h"
 #include "index_core.h"
+#include "ref_core.h"
 
 namespace csv {
 
@@ -637,6 +641,176 @@ __global__ __launch_bounds__(256) void k_deflate_offsets(const int* size, i64 n,
     __syncthreads();
     s = part[threadIdx.x];
     for (i64 k = b; k < e; k++) { src_off[k] = k * DFL_SLOT; dst_off[k] = s; s += size[k]; }
+}
+
+// ------------------------------------------------------------------------------------ reference gather
+// The 64-lane form of ref_core.h's Lanes.
+struct RefWave {
+    __device__ __forceinline__ int lane() const { return lane_id(); }
+    __device__ __forceinline__ int width() const { return WAVE; }
+};
+
+struct RefGatherArgs {
+    RefBlocks B;                    // the touched blocks, inflated back to back in device memory (k_bgzf_inflate wrote them)
+    i64 n_ranges, n_tiles;
+    const i64* tile_first;          // n_ranges + 1: the tiles in front of a range
+    const i64* out_off;             // n_ranges + 1: where a range's bases start in `out`
+    const i64* base_off; const int* lb; const int* lw; const i64* beg;     // host-checked: every source byte lies in a block
+    uint8_t* out;
+};
+
+// One wavefront per output tile of REF_TILE bases, a grid-stride loop over the tiles: the tile's range and the block of its first
+// source byte by binary search, then base by base with the line arithmetic (ref_core.h).  No LDS, no barrier.
+__global__ __launch_bounds__(256) void k_ref_gather(RefGatherArgs A)
+{
+    const RefWave L;
+    for (i64 t = ((i64)blockIdx.x * 256 + threadIdx.x) >> 6; t < A.n_tiles; t += ((i64)gridDim.x * 256) >> 6)
+        ref_gather_tile(L, A.B, A.n_ranges, A.tile_first, A.out_off, A.base_off, A.lb, A.lw, A.beg, t, A.out);
+}
+
+// ------------------------------------------------------------------------------------ .fai event rows
+// The line breaks of a window of FASTA text that k_bgzf_inflate left on the device, as ref_core.h's event rows.  A workgroup takes a
+// tile of FAI_TILE bytes, each of its four wavefronts a quarter of it, 64 bytes a step: one ballot per step says where the line
+// breaks are, and the line break before a lane's own (and the one before that: the row rule compares a line with the line before) is
+// a bit of the same ballot or the wavefront's running pair.  What runs into a wavefront from the left - the running "previous line
+// break" - is the maximum over everything before it: k_fai_tiles leaves the last two line breaks of every tile, and a tile folds the
+// tiles before it with wave_incl_max_i64 and its own wavefronts' pairs through LDS.  Three launches over the window: k_fai_tiles,
+// k_fai_events<false> (rows per wavefront -> cnt), k_fai_events<true> (cnt summed by block_prefix_of -> where a wavefront's rows go).
+// Bounds: a byte is read at 0 <= i < n only (fai_row reads a line's first and last byte, both inside [0, e)); a row is written at
+// an index below row_cap only; cnt has 4 and top 2 entries per tile.
+constexpr int FAI_TILE = 32768, FAI_WAVE_BYTES = FAI_TILE / 4;
+
+struct FaiOut { i64 n_rows; FaiCarry tail; };
+
+struct FaiArgs {
+    const uint8_t* d; i64 n, base;  // the window: n > 0 bytes whose first has absolute offset base
+    FaiCarry c;
+    int n_tiles;
+    i64* top;                       // 2 per tile: its last line break and the one before, window-relative (FAI_NONE: none)
+    int* cnt;                       // 4 per tile: the rows of each wavefront
+    FaiRow* rows; i64 row_cap;
+    FaiOut* out;
+};
+
+// the pair (m1 > m2) after the line breaks `mask` of the 64 bytes at p0
+__device__ __forceinline__ void fai_push(u64 mask, i64 p0, i64& m1, i64& m2)
+{
+    if (!mask) return;
+    const int hi = 63 - __builtin_clzll(mask);
+    const u64 rest = mask & ~(1ull << hi);
+    m2 = rest ? p0 + (63 - __builtin_clzll(rest)) : m1;
+    m1 = p0 + hi;
+}
+
+// the last two line breaks of bytes [lo, hi) (a wavefront's share): wave-uniform
+__device__ __forceinline__ void fai_wave_top2(const uint8_t* d, i64 lo, i64 hi, i64& m1, i64& m2)
+{
+    m1 = m2 = FAI_NONE;
+    for (i64 p0 = lo; p0 < hi; p0 += WAVE) {
+        const i64 i = p0 + lane_id();
+        fai_push(__ballot(i < hi && d[i] == '\n' ? 1 : 0), p0, m1, m2);
+    }
+}
+
+// the four wavefronts' pairs in sh[2 w], sh[2 w + 1] (in order of position) on top of (m1, m2): the pair after wavefronts [0, upto)
+__device__ __forceinline__ void fai_fold(const i64* sh, int upto, i64& m1, i64& m2)
+{
+    for (int w = 0; w < upto; w++) {
+        const i64 a = sh[2 * w], b = sh[2 * w + 1];
+        if (a == FAI_NONE) continue;
+        m2 = b != FAI_NONE ? b : m1;
+        m1 = a;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_fai_tiles(FaiArgs A)
+{
+    __shared__ i64 sh[8];
+    const int w = threadIdx.x >> 6;
+    const i64 t0 = (i64)blockIdx.x * FAI_TILE, lo = t0 + (i64)w * FAI_WAVE_BYTES, hi = lo + FAI_WAVE_BYTES < A.n ? lo + FAI_WAVE_BYTES : A.n;
+    i64 m1, m2;
+    fai_wave_top2(A.d, lo, hi, m1, m2);
+    if (lane_id() == 0) { sh[2 * w] = m1; sh[2 * w + 1] = m2; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        i64 a = FAI_NONE, b = FAI_NONE;
+        fai_fold(sh, 4, a, b);
+        A.top[2 * (i64)blockIdx.x] = a; A.top[2 * (i64)blockIdx.x + 1] = b;
+    }
+}
+
+// the maximum of v over the workgroup; every thread gets it (sh: 4 values)
+__device__ __forceinline__ i64 fai_block_max(i64 v, i64* sh)
+{
+    v = lane63_i64(wave_incl_max_i64(v));
+    if (lane_id() == 0) sh[threadIdx.x >> 6] = v;
+    __syncthreads();
+    i64 m = sh[0];
+    for (int k = 1; k < 4; k++) m = sh[k] > m ? sh[k] : m;
+    __syncthreads();
+    return m;
+}
+
+template <bool WRITE> __global__ __launch_bounds__(256) void k_fai_events(FaiArgs A)
+{
+    __shared__ i64 sh[8], red[4];
+    const int t = blockIdx.x, w = threadIdx.x >> 6;
+    // the last two line breaks in front of this tile: the largest, then the largest below it (FAI_NONE is below every position)
+    i64 v = FAI_NONE;
+    for (int k = threadIdx.x; k < t; k += 256) { const i64 a = A.top[2 * (i64)k]; v = a > v ? a : v; }
+    const i64 in1 = fai_block_max(v, red);
+    v = FAI_NONE;
+    for (int k = threadIdx.x; k < 2 * t; k += 256) { const i64 a = A.top[k]; if (a < in1 && a > v) v = a; }
+    const i64 in2 = fai_block_max(v, red);
+    // the wavefronts' own pairs, so that each knows what runs into it
+    const i64 t0 = (i64)t * FAI_TILE, lo = t0 + (i64)w * FAI_WAVE_BYTES, hi = lo + FAI_WAVE_BYTES < A.n ? lo + FAI_WAVE_BYTES : A.n;
+    i64 m1, m2;
+    fai_wave_top2(A.d, lo, hi, m1, m2);
+    if (lane_id() == 0) { sh[2 * w] = m1; sh[2 * w + 1] = m2; }
+    __syncthreads();
+    i64 q1 = in1, q2 = in2;                                        // the running pair: wave-uniform
+    fai_fold(sh, w, q1, q2);
+    i64 at = 0;                                                    // where this wavefront's rows go
+    if (WRITE) {
+        at = block_prefix_of(A.cnt, 4 * t, red);
+        for (int k = 0; k < w; k++) at += A.cnt[4 * (i64)t + k];
+    }
+    int rows = 0;
+    for (i64 p0 = lo; p0 < hi; p0 += WAVE) {
+        const i64 e = p0 + lane_id();
+        const bool nl = e < hi && A.d[e] == '\n';
+        const u64 mask = __ballot(nl ? 1 : 0);
+        if (!mask) continue;
+        bool hit = false;
+        FaiRow r{0, 0, 0};
+        if (nl) {
+            // the line breaks before this lane's: bits of the ballot below it, then the running pair
+            const u64 below = mask & lanemask_lt();
+            i64 a = q1, b = q2;
+            fai_push(below, p0, a, b);
+            hit = fai_event(A.d, A.base, A.c, e, a, b, &r);
+        }
+        const u64 hits = __ballot(hit ? 1 : 0);
+        if (WRITE && hit) {
+            const i64 k = at + rows + __popcll(hits & lanemask_lt());
+            if (k < A.row_cap) A.rows[k] = r;
+        }
+        rows += __popcll(hits);
+        fai_push(mask, p0, q1, q2);
+    }
+    if (!WRITE && lane_id() == 0) A.cnt[4 * (i64)t + w] = rows;
+    if (WRITE && t == (int)gridDim.x - 1) {
+        // the last tile: the rows of the whole window, and the line in progress behind its last line break
+        __syncthreads();
+        if (lane_id() == 63) red[w] = at + rows;                   // (the last wavefront's is the total)
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            i64 a = in1, b = in2;
+            fai_fold(sh, 4, a, b);
+            A.out->n_rows = red[3];
+            A.out->tail = fai_tail(A.d, A.n, A.base, A.c, a);
+        }
+    }
 }
 
 }  // namespace csv

@@ -167,6 +167,17 @@ struct DeflateState {
     void own(std::vector<Buf*>& v) { v.insert(v.end(), {&in, &tab, &slots, &tok, &size, &offs, &image}); }
 };
 
+// Reference gather (stage_ref.hip.h): the inflated bytes of the touched blocks, the block and range tables and
+// the gathered bases of ONE csv_ref_gather call.  Stand-alone and grow-only; dead when the call returns; no other stage reads or
+// writes them (the inflate in front of the gather runs through InflateState's buffers, which are as dead between calls).
+struct RefState {
+    Buf data, tab, out, fai, fai_rows;      // fai: k_fai_events' tile tables and its FaiOut
+    std::vector<char> tab_h;
+    std::vector<int64_t> data_off;
+    std::vector<long long> out_off, tile_first;
+    void own(std::vector<Buf*>& v) { v.insert(v.end(), {&data, &tab, &out, &fai, &fai_rows}); }
+};
+
 // Record framing on the device (stage_frame.hip.h), all stand-alone and grow-only.  win: the two window
 // buffers of the reader - win[cur] holds the inflated window [0, win_n), the other one receives the next window, whose kept tail is
 // copied over from win[cur] (two buffers: no copy overlaps).  tab (block tables, guesses, exits, counts, the scan's work space, the
@@ -348,7 +359,7 @@ struct csv_ctx {
     BatchState bt; ReadsOrderState ro; ResultState res; TableState tab;
     // ---- the extraction-side stages (their lifetime rules: at the structs)
     PoolState pool; NameState nm; BamState bm; SaState sa; SeqState seq; VcfStrState vs; AlnState al; ReadsTabState rt;
-    RebuildState rb; CigarState cg; SplitState sp; InflateState inf; FrameState fr; IndexBuildState ixb; DeflateState dfl;
+    RebuildState rb; CigarState cg; SplitState sp; InflateState inf; FrameState fr; IndexBuildState ixb; DeflateState dfl; RefState ref;
 };
 
 namespace {

@@ -19,6 +19,7 @@
 
 #include "../../include/cutesv_hip.h"
 #include "soa_access.h"
+#include "ref_core.h"
 
 namespace {
 
@@ -105,7 +106,44 @@ inline int emitted_id(const csv_vcf_in* in, const csv_batch_out& R, int64_t c)
     return ID_BND;
 }
 
-int emit_slice(const csv_vcf_in* in, const int64_t* v, int64_t nv, int ch, int64_t* svid, Sink& o);
+// where the reference bases of the records come from: the contigs of csv_vcf_in (blob == NULL), or - csv_vcf_emit_ref - per call
+// the bases of its range, back to back: call c's are blob[off[c] .. off[c + 1])
+struct RefSrc { const char* blob; const int64_t* off; };
+
+// The contig bases the record of call c reads: [b, e), of which a DEL record prints [b, slice_e) as its REF.  ONE definition, for
+// emit_slice and for csv_vcf_ref_ranges (generate_output: INS :297, DEL :299-300, DUP :334, INV :360-365, BND :431-434).  Empty
+// (b == e): a call the size filters drop, or INS / DEL under ignore_sequence.  slen: the contig's length, 0 for a contig without
+// sequence; a range that is not inside [0, slen) is the caller's to judge ('N' for BND, CSV_E_INVALID otherwise).
+struct RefRange { int64_t b, e, slice_e; bool bnd; };
+inline RefRange call_ref_range(const csv_vcf_in* in, const csv_batch_out& R, int64_t c, int64_t slen)
+{
+    RefRange r{0, 0, 0, false};
+    if (emitted_id(in, R, c) < 0) return r;
+    const int type = in->seg[R.call_seg[c]].svtype;
+    const long long pos = csv_soa::bp1(R, c), prev = pos - 1 > 0 ? pos - 1 : 0;
+    if (type == CSV_DEL || type == CSV_INS) {
+        if (in->ignore_sequence) return r;
+        r.b = prev; r.e = r.slice_e = prev + 1;                                        // ref_chrom[max(pos-1, 0)] (:297)
+        if (type == CSV_DEL) {
+            long long r1 = pos + csv_soa::bp2(R, c);                                    // slice end, clamped like Python
+            if (r1 > slen) r1 = slen;
+            r.slice_e = r1 > prev ? r1 : prev;
+            if (r1 > r.e) r.e = r1;
+        }
+    } else if (type == CSV_DUP) {
+        r.b = pos; r.e = pos + 1;                                                       // ref_chrom[int(i[2])] (:334)
+    } else if (type == CSV_INV) {
+        const bool pp = strcmp(in->strand_name[csv_soa::call_aux(R, c)], "++") == 0;    // :360-365
+        r.b = pp ? prev : pos; r.e = r.b + 1;
+    } else {
+        const bool nfirst = (csv_soa::call_aux(R, c) & 7) < 2;                          // ALT starts with 'N' (types A/B)
+        r.b = nfirst ? prev : pos; r.e = r.b + 1; r.bnd = true;
+    }
+    return r;
+}
+inline bool ref_range_inside(const RefRange& r, int64_t slen) { return r.b >= 0 && r.e <= slen; }
+
+int emit_slice(const csv_vcf_in* in, const RefSrc& src, const int64_t* v, int64_t nv, int ch, int64_t* svid, Sink& o);
 
 // A team of worker threads that lives as long as the process (thread creation is ~30 us: 15 fresh threads per call were a third
 // of a 1.4 ms emission).  Between calls the workers sleep on a condition variable; inside a call (wake() .. park()) they spin
@@ -184,7 +222,8 @@ struct TeamLease {
 };
 }  // namespace
 
-extern "C" int csv_vcf_emit(const csv_vcf_in* in, char* out, int64_t cap, int64_t* n_written, int64_t* svid)
+namespace {
+int vcf_emit_impl(const csv_vcf_in* in, const RefSrc& src, char* out, int64_t cap, int64_t* n_written, int64_t* svid)
 {
     if (!in || !in->res || !n_written || !svid) return CSV_E_INVALID;
     const csv_batch_out& R = *in->res;
@@ -244,7 +283,7 @@ extern "C" int csv_vcf_emit(const csv_vcf_in* in, char* out, int64_t cap, int64_
         Sink o{tl_buf};
         x.buf = &tl_buf; x.off = tl_buf.size();
         int64_t sv[5] = {x.start[0], x.start[1], x.start[2], x.start[3], x.start[4]};
-        x.rc = emit_slice(in, idx.data() + x.lo, x.hi - x.lo, x.ch, sv, o);
+        x.rc = emit_slice(in, src, idx.data() + x.lo, x.hi - x.lo, x.ch, sv, o);
         x.len = tl_buf.size() - x.off;
     });
     int64_t total = 0;
@@ -257,22 +296,58 @@ extern "C" int csv_vcf_emit(const csv_vcf_in* in, char* out, int64_t cap, int64_
     for (int t = 0; t < 5; t++) svid[t] = run[t];
     return CSV_OK;
 }
+}  // namespace
+
+extern "C" int csv_vcf_emit(const csv_vcf_in* in, char* out, int64_t cap, int64_t* n_written, int64_t* svid)
+{
+    return vcf_emit_impl(in, RefSrc{nullptr, nullptr}, out, cap, n_written, svid);
+}
+
+// csv_vcf_emit with the reference bases of call c taken from ref_blob[ref_off[c] .. ref_off[c + 1]): the bases of the range
+// csv_vcf_ref_ranges gives for it (a BND call without a readable base, and every call without a range: no bytes)
+extern "C" int csv_vcf_emit_ref(const csv_vcf_in* in, const char* ref_blob, const int64_t* ref_off, char* out, int64_t cap, int64_t* n_written, int64_t* svid)
+{
+    static const char kNone = 0;
+    if (!ref_off) return CSV_E_INVALID;
+    return vcf_emit_impl(in, RefSrc{ref_blob ? ref_blob : &kNone, ref_off}, out, cap, n_written, svid);
+}
+
+// per call the contig (index into chrom_name) and the bases [beg, end) of it that the call's record reads (call_ref_range)
+extern "C" int csv_vcf_ref_ranges(const csv_vcf_in* in, int64_t* beg, int64_t* end, int32_t* chrom)
+{
+    if (!in || !in->res) return CSV_E_INVALID;
+    const csv_batch_out& R = *in->res;
+    if (R.n_calls > 0 && (!beg || !end || !chrom)) return CSV_E_INVALID;
+    for (int64_t c = 0; c < R.n_calls; c++) {
+        const int k = R.call_seg[c];
+        if (k < 0 || k >= in->n_seg) return CSV_E_INVALID;
+        const int ch = in->seg[k].chrom;
+        if (ch < 0 || ch >= in->n_chrom) return CSV_E_INVALID;
+        const int64_t slen = in->chrom_len ? in->chrom_len[ch] : 0;
+        RefRange r = call_ref_range(in, R, c, slen);
+        if (r.e > r.b && !ref_range_inside(r, slen)) {
+            if (!r.bnd) return CSV_E_INVALID;                                            // what csv_vcf_emit answers for it
+            r.b = r.e = 0;                                                              // try/except -> 'N' (:431-434)
+        }
+        beg[c] = r.b; end[c] = r.e; chrom[c] = ch;
+    }
+    return CSV_OK;
+}
 
 namespace {
 // the records of the calls v[0 .. nv) of chromosome ch, in that order; svid: the counters to start with
-int emit_slice(const csv_vcf_in* in, const int64_t* v, int64_t nv, int ch, int64_t* svid, Sink& o)
+int emit_slice(const csv_vcf_in* in, const RefSrc& src, const int64_t* v, int64_t nv, int ch, int64_t* svid, Sink& o)
 {
     const csv_batch_out& R = *in->res;
     static const char* kFormat = "GT:DR:DV:PL:GQ";
     {
-        const char* seq = in->chrom_seq ? in->chrom_seq[ch] : nullptr;
-        const int64_t slen = in->chrom_len ? in->chrom_len[ch] : 0;
+        const char* seq = (!src.blob && in->chrom_seq) ? in->chrom_seq[ch] : nullptr;
+        const int64_t clen = in->chrom_len ? in->chrom_len[ch] : 0;
+        const int64_t slen = (src.blob || seq) ? clen : 0;                              // (a contig without sequence has no base to read)
         const char* cname = in->chrom_name[ch];
         // a contig read straight from a FASTA file (mmap): line_bases bases, then the line break, per line of line_width bytes
         const int64_t lb = (in->chrom_line_bases && in->chrom_line_width) ? in->chrom_line_bases[ch] : 0;
         const int64_t lw = lb > 0 ? in->chrom_line_width[ch] : 0;
-        auto at = [&](int64_t i) -> char { return lb > 0 ? seq[(i / lb) * lw + i % lb] : seq[i]; };
-        auto base = [&](int64_t i, char& c) -> bool { if (!seq || i < 0 || i >= slen) return false; c = at(i); return true; };
         for (int64_t qi = 0; qi < nv; qi++) {
             const int64_t c = v[qi];
             const csv_segment& sg = in->seg[R.call_seg[c]];
@@ -291,6 +366,16 @@ int emit_slice(const csv_vcf_in* in, const int64_t* v, int64_t nv, int ch, int64
             const char* filt = "PASS";
             if (!(g.qual_n == 1 && g.qual[0] == '.')) filt = strtod(std::string(g.qual, g.qual_n).c_str(), nullptr) >= 5.0 ? "PASS" : "q5";
             const long long pos = csv_soa::bp1(R, c), re = R.support[c];
+            if (emitted_id(in, R, c) < 0) continue;                                     // the size filters (:265-268, 315-316, 351-352)
+            const RefRange rr = call_ref_range(in, R, c, slen);
+            const bool readable = rr.e > rr.b && ref_range_inside(rr, slen);
+            if (rr.e > rr.b && !readable && !rr.bnd) return CSV_E_INVALID;               // a reference sequence is missing or too short
+            const char* mine = nullptr;                                                 // csv_vcf_emit_ref: the bases of [rr.b, rr.e)
+            if (src.blob) {
+                if (src.off[c + 1] - src.off[c] != (readable ? rr.e - rr.b : 0)) return CSV_E_INVALID;
+                mine = src.blob + src.off[c];
+            }
+            auto at = [&](int64_t i) -> char { return mine ? mine[i - rr.b] : lb > 0 ? seq[(i / lb) * lw + i % lb] : seq[i]; };
             auto put_rnames = [&]() {
                 if (in->report_readid) { o.put(";RNAMES="); if (in->rnames) o.put(in->rnames + in->rnames_off[c], (size_t)(in->rnames_off[c + 1] - in->rnames_off[c])); }
             };
@@ -307,30 +392,26 @@ int emit_slice(const csv_vcf_in* in, const int64_t* v, int64_t nv, int ch, int64
             };
             if (type == CSV_DEL || type == CSV_INS) {
                 const long long len = csv_soa::bp2(R, c);                                         // |SVLEN|
-                if (len > in->max_size && in->max_size != -1) continue;                   // :265-266
-                if (len < in->min_size) continue;                                       // :267-268
                 const long long end = type == CSV_INS ? pos : pos + len;
-                const long long r0 = pos - 1 > 0 ? pos - 1 : 0;
+                const long long r0 = rr.b;
                 o.put(cname); o.put('\t'); o.num(pos); o.put('\t');
                 o.put(type == CSV_INS ? "cuteSV.INS." : "cuteSV.DEL."); o.num(svid[type == CSV_INS ? ID_INS : ID_DEL]++); o.put('\t');
                 if (in->ignore_sequence) {
                     o.put("N\t"); o.put(type == CSV_INS ? "<INS>" : "<DEL>");
                 } else if (type == CSV_INS) {
-                    char b0;
-                    if (!base(r0, b0)) return CSV_E_INVALID;                             // ref_chrom[max(pos-1, 0)] (:297)
+                    const char b0 = at(r0);                                             // ref_chrom[max(pos-1, 0)] (:297)
                     o.put(iupac(b0)); o.put('\t'); o.put(b0);
                     if (in->ins_alt) o.put(in->ins_alt + in->ins_alt_off[c], (size_t)(in->ins_alt_off[c + 1] - in->ins_alt_off[c]));
                 } else {
-                    long long r1 = pos + len;                                           // slice end, clamped like Python
-                    if (r1 > slen) r1 = slen;
-                    if (!seq && r1 > r0) return CSV_E_INVALID;
+                    const long long r1 = rr.slice_e;                                    // slice end, clamped like Python
                     // the deleted bases: whole runs of a FASTA line at a time (memcpy), then the IUPAC table over the copy
                     // (a call, a division and a push_back per base made this slice 95 % of the emitter's time on a 30x genome)
                     if (r1 > r0) {
                         const size_t w0 = o.buf.size();
                         o.buf.resize(w0 + (size_t)(r1 - r0));
                         char* dst = &o.buf[w0];
-                        if (lb > 0) {
+                        if (mine) memcpy(dst, mine, (size_t)(r1 - r0));
+                        else if (lb > 0) {
                             long long i = r0;
                             while (i < r1) {
                                 const long long in_line = i % lb, run = std::min<long long>(lb - in_line, r1 - i);
@@ -342,9 +423,7 @@ int emit_slice(const csv_vcf_in* in, const int64_t* v, int64_t nv, int ch, int64
                         for (long long k = 0; k < r1 - r0; k++) p[k] = kIupac.t[(unsigned char)p[k]];
                     }
                     o.put('\t');
-                    char b0;
-                    if (!base(r0, b0)) return CSV_E_INVALID;
-                    o.put(b0);
+                    o.put(at(r0));
                 }
                 o.put('\t'); o.put(g.qual, g.qual_n); o.put('\t'); o.put(filt); o.put('\t');
                 o.put(imprecise ? "IMPRECISE" : "PRECISE");
@@ -360,9 +439,7 @@ int emit_slice(const csv_vcf_in* in, const int64_t* v, int64_t nv, int ch, int64
                 put_tail();
             } else if (type == CSV_DUP) {
                 const long long len = csv_soa::bp2(R, c) - csv_soa::bp1(R, c);
-                if (llabs(len) > in->max_size && in->max_size != -1) continue;            // :315-316
-                char b0;
-                if (!base(pos, b0)) return CSV_E_INVALID;                                // ref_chrom[int(i[2])] (:334)
+                const char b0 = at(rr.b);                                               // ref_chrom[int(i[2])] (:334)
                 o.put(cname); o.put('\t'); o.num(pos + 1); o.put('\t');
                 o.put("cuteSV.DUP."); o.num(svid[ID_DUP]++); o.put('\t');
                 o.put(iupac(b0)); o.put("\t<DUP>\t");
@@ -376,13 +453,10 @@ int emit_slice(const csv_vcf_in* in, const int64_t* v, int64_t nv, int ch, int64
                 put_tail();
             } else if (type == CSV_INV) {
                 const long long len = csv_soa::bp2(R, c) - csv_soa::bp1(R, c);
-                if (llabs(len) > in->max_size && in->max_size != -1) continue;            // :351-352
                 const char* strand = in->strand_name[csv_soa::call_aux(R, c)];
                 const bool pp = strcmp(strand, "++") == 0;                              // :360-365
                 const long long pinv = pp ? pos : pos + 1;
-                const long long ridx = pp ? (pos - 1 > 0 ? pos - 1 : 0) : pos;
-                char b0;
-                if (!base(ridx, b0)) return CSV_E_INVALID;
+                const char b0 = at(rr.b);
                 o.put(cname); o.put('\t'); o.num(pinv); o.put('\t');
                 o.put("cuteSV.INV."); o.num(svid[ID_INV]++); o.put('\t');
                 o.put(iupac(b0)); o.put("\t<INV>\t");
@@ -400,9 +474,7 @@ int emit_slice(const csv_vcf_in* in, const int64_t* v, int64_t nv, int ch, int64
                 const long long mate = csv_soa::bp2(R, c) + ((code == 0 || code == 2) ? 1 : 0);    // TRA:140
                 const bool nfirst = code < 2;                                           // ALT starts with 'N' (types A/B)
                 const long long pbnd = nfirst ? pos : pos + 1;
-                char b0 = 'N';
-                if (nfirst) { char t; if (base(pos - 1 > 0 ? pos - 1 : 0, t)) b0 = t; }  // try/except -> 'N' (:431-434)
-                else { char t; if (base(pos, t)) b0 = t; }
+                const char b0 = readable ? at(rr.b) : 'N';                              // try/except -> 'N' (:431-434)
                 o.put(cname); o.put('\t'); o.num(pbnd); o.put('\t');
                 o.put("cuteSV.BND."); o.num(svid[ID_BND]++); o.put('\t');
                 o.put(iupac(b0)); o.put('\t');
@@ -476,6 +548,64 @@ extern "C" int64_t csv_fasta_index(const char* data, int64_t size, int64_t max_c
         }
         n++;
         p = q;
+    }
+    return n;
+}
+
+// ---------------------------------------------------------------------------------------- FASTA index, window after window
+// csv_fasta_index for a text that is never in memory whole (a BGZF-compressed FASTA inflated window by window):
+// for every cut of the text into windows, the entries and the verdict csv_fasta_index gives over the whole text.  The rules above are
+// rules about whole lines - a line's first byte, its bytes, its last byte, whether a line break ends it - so the state between two
+// windows is the line in progress (and, of a header line, its name so far).  The rules stand once more in ref_core.h's FaiStream,
+// which also takes a window as event rows; tests/test_bgzf_reference.py holds it to csv_fasta_index at every cut.
+struct csv_fai_stream : csv::FaiStream {};
+
+extern "C" csv_fai_stream* csv_fasta_index_stream_open(void) { return new csv_fai_stream(); }
+extern "C" void csv_fasta_index_stream_close(csv_fai_stream* s) { delete s; }
+
+extern "C" int csv_fasta_index_stream_feed(csv_fai_stream* s, const char* data, int64_t size)
+{
+    if (!s || size < 0 || (size > 0 && !data)) return CSV_E_INVALID;
+    return s->feed(data, size) ? CSV_OK : CSV_E_INVALID;
+}
+
+// The same window as event rows (ref_core.h: csv_fai_events' or csv_fai_events_host's): carry[3] <- what the next window's rows are
+// made with; rows: 3 int64 per row; hdr: the header texts; tail[3]: the carry behind the window.  CSV_E_INVALID: the text is refused,
+// or the rows do not describe a window behind the text fed so far.
+extern "C" int csv_fasta_index_stream_carry(const csv_fai_stream* s, int64_t* carry)
+{
+    if (!s || !carry) return CSV_E_INVALID;
+    const csv::FaiCarry c = s->carry();
+    carry[0] = c.start; carry[1] = c.first; carry[2] = c.last;
+    return CSV_OK;
+}
+
+extern "C" int csv_fasta_index_stream_rows(csv_fai_stream* s, const int64_t* rows, int64_t n_rows, const char* hdr, int64_t hdr_bytes, int64_t window_bytes, const int64_t* tail)
+{
+    if (!s || n_rows < 0 || hdr_bytes < 0 || window_bytes < 0 || !tail || (n_rows > 0 && !rows) || (hdr_bytes > 0 && !hdr)) return CSV_E_INVALID;
+    static_assert(sizeof(csv::FaiRow) == 24, "a row is three int64");
+    return s->rows((const csv::FaiRow*)rows, n_rows, hdr, hdr_bytes, window_bytes, csv::FaiCarry{tail[0], tail[1], tail[2]}) ? CSV_OK : CSV_E_INVALID;
+}
+
+// the end of the text: the last line, when no line break ended it, is judged now.  -> the number of contigs (the arrays hold the first
+// max_contigs; *names_bytes = the bytes of all names, written back to back into names when they fit names_cap; name_off addresses
+// them there), or -CSV_E_INVALID.  Call again with larger arrays when either is exceeded: finish may be repeated.
+extern "C" int64_t csv_fasta_index_stream_finish(csv_fai_stream* s, int64_t max_contigs, char* names, int64_t names_cap, int64_t* names_bytes, int64_t* name_off,
+                                                 int32_t* name_len, int64_t* length, int64_t* offset, int32_t* line_bases, int32_t* line_width)
+{
+    if (!s) return -(int64_t)CSV_E_INVALID;
+    if (!s->finish()) return -(int64_t)CSV_E_INVALID;
+    if (names_bytes) *names_bytes = (int64_t)s->names.size();
+    if (names && (int64_t)s->names.size() <= names_cap) memcpy(names, s->names.data(), s->names.size());
+    const int64_t n = (int64_t)s->ent.size();
+    for (int64_t i = 0; i < n && i < max_contigs; i++) {
+        const csv::FaiStream::Entry& e = s->ent[(size_t)i];
+        if (name_off) name_off[i] = e.name_off;
+        if (name_len) name_len[i] = e.name_len;
+        if (length) length[i] = e.length;
+        if (offset) offset[i] = e.offset;
+        if (line_bases) line_bases[i] = e.lb;
+        if (line_width) line_width[i] = e.lw;
     }
     return n;
 }

@@ -64,7 +64,7 @@ def main(argv=None, ctx=None):
             json.dump(digests(results), f, indent=0, sort_keys=True)
         return 0
     from . import fasta, vcf
-    text, _ = vcf.emit_stage(results, fasta.Reference(a.fasta), min_size=p.min_size, max_size=p.max_size, genotype=p.genotype,
+    text, _ = vcf.emit_stage(results, fasta.open_reference(a.fasta), min_size=p.min_size, max_size=p.max_size, genotype=p.genotype,
                              as_bytes=True)
     with open(a.out, "wb") as f:
         f.write(text)

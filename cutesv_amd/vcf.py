@@ -31,13 +31,17 @@ _TLS = threading.local()          # the recycled output buffer is per thread: cs
 
 
 def emit_records(store, segments, res, reference, min_size=30, max_size=100000, genotype=False, report_readid=False,
-                 ignore_sequence=False, svid=None, as_bytes=False, as_view=False, ins_alt=None, rnames=None):
+                 ignore_sequence=False, svid=None, as_bytes=False, as_view=False, ins_alt=None, rnames=None, ref_ctx=None, ref_route=None):
     """calls of one batch -> (VCF body text, svid counters).
 
     segments   the csv_segment records the batch was run with (HostBatch.segments)
     res        _abi.HostResult of that batch
-    reference  a fasta.Reference (memory-mapped FASTA + .fai: bases are read in C straight from the mapping), or
+    reference  a fasta.Reference (memory-mapped FASTA + .fai: bases are read in C straight from the mapping), a
+               fasta.BgzfReference (a BGZF-compressed FASTA: csv_vcf_ref_ranges says which bases each call's record reads,
+               reference.gather fetches them out of the blocks they touch, csv_vcf_emit_ref writes the records), or
                {chromosome name: sequence (str or bytes)}; may miss chromosomes without calls
+    ref_ctx / ref_route   the context and the route ("host", "device"; None: the reference's own) of BgzfReference.gather;
+               no other kind of reference looks at them
     svid       running counters [INS, DEL, BND, DUP, INV] (main script :1209-1213), advanced in place
     as_bytes   return the text as `bytes` (what a file is written from) instead of decoding it to `str`
     as_view    return a memoryview of this thread's output buffer instead (valid until the thread's next emit_records call):
@@ -56,9 +60,15 @@ def emit_records(store, segments, res, reference, min_size=30, max_size=100000, 
     call_type = segs["svtype"][t["call_seg"]] if n else np.zeros(0, np.int32)
     nch = len(store.chroms)
     names = (C.c_char_p * nch)(*[c.encode() for c in store.chroms])
-    from .fasta import Reference
+    from .fasta import BgzfReference, Reference
     line_bases = line_width = None
-    if isinstance(reference, Reference):
+    bgzf_ref = isinstance(reference, BgzfReference)
+    if bgzf_ref:
+        ref_idx = np.array([reference.index.get(c, -1) for c in store.chroms], np.int64)
+        seqs = (C.c_char_p * nch)()
+        clen = np.array([int(reference.length[i]) if i >= 0 else 0 for i in ref_idx], np.int64)
+        seq_bytes = reference
+    elif isinstance(reference, Reference):
         ent = [reference.contig(c) if c in reference else (0, 0, 0, 0) for c in store.chroms]
         seqs = (C.c_void_p * nch)(*[e[0] or None for e in ent])
         clen = np.array([e[1] for e in ent], np.int64)
@@ -134,14 +144,29 @@ def emit_records(store, segments, res, reference, min_size=30, max_size=100000, 
                 strand_name=strands, gl_key=keys.ctypes.data, gl_str=gl_strs, n_gl=len(keys),
                 min_size=min_size, max_size=max_size, genotype=int(bool(genotype)), report_readid=int(bool(report_readid)),
                 ignore_sequence=int(bool(ignore_sequence)))
-    cap = 256 * max(n, 1) + (len(alt_blob) if alt_blob else 0) + (len(rn_blob) if rn_blob else 0) + 4096
+    ref_blob = ref_off = None
+    if bgzf_ref:
+        beg, end, chrom = np.zeros(n, np.int64), np.zeros(n, np.int64), np.zeros(n, np.int32)
+        rc = L.csv_vcf_ref_ranges(C.byref(vin), beg.ctypes.data, end.ctypes.data, chrom.ctypes.data)
+        if rc != _abi.OK:
+            raise RuntimeError("csv_vcf_emit: %s (a reference sequence is missing or too short?)" % _abi.ERR_NAME.get(rc, rc))
+        ref_blob, ref_off = np.zeros(0, np.uint8), np.zeros(n + 1, np.int64)
+        if (end > beg).any():                              # (an empty range reads nothing of any contig: it is asked of contig 0)
+            idx = np.where(end > beg, ref_idx[chrom], 0)
+            ref_blob, ref_off = reference.gather(idx, beg, end, ctx=ref_ctx, route=ref_route)
+            ref_off = np.ascontiguousarray(ref_off, np.int64)
+    cap = 256 * max(n, 1) + (len(alt_blob) if alt_blob else 0) + (len(rn_blob) if rn_blob else 0) + (len(ref_blob) if ref_blob is not None else 0) + 4096
     for _ in range(2):
         buf = getattr(_TLS, "buf", None)
         if buf is None or len(buf) < cap:                 # (recycled: a fresh zero-filled buffer per call costs as much as the emitter)
             buf = _TLS.buf = np.empty(cap, np.uint8)
         need = C.c_int64(0)
         sv = svid.copy()
-        rc = L.csv_vcf_emit(C.byref(vin), C.cast(buf.ctypes.data, C.c_char_p), len(buf), C.byref(need), sv.ctypes.data)
+        if bgzf_ref:
+            rc = L.csv_vcf_emit_ref(C.byref(vin), ref_blob.ctypes.data if len(ref_blob) else None, ref_off.ctypes.data, C.cast(buf.ctypes.data, C.c_char_p), len(buf), C.byref(need),
+                                    sv.ctypes.data)
+        else:
+            rc = L.csv_vcf_emit(C.byref(vin), C.cast(buf.ctypes.data, C.c_char_p), len(buf), C.byref(need), sv.ctypes.data)
         if rc == _abi.E_CAPACITY:
             cap = need.value + 16
             continue

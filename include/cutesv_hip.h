@@ -816,6 +816,39 @@ int csv_vcf_emit(const csv_vcf_in* in, char* out, int64_t cap, int64_t* n_writte
 int64_t csv_fasta_index(const char* data, int64_t size, int64_t max_contigs, int64_t* name_off, int32_t* name_len,
                         int64_t* length, int64_t* offset, int32_t* line_bases, int32_t* line_width);
 
+/* csv_fasta_index for a text that is never in memory whole (a BGZF-compressed FASTA inflated window by window):
+ * open, feed the windows in order, finish, close.  For every cut of a text into windows the entries and the verdict are those of
+ * csv_fasta_index over the whole text.  feed: CSV_OK, or CSV_E_INVALID from the first refusal on.  finish: the number of contigs
+ * or -CSV_E_INVALID; the arrays receive the first max_contigs entries, *names_bytes the bytes of all names, `names` those bytes back
+ * to back when they fit names_cap (name_off addresses them there).  finish may be called again with larger arrays.  No GPU work. */
+typedef struct csv_fai_stream csv_fai_stream;
+csv_fai_stream* csv_fasta_index_stream_open(void);
+int csv_fasta_index_stream_feed(csv_fai_stream* s, const char* data, int64_t size);
+int64_t csv_fasta_index_stream_finish(csv_fai_stream* s, int64_t max_contigs, char* names, int64_t names_cap, int64_t* names_bytes, int64_t* name_off,
+                                      int32_t* name_len, int64_t* length, int64_t* offset, int32_t* line_bases, int32_t* line_width);
+void csv_fasta_index_stream_close(csv_fai_stream* s);
+/* A window may also be fed as its event rows (csrc/ref_core.h; csv_fai_events below makes them on the device, csv_fai_events_host on
+ * the host), in any mix with windows fed as bytes.  carry: carry[3] <- the line in progress (its absolute first byte, that byte, the
+ * last byte seen), which the rows of the next window are made with.  rows: the next window, window_bytes long, as n_rows rows of 3
+ * int64 {absolute first byte of a line, its bytes without the line break, its bases | 1 << 62 for a header}, the header texts and the
+ * carry behind the window, as csv_fai_events gave them.  CSV_E_INVALID: the text is refused, or the rows do not describe a window
+ * behind the text fed so far. */
+int csv_fasta_index_stream_carry(const csv_fai_stream* s, int64_t* carry /* [3] */);
+int csv_fasta_index_stream_rows(csv_fai_stream* s, const int64_t* rows, int64_t n_rows, const char* hdr, int64_t hdr_bytes, int64_t window_bytes,
+                                const int64_t* tail /* [3] */);
+
+/* The reference bases of the calls from somewhere else than chrom_seq (a BGZF-compressed FASTA: fasta.BgzfReference.gather).
+ * csv_vcf_ref_ranges: per call c its contig chrom[c] (an index into chrom_name) and the bases [beg[c], end[c]) of it that the call's
+ * record reads - INS [max(pos-1,0), +1), DEL [max(pos-1,0), min(pos+len, contig length)), DUP [pos, +1), INV the '++' / other rule,
+ * BND either of its two indices; empty for a call the size filters drop, for INS / DEL under ignore_sequence, and for a BND call whose
+ * base does not exist (its record says 'N').  chrom_len gives the contig lengths (0: the contig has no sequence); chrom_seq is not
+ * read.  CSV_E_INVALID where csv_vcf_emit answers that: another call whose range is not inside its contig.
+ * csv_vcf_emit_ref: csv_vcf_emit with the bases of call c's range taken from ref_blob[ref_off[c] .. ref_off[c + 1]) (n_calls + 1
+ * offsets) in place of chrom_seq; CSV_E_INVALID also when a call's bytes are not as many as its range.  One function defines the
+ * ranges for both and for csv_vcf_emit. */
+int csv_vcf_ref_ranges(const csv_vcf_in* in, int64_t* beg, int64_t* end, int32_t* chrom);
+int csv_vcf_emit_ref(const csv_vcf_in* in, const char* ref_blob, const int64_t* ref_off, char* out, int64_t cap, int64_t* n_written, int64_t* svid);
+
 /* ---------------------------------------------------------------------------------------------
  * Host-side row builder: the structure-of-arrays result -> the row lists the reference's resolvers return
  * (DEL 13 fields INDEL:207-219 / 464-478, INS 14 INDEL:419-432, DUP 11 DUP:121-131 / 170-180, INV 12 INV:145-156 /
@@ -1037,6 +1070,47 @@ int csv_bgzf_deflate_host(const uint8_t* in, int64_t in_bytes, int32_t n_blocks,
  * reappears, a position at or beyond 2^29, a line without a numeric POS - named by the ordinal of the data line, from 0. */
 int csv_tbx_build(const char* text, int64_t text_bytes, int64_t n_blocks, const int64_t* uoff, const int64_t* coff, const uint32_t* isize,
                   uint8_t* out, int64_t out_cap, int64_t* out_bytes, char* err, int32_t err_cap);
+
+/* Reference bases out of a BGZF-compressed FASTA: n_ranges base ranges, cut out of the n_blocks BGZF blocks
+ * they touch, on the device.  Block k: the raw-deflate payload comp[in_off[k] .. + in_len[k]), which inflates to the isize[k] (0 ..
+ * 65536) bytes at the uncompressed offsets [uoff[k], uoff[k] + isize[k]) with CRC32 crc[k]; the blocks are sorted by uoff and do not
+ * overlap; they need not be adjacent.  Range r: bases [beg[r], end[r]) of a contig whose first base sits at uncompressed offset
+ * base_off[r], with line_bases[r] bases per line of line_width[r] bytes - base i lies at base_off + (i / lb) * lw + i % lb.  Ranges may
+ * be unsorted, empty, equal or overlapping.  out receives the bases of the ranges in order, line breaks left out; out_off the n_ranges
+ * + 1 offsets; *out_bytes their sum.  When that exceeds out_cap the call still returns CSV_OK, *out_bytes tells the need, and no byte
+ * of `out` or of block_status is written.  block_status[k]: csv_bgzf_inflate's status byte of block k (all 0 when no range has a
+ * base: nothing is inflated then); the bytes of ranges that read a block with a non-zero status are unspecified, and nothing outside
+ * out[0, *out_bytes) is written.  CSV_E_INVALID with a text, nothing launched and nothing written: a null pointer, a negative count,
+ * line_bases <= 0, line_width < line_bases, beg < 0, end < beg, overlapping or unsorted blocks, a payload outside comp, flags != 0
+ * (none is defined), a range any of whose source bytes lies in none of the blocks (named by its ordinal).  ms_kernels (may be NULL):
+ * device time of the inflate and of the gather.  The entry uses device buffers of its own and leaves everything else the context
+ * holds as it is. */
+int csv_ref_gather(csv_ctx* ctx, const uint8_t* comp, int64_t comp_bytes, int32_t n_blocks, const int64_t* in_off, const int32_t* in_len,
+                   const int64_t* uoff, const int32_t* isize, const uint32_t* crc, int64_t n_ranges, const int64_t* base_off,
+                   const int32_t* line_bases, const int32_t* line_width, const int64_t* beg, const int64_t* end, uint8_t* out, int64_t out_cap,
+                   int64_t* out_off, int64_t* out_bytes, uint8_t* block_status, int32_t flags, double* ms_kernels /* [2] */);
+/* the same on the host, one thread, no context, from blocks that are inflated already: block k's bytes are data[data_off[k] .. +
+ * isize[k]).  The refusal's text goes to err (may be NULL). */
+int csv_ref_gather_host(const uint8_t* data, int64_t data_bytes, int32_t n_blocks, const int64_t* data_off, const int64_t* uoff,
+                        const int32_t* isize, int64_t n_ranges, const int64_t* base_off, const int32_t* line_bases, const int32_t* line_width,
+                        const int64_t* beg, const int64_t* end, uint8_t* out, int64_t out_cap, int64_t* out_off, int64_t* out_bytes,
+                        char* err, int32_t err_cap);
+
+/* The .fai of a BGZF-compressed FASTA on the device: one window of its text - the n_blocks adjacent blocks
+ * whose text starts at uncompressed offset `base`, given as csv_ref_gather takes them - is inflated on the device and reduced there to
+ * event rows: one row of 3 int64 per line that a line break inside the window ends and that matters (the window's first, a header,
+ * the line after a header, a line whose bytes or bases differ from the line before).  carry[3]: csv_fasta_index_stream_carry's.
+ * rows / *n_rows, tail[3] and hdr / *hdr_bytes are what csv_fasta_index_stream_rows takes.  *n_rows > row_cap or *hdr_bytes > hdr_cap:
+ * the call returns CSV_OK, reports the need and fills neither; *n_rows == -1: a block has a non-zero status (block_status as
+ * csv_bgzf_inflate's).  Such a window is the host's: inflate it there and feed its bytes.  A window holds at most 2^30 bytes.
+ * ms_kernels (may be NULL): device time of the inflate and of the event kernels.  Device buffers of the entry's own, as csv_ref_gather. */
+int csv_fai_events(csv_ctx* ctx, const uint8_t* comp, int64_t comp_bytes, int32_t n_blocks, const int64_t* in_off, const int32_t* in_len,
+                   const int32_t* isize, const uint32_t* crc, int64_t base, const int64_t* carry /* [3] */, int64_t* rows, int64_t row_cap,
+                   int64_t* n_rows, int64_t* tail /* [3] */, char* hdr, int64_t hdr_cap, int64_t* hdr_bytes, uint8_t* block_status,
+                   double* ms_kernels /* [2] */);
+/* the same on the host from the window's inflated bytes, no context: the twin (rows beyond row_cap are counted, not written) */
+int csv_fai_events_host(const uint8_t* data, int64_t n, int64_t base, const int64_t* carry /* [3] */, int64_t* rows, int64_t row_cap,
+                        int64_t* n_rows, int64_t* tail /* [3] */, char* hdr, int64_t hdr_cap, int64_t* hdr_bytes);
 
 /* Record framing on the device, opt-in.  ctx != NULL: it must be the context of the reader's device inflate
  * route (csv_bam_set_inflate with the same ctx before; CSV_E_STATE otherwise).  From then on the inflated window stays in device
