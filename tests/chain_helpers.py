@@ -41,6 +41,7 @@ class Case:
         self.name, self.family, self.group, self.segs = name, family, group, segs
         self.a, self.b, self.aux = np.asarray(a, np.int64), np.asarray(b, np.int64), np.asarray(aux, np.int64)
         self.cells, self.checks, self.reads, self.only32 = set(cells), list(checks), reads, only32
+        self.rid = None                                      # read ids other than the row index (emit_helpers.EmitCase)
         n = len(self.a)
         assert sum(s["n"] for s in segs) == n == len(self.b) == len(self.aux), name
         lim = 1 << 31
@@ -74,7 +75,8 @@ class Case:
         copy = copy or (lambda x: x)
         dt = np.int32 if narrow else np.int64
         a, b = copy(self.a.astype(dt)), copy(self.b.astype(dt))
-        rid, aux = copy(np.arange(self.n_sig, dtype=np.int32)), copy(self.aux.astype(np.int32))
+        rid = copy(np.arange(self.n_sig, dtype=np.int32) if self.rid is None else np.ascontiguousarray(self.rid, np.int32))
+        aux = copy(self.aux.astype(np.int32))
         kw = {}
         if self.reads is not None:
             n_chrom, off, rs, re, rp, ri = self.reads
