@@ -13,8 +13,14 @@ columns on the device; csv_cluster_batch clusters them in place; the ALT bases o
 RNAMES text are gathered on the device (rebuild.alt_gather / support_join) and handed to the native emitter as they are.
 Nothing here loops in Python over records, signatures or supports: only over tasks, segments and contigs.
 
+call_bam is that chain as a list of phases: resolve_options checks and defaults the option keywords without
+touching a file or the device, _session opens or borrows the reader and the context, sets the routes and puts everything back, _Laps
+keeps `timings` and `read_stats`; then _chrom_table, _task_list, _run_tasks, _rebuild, _cluster, the TRA genotyping, the two gathers, emit.
+
 The text is the VCF BODY: the records of main script :1208-1237 in its order.  The header stays the driver's (DESIGN.md
 section 11)."""
+import collections
+import contextlib
 import dataclasses
 import math
 import os
@@ -23,7 +29,7 @@ from dataclasses import dataclass, field
 
 import numpy as np
 
-from . import _abi
+from . import _abi, aln, bam as bam_mod, bed as bed_mod, engine, extract, fasta, reads as reads_mod, rebuild, vcf
 from .columns import Params, TYPES, segment_record
 
 
@@ -174,6 +180,193 @@ class _Shim:
         self.chroms, self.strands = list(chroms), tuple(strands)
 
 
+# call_bam's option keywords, checked and with their defaults filled in (resolve_options; call_bam's docstring has the meanings).  regions: the bed.Regions
+# of include_bed or None; mode: tra_gt_mode's answer; cp: the CallParams; p: cp.resolve with genotype_tra set for mode "reads_table"; reads_dev: the tasks
+# append to the context's device-resident reads table; build_index: index="build" for a path - the session builds what the file lacks
+Options = dataclasses.make_dataclass("Options", "reads_table frame inflate ref_route gates regions mode cp p reads_dev task_cut cut_threads index_format build_index".split(),
+                                     frozen=True)
+
+
+def _route(name, value, default):
+    """a host/device option: None takes `default` (None is then kept); ValueError for anything else"""
+    value = default if value is None else value
+    if value not in (None, "host", "device"):
+        raise ValueError("%s must be 'host' or 'device', not %r" % (name, value))
+    return value
+
+
+def resolve_options(bam, index, params, tra_gt=None, include_bed=None, gates=None, reads_table=None, inflate=None, frame=None, task_cut=None, cut_threads=16,
+                    index_format="bai", ref_route=None):
+    """call_bam's keywords as they arrive -> Options.  Pure: of `bam` it reads whether it is an open reader with an index, it opens nothing
+    but a BED file, and DEFAULT_* are read now.  The refusals fire in the order below; `gates` is task_to_pool's to
+    check, and the second index check ("none was found for <path>") is the session's, which knows the reader."""
+    is_reader = hasattr(bam, "references")
+    if index_format not in ("bai", "csi"):
+        raise ValueError("index_format must be 'bai' or 'csi', not %r" % (index_format,))
+    ref_route = _route("ref_route", ref_route, None)
+    if task_cut not in (None, "uniform", "index"):
+        raise ValueError("task_cut must be None, 'uniform' or 'index', not %r" % (task_cut,))
+    if task_cut == "index" and not (getattr(bam, "has_index", False) if is_reader else index is not False):
+        raise ValueError("task_cut='index' needs a BAM index (.bai): this reader has none")
+    reads_table = _route("reads_table", reads_table, DEFAULT_READS_TABLE)
+    frame = _route("frame", frame, DEFAULT_FRAME)
+    if frame == "device" and inflate == "host":
+        raise ValueError("frame='device' needs the device inflate: inflate='host' cannot be combined with it")
+    inflate = _route("inflate", inflate, "device" if frame == "device" else DEFAULT_INFLATE)
+    regions = None if include_bed is None else include_bed if isinstance(include_bed, bed_mod.Regions) else bed_mod.load_bed(include_bed)
+    if gates is None:
+        gates = "device" if regions is not None else DEFAULT_GATES
+    cp = params if isinstance(params, CallParams) else CallParams(resolve=params)
+    mode = tra_gt_mode(cp.resolve.genotype, tra_gt)
+    if task_cut == "index" and (not isinstance(cut_threads, (int, np.integer)) or cut_threads < 1):
+        raise ValueError("cut_threads must be a positive integer, not %r" % (cut_threads,))
+    p = dataclasses.replace(cp.resolve, genotype_tra=(mode == "reads_table"))
+    return Options(reads_table, frame, inflate, ref_route, gates, regions, mode, cp, p, reads_table == "device" and p.genotype, task_cut, cut_threads, index_format,
+                   not is_reader and isinstance(index, str) and index == "build")
+
+
+@contextlib.contextmanager
+def _session(bam, ctx, opts, threads, index, timings, read_stats):
+    """-> (reader, context, laps) for one call: on the call's inflate and frame routes, with the index built when that was asked for.  What
+    the session opened is closed at the end, the reader before the context it may inflate on, and as soon as a later step fails; a reader
+    that was handed in gets its previous inflate setting back, and device framing if it had it; a context that was handed in is left alone."""
+    with contextlib.ExitStack() as stack:
+        own_ctx = stack.enter_context(contextlib.ExitStack())          # (entered first, so released last: after the reader)
+        bf = bam if isinstance(bam, bam_mod.BamFile) else stack.enter_context(
+            contextlib.closing(bam_mod.BamFile(bam, threads=threads, index=None if opts.build_index else index)))
+        if ctx is None:
+            ctx = own_ctx.enter_context(contextlib.closing(engine.Context(0)))
+        laps = _Laps(timings, read_stats)
+        if opts.task_cut == "index" and not bf.has_index and not opts.build_index:
+            raise ValueError("task_cut='index' needs a BAM index (.bai): none was found for %s" % bf.path)
+        was_framed = bf.frame is not None
+        previous = bf.set_inflate(ctx if opts.inflate == "device" else None)
+        if bf is bam and was_framed:
+            stack.callback(bf.set_frame, "device")
+        if bf is bam:
+            stack.callback(bf.set_inflate, previous)                   # (callbacks run last in, first out: the inflate setting goes back first)
+        bf.set_frame(opts.frame)
+        if opts.build_index:
+            if not bf.has_index:
+                bf.build_index(format=opts.index_format)
+            laps.lap("ms_index")
+        yield bf, ctx, laps
+
+
+class _Laps:
+    """the caller's `timings` and `read_stats` (either may be None): lap(key) adds the wall milliseconds since the last lap (or the start) to timings[key];
+    add_task the sums of one task - `stats`: the reader's last_stats (a task reads its records in one call), `r`: what task_to_pool returned"""
+
+    def __init__(self, timings, read_stats):
+        self.timings, self.read_stats, self.clock = timings, read_stats, time.perf_counter()
+
+    def lap(self, key):
+        now = time.perf_counter()
+        if self.timings is not None:
+            self.timings[key] = self.timings.get(key, 0.0) + (now - self.clock) * 1e3
+        self.clock = now
+
+    def add_task(self, stats, r):
+        if self.timings is not None:
+            for key in ("ms_inflate", "ms_frame"):
+                self.timings[key] = self.timings.get(key, 0.0) + stats[key]
+        if self.read_stats is not None:
+            self.read_stats["compressed_bytes"] = self.read_stats.get("compressed_bytes", 0) + stats["compressed_bytes"]
+            self.read_stats["n_records"] = self.read_stats.get("n_records", 0) + r["n_records"]
+            self.read_stats.setdefault("task_records", []).append(r["n_records"])
+
+
+# the contigs' names sorted, {contig: bases}, {contig: name rank}, the lengths in rank order, the contigs to call on
+_Chroms = collections.namedtuple("_Chroms", "names length crank contig_len wanted")
+
+
+def _chrom_table(bf, chroms):
+    """the chromosome table in name order: a chromosome's index is its name rank, the numbering of rebuild._segments and of a TRA row's mate"""
+    names = sorted(bf.references)
+    wanted = names if chroms is None else [c for c in names if c in set(chroms)]
+    if chroms is not None and len(wanted) != len(set(chroms)):
+        raise KeyError("no reference %r in the BAM header" % sorted(set(chroms) - set(names))[0])
+    length = dict(zip(bf.references, bf.lengths))
+    return _Chroms(names, length, {c: i for i, c in enumerate(names)}, np.array([length[c] for c in names], np.int64), wanted)
+
+
+def _task_list(bf, ch, opts, batch):
+    """-> [(contig, start, end)] in name order, which keeps the ordering contracts of the appends; the bounds as the cut makes them: floats under the index cut"""
+    if opts.task_cut != "index":
+        return [(c, t0, t1) for c in ch.wanted for t0, t1 in cut_tasks(ch.length[c], batch)]
+    by_contig = {}
+    for c, t0, t1 in cut_tasks_index(bf.index_statistics(), ch.length, batch, int(opts.cut_threads)):
+        by_contig.setdefault(c, []).append((t0, t1))
+    return [(c, t0, t1) for c in ch.wanted for t0, t1 in by_contig.get(c, [])]
+
+
+def _run_tasks(ctx, bf, ch, tasks, opts, laps):
+    """the pools reset, every task through extract.task_to_pool -> [(chromosome index, its reads-table columns)] for reads_table="host" with genotype, else []"""
+    n_chrom, crank = len(ch.names), ch.crank
+    seg_of = {t: ti * n_chrom for ti, t in enumerate(TYPES)}
+    seg_base = [seg_of[t] for t in ("DEL", "INS", "DUP", "INV", "TRA")]
+    rebuild.pool_reset(ctx)
+    rebuild.name_pool_reset(ctx)
+    if opts.mode == "alignments":
+        aln.reset(ctx, n_chrom)
+    if opts.reads_dev:
+        reads_mod.reset(ctx, n_chrom)
+    tables = []
+    skip = opts.regions is not None and bf.has_index and opts.mode != "alignments"      # a task reads its regions only: the alignment table needs every record
+    for c, t0, t1 in tasks:
+        regs = None if opts.regions is None else opts.regions.for_task(c, t0, t1)      # (the bounds as they are)
+        i0, i1 = task_bounds(t0, t1)
+        r = extract.task_to_pool(ctx, bf, c, i0, i1, crank, *opts.cp.pipe_args(), seg_of["INS"] + crank[c], seg_of["DEL"] + crank[c], seg_base, None,
+                                 name_pool=True, seq_pool=True, aln=(opts.mode == "alignments"), gates=opts.gates, reads="device" if opts.reads_dev else "host",
+                                 bed_regions=regs, ranges=task_ranges(bf, c, regs, i0, i1) if skip else None)
+        if opts.p.genotype and not opts.reads_dev:
+            tables.append((crank[c], r))
+        laps.add_task(bf.last_stats, r)
+    return tables
+
+
+def _empty_result(sigs_dir, as_bytes, svid):
+    """no signature at all: an empty text, and with sigs_dir five empty files, as the reference's open(..., "w") leaves them"""
+    if sigs_dir is not None:
+        for t in TYPES:
+            open(os.path.join(sigs_dir, t + ".sigs"), "wb").close()
+    return (b"" if as_bytes else ""), (np.zeros(5, np.int64) if svid is None else svid)
+
+
+def _rebuild(ctx, names):
+    """the pool sorted and de-duplicated by read name, INS ties settled from the sequences, columns kept on the device -> (contig order, rebuild)"""
+    order, _, major, nodedup = rebuild._segments(names, True)
+    rb = rebuild.rebuild_pool_by_name(ctx, major, nodedup, keep_on_device=True, ties="seqs")
+    if rb["n_ins_ties"]:
+        raise ValueError("%d INS rows were not settled on the device" % rb["n_ins_ties"])
+    return order, rb
+
+
+def _cluster(ctx, ch, order, rb, tables, opts):
+    """one segment record per (type, contig) with rows, the genotyping reads table (device, host or none), csv_cluster_batch in place -> (segs, result)"""
+    n_chrom, p = len(ch.names), opts.p
+    off = np.r_[0, np.cumsum(rb["seg_count"])]
+    segs = [segment_record(TYPES[s // n_chrom], order[s % n_chrom], int(off[s]), int(off[s + 1]), p, have_contig_len=p.genotype_tra)
+            for s in np.flatnonzero(rb["seg_count"]).tolist()]
+    segs = np.array(segs, dtype=_abi.SEGMENT_DTYPE)
+    reads = {}
+    if opts.reads_dev:
+        # (`wanted` is in name-rank order and a contig's tasks ran in order: the appends arrived grouped by chromosome)
+        reads = dict(reads_dev=reads_mod.batch_columns(ctx, n_chrom, reads_mod.RANK_FROM_NAMES))
+    elif p.genotype and tables:
+        reads = reads_mod.table_host(tables, rebuild.name_ranks(ctx)["rank"], n_chrom)
+    if reads and p.genotype_tra:
+        reads["contig_len"] = ch.contig_len
+    return segs, ctx.cluster_batch(_abi.HostBatch.on_device(segs, rb["dev"], rb["n_out"], n_chrom=n_chrom, keep=ctx, **reads))
+
+
+def _gather_alt(ctx, segs, res, t):
+    """the ALT bases of the INS calls, gathered on the device -> (blob, lengths)"""
+    ins = np.flatnonzero(segs["svtype"][t["call_seg"]] == _abi.INS) if res.n_calls else np.zeros(0, np.int64)
+    blob, aoff = rebuild.alt_gather(ctx, t["seq_pick"][ins], t["bp2"][ins])
+    return blob, np.diff(aoff)
+
+
 def call_bam(bam, reference, params, ctx=None, chroms=None, batch=10_000_000, report_readid=False, ignore_sequence=False, threads=None, svid=None,
              as_bytes=False, timings=None, tra_gt=None, include_bed=None, gates=None, reads_table=None, sigs_dir=None, inflate=None, index=None, task_cut=None,
              cut_threads=16, read_stats=None, frame=None, index_format="bai", ref_route=None):
@@ -227,162 +420,52 @@ def call_bam(bam, reference, params, ctx=None, chroms=None, batch=10_000_000, re
                looks at it.
     read_stats a dict that receives what the tasks' reads cost: compressed_bytes and n_records summed over the tasks, task_records - the
                records each task read, in task order."""
-    if index_format not in ("bai", "csi"):
-        raise ValueError("index_format must be 'bai' or 'csi', not %r" % (index_format,))
-    if ref_route not in (None, "host", "device"):
-        raise ValueError("ref_route must be 'host' or 'device', not %r" % (ref_route,))
-    if task_cut not in (None, "uniform", "index"):
-        raise ValueError("task_cut must be None, 'uniform' or 'index', not %r" % (task_cut,))
-    if task_cut == "index" and not (getattr(bam, "has_index", False) if hasattr(bam, "references") else index is not False):
-        raise ValueError("task_cut='index' needs a BAM index (.bai): this reader has none")
-    from . import aln, bam as bam_mod, bed as bed_mod, engine, extract, reads as reads_mod, rebuild, vcf
-    if reads_table is None:
-        reads_table = DEFAULT_READS_TABLE
-    if reads_table not in ("host", "device"):
-        raise ValueError("reads_table must be 'host' or 'device', not %r" % (reads_table,))
-    if frame is None:
-        frame = DEFAULT_FRAME
-    if frame not in ("host", "device"):
-        raise ValueError("frame must be 'host' or 'device', not %r" % (frame,))
-    if frame == "device" and inflate == "host":
-        raise ValueError("frame='device' needs the device inflate: inflate='host' cannot be combined with it")
-    if inflate is None:
-        inflate = "device" if frame == "device" else DEFAULT_INFLATE
-    if inflate not in ("host", "device"):
-        raise ValueError("inflate must be 'host' or 'device', not %r" % (inflate,))
-    regions = None if include_bed is None else include_bed if isinstance(include_bed, bed_mod.Regions) else bed_mod.load_bed(include_bed)
-    if gates is None:
-        gates = "device" if regions is not None else DEFAULT_GATES
-    cp = params if isinstance(params, CallParams) else CallParams(resolve=params)
-    mode = tra_gt_mode(cp.resolve.genotype, tra_gt)
-    p = dataclasses.replace(cp.resolve, genotype_tra=(mode == "reads_table"))
-    own_bam = not isinstance(bam, bam_mod.BamFile)
-    build_index = own_bam and isinstance(index, str) and index == "build"
-    bf = bam_mod.BamFile(bam, threads=threads, index=None if build_index else index) if own_bam else bam
-    own_ctx = ctx is None
-    if own_ctx:
-        ctx = engine.Context(0)
-    restore = None                                            # the reader's inflate route before this call, once it has been changed
-    clock = [time.perf_counter()]
-
-    def lap(key):
-        now = time.perf_counter()
-        if timings is not None:
-            timings[key] = timings.get(key, 0.0) + (now - clock[0]) * 1e3
-        clock[0] = now
-    try:
-        if task_cut == "index" and not bf.has_index and not build_index:
-            raise ValueError("task_cut='index' needs a BAM index (.bai): none was found for %s" % bf.path)
-        was_framed = bf.frame is not None
-        restore = (bf.set_inflate(ctx if inflate == "device" else None), was_framed)
-        bf.set_frame(frame)
-        if build_index:
-            if not bf.has_index:
-                bf.build_index(format=index_format)
-            lap("ms_index")
-        # the chromosome table in name order: a chromosome's index is its name rank, the numbering of rebuild._segments and of a TRA row's mate
-        names = sorted(bf.references)
-        length = dict(zip(bf.references, bf.lengths))
-        crank = {c: i for i, c in enumerate(names)}
-        n_chrom = len(names)
-        wanted = names if chroms is None else [c for c in names if c in set(chroms)]
-        if chroms is not None and len(wanted) != len(set(chroms)):
-            raise KeyError("no reference %r in the BAM header" % sorted(set(chroms) - set(names))[0])
-        seg_of = {t: ti * n_chrom for ti, t in enumerate(TYPES)}
-        seg_base = [seg_of[t] for t in ("DEL", "INS", "DUP", "INV", "TRA")]
-        rebuild.pool_reset(ctx)
-        rebuild.name_pool_reset(ctx)
-        if mode == "alignments":
-            aln.reset(ctx, n_chrom)
-        reads_dev = reads_table == "device" and p.genotype
-        if reads_dev:
-            reads_mod.reset(ctx, n_chrom)
-        tables = []                                           # reads_table="host", per task: (chromosome index, its reads-table columns)
-        by_contig = {}
-        if task_cut == "index":
-            if not isinstance(cut_threads, (int, np.integer)) or cut_threads < 1:
-                raise ValueError("cut_threads must be a positive integer, not %r" % (cut_threads,))
-            for c, t0, t1 in cut_tasks_index(bf.index_statistics(), length, batch, int(cut_threads)):
-                by_contig.setdefault(c, []).append((t0, t1))
-        # (contigs are visited in name order, which keeps the ordering contracts of the appends; with an index the seeks between them are free)
-        skip = regions is not None and bf.has_index and mode != "alignments"      # a task reads its regions only: the alignment table needs every record
-        for c in wanted:
-            for t0, t1 in (by_contig.get(c, []) if task_cut == "index" else cut_tasks(length[c], batch)):
-                regs = None if regions is None else regions.for_task(c, t0, t1)                # (the bounds as they are: floats under the index cut)
-                i0, i1 = task_bounds(t0, t1)
-                r = extract.task_to_pool(ctx, bf, c, i0, i1, crank, *cp.pipe_args(), seg_of["INS"] + crank[c], seg_of["DEL"] + crank[c], seg_base, None,
-                                         name_pool=True, seq_pool=True, aln=(mode == "alignments"), gates=gates, reads="device" if reads_dev else "host",
-                                         bed_regions=regs, ranges=task_ranges(bf, c, regs, i0, i1) if skip else None)
-                if p.genotype and not reads_dev:
-                    tables.append((crank[c], r))
-                if timings is not None:
-                    timings["ms_inflate"] = timings.get("ms_inflate", 0.0) + bf.last_stats["ms_inflate"]      # (a task reads its records in one call)
-                    timings["ms_frame"] = timings.get("ms_frame", 0.0) + bf.last_stats["ms_frame"]
-                if read_stats is not None:
-                    read_stats["compressed_bytes"] = read_stats.get("compressed_bytes", 0) + bf.last_stats["compressed_bytes"]
-                    read_stats["n_records"] = read_stats.get("n_records", 0) + r["n_records"]
-                    read_stats.setdefault("task_records", []).append(r["n_records"])
-        lap("ms_tasks")
+    opts = resolve_options(bam, index, params, tra_gt, include_bed, gates, reads_table, inflate, frame, task_cut, cut_threads, index_format, ref_route)
+    with _session(bam, ctx, opts, threads, index, timings, read_stats) as (bf, ctx, laps):
+        ch = _chrom_table(bf, chroms)
+        tables = _run_tasks(ctx, bf, ch, _task_list(bf, ch, opts, batch), opts, laps)
+        laps.lap("ms_tasks")
         if rebuild.pool_rows(ctx) == 0:
-            if sigs_dir is not None:                           # (no signature at all: five empty files, as the reference's open(..., "w") leaves them)
-                for t in TYPES:
-                    open(os.path.join(sigs_dir, t + ".sigs"), "wb").close()
-            return (b"" if as_bytes else ""), (np.zeros(5, np.int64) if svid is None else svid)
-        order, _, major, nodedup = rebuild._segments(names, True)
-        rb = rebuild.rebuild_pool_by_name(ctx, major, nodedup, keep_on_device=True, ties="seqs")
-        if rb["n_ins_ties"]:
-            raise ValueError("%d INS rows were not settled on the device" % rb["n_ins_ties"])
-        lap("ms_rebuild")
+            return _empty_result(sigs_dir, as_bytes, svid)
+        order, rb = _rebuild(ctx, ch.names)
+        laps.lap("ms_rebuild")
         if sigs_dir is not None:
-            rebuild.write_sigs(ctx, rb, names, sigs_dir)
-            lap("ms_sigs")
-        off = np.r_[0, np.cumsum(rb["seg_count"])]
-        have_len = p.genotype_tra
-        segs = [segment_record(TYPES[s // n_chrom], order[s % n_chrom], int(off[s]), int(off[s + 1]), p, have_contig_len=have_len)
-                for s in np.flatnonzero(rb["seg_count"]).tolist()]
-        segs = np.array(segs, dtype=_abi.SEGMENT_DTYPE)
-        reads = {}
-        if reads_dev:
-            # (`wanted` is in name-rank order and a contig's tasks ran in order: the appends arrived grouped by chromosome)
-            reads = dict(reads_dev=reads_mod.batch_columns(ctx, n_chrom, reads_mod.RANK_FROM_NAMES))
-        elif p.genotype and tables:
-            reads = reads_mod.table_host(tables, rebuild.name_ranks(ctx)["rank"], n_chrom)
-        if reads and p.genotype_tra:
-            reads["contig_len"] = np.array([length[c] for c in names], np.int64)
-        hb = _abi.HostBatch.on_device(segs, rb["dev"], rb["n_out"], n_chrom=n_chrom, keep=ctx, **reads)
-        res = ctx.cluster_batch(hb)
-        lap("ms_cluster")
-        if mode == "alignments":
-            _genotype_tra_from_alignments(ctx, segs, res, np.array([length[c] for c in names], np.int64), p)
-        lap("ms_tra_gt")
+            rebuild.write_sigs(ctx, rb, ch.names, sigs_dir)
+            laps.lap("ms_sigs")
+        segs, res = _cluster(ctx, ch, order, rb, tables, opts)
+        laps.lap("ms_cluster")
+        if opts.mode == "alignments":
+            _genotype_tra_from_alignments(ctx, segs, res, ch.contig_len, opts.p)
+        laps.lap("ms_tra_gt")
         t = res.trimmed()
-        ins_alt = rnames = None
-        if not ignore_sequence:
-            ins = np.flatnonzero(segs["svtype"][t["call_seg"]] == _abi.INS) if res.n_calls else np.zeros(0, np.int64)
-            blob, aoff = rebuild.alt_gather(ctx, t["seq_pick"][ins], t["bp2"][ins])
-            ins_alt = (blob, np.diff(aoff))
-        lap("ms_alt_gather")
-        if report_readid:
-            rnames = rebuild.support_join(ctx, t["support_off"], t["support_sig"])
-        lap("ms_support_join")
-        out = vcf.emit_records(_Shim(names), segs, res, reference, min_size=p.min_size, max_size=p.max_size, genotype=p.genotype, report_readid=report_readid,
-                               ignore_sequence=ignore_sequence, svid=svid, as_bytes=as_bytes, ins_alt=ins_alt, rnames=rnames, ref_ctx=ctx, ref_route=ref_route)
-        lap("ms_emit")
+        ins_alt = None if ignore_sequence else _gather_alt(ctx, segs, res, t)
+        laps.lap("ms_alt_gather")
+        rnames = rebuild.support_join(ctx, t["support_off"], t["support_sig"]) if report_readid else None
+        laps.lap("ms_support_join")
+        out = vcf.emit_records(_Shim(ch.names), segs, res, reference, min_size=opts.p.min_size, max_size=opts.p.max_size, genotype=opts.p.genotype, report_readid=report_readid,
+                               ignore_sequence=ignore_sequence, svid=svid, as_bytes=as_bytes, ins_alt=ins_alt, rnames=rnames, ref_ctx=ctx, ref_route=opts.ref_route)
+        laps.lap("ms_emit")
         return out
-    finally:
-        if restore is not None and not own_bam:
-            bf.set_inflate(restore[0])
-            if restore[1]:
-                bf.set_frame("device")
-        if own_bam:                                            # (the reader goes before the context it may inflate on)
-            bf.close()
-        if own_ctx:
-            ctx.close()
+
+
+def add_route_options(ap):
+    """the route options that python -m cutesv_amd.call and cli.py's own parser share, declared here once"""
+    hd = ["host", "device"]
+    ap.add_argument("--reads_table", default=None, choices=hd, help="with --genotype: where the genotyping reads table is built (default: %s)" % DEFAULT_READS_TABLE)
+    ap.add_argument("--tra_gt", default=None, choices=list(TRA_GT_MODES),
+                    help="with --genotype: how BND records are genotyped (default: CUTESV_AMD_TRA_GT, else alignments - every alignment counts, as in cuteSV)")
+    ap.add_argument("--inflate", default=None, choices=hd, help="where the BAM's BGZF blocks are inflated (default: %s)" % DEFAULT_INFLATE)
+    ap.add_argument("--frame", default=None, choices=hd, help="where the BAM's records are framed (default: %s; device takes the device inflate)" % DEFAULT_FRAME)
+    ap.add_argument("--ref_route", default=None, choices=hd, help="where the REF bases of a BGZF-compressed reference are gathered (default: %s)" % fasta.DEFAULT_REF_ROUTE)
+
+
+def command_line_tra_gt(tra_gt, genotype):
+    """--tra_gt as a command line hands it to call_bam: with --genotype and neither the option nor CUTESV_AMD_TRA_GT, "alignments" - as cuteSV counts"""
+    return "alignments" if tra_gt is None and genotype and "CUTESV_AMD_TRA_GT" not in os.environ else tra_gt
 
 
 def main(argv=None):
     import argparse
-    from . import fasta
     ap = argparse.ArgumentParser(prog="python -m cutesv_amd.call", description="SV calls of a BAM file as VCF records (the body; no header)")
     ap.add_argument("bam")
     ap.add_argument("reference", help="reference FASTA, plain or BGZF-compressed (an .fai - and a .gzi - beside it is used, or built in memory)")
@@ -391,39 +474,24 @@ def main(argv=None):
     ap.add_argument("--genotype", action="store_true")
     ap.add_argument("--report_readid", action="store_true")
     ap.add_argument("--ignore_sequence", action="store_true", help="<INS> instead of the inserted bases")
-    ap.add_argument("--min_support", type=int, default=10)
-    ap.add_argument("--min_size", type=int, default=30)
-    ap.add_argument("--max_size", type=int, default=100000)
-    ap.add_argument("--min_mapq", type=int, default=20)
-    ap.add_argument("--min_read_len", type=int, default=500)
-    ap.add_argument("--max_split_parts", type=int, default=7)
-    ap.add_argument("--min_siglength", type=int, default=10)
-    ap.add_argument("--merge_del_threshold", type=int, default=0)
-    ap.add_argument("--merge_ins_threshold", type=int, default=100)
+    for name, default in (("min_support", 10), ("min_size", 30), ("max_size", 100000), ("min_mapq", 20), ("min_read_len", 500), ("max_split_parts", 7),
+                          ("min_siglength", 10), ("merge_del_threshold", 0), ("merge_ins_threshold", 100)):
+        ap.add_argument("--" + name, type=int, default=default)
     ap.add_argument("--batch", type=int, default=10_000_000, help="reference bases per extraction task")
     ap.add_argument("--threads", type=int, default=None, help="host threads that inflate the BAM")
     ap.add_argument("--chroms", default=None, help="comma-separated contigs (default: all)")
     ap.add_argument("--include_bed", "-include_bed", default=None, metavar="FILE",
                     help="only call where the regions of this BED file are (padded by 1000 bases, as in cuteSV); the calls then depend on --batch")
-    ap.add_argument("--reads_table", default=None, choices=["host", "device"],
-                    help="with --genotype: where the genotyping reads table is built (default: %s)" % DEFAULT_READS_TABLE)
-    ap.add_argument("--tra_gt", default=None, choices=list(TRA_GT_MODES),
-                    help="with --genotype: how BND records are genotyped (default: CUTESV_AMD_TRA_GT, else alignments - every alignment counts, as in cuteSV)")
-    ap.add_argument("--inflate", default=None, choices=["host", "device"], help="where the BAM's BGZF blocks are inflated (default: %s)" % DEFAULT_INFLATE)
-    ap.add_argument("--frame", default=None, choices=["host", "device"], help="where the BAM's records are framed (default: %s; device takes the device inflate)" % DEFAULT_FRAME)
-    ap.add_argument("--ref_route", default=None, choices=["host", "device"],
-                    help="where the REF bases of a BGZF-compressed reference are gathered (default: %s)" % fasta.DEFAULT_REF_ROUTE)
+    add_route_options(ap)
     ap.add_argument("--sigs_dir", default=None, metavar="DIR", help="also write the rebuilt signatures there as cuteSV's --write_old_sigs files (DEL.sigs .. TRA.sigs)")
     a = ap.parse_args(argv)
-    tra_gt = a.tra_gt
-    if tra_gt is None and a.genotype and "CUTESV_AMD_TRA_GT" not in os.environ:
-        tra_gt = "alignments"
     p = getattr(Params, a.preset)(min_support=a.min_support, min_size=a.min_size, max_size=a.max_size, genotype=a.genotype)
     cp = CallParams(p, min_mapq=a.min_mapq, max_split_parts=a.max_split_parts, min_read_len=a.min_read_len, min_siglength=a.min_siglength,
                     merge_del_threshold=a.merge_del_threshold, merge_ins_threshold=a.merge_ins_threshold)
-    text, svid = call_bam(a.bam, fasta.open_reference(a.reference, threads=a.threads), cp, chroms=a.chroms.split(",") if a.chroms else None, batch=a.batch,
-                          report_readid=a.report_readid, ignore_sequence=a.ignore_sequence, threads=a.threads, as_bytes=True, tra_gt=tra_gt,
-                          include_bed=a.include_bed, reads_table=a.reads_table, sigs_dir=a.sigs_dir, inflate=a.inflate, frame=a.frame, ref_route=a.ref_route)
+    with fasta.opened_reference(a.reference, a.threads) as reference:
+        text, svid = call_bam(a.bam, reference, cp, chroms=a.chroms.split(",") if a.chroms else None, batch=a.batch, report_readid=a.report_readid,
+                              ignore_sequence=a.ignore_sequence, threads=a.threads, as_bytes=True, tra_gt=command_line_tra_gt(a.tra_gt, a.genotype),
+                              include_bed=a.include_bed, reads_table=a.reads_table, sigs_dir=a.sigs_dir, inflate=a.inflate, frame=a.frame, ref_route=a.ref_route)
     with open(a.out, "wb") as f:
         f.write(text)
     print("%d records: INS %d, DEL %d, BND %d, DUP %d, INV %d" % (text.count(b"\n"), *svid.tolist()))

@@ -12,9 +12,9 @@ the end, as cuteSV's cleanup removes its own.  An OUT name that ends in .gz or .
 one stream - with its tabix index OUT.tbi beside it (bgzf.py; --bgzf picks the compressor: zlib on host threads
 or csv_bgzf_deflate on the device); any other name receives the plain text, as before.
 
-The files of this chain: cli.py (this command line) -> call.py (call_bam: BAM to VCF records) over bam.py (the reader), extract.py,
-rebuild.py, engine.py and genotype.py; vcf.py (header and records), fasta.py (the reference), bgzf.py (the BGZF writer and the tabix
-index of a compressed OUT).
+The files of this chain: cli.py (this command line) -> call.py (call_bam: BAM to VCF records in named phases, its options resolver and
+reader session, and what the two command lines share) over bam.py (the reader), extract.py, rebuild.py, engine.py and genotype.py;
+vcf.py (header and records), fasta.py (the reference), bgzf.py (the BGZF writer and the tabix index of a compressed OUT).
 
 What differs from cuteSV, on purpose:
   * The extraction tasks: with a .bai beside the BAM file (cuteSV cannot run without one) they are cuteSV's own cut from the index
@@ -100,18 +100,14 @@ def _parser():
 
 
 def _own_parser():
-    """the nine options cuteSV does not have; parsed apart (split_own), so that they shadow no abbreviation of a cuteSV flag"""
+    """the nine options cuteSV does not have (five are call.add_route_options'); parsed apart (split_own), so that they shadow no abbreviation of a cuteSV flag"""
     from . import call
     ap = argparse.ArgumentParser(add_help=False, allow_abbrev=False)
-    ap.add_argument("--reads_table", default=None, choices=["host", "device"])
-    ap.add_argument("--tra_gt", default=None, choices=list(call.TRA_GT_MODES))
-    ap.add_argument("--inflate", default=None, choices=["host", "device"])
-    ap.add_argument("--frame", default=None, choices=["host", "device"])
+    call.add_route_options(ap)
     ap.add_argument("--task_cut", default=None, choices=["index", "uniform"])
     ap.add_argument("--build_index", action="store_true")
     ap.add_argument("--index_format", default="bai", choices=["bai", "csi"])
     ap.add_argument("--bgzf", default=None, choices=["host", "device"])
-    ap.add_argument("--ref_route", default=None, choices=["host", "device"])
     return ap
 
 
@@ -173,9 +169,7 @@ def main(argv=None):
         if os.path.exists(path):
             raise FileExistsError("[Errno 17] File exists: '%s'" % path)
     from . import bam as bam_mod, call, fasta, vcf
-    tra_gt = own.tra_gt
-    if tra_gt is None and a.genotype and "CUTESV_AMD_TRA_GT" not in os.environ:
-        tra_gt = "alignments"
+    tra_gt = call.command_line_tra_gt(own.tra_gt, a.genotype)
     sigs_dir = a.work_dir if a.write_old_sigs else None
     t0 = time.perf_counter()
     timings = {}
@@ -195,11 +189,11 @@ def main(argv=None):
             task_cut = "index" if bf.has_index else "uniform"
             if not bf.has_index:
                 _log("no BAM index (.bai) beside %s: the tasks are the uniform cut by -b, not cuteSV's cut from the index statistics" % a.input)
-        reference = fasta.open_reference(a.reference, threads=a.threads)            # (plain text or BGZF, as pysam.FastaFile takes either)
-        body, svid = call.call_bam(source, reference, call_params(a), batch=a.batches, report_readid=a.report_readid,
-                                   ignore_sequence=a.ignore_sequence, as_bytes=True, timings=timings, tra_gt=tra_gt, include_bed=a.include_bed,
-                                   reads_table=own.reads_table, sigs_dir=sigs_dir, inflate=own.inflate, frame=own.frame, task_cut=task_cut, cut_threads=a.threads,
-                                   threads=a.threads, index=index, index_format=own.index_format, ref_route=own.ref_route)
+        with fasta.opened_reference(a.reference, a.threads) as reference:           # (plain text or BGZF, as pysam.FastaFile takes either)
+            body, svid = call.call_bam(source, reference, call_params(a), batch=a.batches, report_readid=a.report_readid,
+                                       ignore_sequence=a.ignore_sequence, as_bytes=True, timings=timings, tra_gt=tra_gt, include_bed=a.include_bed,
+                                       reads_table=own.reads_table, sigs_dir=sigs_dir, inflate=own.inflate, frame=own.frame, task_cut=task_cut, cut_threads=a.threads,
+                                       threads=a.threads, index=index, index_format=own.index_format, ref_route=own.ref_route)
     finally:
         bf.close()
     for key, ms in timings.items():

@@ -19,6 +19,7 @@ and for tests.
     python -m cutesv_amd.fasta FILE --faidx [--route host|device] [--write]      the .fai (and the .gzi) of a FASTA file, plain or BGZF
 """
 import argparse
+import contextlib
 import ctypes as C
 import gzip
 import mmap
@@ -188,6 +189,17 @@ def open_reference(path, ctx=None, route=None, threads=None, **kw):
     if route is not None and route not in REF_ROUTES:
         raise ValueError("route must be one of %s, not %r" % (", ".join(REF_ROUTES), route))
     return Reference(path, **kw)
+
+
+@contextlib.contextmanager
+def opened_reference(path, threads=None):
+    """open_reference for a command line: the mapping, the descriptor and the thread pool are released at the end, whatever the call did"""
+    reference = open_reference(path, threads=threads)
+    try:
+        yield reference
+    finally:
+        if hasattr(reference, "close"):         # (both kinds have it; a stand-in without one is left alone)
+            reference.close()
 
 
 def parse_gzi(data, what=".gzi"):

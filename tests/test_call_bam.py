@@ -440,3 +440,28 @@ def test_gpu_call_bam_from_a_path_and_the_command_line(planted, tmp_path, monkey
     assert call.main([path, fa, "-o", out, "--preset", "ont", "--min_support", "3"]) == 0
     with open(out) as f:
         assert f.read() == text
+
+
+@pytest.mark.gpu
+def test_gpu_call_bam_fills_timings_in_the_order_of_its_phases(ctx, planted, tmp_path):
+    """the keys of `timings` in insertion order, which is the order the command line logs them in: the sums over the tasks, then one lap per
+    phase; ms_sigs only with sigs_dir, ms_index in front with index="build", nothing after ms_tasks when the pool stays empty, and the same
+    keys however many tasks a contig is cut into"""
+    path, ref = planted
+    cp = call.CallParams(Params.ont(min_support=3))
+    tasks = ["ms_inflate", "ms_frame", "ms_tasks"]
+    tail = ["ms_cluster", "ms_tra_gt", "ms_alt_gather", "ms_support_join", "ms_emit"]
+    seen = {}
+    with bam.BamFile(path) as bf:
+        for name, kw in (("defaults", {}), ("sigs", dict(sigs_dir=str(tmp_path))), ("empty", dict(chroms=["chrB"])), ("many tasks", dict(batch=2000))):
+            seen[name] = {}
+            text, _ = call.call_bam(bf, ref, cp, ctx=ctx, timings=seen[name], **kw)
+            assert (text == "") == (name == "empty")
+    seen["build"] = {}
+    call.call_bam(path, ref, cp, ctx=ctx, index="build", timings=seen["build"])
+    assert list(seen["defaults"]) == tasks + ["ms_rebuild"] + tail
+    assert list(seen["sigs"]) == tasks + ["ms_rebuild", "ms_sigs"] + tail
+    assert list(seen["build"]) == ["ms_index"] + tasks + ["ms_rebuild"] + tail
+    assert list(seen["empty"]) == tasks
+    assert list(seen["many tasks"]) == list(seen["defaults"])
+    assert all(isinstance(v, float) and v >= 0 for t in seen.values() for v in t.values())
