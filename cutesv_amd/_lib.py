@@ -132,6 +132,15 @@ SYMBOLS = [
     ("csv_fasta_index_stream_rows", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]),
     ("csv_vcf_ref_ranges", C.c_int, [C.POINTER(_abi.VcfIn), C.c_void_p, C.c_void_p, C.c_void_p]),
     ("csv_vcf_emit_ref", C.c_int, [C.POINTER(_abi.VcfIn), C.c_void_p, C.c_void_p, C.c_char_p, C.c_int64, C.POINTER(C.c_int64), C.c_void_p]),
+    ("csv_vcf_emit_core_host", C.c_int, [C.POINTER(_abi.VcfIn), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.c_void_p]),
+    ("csv_vcf_emit_device", C.c_int, [C.c_void_p, C.POINTER(_abi.VcfIn), C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p,
+                                      C.c_int64, C.POINTER(C.c_int64), C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.c_void_p, C.POINTER(C.c_int32),
+                                      C.POINTER(C.c_double)]),
+    ("csv_vcf_text_info", C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    ("csv_vcf_text_fetch", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]),
+    ("csv_bgzf_deflate_text", C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_double)]),
+    ("csv_tbx_build_rows", C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                     C.POINTER(C.c_int64), C.c_char_p, C.c_int32]),
     ("csv_ref_gather", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(C.c_int64), C.c_void_p, C.c_int32, C.c_void_p]),
     ("csv_ref_gather_host", C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,

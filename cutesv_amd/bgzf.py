@@ -2,6 +2,8 @@
 
     compress(data, ctx=None, route=None)   -> (the file image, ending in the end-of-file block; the block table)
     tabix_vcf(text, block_table)           -> the bytes of the .tbi (itself BGZF-compressed)
+    compress_kept(ctx, kept)               -> the same pair for a text a device emit left on the context
+    tabix_rows(kept, block_table)          -> the .tbi of that text from the emitter's rows: the text never comes down
     python -m cutesv_amd.bgzf FILE [-o OUT] [--tabix] [--route host|device]
 
 The input is cut every 65280 bytes, bgzip's cut: the stored form of such a block is 65311 bytes, so a block that does not compress
@@ -120,6 +122,56 @@ def compress(data, ctx=None, route=None, level=6, threads=HOST_THREADS, timings=
     uoff = np.append(off, np.int64(n))
     isize = np.append(ln.astype(np.uint32), np.uint32(0))
     return image, (uoff, coff, isize)
+
+
+def compress_kept(ctx, kept, timings=None):
+    """csv_bgzf_deflate_text: the text a device emit left on `ctx` (kept: a vcf.KeptText) compressed where it lies -> (image bytes, block
+    table), as compress gives them for the same bytes on route "device"; only the compressed blocks come down"""
+    kept.check()
+    n = kept.n_bytes
+    off, ln = _cuts(n)
+    nb = len(ln)
+    cap = n + 31 * nb
+    out, sizes = np.empty(max(cap, 1), np.uint8), np.zeros(max(nb, 1), np.int32)
+    need, ms = C.c_int64(-1), C.c_double(0)
+    ptr = lambda a: a.ctypes.data if len(a) else None                              # noqa: E731
+    ctx._check(lib().csv_bgzf_deflate_text(ctx._h, nb, ptr(off), ptr(ln), out.ctypes.data, cap, sizes.ctypes.data, C.byref(need), C.byref(ms)))
+    if timings is not None:
+        timings["ms_bgzf_kernels"] = ms.value
+    coff = np.zeros(nb + 1, np.int64)
+    coff[1:] = np.cumsum(sizes[:nb].astype(np.int64))
+    return out[: need.value].tobytes() + EOF_BLOCK, (np.append(off, np.int64(n)), coff, np.append(ln.astype(np.uint32), np.uint32(0)))
+
+
+def tabix_rows_raw(names, rows, text_bytes, block_table):
+    """csv_tbx_build_rows: the .tbi of the records `rows` describes (int64[n, 4]: name index, beg, end, offset) in a text of text_bytes
+    bytes that lies in the blocks of `block_table`, before its own compression - the bytes csv_tbx_build gives over that text"""
+    uoff, coff, isize = (np.ascontiguousarray(a, dt) for a, dt in zip(block_table, (np.int64, np.int64, np.uint32)))
+    if not (len(uoff) == len(coff) == len(isize) >= 1):
+        raise ValueError("the block table needs one row per block, the end-of-file block included")
+    rows = np.ascontiguousarray(rows, np.int64).reshape(-1, 4)
+    enc = [s.encode() for s in names]
+    blob = b"".join(enc)
+    noff = np.zeros(len(enc) + 1, np.int64)
+    if enc:
+        noff[1:] = np.cumsum([len(e) for e in enc])
+    need, err = C.c_int64(0), C.create_string_buffer(512)
+    out = np.zeros(1 << 16, np.uint8)
+    for _ in range(2):
+        rc = lib().csv_tbx_build_rows(blob, noff.ctypes.data, len(enc), rows.ctypes.data if len(rows) else None, len(rows), int(text_bytes), len(uoff), uoff.ctypes.data,
+                                      coff.ctypes.data, isize.ctypes.data, out.ctypes.data, len(out), C.byref(need), err, len(err))
+        if rc:
+            raise BgzfError(err.value.decode() or "csv_tbx_build_rows failed (%d)" % rc)
+        if need.value <= len(out):
+            return out[: need.value].tobytes()
+        out = np.zeros(need.value, np.uint8)
+    raise BgzfError("csv_tbx_build_rows: the size changed between two calls")
+
+
+def tabix_rows(kept, block_table, ctx=None, route="host"):
+    """-> the bytes of out.vcf.gz.tbi for a kept text (vcf.KeptText) whose compressed blocks `block_table` describes (compress_kept's second
+    result): tabix_vcf's bytes, from the rows the emitter wrote beside the text instead of the text"""
+    return compress(tabix_rows_raw(kept.names, kept.rows, kept.n_bytes, block_table), ctx=ctx, route=route)[0]
 
 
 def blocks_of(image):

@@ -131,7 +131,11 @@ DEFAULT_READS_TABLE = "host"    # where call_bam builds the genotyping reads tab
 DEFAULT_FRAME = "host"          # where call_bam frames the BAM's records: "device" is opt-in; DESIGN.md section 29 has the rule for a change
 DEFAULT_INFLATE = "host"        # where call_bam inflates the BAM's BGZF blocks: "device" is opt-in until scripts/inflate_stage.py has been run on an MI355X
                                 # and its figures pass the rule of DESIGN.md section 27
+DEFAULT_EMIT = "host"           # where call_bam writes the record text: "device" is opt-in; DESIGN.md section 38 has the rule for a change
 TRA_GT_MODES = ("alignments", "reads_table", "off")
+
+# what call_bam returns in the text's place with bgzf_prefix=: the BGZF image of prefix + records, its .tbi, the bytes of that text, its records
+Compressed = collections.namedtuple("Compressed", "image tbi text_bytes n_records")
 
 
 def tra_gt_mode(genotype, tra_gt=None):
@@ -183,7 +187,7 @@ class _Shim:
 # call_bam's option keywords, checked and with their defaults filled in (resolve_options; call_bam's docstring has the meanings).  regions: the bed.Regions
 # of include_bed or None; mode: tra_gt_mode's answer; cp: the CallParams; p: cp.resolve with genotype_tra set for mode "reads_table"; reads_dev: the tasks
 # append to the context's device-resident reads table; build_index: index="build" for a path - the session builds what the file lacks
-Options = dataclasses.make_dataclass("Options", "reads_table frame inflate ref_route gates regions mode cp p reads_dev task_cut cut_threads index_format build_index".split(),
+Options = dataclasses.make_dataclass("Options", "reads_table frame inflate ref_route gates regions mode cp p reads_dev task_cut cut_threads index_format build_index emit".split(),
                                      frozen=True)
 
 
@@ -196,7 +200,7 @@ def _route(name, value, default):
 
 
 def resolve_options(bam, index, params, tra_gt=None, include_bed=None, gates=None, reads_table=None, inflate=None, frame=None, task_cut=None, cut_threads=16,
-                    index_format="bai", ref_route=None):
+                    index_format="bai", ref_route=None, emit=None):
     """call_bam's keywords as they arrive -> Options.  Pure: of `bam` it reads whether it is an open reader with an index, it opens nothing
     but a BED file, and DEFAULT_* are read now.  The refusals fire in the order below; `gates` is task_to_pool's to
     check, and the second index check ("none was found for <path>") is the session's, which knows the reader."""
@@ -204,6 +208,7 @@ def resolve_options(bam, index, params, tra_gt=None, include_bed=None, gates=Non
     if index_format not in ("bai", "csi"):
         raise ValueError("index_format must be 'bai' or 'csi', not %r" % (index_format,))
     ref_route = _route("ref_route", ref_route, None)
+    emit = _route("emit", emit, DEFAULT_EMIT)
     if task_cut not in (None, "uniform", "index"):
         raise ValueError("task_cut must be None, 'uniform' or 'index', not %r" % (task_cut,))
     if task_cut == "index" and not (getattr(bam, "has_index", False) if is_reader else index is not False):
@@ -222,7 +227,7 @@ def resolve_options(bam, index, params, tra_gt=None, include_bed=None, gates=Non
         raise ValueError("cut_threads must be a positive integer, not %r" % (cut_threads,))
     p = dataclasses.replace(cp.resolve, genotype_tra=(mode == "reads_table"))
     return Options(reads_table, frame, inflate, ref_route, gates, regions, mode, cp, p, reads_table == "device" and p.genotype, task_cut, cut_threads, index_format,
-                   not is_reader and isinstance(index, str) and index == "build")
+                   not is_reader and isinstance(index, str) and index == "build", emit)
 
 
 @contextlib.contextmanager
@@ -367,9 +372,36 @@ def _gather_alt(ctx, segs, res, t):
     return blob, np.diff(aoff)
 
 
+def _compressed_host(ctx, text):
+    """a text that is on the host (a header without records) as call_bam's Compressed"""
+    from . import bgzf
+    image, table = bgzf.compress(text, ctx=ctx, route="device")
+    return Compressed(image, bgzf.tabix_vcf(text, table, ctx=ctx, route="device"), len(text), 0)
+
+
+def _emit_on_device(ctx, ch, segs, res, t, reference, opts, report_readid, ignore_sequence, svid, as_bytes, bgzf_prefix, timings, laps):
+    """emit="device": the fused form of _gather_alt, support_join and the emitter - picks, clips and support offsets visit the host, the
+    strings they select do not -> call_bam's result"""
+    ins = np.flatnonzero(segs["svtype"][t["call_seg"]] == _abi.INS) if res.n_calls else np.zeros(0, np.int64)
+    from_pool = (np.zeros(0, np.int64), np.zeros(0, np.int64)) if ignore_sequence else (t["seq_pick"][ins], t["bp2"][ins])
+    own = {} if timings is None else timings
+    out, svid = vcf.emit_records(_Shim(ch.names), segs, res, reference, min_size=opts.p.min_size, max_size=opts.p.max_size, genotype=opts.p.genotype,
+                                 report_readid=report_readid, ignore_sequence=ignore_sequence, svid=svid, as_bytes=as_bytes, ref_ctx=ctx, ref_route=opts.ref_route,
+                                 route="device", ctx=ctx, from_pool=from_pool, keep=bgzf_prefix, timings=own)
+    laps.lap("ms_emit")
+    if bgzf_prefix is None:
+        return out, svid
+    from . import bgzf
+    image, table = bgzf.compress_kept(ctx, out, timings=timings)
+    laps.lap("ms_bgzf")
+    tbi = bgzf.tabix_rows(out, table, ctx=ctx, route="device")
+    laps.lap("ms_tabix")
+    return Compressed(image, tbi, out.n_bytes, out.n_records), svid
+
+
 def call_bam(bam, reference, params, ctx=None, chroms=None, batch=10_000_000, report_readid=False, ignore_sequence=False, threads=None, svid=None,
              as_bytes=False, timings=None, tra_gt=None, include_bed=None, gates=None, reads_table=None, sigs_dir=None, inflate=None, index=None, task_cut=None,
-             cut_threads=16, read_stats=None, frame=None, index_format="bai", ref_route=None):
+             cut_threads=16, read_stats=None, frame=None, index_format="bai", ref_route=None, emit=None, bgzf_prefix=None):
     """-> (VCF body text, svid counters [INS, DEL, BND, DUP, INV]).
 
     bam        a path or an open bam.BamFile (coordinate-sorted; no index is needed, one beside the file is used - see `index`)
@@ -418,15 +450,24 @@ def call_bam(bam, reference, params, ctx=None, chroms=None, batch=10_000_000, re
     ref_route  "host" or "device": where the REF bases of a fasta.BgzfReference are gathered (None: the reference's own route, else
                fasta.DEFAULT_REF_ROUTE).  device: on `ctx`.  Same text either way; no other kind of reference
                looks at it.
+    emit       "host" or "device": where the record text is written (None: DEFAULT_EMIT).  device: on `ctx` - the ALT
+               bases and the read names are gathered from the kept rebuild inside the emit and stay on the device, k_vcf_write writes
+               the records; timings gets ms_emit_kernels.  Same text either way.
+    bgzf_prefix  bytes (with emit="device"; ValueError otherwise): the text - these bytes, a VCF header, and the records behind them -
+               stays on the device, is compressed there and indexed from the emitter's rows; the call returns
+               (Compressed(image, tbi, text_bytes, n_records), svid) and the text never comes down.
     read_stats a dict that receives what the tasks' reads cost: compressed_bytes and n_records summed over the tasks, task_records - the
                records each task read, in task order."""
-    opts = resolve_options(bam, index, params, tra_gt, include_bed, gates, reads_table, inflate, frame, task_cut, cut_threads, index_format, ref_route)
+    opts = resolve_options(bam, index, params, tra_gt, include_bed, gates, reads_table, inflate, frame, task_cut, cut_threads, index_format, ref_route, emit)
+    if bgzf_prefix is not None and opts.emit != "device":
+        raise ValueError("bgzf_prefix needs emit='device': the host emitter's text is compressed by bgzf.compress")
     with _session(bam, ctx, opts, threads, index, timings, read_stats) as (bf, ctx, laps):
         ch = _chrom_table(bf, chroms)
         tables = _run_tasks(ctx, bf, ch, _task_list(bf, ch, opts, batch), opts, laps)
         laps.lap("ms_tasks")
         if rebuild.pool_rows(ctx) == 0:
-            return _empty_result(sigs_dir, as_bytes, svid)
+            text, svid = _empty_result(sigs_dir, as_bytes, svid)
+            return (text, svid) if bgzf_prefix is None else (_compressed_host(ctx, bytes(bgzf_prefix)), svid)
         order, rb = _rebuild(ctx, ch.names)
         laps.lap("ms_rebuild")
         if sigs_dir is not None:
@@ -438,6 +479,8 @@ def call_bam(bam, reference, params, ctx=None, chroms=None, batch=10_000_000, re
             _genotype_tra_from_alignments(ctx, segs, res, ch.contig_len, opts.p)
         laps.lap("ms_tra_gt")
         t = res.trimmed()
+        if opts.emit == "device":
+            return _emit_on_device(ctx, ch, segs, res, t, reference, opts, report_readid, ignore_sequence, svid, as_bytes, bgzf_prefix, timings, laps)
         ins_alt = None if ignore_sequence else _gather_alt(ctx, segs, res, t)
         laps.lap("ms_alt_gather")
         rnames = rebuild.support_join(ctx, t["support_off"], t["support_sig"]) if report_readid else None
@@ -457,6 +500,7 @@ def add_route_options(ap):
     ap.add_argument("--inflate", default=None, choices=hd, help="where the BAM's BGZF blocks are inflated (default: %s)" % DEFAULT_INFLATE)
     ap.add_argument("--frame", default=None, choices=hd, help="where the BAM's records are framed (default: %s; device takes the device inflate)" % DEFAULT_FRAME)
     ap.add_argument("--ref_route", default=None, choices=hd, help="where the REF bases of a BGZF-compressed reference are gathered (default: %s)" % fasta.DEFAULT_REF_ROUTE)
+    ap.add_argument("--emit", default=None, choices=hd, help="where the record text is written (default: %s)" % DEFAULT_EMIT)
 
 
 def command_line_tra_gt(tra_gt, genotype):
@@ -491,7 +535,7 @@ def main(argv=None):
     with fasta.opened_reference(a.reference, a.threads) as reference:
         text, svid = call_bam(a.bam, reference, cp, chroms=a.chroms.split(",") if a.chroms else None, batch=a.batch, report_readid=a.report_readid,
                               ignore_sequence=a.ignore_sequence, threads=a.threads, as_bytes=True, tra_gt=command_line_tra_gt(a.tra_gt, a.genotype),
-                              include_bed=a.include_bed, reads_table=a.reads_table, sigs_dir=a.sigs_dir, inflate=a.inflate, frame=a.frame, ref_route=a.ref_route)
+                              include_bed=a.include_bed, reads_table=a.reads_table, sigs_dir=a.sigs_dir, inflate=a.inflate, frame=a.frame, ref_route=a.ref_route, emit=a.emit)
     with open(a.out, "wb") as f:
         f.write(text)
     print("%d records: INS %d, DEL %d, BND %d, DUP %d, INV %d" % (text.count(b"\n"), *svid.tolist()))

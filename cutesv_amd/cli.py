@@ -2,7 +2,7 @@
 
     python -m cutesv_amd BAM REF OUT.vcf WORK_DIR [cuteSV's flags] [--reads_table {host,device}] [--tra_gt MODE] [--inflate {host,device}] [--frame {host,device}]
                          [--task_cut {index,uniform}] [--build_index] [--index_format {bai,csi}] [--bgzf {host,device}]
-                         [--ref_route {host,device}]
+                         [--ref_route {host,device}] [--emit {host,device}]
 
 `parse_args` accepts every option of cuteSV v2.1.4 under the same short and long spellings, with the same destination, type
 and default, so a command line written for cuteSV runs here unchanged; `main` maps them onto call.call_bam and writes a complete
@@ -29,6 +29,7 @@ What differs from cuteSV, on purpose:
   * --read_range is accepted and unused, as on cuteSV's calling path.  -t sizes the BAM reader's inflate threads.
 """
 import argparse
+import contextlib
 import os
 import sys
 import time
@@ -100,7 +101,7 @@ def _parser():
 
 
 def _own_parser():
-    """the nine options cuteSV does not have (five are call.add_route_options'); parsed apart (split_own), so that they shadow no abbreviation of a cuteSV flag"""
+    """the ten options cuteSV does not have (six are call.add_route_options'); parsed apart (split_own), so that they shadow no abbreviation of a cuteSV flag"""
     from . import call
     ap = argparse.ArgumentParser(add_help=False, allow_abbrev=False)
     call.add_route_options(ap)
@@ -112,7 +113,7 @@ def _own_parser():
 
 
 def split_own(argv):
-    """-> (namespace of --reads_table / --tra_gt / --inflate / --frame / --task_cut / --build_index / --index_format / --bgzf / --ref_route, argv without them)"""
+    """-> (namespace of --reads_table / --tra_gt / --inflate / --frame / --task_cut / --build_index / --index_format / --bgzf / --ref_route / --emit, argv without them)"""
     return _own_parser().parse_known_args(list(argv))
 
 
@@ -189,25 +190,43 @@ def main(argv=None):
             task_cut = "index" if bf.has_index else "uniform"
             if not bf.has_index:
                 _log("no BAM index (.bai) beside %s: the tasks are the uniform cut by -b, not cuteSV's cut from the index statistics" % a.input)
-        with fasta.opened_reference(a.reference, a.threads) as reference:           # (plain text or BGZF, as pysam.FastaFile takes either)
+        # a compressed OUT with the device emitter and the device compressor: the header is the prefix of a text that never comes down,
+        # and one context serves the whole run
+        fused = a.output.endswith((".gz", ".bgz")) and own.emit == "device" and own.bgzf == "device"
+        header = vcf.header_text(contigs, a.sample, argv).encode()
+        with contextlib.ExitStack() as stack:
+            reference = stack.enter_context(fasta.opened_reference(a.reference, a.threads))           # (plain text or BGZF, as pysam.FastaFile takes either)
+            more = {}
+            if fused:
+                from . import engine
+                more = dict(ctx=stack.enter_context(contextlib.closing(engine.Context(0))), bgzf_prefix=header)
             body, svid = call.call_bam(source, reference, call_params(a), batch=a.batches, report_readid=a.report_readid,
                                        ignore_sequence=a.ignore_sequence, as_bytes=True, timings=timings, tra_gt=tra_gt, include_bed=a.include_bed,
                                        reads_table=own.reads_table, sigs_dir=sigs_dir, inflate=own.inflate, frame=own.frame, task_cut=task_cut, cut_threads=a.threads,
-                                       threads=a.threads, index=index, index_format=own.index_format, ref_route=own.ref_route)
+                                       threads=a.threads, index=index, index_format=own.index_format, ref_route=own.ref_route, emit=own.emit, **more)
     finally:
         bf.close()
     for key, ms in timings.items():
         _log("%-16s %10.1f ms" % (key[3:] if key.startswith("ms_") else key, ms))
-    text = vcf.header_text(contigs, a.sample, argv).encode() + body
-    if a.output.endswith((".gz", ".bgz")):
-        _write_bgzf(a.output, text, own.bgzf)
-    else:
+    if fused:
+        n_records = body.n_records                            # (the rows count the records: the text is not here to be searched)
         with open(a.output, "wb") as f:
-            f.write(text)
+            f.write(body.image)
+        with open(a.output + ".tbi", "wb") as f:
+            f.write(body.tbi)
+        _log("%-16s %d -> %d bytes on the device, %s.tbi %d bytes" % ("bgzf", body.text_bytes, len(body.image), os.path.basename(a.output), len(body.tbi)))
+    else:
+        n_records = body.count(b"\n")
+        text = header + body
+        if a.output.endswith((".gz", ".bgz")):
+            _write_bgzf(a.output, text, own.bgzf)
+        else:
+            with open(a.output, "wb") as f:
+                f.write(text)
     if sigs_dir is not None and not a.retain_work_dir:
         for t in TYPES:
             path = os.path.join(sigs_dir, t + ".sigs")
             if os.path.exists(path):
                 os.remove(path)
-    _log("%d records (INS %d, DEL %d, BND %d, DUP %d, INV %d) in %.2f s" % (body.count(b"\n"), *svid.tolist(), time.perf_counter() - t0))
+    _log("%d records (INS %d, DEL %d, BND %d, DUP %d, INV %d) in %.2f s" % (n_records, *svid.tolist(), time.perf_counter() - t0))
     return 0

@@ -167,6 +167,21 @@ struct DeflateState {
     void own(std::vector<Buf*>& v) { v.insert(v.end(), {&in, &tab, &slots, &tok, &size, &offs, &image}); }
 };
 
+// The VCF records (stage_vcf_emit.hip.h): work (the view's tables, the emission order, the three count columns, the
+// scan's tile sums and totals), blobs (the REF, ALT and RNAMES bytes the caller sent), alt / rn (the ALT and RNAMES bytes gathered from a
+// kept rebuild, CSV_VCF_*_FROM_POOL) and rows are dead when csv_vcf_emit_device returns.
+// text - the prefix and the records behind it - is dead too unless the call asked for CSV_VCF_KEEP_TEXT: then text[0 .. text_bytes)
+// stays, `kept` is set, and csv_vcf_text_fetch / csv_bgzf_deflate_text read it until the next csv_vcf_emit_device, which drops it
+// (gen counts the emits: a caller's handle is good while the context's gen is its own).  Stand-alone and grow-only; no other stage
+// reads or writes them.
+struct VcfEmitState {
+    Buf work, blobs, alt, rn, text, rows;
+    uint64_t gen = 0;
+    bool kept = false;
+    i64 text_bytes = 0;
+    void own(std::vector<Buf*>& v) { v.insert(v.end(), {&work, &blobs, &alt, &rn, &text, &rows}); }
+};
+
 // Reference gather (stage_ref.hip.h): the inflated bytes of the touched blocks, the block and range tables and
 // the gathered bases of ONE csv_ref_gather call.  Stand-alone and grow-only; dead when the call returns; no other stage reads or
 // writes them (the inflate in front of the gather runs through InflateState's buffers, which are as dead between calls).
@@ -359,7 +374,7 @@ struct csv_ctx {
     BatchState bt; ReadsOrderState ro; ResultState res; TableState tab;
     // ---- the extraction-side stages (their lifetime rules: at the structs)
     PoolState pool; NameState nm; BamState bm; SaState sa; SeqState seq; VcfStrState vs; AlnState al; ReadsTabState rt;
-    RebuildState rb; CigarState cg; SplitState sp; InflateState inf; FrameState fr; IndexBuildState ixb; DeflateState dfl; RefState ref;
+    RebuildState rb; CigarState cg; SplitState sp; InflateState inf; FrameState fr; IndexBuildState ixb; DeflateState dfl; RefState ref; VcfEmitState ve;
 };
 
 namespace {

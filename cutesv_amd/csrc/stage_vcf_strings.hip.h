@@ -14,9 +14,11 @@ static int vs_ready(csv_ctx* c, const char* what)
 // (n_off = picks / calls).  front: bytes of the entry's own tables at the head of vs.work, which upload(base) fills;
 // plan(base, cnt, err) launches the length kernel, offsets(base, cnt, tot, off64) the kernel that makes the caller's offsets
 // from the scanned lengths, copy(base, cnt, blob) the copy kernel.  Nothing is written to `out` unless everything is in order.
+// dev_dst (nullable): the blob is made in THAT buffer and stays there - no capacity to judge, no copy to `out` (csv_vcf_emit_device
+// reads it where it lies); without it the blob passes through vs.out on its way to the host.
 template <class UploadFn, class PlanFn, class OffFn, class CopyFn>
 static int vs_gather(csv_ctx* c, const char* what, i64 n_items, i64 n_off, size_t front, UploadFn upload, PlanFn plan, OffFn offsets, CopyFn copy, char* out, i64 cap,
-                     int64_t* out_off)
+                     int64_t* out_off, Buf* dev_dst)
 {
     VcfStrState& v = c->vs;
     hipStream_t st = c->stream;
@@ -43,11 +45,13 @@ static int vs_gather(csv_ctx* c, const char* what, i64 n_items, i64 n_off, size_
     if (got[0] < 0 || got[0] >= (1ll << 31) - 4096) return fail(c, CSV_E_INVALID, "%s: %lld bytes in one call: split the batch", what, (long long)got[0]);
     memcpy(out_off, off.data(), (size_t)(n_off + 1) * 8);
     const i64 need = out_off[n_off];
-    if (need > cap) return fail(c, CSV_E_CAPACITY, "out: %lld bytes are needed", (long long)need);
+    if (!dev_dst && need > cap) return fail(c, CSV_E_CAPACITY, "out: %lld bytes are needed", (long long)need);
     if (need == 0) return CSV_OK;
-    TRY(reserve(c, v.out, (size_t)need + 8));
-    copy(g, cnt, dp<uint8_t>(v.out));
+    Buf& dst = dev_dst ? *dev_dst : v.out;
+    TRY(reserve(c, dst, (size_t)need + 8));
+    copy(g, cnt, dp<uint8_t>(dst));
     HIP_TRY(c, hipGetLastError());
+    if (dev_dst) return CSV_OK;
     HIP_TRY(c, hipMemcpyAsync(out, v.out.p, (size_t)need, hipMemcpyDeviceToHost, st));
     HIP_TRY(c, hipStreamSynchronize(st));
     return CSV_OK;
@@ -57,11 +61,9 @@ static int vs_gather(csv_ctx* c, const char* what, i64 n_items, i64 n_off, size_
 static int vs_grid_threads(i64 n) { return std::max(1, std::min(div_up(n, 256), 65536)); }
 static int vs_grid_waves(i64 n) { return std::max(1, std::min(div_up(n, 4), 8192)); }
 
-extern "C" {
-
-int csv_seq_alt_gather(csv_ctx* c, int64_t n, const void* pick, const void* clip, int32_t flags, char* out, int64_t cap, int64_t* out_off)
+// the bodies of the two entries; dev_dst: vs_gather's
+static int alt_gather_run(csv_ctx* c, int64_t n, const void* pick, const void* clip, int32_t flags, char* out, int64_t cap, int64_t* out_off, Buf* dev_dst)
 {
-    if (!c) return CSV_E_INVALID;
     if (n < 0 || cap < 0 || !out_off || (n > 0 && (!pick || !clip)) || (cap > 0 && !out) || (flags & ~CSV_OUT_COORD_I32)) return fail(c, CSV_E_INVALID, "bad alt gather");
     if (n >= (1ll << 31) - 4096) return fail(c, CSV_E_INVALID, "csv_seq_alt_gather: too many picks (%lld): split the batch", (long long)n);
     TRY(vs_ready(c, "csv_seq_alt_gather"));
@@ -88,12 +90,12 @@ int csv_seq_alt_gather(csv_ctx* c, int64_t n, const void* pick, const void* clip
         [&](char* g, int4* cnt, int* err) { hipLaunchKernelGGL(k_alt_plan, dim3(vs_grid_threads(n)), dim3(256), 0, st, R, dp<i64>(s.off), (const int*)g, (const int*)(g + o_clip), n, cnt, err); },
         [&](char*, int4* cnt, i64* tot, i64* off) { hipLaunchKernelGGL(k_vs_offsets, dim3(vs_grid_threads(n + 1)), dim3(256), 0, st, cnt, tot, n, off); },
         [&](char* g, int4* cnt, uint8_t* blob) { hipLaunchKernelGGL(k_alt_copy, dim3(vs_grid_waves(n)), dim3(256), 0, st, R, dp<uint8_t>(s.blob), dp<i64>(s.off), (const int*)g, (const int*)(g + o_clip), n, cnt, blob); },
-        out, cap, out_off);
+        out, cap, out_off, dev_dst);
 }
 
-int csv_name_support_join(csv_ctx* c, int64_t n_calls, const int64_t* support_off, const int64_t* support_sig, const int32_t* support_sig32, char* out, int64_t cap, int64_t* out_off)
+static int support_join_run(csv_ctx* c, int64_t n_calls, const int64_t* support_off, const int64_t* support_sig, const int32_t* support_sig32, char* out, int64_t cap, int64_t* out_off,
+                            Buf* dev_dst)
 {
-    if (!c) return CSV_E_INVALID;
     if (n_calls < 0 || cap < 0 || !out_off || !support_off || (cap > 0 && !out) || (support_sig && support_sig32)) return fail(c, CSV_E_INVALID, "bad support join");
     if (n_calls >= (1ll << 30)) return fail(c, CSV_E_INVALID, "csv_name_support_join: too many calls (%lld): split the batch", (long long)n_calls);
     TRY(vs_ready(c, "csv_name_support_join"));
@@ -137,7 +139,21 @@ int csv_name_support_join(csv_ctx* c, int64_t n_calls, const int64_t* support_of
         [&](char* g, int4* cnt, int* err) { hipLaunchKernelGGL(k_join_plan, dim3(vs_grid_threads(ns)), dim3(256), 0, st, R, N, (const int*)g, ns, cnt, err); },
         [&](char* g, int4* cnt, i64* tot, i64* off) { hipLaunchKernelGGL(k_join_call_off, dim3(vs_grid_threads(n_calls + 1)), dim3(256), 0, st, cnt, tot, (const i64*)(g + o_soff), (const i64*)(g + o_bef), n_calls, ns, off); },
         [&](char* g, int4* cnt, uint8_t* blob) { hipLaunchKernelGGL(k_join_copy, dim3(vs_grid_waves(ns)), dim3(256), 0, st, R, N, (const int*)g, (const int*)(g + o_adj), ns, cnt, blob); },
-        out, cap, out_off);
+        out, cap, out_off, dev_dst);
+}
+
+extern "C" {
+
+int csv_seq_alt_gather(csv_ctx* c, int64_t n, const void* pick, const void* clip, int32_t flags, char* out, int64_t cap, int64_t* out_off)
+{
+    if (!c) return CSV_E_INVALID;
+    return alt_gather_run(c, n, pick, clip, flags, out, cap, out_off, nullptr);
+}
+
+int csv_name_support_join(csv_ctx* c, int64_t n_calls, const int64_t* support_off, const int64_t* support_sig, const int32_t* support_sig32, char* out, int64_t cap, int64_t* out_off)
+{
+    if (!c) return CSV_E_INVALID;
+    return support_join_run(c, n_calls, support_off, support_sig, support_sig32, out, cap, out_off, nullptr);
 }
 
 }  // extern "C"

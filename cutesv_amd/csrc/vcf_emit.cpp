@@ -20,6 +20,7 @@
 #include "../../include/cutesv_hip.h"
 #include "soa_access.h"
 #include "ref_core.h"
+#include "vcf_core.h"
 
 namespace {
 
@@ -87,59 +88,28 @@ bool split_gl(const char* s, GlRow& r)
 // by a first pass over the slices.  Order of the text: chromosomes by name rank, records by position, as the reference writes.
 namespace {
 constexpr int64_t VCF_SLICE = 1024;                    // calls per work item
-enum { ID_INS = 0, ID_DEL = 1, ID_BND = 2, ID_DUP = 3, ID_INV = 4 };
+enum { ID_INS = csv::VCF_ID_INS, ID_DEL = csv::VCF_ID_DEL, ID_BND = csv::VCF_ID_BND, ID_DUP = csv::VCF_ID_DUP, ID_INV = csv::VCF_ID_INV };
 
-// size filters of generate_output (cuteSV_genotype.py:265-268, 315-316, 351-352): is the call written, and under which counter
+// size filters of generate_output: the rule is vcf_core.h's (ONE definition, for this emitter and for the device's)
 inline int emitted_id(const csv_vcf_in* in, const csv_batch_out& R, int64_t c)
 {
-    const int type = in->seg[R.call_seg[c]].svtype;
-    if (type == CSV_DEL || type == CSV_INS) {
-        const long long len = csv_soa::bp2(R, c);
-        if ((len > in->max_size && in->max_size != -1) || len < in->min_size) return -1;
-        return type == CSV_INS ? ID_INS : ID_DEL;
-    }
-    if (type == CSV_DUP || type == CSV_INV) {
-        const long long len = csv_soa::bp2(R, c) - csv_soa::bp1(R, c);
-        if (llabs(len) > in->max_size && in->max_size != -1) return -1;
-        return type == CSV_DUP ? ID_DUP : ID_INV;
-    }
-    return ID_BND;
+    return csv::vcf_emitted_id(in->seg[R.call_seg[c]].svtype, csv_soa::bp1(R, c), csv_soa::bp2(R, c), in->min_size, in->max_size);
 }
 
 // where the reference bases of the records come from: the contigs of csv_vcf_in (blob == NULL), or - csv_vcf_emit_ref - per call
 // the bases of its range, back to back: call c's are blob[off[c] .. off[c + 1])
 struct RefSrc { const char* blob; const int64_t* off; };
 
-// The contig bases the record of call c reads: [b, e), of which a DEL record prints [b, slice_e) as its REF.  ONE definition, for
-// emit_slice and for csv_vcf_ref_ranges (generate_output: INS :297, DEL :299-300, DUP :334, INV :360-365, BND :431-434).  Empty
-// (b == e): a call the size filters drop, or INS / DEL under ignore_sequence.  slen: the contig's length, 0 for a contig without
-// sequence; a range that is not inside [0, slen) is the caller's to judge ('N' for BND, CSV_E_INVALID otherwise).
-struct RefRange { int64_t b, e, slice_e; bool bnd; };
+// The contig bases the record of call c reads: [b, e), of which a DEL record prints [b, slice_e) as its REF.  ONE definition
+// (vcf_core.h's vcf_ref_range), for emit_slice, for csv_vcf_ref_ranges and for the device emitter.  Empty (b == e): a call the size
+// filters drop, or INS / DEL under ignore_sequence.  slen: the contig's length, 0 for a contig without sequence; a range that is not
+// inside [0, slen) is the caller's to judge ('N' for BND, CSV_E_INVALID otherwise).
+typedef csv::VcfRefRange RefRange;
 inline RefRange call_ref_range(const csv_vcf_in* in, const csv_batch_out& R, int64_t c, int64_t slen)
 {
-    RefRange r{0, 0, 0, false};
-    if (emitted_id(in, R, c) < 0) return r;
-    const int type = in->seg[R.call_seg[c]].svtype;
-    const long long pos = csv_soa::bp1(R, c), prev = pos - 1 > 0 ? pos - 1 : 0;
-    if (type == CSV_DEL || type == CSV_INS) {
-        if (in->ignore_sequence) return r;
-        r.b = prev; r.e = r.slice_e = prev + 1;                                        // ref_chrom[max(pos-1, 0)] (:297)
-        if (type == CSV_DEL) {
-            long long r1 = pos + csv_soa::bp2(R, c);                                    // slice end, clamped like Python
-            if (r1 > slen) r1 = slen;
-            r.slice_e = r1 > prev ? r1 : prev;
-            if (r1 > r.e) r.e = r1;
-        }
-    } else if (type == CSV_DUP) {
-        r.b = pos; r.e = pos + 1;                                                       // ref_chrom[int(i[2])] (:334)
-    } else if (type == CSV_INV) {
-        const bool pp = strcmp(in->strand_name[csv_soa::call_aux(R, c)], "++") == 0;    // :360-365
-        r.b = pp ? prev : pos; r.e = r.b + 1;
-    } else {
-        const bool nfirst = (csv_soa::call_aux(R, c) & 7) < 2;                          // ALT starts with 'N' (types A/B)
-        r.b = nfirst ? prev : pos; r.e = r.b + 1; r.bnd = true;
-    }
-    return r;
+    const int id = emitted_id(in, R, c), type = in->seg[R.call_seg[c]].svtype;
+    const bool pp = id >= 0 && type == CSV_INV && strcmp(in->strand_name[csv_soa::call_aux(R, c)], "++") == 0;    // :360-365
+    return csv::vcf_ref_range(id, type, in->ignore_sequence != 0, csv_soa::bp1(R, c), csv_soa::bp2(R, c), csv_soa::call_aux(R, c), pp, slen);
 }
 inline bool ref_range_inside(const RefRange& r, int64_t slen) { return r.b >= 0 && r.e <= slen; }
 
@@ -496,6 +466,175 @@ int emit_slice(const csv_vcf_in* in, const RefSrc& src, const int64_t* v, int64_
     return CSV_OK;
 }
 }  // namespace
+
+// ---------------------------------------------------------------------------------------- the record core (vcf_core.h)
+// csv_vcf_in -> the flat view the record core reads, checked: what csv_vcf_emit_core_host and csv_vcf_emit_device (stage_vcf_emit.hip.h)
+// both start with.  Everything the core trusts is judged here, before a byte is written or a kernel launched.
+namespace csv {
+
+int vcf_host_prepare(const csv_vcf_in* in, const char* ref_blob, const int64_t* ref_off, VcfHost& H)
+{
+    if (!in || !in->res || !ref_off || in->n_seg < 0 || in->n_chrom < 0 || in->n_gl < 0) return CSV_E_INVALID;
+    const csv_batch_out& R = *in->res;
+    const int64_t nc = R.n_calls;
+    if (nc < 0 || (nc > 0 && (!R.call_seg || !R.bp1 || !R.bp2 || !R.support || !in->seg))) return CSV_E_INVALID;
+    if ((in->n_chrom > 0 && (!in->chrom_name || !in->chrom_rank)) || (in->n_gl > 0 && (!in->gl_key || !in->gl_str))) return CSV_E_INVALID;
+    const bool with_alt = in->ins_alt && in->ins_alt_off && !in->ignore_sequence, with_rn = in->report_readid && in->rnames && in->rnames_off;
+    // the genotype table: the four strings of every key back to back, and the two facts the records need of them
+    std::vector<int32_t> gl_off{0};
+    std::vector<uint8_t> gl, gl_flag((size_t)in->n_gl, 0);
+    std::vector<char> gl_ok((size_t)in->n_gl, 0);
+    for (int r = 0; r < in->n_gl; r++) {
+        GlRow g{};
+        const bool ok = in->gl_str[r] && split_gl(in->gl_str[r], g);
+        gl_ok[(size_t)r] = ok;
+        const char* f[4] = {g.gt, g.pl, g.gq, g.qual};
+        const size_t fn[4] = {g.gt_n, g.pl_n, g.gq_n, g.qual_n};
+        for (int k = 0; k < 4; k++) {
+            if (ok) gl.insert(gl.end(), f[k], f[k] + fn[k]);
+            gl_off.push_back((int32_t)gl.size());
+        }
+        if (!ok) continue;
+        const bool q5 = !(g.qual_n == 1 && g.qual[0] == '.') && strtod(std::string(g.qual, g.qual_n).c_str(), nullptr) < 5.0;      // (cuteSV_genotype.py:289-292)
+        gl_flag[(size_t)r] = (uint8_t)((q5 ? 1 : 0) | ((g.gt_n == 3 && memcmp(g.gt, "0/0", 3) == 0) ? 2 : 0));
+    }
+    // the calls, every one judged; the columns as the core reads them
+    std::vector<int32_t> c32((size_t)nc * 7);
+    std::vector<int64_t> c64((size_t)nc * 2 + 3 * ((size_t)nc + 1), 0);
+    int32_t *o_seg = c32.data(), *o_aux = o_seg + nc, *o_sup = o_aux + nc, *o_cip = o_sup + nc, *o_cil = o_cip + nc, *o_dr = o_cil + nc, *o_gl = o_dr + nc;
+    int64_t *o_bp1 = c64.data(), *o_bp2 = o_bp1 + nc, *o_ref = o_bp2 + nc, *o_alt = o_ref + nc + 1, *o_rn = o_alt + nc + 1;
+    int n_strand = 0;
+    H.ref_bytes = H.alt_bytes = H.rn_bytes = 0;
+    for (int64_t c = 0; c < nc; c++) {
+        const int k = R.call_seg[c];
+        if (k < 0 || k >= in->n_seg) return CSV_E_INVALID;
+        const csv_segment& sg = in->seg[k];
+        const int ch = sg.chrom;
+        if (ch < 0 || ch >= in->n_chrom) return CSV_E_INVALID;
+        const int aux = csv_soa::call_aux(R, c);
+        o_seg[c] = k; o_aux[c] = aux; o_sup[c] = R.support[c]; o_cip[c] = csv_soa::cipos(R, c); o_cil[c] = csv_soa::cilen(R, c);
+        o_dr[c] = csv_soa::dr(R, c); o_gl[c] = csv_soa::gl_idx(R, c);
+        o_bp1[c] = csv_soa::bp1(R, c); o_bp2[c] = csv_soa::bp2(R, c);
+        const bool gt_on = sg.genotype != 0 && o_gl[c] >= 0;
+        if (gt_on) {                                                                    // (a filtered call's row is looked up too, as emit_slice does)
+            const int32_t* it = std::lower_bound(in->gl_key, in->gl_key + in->n_gl, o_gl[c]);
+            if (it == in->gl_key + in->n_gl || *it != o_gl[c] || !gl_ok[(size_t)(it - in->gl_key)]) return CSV_E_INVALID;
+        }
+        const int id = emitted_id(in, R, c);
+        if (id < 0) continue;
+        if (id == ID_INV) { if (aux < 0 || !in->strand_name || !in->strand_name[aux]) return CSV_E_INVALID; if (aux + 1 > n_strand) n_strand = aux + 1; }
+        if (id == ID_BND && (aux < 0 || (aux >> 3) >= in->n_chrom)) return CSV_E_INVALID;
+        if (in->genotype && gt_on && (o_sup[c] < 0 || o_dr[c] < 0 || (int64_t)o_sup[c] + o_dr[c] <= 0)) return CSV_E_INVALID;
+        const int64_t slen = in->chrom_len ? in->chrom_len[ch] : 0;
+        const RefRange rr = call_ref_range(in, R, c, slen);
+        const bool readable = rr.e > rr.b && ref_range_inside(rr, slen);
+        if (rr.e > rr.b && !readable && !rr.bnd) return CSV_E_INVALID;                   // a reference sequence is missing or too short
+        if (ref_off[c] < 0 || ref_off[c + 1] - ref_off[c] != (readable ? rr.e - rr.b : 0)) return CSV_E_INVALID;
+        o_ref[c] = ref_off[c]; o_ref[c + 1] = ref_off[c + 1];
+        if (ref_off[c + 1] > ref_off[c] && !ref_blob) return CSV_E_INVALID;
+        H.ref_bytes = std::max<vcf_i64>(H.ref_bytes, ref_off[c + 1]);
+        if (with_alt && id == ID_INS) {
+            if (in->ins_alt_off[c] < 0 || in->ins_alt_off[c + 1] < in->ins_alt_off[c]) return CSV_E_INVALID;
+            H.alt_bytes = std::max<vcf_i64>(H.alt_bytes, in->ins_alt_off[c + 1]);
+        }
+        if (with_rn) {
+            if (in->rnames_off[c] < 0 || in->rnames_off[c + 1] < in->rnames_off[c]) return CSV_E_INVALID;
+            H.rn_bytes = std::max<vcf_i64>(H.rn_bytes, in->rnames_off[c + 1]);
+        }
+    }
+    // (the offsets are read per call, c and c + 1: a call that was skipped above keeps its own pair out of the caller's arrays)
+    for (int64_t c = 0; c <= nc; c++) { o_ref[c] = ref_off[c]; if (with_alt) o_alt[c] = in->ins_alt_off[c]; if (with_rn) o_rn[c] = in->rnames_off[c]; }
+    std::vector<int32_t> seg3((size_t)in->n_seg * 3), chrom_off{0}, strand_off{0};
+    for (int k = 0; k < in->n_seg; k++) { seg3[(size_t)k] = in->seg[k].svtype; seg3[(size_t)in->n_seg + k] = in->seg[k].chrom; seg3[(size_t)2 * in->n_seg + k] = in->seg[k].genotype; }
+    std::vector<uint8_t> chrom, strand;
+    std::vector<int64_t> chrom_len((size_t)in->n_chrom, 0);
+    for (int i = 0; i < in->n_chrom; i++) {
+        if (!in->chrom_name[i]) return CSV_E_INVALID;
+        chrom.insert(chrom.end(), in->chrom_name[i], in->chrom_name[i] + strlen(in->chrom_name[i]));
+        chrom_off.push_back((int32_t)chrom.size());
+        if (in->chrom_len) chrom_len[(size_t)i] = in->chrom_len[i];
+    }
+    for (int i = 0; i < n_strand; i++) {
+        const char* s = in->strand_name[i] ? in->strand_name[i] : "";
+        strand.insert(strand.end(), s, s + strlen(s));
+        strand_off.push_back((int32_t)strand.size());
+    }
+    // one block: every table at a multiple of 8
+    struct Part { const void* p; size_t bytes; size_t at; };
+    Part parts[] = {{c64.data(), c64.size() * 8, 0}, {chrom_len.data(), chrom_len.size() * 8, 0}, {c32.data(), c32.size() * 4, 0}, {seg3.data(), seg3.size() * 4, 0},
+                    {chrom_off.data(), chrom_off.size() * 4, 0}, {strand_off.data(), strand_off.size() * 4, 0}, {in->gl_key, (size_t)in->n_gl * 4, 0}, {gl_off.data(), gl_off.size() * 4, 0},
+                    {chrom.data(), chrom.size(), 0}, {strand.data(), strand.size(), 0}, {gl.data(), gl.size(), 0}, {gl_flag.data(), gl_flag.size(), 0}};
+    size_t total = 0;
+    for (Part& q : parts) { q.at = total; total += (q.bytes + 7) & ~(size_t)7; }
+    H.pack.assign(total + 8, 0);
+    for (const Part& q : parts) if (q.bytes) memcpy(H.pack.data() + q.at, q.p, q.bytes);
+    char* b = H.pack.data();
+    VcfView& V = H.view;
+    V = VcfView{};
+    V.n_calls = nc;
+    const vcf_i64* p64 = (const vcf_i64*)(b + parts[0].at);
+    V.bp1 = p64; V.bp2 = p64 + nc; V.ref_off = p64 + 2 * nc; V.alt_off = with_alt ? p64 + 3 * nc + 1 : nullptr; V.rn_off = with_rn ? p64 + 4 * nc + 2 : nullptr;
+    V.chrom_len = (const vcf_i64*)(b + parts[1].at);
+    const int32_t* p32 = (const int32_t*)(b + parts[2].at);
+    V.call_seg = p32; V.call_aux = p32 + nc; V.support = p32 + 2 * nc; V.cipos = p32 + 3 * nc; V.cilen = p32 + 4 * nc; V.dr = p32 + 5 * nc; V.gl_idx = p32 + 6 * nc;
+    const int32_t* ps = (const int32_t*)(b + parts[3].at);
+    V.seg_type = ps; V.seg_chrom = ps + in->n_seg; V.seg_gt = ps + 2 * in->n_seg;
+    V.n_chrom = in->n_chrom; V.chrom_off = (const int32_t*)(b + parts[4].at); V.chrom = (const uint8_t*)(b + parts[8].at);
+    V.n_strand = n_strand; V.strand_off = (const int32_t*)(b + parts[5].at); V.strand = (const uint8_t*)(b + parts[9].at);
+    V.n_gl = in->n_gl; V.gl_key = (const int32_t*)(b + parts[6].at); V.gl_off = (const int32_t*)(b + parts[7].at); V.gl = (const uint8_t*)(b + parts[10].at);
+    V.gl_flag = (const uint8_t*)(b + parts[11].at);
+    V.ref = (const uint8_t*)ref_blob; V.alt = (const uint8_t*)in->ins_alt; V.rn = (const uint8_t*)in->rnames;
+    V.min_size = in->min_size; V.max_size = in->max_size; V.genotype = in->genotype; V.report_readid = in->report_readid; V.ignore_sequence = in->ignore_sequence;
+    // emission order, as vcf_emit_impl makes it: a counting sort by chromosome, the chromosomes by rank, a stable sort by bp1 in each
+    std::vector<int64_t> coff((size_t)in->n_chrom + 1, 0), idx((size_t)nc);
+    for (int64_t c = 0; c < nc; c++) coff[(size_t)in->seg[R.call_seg[c]].chrom + 1]++;
+    for (int i = 0; i < in->n_chrom; i++) coff[(size_t)i + 1] += coff[(size_t)i];
+    {
+        std::vector<int64_t> fill(coff.begin(), coff.end() - 1);
+        for (int64_t c = 0; c < nc; c++) idx[(size_t)fill[(size_t)in->seg[R.call_seg[c]].chrom]++] = c;
+    }
+    std::vector<int> chroms(in->n_chrom);
+    for (int i = 0; i < in->n_chrom; i++) chroms[i] = i;
+    std::sort(chroms.begin(), chroms.end(), [&](int x, int y) { return in->chrom_rank[x] < in->chrom_rank[y]; });
+    H.order.clear();
+    H.order.reserve((size_t)nc);
+    for (int ch : chroms) {
+        std::stable_sort(idx.begin() + coff[(size_t)ch], idx.begin() + coff[(size_t)ch + 1], [&](int64_t x, int64_t y) { return o_bp1[x] < o_bp1[y]; });
+        H.order.insert(H.order.end(), idx.begin() + coff[(size_t)ch], idx.begin() + coff[(size_t)ch + 1]);
+    }
+    return CSV_OK;
+}
+
+VcfView vcf_view_moved(const VcfHost& H, const char* base, const uint8_t* ref, const uint8_t* alt, const uint8_t* rn)
+{
+    VcfView V = H.view;
+    const char* old = H.pack.data();
+    auto mv = [&](auto*& p) { if (p) p = (std::remove_reference_t<decltype(p)>)(base + ((const char*)p - old)); };
+    mv(V.call_seg); mv(V.call_aux); mv(V.support); mv(V.cipos); mv(V.cilen); mv(V.dr); mv(V.gl_idx); mv(V.bp1); mv(V.bp2); mv(V.ref_off); mv(V.alt_off); mv(V.rn_off);
+    mv(V.seg_type); mv(V.seg_chrom); mv(V.seg_gt); mv(V.chrom_off); mv(V.chrom); mv(V.chrom_len); mv(V.strand_off); mv(V.strand); mv(V.gl_key); mv(V.gl_off); mv(V.gl); mv(V.gl_flag);
+    V.ref = ref; V.alt = alt; V.rn = rn;
+    return V;
+}
+
+}  // namespace csv
+
+// csv_vcf_emit_ref's records from the record core with one lane and no context: the host form of csv_vcf_emit_device
+extern "C" int csv_vcf_emit_core_host(const csv_vcf_in* in, const char* ref_blob, const int64_t* ref_off, char* out, int64_t cap, int64_t* n_written, int64_t* svid)
+{
+    if (!n_written || !svid) return CSV_E_INVALID;
+    csv::VcfHost H;
+    const int rc = csv::vcf_host_prepare(in, ref_blob, ref_off, H);
+    if (rc != CSV_OK) return rc;
+    const csv::VcfView& V = H.view;
+    int64_t run[5] = {svid[0], svid[1], svid[2], svid[3], svid[4]}, total = 0;
+    for (int64_t c : H.order) { const int id = csv::vcf_call_id(V, c); if (id >= 0) total += csv::vcf_record_len(V, c, id, run[id]++); }
+    *n_written = total;
+    if (!out || total > cap) return CSV_E_CAPACITY;
+    int64_t at = 0, sv[5] = {svid[0], svid[1], svid[2], svid[3], svid[4]};
+    for (int64_t c : H.order) { const int id = csv::vcf_call_id(V, c); if (id >= 0) at = csv::vcf_record_write(V, c, id, sv[id]++, (uint8_t*)out, at, 0, 1, nullptr); }
+    for (int t = 0; t < 5; t++) svid[t] = run[t];
+    return CSV_OK;
+}
 
 // ---------------------------------------------------------------------------------------- FASTA index
 // The `.fai` of a FASTA file held in memory (mmap): per contig its name (up to the first white space of the header), length,

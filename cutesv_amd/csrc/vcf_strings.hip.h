@@ -21,6 +21,7 @@
 #include <stdint.h>
 #include "wave.hip.h"
 #include "names.hip.h"
+#include "vcf_core.h"
 
 namespace csv {
 
@@ -259,6 +260,64 @@ __global__ __launch_bounds__(256) void k_sigs_write(StRows R, VsNames N, StTable
             o += aux;
         }
         st_put_byte(out, o, lane, '\n');
+    }
+}
+
+// ------------------------------------------------------------------------------------ the VCF records
+// The record text itself: the calls of a batch, as the flat view of vcf_core.h, become the lines of the VCF body
+// in emission order (`order`: slot q writes call order[q]).  The record of a call is vcf_core.h's vcf_record, the one source the host
+// form runs with one lane.
+//   k_vcf_plan      one thread per slot: the emitted id (-1: a size filter drops the call) as the six counts {INS, DEL, BND} / {DUP, INV,
+//                   emitted}.  A record's length depends on the digits of its SVID, and the SVID is the count of emitted records of its
+//                   type in front of it: so the counts go through the scan of scan.hip.h first ...
+//   k_vcf_len       ... then one thread per slot computes the record's length (vcf_record_len: a sink that only counts), and the lengths
+//                   are scanned
+//   k_vcf_write     one wavefront per slot: every piece of the record is stored by the 64 lanes, neighbouring lanes neighbouring bytes - the
+//                   REF bases through the IUPAC table, a number as one digit per lane - looping over long pieces (a DEL's REF may be 100
+//                   kb); lane 0 writes the record's row {chromosome, beg, end, offset of the record in the text}
+// All three walk their slots with a grid-stride loop (the host caps the grid).  Bounds: the view was judged on the host before anything
+// is launched (vcf_host_prepare): every index lies inside its table, every call's bytes inside its blob.  A record is written to
+// out[prefix + off .. prefix + off + len) with off, len from the same vcf_record that writes it, inside the prefix + total bytes the host
+// reserved; its row to rows[4 r .. 4 r + 4), r = the emitted records in front of it < their total.
+struct VeArgs { VcfView V; const i64* order; i64 n; i64 sv_ins, sv_del, sv_bnd, sv_dup, sv_inv; i64 prefix; };
+
+__global__ __launch_bounds__(256) void k_vcf_plan(VeArgs A, int4* cnt_a, int4* cnt_b)
+{
+    for (i64 q = (i64)blockIdx.x * 256 + threadIdx.x; q < A.n; q += (i64)gridDim.x * 256) {
+        const int id = vcf_call_id(A.V, A.order[q]);
+        cnt_a[q] = make_int4(id == VCF_ID_INS, id == VCF_ID_DEL, id == VCF_ID_BND, 0);
+        cnt_b[q] = make_int4(id == VCF_ID_DUP, id == VCF_ID_INV, id >= 0, 0);
+    }
+}
+
+// the SVID of slot q's record: the caller's counter of its type plus the records of that type in front of it (cnt_a / cnt_b scanned)
+__device__ __forceinline__ i64 ve_svid(const VeArgs& A, const int4* cnt_a, const int4* cnt_b, i64 q, int id)
+{
+    const int4 a = cnt_a[q], b = cnt_b[q];
+    return id == VCF_ID_INS ? A.sv_ins + a.x : id == VCF_ID_DEL ? A.sv_del + a.y : id == VCF_ID_BND ? A.sv_bnd + a.z : id == VCF_ID_DUP ? A.sv_dup + b.x : A.sv_inv + b.y;
+}
+
+__global__ __launch_bounds__(256) void k_vcf_len(VeArgs A, const int4* cnt_a, const int4* cnt_b, int4* cnt_c)
+{
+    for (i64 q = (i64)blockIdx.x * 256 + threadIdx.x; q < A.n; q += (i64)gridDim.x * 256) {
+        const i64 c = A.order[q];
+        const int id = vcf_call_id(A.V, c);
+        cnt_c[q] = make_int4(id < 0 ? 0 : (int)vcf_record_len(A.V, c, id, ve_svid(A, cnt_a, cnt_b, q, id)), 0, 0, 0);
+    }
+}
+
+// one wavefront per slot (launched only when the text fits 31 bits); cnt_a / cnt_b / cnt_c hold the exclusive prefixes
+__global__ __launch_bounds__(256) void k_vcf_write(VeArgs A, const int4* cnt_a, const int4* cnt_b, const int4* cnt_c, uint8_t* out, i64* rows)
+{
+    const int lane = threadIdx.x & 63;
+    for (i64 q = (i64)blockIdx.x * 4 + (threadIdx.x >> 6); q < A.n; q += (i64)gridDim.x * 4) {
+        const i64 c = A.order[q];
+        const int id = vcf_call_id(A.V, c);
+        if (id < 0) continue;
+        const i64 o = A.prefix + (i64)cnt_c[q].x;
+        VcfRow row;
+        vcf_record_write(A.V, c, id, ve_svid(A, cnt_a, cnt_b, q, id), out, o, lane, 64, &row);
+        if (lane < 4) rows[4 * (i64)cnt_b[q].z + lane] = lane == 0 ? (i64)row.chrom : lane == 1 ? row.beg : lane == 2 ? row.end : o;
     }
 }
 

@@ -30,8 +30,58 @@ _TLS = threading.local()          # the recycled output buffer is per thread: cs
                                   # concurrent callers (a second caller gets a worker team of its own), so must its caller's buffer
 
 
+ROUTES = ("host", "device", "core")
+DEFAULT_ROUTE = "host"            # the rule of DESIGN.md section 38 decides a change; its measurement has not been made
+KEEP_TEXT, ALT_FROM_POOL, RNAMES_FROM_POOL = 1, 2, 4        # CSV_VCF_* of include/cutesv_hip.h
+
+
+class KeptText:
+    """The text csv_vcf_emit_device left in device memory (emit_records(route="device", keep=prefix)): n_bytes - prefix and records;
+    n_records; rows int64[n_records, 4] - {name index, beg, end, offset of the record in the text}; names - the chromosomes that
+    emitted a record, in order of first appearance; fetch() - the bytes, brought down.  Good until the context's next device emit:
+    after that every use raises."""
+
+    def __init__(self, ctx, n_bytes, rows, names, ms_kernels):
+        self.ctx, self.n_bytes, self.rows, self.names, self.ms_kernels = ctx, int(n_bytes), rows, list(names), ms_kernels
+        self.n_records = len(rows)
+        self._gen = self._info()[0]
+
+    def _info(self):
+        gen, nbytes = C.c_int64(0), C.c_int64(0)
+        self.ctx._check(lib().csv_vcf_text_info(self.ctx._h, C.byref(gen), C.byref(nbytes)))
+        return gen.value, nbytes.value
+
+    def check(self):
+        if self._info() != (self._gen, self.n_bytes):
+            raise RuntimeError("the kept VCF text is gone: the context has emitted again since")
+
+    def fetch(self):
+        self.check()
+        out, need = np.empty(max(self.n_bytes, 1), np.uint8), C.c_int64(0)
+        self.ctx._check(lib().csv_vcf_text_fetch(self.ctx._h, out.ctypes.data, self.n_bytes, C.byref(need)))
+        return out[:need.value].tobytes()
+
+
+def _host_ref_gather(store, reference, seq_bytes, chrom, beg, end):
+    """the bases of the ranges csv_vcf_ref_ranges gave, back to back, for a fasta.Reference or {name: sequence} -> (blob uint8, off int64[n + 1])"""
+    from .fasta import Reference
+    n = len(beg)
+    off = np.zeros(n + 1, np.int64)
+    np.cumsum(end - beg, out=off[1:])
+    parts = []
+    mapped = isinstance(reference, Reference)
+    for c in np.flatnonzero(end > beg).tolist():
+        ch, b, e = int(chrom[c]), int(beg[c]), int(end[c])
+        parts.append(reference.fetch(store.chroms[ch], b, e).encode() if mapped else seq_bytes[ch][b:e])
+    blob = np.frombuffer(b"".join(parts), np.uint8)
+    if len(blob) != int(off[-1]):
+        raise RuntimeError("csv_vcf_emit: a reference sequence is missing or too short")
+    return blob, off
+
+
 def emit_records(store, segments, res, reference, min_size=30, max_size=100000, genotype=False, report_readid=False,
-                 ignore_sequence=False, svid=None, as_bytes=False, as_view=False, ins_alt=None, rnames=None, ref_ctx=None, ref_route=None):
+                 ignore_sequence=False, svid=None, as_bytes=False, as_view=False, ins_alt=None, rnames=None, ref_ctx=None, ref_route=None,
+                 route=None, ctx=None, from_pool=None, keep=None, timings=None):
     """calls of one batch -> (VCF body text, svid counters).
 
     segments   the csv_segment records the batch was run with (HostBatch.segments)
@@ -52,7 +102,24 @@ def emit_records(store, segments, res, reference, min_size=30, max_size=100000, 
     rnames     (blob, off int64[n_calls + 1]): the RNAMES text of every call (rebuild.support_join) - `store.names` is not
                looked at; only read with report_readid.  ValueError unless the offsets cover exactly the calls and the blob
     With ins_alt / rnames `store` needs nothing but `chroms` and `strands`.
+    route      None (DEFAULT_ROUTE), "host" - csv_vcf_emit / csv_vcf_emit_ref, the thread team; "device" - csv_vcf_emit_device on `ctx`
+               (an engine.Context): the records are written by k_vcf_write; "core" - csv_vcf_emit_core_host, the
+               device's record rule with one lane on the host, for checks.  The text is the same on every route.  On "device" and "core"
+               the REF bases of every kind of reference come per call: csv_vcf_ref_ranges plus the reference's own gather.
+    from_pool  (route="device") (pick, clip): the ALT bases of the INS calls and, with report_readid, the RNAMES text are gathered from
+               the context's kept pool rebuild inside the call and never come down - pick / clip per INS call in call order, as
+               rebuild.alt_gather takes them (None with ignore_sequence); the read names come from the result's support lists
+    keep       (route="device") bytes that stand in front of the records (a VCF header; b"" for none): the text stays in device memory
+               and a KeptText comes back in its place - (KeptText, svid)
+    timings    a dict that receives ms_emit_kernels on the device route
     """
+    route = DEFAULT_ROUTE if route is None else route
+    if route not in ROUTES:
+        raise ValueError("route must be one of %s, not %r" % (", ".join(ROUTES), route))
+    if route == "device" and ctx is None:
+        raise ValueError("emit_records: route='device' needs ctx")
+    if route != "device" and (from_pool is not None or keep is not None):
+        raise ValueError("emit_records: from_pool and keep belong to route='device'")
     L = lib()
     t = res.trimmed()
     n = res.n_calls
@@ -86,7 +153,13 @@ def emit_records(store, segments, res, reference, min_size=30, max_size=100000, 
     # inserted sequences of INS calls, sliced to SVLEN
     alt_blob, alt_off = None, None
     rn_blob, rn_off = None, None
-    if ins_alt is not None and not ignore_sequence:
+    pooled = from_pool is not None
+    if pooled:
+        if ins_alt is not None or rnames is not None:
+            raise ValueError("emit_records: from_pool takes the place of ins_alt and rnames")
+        if n and report_readid and (t["support_sig"] is None or t["support_off"] is None):
+            raise ValueError("emit_records: report_readid needs the support lists (the result was made with CSV_OUT_NO_SUPPORT_LIST)")
+    elif ins_alt is not None and not ignore_sequence:
         ins = np.flatnonzero(call_type == _abi.INS)
         alt_blob, took = ins_alt
         took = np.asarray(took, np.int64)
@@ -106,7 +179,7 @@ def emit_records(store, segments, res, reference, min_size=30, max_size=100000, 
         rn_blob = bytes(rn_blob)
     elif n and report_readid and (t["support_sig"] is None or t["support_off"] is None):
         raise ValueError("emit_records: report_readid needs the support lists (the result was made with CSV_OUT_NO_SUPPORT_LIST)")
-    if ins_alt is None and n and not ignore_sequence and (call_type == _abi.INS).any():
+    if not pooled and ins_alt is None and n and not ignore_sequence and (call_type == _abi.INS).any():
         from . import _cols_native as cn                     # (built by the same make as the library; no Python fallback)
         ins = np.flatnonzero(call_type == _abi.INS)
         pick = np.ascontiguousarray(t["seq_pick"][ins], np.int64)
@@ -125,7 +198,7 @@ def emit_records(store, segments, res, reference, min_size=30, max_size=100000, 
         alt_off = np.zeros(n + 1, np.int64)
         alt_off[ins + 1] = took
         np.cumsum(alt_off, out=alt_off)
-    if rnames is None and n and report_readid:
+    if not pooled and rnames is None and n and report_readid:
         nm = store.names.take(store.read_id[t["support_sig"]])
         so = t["support_off"].tolist()
         rn_blob, rn_off = _csr([",".join(nm[so[c]:so[c + 1]]) for c in range(n)])
@@ -145,16 +218,22 @@ def emit_records(store, segments, res, reference, min_size=30, max_size=100000, 
                 min_size=min_size, max_size=max_size, genotype=int(bool(genotype)), report_readid=int(bool(report_readid)),
                 ignore_sequence=int(bool(ignore_sequence)))
     ref_blob = ref_off = None
-    if bgzf_ref:
+    per_call = bgzf_ref or route != "host"
+    if per_call:
         beg, end, chrom = np.zeros(n, np.int64), np.zeros(n, np.int64), np.zeros(n, np.int32)
         rc = L.csv_vcf_ref_ranges(C.byref(vin), beg.ctypes.data, end.ctypes.data, chrom.ctypes.data)
         if rc != _abi.OK:
             raise RuntimeError("csv_vcf_emit: %s (a reference sequence is missing or too short?)" % _abi.ERR_NAME.get(rc, rc))
         ref_blob, ref_off = np.zeros(0, np.uint8), np.zeros(n + 1, np.int64)
-        if (end > beg).any():                              # (an empty range reads nothing of any contig: it is asked of contig 0)
+        if not bgzf_ref:
+            ref_blob, ref_off = _host_ref_gather(store, reference, seq_bytes, chrom, beg, end)
+        elif (end > beg).any():                            # (an empty range reads nothing of any contig: it is asked of contig 0)
             idx = np.where(end > beg, ref_idx[chrom], 0)
             ref_blob, ref_off = reference.gather(idx, beg, end, ctx=ref_ctx, route=ref_route)
             ref_off = np.ascontiguousarray(ref_off, np.int64)
+    if route == "device":
+        return _emit_device(L, ctx, vin, n, ref_blob, ref_off, store, svid, from_pool, keep, as_bytes, timings,
+                            (len(alt_blob) if alt_blob else 0) + (len(rn_blob) if rn_blob else 0), ignore_sequence)
     cap = 256 * max(n, 1) + (len(alt_blob) if alt_blob else 0) + (len(rn_blob) if rn_blob else 0) + (len(ref_blob) if ref_blob is not None else 0) + 4096
     for _ in range(2):
         buf = getattr(_TLS, "buf", None)
@@ -162,7 +241,9 @@ def emit_records(store, segments, res, reference, min_size=30, max_size=100000, 
             buf = _TLS.buf = np.empty(cap, np.uint8)
         need = C.c_int64(0)
         sv = svid.copy()
-        if bgzf_ref:
+        if route == "core":
+            rc = L.csv_vcf_emit_core_host(C.byref(vin), ref_blob.ctypes.data if len(ref_blob) else None, ref_off.ctypes.data, buf.ctypes.data, len(buf), C.byref(need), sv.ctypes.data)
+        elif bgzf_ref:
             rc = L.csv_vcf_emit_ref(C.byref(vin), ref_blob.ctypes.data if len(ref_blob) else None, ref_off.ctypes.data, C.cast(buf.ctypes.data, C.c_char_p), len(buf), C.byref(need),
                                     sv.ctypes.data)
         else:
@@ -178,6 +259,44 @@ def emit_records(store, segments, res, reference, min_size=30, max_size=100000, 
         raw = buf[:need.value].tobytes()
         return (raw if as_bytes else raw.decode()), svid
     raise RuntimeError("csv_vcf_emit: capacity retry failed")
+
+
+def _emit_device(L, ctx, vin, n, ref_blob, ref_off, store, svid, from_pool, keep, as_bytes, timings, string_bytes, ignore_sequence):
+    """csv_vcf_emit_device with its capacity negotiated -> (text or KeptText, svid)"""
+    flags, n_pick, pick, clip = 0, 0, None, None
+    if from_pool is not None:
+        flags |= RNAMES_FROM_POOL
+        if not ignore_sequence:
+            pick, clip = (np.ascontiguousarray(a, np.int64) for a in from_pool)
+            if pick.shape != clip.shape or pick.ndim != 1:
+                raise ValueError("emit_records: from_pool must be (pick, clip), one entry each per INS call")
+            flags |= ALT_FROM_POOL
+            n_pick = len(pick)
+    prefix = b"" if keep is None else bytes(keep)
+    if keep is not None:
+        flags |= KEEP_TEXT
+    rows, name_chrom = np.zeros((max(n, 1), 4), np.int64), np.zeros(max(len(store.chroms), 1), np.int32)
+    n_rows, n_names, need, ms = C.c_int64(0), C.c_int32(0), C.c_int64(0), C.c_double(0)
+    ptr = lambda a: a.ctypes.data if a is not None and len(a) else None            # noqa: E731
+    cap = 0 if keep is not None else 256 * max(n, 1) + string_bytes + len(ref_blob) + 4096
+    for _ in range(3):
+        buf = None if keep is not None else np.empty(cap, np.uint8)
+        sv = svid.copy()
+        rc = L.csv_vcf_emit_device(ctx._h, C.byref(vin), ptr(ref_blob), ref_off.ctypes.data, n_pick, ptr(pick), ptr(clip), prefix if prefix else None, len(prefix), flags,
+                                   None if buf is None else buf.ctypes.data, cap, C.byref(need), sv.ctypes.data, rows.ctypes.data, len(rows), C.byref(n_rows),
+                                   name_chrom.ctypes.data, C.byref(n_names), C.byref(ms))
+        if rc == _abi.E_CAPACITY and keep is None:
+            cap = need.value + 16
+            continue
+        ctx._check(rc)
+        svid[:] = sv
+        if timings is not None:
+            timings["ms_emit_kernels"] = timings.get("ms_emit_kernels", 0.0) + ms.value
+        if keep is not None:
+            return KeptText(ctx, need.value, rows[:n_rows.value].copy(), [store.chroms[i] for i in name_chrom[:n_names.value].tolist()], ms.value), svid
+        raw = buf[:need.value].tobytes()
+        return (raw if as_bytes else raw.decode()), svid
+    raise RuntimeError("csv_vcf_emit_device: capacity retry failed")
 
 
 # ------------------------------------------------------------------------------------ the header

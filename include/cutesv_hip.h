@@ -849,6 +849,30 @@ int csv_fasta_index_stream_rows(csv_fai_stream* s, const int64_t* rows, int64_t 
 int csv_vcf_ref_ranges(const csv_vcf_in* in, int64_t* beg, int64_t* end, int32_t* chrom);
 int csv_vcf_emit_ref(const csv_vcf_in* in, const char* ref_blob, const int64_t* ref_off, char* out, int64_t cap, int64_t* n_written, int64_t* svid);
 
+/* The records on the device.  One rule writes a record for the host and for the device (csrc/vcf_core.h); these
+ * entries give csv_vcf_emit_ref's text, byte for byte.
+ * csv_vcf_emit_core_host: the rule with one lane and no context - csv_vcf_emit_ref's arguments and contract.
+ * csv_vcf_emit_device: the same on the GPU.  `in` as it is (chrom_seq and the line arrays are not read); REF bases per call as
+ *   csv_vcf_emit_ref takes them.  ALT and RNAMES come from the CSR blobs of `in` (uploaded), or - CSV_VCF_ALT_FROM_POOL, with pick / clip
+ *   per INS call in call order as csv_seq_alt_gather takes them (int64); CSV_VCF_RNAMES_FROM_POOL, with the support lists of in->res -
+ *   from the context's kept pool rebuild: csv_seq_alt_gather's and csv_name_support_join's kernels run, their blobs stay on the device,
+ *   and their rules and refusals hold with the same texts.  prefix: bytes that stand in front of the records (a VCF header); out, rows'
+ *   offsets and *n_written cover prefix + records.  rows (nullable): four int64 per emitted record, in emission order - {name index,
+ *   beg, end, offset of the record} - the name index counting the chromosomes that emit a record in order of first appearance
+ *   (name_chrom[k] <- the chromosome of name k, *n_names <- their number), beg / end the tabix interval of csv_tbx_build's rule.
+ *   CSV_VCF_KEEP_TEXT: the text stays in the context (out may be NULL) until the next csv_vcf_emit_device; csv_vcf_text_fetch brings it
+ *   down, csv_bgzf_deflate_text compresses it there, csv_vcf_text_info tells how many emits the context has seen and the kept bytes.
+ *   CSV_OK; CSV_E_CAPACITY with the need in *n_written / *n_rows and nothing stored; CSV_E_INVALID with nothing stored wherever the host
+ *   emitter says it, for what it would read outside its tables, and for a text of 2^31 - 4096 bytes or more.  Everything is judged on the
+ *   host before a kernel is launched; svid advances only on success. */
+enum { CSV_VCF_KEEP_TEXT = 1, CSV_VCF_ALT_FROM_POOL = 2, CSV_VCF_RNAMES_FROM_POOL = 4 };
+int csv_vcf_emit_core_host(const csv_vcf_in* in, const char* ref_blob, const int64_t* ref_off, char* out, int64_t cap, int64_t* n_written, int64_t* svid);
+int csv_vcf_emit_device(csv_ctx* ctx, const csv_vcf_in* in, const char* ref_blob, const int64_t* ref_off, int64_t n_pick, const int64_t* pick, const int64_t* clip,
+                        const char* prefix, int64_t prefix_bytes, int32_t flags, char* out, int64_t cap, int64_t* n_written, int64_t* svid /* [5] */, int64_t* rows,
+                        int64_t rows_cap, int64_t* n_rows, int32_t* name_chrom, int32_t* n_names, double* ms_kernels);
+int csv_vcf_text_info(csv_ctx* ctx, int64_t* gen, int64_t* bytes);
+int csv_vcf_text_fetch(csv_ctx* ctx, char* out, int64_t cap, int64_t* need);
+
 /* ---------------------------------------------------------------------------------------------
  * Host-side row builder: the structure-of-arrays result -> the row lists the reference's resolvers return
  * (DEL 13 fields INDEL:207-219 / 464-478, INS 14 INDEL:419-432, DUP 11 DUP:121-131 / 170-180, INV 12 INV:145-156 /
@@ -1070,6 +1094,14 @@ int csv_bgzf_deflate_host(const uint8_t* in, int64_t in_bytes, int32_t n_blocks,
  * reappears, a position at or beyond 2^29, a line without a numeric POS - named by the ordinal of the data line, from 0. */
 int csv_tbx_build(const char* text, int64_t text_bytes, int64_t n_blocks, const int64_t* uoff, const int64_t* coff, const uint32_t* isize,
                   uint8_t* out, int64_t out_cap, int64_t* out_bytes, char* err, int32_t err_cap);
+/* csv_bgzf_deflate with the context's kept VCF text (CSV_VCF_KEEP_TEXT) as its input; CSV_E_INVALID also when there is none or a range
+ * lies outside it.  csv_tbx_build_rows: pass 2 of csv_tbx_build fed from csv_vcf_emit_device's rows instead of the text - names back to
+ * back with n_names + 1 offsets, record r's bytes end where record r + 1 starts, the last at text_bytes - the same bytes, the same
+ * refusals by ordinal. */
+int csv_bgzf_deflate_text(csv_ctx* ctx, int32_t n_blocks, const int64_t* in_off, const int32_t* in_len, uint8_t* out, int64_t out_cap, int32_t* block_bytes,
+                          int64_t* out_bytes, double* ms_kernels);
+int csv_tbx_build_rows(const char* names, const int64_t* name_off, int32_t n_names, const int64_t* rows, int64_t n_rows, int64_t text_bytes, int64_t n_blocks,
+                       const int64_t* uoff, const int64_t* coff, const uint32_t* isize, uint8_t* out, int64_t out_cap, int64_t* out_bytes, char* err, int32_t err_cap);
 
 /* Reference bases out of a BGZF-compressed FASTA: n_ranges base ranges, cut out of the n_blocks BGZF blocks
  * they touch, on the device.  Block k: the raw-deflate payload comp[in_off[k] .. + in_len[k]), which inflates to the isize[k] (0 ..
