@@ -104,6 +104,10 @@ SYMBOLS = [
     ("csv_bam_index_build_csi", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]),
     ("csv_bam_index_payload", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]),
     ("csv_bam_index_build_stats_csi", C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_double)]),
+    ("csv_bam_sort", C.c_int, [C.c_void_p, C.c_void_p, C.c_char_p, C.c_int64, C.c_int32, C.c_int32]),
+    ("csv_bam_sort_host", C.c_int, [C.c_void_p, C.c_char_p, C.c_int64, C.c_int32, C.c_int32]),
+    ("csv_bam_sort_stats", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("csv_bam_sort_blocks", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]),
     ("csv_bgzf_inflate", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32,
                                    C.c_void_p, C.POINTER(C.c_double)]),
     ("csv_bgzf_deflate", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(C.c_int64), C.c_int32,

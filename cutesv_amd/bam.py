@@ -23,6 +23,12 @@ index a file with a contig of 2^29 bases or more needs.
 
     python -m cutesv_amd.bam FILE [--chrom C] [--dump-columns DIR] [--inflate {host,device}] [--frame {host,device}] [--idxstats]
     python -m cutesv_amd.bam FILE --index [--csi [--min_shift N]] [--index_out PATH] [--force] [--inflate {host,device}] [--frame {host,device}]
+    python -m cutesv_amd.bam FILE --sort -o OUT [--index [--csi]] [--force] [--sort_route {host,device}] [--max_bytes N] [--inflate {host,device}] [--frame {host,device}]
+
+`sort_bam` sorts a file by coordinate - what an aligner writes goes straight in: the inflated stream stays in device
+memory, the keys are sorted by the rebuild's radix passes, k_sort_gather moves every byte once into sorted order and the device
+compressor writes the BGZF blocks; `sort_bam_host_twin` is the same on the host.  It is the one place that opens a file whose header
+does not say SO:coordinate.
 """
 import ctypes as C
 import os
@@ -175,7 +181,7 @@ class BamFile:
     a forward scan that stops at the first record starting at or after `end`: no index file is needed.  With an index
     (`has_index`) the scan starts at the linear-index entry of `start`; what it yields is the same, byte for byte."""
 
-    def __init__(self, path, threads=None, inflate=None, index=None, frame=None):
+    def __init__(self, path, threads=None, inflate=None, index=None, frame=None, _any_order=False):
         """frame: None or "host" - the records are framed on the host; "device" - on the device of `inflate`, which must be a
         Context (set_frame).
         inflate: None or "host" - the BGZF blocks are inflated on `threads` host threads; an engine.Context - on its device
@@ -207,7 +213,7 @@ class BamFile:
         hd = [ln for ln in self.header_text.split("\n") if ln.startswith("@HD")]
         so = [f[3:] for ln in hd for f in ln.split("\t") if f.startswith("SO:")]
         self.sort_order = so[0] if so else None
-        if self.sort_order != "coordinate":
+        if self.sort_order != "coordinate" and not _any_order:              # (_any_order: sort_bam's own reader, and nobody else's)
             self.close()
             raise BamError("%s: the header says SO:%s; a coordinate-sorted file is needed (samtools sort)" % (path, self.sort_order or "<missing>"))
         self.set_inflate(inflate)
@@ -709,6 +715,100 @@ def decode_host(chunk, check=True):
 COLUMNS = tuple(name for name, _, _ in _OUT)
 
 
+# ------------------------------------------------------------------------------------ coordinate sort
+SORT_ROUTES = ("device", "host")
+_SORT_COUNTS = ("records", "inversions", "inflated_bytes", "stream_bytes", "out_bytes", "blocks", "slices", "passes", "bytes_up", "bytes_down")
+
+
+def sort_bam(path, out, ctx=None, route="device", inflate=None, frame=None, threads=None, max_bytes=None, slice_blocks=None, index=False, overwrite=False,
+             window_blocks=None):
+    """Sort the BAM file `path` by coordinate into `out`: the job of samtools sort, and with index= of
+    samtools sort --write-index.  The file is opened here, and only here is a header that does not say SO:coordinate accepted.
+    route "device": csv_bam_sort on `ctx` (None: a Context on device 0 for the call) - keys, order, gather and compression on the
+    device; "host": csv_bam_sort_host, the same rules on the host and the same file byte for byte.  inflate / frame / threads /
+    window_blocks pick the reader's routes as BamFile does; inflate="device" means `ctx`.  max_bytes: the budget for the inflated
+    stream plus one slice (None: half of the device's free memory; no limit on the host route); a file beyond it raises BamError
+    before anything is read.  slice_blocks: BGZF blocks of 65280 bytes per slice (None: 256).  index: False, "bai" (or True) or
+    "csi" - BamFile(out).build_index(write=True) on the written file, on the same routes.
+    The file is written through a temporary file beside `out` and os.replace.  FileExistsError, before anything is read, when `out`
+    exists and overwrite is not set.  BamError "cannot sort: record N ...": a refID the header does not have or a pos below -1; nothing
+    is written.  -> stats: records, inversions (0: the input was in order), inflated_bytes, stream_bytes, out_bytes, blocks, slices,
+    passes, bytes_up, bytes_down, ms (wall), ms_keys / ms_sort / ms_gather / ms_deflate (device time), route, inflate, frame,
+    block_table (uoff, coff, isize) and - with index= - index, the stats of the index build."""
+    if route not in SORT_ROUTES:
+        raise ValueError("route must be one of %s, not %r" % (", ".join(SORT_ROUTES), route))
+    if index not in (False, None, True, "bai", "csi"):
+        raise ValueError("index is False, \"bai\" or \"csi\", not %r" % (index,))
+    out = os.fspath(out)
+    if os.path.exists(out) and not overwrite:
+        raise FileExistsError("%s exists (overwrite=True replaces it)" % out)
+    if os.path.exists(out) and os.path.samefile(path, out):
+        raise ValueError("%s cannot be sorted onto itself" % out)
+    own = None
+    wants_ctx = route == "device" or (isinstance(inflate, str) and inflate == "device")
+    if wants_ctx and ctx is None:
+        from . import engine
+        own = ctx = engine.Context(0)
+    if isinstance(inflate, str) and inflate == "device":
+        inflate = ctx
+    if route == "host" and not (frame is None or frame == "host"):
+        raise ValueError("route='host' frames on the host")
+    tmp = None
+    try:
+        bf = BamFile(path, threads=threads, inflate=inflate, index=False, frame=None, _any_order=True)
+        try:
+            if window_blocks is not None:
+                bf.set_inflate(inflate, window_blocks=window_blocks)
+            bf.set_frame(frame)
+            fd, tmp = tempfile.mkstemp(prefix=os.path.basename(out) + ".", suffix=".tmp", dir=os.path.dirname(out) or ".")
+            os.close(fd)
+            os.unlink(tmp)                                     # (the library creates the file itself, and only after the verdict)
+            bf._read_serial += 1
+            t0 = time.perf_counter()
+            budget = 0 if max_bytes is None else int(max_bytes)
+            if max_bytes is not None and budget <= 0:
+                raise ValueError("max_bytes must be positive, not %r" % (max_bytes,))
+            blocks = 0 if slice_blocks is None else int(slice_blocks)
+            if slice_blocks is not None and not 1 <= blocks <= 32768:
+                raise ValueError("slice_blocks must lie in 1 .. 32768, not %r" % (slice_blocks,))
+            if route == "device":
+                rc = bf._L.csv_bam_sort(bf._h, ctx._h, os.fsencode(tmp), budget, blocks, 0)
+            else:
+                rc = bf._L.csv_bam_sort_host(bf._h, os.fsencode(tmp), budget, blocks, 0)
+            ms = (time.perf_counter() - t0) * 1e3
+            if rc:
+                raise BamError("%s: %s" % (path, bf._error_text()))
+            counts, dev_ms = np.zeros(len(_SORT_COUNTS), np.int64), np.zeros(4, np.float64)
+            bf._L.csv_bam_sort_stats(bf._h, counts.ctypes.data, dev_ms.ctypes.data)
+            stats = dict(zip(_SORT_COUNTS, (int(v) for v in counts)))
+            stats.update(ms=ms, ms_keys=float(dev_ms[0]), ms_sort=float(dev_ms[1]), ms_gather=float(dev_ms[2]), ms_deflate=float(dev_ms[3]), route=route,
+                         inflate="host" if bf.inflate is None else "device", frame="host" if bf.frame is None else "device", written=out, index=None)
+            nb = stats["blocks"]
+            uoff, coff, isize, need = np.zeros(nb, np.int64), np.zeros(nb, np.int64), np.zeros(nb, np.uint32), C.c_int64()
+            if bf._L.csv_bam_sort_blocks(bf._h, uoff.ctypes.data, coff.ctypes.data, isize.ctypes.data, nb, C.byref(need)):
+                raise BamError("%s: the block table of the sorted file cannot be fetched" % path)
+            stats["block_table"] = (uoff, coff, isize)
+        finally:
+            bf.close()
+        os.replace(tmp, out)
+        tmp = None
+        if index not in (False, None):
+            fmt = "bai" if index is True else index
+            with BamFile(out, threads=threads, inflate=inflate, frame=frame, index=False) as sf:
+                stats["index"] = sf.build_index(write=True, overwrite=overwrite, format=fmt)
+        return stats
+    finally:
+        if tmp is not None and os.path.exists(tmp):
+            os.unlink(tmp)
+        if own is not None:
+            own.close()
+
+
+def sort_bam_host_twin(path, out, **kw):
+    """sort_bam on route "host": the twin of the device route - the same order, the same refusals, the same file"""
+    return sort_bam(path, out, route="host", **kw)
+
+
 # ------------------------------------------------------------------------------------ command line
 def main(argv=None):
     import argparse
@@ -724,10 +824,22 @@ def main(argv=None):
     ap.add_argument("--csi", action="store_true", help="with --index: build a CSI index and write it to FILE.csi (samtools index -c): the format for contigs of 2^29 bases or more")
     ap.add_argument("--min_shift", type=int, default=14, metavar="N", help="with --index --csi: 2^N bases per window of the index [14]")
     ap.add_argument("--index_out", metavar="PATH", default=None, help="with --index: write the index there instead")
-    ap.add_argument("--force", action="store_true", help="with --index: replace an index file that exists")
+    ap.add_argument("--force", action="store_true", help="with --index or --sort: replace a file that exists")
+    ap.add_argument("--sort", action="store_true", help="sort FILE by coordinate into -o OUT (the job of samtools sort; with --index: of samtools sort --write-index), and stop")
+    ap.add_argument("-o", "--output", metavar="OUT", default=None, help="with --sort: the sorted file")
+    ap.add_argument("--sort_route", default="device", choices=["host", "device"], help="with --sort: where keys, order, gather and compression run [%(default)s]")
+    ap.add_argument("--max_bytes", type=int, default=None, metavar="N", help="with --sort: the budget for the inflated stream plus one slice [device: half of the free memory]")
     a = ap.parse_args(argv)
-    if (a.index_out is not None or a.force) and not a.index:
-        ap.error("--index_out and --force go with --index")
+    if (a.output is not None or a.sort_route != "device" or a.max_bytes is not None) and not a.sort:
+        ap.error("-o, --sort_route and --max_bytes go with --sort")
+    if a.sort and a.output is None:
+        ap.error("--sort needs -o OUT")
+    if a.sort and (a.index_out is not None or a.idxstats or a.dump_columns or a.chrom is not None):
+        ap.error("--sort goes with -o, --index, --csi, --force, --sort_route, --max_bytes, --inflate, --frame and --threads only")
+    if a.sort and a.sort_route == "host" and a.frame == "device":
+        ap.error("--sort_route host frames on the host")
+    if (a.index_out is not None or a.force) and not (a.index or a.sort):
+        ap.error("--index_out goes with --index, --force with --index or --sort")
     if (a.csi or a.min_shift != 14) and not a.index:
         ap.error("--csi and --min_shift go with --index")
     if a.min_shift != 14 and not a.csi:
@@ -741,7 +853,7 @@ def main(argv=None):
     if a.frame == "device" and a.inflate != "device":
         ap.error("--frame device needs --inflate device")
     ctx = None
-    if a.inflate == "device":
+    if a.inflate == "device" or (a.sort and a.sort_route == "device"):
         from . import engine
         ctx = engine.Context(0)
     try:
@@ -752,6 +864,17 @@ def main(argv=None):
 
 
 def _main(a, ap, ctx):
+    if a.sort:
+        try:
+            st = sort_bam(a.bam, a.output, ctx=ctx, route=a.sort_route, inflate=ctx if a.inflate == "device" else None, frame=a.frame, threads=a.threads, max_bytes=a.max_bytes,
+                          index=("csi" if a.csi else "bai") if a.index else False, overwrite=a.force)
+        except FileExistsError as e:
+            ap.error("%s: --force replaces it" % e)
+        print("wrote %s: %d records (%d adjacent inversions) in %d blocks, %d -> %d bytes, %.1f ms (sort %s, inflate %s, frame %s)"
+              % (st["written"], st["records"], st["inversions"], st["blocks"], st["inflated_bytes"], st["out_bytes"], st["ms"], st["route"], st["inflate"], st["frame"]))
+        if st["index"] is not None:
+            print("wrote %s: %d bytes" % (st["index"]["written"], st["index"]["index_bytes"]))
+        return 0
     if a.index:
         with BamFile(a.bam, threads=a.threads, inflate=ctx, frame=a.frame, index=False) as bf:
             try:

@@ -2,7 +2,7 @@
 
     python -m cutesv_amd BAM REF OUT.vcf WORK_DIR [cuteSV's flags] [--reads_table {host,device}] [--tra_gt MODE] [--inflate {host,device}] [--frame {host,device}]
                          [--task_cut {index,uniform}] [--build_index] [--index_format {bai,csi}] [--bgzf {host,device}]
-                         [--ref_route {host,device}] [--emit {host,device}]
+                         [--ref_route {host,device}] [--emit {host,device}] [--sort_input {host,device}]
 
 `parse_args` accepts every option of cuteSV v2.1.4 under the same short and long spellings, with the same destination, type
 and default, so a command line written for cuteSV runs here unchanged; `main` maps them onto call.call_bam and writes a complete
@@ -24,6 +24,10 @@ What differs from cuteSV, on purpose:
     more) and the cut is cuteSV's.  A .csi beside the file serves as a .bai does.  The calls do not depend on the
     cut - except with -include_bed, where a task's reads are tested against the regions of that task only: there the uniform cut
     can differ from cuteSV's on contigs whose batch it would have shrunk.
+  * --sort_input takes a BAM file in any order - what `minimap2 -a | samtools view -b` writes: it is sorted by coordinate first
+    (bam.sort_bam; "device": keys, order, gather and compression on the GPU, "host": the same on the host) into
+    WORK_DIR/<BAM's name minus .bam>.sorted.bam, and the run goes on with that file exactly as with a sorted input; the file is removed at
+    the end unless --retain_work_dir is set.  Without the option an unsorted input is refused, as before.
   * reads.sigs is not written (its row order in cuteSV depends on which worker process wrote which task).
   * Force calling (-Ivcf) is not available, as in cuteSV v2.1.4 itself.
   * --read_range is accepted and unused, as on cuteSV's calling path.  -t sizes the BAM reader's inflate threads.
@@ -101,7 +105,7 @@ def _parser():
 
 
 def _own_parser():
-    """the ten options cuteSV does not have (six are call.add_route_options'); parsed apart (split_own), so that they shadow no abbreviation of a cuteSV flag"""
+    """the eleven options cuteSV does not have (six are call.add_route_options'); parsed apart (split_own), so that they shadow no abbreviation of a cuteSV flag"""
     from . import call
     ap = argparse.ArgumentParser(add_help=False, allow_abbrev=False)
     call.add_route_options(ap)
@@ -109,11 +113,12 @@ def _own_parser():
     ap.add_argument("--build_index", action="store_true")
     ap.add_argument("--index_format", default="bai", choices=["bai", "csi"])
     ap.add_argument("--bgzf", default=None, choices=["host", "device"])
+    ap.add_argument("--sort_input", default=None, choices=["host", "device"])
     return ap
 
 
 def split_own(argv):
-    """-> (namespace of --reads_table / --tra_gt / --inflate / --frame / --task_cut / --build_index / --index_format / --bgzf / --ref_route / --emit, argv without them)"""
+    """-> (namespace of --reads_table / --tra_gt / --inflate / --frame / --task_cut / --build_index / --index_format / --bgzf / --ref_route / --emit / --sort_input, argv without them)"""
     return _own_parser().parse_known_args(list(argv))
 
 
@@ -155,10 +160,47 @@ def _write_bgzf(path, text, route):
     _log("%-16s %10.1f ms  (%s.tbi, %d bytes)" % ("tabix", 1e3 * (t2 - t1), os.path.basename(path), len(tbi)))
 
 
+def sorted_input_path(work_dir, bam_path):
+    """where --sort_input writes the sorted file: WORK_DIR/<the BAM's name minus .bam>.sorted.bam"""
+    base = os.path.basename(bam_path)
+    return os.path.join(work_dir, (base[:-4] if base.endswith(".bam") else base) + ".sorted.bam")
+
+
+def _sort_input(a, own):
+    """--sort_input: the input sorted by coordinate into WORK_DIR on the routes of --inflate / --frame -> the sorted file's path"""
+    from . import bam as bam_mod
+    out = sorted_input_path(a.work_dir, a.input)
+    if os.path.exists(out):
+        raise FileExistsError("[Errno 17] File exists: '%s'" % out)
+    _log("%s is sorted by coordinate into %s (--sort_input %s)" % (a.input, out, own.sort_input))
+    frame = own.frame if own.sort_input == "device" else None
+    st = bam_mod.sort_bam(a.input, out, route=own.sort_input, inflate=own.inflate, frame=frame, threads=a.threads)
+    _log("%-16s %10.1f ms  (%d records, %d adjacent inversions, %d -> %d bytes in %d blocks; device: keys %.2f, sort %.2f, gather %.2f, deflate %.2f ms)"
+         % ("sort_input", st["ms"], st["records"], st["inversions"], st["inflated_bytes"], st["out_bytes"], st["blocks"], st["ms_keys"], st["ms_sort"], st["ms_gather"], st["ms_deflate"]))
+    return out
+
+
 def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
     own, rest = split_own(argv)
     a = parse_args(rest)
+    if own.sort_input is None:
+        return _run(a, own, argv)
+    if not os.path.isdir(a.work_dir):
+        raise FileNotFoundError("[Errno 2] No such directory: '%s'" % a.work_dir)
+    sorted_path = _sort_input(a, own)
+    try:
+        a.input = sorted_path
+        return _run(a, own, argv)
+    finally:
+        if not a.retain_work_dir:
+            for path in (sorted_path, sorted_path + ".bai", sorted_path + ".csi"):
+                if os.path.exists(path):
+                    os.remove(path)
+            _log("%s removed (--retain_work_dir keeps it)" % sorted_path)
+
+
+def _run(a, own, argv):
     if a.Ivcf is not None:
         raise ValueError("force calling is not available here (it is disabled in cuteSV %s as well): use cuteFC to regenotype a given SV set" % VERSION)
     if not os.path.isfile(a.reference):

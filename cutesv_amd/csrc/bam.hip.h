@@ -23,7 +23,8 @@
 // way back out: k_bgzf_deflate, one wavefront per block over deflate_core.h, and k_deflate_offsets.
 // And k_ref_gather: base ranges of a BGZF-compressed FASTA cut out of the blocks k_bgzf_inflate left on the device, one wavefront per
 // output tile over ref_core.h; and k_fai_tiles / k_fai_events: the lines of such a text as the event rows its .fai
-// is assembled from.
+// is assembled from.  And the coordinate sort of a whole file (sort_core.h): k_sort_keys, k_sort_dst_tiles /
+// k_sort_dst_scan and k_sort_gather, the kernel every byte of the file passes through on its way into sorted order.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -34,6 +35,7 @@
 #include "frame_core.h"
 #include "index_core.h"
 #include "ref_core.h"
+#include "sort_core.h"
 
 namespace csv {
 
@@ -810,6 +812,174 @@ template <bool WRITE> __global__ __launch_bounds__(256) void k_fai_events(FaiArg
             A.out->n_rows = red[3];
             A.out->tail = fai_tail(A.d, A.n, A.base, A.c, a);
         }
+    }
+}
+
+// ------------------------------------------------------------------------------------ the coordinate sort
+// The kernels of the coordinate sort of a BAM file; sort_core.h holds the rules.  The whole
+// inflated stream lies in one arena in device memory; `starts` names its records.
+//   k_sort_keys      one thread per record: key and length out of the record's bytes; the first refused record by a 64-bit atomicMin of
+//                    ordinal << 3 | why; the adjacent inversions (key[i] < key[i - 1]); the OR of all keys, from which the host names the
+//                    8-bit digits the radix passes have to look at
+//   (the permutation comes from sort.hip.h's k_sort_* passes over the key column: there is no second radix sort)
+//   k_sort_dst_tiles / k_sort_dst_scan   the lengths gathered through the permutation and their exclusive 64-bit prefix sums: dst
+//   k_sort_gather    the hot path: every byte of the file passes through it once.  Output-driven: a wavefront owns SORT_GATHER_TILE
+//                    bytes of the slice buffer and every lane writes aligned 16-byte pieces of it, so the time does not depend on the mix
+//                    of record lengths - 40-byte records and a 300 KB read cost the same per byte, and no wavefront copies a long record
+//                    alone.  Two wave-uniform binary searches over dst bracket the records that feed the tile; a lane searches only that
+//                    bracket (at most tile / 36 + 2 entries, hot in the cache).  A piece that lies inside one record is read as five
+//                    aligned dwords funnel-shifted to the source's alignment; a piece that crosses a record boundary, the header's end or
+//                    the stream's end is assembled byte by byte by sort_core.h's piece rule.  All offsets are 64-bit.
+// Bounds.  The host has checked the chain: every start lies in [first record, arena end), whole records only, so key fields (36
+// bytes) and every source byte are inside the arena; the aligned dword reads reach at most 3 bytes in front of a source (never in
+// front of the arena: the header precedes the first record) and 7 bytes behind it (the arena has 32 bytes of slack).  A lane stores
+// only inside [0, round_up(len, 16)) of the slice buffer, which has that room.
+
+// Bytes of the slice buffer per wavefront: 64 lanes x 16 bytes x 4 rounds.  Chosen, not measured: 4 rounds amortise the two bracket
+// searches (2 x ~25 dependent loads for 16 M records) over 256 stores, and a 16 MiB slice still gives 4096 wavefronts, 4 per SIMD.
+constexpr int SORT_GATHER_TILE = 4096;
+
+struct SortKeyArgs {
+    const uint8_t* arena; i64 arena_bytes; const i64* starts; i64 n; int n_ref;
+    u64* key; i64* len;
+    u64* verdict;                   // [0] min of ordinal << 3 | why (SORT_NONE: none), [1] inversions, [2] OR of the keys
+};
+
+__global__ __launch_bounds__(256) void k_sort_keys(SortKeyArgs A)
+{
+    const i64 i = (i64)blockIdx.x * 256 + threadIdx.x;
+    const bool in = i < A.n;
+    u64 key = 0;
+    int inv = 0;
+    if (in) {
+        const SortFields f = sort_fields(A.arena + A.starts[i]);
+        int why = sort_refuse(f, A.n_ref);
+        if (f.len < 36 || f.len > A.arena_bytes - A.starts[i]) why = SORT_WHY_CHAIN;   // (not the bytes the reader stepped over: nothing may be gathered)
+        if (why) atomicMin((unsigned long long*)&A.verdict[0], (unsigned long long)((u64)i << 3 | (u64)why));
+        else key = sort_key(f, A.n_ref);
+        A.key[i] = key; A.len[i] = f.len;
+        if (i > 0) {                                              // (the neighbour's key again from its bytes: no second launch, no barrier)
+            const SortFields g = sort_fields(A.arena + A.starts[i - 1]);
+            inv = !why && !sort_refuse(g, A.n_ref) && key < sort_key(g, A.n_ref);
+        }
+    }
+    const u64 votes = __ballot(inv);
+    u64 any = key;
+    for (int m = 1; m < 64; m <<= 1) any |= (u64)shfl_xor_i64((i64)any, m);
+    if (lane_id() == 0) {
+        if (votes) atomicAdd((unsigned long long*)&A.verdict[1], (unsigned long long)__popcll(votes));
+        if (any) atomicOr((unsigned long long*)&A.verdict[2], (unsigned long long)any);
+    }
+}
+
+// dst: per tile of 1024 sorted records the sum of their lengths, then every tile its carry and its own exclusive scan
+constexpr int SORT_DST_TILE = 1024;
+struct SortDstArgs { const i64* len; const int* perm; i64 n; i64* dst; i64* tile_sum; };      // perm NULL: the identity; dst: n + 1
+
+__global__ __launch_bounds__(256) void k_sort_dst_tiles(SortDstArgs A)
+{
+    __shared__ i64 sh[4];
+    const i64 base = (i64)blockIdx.x * SORT_DST_TILE;
+    i64 s = 0;
+    for (int k = threadIdx.x; k < SORT_DST_TILE; k += 256) {
+        const i64 r = base + k;
+        if (r < A.n) s += A.len[A.perm ? A.perm[r] : r];
+    }
+    s = wave_sum_i64(s);
+    if (lane_id() == 0) sh[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) A.tile_sum[blockIdx.x] = sh[0] + sh[1] + sh[2] + sh[3];
+}
+
+__global__ __launch_bounds__(256) void k_sort_dst_scan(SortDstArgs A)
+{
+    __shared__ i64 sh[4], ws[4];
+    __shared__ i64 carry;
+    const i64 before = block_prefix_of64(A.tile_sum, (int)blockIdx.x, sh);
+    if (threadIdx.x == 0) carry = before;
+    __syncthreads();
+    const i64 base = (i64)blockIdx.x * SORT_DST_TILE;
+    for (int b0 = 0; b0 < SORT_DST_TILE; b0 += 256) {
+        const i64 r = base + b0 + threadIdx.x;
+        const i64 v = r < A.n ? A.len[A.perm ? A.perm[r] : r] : 0;
+        const i64 inc = wave_incl_scan_i64(v);
+        if (lane_id() == 63) ws[threadIdx.x >> 6] = inc;
+        __syncthreads();
+        i64 off = carry;
+        for (int q = 0; q < (int)(threadIdx.x >> 6); q++) off += ws[q];
+        off += inc - v;
+        if (r < A.n) A.dst[r] = off;
+        if (r == A.n - 1) A.dst[A.n] = off + v;
+        __syncthreads();
+        if (threadIdx.x == 255) carry = off + v;
+        __syncthreads();
+    }
+}
+
+struct SortGatherArgs {
+    const uint8_t* arena; const uint8_t* hdr; i64 H;
+    const i64* starts; const int* perm; const i64* dst; i64 n;     // perm NULL: the identity; dst: n + 1 (unused when n == 0)
+    i64 s0, len;                    // the slice: bytes [s0, s0 + len) of the sorted stream; s0 is a multiple of 16
+    uint8_t* out;                   // the slice buffer: round_up(len, 16) bytes are written, 16-byte aligned
+};
+
+// 16 bytes at any alignment as five aligned dwords, funnel-shifted
+__device__ __forceinline__ uint4 sort_ld16(const uint8_t* p)
+{
+    const uintptr_t a = (uintptr_t)p;
+    const uint32_t* w = (const uint32_t*)(a & ~(uintptr_t)3);
+    const uint32_t sh = (uint32_t)(a & 3) * 8;
+    const uint32_t w0 = w[0], w1 = w[1], w2 = w[2], w3 = w[3], w4 = w[4];
+    return make_uint4(__builtin_amdgcn_alignbit(w1, w0, sh), __builtin_amdgcn_alignbit(w2, w1, sh), __builtin_amdgcn_alignbit(w3, w2, sh), __builtin_amdgcn_alignbit(w4, w3, sh));
+}
+
+__global__ __launch_bounds__(256) void k_sort_gather(SortGatherArgs A)
+{
+    const i64 tile = ((i64)blockIdx.x * 256 + threadIdx.x) >> 6;
+    const i64 t0 = tile * SORT_GATHER_TILE;                       // in the slice
+    if (t0 >= A.len) return;
+    const i64 t1 = t0 + SORT_GATHER_TILE < A.len ? t0 + SORT_GATHER_TILE : A.len;
+    const i64 end = A.s0 + A.len;                                 // of the slice, in the stream
+    // the records that feed the tile: [lo, hi] (wave-uniform)
+    i64 lo = 0, hi = 0;
+    if (A.n > 0 && A.s0 + t1 > A.H) {
+        const i64 ra = A.s0 + t0 > A.H ? A.s0 + t0 - A.H : 0;
+        lo = sort_first_record(A.dst, 0, A.n - 1, ra);
+        hi = sort_first_record(A.dst, lo, A.n - 1, A.s0 + t1 - 1 - A.H);
+    }
+    for (int q = 0; q < SORT_GATHER_TILE / (64 * 16); q++) {
+        const i64 at = t0 + ((i64)q * 64 + lane_id()) * 16;      // in the slice
+        if (at >= t1) break;
+        const i64 o = A.s0 + at;                                  // in the stream
+        uint4 v;
+        if (o + 16 <= A.H) v = *(const uint4*)(A.hdr + o);
+        else {
+            i64 r = o >= A.H ? sort_first_record(A.dst, lo, hi, o - A.H) : 0;
+            if (o >= A.H && o + 16 <= end && o + 16 - A.H <= A.dst[r + 1])
+                v = sort_ld16(A.arena + A.starts[A.perm ? A.perm[r] : r] + (o - A.H - A.dst[r]));
+            else {                                                // a boundary inside the piece: sort_tile_fill's rule, byte by byte
+                uint32_t w[4] = {0, 0, 0, 0};
+                i64 src = -1, left = 0;                           // the running source, and its bytes still inside the record
+                for (int j = 0; j < 16; j++) {
+                    const i64 p = o + j;
+                    if (p >= end) break;                          // (behind the stream's end the piece stays zero)
+                    uint32_t b;
+                    if (p < A.H) b = A.hdr[p];
+                    else {
+                        if (left == 0) {
+                            if (src >= 0) r++;
+                            const i64 in_rec = p - A.H - A.dst[r];
+                            src = A.starts[A.perm ? A.perm[r] : r] + in_rec;
+                            left = A.dst[r + 1] - A.dst[r] - in_rec;
+                        }
+                        b = A.arena[src]; src++; left--;
+                    }
+                    w[j >> 2] |= b << (8 * (j & 3));
+                }
+                v = make_uint4(w[0], w[1], w[2], w[3]);
+            }
+        }
+        *(uint4*)(A.out + at) = v;
     }
 }
 

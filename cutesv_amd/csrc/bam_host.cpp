@@ -6,7 +6,9 @@
 // records are framed there (frame_core.h) and the scan runs over the rows of the record table.  With an index (bai_index.h, section
 // 28) a region's scan starts at its linear-index entry; the index moves the starting point and nothing else.  csv_bam_index_build
 // (section 30) makes one in a whole-file pass on the reader's routes, through index_core.h.  A .csi (csi_index.h, section 32) is read
-// and built as well: index_start / index_stop are the one place that knows which of the two the reader has.
+// and built as well: index_start / index_stop are the one place that knows which of the two the reader has.  csv_bam_sort (section
+// 39) is the other whole-file pass: it assumes nothing about the file's order and writes the records sorted by coordinate, through
+// sort_core.h.
 //
 // Written from the SAM/BAM specification (SAMv1, sections 4.1 "The BGZF compression format" and 4.2 "The BAM format"):
 //   BGZF block  = gzip member with one extra subfield 'B','C' (u16 BSIZE = block size - 1), raw deflate payload, CRC32, ISIZE
@@ -28,6 +30,7 @@
 #include <atomic>
 #include <chrono>
 #include <map>
+#include <new>
 #include <string>
 #include <thread>
 #include <vector>
@@ -37,6 +40,7 @@
 #include "csi_index.h"
 #include "frame_core.h"
 #include "index_core.h"
+#include "sort_core.h"
 
 namespace {
 
@@ -142,6 +146,14 @@ struct csv_bam {
         i64                  records = 0, runs = 0, frame_runs = 0, windows = 0, up = 0, down = 0, bins = 0;
         double               ms_kernels = 0, ms_loff = 0;
     } ix;
+    // the last csv_bam_sort / csv_bam_sort_host: its counters and the block table of the file it wrote, the
+    // end-of-file block included
+    struct Sorted {
+        i64                   records = 0, inversions = 0, inflated = 0, stream = 0, out_bytes = 0, blocks = 0, slices = 0, passes = 0, up = 0, down = 0;
+        double                ms[4] = {0, 0, 0, 0};          // device time: keys, sort, gather, deflate
+        std::vector<i64>      uoff, coff;
+        std::vector<uint32_t> isize;
+    } so;
     struct Chunk {                               // the chunk handed out last (the host route's images), and what the read cost
         std::vector<uint8_t>  slim, host;
         std::vector<i64>      rec_off, host_off;
@@ -874,6 +886,237 @@ int index_build_device(csv_bam* b, const IxTables& T, csv::ix::Builder* B)
     return CSV_OK;
 }
 
+// ---- the coordinate sort (sort_core.h)
+}  // namespace
+// (weak, as sort_core.h's device entries are: the host form's compressor lives in bgzf_host.cpp, which a stand-alone build of this file leaves out)
+extern "C" __attribute__((weak)) int csv_bgzf_deflate_host(const uint8_t* in, int64_t in_bytes, int32_t n_blocks, const int64_t* in_off, const int32_t* in_len, uint8_t* out,
+                                                          int64_t out_cap, int32_t* block_bytes, int64_t* out_bytes, int32_t* coding_bytes);
+namespace {
+// Where the inflated stream goes while the pass walks the file: the device arena of `ctx`, or - the host form - a host vector.  Both
+// hold the stream at its own offsets, so a record's start in the stream is its start there.  hi: everything below it has arrived
+struct SortSink { csv_ctx* ctx; std::vector<uint8_t>* host; i64 hi; };
+
+int fail_sort_device(csv_bam* b, csv_ctx* ctx, int rc) { return fail(b, rc, "the device sort failed: %s", csv_last_error(ctx)); }
+
+// the bytes of the reader's window that the sink does not have yet.  Windows only move forward and begin at the block of the cursor,
+// which lies at or below hi: what a window skips at its front is header bytes in front of the first record
+int sort_take(csv_bam* b, SortSink* S)
+{
+    const i64 w_end = b->win.u0 + b->win.n;
+    if (b->win.n <= 0 || w_end <= S->hi) return CSV_OK;
+    if (b->win.u0 > S->hi && S->hi > b->hdr.first_rec) return fail(b, CSV_E_INVALID, "%sthe sort lost the bytes in front of inflated byte %lld", "", (long long)b->win.u0);
+    const i64 from = std::max(S->hi, b->win.u0), len = w_end - from;
+    if (S->ctx) {
+        const int rc = csv_sort_append(S->ctx, from, b->fr.ctx ? nullptr : b->win.p + (from - b->win.u0), from - b->win.u0, len);
+        if (rc) return fail_sort_device(b, S->ctx, rc);
+    } else memcpy(S->host->data() + from, b->win.p + (from - b->win.u0), (size_t)len);
+    S->hi = w_end;
+    return CSV_OK;
+}
+
+// Every record start of the file, window by window on the reader's routes, while the windows' bytes go to the sink.  The pass assumes
+// nothing about the file's order: it never stops at a record, only at the stream's end.  The framing route takes the starts from
+// frame_step's rows; the others step from block_size to block_size with next_host's checks and texts - but ask for the record from
+// its first byte on, so that a refill never drops the block in which the record began before the sink has it.
+int sort_collect(csv_bam* b, SortSink* S, std::vector<csv::so_i64>* starts)
+{
+    int rc;
+    if (b->fr.ctx) {
+        bool at_tail = false;
+        int idle = 0;
+        b->fr.valid = false;
+        for (;;) {
+            const i64 cur = b->scan.cur;
+            bool at_end;
+            if ((rc = frame_step(b, at_tail, true, &at_end)) != CSV_OK) return rc;
+            if (at_end) return CSV_OK;
+            if ((rc = sort_take(b, S)) != CSV_OK) return rc;
+            for (i64 k = 0; k < b->fr.n; k++) starts->push_back(b->win.u0 + b->fr.rows[k].off);
+            if (b->fr.tail > cur) idle = 0;
+            else if (++idle > 4) return fail(b, CSV_E_INVALID, "%sthe device framing made no progress at inflated byte %lld", "", (long long)cur);
+            at_tail = b->fr.tail_has_bs;
+            b->scan.cur = b->fr.tail;
+        }
+    }
+    for (;;) {
+        const i64 cur = b->scan.cur;
+        const uint8_t* p = at(b, cur, 4, &rc);
+        if (rc) return rc;
+        if (!p) return cur == b->file.utotal ? CSV_OK : fail_ends_inside(b, cur);
+        if ((rc = sort_take(b, S)) != CSV_OK) return rc;
+        const i64 bs = rd_i32(p);
+        if (bs < 32) return fail_small_bs(b, cur);
+        p = at(b, cur, 4 + bs, &rc);
+        if (rc) return rc;
+        if (!p) return fail_ends_inside(b, cur);
+        if ((rc = sort_take(b, S)) != CSV_OK) return rc;
+        starts->push_back(cur);
+        b->scan.cur = cur + 4 + bs;
+    }
+}
+
+// the BAM header as the file holds it: the blocks in front of the first record, inflated on the host whatever the routes are
+int sort_raw_header(csv_bam* b, std::vector<uint8_t>* head)
+{
+    std::vector<uint8_t> buf;
+    for (const Block& k : b->file.blocks) {
+        if (k.uoff >= b->hdr.first_rec) break;
+        buf.resize((size_t)(k.uoff + k.isize));
+        if (!inflate_block(b, k, buf.data() + k.uoff)) return fail(b, CSV_E_INVALID, "%sBGZF block at byte %lld does not inflate (or fails its CRC)", "", (long long)k.coff);
+    }
+    if ((i64)buf.size() < b->hdr.first_rec) return fail(b, CSV_E_INVALID, "%sthe file ends inside the BAM header", "");
+    head->assign(buf.begin(), buf.begin() + b->hdr.first_rec);
+    return CSV_OK;
+}
+
+// csv_bam_sort (ctx) and csv_bam_sort_host (ctx NULL): one body.  The routes differ in where the stream is collected, in who computes
+// keys, order and dst, and in who fills and compresses a slice; the rules are sort_core.h's on both, and csv_bgzf_deflate_host gives
+// the device compressor's bytes: the files are equal byte for byte.
+int sort_run(csv_bam* b, csv_ctx* ctx, const char* out_path, int64_t max_bytes, int32_t slice_blocks)
+{
+    if (ctx ? !csv_sort_begin : !csv_bgzf_deflate_host) return fail(b, CSV_E_STATE, "this build of the reader has no %s route for the sort", ctx ? "device" : "host");
+    csv_bam::Sorted& so = b->so;
+    so = csv_bam::Sorted();
+    csv_bam::Scan& s = b->scan;
+    begin_read(b);                                           // the sort is a read; the scan state of a region is forgotten as well
+    s.seeked = false; s.ahead_block = -1; s.hint_at = -1; s.range_i = 0;
+    const i64 slice_bytes = (i64)(slice_blocks > 0 ? slice_blocks : csv::SORT_SLICE_BLOCKS) * csv::SORT_BLOCK;
+    const i64 inflated = b->file.utotal, need = inflated + slice_bytes;
+    so.inflated = inflated;
+    int rc;
+    // the budget, before the first window is read
+    i64 budget = max_bytes;
+    if (ctx && budget <= 0) {
+        int64_t free_bytes = 0;
+        if ((rc = csv_sort_free_bytes(ctx, &free_bytes)) != CSV_OK) return fail_sort_device(b, ctx, rc);
+        budget = free_bytes / 2;
+    }
+    if (budget > 0 && need > budget) {
+        char buf[384];
+        snprintf(buf, sizeof buf, "cannot sort: the inflated stream (%lld bytes) and one slice (%lld bytes) take %lld bytes, the budget is %lld bytes; files beyond it are not sorted here (samtools sort)",
+                 (long long)inflated, (long long)slice_bytes, (long long)need, (long long)budget);
+        b->err = buf;
+        return CSV_E_CAPACITY;
+    }
+    std::vector<uint8_t> head, hdr, arena_h, slice_h, image;
+    std::vector<csv::so_i64> starts, dst;                    // (so_i64: the core's 64-bit integer, int64_t's size)
+    static_assert(sizeof(csv::so_i64) == sizeof(int64_t), "the starts table is handed on as it is");
+    std::vector<int32_t> perm, sizes;
+    std::vector<uint64_t> keys;
+    if ((rc = sort_raw_header(b, &head)) != CSV_OK) return rc;
+    if (!csv::sort_header(head.data(), (i64)head.size(), &hdr)) return fail(b, CSV_E_INVALID, "%scannot sort: the BAM header cannot be rewritten", "");
+    const i64 H = (i64)hdr.size();
+    FILE* f = nullptr;
+    bool opened = false;                                     // a sort is open on the context
+    auto finish = [&](int code) {                            // every way out: the context's arena goes back, a failed sort leaves no file
+        if (opened) csv_sort_end(ctx);
+        if (f) { if (fclose(f) != 0 && !code) code = fail(b, CSV_E_INVALID, "cannot write %s", out_path); if (code) remove(out_path); }
+        s.cur = b->hdr.first_rec;
+        b->win.n = 0; b->fr.valid = false;                   // (what a later read costs does not depend on what the sort left in the window)
+        return code;
+    };
+    try {
+        if (!ctx) arena_h.resize((size_t)inflated + 8);
+        slice_h.resize(ctx ? 0 : (size_t)slice_bytes);
+        image.resize((size_t)(slice_bytes + 31 * (slice_bytes / csv::SORT_BLOCK)));
+        sizes.resize((size_t)(slice_bytes / csv::SORT_BLOCK));
+    } catch (const std::bad_alloc&) { return fail(b, CSV_E_NOMEM, "%scannot sort: no memory for the inflated stream (%lld bytes)", "", (long long)inflated); }
+    if (ctx) {
+        if ((rc = csv_sort_begin(ctx, inflated, hdr.data(), H, slice_bytes)) != CSV_OK) return finish(fail_sort_device(b, ctx, rc));
+        opened = true;
+    }
+    // the windows and the record starts
+    SortSink S{ctx, &arena_h, 0};
+    s.cur = b->hdr.first_rec;
+    b->win.n = 0; b->fr.valid = false;
+    try {
+        rc = sort_collect(b, &S, &starts);
+    } catch (const std::bad_alloc&) { rc = fail(b, CSV_E_NOMEM, "%scannot sort: no memory for the table of record starts (%lld records so far)", "", (long long)starts.size()); }
+    if (rc) return finish(rc);
+    const i64 n = (i64)starts.size();
+    for (i64 i = 0; i < n; i++)                              // (the chain: what every later step relies on)
+        if (starts[(size_t)i] < b->hdr.first_rec || starts[(size_t)i] > inflated - 36 || (i && starts[(size_t)i] < starts[(size_t)i - 1] + 36))
+            return finish(fail(b, CSV_E_INVALID, "%scannot sort: the chain of records breaks at record %lld", "", (long long)i));
+    // keys, verdict, order, dst
+    uint64_t bad = csv::SORT_NONE;
+    i64 record_bytes = 0;
+    if (ctx) {
+        csv_sort_verdict V;
+        if ((rc = csv_sort_order(ctx, n, (const int64_t*)starts.data(), b->hdr.n_ref, &V)) != CSV_OK) return finish(fail_sort_device(b, ctx, rc));
+        bad = V.bad; so.inversions = V.inversions; so.passes = V.passes; record_bytes = V.record_bytes;
+    } else {
+        try { keys.resize((size_t)n); perm.resize((size_t)n); dst.resize((size_t)n + 1); }
+        catch (const std::bad_alloc&) { return finish(fail(b, CSV_E_NOMEM, "%scannot sort: no memory for the tables of %lld records", "", (long long)n)); }
+        for (i64 i = 0; i < n; i++) {
+            const csv::SortFields fl = csv::sort_fields(arena_h.data() + starts[(size_t)i]);
+            const int why = csv::sort_refuse(fl, b->hdr.n_ref);
+            if (why) { bad = (uint64_t)i << 3 | (uint64_t)why; break; }
+            keys[(size_t)i] = csv::sort_key(fl, b->hdr.n_ref);
+            if (i && keys[(size_t)i] < keys[(size_t)i - 1]) so.inversions++;
+            perm[(size_t)i] = (int32_t)i;
+        }
+        if (bad == csv::SORT_NONE) {
+            std::stable_sort(perm.begin(), perm.end(), [&](int32_t x, int32_t y) { return keys[(size_t)x] < keys[(size_t)y]; });
+            for (i64 r = 0; r < n; r++) { dst[(size_t)r] = record_bytes; record_bytes += csv::sort_fields(arena_h.data() + starts[(size_t)perm[(size_t)r]]).len; }
+            dst[(size_t)n] = record_bytes;
+        }
+    }
+    if (bad != csv::SORT_NONE) {
+        const int why = (int)(bad & 7);
+        if (why == csv::SORT_WHY_CHAIN) return finish(fail(b, CSV_E_INVALID, "%scannot sort: record %lld is not the record the reader stepped over", "", (long long)(bad >> 3)));
+        char buf[384];
+        snprintf(buf, sizeof buf, "cannot sort: record %lld %s", (long long)(bad >> 3), csv::sort_refusal_text(why, b->hdr.n_ref).c_str());
+        b->err = buf;
+        return finish(CSV_E_INVALID);
+    }
+    if (record_bytes != inflated - b->hdr.first_rec)
+        return finish(fail(b, CSV_E_INVALID, "%scannot sort: the records take %lld bytes, not the stream's", "", (long long)record_bytes));
+    // the sorted stream, slice by slice: gathered, compressed, written
+    const i64 total = H + record_bytes;
+    so.records = n; so.stream = total;
+    f = fopen(out_path, "wb");
+    if (!f) return finish(fail(b, CSV_E_INVALID, "cannot write %s", out_path));
+    i64 coff = 0;
+    for (i64 s0 = 0; s0 < total; s0 += slice_bytes) {
+        const i64 len = std::min(slice_bytes, total - s0);
+        const int32_t nb = (int32_t)((len + csv::SORT_BLOCK - 1) / csv::SORT_BLOCK);
+        int64_t out_bytes = 0;
+        if (ctx) {
+            if ((rc = csv_sort_slice(ctx, s0, len, image.data(), (int64_t)image.size(), sizes.data(), &out_bytes)) != CSV_OK) return finish(fail_sort_device(b, ctx, rc));
+        } else {
+            csv::sort_tile_fill(slice_h.data(), s0, s0 + len, hdr.data(), H, arena_h.data(), starts.data(), perm.data(), dst.data(), n);
+            std::vector<int64_t> off((size_t)nb);
+            std::vector<int32_t> ln((size_t)nb);
+            for (int32_t k = 0; k < nb; k++) { off[(size_t)k] = (i64)k * csv::SORT_BLOCK; ln[(size_t)k] = (int32_t)std::min<i64>(csv::SORT_BLOCK, len - (i64)k * csv::SORT_BLOCK); }
+            rc = csv_bgzf_deflate_host(slice_h.data(), len, nb, off.data(), ln.data(), image.data(), (int64_t)image.size(), sizes.data(), &out_bytes, nullptr);
+            if (rc) return finish(fail(b, rc, "%scannot sort: the slice at stream byte %lld does not deflate", "", (long long)s0));
+        }
+        if (out_bytes <= 0 || out_bytes > (int64_t)image.size()) return finish(fail(b, CSV_E_INVALID, "%scannot sort: the slice at stream byte %lld compressed to nothing", "", (long long)s0));
+        if (fwrite(image.data(), 1, (size_t)out_bytes, f) != (size_t)out_bytes) return finish(fail(b, CSV_E_INVALID, "cannot write %s", out_path));
+        for (int32_t k = 0; k < nb; k++) {
+            so.uoff.push_back(s0 + (i64)k * csv::SORT_BLOCK); so.coff.push_back(coff);
+            so.isize.push_back((uint32_t)std::min<i64>(csv::SORT_BLOCK, len - (i64)k * csv::SORT_BLOCK));
+            coff += sizes[(size_t)k];
+        }
+        so.slices++;
+    }
+    static const uint8_t eof_block[28] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0, 0x1b, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    if (fwrite(eof_block, 1, sizeof eof_block, f) != sizeof eof_block) return finish(fail(b, CSV_E_INVALID, "cannot write %s", out_path));
+    so.uoff.push_back(total); so.coff.push_back(coff); so.isize.push_back(0);
+    so.blocks = (i64)so.uoff.size(); so.out_bytes = coff + (i64)sizeof eof_block;
+    if (ctx) {
+        int64_t up = 0, down = 0;
+        csv_sort_counters(ctx, so.ms, &up, &down);
+        so.up = up; so.down = down;
+        if (b->fr.ctx) {
+            int64_t dn_f = 0, up_f = 0;
+            csv_frame_counters(b->fr.ctx, nullptr, nullptr, nullptr, &dn_f, &up_f, 0);
+            so.up += up_f; so.down += dn_f;
+        }
+    }
+    return finish(CSV_OK);
+}
+
 }  // namespace
 
 // ---- the C entry points (include/cutesv_hip.h)
@@ -1217,6 +1460,43 @@ int csv_bam_index_build_stats(const csv_bam* b, int64_t* records, int64_t* runs,
     if (bytes_down) *bytes_down = b->ix.down;
     if (frame_runs) *frame_runs = b->ix.frame_runs;
     if (index_windows) *index_windows = b->ix.windows;
+    return CSV_OK;
+}
+
+int csv_bam_sort(csv_bam* b, csv_ctx* ctx, const char* out_path, int64_t max_bytes, int32_t slice_blocks, int32_t flags)
+{
+    if (!b) return CSV_E_INVALID;
+    if (!ctx || !out_path || flags != 0 || slice_blocks < 0 || slice_blocks > 32768) return fail(b, CSV_E_INVALID, "%sbad sort call", "");
+    if (b->dev.ctx && b->dev.ctx != ctx) return fail(b, CSV_E_STATE, "%sthe sort needs the context the reader inflates on", "");
+    return sort_run(b, ctx, out_path, max_bytes, slice_blocks);
+}
+
+int csv_bam_sort_host(csv_bam* b, const char* out_path, int64_t max_bytes, int32_t slice_blocks, int32_t flags)
+{
+    if (!b) return CSV_E_INVALID;
+    if (!out_path || flags != 0 || slice_blocks < 0 || slice_blocks > 32768) return fail(b, CSV_E_INVALID, "%sbad sort call", "");
+    if (b->fr.ctx) return fail(b, CSV_E_STATE, "%sthe host form of the sort frames on the host (csv_bam_set_frame(bam, NULL) first)", "");
+    return sort_run(b, nullptr, out_path, max_bytes, slice_blocks);
+}
+
+int csv_bam_sort_stats(const csv_bam* b, int64_t* counts, double* ms)
+{
+    if (!b) return CSV_E_INVALID;
+    const csv_bam::Sorted& so = b->so;
+    if (counts) { const int64_t v[10] = {so.records, so.inversions, so.inflated, so.stream, so.out_bytes, so.blocks, so.slices, so.passes, so.up, so.down}; memcpy(counts, v, sizeof v); }
+    if (ms) memcpy(ms, so.ms, sizeof so.ms);
+    return CSV_OK;
+}
+
+int csv_bam_sort_blocks(const csv_bam* b, int64_t* uoff, int64_t* coff, uint32_t* isize, int64_t cap, int64_t* need)
+{
+    if (!b) return CSV_E_INVALID;
+    const csv_bam::Sorted& so = b->so;
+    const int64_t n = (int64_t)so.uoff.size();
+    if (need) *need = n;
+    if (n == 0) return CSV_E_STATE;
+    if (!uoff || !coff || !isize || cap < n) return CSV_E_CAPACITY;
+    for (int64_t k = 0; k < n; k++) { uoff[k] = so.uoff[(size_t)k]; coff[k] = so.coff[(size_t)k]; isize[k] = so.isize[(size_t)k]; }
     return CSV_OK;
 }
 

@@ -240,6 +240,23 @@ struct IndexBuildState {
     void own(std::vector<Buf*>& v) { v.insert(v.end(), {&blocks, &refs, &lin, &counts, &work}); }
 };
 
+// The coordinate sort of a BAM file (stage_bam_sort.hip.h), all stand-alone.  arena (the whole inflated stream at
+// its own offsets, 32 bytes of slack behind it), hdr (the rewritten header), starts, key, len, perm[2], hist, tot, dst, tiles and
+// verdict live from csv_sort_begin to csv_sort_end: one sort; csv_sort_end gives the arena back, the rest is grow-only.  slice: the
+// gathered bytes of one csv_sort_slice, which DeflateState's buffers then compress where they lie.  csv_sort_append READS FrameState's
+// current window when the reader frames on the device; nothing else of the context is touched but its stream and its first two
+// timing events.
+struct BamSortState {
+    Buf arena, hdr, starts, key, len, perm[2], hist, tot, dst, tiles, verdict, slice;
+    i64 arena_bytes = -1, hdr_bytes = 0, slice_bytes = 0, n = -1, total = 0;      // arena_bytes -1: no sort is open; n -1: not ordered yet
+    const int* order = nullptr;                // the final permutation (NULL: the identity)
+    std::vector<i64> off_h;
+    std::vector<int32_t> len_h;
+    double ms[4] = {0, 0, 0, 0};               // keys, sort (passes and dst), gather, deflate
+    i64 bytes_up = 0, bytes_down = 0;
+    void own(std::vector<Buf*>& v) { v.insert(v.end(), {&arena, &hdr, &starts, &key, &len, &perm[0], &perm[1], &hist, &tot, &dst, &tiles, &verdict, &slice}); }
+};
+
 // ---- The state of the engine (stage_upload / stage_run / stage_results.hip.h): the path csv_batch_upload -> csv_batch_run ->
 // csv_batch_download / csv_batch_publish_* and the one-shot csv_cluster_batch.  One struct per concern, with the same kind of rule.
 
@@ -374,7 +391,7 @@ struct csv_ctx {
     BatchState bt; ReadsOrderState ro; ResultState res; TableState tab;
     // ---- the extraction-side stages (their lifetime rules: at the structs)
     PoolState pool; NameState nm; BamState bm; SaState sa; SeqState seq; VcfStrState vs; AlnState al; ReadsTabState rt;
-    RebuildState rb; CigarState cg; SplitState sp; InflateState inf; FrameState fr; IndexBuildState ixb; DeflateState dfl; RefState ref; VcfEmitState ve;
+    RebuildState rb; CigarState cg; SplitState sp; InflateState inf; FrameState fr; IndexBuildState ixb; DeflateState dfl; RefState ref; VcfEmitState ve; BamSortState bs;
 };
 
 namespace {

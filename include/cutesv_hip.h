@@ -1032,6 +1032,35 @@ int         csv_bam_index_build_csi(csv_bam* bam, int32_t min_shift, int32_t dep
 int         csv_bam_index_payload(const csv_bam* bam, uint8_t* out, int64_t cap, int64_t* need);
 int         csv_bam_index_build_stats_csi(const csv_bam* bam, int64_t* bins, double* ms_loff);
 
+/* Coordinate-sorting a BAM file (csrc/sort_core.h): what an aligner wrote -> the file this reader takes, with no
+ * other tool.  csv_bam_sort runs one pass over the whole open file on the reader's current routes - the inflated bytes of every window
+ * are appended to one arena in ctx's device memory (device to device when the reader frames there, uploaded otherwise), the record
+ * starts come from the framed rows or from a host walk - and then, on ctx: k_sort_keys (key = refid' << 33 | (pos + 1) << 1 | reverse
+ * bit with refid' = n_ref for refid -1; so a contig's pos -1 records come first, forward before reverse, records without a reference
+ * last), the stable radix passes of the rebuild's permutation sort over the digits some key uses, the lengths' prefix sums, and per
+ * slice of at most slice_blocks (0: 256; at most 32768) BGZF blocks of 65280 bytes k_sort_gather and the device compressor; only the
+ * compressed blocks come down.  Records of equal key keep their input order.  The file written to out_path is the header with its
+ * text changed in one place (@HD's SO: field becomes SO:coordinate, appended when absent; GO: and SS: fields are dropped; a text
+ * without @HD gets "@HD\tVN:1.6\tSO:coordinate\n" in front; no @PG line is added), the records in order, and the end-of-file block.
+ * csv_bam_sort_host is the core's host form: no context, the reader's host framing, std::stable_sort and csv_bgzf_deflate_host - the
+ * same file byte for byte.  flags: 0 (none is defined).  out_path is created only after the verdict and removed when a later step
+ * fails; the caller owns the rule for a file that exists (cutesv_amd.bam.sort_bam writes beside the target and renames).
+ * CSV_E_CAPACITY, before the first window is read, with a csv_bam_error text that names both numbers: the inflated stream plus one
+ * slice exceed max_bytes (<= 0: half of the device's free memory at the call; the host form: no limit).  Files beyond the budget are
+ * not sorted here: no run files, no merge.  CSV_E_INVALID with the text "cannot sort: record <ordinal> ..." and nothing written: a refID
+ * outside [-1, n_ref) or a pos below -1; the texts are the same on both forms.  CSV_E_NOMEM with a text: a table that cannot be
+ * allocated.  A damaged block or a broken record chain gives the reader's own error.  The sort counts as a read: a device chunk
+ * handed out before it is dead; an index the reader has stays.
+ * csv_bam_sort_stats, of the last sort: counts[10] = records, inversions (adjacent pairs key[i] < key[i - 1] of the input: 0 means it
+ * was in order), inflated bytes of the input, bytes of the sorted stream, bytes of the file, BGZF blocks (the end-of-file block
+ * included), slices, radix passes run (0 on the host form), bytes copied up and down (0 on the host form); ms[4] = device time of the
+ * key kernel, of the passes with the prefix sums, of the gather, of the compressor.  csv_bam_sort_blocks: the block table {uoff, coff,
+ * isize} of the file, one row per block; *need = the rows; CSV_E_STATE: nothing was sorted; CSV_E_CAPACITY: cap is below *need. */
+int csv_bam_sort(csv_bam* bam, csv_ctx* ctx, const char* out_path, int64_t max_bytes, int32_t slice_blocks, int32_t flags);
+int csv_bam_sort_host(csv_bam* bam, const char* out_path, int64_t max_bytes, int32_t slice_blocks, int32_t flags);
+int csv_bam_sort_stats(const csv_bam* bam, int64_t* counts, double* ms);
+int csv_bam_sort_blocks(const csv_bam* bam, int64_t* uoff, int64_t* coff, uint32_t* isize, int64_t cap, int64_t* need);
+
 /* BGZF inflate on the device: the raw-deflate payloads of n_blocks BGZF blocks -> their bytes, one wavefront
  * per block.  Block k's payload is comp[in_off[k] .. + in_len[k]), its out_len[k] (= ISIZE) bytes go to out[out_off[k] ..), crc[k]
  * is the CRC32 of its trailer; comp, out and status are host memory.
