@@ -108,6 +108,11 @@ SYMBOLS = [
     ("csv_bam_sort_host", C.c_int, [C.c_void_p, C.c_char_p, C.c_int64, C.c_int32, C.c_int32]),
     ("csv_bam_sort_stats", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     ("csv_bam_sort_blocks", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]),
+    ("csv_sam_to_bam", C.c_int, [C.c_void_p, C.c_char_p, C.c_char_p, C.c_int64, C.c_int32]),
+    ("csv_sam_to_bam_host", C.c_int, [C.c_char_p, C.c_char_p, C.c_int64, C.c_int32, C.c_char_p, C.c_int]),
+    ("csv_sam_stats", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("csv_sam_records", C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.c_void_p, C.c_char_p,
+                                  C.c_int]),
     ("csv_bgzf_inflate", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32,
                                    C.c_void_p, C.POINTER(C.c_double)]),
     ("csv_bgzf_deflate", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(C.c_int64), C.c_int32,

@@ -730,6 +730,8 @@ def sort_bam(path, out, ctx=None, route="device", inflate=None, frame=None, thre
     stream plus one slice (None: half of the device's free memory; no limit on the host route); a file beyond it raises BamError
     before anything is read.  slice_blocks: BGZF blocks of 65280 bytes per slice (None: 256).  index: False, "bai" (or True) or
     "csi" - BamFile(out).build_index(write=True) on the written file, on the same routes.
+    A SAM input (plain text, told by content: sam.is_sam) is converted first - sam.sam_to_bam on the same `route`, into a temporary BAM
+    beside `out` that is removed at the end - and stats["sam"] holds that conversion's stats.
     The file is written through a temporary file beside `out` and os.replace.  FileExistsError, before anything is read, when `out`
     exists and overwrite is not set.  BamError "cannot sort: record N ...": a refID the header does not have or a pos below -1; nothing
     is written.  -> stats: records, inversions (0: the input was in order), inflated_bytes, stream_bytes, out_bytes, blocks, slices,
@@ -749,6 +751,22 @@ def sort_bam(path, out, ctx=None, route="device", inflate=None, frame=None, thre
     if wants_ctx and ctx is None:
         from . import engine
         own = ctx = engine.Context(0)
+    from . import sam as sam_mod
+    if sam_mod.is_sam(path):
+        # SAM text: converted on the sort's route into a temporary BAM beside `out`, which is then sorted as any other
+        fd, converted = tempfile.mkstemp(prefix=os.path.basename(out) + ".", suffix=".sam.bam", dir=os.path.dirname(out) or ".")
+        os.close(fd)
+        try:
+            sam_stats = sam_mod.sam_to_bam(path, converted, ctx=ctx, route=route, threads=threads, overwrite=True)
+            stats = sort_bam(converted, out, ctx=ctx, route=route, inflate=inflate, frame=frame, threads=threads, max_bytes=max_bytes, slice_blocks=slice_blocks, index=index,
+                             overwrite=overwrite, window_blocks=window_blocks)
+            stats["sam"] = sam_stats
+            return stats
+        finally:
+            if os.path.exists(converted):
+                os.unlink(converted)
+            if own is not None:
+                own.close()
     if isinstance(inflate, str) and inflate == "device":
         inflate = ctx
     if route == "host" and not (frame is None or frame == "host"):
@@ -813,7 +831,7 @@ def sort_bam_host_twin(path, out, **kw):
 def main(argv=None):
     import argparse
     ap = argparse.ArgumentParser(prog="python -m cutesv_amd.bam", description="header and per-contig record counts of a coordinate-sorted BAM file")
-    ap.add_argument("bam")
+    ap.add_argument("bam", help="the BAM file; with --sort also SAM text")
     ap.add_argument("--chrom", default=None, help="only this contig")
     ap.add_argument("--threads", type=int, default=None, help="host threads of the inflate (default: min(16, CPUs))")
     ap.add_argument("--dump-columns", metavar="DIR", default=None, help="write the decoded columns of --chrom (host decode) as DIR/<column>.npy")

@@ -24,7 +24,8 @@ What differs from cuteSV, on purpose:
     more) and the cut is cuteSV's.  A .csi beside the file serves as a .bai does.  The calls do not depend on the
     cut - except with -include_bed, where a task's reads are tested against the regions of that task only: there the uniform cut
     can differ from cuteSV's on contigs whose batch it would have shrunk.
-  * --sort_input takes a BAM file in any order - what `minimap2 -a | samtools view -b` writes: it is sorted by coordinate first
+  * --sort_input takes a BAM file in any order - what `minimap2 -a | samtools view -b` writes - or the SAM text `minimap2 -a` writes
+    itself (told by content; converted first on the same route): it is sorted by coordinate first
     (bam.sort_bam; "device": keys, order, gather and compression on the GPU, "host": the same on the host) into
     WORK_DIR/<BAM's name minus .bam>.sorted.bam, and the run goes on with that file exactly as with a sorted input; the file is removed at
     the end unless --retain_work_dir is set.  Without the option an unsorted input is refused, as before.
@@ -161,9 +162,9 @@ def _write_bgzf(path, text, route):
 
 
 def sorted_input_path(work_dir, bam_path):
-    """where --sort_input writes the sorted file: WORK_DIR/<the BAM's name minus .bam>.sorted.bam"""
+    """where --sort_input writes the sorted file: WORK_DIR/<the input's name minus .bam or .sam>.sorted.bam"""
     base = os.path.basename(bam_path)
-    return os.path.join(work_dir, (base[:-4] if base.endswith(".bam") else base) + ".sorted.bam")
+    return os.path.join(work_dir, (base[:-4] if base.endswith((".bam", ".sam")) else base) + ".sorted.bam")
 
 
 def _sort_input(a, own):
@@ -175,6 +176,10 @@ def _sort_input(a, own):
     _log("%s is sorted by coordinate into %s (--sort_input %s)" % (a.input, out, own.sort_input))
     frame = own.frame if own.sort_input == "device" else None
     st = bam_mod.sort_bam(a.input, out, route=own.sort_input, inflate=own.inflate, frame=frame, threads=a.threads)
+    if st.get("sam") is not None:
+        sm = st["sam"]
+        _log("%-16s %10.1f ms  (SAM text: %d lines, %d -> %d bytes in %d blocks, %d windows; device: lines %.2f, plan %.2f, write %.2f, deflate %.2f ms)"
+             % ("sam_to_bam", sm["ms"], sm["lines"], sm["text_bytes"], sm["out_bytes"], sm["blocks"], sm["windows"], sm["ms_lines"], sm["ms_plan"], sm["ms_write"], sm["ms_deflate"]))
     _log("%-16s %10.1f ms  (%d records, %d adjacent inversions, %d -> %d bytes in %d blocks; device: keys %.2f, sort %.2f, gather %.2f, deflate %.2f ms)"
          % ("sort_input", st["ms"], st["records"], st["inversions"], st["inflated_bytes"], st["out_bytes"], st["blocks"], st["ms_keys"], st["ms_sort"], st["ms_gather"], st["ms_deflate"]))
     return out

@@ -24,7 +24,8 @@
 // And k_ref_gather: base ranges of a BGZF-compressed FASTA cut out of the blocks k_bgzf_inflate left on the device, one wavefront per
 // output tile over ref_core.h; and k_fai_tiles / k_fai_events: the lines of such a text as the event rows its .fai
 // is assembled from.  And the coordinate sort of a whole file (sort_core.h): k_sort_keys, k_sort_dst_tiles /
-// k_sort_dst_scan and k_sort_gather, the kernel every byte of the file passes through on its way into sorted order.
+// k_sort_dst_scan and k_sort_gather, the kernel every byte of the file passes through on its way into sorted order.  And the way in from an
+// aligner's text (sam_core.h): k_sam_marks, k_sam_plan, k_sam_small and k_sam_bulk turn a window of SAM lines into BAM records.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -36,6 +37,7 @@
 #include "index_core.h"
 #include "ref_core.h"
 #include "sort_core.h"
+#include "sam_core.h"
 
 namespace csv {
 
@@ -981,6 +983,513 @@ __global__ __launch_bounds__(256) void k_sort_gather(SortGatherArgs A)
         }
         *(uint4*)(A.out + at) = v;
     }
+}
+
+// ------------------------------------------------------------------------------------ SAM text to BAM records
+// A window of SAM text - whole alignment lines, the last byte a line break - lies in device memory; sam_core.h holds the rules.
+//   k_sam_marks<false / true>   the line breaks and the tabs of the window as two sorted position lists.  A workgroup takes SAM_TILE bytes,
+//                    a wavefront a quarter, a lane 16 bytes a step (one aligned load); a lane's marks are a 16-bit mask, their places the
+//                    wave scan of the popcounts over the wavefront's running count; the count pass leaves the wavefronts' counts, the write
+//                    pass sums those in front (block_prefix_of).  A 4 MB line and a 200-byte line cost the same per byte.
+//   k_sam_plan       one wavefront per line: its fields are cuts of the tab list (two wave-uniform searches), every number is read a digit
+//                    per lane (sam_wave_int / sam_wave_float), the CIGAR and the tags lanes striding with ballots.  Out: the row (what the
+//                    write pass needs again) and the record's size - or the mark "host item": every line outside the strict grammar,
+//                    which means every line that may be refused, and B:f arrays.  The host runs sam_core.h's serial rule on those lines.
+//   (one exclusive 64-bit scan of the sizes - k_sort_dst_tiles / k_sort_dst_scan, the sort's - gives dst)
+//   k_sam_small      one wavefront per record: block_size, the fixed fields, the name, the CIGAR words (or the placeholder and the
+//                    CG:B:I tag) and the tags; a float outside the fast path leaves a patch row
+//   k_sam_bulk       the hot path, output-driven as k_sort_gather is: a wavefront owns SAM_BULK_TILE bytes of the stream buffer, brackets
+//                    the records that feed it with two searches over dst, and every lane writes aligned 16-byte pieces of SEQ (32 text
+//                    bytes -> 16) and QUAL (16 -> 16, a byte below 33 reported by atomicMin of the line's ordinal); a piece that holds a
+//                    region's edge is written byte by byte, and only the bytes that belong to SEQ or QUAL
+//   k_sam_items / k_sam_item_len / k_sam_patch   the host's records copied into their places, their sizes, the patched floats
+// Bounds.  Text is read at [0, n) only, except sort_ld16's aligned dwords (at most 3 bytes in front of a SEQ or QUAL field, which
+// never begins a window, and 19 behind its last piece: the text buffer has 64 bytes of slack).  A record's bytes are written inside
+// [base + dst[r], base + dst[r + 1]) only: plan and write pass call the same functions on the same text, so sizes and bytes agree.
+constexpr int SAM_TILE = 32768, SAM_WAVE_BYTES = SAM_TILE / 4;
+// Bytes of the stream buffer per wavefront of k_sam_bulk: 64 lanes x 16 bytes x 4 rounds, k_sort_gather's choice for its reasons
+// (two bracket searches amortised over 256 stores); chosen, not measured.
+constexpr int SAM_BULK_TILE = 4096;
+constexpr int SAM_ROW_HOST = 1, SAM_ROW_CG = 2, SAM_ROW_QSTAR = 4;
+
+struct SamRow { i64 seq_text, qual_text, ref_len; int n_ops, l_seq, seq_out, flags; i64 tab0; int ntab, pad; };
+struct SamPatch { i64 out_off, text_off; int len, pad; };
+
+struct SamArgs {
+    const uint8_t* t; i64 n;        // the window: n > 0 bytes, the last a line break
+    int* cnt_nl; int* cnt_tab;      // 4 per tile of SAM_TILE bytes
+    i64* nl; i64* tab; i64 n_lines, n_tabs;
+    SamNames names;
+    SamRow* rows; i64* len; const i64* dst;
+    int* items; int* counters;      // the host items' lines (n_lines entries); [0] their count, [1] the patch rows, [2] the CG records
+    u64* verdict;                   // the lowest line ordinal (in the window) with a QUAL byte below 33; ~0: none
+    uint8_t* out; i64 base, total;  // the stream buffer; the records begin at base and take total bytes
+    SamPatch* patches; i64 patch_cap;
+};
+
+template <bool WRITE> __global__ __launch_bounds__(256) void k_sam_marks(SamArgs A)
+{
+    __shared__ i64 red[4];
+    const int t = blockIdx.x, w = threadIdx.x >> 6;
+    const i64 lo = (i64)t * SAM_TILE + (i64)w * SAM_WAVE_BYTES, hi = lo + SAM_WAVE_BYTES < A.n ? lo + SAM_WAVE_BYTES : A.n;
+    i64 at_nl = 0, at_tab = 0;
+    if (WRITE) {
+        at_nl = block_prefix_of(A.cnt_nl, 4 * t, red);
+        at_tab = block_prefix_of(A.cnt_tab, 4 * t, red);
+        for (int k = 0; k < w; k++) { at_nl += A.cnt_nl[4 * (i64)t + k]; at_tab += A.cnt_tab[4 * (i64)t + k]; }
+    }
+    for (i64 p0 = lo; p0 < hi; p0 += 64 * 16) {
+        const i64 p = p0 + (i64)lane_id() * 16;
+        uint32_t m_nl = 0, m_tab = 0;
+        if (p < hi) {
+            const uint4 v = *(const uint4*)(A.t + p);           // (aligned: the buffer and every p are multiples of 16; the buffer has slack)
+            const uint32_t x[4] = {v.x, v.y, v.z, v.w};
+            for (int j = 0; j < 16; j++) {
+                const uint32_t c = (x[j >> 2] >> (8 * (j & 3))) & 255u;
+                if (p + j < hi) { m_nl |= (uint32_t)(c == '\n') << j; m_tab |= (uint32_t)(c == '\t') << j; }
+            }
+        }
+        const int c_nl = __popc(m_nl), c_tab = __popc(m_tab);
+        const int i_nl = wave_incl_scan_i32(c_nl), i_tab = wave_incl_scan_i32(c_tab);
+        if (WRITE) {
+            i64 k = at_nl + i_nl - c_nl;
+            for (uint32_t m = m_nl; m; m &= m - 1, k++) if (k < A.n_lines) A.nl[k] = p + __builtin_ctz(m);
+            k = at_tab + i_tab - c_tab;
+            for (uint32_t m = m_tab; m; m &= m - 1, k++) if (k < A.n_tabs) A.tab[k] = p + __builtin_ctz(m);
+        }
+        at_nl += __builtin_amdgcn_readlane(i_nl, 63); at_tab += __builtin_amdgcn_readlane(i_tab, 63);
+    }
+    if (!WRITE && lane_id() == 0) { A.cnt_nl[4 * (i64)t + w] = (int)at_nl; A.cnt_tab[4 * (i64)t + w] = (int)at_tab; }
+}
+
+__device__ __forceinline__ u64 sam_bits(int a, int b) { return a >= b ? 0ull : (b >= 64 ? ~0ull : (1ull << b) - 1ull) & ~((1ull << a) - 1ull); }     // lanes [a, b), a < 64
+
+// the first index in [0, n) with a[index] >= x (n: none); wave-uniform
+__device__ __forceinline__ i64 sam_lower(const i64* a, i64 n, i64 x)
+{
+    i64 lo = 0, hi = n;
+    while (lo < hi) {
+        const i64 m = lo + (hi - lo) / 2;
+        if (a[m] < x) lo = m + 1; else hi = m;
+    }
+    return lo;
+}
+
+// sam_int_text, a digit per lane
+__device__ __forceinline__ bool sam_wave_int(const uint8_t* t, i64 b, i64 e, bool sign_ok, i64* v)
+{
+    const i64 n = e - b;
+    if (n < 1 || n > 19) return false;
+    const uint32_t c0 = t[b];
+    const bool sg = sign_ok && (c0 == '-' || c0 == '+');
+    const int s = sg ? 1 : 0, nd = (int)n - s, l = lane_id();
+    if (nd < 1 || nd > 18) return false;
+    const uint32_t c = l < n ? t[b + l] : 0u;
+    const bool isd = l >= s && l < n && sam_digit(c);
+    if (__popcll(__ballot(isd ? 1 : 0)) != nd) return false;
+    const i64 sum = wave_sum_i64(isd ? (i64)((u64)(c - '0') * sam_pow10((int)n - 1 - l)) : 0);
+    *v = sg && c0 == '-' ? -sum : sum;
+    return true;
+}
+
+// sam_float_text, a byte per lane: 0 not the grammar, 1 slow, 2 fast
+__device__ __forceinline__ int sam_wave_float(const uint8_t* t, i64 b, i64 e, float* f)
+{
+    const i64 n64 = e - b;
+    if (n64 < 1 || n64 > SAM_NUM_MAX) return 0;
+    const int n = (int)n64, l = lane_id();
+    const bool in = l < n;
+    const uint32_t c = in ? t[b + l] : 0u;
+    const u64 dig = __ballot(in && sam_digit(c) ? 1 : 0), dot = __ballot(in && c == '.' ? 1 : 0), ee = __ballot(in && (c == 'e' || c == 'E') ? 1 : 0);
+    const u64 sg = __ballot(in && (c == '-' || c == '+') ? 1 : 0), minus = __ballot(in && c == '-' ? 1 : 0);
+    const int s = (int)(sg & 1ull);
+    if (__popcll(ee) > 1) return 0;
+    const int E = ee ? __builtin_ctzll(ee) : n;
+    if (E <= s) return 0;
+    const u64 mm = sam_bits(s, E), md = dig & mm, mdot = dot & mm;
+    if (__popcll(mdot) > 1 || (md | mdot) != mm) return 0;
+    int nfrac = 0;
+    if (mdot) {
+        const int d = __builtin_ctzll(mdot);
+        if (d == s || d == E - 1) return 0;
+        nfrac = E - 1 - d;
+    }
+    SamFloat q{(int)(minus & 1ull), 0, 0, 0, 0};
+    i64 expv = 0;
+    bool eneg = false;
+    if (ee) {
+        int x0 = E + 1;
+        if (x0 < n && ((sg >> x0) & 1ull)) { eneg = (minus >> x0) & 1ull; x0++; }
+        if (x0 >= n) return 0;
+        const u64 xm = sam_bits(x0, n);
+        if ((dig & xm) != xm) return 0;
+        q.nexp = n - x0;
+        if (q.nexp <= 4) expv = wave_sum_i64(((xm >> l) & 1ull) ? (i64)((u64)(c - '0') * sam_pow10(n - 1 - l)) : 0);
+    }
+    const u64 nz = __ballot(((md >> l) & 1ull) && c != '0' ? 1 : 0);
+    if (nz) {
+        const u64 sig = md & ~((1ull << __builtin_ctzll(nz)) - 1ull);
+        q.nsig = __popcll(sig);
+        if (q.nsig <= 15) {
+            const int r = __popcll(sig & (l >= 63 ? 0ull : ~0ull << (l + 1)));
+            q.mant = (u64)wave_sum_i64(((sig >> l) & 1ull) ? (i64)((u64)(c - '0') * sam_pow10(r)) : 0);
+        }
+    }
+    q.exp10 = (eneg ? -expv : expv) - nfrac;
+    return sam_float_class(q, f);
+}
+
+// sam_name_find, 64 bytes a comparison step
+__device__ __forceinline__ int sam_wave_name(const SamNames& N, const uint8_t* t, i64 b, i64 e)
+{
+    const i64 qn = e - b;
+    int lo = 0, hi = N.n - 1;
+    while (lo <= hi) {
+        const int m = lo + (hi - lo) / 2;
+        const i64 nb = N.off[m], nn = N.off[m + 1] - nb, mn = qn < nn ? qn : nn;
+        int cmp = 0;
+        for (i64 k = 0; k < mn && !cmp; k += 64) {
+            const i64 j = k + lane_id();
+            const int a = j < mn ? t[b + j] : 0, c = j < mn ? N.blob[nb + j] : 0;
+            const u64 diff = __ballot(a != c ? 1 : 0);
+            if (diff) {
+                const int d = __builtin_ctzll(diff);
+                cmp = __shfl(a, d) < __shfl(c, d) ? -1 : 1;
+            }
+        }
+        if (!cmp) cmp = qn < nn ? -1 : qn > nn ? 1 : 0;
+        if (cmp == 0) return N.id[m];
+        if (cmp < 0) hi = m - 1; else lo = m + 1;
+    }
+    return -2;
+}
+
+// the CIGAR text t[b, e), lanes striding: its operations counted (and, out != NULL, written as BAM words at out, which has their room),
+// the reference bases they span.  false: not a CIGAR.  A lane that stands on an operation reads its own length backwards, 10 bytes at most
+__device__ __forceinline__ bool sam_wave_cigar(const uint8_t* t, i64 b, i64 e, uint8_t* out, i64* n_ops, i64* ref_len)
+{
+    *n_ops = 0; *ref_len = 0;
+    if (e - b == 1 && t[b] == '*') return true;
+    if (e <= b || sam_digit(t[e - 1])) return false;
+    i64 ops = 0, rl = 0;
+    bool ok = true;
+    for (i64 p0 = b; p0 < e; p0 += 64) {
+        const i64 i = p0 + lane_id();
+        const bool in = i < e;
+        const uint32_t c = in ? t[i] : (uint32_t)'0';
+        const int op = sam_digit(c) ? -1 : sam_cigar_op(c);
+        bool bad = in && !sam_digit(c) && op < 0, is_op = in && op >= 0;
+        i64 len = 0;
+        if (is_op) {
+            int nd = 0;
+            i64 mul = 1;
+            for (i64 j = i - 1; j >= b && nd < 10 && sam_digit(t[j]); j--, nd++, mul *= 10) len += (i64)(t[j] - '0') * mul;
+            if (nd == 0 || nd > 9 || len >= (1ll << 28)) { bad = true; is_op = false; }
+        }
+        const u64 m = __ballot(is_op ? 1 : 0);
+        if (out && is_op) sam_put32(out + 4 * (ops + __popcll(m & lanemask_lt())), (uint32_t)len << 4 | (uint32_t)op);
+        rl += wave_sum_i64(is_op && sam_op_on_ref(op) ? len : 0);
+        ops += __popcll(m);
+        if (__ballot(bad ? 1 : 0)) ok = false;
+    }
+    *n_ops = ops; *ref_len = rl;
+    return ok;
+}
+
+// One optional field t[b, e) as a BAM tag: its bytes, or -1 when the text is outside the device's grammar (the line becomes a host item).
+// WRITE: the tag is written at o (offset o_abs of the stream buffer); a slow float leaves zeros and a patch row
+template <bool WRITE> __device__ __forceinline__ i64 sam_wave_tag(const SamArgs& A, i64 b, i64 e, uint8_t* o, i64 o_abs)
+{
+    const uint8_t* t = A.t;
+    const i64 n = e - b;
+    const int l = lane_id();
+    if (n < 5 || t[b + 2] != ':' || t[b + 4] != ':') return -1;
+    const uint32_t type = t[b + 3];
+    const i64 vb = b + 5, vn = n - 5;
+    if (WRITE && l < 2) o[l] = t[b + l];
+    switch (type) {
+    case 'A':
+        if (vn != 1) return -1;
+        if (WRITE && l == 0) { o[2] = 'A'; o[3] = t[vb]; }
+        return 4;
+    case 'i': {
+        i64 x;
+        int w;
+        if (!sam_wave_int(t, vb, e, true, &x)) return -1;
+        const int ty = sam_int_type(x, &w);
+        if (!ty) return -1;
+        if (WRITE) { if (l == 0) o[2] = (uint8_t)ty; if (l < w) o[3 + l] = (uint8_t)((u64)x >> (8 * l)); }
+        return 3 + w;
+    }
+    case 'f': {
+        float f = 0;
+        const int cls = sam_wave_float(t, vb, e, &f);
+        if (cls == 0) return -1;
+        if (WRITE) {
+            if (l == 0) o[2] = 'f';
+            if (l < 4) o[3 + l] = cls == 2 ? (uint8_t)(__float_as_uint(f) >> (8 * l)) : (uint8_t)0;
+            if (cls == 1 && l == 0) {
+                const int k = atomicAdd(&A.counters[1], 1);
+                if (k < A.patch_cap) A.patches[k] = SamPatch{o_abs + 3, vb, (int)vn, 0};
+            }
+        }
+        return 7;
+    }
+    case 'H': {
+        if (vn & 1) return -1;
+        bool bad = false;
+        for (i64 k = l; k < vn; k += 64) {
+            const uint32_t c = t[vb + k];
+            if (!(sam_digit(c) || (c >= 'A' && c <= 'F') || (c >= 'a' && c <= 'f'))) bad = true;
+        }
+        if (__ballot(bad ? 1 : 0)) return -1;
+    }
+    /* fall through */
+    case 'Z':
+        if (WRITE) {
+            if (l == 0) { o[2] = (uint8_t)type; o[3 + vn] = 0; }
+            for (i64 k = l; k < vn; k += 64) o[3 + k] = t[vb + k];
+        }
+        return 4 + vn;
+    case 'B': {
+        if (vn < 1 || (vn > 1 && t[vb + 1] != ',')) return -1;
+        const uint32_t sub = t[vb];
+        i64 lo, hi;
+        const int w = sam_sub_width(sub, &lo, &hi);
+        if (!w || sub == 'f') return -1;                          // (B:f: a host item)
+        i64 count = 0;
+        bool ok = true;
+        for (i64 p0 = vb + 1; p0 < e; p0 += 64) {
+            const i64 i = p0 + l;
+            const bool comma = i < e && t[i] == ',';
+            const u64 m = __ballot(comma ? 1 : 0);
+            bool bad = false;
+            if (comma) {                                          // the element behind this lane's comma: 19 bytes at most
+                i64 q = i + 1, x = 0;
+                while (q < e && t[q] != ',' && q - i <= 20) q++;
+                if ((q < e && t[q] != ',') || !sam_int_text(t + i + 1, q - i - 1, true, &x) || x < lo || x > hi) bad = true;
+                else if (WRITE) {
+                    uint8_t* d = o + 8 + (count + __popcll(m & lanemask_lt())) * w;
+                    for (int k = 0; k < w; k++) d[k] = (uint8_t)((u64)x >> (8 * k));
+                }
+            }
+            if (__ballot(bad ? 1 : 0)) ok = false;
+            count += __popcll(m);
+        }
+        if (!ok || count > 0xffffffffll) return -1;
+        if (WRITE && l == 0) { o[2] = 'B'; o[3] = (uint8_t)sub; sam_put32(o + 4, (uint32_t)count); }
+        return 8 + count * w;
+    }
+    default: return -1;
+    }
+}
+
+// the line's first 11 fields as cuts of the tab list: false when it has fewer.  fb / fe: their begins and ends
+__device__ __forceinline__ bool sam_fields(const SamArgs& A, i64 line, i64& beg, i64& end, i64& tab0, i64& ntab, i64* fb, i64* fe)
+{
+    beg = line == 0 ? 0 : A.nl[line - 1] + 1; end = A.nl[line];
+    tab0 = sam_lower(A.tab, A.n_tabs, beg);
+    ntab = sam_lower(A.tab, A.n_tabs, end) - tab0;
+    if (ntab < 10) return false;
+    for (int k = 0; k < 11; k++) {
+        fb[k] = k == 0 ? beg : A.tab[tab0 + k - 1] + 1;
+        fe[k] = k < ntab ? A.tab[tab0 + k] : end;
+    }
+    return true;
+}
+
+__global__ __launch_bounds__(256) void k_sam_plan(SamArgs A)
+{
+    const i64 line = ((i64)blockIdx.x * 256 + threadIdx.x) >> 6;
+    if (line >= A.n_lines) return;
+    const uint8_t* t = A.t;
+    SamRow R{0, 0, 0, 0, 0, 0, SAM_ROW_HOST, 0, 0, 0};
+    i64 size = 0;
+    i64 beg, end, tab0, ntab, fb[11], fe[11];
+    do {                                                          // (left by `break` where the line becomes a host item; wave-uniform)
+        if (!sam_fields(A, line, beg, end, tab0, ntab, fb, fe)) break;
+        if (t[end - 1] == '\r' || t[beg] == '@') break;
+        bool empty = false;
+        for (int k = 0; k < 11; k++) empty |= fe[k] <= fb[k];
+        if (empty) break;
+        const i64 l_name = fe[0] - fb[0];
+        if (l_name > SAM_QNAME_MAX) break;
+        i64 v;
+        if (!sam_wave_int(t, fb[1], fe[1], false, &v) || v > 65535) break;
+        if (!sam_wave_int(t, fb[3], fe[3], false, &v) || v > 2147483647) break;
+        if (!sam_wave_int(t, fb[4], fe[4], false, &v) || v > 255) break;
+        if (!sam_wave_int(t, fb[7], fe[7], false, &v) || v > 2147483647) break;
+        if (!sam_wave_int(t, fb[8], fe[8], true, &v) || v > 2147483647 || v < -2147483647) break;
+        if (!(fe[2] - fb[2] == 1 && t[fb[2]] == '*') && sam_wave_name(A.names, t, fb[2], fe[2]) == -2) break;
+        if (!(fe[6] - fb[6] == 1 && (t[fb[6]] == '*' || t[fb[6]] == '=')) && sam_wave_name(A.names, t, fb[6], fe[6]) == -2) break;
+        i64 n_ops, ref_len;
+        if (!sam_wave_cigar(t, fb[5], fe[5], nullptr, &n_ops, &ref_len)) break;
+        const i64 l_seq = fe[9] - fb[9] == 1 && t[fb[9]] == '*' ? 0 : fe[9] - fb[9];
+        const bool qstar = fe[10] - fb[10] == 1 && t[fb[10]] == '*';
+        if (!qstar && fe[10] - fb[10] != l_seq) break;
+        i64 tags = 0;
+        bool ok = true;
+        for (i64 k = 11; k <= ntab && ok; k++) {
+            const i64 b = A.tab[tab0 + k - 1] + 1, e = k < ntab ? A.tab[tab0 + k] : end;
+            const i64 sz = sam_wave_tag<false>(A, b, e, nullptr, 0);
+            if (sz < 0) ok = false; else tags += sz;
+        }
+        if (!ok) break;
+        const bool cg = n_ops > SAM_MAX_OPS;
+        const i64 seq_out = 36 + l_name + 1 + 4 * (cg ? 2 : n_ops);
+        size = seq_out + (l_seq + 1) / 2 + l_seq + tags + (cg ? 8 + 4 * n_ops : 0);
+        if (size - 4 > 2147483647ll) { size = 0; break; }
+        R = SamRow{fb[9], fb[10], ref_len, (int)n_ops, (int)l_seq, (int)seq_out, (cg ? SAM_ROW_CG : 0) | (qstar ? SAM_ROW_QSTAR : 0), tab0, (int)ntab, 0};
+    } while (false);
+    if (lane_id() == 0) {
+        A.rows[line] = R; A.len[line] = size;
+        if (R.flags & SAM_ROW_HOST) A.items[atomicAdd(&A.counters[0], 1)] = (int)line;
+        if (R.flags & SAM_ROW_CG) atomicAdd(&A.counters[2], 1);
+    }
+}
+
+__global__ __launch_bounds__(256) void k_sam_small(SamArgs A)
+{
+    const i64 line = ((i64)blockIdx.x * 256 + threadIdx.x) >> 6;
+    if (line >= A.n_lines) return;
+    const SamRow R = A.rows[line];
+    if (R.flags & SAM_ROW_HOST) return;
+    const uint8_t* t = A.t;
+    const int l = lane_id();
+    i64 beg, end, tab0, ntab, fb[11], fe[11];
+    if (!sam_fields(A, line, beg, end, tab0, ntab, fb, fe)) return;
+    const i64 o_rec = A.base + A.dst[line], size = A.dst[line + 1] - A.dst[line];
+    uint8_t* rec = A.out + o_rec;
+    SamFixed x{};
+    i64 v = 0;
+    sam_wave_int(t, fb[1], fe[1], false, &v); x.flag = (uint32_t)v;
+    sam_wave_int(t, fb[3], fe[3], false, &v); x.pos = (int32_t)(v - 1);
+    sam_wave_int(t, fb[4], fe[4], false, &v); x.mapq = (uint32_t)v;
+    sam_wave_int(t, fb[7], fe[7], false, &v); x.next_pos = (int32_t)(v - 1);
+    sam_wave_int(t, fb[8], fe[8], true, &v); x.tlen = (int32_t)v;
+    x.refid = fe[2] - fb[2] == 1 && t[fb[2]] == '*' ? -1 : sam_wave_name(A.names, t, fb[2], fe[2]);
+    if (fe[6] - fb[6] == 1 && t[fb[6]] == '*') x.next_refid = -1;
+    else if (fe[6] - fb[6] == 1 && t[fb[6]] == '=') x.next_refid = x.refid;
+    else x.next_refid = sam_wave_name(A.names, t, fb[6], fe[6]);
+    const i64 l_name = fe[0] - fb[0];
+    const bool cg = R.flags & SAM_ROW_CG;
+    x.l_name = (uint32_t)l_name + 1; x.n_cigar = cg ? 2u : (uint32_t)R.n_ops; x.l_seq = (uint32_t)R.l_seq; x.bin = sam_bin(x.pos, R.ref_len);
+    if (l == 0) { sam_put32(rec, (uint32_t)(size - 4)); sam_put_fixed(rec + 4, x); rec[36 + l_name] = 0; }
+    for (i64 k = l; k < l_name; k += 64) rec[36 + k] = t[fb[0] + k];
+    uint8_t* oc = rec + 36 + l_name + 1;
+    i64 n_ops, ref_len;
+    if (cg) { if (l == 0) { sam_put32(oc, (uint32_t)R.l_seq << 4 | 4u); sam_put32(oc + 4, (uint32_t)R.ref_len << 4 | 3u); } }
+    else sam_wave_cigar(t, fb[5], fe[5], oc, &n_ops, &ref_len);
+    i64 ot = R.seq_out + (R.l_seq + 1) / 2 + R.l_seq;             // in the record
+    for (i64 k = 11; k <= ntab; k++) {
+        const i64 b = A.tab[tab0 + k - 1] + 1, e = k < ntab ? A.tab[tab0 + k] : end;
+        const i64 sz = sam_wave_tag<true>(A, b, e, rec + ot, o_rec + ot);
+        if (sz < 0) return;                                       // (the plan took this tag: never)
+        ot += sz;
+    }
+    if (cg) {
+        if (l == 0) { rec[ot] = 'C'; rec[ot + 1] = 'G'; rec[ot + 2] = 'B'; rec[ot + 3] = 'I'; sam_put32(rec + ot + 4, (uint32_t)R.n_ops); }
+        sam_wave_cigar(t, fb[5], fe[5], rec + ot + 8, &n_ops, &ref_len);
+    }
+}
+
+// the byte at in_rec of record r when it belongs to SEQ or QUAL (true), read from the text
+__device__ __forceinline__ bool sam_bulk_byte(const SamArgs& A, const SamRow& R, i64 r, i64 in_rec, uint32_t* b)
+{
+    const i64 s0 = R.seq_out, s1 = s0 + (R.l_seq + 1) / 2, q1 = s1 + R.l_seq;
+    if ((R.flags & SAM_ROW_HOST) || in_rec < s0 || in_rec >= q1) return false;
+    if (in_rec < s1) {
+        const i64 k = 2 * (in_rec - s0);
+        *b = sam_base_code(A.t[R.seq_text + k]) << 4 | (k + 1 < R.l_seq ? sam_base_code(A.t[R.seq_text + k + 1]) : 0u);
+        return true;
+    }
+    if (R.flags & SAM_ROW_QSTAR) { *b = 0xffu; return true; }
+    const uint32_t c = A.t[R.qual_text + (in_rec - s1)];
+    if (c < 33) atomicMin((unsigned long long*)A.verdict, (unsigned long long)r);
+    *b = (c - 33) & 255u;
+    return true;
+}
+
+__global__ __launch_bounds__(256) void k_sam_bulk(SamArgs A)
+{
+    const i64 tile = ((i64)blockIdx.x * 256 + threadIdx.x) >> 6;
+    const i64 end = A.base + A.total;
+    i64 t0 = tile * SAM_BULK_TILE, t1 = t0 + SAM_BULK_TILE < end ? t0 + SAM_BULK_TILE : end;
+    if (t0 >= end || t1 <= A.base || A.n_lines <= 0) return;
+    const i64 n = A.n_lines;
+    const i64 lo = sort_first_record(A.dst, 0, n - 1, (t0 > A.base ? t0 : A.base) - A.base), hi = sort_first_record(A.dst, lo, n - 1, t1 - 1 - A.base);
+    for (int q = 0; q < SAM_BULK_TILE / (64 * 16); q++) {
+        const i64 o = t0 + ((i64)q * 64 + lane_id()) * 16;       // in the stream buffer
+        if (o >= t1) break;
+        if (o + 16 <= A.base) continue;
+        i64 r = sort_first_record(A.dst, lo, hi, (o > A.base ? o : A.base) - A.base);
+        const SamRow R = A.rows[r];
+        const i64 in_rec = o - A.base - A.dst[r];
+        const i64 s0 = R.seq_out, s1 = s0 + (R.l_seq + 1) / 2, q1 = s1 + R.l_seq;
+        if (o >= A.base && !(R.flags & SAM_ROW_HOST) && in_rec >= s0 && in_rec + 16 <= s0 + R.l_seq / 2) {
+            // 16 bytes of SEQ out of 32 bases
+            const uint8_t* src = A.t + R.seq_text + 2 * (in_rec - s0);
+            const uint4 a = sort_ld16(src), b = sort_ld16(src + 16);
+            const uint32_t w[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+            uint32_t v[4];
+            for (int k = 0; k < 4; k++) {
+                const uint32_t x = w[2 * k], y = w[2 * k + 1];
+                v[k] = (sam_base_code(x & 255u) << 4 | sam_base_code((x >> 8) & 255u)) | (sam_base_code((x >> 16) & 255u) << 4 | sam_base_code(x >> 24)) << 8
+                     | (sam_base_code(y & 255u) << 4 | sam_base_code((y >> 8) & 255u)) << 16 | (sam_base_code((y >> 16) & 255u) << 4 | sam_base_code(y >> 24)) << 24;
+            }
+            *(uint4*)(A.out + o) = make_uint4(v[0], v[1], v[2], v[3]);
+        } else if (o >= A.base && !(R.flags & SAM_ROW_HOST) && in_rec >= s1 && in_rec + 16 <= q1) {
+            uint4 a = make_uint4(~0u, ~0u, ~0u, ~0u);
+            if (!(R.flags & SAM_ROW_QSTAR)) {
+                a = sort_ld16(A.t + R.qual_text + (in_rec - s1));
+                uint32_t w[4] = {a.x, a.y, a.z, a.w};
+                bool bad = false;
+                for (int k = 0; k < 4; k++) {
+                    uint32_t y = 0;
+                    for (int j = 0; j < 32; j += 8) { const uint32_t c = (w[k] >> j) & 255u; bad |= c < 33; y |= ((c - 33) & 255u) << j; }
+                    w[k] = y;
+                }
+                if (bad) atomicMin((unsigned long long*)A.verdict, (unsigned long long)r);
+                a = make_uint4(w[0], w[1], w[2], w[3]);
+            }
+            *(uint4*)(A.out + o) = a;
+        } else {
+            // a piece with an edge in it: byte by byte, and only the bytes of SEQ and QUAL
+            SamRow Q = R;
+            for (int j = 0; j < 16; j++) {
+                const i64 p = o + j;
+                if (p < A.base) continue;
+                if (p >= end) break;
+                while (p - A.base >= A.dst[r + 1]) { r++; Q = A.rows[r]; }
+                uint32_t b;
+                if (sam_bulk_byte(A, Q, r, p - A.base - A.dst[r], &b)) A.out[p] = (uint8_t)b;
+            }
+        }
+    }
+}
+
+struct SamItemArgs { const int* line; const i64* src_off; const i64* size; i64 n; const uint8_t* src; i64* len; const i64* dst; uint8_t* out; i64 base; };
+
+__global__ __launch_bounds__(256) void k_sam_item_len(SamItemArgs A)
+{
+    const i64 i = (i64)blockIdx.x * 256 + threadIdx.x;
+    if (i < A.n) A.len[A.line[i]] = A.size[i];
+}
+
+// one wavefront per host item: its record into its place
+__global__ __launch_bounds__(256) void k_sam_items(SamItemArgs A)
+{
+    const i64 i = ((i64)blockIdx.x * 256 + threadIdx.x) >> 6;
+    if (i >= A.n) return;
+    const uint8_t* s = A.src + A.src_off[i];
+    uint8_t* d = A.out + A.base + A.dst[A.line[i]];
+    for (i64 k = lane_id(); k < A.size[i]; k += 64) d[k] = s[k];
+}
+
+__global__ __launch_bounds__(256) void k_sam_patch(const SamPatch* P, const uint32_t* bits, i64 n, uint8_t* out)
+{
+    const i64 i = (i64)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) sam_put32(out + P[i].out_off, bits[i]);
 }
 
 }  // namespace csv

@@ -257,6 +257,20 @@ struct BamSortState {
     void own(std::vector<Buf*>& v) { v.insert(v.end(), {&arena, &hdr, &starts, &key, &len, &perm[0], &perm[1], &hist, &tot, &dst, &tiles, &verdict, &slice}); }
 };
 
+// SAM text -> BAM (stage_sam.hip.h).  Everything lives for one csv_sam_to_bam call and is grow-only between calls:
+// text - the window; nl / tab - its marks; rows / len / dst - the plan and its scan; stream - the window's part of the BAM stream, which
+// DeflateState's buffers compress where it lies; carry - the bytes of a partial last block on their way in front of the next window's
+// stream.  Nothing else of the context is touched but its stream, its staging block and its first three timing events.
+struct SamState {
+    Buf text, cnt, small, nl, tab, rows, len, dst, tiles, items, patches, stream, carry, names, names_tab, item_tab, item_bytes, patch_bits;
+    i64 carry_bytes = 0;
+    SamStats st;
+    std::vector<int> cnt_h, item_line;
+    std::vector<i64> nl_h, item_off, item_size;
+    std::vector<uint8_t> item_rec;
+    void own(std::vector<Buf*>& v) { v.insert(v.end(), {&text, &cnt, &small, &nl, &tab, &rows, &len, &dst, &tiles, &items, &patches, &stream, &carry, &names, &names_tab, &item_tab, &item_bytes, &patch_bits}); }
+};
+
 // ---- The state of the engine (stage_upload / stage_run / stage_results.hip.h): the path csv_batch_upload -> csv_batch_run ->
 // csv_batch_download / csv_batch_publish_* and the one-shot csv_cluster_batch.  One struct per concern, with the same kind of rule.
 
@@ -391,7 +405,7 @@ struct csv_ctx {
     BatchState bt; ReadsOrderState ro; ResultState res; TableState tab;
     // ---- the extraction-side stages (their lifetime rules: at the structs)
     PoolState pool; NameState nm; BamState bm; SaState sa; SeqState seq; VcfStrState vs; AlnState al; ReadsTabState rt;
-    RebuildState rb; CigarState cg; SplitState sp; InflateState inf; FrameState fr; IndexBuildState ixb; DeflateState dfl; RefState ref; VcfEmitState ve; BamSortState bs;
+    RebuildState rb; CigarState cg; SplitState sp; InflateState inf; FrameState fr; IndexBuildState ixb; DeflateState dfl; RefState ref; VcfEmitState ve; BamSortState bs; SamState sam;
 };
 
 namespace {

@@ -233,7 +233,7 @@ void csv_ctx_destroy(csv_ctx* c)
     (void)hipDeviceSynchronize();
     std::vector<Buf*> own = {&c->flush};
     c->ro.own(own); c->res.own(own); c->tab.own(own);
-    c->pool.own(own); c->sp.own(own); c->bm.own(own); c->sa.own(own); c->nm.own(own); c->seq.own(own); c->vs.own(own); c->al.own(own); c->rt.own(own); c->inf.own(own); c->fr.own(own); c->ixb.own(own); c->dfl.own(own); c->ref.own(own); c->ve.own(own); c->bs.own(own);
+    c->pool.own(own); c->sp.own(own); c->bm.own(own); c->sa.own(own); c->nm.own(own); c->seq.own(own); c->vs.own(own); c->al.own(own); c->rt.own(own); c->inf.own(own); c->fr.own(own); c->ixb.own(own); c->dfl.own(own); c->ref.own(own); c->ve.own(own); c->bs.own(own); c->sam.own(own);
     for (Buf* b : own) if (b->p) (void)hipFree(b->p);
     for (Arena* a : {&c->arena, &c->scratch, &c->bm.arena, &c->sa.arena, &c->nm.arena}) if (a->base) (void)hipFree(a->base);
     if (c->h_pin) (void)hipHostFree(c->h_pin);
@@ -321,6 +321,7 @@ int csv_cache_flush(csv_ctx* c, int64_t bytes)
 #include "stage_frame.hip.h"
 #include "stage_index.hip.h"
 #include "stage_bam_sort.hip.h"
+#include "stage_sam.hip.h"
 #include "stage_aln.hip.h"
 #include "stage_gates.hip.h"
 #include "stage_reads.hip.h"

@@ -1061,6 +1061,34 @@ int csv_bam_sort_host(csv_bam* bam, const char* out_path, int64_t max_bytes, int
 int csv_bam_sort_stats(const csv_bam* bam, int64_t* counts, double* ms);
 int csv_bam_sort_blocks(const csv_bam* bam, int64_t* uoff, int64_t* coff, uint32_t* isize, int64_t cap, int64_t* need);
 
+/* SAM text -> BAM file (csrc/sam_core.h): what `minimap2 -a` writes -> the file csv_bam_sort takes, with no other
+ * tool.  The leading @ lines become the header (text verbatim, references from the @SQ lines in order); every alignment line becomes
+ * one record by the rules of SAMv1 1.4 / 4.2: names looked up in the @SQ names, POS and PNEXT minus one, bin = reg2bin(pos, pos +
+ * max(reference length, 1)) & 0xffff, SEQ as 4-bit codes of =ACMGRSVTWYHKDBN without regard to case, QUAL minus 33 (`*`: 0xff), an `i`
+ * tag in the smallest of c C s S i I, `f` as (float) strtod(text), a CIGAR of more than 65535 operations as the <l_seq>S<span>N
+ * placeholder with a CG:B:I tag behind the line's own tags.  The stream is cut into BGZF blocks of 65280 bytes and the end-of-file
+ * block is appended: the file is a pure function of the text, not of window_bytes (text per window; 0: 64 MiB; a longer line makes its
+ * window grow) and not of the route.
+ * csv_sam_to_bam: the device route.  The text goes up window by window; k_sam_marks, k_sam_plan, one scan, k_sam_small and k_sam_bulk
+ * write the records into device memory, where the device compressor takes them; lines outside the device's strict grammar (every line
+ * that may be refused; B:f arrays) are computed on the host one by one, floats outside the fast path of sam_core.h come back as four
+ * bytes each.  flags: none is defined.  csv_sam_to_bam_host: the core's serial form over line ranges on `threads` host threads (0: 1)
+ * and csv_bgzf_deflate_host; the same file byte for byte.  Both create the file only after the first window's verdict and remove it
+ * when a later step fails.  CSV_E_INVALID with the text "line <1-based line of the file> <why>" (csv_last_error / err): the lowest
+ * refused line; also a header without @SQ before alignment lines, an @SQ line without SN or LN, a reference named twice.
+ * csv_sam_stats (ctx NULL: of this thread's last csv_sam_to_bam_host): counts[12] = lines, records, header bytes (the BAM header),
+ * text bytes, stream bytes, file bytes, BGZF blocks (the end-of-file block included), windows, floats outside the fast path, CG
+ * records, bytes up, bytes down; ms[4] = device time of the marks, the plan, the scan and write kernels, the compressor.
+ * csv_sam_records: the line rule over text[0, n) (whole lines; the last may lack its line break) without files, on the host: the
+ * records back to back in out[0, *need); the names are name_blob[name_off[i], name_off[i + 1]) in header order; first_line: the 1-based
+ * number the first line is reported as; counts (may be NULL): lines, floats outside the fast path, CG records.  CSV_E_CAPACITY: cap is
+ * below *need. */
+int csv_sam_to_bam(csv_ctx* ctx, const char* sam_path, const char* out_path, int64_t window_bytes, int32_t flags);
+int csv_sam_to_bam_host(const char* sam_path, const char* out_path, int64_t window_bytes, int32_t threads, char* err, int err_cap);
+int csv_sam_stats(const csv_ctx* ctx, int64_t* counts, double* ms);
+int csv_sam_records(const uint8_t* text, int64_t n, int32_t n_ref, const uint8_t* name_blob, const int32_t* name_off, int64_t first_line, uint8_t* out, int64_t cap,
+                    int64_t* need, int64_t* counts, char* err, int err_cap);
+
 /* BGZF inflate on the device: the raw-deflate payloads of n_blocks BGZF blocks -> their bytes, one wavefront
  * per block.  Block k's payload is comp[in_off[k] .. + in_len[k]), its out_len[k] (= ISIZE) bytes go to out[out_off[k] ..), crc[k]
  * is the CRC32 of its trailer; comp, out and status are host memory.
